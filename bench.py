@@ -11,17 +11,24 @@ Workload (BASELINE.json configs[1]): RealNVP, d = 64, 8 affine couplings (= real
 [64, 64], 4)), 2-hidden-layer conditioners of width 64, batch 65 536 PER GPU (weak scaling),
 fp32, diag-Gaussian target, synthetic Glorot weights.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (the coupling reverse
-pass, fp32 MFMA bound); `cpu_baseline` is the reference's step under torch-CPU autograd on all host
-cores at the SAME batch (oracle/nf_torch_cpu.py; the Julia reference cannot run on this box).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps, writes the last timed step's outputs
+when `--dump-outputs DIR` is given, and prints `value` / `ms_per_step` with the run's configuration.  `--full` adds what
+takes extra work or extra runs: HIP-event brackets of the dominant kernel inside the timed region and the `roofline` built
+on them (the coupling reverse pass, fp32 MFMA bound), per-step medians, the sustained-clock figures below, a per-kernel
+breakdown of extra untimed steps, and `cpu_baseline` -- the reference's step under torch-CPU autograd / a fused C++ step on
+all host cores at the SAME batch (oracle/nf_torch_cpu.py, oracle/nf_cpu_omp.py; the Julia reference cannot run there).
 
-Timing: W untimed warm-up steps, then EXACTLY K steps between barrier + synchronize: `value`, `ms_per_step` and
-`roofline.frac` are those K steps -- the driver's protocol, nothing inserted.  On an MI355X that has been idle (even for 50 ms)
+Timing: W untimed warm-up steps, then EXACTLY K steps between barrier + synchronize: `value` and `ms_per_step` (and, with
+`--full`, `roofline.frac`) are those K steps -- the driver's protocol, nothing inserted.  On an MI355X that has been idle (even for 50 ms)
 the shader clock DROPS from 2.4 GHz to 1.6-2.0 GHz when the load arrives and takes ~40 cfg-2 steps (25 ms) to come back
 (tools/bench_ramp.py reads the clock next to every step: profiles/r4a_step_ramp_clocks.txt; step time x clock is constant), so
 with `--steps 20 --warmup 5` the timed region rides that ramp.  What a training run of thousands of steps sees is reported
-NEXT to it, never as `value`: after the timed region `--prewarm` more untimed steps and K more timed ones ->
+NEXT to it under `--full`, never as `value`: after the timed region `--prewarm` more untimed steps and K more timed ones ->
 `value_sustained_clock`, `ms_per_step_sustained_clock`, `roofline.frac_sustained_clock` (`--prewarm 0` skips that).
+
+`--dump-outputs DIR`: what the timed path handed its caller after the LAST timed step -- theta after the Adam update, Adam's
+first and second moments, the step's loss and gradient norm (and, for `--split-calls`, the gradient) -- as DIR/<name>.npy,
+float32 / float64, written before anything else runs.  Inputs are seeded, so two builds can be compared output for output.
 
 Multi-GPU: one process per GPU.  Under `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N`
 the ranks come from the environment; a bare `python bench.py --gpus N` starts the N ranks itself (the parent
@@ -172,6 +179,22 @@ def cpu_baseline(seconds_budget: float = 24.0):
     return best
 
 
+DUMP_LIMIT_BYTES = 60 << 20  # array data; with the files' headers the dump stays under 64 MB
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: every array as out_dir/<name>.npy.  Should they exceed DUMP_LIMIT_BYTES in all (cfg 4 with
+    --split-calls), each array keeps its share of the limit as a fixed, seeded sample of its flattened elements in index
+    order, the same elements in every run."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES and a.size > 1:
+            keep = a.size * DUMP_LIMIT_BYTES // total
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def _free_port() -> int:
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -317,14 +340,15 @@ def run_once(args, world, world_observed, rank, dev, dist, damp, state):
             dist.barrier()
         torch.cuda.synchronize(dev)
 
-    if not args.no_kernel_events:
+    kernel_events = args.full and not args.no_kernel_events
+    if kernel_events:
         # create the library's event pool NOW: doing it between the pre-warm and the timed region leaves the GPU idle for
         # milliseconds, long enough for its clocks to fall back
         nf._lib.check(lib.nf_prof_enable(ctx.ptr, 1))
         nf._lib.check(lib.nf_prof_enable(ctx.ptr, 0))
     # (created BEFORE the warm-up: whatever the host does between the warm-up and the timed region is GPU idle time, and the
-    # shader clock falls back during idle time -- tools/bench_ramp.py)
-    marks = [torch.cuda.Event(enable_timing=True) for _ in range(2 * (args.steps + 1))]
+    # shader clock falls back during idle time -- tools/bench_ramp.py).  Per-step marks (the median) are a --full figure.
+    marks = [torch.cuda.Event(enable_timing=True) for _ in range(2 * (args.steps + 1))] if args.full else None
     graph = None
     if use_graph:
         # warm-up eagerly through the device-counter form (sizes the workspace, sets kernel attributes, packs the weights),
@@ -355,30 +379,50 @@ def run_once(args, world, world_observed, rank, dev, dist, damp, state):
     first = args.warmup  # index of the first timed step
 
     def timed_region(first_step: int, marks_off: int):
-        """EXACTLY K steps between barrier + synchronize (max over ranks), with the dominant kernel bracketed by HIP events on
-        the launch stream (every 4th launch: an event pair between two kernels of one stream drains the queue, ~30 us per
-        bracketed cfg-2 step, measured A/B with --no-kernel-events).  Returns (elapsed s, sorted per-step ms, kernel avg ms, n)."""
-        if not args.no_kernel_events and not use_graph:
+        """EXACTLY K steps between barrier + synchronize (max over ranks).  With --full the dominant kernel is bracketed by
+        HIP events on the launch stream (every 4th launch: an event pair between two kernels of one stream drains the queue,
+        ~30 us per bracketed cfg-2 step, measured A/B with --no-kernel-events) and every step is marked for the median.
+        Returns (elapsed s, sorted per-step ms or None, kernel avg ms, n)."""
+        if kernel_events and not use_graph:
             nf._lib.check(lib.nf_prof_enable(ctx.ptr, 1 if os.environ.get("NF_BENCH_EVENTS_EVERY_STEP") else 3))
         barrier()
         t0 = time.perf_counter()
-        marks[marks_off].record()
+        if marks is not None:
+            marks[marks_off].record()
         for k, i in enumerate(range(first_step, first_step + args.steps)):
             step(i, read_stats=(k == args.steps - 1))
-            marks[marks_off + k + 1].record()  # same stream as the library's launches: per-step device time for the median
+            if marks is not None:
+                marks[marks_off + k + 1].record()  # same stream as the library's launches: per-step device time for the median
         barrier()
         el = time.perf_counter() - t0
-        per_step = sorted(marks[marks_off + k].elapsed_time(marks[marks_off + k + 1]) for k in range(args.steps))
+        per_step = None
+        if marks is not None:
+            per_step = sorted(marks[marks_off + k].elapsed_time(marks[marks_off + k + 1]) for k in range(args.steps))
         if dist is not None:
             t = torch.tensor([el], dtype=torch.float64, device=dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el = float(t[0])
         a_ms, c_n = C.c_double(0.0), C.c_int64(0)
-        nf._lib.check(lib.nf_prof_read(ctx.ptr, DOMINANT[0], C.byref(a_ms), C.byref(c_n)))
+        if kernel_events:
+            nf._lib.check(lib.nf_prof_read(ctx.ptr, DOMINANT[0], C.byref(a_ms), C.byref(c_n)))
         return el, per_step, a_ms.value, c_n.value
 
     elapsed, step_ms, dom_ms, dom_cnt = timed_region(first, 0)
     first += args.steps
+    if args.dump_outputs and rank == 0:
+        # the last timed step's results, before the pre-warm or the breakdown below moves theta on
+        outs = {"theta": theta, "adam_m": m, "adam_v": v}
+        if use_graph:
+            stats = (float(stat_dev[0]), float(stat_dev[1]))
+        elif fused_step:
+            stats = (stat_host[0].value, stat_host[1].value)
+        else:
+            stats = (float(out[P]), float(gnorm))
+            outs["grad"] = out[:P]
+        arrays = {k: t.detach().cpu().numpy().astype(np.float32) for k, t in outs.items()}
+        arrays["loss"] = np.array([stats[0]], dtype=np.float64)
+        arrays["grad_norm"] = np.array([stats[1]], dtype=np.float64)
+        dump_outputs(args.dump_outputs, arrays)
     sustained = None
     if args.prewarm > 0:
         for i in range(args.prewarm):
@@ -397,19 +441,20 @@ def run_once(args, world, world_observed, rank, dev, dist, damp, state):
         loss, gnorm_v = float(out[P]), float(gnorm)
     assert np.isfinite(loss) and np.isfinite(gnorm_v), "non-finite loss / gradient norm"
 
-    # per-kernel breakdown: a few extra, UNTIMED steps with every kernel bracketed
+    # per-kernel breakdown (--full): a few extra, UNTIMED steps with every kernel bracketed
     kernel_ms = {}
     nbreak = 5
-    nf._lib.check(lib.nf_prof_enable(ctx.ptr, 2))
-    for i in range(nbreak):
-        step(first + i)
-    torch.cuda.synchronize(dev)
-    for name in KERNEL_NAMES:
-        a, c = C.c_double(0.0), C.c_int64(0)
-        lib.nf_prof_read(ctx.ptr, name, C.byref(a), C.byref(c))
-        if c.value:  # kernels fused away in this configuration are not listed
-            kernel_ms[name.decode()] = {"avg_ms": round(a.value, 5), "launches_per_step": c.value / nbreak}
-    nf._lib.check(lib.nf_prof_enable(ctx.ptr, 0))
+    if args.full:
+        nf._lib.check(lib.nf_prof_enable(ctx.ptr, 2))
+        for i in range(nbreak):
+            step(first + i)
+        torch.cuda.synchronize(dev)
+        for name in KERNEL_NAMES:
+            a, c = C.c_double(0.0), C.c_int64(0)
+            lib.nf_prof_read(ctx.ptr, name, C.byref(a), C.byref(c))
+            if c.value:  # kernels fused away in this configuration are not listed
+                kernel_ms[name.decode()] = {"avg_ms": round(a.value, 5), "launches_per_step": c.value / nbreak}
+        nf._lib.check(lib.nf_prof_enable(ctx.ptr, 0))
     events_in_timed_region = cnt.value > 0
     if not events_in_timed_region and DOMINANT[0].decode() in kernel_ms:
         # graph replay (no event brackets inside a captured graph) or --no-kernel-events: the dominant kernel's duration
@@ -427,7 +472,7 @@ def run_once(args, world, world_observed, rank, dev, dist, damp, state):
         flop_per_launch = FLOPS_BWD_PER_SAMPLE_PER_COUPLING * couplings_per_launch * n_local
         achieved = flop_per_launch / (avg_ms.value * 1e-3) / 1e12 if avg_ms.value > 0 else 0.0
         traffic, traffic_src = (None, None)
-        if n_local == BATCH and args.workload in ("cfg2", "cfg3"):
+        if args.full and n_local == BATCH and args.workload in ("cfg2", "cfg3"):
             traffic, traffic_src = pmc_traffic(("k_affine_bwd_pair" if PAIR else "k_affine_bwd_stashed" if STASHED else "k_affine_bwd_all") if args.workload == "cfg2" else "k_rqs_bwd")
         rec = {
             "metric": "elbo_samples_per_sec",
@@ -437,7 +482,7 @@ def run_once(args, world, world_observed, rank, dev, dist, damp, state):
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": ms_per_step,
-            "ms_per_step_median": step_ms[len(step_ms) // 2],
+            "ms_per_step_median": None if step_ms is None else step_ms[len(step_ms) // 2],
             "value_sustained_clock": None if sustained is None else n_global * args.steps / sustained[0],
             "ms_per_step_sustained_clock": None if sustained is None else 1e3 * sustained[0] / args.steps,
             "higher_is_better": True,
@@ -464,7 +509,7 @@ def run_once(args, world, world_observed, rank, dev, dist, damp, state):
                 "init": "Glorot-uniform weights, zero biases (Flux default)" + (f", theta scaled by {damp}" if damp is not None else ""),
                 "final_loss": loss,
                 "final_gradient_norm": gnorm_v,
-                "timing": (f"value / ms_per_step / roofline.frac: the {args.steps} steps straight after the {args.warmup} warm-ups "
+                "timing": (f"value / ms_per_step{' / roofline.frac' if args.full else ''}: the {args.steps} steps straight after the {args.warmup} warm-ups "
                            "(the command's protocol; after any idle an MI355X drops its shader clock to 1.6-2.0 GHz when load arrives "
                            "and needs ~40 cfg-2 steps to return to 2.4 GHz: profiles/r4a_step_ramp_clocks.txt).  "
                            + ("" if sustained is None else
@@ -474,7 +519,9 @@ def run_once(args, world, world_observed, rank, dev, dist, damp, state):
                 "untimed_steps_before_value_sustained_clock": None if sustained is None else args.warmup + args.steps + args.prewarm,
                 "weight_cache": "nf_ctx_set_weight_cache(ctx, 1), as train_flow's loop sets it" if fused_step else "not used",
             },
-            "roofline": {
+        }
+        if args.full:
+            rec["roofline"] = {
                 "kernel": DOMINANT[1],
                 "bound": "mfma",
                 "achieved": achieved,
@@ -509,11 +556,10 @@ def run_once(args, world, world_observed, rank, dev, dist, damp, state):
                 "frac_sustained_clock": None if sustained is None or sustained[2] <= 0 else
                                         flop_per_launch / (sustained[2] * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS,
                 "avg_launch_ms_sustained_clock": None if sustained is None else sustained[2],
-            },
-            "kernels": kernel_ms,
-            "kernels_note": "per-kernel HIP-event averages of 5 extra steps AFTER the timed region and the sustained-clock measurement (post-run, sustained clock) -- compare with roofline.avg_launch_ms_sustained_clock, not with roofline.avg_launch_ms",
-        }
-        if world == 1 and not args.no_cpu_baseline and args.workload == "cfg2":
+            }
+            rec["kernels"] = kernel_ms
+            rec["kernels_note"] = "per-kernel HIP-event averages of 5 extra steps AFTER the timed region and the sustained-clock measurement (post-run, sustained clock) -- compare with roofline.avg_launch_ms_sustained_clock, not with roofline.avg_launch_ms"
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload == "cfg2":
             rec["cpu_baseline"] = cpu_baseline()
             rec["gpu_over_cpu"] = value / rec["cpu_baseline"]["value"]
         print(json.dumps(rec))
@@ -527,7 +573,8 @@ def main():
     ap.add_argument("--prewarm", type=int, default=None,
                     help="untimed steps AFTER the timed K, followed by K more timed steps reported as *_sustained_clock (the GPU's "
                          "shader clock needs ~40 cfg-2 steps under load to return to 2.4 GHz, profiles/r4a_step_ramp_clocks.txt); "
-                         "default per workload (cfg2 120, cfg3 60, cfg4 4), 0 = no sustained-clock figure.  Never affects `value`")
+                         "default with --full per workload (cfg2 120, cfg3 60, cfg4 4), otherwise 0 = no sustained-clock figure.  "
+                         "Never affects `value`")
     ap.add_argument("--batch", type=int, default=None, help="samples per GPU per step")
     ap.add_argument("--workload", choices=("cfg2", "cfg3", "cfg4"), default="cfg2",
                     help="cfg2 = the headline line (default); cfg3 = NSF d=32 K=8, 131072 per GPU; "
@@ -543,12 +590,20 @@ def main():
     ap.add_argument("--damp", type=float, default=None,
                     help="scale the Glorot-initialised theta (cfg4: --damp 0.5 is the contraction the parity tests judge; the "
                          "default is the Flux initialisation)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: event brackets of the dominant kernel in the timed "
+                         "region and the roofline, per-step median, sustained-clock figures, per-kernel breakdown, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (theta, Adam moments, loss, gradient norm) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-kernel-events", action="store_true",
-                    help="do not bracket kernels with HIP events in the timed region (roofline object is then empty)")
+                    help="with --full: do not bracket kernels with HIP events in the timed region (the roofline then comes from "
+                         "the bracketed steps after it)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.prewarm is None:
-        args.prewarm = {"cfg2": 120, "cfg3": 60, "cfg4": 4}[args.workload]
+        args.prewarm = {"cfg2": 120, "cfg3": 60, "cfg4": 4}[args.workload] if args.full else 0
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus))  # the parent only supervises; ranks are fresh processes

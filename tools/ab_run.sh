@@ -10,7 +10,7 @@ cp normalizingflows.jl_amd/libnfhip.so /tmp/libnfhip_shipped.so
 for i in $(seq 1 "$rep"); do
   for v in "$@"; do
     cp "normalizingflows.jl_amd/ab/$v.so" normalizingflows.jl_amd/libnfhip.so
-    python3 bench.py $bargs > "${out}_${v}_$i.json" 2> "${out}_${v}_$i.err"
+    python3 bench.py --full $bargs > "${out}_${v}_$i.json" 2> "${out}_${v}_$i.err"
   done
 done
 cp /tmp/libnfhip_shipped.so normalizingflows.jl_amd/libnfhip.so

@@ -7,6 +7,7 @@ import os
 import re
 import subprocess
 import sys
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = "/opt/rocm/lib/llvm/bin/"
@@ -48,20 +49,20 @@ def scan(disasm):
 
 
 def main():
-    tmp = "/tmp/nfhip_co"
-    os.makedirs(tmp, exist_ok=True)
     bdir = os.path.join(ROOT, "normalizingflows.jl_amd", "build")
     bad = []
     nstores = 0
-    for obj in sorted(f for f in os.listdir(bdir) if f.endswith(".o")):
-        fb, co = os.path.join(tmp, obj + ".fatbin"), os.path.join(tmp, obj + ".co")
-        if subprocess.run([LLVM + "llvm-objcopy", "--dump-section", f".hip_fatbin={fb}", os.path.join(bdir, obj)], capture_output=True).returncode:
-            continue
-        subprocess.run([LLVM + "clang-offload-bundler", "--unbundle", "--type=o", f"--input={fb}",
-                        "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"], check=True)
-        dis = subprocess.run([LLVM + "llvm-objdump", "-d", co], capture_output=True, text=True).stdout
-        nstores += len(re.findall(r"_store_dwordx[34]", dis))
-        bad += scan(dis)
+    # a private directory per call: a fixed path under /tmp may belong to another user, and then every object is skipped
+    with tempfile.TemporaryDirectory(prefix="nfhip_co_") as tmp:
+        for obj in sorted(f for f in os.listdir(bdir) if f.endswith(".o")):
+            fb, co = os.path.join(tmp, obj + ".fatbin"), os.path.join(tmp, obj + ".co")
+            if subprocess.run([LLVM + "llvm-objcopy", "--dump-section", f".hip_fatbin={fb}", os.path.join(bdir, obj)], capture_output=True).returncode:
+                continue
+            subprocess.run([LLVM + "clang-offload-bundler", "--unbundle", "--type=o", f"--input={fb}",
+                            "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"], check=True)
+            dis = subprocess.run([LLVM + "llvm-objdump", "-d", co], capture_output=True, text=True).stdout
+            nstores += len(re.findall(r"_store_dwordx[34]", dis))
+            bad += scan(dis)
     names = subprocess.run(["c++filt"], input="\n".join(b[0] for b in bad), capture_output=True, text=True).stdout.split("\n")
     for n, b in zip(names, bad):
         print(f"{n[:110]}\n    {b[1]}\n    {b[2]}")

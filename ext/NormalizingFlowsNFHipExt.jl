@@ -525,4 +525,53 @@ function train_flow_fused(rng::NFHipRNG, flow::Bijectors.TransformedDistribution
     return Bijectors.transformed(dflow.dist, NFHipTransform(θ, t.desc, t.re, false, t.keep)), stats, (m=m, v=v, t=steps)
 end
 
+# train_flow_fused(flow, loglikelihood, xs; max_iters, optimiser::Adam, state): the forward-KL loop, train_flow(loglikelihood,
+# flow, xs) with each iteration ONE nf_loglikelihood_step (value and gradient of -loglikelihood, Adam, norm(g)); same numbers
+# as train_flow over AutoNFHip (tests/test_gpu_fkl_step.py checks that through the Python mirror, objectives._optimize_fused_fkl).
+# Adam's t - 1 is the step index; there are no draws, so any `state` continues.  Single-rank contexts only: under a
+# communicator nf_loglikelihood_step all-reduces inside the library, a data-parallel run of its own.
+function train_flow_fused(flow::Bijectors.TransformedDistribution, ::typeof(NormalizingFlows.loglikelihood), xs::ROCMatrix;
+                          max_iters::Int=1000, optimiser::Optimisers.Adam=Optimisers.Adam(), state=nothing)
+    comm_size() <= 1 || error("nfhip: train_flow_fused needs a single-rank context")
+    dflow = flow isa DeviceFlow ? flow : nfhip(flow)
+    t = dflow.transform
+    θ = copy(t.θ)
+    ys = convert(ROCMatrix{eltype(θ)}, xs)
+    N = Int64(size(ys, 2))
+    m = state === nothing ? zero(θ) : copy(state.m)
+    v = state === nothing ? zero(θ) : copy(state.v)
+    steps = state === nothing ? 0 : Int(state.t)
+    stats = NamedTuple[]
+    weight_cache!(true)
+    try
+        for i in 1:max_iters
+            loss, gnorm = Ref{Cdouble}(0), Ref{Cdouble}(0)
+            code = ccall((:nf_loglikelihood_step, libnfhip), Cint,
+                         (Ptr{Cvoid}, Ref{NFDesc}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, UInt32,
+                          Cdouble, Cdouble, Cdouble, Cdouble, Ref{Cdouble}, Ref{Cdouble}),
+                         context(), t.desc, devptr(θ), devptr(m), devptr(v), devptr(ys), N, N, UInt32(steps),
+                         optimiser.eta, optimiser.beta[1], optimiser.beta[2], optimiser.epsilon, loss, gnorm)
+            code == NF_ERR_NONFINITE || check(code)   # a non-finite loss is recorded
+            steps += 1
+            push!(stats, (iteration=i, loss=loss[], gradient_norm=gnorm[]))
+        end
+    finally
+        weight_cache!(false)
+    end
+    return Bijectors.transformed(dflow.dist, NFHipTransform(θ, t.desc, t.re, false, t.keep)), stats, (m=m, v=v, t=steps)
+end
+
+# The capturable form (hipGraph): Adam's t - 1 lives in `counter` (device UInt32), which the step increments; `out` (2 elements,
+# optional) receives [loss ; norm(g)].  NF_ERR_UNSUPPORTED (an error here) for flows without the fused form.
+function loglikelihood_step_enqueue!(θ::ROCVector{T}, m::ROCVector{T}, v::ROCVector{T}, desc::NFDesc, ys::ROCMatrix{T},
+                                     counter::ROCVector{UInt32}, rule::Optimisers.Adam, out=nothing) where {T}
+    N = Int64(size(ys, 2))
+    check(ccall((:nf_loglikelihood_step_enqueue, libnfhip), Cint,
+                (Ptr{Cvoid}, Ref{NFDesc}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid},
+                 Cdouble, Cdouble, Cdouble, Cdouble, Ptr{Cvoid}),
+                context(), desc, devptr(θ), devptr(m), devptr(v), devptr(ys), N, N, devptr(counter),
+                rule.eta, rule.beta[1], rule.beta[2], rule.epsilon, devptr(out)))
+    return nothing
+end
+
 end # module

@@ -339,6 +339,26 @@ int nf_ctx_set_weight_cache(nf_ctx *ctx, int32_t enable);
 int nf_elbo_step_enqueue(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, void *theta, void *m, void *v,
                          int64_t N, uint64_t seed, uint32_t *step_device, double lr, double beta1, double beta2,
                          double eps, void *out_loss_gnorm_device);
+/* One iteration of train_flow(loglikelihood, flow, ys): value and gradient of -loglikelihood(rng, re(theta), ys)
+ * over THIS rank's N_local columns of an N_global-column data set (N_global <= 0: N_local * comm size), the
+ * all-reduce of [grad ; loss] when the context holds a communicator, Optimisers.update! with Adam (t = step + 1),
+ * norm(g).  loss_host / gnorm_host as nf_elbo_step (NULL for both = asynchronous).
+ * Every flow nf_loglikelihood_value_and_grad accepts works; the weight-image cache (nf_ctx_set_weight_cache) and the stash
+ * budget behave as in nf_elbo_step.  LDS-resident RealNVP flows whose inverse chain keeps a stash (the flows nf_elbo_step runs
+ * in three launches) run as one launch per stash chunk that reads ys in place (inverse chain, stash, loss partials, the
+ * reverse pass's seed), the reverse pass, the fused epilogue and a one-block finish; LDS-resident spline couplings on a
+ * context without a communicator run the same fused inverse chain (leaving z and the spline tape), one reverse launch per
+ * coupling, the fused epilogue and the finish.  Every other flow runs nf_loglikelihood_value_and_grad, the all-reduce and
+ * nf_adam_update inside the call.  All give theta, m and v bit for bit equal to those calls made one by one. */
+int nf_loglikelihood_step(nf_ctx *ctx, const nf_flow_desc *desc, void *theta, void *m, void *v, const void *ys,
+                          int64_t N_local, int64_t N_global, uint32_t step, double lr, double beta1, double beta2,
+                          double eps, double *loss_host, double *gnorm_host);
+/* The same with Adam's t - 1 read from and incremented in *step_device; capturable after one warm-up call (as
+ * nf_elbo_step_enqueue); out_loss_gnorm_device (optional, 2 floats) receives [loss ; norm(g)].
+ * NF_ERR_UNSUPPORTED for flows without the fused form. */
+int nf_loglikelihood_step_enqueue(nf_ctx *ctx, const nf_flow_desc *desc, void *theta, void *m, void *v, const void *ys,
+                                  int64_t N_local, int64_t N_global, uint32_t *step_device, double lr, double beta1,
+                                  double beta2, double eps, void *out_loss_gnorm_device);
 
 /* ---- (e) multi-GPU: the path's one collective ----------------------------------- */
 /* The ELBO is a mean over independent draws (src/objectives/elbo.jl:68,91,96), so ranks take sample shards

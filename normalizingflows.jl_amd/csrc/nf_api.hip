@@ -44,6 +44,9 @@ int nf_affine_chain_elbo(nf_ctx *, const nf_flow_desc *, long N, uint64_t seed, 
                          const float *mu, const float *var, float *yt, float *gt, double gscale, double *partial,
                          double pscale, float *stash = nullptr, const uint32_t *stream_ptr = nullptr);
 long nf_affine_epilogue_blocks(const nf_flow_desc *desc);
+bool nf_affine_chain_fkl_ok(const nf_flow_desc *desc);
+int nf_affine_chain_fkl(nf_ctx *, const nf_flow_desc *, const float *ys, long N, float *gt, double gscale, double *partial,
+                        double pscale, float *stash);
 int nf_affine_epilogue(nf_ctx *, const nf_flow_desc *, int mode, const float *slab, int nslab, float *g, const double *lpart,
                        int nlpart, float *theta, float *m, float *v, double lr, double b1, double b2, double eps, unsigned t_val,
                        unsigned *t_ptr, double *gpart);
@@ -90,7 +93,11 @@ int nf_rqs_chain_elbo(nf_ctx *, const nf_flow_desc *, long N, uint64_t seed, uin
 int nf_rqs_reduce_slabs(nf_ctx *, const nf_flow_desc *, const float *slab, int nslab, float *g);
 long nf_rqs_epilogue_blocks(const nf_flow_desc *desc);
 int nf_rqs_epilogue(nf_ctx *, const nf_flow_desc *, const float *slab, int nslab, float *g, const double *lpart, int nlpart, float *theta,
-                    float *m, float *v, double lr, double b1, double b2, double eps, unsigned t_val, double *gpart);
+                    float *m, float *v, double lr, double b1, double b2, double eps, unsigned t_val, double *gpart,
+                    const unsigned *t_ptr = nullptr);
+bool nf_rqs_chain_fkl_ok(const nf_flow_desc *desc);
+int nf_rqs_chain_fkl(nf_ctx *, const nf_flow_desc *, const float *ys, long N, float *zt, float *gt, double gscale, double *partial,
+                     double pscale, void *tape);
 
 // planar / radial / mean-field flows (nf_simple.hip)
 bool nf_simple_supported(const nf_flow_desc *desc);
@@ -2216,6 +2223,174 @@ extern "C" int nf_elbo_step_enqueue(nf_ctx *ctx, const nf_flow_desc *desc, const
   return NF_OK;
 }
 
+// ---- the forward-KL training step -----------------------------------------------------------------------------------
+// nf_loglikelihood_step for LDS-resident RealNVP flows whose inverse chain leaves a stash (the family nf_elbo_step fuses) is
+// one launch per stash chunk of k_affine_chain<FUSED, INVERSE, STASH> (ys read in place, inverse chain + stash, the seed
+// z / N_global and the loss partials), the inverse-direction k_affine_bwd_stashed, k_affine_epilogue and k_finish_sum -- the
+// layout conversion, the separate base-density launch, the slab reduction and Adam of the split calls are folded away, and
+// so is the next step's pack under the weight cache.  LDS-resident spline couplings on one rank: k_rqs_chain<INVERSE, FUSED>
+// (the same tail, leaving z and the spline tape), the inverse-direction reverse launch per coupling, k_rqs_epilogue and
+// k_finish_sum.  Every element of z, ladj and the seed is computed as nf_loglikelihood_value_and_grad computes it, so theta, m
+// and v equal the split calls' bits.  The loss is not bit-equal: the per-sample log q0(z) is evaluated as the fused ELBO
+// forward does (-d log(2 pi) / 2 - ||z||^2 / 2, not the target kernel's per-feature sum) and the double partials are grouped
+// by workgroup; it agrees to float rounding.  Every other flow runs the split sequence inside the call.
+static bool fkl_step_fusable(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
+  if (N < 1 || flow_base(desc) || is_composite(desc) || desc->dtype != NF_DTYPE_F32) return false;
+  if (!(desc->kind == NF_KIND_REALNVP && nf_affine_supported(desc) && nf_affine_chain_fkl_ok(desc))) return false;
+  return affine_stash_chunk(ctx, desc, N) > 0;
+}
+// loss partials of a chunked step: one per workgroup of every chunk's chain launch
+static long fkl_step_npart(nf_ctx *ctx, long N, long chunk) {
+  long n = 0;
+  for (long o = 0; o < N; o += chunk) n += nf_affine_chain_grid(ctx, N - o < chunk ? N - o : chunk);
+  return n;
+}
+static size_t fkl_step_need(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
+  const long snc = affine_stash_chunk(ctx, desc, N);
+  if (!snc) return 0;
+  return carve_bytes(tiled_elems(desc, N) * 4) + carve_bytes((size_t)fkl_step_npart(ctx, N, snc) * 8) +
+         carve_bytes(chunked_slab_floats(ctx, desc, N, snc, coupling_slab_floats(ctx, desc, N)) * 4) +
+         carve_bytes(affine_stash_bytes(ctx, desc, snc)) + carve_bytes((size_t)nf_affine_epilogue_blocks(desc) * 8);
+}
+// spline couplings: one rank (as step_fusable_rqs), the LDS-resident geometries with a forward-KL chain kernel
+static bool fkl_step_fusable_rqs(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
+  if (N < 1 || ctx->comm || flow_base(desc) || is_composite(desc) || desc->dtype != NF_DTYPE_F32) return false;
+  return desc->kind == NF_KIND_NSF && nf_rqs_supported(desc) && nf_rqs_chain_fkl_ok(desc);
+}
+static size_t fkl_step_need_rqs(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
+  const size_t te = tiled_elems(desc, N);
+  return 2 * carve_bytes(te * 4) + carve_bytes((size_t)nf_rqs_chain_grid(ctx, N) * 8) +
+         carve_bytes((size_t)coupling_bwd_grid(ctx, desc, N) * coupling_slab_floats(ctx, desc, N) * 4) + rqs_tape_b(desc, N) +
+         carve_bytes((size_t)nf_rqs_epilogue_blocks(desc) * 8);
+}
+static int fkl_step_fused_rqs(nf_ctx *ctx, const nf_flow_desc *desc, float *theta, float *m, float *v, const float *ys, long N,
+                              long Ng, uint32_t step_val, uint32_t *step_ptr, double lr, double beta1, double beta2, double eps) {
+  const long P = nf_param_count(desc);
+  const double inv = 1.0 / (double)Ng;
+  const size_t te = tiled_elems(desc, N);
+  const int grid = coupling_bwd_grid(ctx, desc, N);
+  const long stride = coupling_slab_floats(ctx, desc, N);
+  const long npart = nf_rqs_chain_grid(ctx, N);
+  const long eblocks = nf_rqs_epilogue_blocks(desc);
+  NF_TRY(nf_ws_reserve(ctx, fkl_step_need_rqs(ctx, desc, N)));
+  Carver cv(ctx->ws);
+  float *zt = cv.take<float>(te);
+  float *gt = cv.take<float>(te);
+  double *partial = cv.take<double>(npart);
+  float *slab = cv.take<float>((size_t)grid * stride);
+  void *tape = (void *)cv.take<char>(rqs_tape_b(desc, N));
+  double *gpart = cv.take<double>(eblocks);
+  float *gbuf = (float *)ctx->gbuf;
+  if (!ctx->wimg_cache || !(ctx->wimg && ctx->wimg_owner == (const void *)theta && ctx->wimg_sig == flow_sig(desc)))
+    NF_TRY(coupling_pack(ctx, desc, theta));
+  NF_TRY(nf_rqs_chain_fkl(ctx, desc, ys, N, zt, gt, -inv, partial, -inv, tape));
+  for (int k = 2 * desc->nlayers - 1; k >= 0; --k)  // forward execution order, as coupling_inv_bwd
+    NF_TRY(nf_rqs_bwd(ctx, desc, k, zt, gt, nullptr, (float)(-inv), N, slab, stride, grid, true, tape));
+  NF_TRY(nf_rqs_epilogue(ctx, desc, slab, grid, gbuf, partial, (int)npart, theta, m, v, lr, beta1, beta2, eps, step_val, gpart,
+                         step_ptr));
+  NF_TRY(nf_launch_finish_sum(ctx, gpart, eblocks, 1, nullptr, gbuf + P + 1, nullptr, step_ptr));
+  ctx->wimg_owner = theta;
+  ctx->wimg_sig = flow_sig(desc);
+  return NF_OK;
+}
+static int fkl_step_fused(nf_ctx *ctx, const nf_flow_desc *desc, float *theta, float *m, float *v, const float *ys, long N, long Ng,
+                          uint32_t step_val, uint32_t *step_ptr, double lr, double beta1, double beta2, double eps) {
+  const long P = nf_param_count(desc);
+  const int world = ctx->comm ? ctx->comm_size : 1;
+  const double inv = 1.0 / (double)Ng;
+  const long stash_nc = affine_stash_chunk(ctx, desc, N);
+  const long stride = coupling_slab_floats(ctx, desc, N);
+  const long eblocks = nf_affine_epilogue_blocks(desc);
+  NF_TRY(nf_ws_reserve(ctx, fkl_step_need(ctx, desc, N)));
+  Carver cv(ctx->ws);
+  float *gt = cv.take<float>(tiled_elems(desc, N));
+  double *partial = cv.take<double>(fkl_step_npart(ctx, N, stash_nc));
+  float *slab = cv.take<float>(chunked_slab_floats(ctx, desc, N, stash_nc, stride));
+  float *stash = cv.take<float>(affine_stash_bytes(ctx, desc, stash_nc) / 4);
+  double *gpart = cv.take<double>(eblocks);
+  float *gbuf = (float *)ctx->gbuf;
+  // packed images: those the previous step's epilogue left (only under nf_ctx_set_weight_cache(ctx, 1)), or a fresh pack
+  if (!ctx->wimg_cache || !(ctx->wimg && ctx->wimg_owner == (const void *)theta && ctx->wimg_sig == flow_sig(desc)))
+    NF_TRY(coupling_pack(ctx, desc, theta));
+  long nslab = 0, npart = 0;
+  for (long o = 0; o < N; o += stash_nc) {
+    const long nc = N - o < stash_nc ? N - o : stash_nc;
+    const int gc = coupling_bwd_grid(ctx, desc, nc);
+    NF_TRY(nf_affine_chain_fkl(ctx, desc, ys + o * desc->d, nc, gt + o * desc->d, -inv, partial + npart, -inv, stash));
+    NF_TRY(nf_affine_bwd_stashed(ctx, desc, stash, gt + o * desc->d, nullptr, (float)(-inv), nc, slab + nslab * stride, stride, gc, true));
+    nslab += gc;
+    npart += nf_affine_chain_grid(ctx, nc);
+  }
+  if (world == 1) {
+    NF_TRY(nf_affine_epilogue(ctx, desc, 3, slab, (int)nslab, gbuf, partial, (int)npart, theta, m, v, lr, beta1, beta2, eps, step_val,
+                              step_ptr, gpart));
+  } else {
+    NF_TRY(nf_affine_epilogue(ctx, desc, 1, slab, (int)nslab, gbuf, partial, (int)npart, nullptr, nullptr, nullptr, lr, beta1, beta2,
+                              eps, step_val, nullptr, gpart));
+    NF_TRY(nf_allreduce_grad_loss(ctx, NF_DTYPE_F32, gbuf, P + 1));
+    NF_TRY(nf_affine_epilogue(ctx, desc, 2, nullptr, 0, gbuf, nullptr, 0, theta, m, v, lr, beta1, beta2, eps, step_val, step_ptr,
+                              gpart));
+  }
+  NF_TRY(nf_launch_finish_sum(ctx, gpart, eblocks, 1, nullptr, gbuf + P + 1, nullptr, step_ptr));
+  ctx->wimg_owner = theta;
+  ctx->wimg_sig = flow_sig(desc);
+  return NF_OK;
+}
+
+extern "C" int nf_loglikelihood_step(nf_ctx *ctx, const nf_flow_desc *desc, void *theta, void *m, void *v, const void *ys,
+                                     int64_t N_local, int64_t N_global, uint32_t step, double lr, double beta1, double beta2,
+                                     double eps, double *loss_host, double *gnorm_host) {
+  if (!ctx || !theta || !m || !v || !ys || N_local < 0) return NF_ERR_ARG;
+  NF_TRY(check_desc(desc));
+  NF_HIP(hipSetDevice(ctx->device));
+  const long P = nf_param_count(desc);
+  const size_t es = esize(desc->dtype);
+  const int world = ctx->comm ? ctx->comm_size : 1;
+  const long Ng = N_global > 0 ? (long)N_global : (long)N_local * world;
+  if (Ng < 1) return NF_ERR_ARG;
+  NF_TRY(gbuf_reserve(ctx, gbuf_need(P, es)));
+  if (fkl_step_fusable(ctx, desc, N_local)) {
+    NF_TRY(fkl_step_fused(ctx, desc, (float *)theta, (float *)m, (float *)v, (const float *)ys, N_local, Ng, step, nullptr, lr, beta1,
+                          beta2, eps));
+  } else if (fkl_step_fusable_rqs(ctx, desc, N_local)) {
+    NF_TRY(fkl_step_fused_rqs(ctx, desc, (float *)theta, (float *)m, (float *)v, (const float *)ys, N_local, Ng, step, nullptr, lr,
+                              beta1, beta2, eps));
+  } else {  // the split sequence: value and gradient, the all-reduce under a communicator, Adam
+    void *gbuf = ctx->gbuf;
+    NF_TRY(nf_loglikelihood_value_and_grad(ctx, desc, theta, ys, N_local, Ng, gbuf));
+    if (world > 1) NF_TRY(nf_allreduce_grad_loss(ctx, desc->dtype, gbuf, P + 1));
+    NF_TRY(nf_adam_update(ctx, desc->dtype, theta, gbuf, m, v, P, lr, beta1, beta2, eps, (int64_t)step + 1,
+                          (char *)gbuf + (size_t)(P + 1) * es));
+  }
+  if (loss_host || gnorm_host) return step_readback(ctx, desc, P, loss_host, gnorm_host);
+  return NF_OK;
+}
+
+// The graph-capturable form, as nf_elbo_step_enqueue: Adam's t - 1 comes from *step_device, which the step increments.
+extern "C" int nf_loglikelihood_step_enqueue(nf_ctx *ctx, const nf_flow_desc *desc, void *theta, void *m, void *v, const void *ys,
+                                             int64_t N_local, int64_t N_global, uint32_t *step_device, double lr, double beta1,
+                                             double beta2, double eps, void *out_loss_gnorm_device) {
+  if (!ctx || !theta || !m || !v || !ys || !step_device || N_local < 0) return NF_ERR_ARG;
+  NF_TRY(check_desc(desc));
+  NF_HIP(hipSetDevice(ctx->device));
+  const long P = nf_param_count(desc);
+  const int world = ctx->comm ? ctx->comm_size : 1;
+  const long Ng = N_global > 0 ? (long)N_global : (long)N_local * world;
+  if (Ng < 1) return NF_ERR_ARG;
+  const bool affine = fkl_step_fusable(ctx, desc, N_local);
+  if (!affine && !fkl_step_fusable_rqs(ctx, desc, N_local)) return NF_ERR_UNSUPPORTED;
+  NF_TRY(gbuf_reserve(ctx, gbuf_need(P, 4)));
+  if (affine)
+    NF_TRY(fkl_step_fused(ctx, desc, (float *)theta, (float *)m, (float *)v, (const float *)ys, N_local, Ng, 0, step_device, lr, beta1,
+                          beta2, eps));
+  else
+    NF_TRY(fkl_step_fused_rqs(ctx, desc, (float *)theta, (float *)m, (float *)v, (const float *)ys, N_local, Ng, 0, step_device, lr,
+                              beta1, beta2, eps));
+  if (out_loss_gnorm_device)
+    NF_HIP(hipMemcpyAsync(out_loss_gnorm_device, (char *)ctx->gbuf + (size_t)P * 4, 8, hipMemcpyDeviceToDevice, ctx->stream));
+  return NF_OK;
+}
+
 // ---- arena sizing ------------------------------------------------------------------------------
 // Upper bound, over EVERY compute entry point called with this flow and up to N samples, of the device memory the
 // context needs: the intermediates arena (the per-entry-point `need` formulas above, restated here -- the arena-mode
@@ -2323,6 +2498,16 @@ extern "C" int64_t nf_workspace_bytes(nf_ctx *ctx, const nf_flow_desc *desc, int
   }
   if (desc->kind == NF_KIND_NSF && desc->dtype == NF_DTYPE_F32 && !is_composite(desc) && !flow_base(desc) && nf_rqs_supported(desc)) {
     const size_t f = step_fused_need_rqs(ctx, desc, N);
+    if (f > need) need = f;
+  }
+  // nf_loglikelihood_step's fused forms (its split form is covered above; the spline form is sized whatever the communicator)
+  if (fkl_step_fusable(ctx, desc, N)) {
+    const size_t f = fkl_step_need(ctx, desc, N);
+    if (f > need) need = f;
+  }
+  if (desc->kind == NF_KIND_NSF && desc->dtype == NF_DTYPE_F32 && !is_composite(desc) && !flow_base(desc) && nf_rqs_supported(desc) &&
+      nf_rqs_chain_fkl_ok(desc)) {
+    const size_t f = fkl_step_need_rqs(ctx, desc, N);
     if (f > need) need = f;
   }
   // nf_adam_update / nf_sgd_update: gradient-norm partials at the tail of the intermediates arena

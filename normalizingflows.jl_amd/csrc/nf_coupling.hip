@@ -394,6 +394,11 @@ __device__ __forceinline__ float coupling_step_stash(const float *__restrict__ i
 // (sample lo, sample hi, feature group, stream)), log q0 and log|det J| never touch memory, and after
 // the last coupling the diagonal-Gaussian target, ybar = gscale * grad log p(y) and the workgroup's
 // partial sum of pscale * elbo_j are computed from the registers (src/objectives/elbo.jl:65-70,93-97).
+// FUSED with INVERSE (and STASH): the forward-KL step's inverse chain in the same way (src/objectives/loglikelihood.jl:26-33):
+// the tile is read from the caller's ys in the standard d x N layout (xt, read only), every coupling inverse leaves its stash,
+// and after the last one the seed gt = gscale * grad log q0(z) (k_target_tiled's arithmetic with mu = 0, var = 1) and the
+// workgroup's partial sum of pscale * (log q0(z_j) + ladj_inv_j) come from the registers; z itself is not written (the
+// reverse pass reads only the stash and the seed).
 struct FusedArgs {
   uint32_t k0, k1, stream;
   const uint32_t *stream_ptr;  // non-null: the Philox stream id is read from device memory (hipGraph replay of the step)
@@ -416,8 +421,9 @@ struct FusedArgs {
 template <class G, bool INVERSE, bool FUSED = false, bool STASH = false, bool SLIM = false, bool B6 = false, int NW = 8>
 __global__ __launch_bounds__(64 * NW) void k_affine_chain(ChainArgs a, float *xt, float *__restrict__ ladj, FusedArgs fa) {
   static_assert(STASH || !SLIM, "SLIM is a stash layout");
-  static_assert(!STASH || !FUSED || !INVERSE, "the fused ELBO forward runs base -> data");
+  static_assert(!FUSED || !INVERSE || STASH, "the fused forward-KL chain leaves the stash of its reverse pass");
   static_assert(G::MB == G::CB, "parity blocks must have equal padded size");
+  constexpr bool FKL = FUSED && INVERSE;  // forward-KL mode; FUSED && !INVERSE is the ELBO forward
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int IMG2 = 2 * G::SIZE;  // s and t images of one coupling are adjacent in wimg
   constexpr int NV4 = IMG2 / 4;
@@ -465,7 +471,7 @@ __global__ __launch_bounds__(64 * NW) void k_affine_chain(ChainArgs a, float *xt
   constexpr int TP = 64 * G::CB;  // padded feature count (E and O halves)
   float *tmu = lds + (B6 ? 3 * B6F : 2 * IMG2), *tiv = tmu + TP, *tc0 = tiv + TP;
   double *wsum = reinterpret_cast<double *>(tc0 + 2);  // [NW] per-wave partial sums (8-byte aligned: TP even)
-  if (FUSED) {
+  if (FUSED && !FKL) {
     for (int i = tid; i < TP; i += 64 * NW) {
       tmu[i] = i < a.d ? fa.mu[i] : 0.f;
       tiv[i] = i < a.d ? 1.f / fa.var[i] : 0.f;
@@ -489,7 +495,26 @@ __global__ __launch_bounds__(64 * NW) void k_affine_chain(ChainArgs a, float *xt
     const TileIO io = make_tile_io(xt, tl, a.d, l31, hi);
     f32x16 E[G::CB], O[G::MB];
     float zz = 0.f;  // FUSED: this lane's share of ||x||^2
-    if (!FUSED) {
+    if constexpr (FKL) {
+      // ys[j * d + f] through one descriptor per tile that spans exactly the tile's samples: lanes of padding samples read 0 from
+      // the hardware, features >= d (which would be the next sample's) are zeroed here -- the values the layout conversion and
+      // tile_load give the plain chain.  The whole byte offset is per lane (voffset), so every access is range-checked.
+      const long nv = a.N - tl * NF_TILE;
+      const __amdgpu_buffer_rsrc_t ysr = __builtin_amdgcn_make_buffer_rsrc(
+          xt + tl * NF_TILE * a.d, 0, live ? (int)((nv < NF_TILE ? nv : NF_TILE) * a.d * 4) : 0, 0x00020000);
+      const int yv = (l31 * a.d + 8 * hi) * 4;
+#pragma unroll
+      for (int b = 0; b < G::CB; ++b)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int f0 = 2 * (b * 32 + (r & 3) + 8 * (r >> 2));  // E[b][r] is feature f0 + 8 hi, O[b][r] the one after it
+          const float e = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ysr, yv + 4 * f0, 0, 0));
+          const float o = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ysr, yv + 4 * f0 + 4, 0, 0));
+          const int f = f0 + 8 * hi;
+          E[b][r] = valid && f < a.d ? e : 0.f;
+          O[b][r] = valid && f + 1 < a.d ? o : 0.f;
+        }
+    } else if (!FUSED) {
 #pragma unroll
       for (int b = 0; b < G::CB; ++b)
 #pragma unroll
@@ -633,19 +658,54 @@ __global__ __launch_bounds__(64 * NW) void k_affine_chain(ChainArgs a, float *xt
       }
     }
     if (live) {
+      if constexpr (!FKL) {
 #pragma unroll
-      for (int b = 0; b < G::CB; ++b)
+        for (int b = 0; b < G::CB; ++b)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          tile_store(io, tile_soff(b, r, 0), E[b][r]);
-          tile_store(io, tile_soff(b, r, 1), O[b][r]);
-        }
+          for (int r = 0; r < 16; ++r) {
+            tile_store(io, tile_soff(b, r, 0), E[b][r]);
+            tile_store(io, tile_soff(b, r, 1), O[b][r]);
+          }
+      }
       lsum += __shfl_xor(lsum, 32);
       if (!FUSED) {
         if (hi == 0 && valid) ladj[j] = INVERSE ? -lsum : lsum;
       }
     }
-    if (FUSED) {
+    if constexpr (FKL) {
+      // loglik_j = log q0(z_j) + ladj_inv_j (ladj_inv = -lsum, what the plain inverse chain stores);  seed = gscale * g with
+      // g = -(z - mu) / var = -z exactly, k_target_tiled's diagonal-Gaussian term at mu = 0, var = 1: the split path's bits.
+      // log q0 is -d log(2 pi) / 2 - ||z||^2 / 2, as the fused ELBO forward evaluates it (not k_target_tiled's per-feature sum)
+      const TileIO gio = make_tile_io(fa.gt, tl, a.d, l31, hi);
+#pragma unroll
+      for (int b = 0; b < G::CB; ++b)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float ze = E[b][r], zo = O[b][r];
+          zz += ze * ze + zo * zo;  // features >= d and padding samples are 0
+          if (live) {
+            tile_store(gio, tile_soff(b, r, 0), valid ? fa.gscale * -ze : 0.f);
+            tile_store(gio, tile_soff(b, r, 1), valid ? fa.gscale * -zo : 0.f);
+          }
+        }
+      zz += __shfl_xor(zz, 32);
+      double contrib = 0.0;
+      if (hi == 0 && valid) {
+        const float logq = (float)(-0.5 * 1.8378770664093453 * a.d) - 0.5f * zz;
+        contrib = fa.pscale * (double)(logq + -lsum);
+      }
+#pragma unroll
+      for (int sft = 16; sft >= 1; sft >>= 1) contrib += __shfl_xor(contrib, sft);  // lanes 0..31 carry the terms
+      if (lane == 0) wsum[wave] = contrib;
+      __syncthreads();
+      if (tid == 0) {
+        double sgrp = 0.0;
+        for (int w = 0; w < NW; ++w) sgrp += wsum[w];
+        wg_total += sgrp;
+      }
+      __syncthreads();
+    }
+    if (FUSED && !FKL) {
       // elbo_j = log p(y_j) - log q0(x_j) + ladj_j ;  ybar = gscale * grad log p(y)
       const TileIO gio = make_tile_io(fa.gt ? fa.gt : xt, tl, a.d, l31, hi);
       float t = 0.f;
@@ -2614,6 +2674,46 @@ int nf_affine_chain(nf_ctx *ctx, const nf_flow_desc *desc, bool inverse, float *
               : launch_chain<NetGeo<1, 2, 2, 1>, true>(ctx, desc, inverse, xt, N, ladj, nullptr, stash);
   return b6 ? launch_chain<NetGeo<1, 2, 2, 1>, false, true>(ctx, desc, inverse, xt, N, ladj, nullptr, stash)
             : launch_chain<NetGeo<1, 2, 2, 1>>(ctx, desc, inverse, xt, N, ladj, nullptr, stash);
+}
+
+// The forward-KL training step's inverse chain (nf_loglikelihood_step): ys (d x N, standard layout, read in place) -> every
+// coupling inverse with its stash, gt <- gscale * grad log q0(z) (tiled) and partial[nf_affine_chain_grid] <- sums of
+// pscale * (log q0(z_j) + ladj_inv_j), in one launch (packed images must be current).  It has the stash writer of the default
+// split sequence (fp32 MFMAs, full stash layout); under the A/B switches NF_FWD_B6_STASH / NF_STASH_SLIM that sequence writes
+// another stash, and the step keeps it.
+bool nf_affine_chain_fkl_ok(const nf_flow_desc *desc) {
+  if (nf_deep_geo_id(desc)) return false;
+  const int size = geo_size(desc);
+  return size && !fwd_b6(true) && !stash_slim(size);
+}
+template <class G>
+static int launch_chain_fkl(nf_ctx *ctx, const nf_flow_desc *desc, const float *ys, long N, const FusedArgs &fa) {
+  const size_t lds = 4 * (size_t)G::SIZE * sizeof(float) + (2 * 64 * G::CB + 2) * sizeof(float) + 12 * sizeof(double);
+  static AttrOnce attr_once;  // once per device: a context on another GPU needs its own
+  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
+    NF_HIP(hipFuncSetAttribute((const void *)k_affine_chain<G, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return NF_OK;
+  }));
+  ChainArgs a;
+  a.wimg = (const float *)ctx->wimg;
+  a.wimg_b6 = nullptr;
+  a.d = desc->d;
+  a.ncoup = 2 * desc->nlayers;
+  a.N = N;
+  ProfScope ps(ctx, "affine_chain_fkl");
+  hipLaunchKernelGGL((k_affine_chain<G, true, true, true>), dim3((unsigned)nf_affine_chain_grid(ctx, N)), dim3(512), lds, ctx->stream, a,
+                     const_cast<float *>(ys), nullptr, fa);
+  return (int)hipGetLastError();
+}
+int nf_affine_chain_fkl(nf_ctx *ctx, const nf_flow_desc *desc, const float *ys, long N, float *gt, double gscale, double *partial,
+                        double pscale, float *stash) {
+  if (!nf_affine_chain_fkl_ok(desc) || !ctx->wimg || !stash) return NF_ERR_UNSUPPORTED;
+  if (N <= 0) return NF_OK;
+  FusedArgs fa{};
+  fa.trace = (long long *)ctx->trace;
+  fa.gt = gt; fa.gscale = (float)gscale; fa.partial = partial; fa.pscale = pscale; fa.stash = stash;
+  if (geo_size(desc) == NetGeo<1, 1, 1, 1>::SIZE) return launch_chain_fkl<NetGeo<1, 1, 1, 1>>(ctx, desc, ys, N, fa);
+  return launch_chain_fkl<NetGeo<1, 2, 2, 1>>(ctx, desc, ys, N, fa);
 }
 
 template <class G>

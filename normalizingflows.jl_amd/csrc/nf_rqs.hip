@@ -185,6 +185,8 @@ struct RqsEpiArgs {
   float *theta, *m, *v, *wimg;
   float lr, b1, b2, eps, c1, c2;  // c1 = 1 - b1^t, c2 = 1 - b2^t, computed on the host as nf_launch_adam does
   double *gpart;        // [gridDim.x] partial sums of g^2
+  const unsigned *t_ptr;  // non-null (hipGraph replay): t - 1 read from the device, c1 / c2 from b1d / b2d as k_affine_epilogue does
+  double b1d, b2d;
 };
 template <class G>
 __global__ __launch_bounds__(256) void k_rqs_epilogue(RqsPackArgs p, RqsEpiArgs a) {
@@ -230,7 +232,13 @@ __global__ __launch_bounds__(256) void k_rqs_epilogue(RqsPackArgs p, RqsEpiArgs 
   if (ti >= 0) {
     const float gsum = (part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]);
     a.g[ti] = gsum;
-    nf_adam_elem<float>(th, mi, vi, gsum, a.lr, a.b1, a.b2, a.eps, a.c1, a.c2);
+    float c1 = a.c1, c2 = a.c2;
+    if (a.t_ptr) {  // graph replay: the step count lives on the device
+      const double t = (double)(*a.t_ptr + 1u);
+      c1 = (float)(1.0 - pow(a.b1d, t));
+      c2 = (float)(1.0 - pow(a.b2d, t));
+    }
+    nf_adam_elem<float>(th, mi, vi, gsum, a.lr, a.b1, a.b2, a.eps, c1, c2);
     a.m[ti] = mi;
     a.v[ti] = vi;
     a.theta[ti] = th;
@@ -409,10 +417,18 @@ __device__ __forceinline__ float rqs_coupling_step(const float *__restrict__ img
 // k_base_sample_tiled), log q0 and the accumulated log|det J| never touch memory, and after the last coupling the
 // diagonal-Gaussian target, ybar = gscale * grad log p(y) and the workgroup's partial sum of pscale * elbo_j come out
 // of the registers (src/objectives/elbo.jl:65-70,93-97).
+// FUSED with INVERSE: the forward-KL step's inverse chain in the same way (src/objectives/loglikelihood.jl:26-33): the tile is
+// read from the caller's ys in the standard d x N layout (fa.ys), the chain leaves z (xt, tiled) and its spline tape, and
+// after the last coupling the seed gt = gscale * grad log q0(z) (k_target_tiled's arithmetic at mu = 0, var = 1) and the
+// workgroup's partial sum of pscale * (log q0(z_j) + ladj_inv_j) come from the registers.
 struct RqsFusedArgs {
   uint32_t k0, k1, stream;
   uint64_t off;           // global index of this shard's first sample
-  const float *mu, *var;  // diagonal-Gaussian target (test/flow.jl:43-46)
+  union {
+    const float *mu;      // diagonal-Gaussian target (test/flow.jl:43-46)
+    const float *ys;      // FUSED && INVERSE: the caller's data, d x N standard layout
+  };
+  const float *var;
   float *gt;              // ybar out (tiled), or nullptr
   float gscale;
   double *partial;        // [gridDim.x] out
@@ -438,6 +454,7 @@ template <class G, bool INVERSE, bool FUSED = false, bool B6 = false>
 __global__ __launch_bounds__(512) void k_rqs_chain(RqsChainArgs a, float *xt, float *__restrict__ ladj, RqsFusedArgs fa) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   using CL = RqsChainLds<G, B6>;
+  constexpr bool FKL = FUSED && INVERSE;  // forward-KL mode; FUSED && !INVERSE is the ELBO forward
   constexpr int NV4 = G::SIZE / 4;
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -472,7 +489,7 @@ __global__ __launch_bounds__(512) void k_rqs_chain(RqsChainArgs a, float *xt, fl
   constexpr int TP = 64 * G::CB;
   float *tmu = lds + CL::WAREA, *tiv = tmu + TP, *tc0 = tiv + TP;
   double *wsum = reinterpret_cast<double *>(tc0 + 2);  // [8] per-wave partial sums (G::SIZE and TP are even)
-  if (FUSED) {
+  if (FUSED && !FKL) {
     for (int i = tid; i < TP; i += 512) {
       tmu[i] = i < a.d ? fa.mu[i] : 0.f;
       tiv[i] = i < a.d ? 1.f / fa.var[i] : 0.f;
@@ -502,7 +519,25 @@ __global__ __launch_bounds__(512) void k_rqs_chain(RqsChainArgs a, float *xt, fl
     const TileIO io = make_tile_io(xt, tl, a.d, l31, hi);
     f32x16 E[G::CB], O[G::MB];
     float zz = 0.f;  // FUSED: this lane's share of ||x||^2
-    if (!FUSED) {
+    if constexpr (FKL) {
+      // ys[j * d + f] through one descriptor per tile that spans exactly the tile's samples (as k_affine_chain's forward-KL
+      // mode): padding samples read 0 from the hardware, features >= d are zeroed here; the whole offset is per lane
+      const long nv = a.N - tl * NF_TILE;
+      const __amdgpu_buffer_rsrc_t ysr = __builtin_amdgcn_make_buffer_rsrc(
+          const_cast<float *>(fa.ys) + tl * NF_TILE * a.d, 0, live ? (int)((nv < NF_TILE ? nv : NF_TILE) * a.d * 4) : 0, 0x00020000);
+      const int yv = (l31 * a.d + 8 * hi) * 4;
+#pragma unroll
+      for (int b = 0; b < G::CB; ++b)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int f0 = 2 * (b * 32 + (r & 3) + 8 * (r >> 2));  // E[b][r] is feature f0 + 8 hi, O[b][r] the one after it
+          const float e = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ysr, yv + 4 * f0, 0, 0));
+          const float o = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ysr, yv + 4 * f0 + 4, 0, 0));
+          const int f = f0 + 8 * hi;
+          E[b][r] = valid && f < a.d ? e : 0.f;
+          O[b][r] = valid && f + 1 < a.d ? o : 0.f;
+        }
+    } else if (!FUSED) {
 #pragma unroll
       for (int b = 0; b < G::CB; ++b)
 #pragma unroll
@@ -596,7 +631,40 @@ __global__ __launch_bounds__(512) void k_rqs_chain(RqsChainArgs a, float *xt, fl
         if (hi == 0 && valid) ladj[j] = lsum;  // inverse: rqs_inv_elem already accumulates -log dy/dx
       }
     }
-    if (FUSED) {
+    if constexpr (FKL) {
+      // loglik_j = log q0(z_j) + ladj_inv_j (ladj_inv = lsum, what the plain inverse chain stores);  seed = gscale * g with
+      // g = -(z - mu) / var = -z exactly, k_target_tiled's diagonal-Gaussian term at mu = 0, var = 1: the split path's bits.
+      // log q0 is -d log(2 pi) / 2 - ||z||^2 / 2, as the fused ELBO forward evaluates it (not k_target_tiled's per-feature sum)
+      const TileIO gio = make_tile_io(fa.gt, tl, a.d, l31, hi);
+#pragma unroll
+      for (int b = 0; b < G::CB; ++b)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float ze = E[b][r], zo = O[b][r];
+          zz += ze * ze + zo * zo;  // features >= d and padding samples are 0
+          if (live) {
+            tile_store(gio, tile_soff(b, r, 0), valid ? fa.gscale * -ze : 0.f);
+            tile_store(gio, tile_soff(b, r, 1), valid ? fa.gscale * -zo : 0.f);
+          }
+        }
+      zz += __shfl_xor(zz, 32);
+      double contrib = 0.0;
+      if (hi == 0 && valid) {
+        const float logq = (float)(-0.5 * 1.8378770664093453 * a.d) - 0.5f * zz;
+        contrib = fa.pscale * (double)(logq + lsum);
+      }
+#pragma unroll
+      for (int sft = 16; sft >= 1; sft >>= 1) contrib += __shfl_xor(contrib, sft);  // lanes 0..31 carry the terms
+      if (lane == 0) wsum[wave] = contrib;
+      __syncthreads();
+      if (tid == 0) {
+        double sgrp = 0.0;
+        for (int w = 0; w < 8; ++w) sgrp += wsum[w];
+        wg_total += sgrp;
+      }
+      __syncthreads();
+    }
+    if (FUSED && !FKL) {
       // elbo_j = log p(y_j) - log q0(x_j) + ladj_j ;  ybar = gscale * grad log p(y)
       const TileIO gio = make_tile_io(fa.gt ? fa.gt : xt, tl, a.d, l31, hi);
       float t = 0.f;
@@ -1948,7 +2016,8 @@ long nf_rqs_epilogue_blocks(const nf_flow_desc *desc) { return ((long)2 * desc->
 // reduce + Adam + the images of the updated theta in one launch (single-rank nf_elbo_step); gpart[nf_rqs_epilogue_blocks] receives the
 // blocks' partials of sum g^2 (finished by nf_launch_finish_sum), g[P] the loss
 int nf_rqs_epilogue(nf_ctx *ctx, const nf_flow_desc *desc, const float *slab, int nslab, float *g, const double *lpart, int nlpart,
-                    float *theta, float *m, float *v, double lr, double b1, double b2, double eps, unsigned t_val, double *gpart) {
+                    float *theta, float *m, float *v, double lr, double b1, double b2, double eps, unsigned t_val, double *gpart,
+                    const unsigned *t_ptr) {
   const int id = rqs_geo_id(desc);
   if (!id || !ctx->wimg) return NF_ERR_UNSUPPORTED;
   const RqsPackArgs p = rqs_pack_args(desc);
@@ -1961,6 +2030,7 @@ int nf_rqs_epilogue(nf_ctx *ctx, const nf_flow_desc *desc, const float *slab, in
   a.c1 = (float)(1.0 - pow(b1, (double)t_val + 1.0));
   a.c2 = (float)(1.0 - pow(b2, (double)t_val + 1.0));
   a.gpart = gpart;
+  a.t_ptr = t_ptr; a.b1d = b1; a.b2d = b2;
   const unsigned grid = (unsigned)nf_rqs_epilogue_blocks(desc);
   ctx->wimg_gen++;  // the fp32 images are rewritten (Adam's theta): the triple images are stale
   ProfScope ps(ctx, "reduce_slabs");
@@ -1973,6 +2043,15 @@ int nf_rqs_epilogue(nf_ctx *ctx, const nf_flow_desc *desc, const float *slab, in
 static bool rqs_fwd_b6() {
   static const bool off = std::getenv("NF_RQS_FWD_FP32") != nullptr;  // A/B switch: the chain kernel's output layer on fp32 MFMAs
   return !off;
+}
+// Geometries with a forward-KL chain kernel (k_rqs_chain<G, true, true, ...>).  The K = 10, d <= 32 geometry is left out: its
+// chain kernels already spill (1.4 KB of scratch for the plain inverse) and the forward-KL mode would spill 0.9 KB, so its
+// nf_loglikelihood_step keeps the split sequence.
+template <class G>
+static constexpr bool rqs_fkl_built = !std::is_same<G, GeoK10L>::value;
+bool nf_rqs_chain_fkl_ok(const nf_flow_desc *desc) {
+  const int id = rqs_geo_id(desc);
+  return id == 1 || id == 2;
 }
 template <class G>
 static int launch_rqs_chain(nf_ctx *ctx, const nf_flow_desc *desc, bool inverse, float *xt, long N, float *ladj,
@@ -1996,12 +2075,15 @@ static int launch_rqs_chain(nf_ctx *ctx, const nf_flow_desc *desc, bool inverse,
         NF_HIP(hipFuncSetAttribute((const void *)k_rqs_chain<G, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds6));
         NF_HIP(hipFuncSetAttribute((const void *)k_rqs_chain<G, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds6));
         NF_HIP(hipFuncSetAttribute((const void *)k_rqs_chain<G, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds6));
+        NF_HIP(hipFuncSetAttribute((const void *)k_rqs_chain<G, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds6));
         return NF_OK;
       }));
       NF_TRY(rqs_b6_refresh<G>(ctx, desc));
       a.wimg6 = (const nf_u32x4 *)((const char *)ctx->wimg + rqs_fp32_bytes(desc));
-      ProfScope ps(ctx, "rqs_chain");
-      if (fused)
+      ProfScope ps(ctx, fused && inverse ? "rqs_chain_fkl" : "rqs_chain");
+      if (fused && inverse)  // forward-KL training step (nf_rqs_chain_fkl)
+        hipLaunchKernelGGL((k_rqs_chain<G, true, true, true>), dim3((unsigned)grid), dim3(512), lds6, ctx->stream, a, xt, ladj, *fused);
+      else if (fused)
         hipLaunchKernelGGL((k_rqs_chain<G, false, true, true>), dim3((unsigned)grid), dim3(512), lds6, ctx->stream, a, xt, ladj, *fused);
       else if (inverse)
         hipLaunchKernelGGL((k_rqs_chain<G, true, false, true>), dim3((unsigned)grid), dim3(512), lds6, ctx->stream, a, xt, ladj, none);
@@ -2017,10 +2099,17 @@ static int launch_rqs_chain(nf_ctx *ctx, const nf_flow_desc *desc, bool inverse,
     NF_HIP(hipFuncSetAttribute((const void *)k_rqs_chain<G, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     NF_HIP(hipFuncSetAttribute((const void *)k_rqs_chain<G, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     NF_HIP(hipFuncSetAttribute((const void *)k_rqs_chain<G, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if constexpr (rqs_fkl_built<G>)
+      NF_HIP(hipFuncSetAttribute((const void *)k_rqs_chain<G, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     return NF_OK;
   }));
-  ProfScope ps(ctx, "rqs_chain");
-  if (fused)
+  ProfScope ps(ctx, fused && inverse ? "rqs_chain_fkl" : "rqs_chain");
+  if (fused && inverse) {
+    if constexpr (rqs_fkl_built<G>)
+      hipLaunchKernelGGL((k_rqs_chain<G, true, true>), dim3((unsigned)grid), dim3(512), lds, ctx->stream, a, xt, ladj, *fused);
+    else
+      return NF_ERR_UNSUPPORTED;
+  } else if (fused)
     hipLaunchKernelGGL((k_rqs_chain<G, false, true>), dim3((unsigned)grid), dim3(512), lds, ctx->stream, a, xt, ladj, *fused);
   else if (inverse)
     hipLaunchKernelGGL((k_rqs_chain<G, true>), dim3((unsigned)grid), dim3(512), lds, ctx->stream, a, xt, ladj, none);
@@ -2047,6 +2136,21 @@ int nf_rqs_chain_elbo(nf_ctx *ctx, const nf_flow_desc *desc, long N, uint64_t se
   fa.k0 = (uint32_t)seed; fa.k1 = (uint32_t)(seed >> 32); fa.stream = stream; fa.off = off;
   fa.mu = mu; fa.var = var; fa.gt = gt; fa.gscale = (float)gscale; fa.partial = partial; fa.pscale = pscale;
 #define RQS_CALL(G) launch_rqs_chain<G>(ctx, desc, false, yt, N, nullptr, -1, &fa, tape)
+  return RQS_DISPATCH(id, RQS_CALL);
+#undef RQS_CALL
+}
+
+// The forward-KL training step's inverse chain (nf_loglikelihood_step): ys (d x N, standard layout) -> zt <- z = T^-1(ys) (tiled),
+// the spline tape, gt <- gscale * grad log q0(z) (tiled) and partial[nf_rqs_chain_grid] <- sums of pscale * (log q0(z_j) +
+// ladj_inv_j), in one launch with the stash-free chain's kernel choice (packed images must be current)
+int nf_rqs_chain_fkl(nf_ctx *ctx, const nf_flow_desc *desc, const float *ys, long N, float *zt, float *gt, double gscale,
+                     double *partial, double pscale, void *tape) {
+  const int id = rqs_geo_id(desc);
+  if (!nf_rqs_chain_fkl_ok(desc) || !ctx->wimg || !tape) return NF_ERR_UNSUPPORTED;
+  if (N <= 0) return NF_OK;
+  RqsFusedArgs fa{};
+  fa.ys = ys; fa.gt = gt; fa.gscale = (float)gscale; fa.partial = partial; fa.pscale = pscale;
+#define RQS_CALL(G) launch_rqs_chain<G>(ctx, desc, true, zt, N, nullptr, -1, &fa, tape)
   return RQS_DISPATCH(id, RQS_CALL);
 #undef RQS_CALL
 }

@@ -127,6 +127,21 @@ def loglikelihood_value_and_gradient(flow: Flow, xs: torch.Tensor, n_global: Opt
     return float(out[flow.P]), out[: flow.P]
 
 
+def loglikelihood_step(flow: Flow, xs: torch.Tensor, opt: "Adam", st: "AdamState", n_global: Optional[int] = None):
+    """One iteration of train_flow(loglikelihood, flow, xs) in one library call (nf_loglikelihood_step): value and
+    gradient of -loglikelihood(rng, re(theta), xs), the all-reduce of [grad ; loss] when the flow's context holds a
+    communicator, Optimisers.update! with Adam on flow.theta / st in place (t = st.t + 1) and norm(g).  For a shard of a
+    global data set pass n_global (default: the columns of xs times the communicator's size).  Returns (loss, norm(g))."""
+    xm, _ = as_batch(xs.to(flow.theta.dtype))
+    ctx = flow.ctx
+    loss, gn = _host_double(), _host_double()
+    check(ctx.lib.nf_loglikelihood_step(ctx.ptr, C.byref(flow.desc), _ptr(flow.theta), _ptr(st.m), _ptr(st.v), _ptr(xm), xm.shape[1],
+                                        0 if n_global is None else int(n_global), st.t, opt.eta, opt.beta[0], opt.beta[1], opt.epsilon,
+                                        C.byref(loss), C.byref(gn)))
+    st.t += 1
+    return loss.value, gn.value
+
+
 # --------------------------------------------------------------------------------------
 # gradients (the device analogue of _value_and_gradient, src/optimize.jl:12-14)
 # --------------------------------------------------------------------------------------
@@ -314,6 +329,63 @@ def _fused_steps_apply(vo, flow: Flow, rest, rng: PhiloxRNG, optimiser, kwargs) 
     return _builtin(flow, rest[0])
 
 
+def _fused_fkl_steps_apply(vo, flow: Flow, rest, optimiser, kwargs) -> bool:
+    """True when a training run is what nf_loglikelihood_step computes in one call per iteration: forward KL on the data
+    set, Adam, no data-parallel hook or communicator, and `state` absent or an AdamState."""
+    if vo is not loglikelihood or len(rest) != 1:
+        return False
+    if not (optimiser is None or isinstance(optimiser, Adam)) or kwargs.get("all_reduce") is not None:
+        return False
+    st = kwargs.get("state")
+    if st is not None and not isinstance(st, AdamState):
+        return False
+    # under a communicator the step would all-reduce inside the library: not the run `optimize` would be
+    return int(flow.ctx.lib.nf_comm_size(flow.ctx.ptr)) <= 1
+
+
+def _optimize_fused_fkl(flow: Flow, theta0: torch.Tensor, reconstruct, xs: torch.Tensor, *, max_iters: int, optimiser: Adam,
+                        show_progress: bool = False, callback=None, hasconverged=None, all_reduce=None, state=None):
+    """`_optimize_fused` for train_flow(loglikelihood, flow, xs): each iteration is ONE nf_loglikelihood_step (inverse
+    chain, reverse pass, Adam, norm(g)); the weight cache is opted in for the loop and out on return, a user `hasconverged`
+    sees the live theta and is followed by nf_ctx_weights_changed.  Same numbers as `optimize` over
+    loglikelihood_value_and_gradient + update."""
+    from ._lib import NF_ERR_NONFINITE
+
+    theta = theta0.clone()
+    st = state if state is not None else setup(optimiser, theta)
+    ctx, lib = flow.ctx, flow.ctx.lib
+    xm, _ = as_batch(xs.to(theta.dtype))
+    opt_stats = []
+    converged = False
+    i = 1
+    loss, gn = _host_double(), _host_double()
+    check(lib.nf_ctx_set_weight_cache(ctx.ptr, 1))
+    try:
+        while i <= max_iters and not converged:
+            theta_before = theta.clone() if callback is not None else None
+            code = lib.nf_loglikelihood_step(ctx.ptr, C.byref(flow.desc), _ptr(theta), _ptr(st.m), _ptr(st.v), _ptr(xm), xm.shape[1],
+                                             xm.shape[1], st.t, optimiser.eta, optimiser.beta[0], optimiser.beta[1],
+                                             optimiser.epsilon, C.byref(loss), C.byref(gn))
+            if code != NF_ERR_NONFINITE:  # a non-finite loss is recorded, as the reference's loop would record it
+                check(code)
+            st.t += 1
+            stat = {"iteration": i, "loss": loss.value, "gradient_norm": gn.value}
+            if callback is not None:
+                new_stat = callback(i, opt_stats, reconstruct, theta_before)
+                if new_stat is not None:
+                    stat.update(new_stat)
+            opt_stats.append(stat)
+            i += 1
+            if hasconverged is not None:
+                converged = hasconverged(i, stat, reconstruct, theta, st)
+                check(lib.nf_ctx_weights_changed(ctx.ptr))  # it was handed the live theta
+            if show_progress and (i % 100 == 0):
+                print(f"Training iter {i}: loss {stat['loss']:.6g} |g| {stat['gradient_norm']:.3g}")
+    finally:
+        lib.nf_ctx_set_weight_cache(ctx.ptr, 0)
+    return theta, opt_stats, st
+
+
 def _optimize_fused(flow: Flow, theta0: torch.Tensor, reconstruct, rng: PhiloxRNG, logp, n: int, *, max_iters: int,
                     optimiser: Adam, show_progress: bool = False, callback=None, hasconverged=None, all_reduce=None,
                     state=None):
@@ -364,8 +436,9 @@ def train_flow(*args, max_iters: int = 1000, optimiser: Adam = None, ADbackend=N
 
     `ADbackend` is accepted for signature compatibility; gradients come from the library's
     hand-derived reverse pass (the role a custom ADTypes backend plays in the reference).  Reverse-KL runs on a
-    built-in target with Adam go through nf_elbo_step, one library call per iteration (`_optimize_fused`); everything
-    else through `optimize` over value_and_gradient + update."""
+    built-in target with Adam go through nf_elbo_step, one library call per iteration (`_optimize_fused`), forward-KL
+    runs with Adam through nf_loglikelihood_step (`_optimize_fused_fkl`); everything else through `optimize` over
+    value_and_gradient + update."""
     if isinstance(args[0], PhiloxRNG):
         rng, vo, flow, *rest = args
     else:
@@ -375,6 +448,10 @@ def train_flow(*args, max_iters: int = 1000, optimiser: Adam = None, ADbackend=N
     if _fused_steps_apply(vo, flow, rest, rng, optimiser, kwargs):
         theta, stats, st = _optimize_fused(flow, theta_flat, re, rng, rest[0], rest[1], max_iters=max_iters,
                                            optimiser=optimiser or Adam(), **kwargs)
+        return re(theta), stats, st
+    if _fused_fkl_steps_apply(vo, flow, rest, optimiser, kwargs):
+        theta, stats, st = _optimize_fused_fkl(flow, theta_flat, re, rest[0], max_iters=max_iters, optimiser=optimiser or Adam(),
+                                               **kwargs)
         return re(theta), stats, st
 
     def loss_and_grad(theta):

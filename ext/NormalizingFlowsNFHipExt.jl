@@ -51,7 +51,7 @@ struct NFTarget
 end
 
 const NF_KIND_PLANAR, NF_KIND_RADIAL, NF_KIND_REALNVP, NF_KIND_NSF, NF_KIND_MEANFIELD = Int32(0), Int32(1), Int32(2), Int32(3), Int32(4)
-const NF_TARGET_DIAGGAUSS, NF_TARGET_BANANA = Int32(0), Int32(1)
+const NF_TARGET_DIAGGAUSS, NF_TARGET_BANANA, NF_TARGET_FUNNEL, NF_TARGET_WARPED, NF_TARGET_CROSS = Int32(0), Int32(1), Int32(2), Int32(3), Int32(4)
 dtype_code(::Type{Float32}) = Int32(0)
 dtype_code(::Type{Float64}) = Int32(1)
 
@@ -192,12 +192,43 @@ struct BananaTarget <: NFHipTarget                    # Banana(d, b, var), examp
     b::Float64
     var::Float64
 end
+struct FunnelTarget <: NFHipTarget                    # Funnel(d, μ, σ), example/targets/neal_funnel.jl:26-44; Funnel(d) = Funnel(d, 0, 9)
+    d::Int
+    μ::Float64
+    σ::Float64
+    function FunnelTarget(d::Integer, μ::Real=0.0, σ::Real=9.0)
+        d >= 2 || error("dim must be >= 2")   # neal_funnel.jl:32
+        σ > 0 || error("σ must be > 0")       # neal_funnel.jl:33
+        return new(d, μ, σ)
+    end
+end
+struct WarpedGaussTarget <: NFHipTarget               # WarpedGauss(σ1, σ2), 2-dimensional, example/targets/warped_gaussian.jl:25-37
+    σ1::Float64
+    σ2::Float64
+    function WarpedGaussTarget(σ1::Real=1.0, σ2::Real=0.12)
+        (σ1 > 0 && σ2 > 0) || error("σ₁, σ₂ must be > 0")   # warped_gaussian.jl:31-32
+        return new(σ1, σ2)
+    end
+end
+struct CrossTarget <: NFHipTarget                     # Cross(μ, σ), 2-dimensional 4-component mixture, example/targets/cross.jl:29-38
+    μ::Float64
+    σ::Float64
+    function CrossTarget(μ::Real=2.0, σ::Real=0.15)
+        σ > 0 || error("σ must be > 0")
+        return new(μ, σ)
+    end
+end
 c_target(t::DiagGaussTarget) = NFTarget(NF_TARGET_DIAGGAUSS, devptr(t.μ), devptr(t.σ²), 0.0, 0.0)
 c_target(t::BananaTarget) = NFTarget(NF_TARGET_BANANA, C_NULL, C_NULL, t.b, t.var)
+c_target(t::FunnelTarget) = NFTarget(NF_TARGET_FUNNEL, C_NULL, C_NULL, t.μ, t.σ)
+c_target(t::WarpedGaussTarget) = NFTarget(NF_TARGET_WARPED, C_NULL, C_NULL, t.σ1, t.σ2)
+c_target(t::CrossTarget) = NFTarget(NF_TARGET_CROSS, C_NULL, C_NULL, t.μ, t.σ)
 function check_target(t::DiagGaussTarget, ::Type{T}, d) where {T}
     (eltype(t.μ) === T && length(t.μ) == d) || error("nfhip: target must be a length-$d ROCVector{$T} pair")
 end
 check_target(t::BananaTarget, ::Type, d) = t.d == d || error("nfhip: Banana dimension mismatch")
+check_target(t::FunnelTarget, ::Type, d) = t.d == d || error("nfhip: Funnel dimension mismatch")
+check_target(t::Union{WarpedGaussTarget,CrossTarget}, ::Type, d) = d == 2 || error("nfhip: WarpedGauss and Cross are 2-dimensional targets")
 
 function (t::NFHipTarget)(ys::ROCMatrix{T}) where {T}
     d, N = size(ys)

@@ -41,7 +41,7 @@ int nf_affine_pack(nf_ctx *, const nf_flow_desc *, const float *theta);
 int nf_affine_chain(nf_ctx *, const nf_flow_desc *, bool inverse, float *xt, long N, float *ladj, float *stash = nullptr);
 long nf_affine_chain_grid(nf_ctx *, long N);
 int nf_affine_chain_elbo(nf_ctx *, const nf_flow_desc *, long N, uint64_t seed, uint64_t off, uint32_t stream,
-                         const float *mu, const float *var, float *yt, float *gt, double gscale, double *partial,
+                         const nf_target *target, float *yt, float *gt, double gscale, double *partial,
                          double pscale, float *stash = nullptr, const uint32_t *stream_ptr = nullptr);
 long nf_affine_epilogue_blocks(const nf_flow_desc *desc);
 bool nf_affine_chain_fkl_ok(const nf_flow_desc *desc);
@@ -88,8 +88,8 @@ int nf_rqs_bwd(nf_ctx *, const nf_flow_desc *, int k, float *y, float *ybar, con
 long nf_rqs_slab_floats(const nf_flow_desc *desc);
 long nf_rqs_chain_grid(nf_ctx *, long N);
 int nf_rqs_chain_elbo(nf_ctx *, const nf_flow_desc *, long N, uint64_t seed, uint64_t off, uint32_t stream,
-                      const float *mu, const float *var, float *yt, float *gt, double gscale, double *partial,
-                      double pscale, void *tape = nullptr);
+                      const nf_target *target, float *yt, float *gt, double gscale, double *partial,
+                      double pscale, void *tape = nullptr, const uint32_t *stream_ptr = nullptr);
 int nf_rqs_reduce_slabs(nf_ctx *, const nf_flow_desc *, const float *slab, int nslab, float *g);
 long nf_rqs_epilogue_blocks(const nf_flow_desc *desc);
 int nf_rqs_epilogue(nf_ctx *, const nf_flow_desc *, const float *slab, int nslab, float *g, const double *lpart, int nlpart, float *theta,
@@ -598,21 +598,21 @@ static long coupling_slab_floats(nf_ctx *ctx, const nf_flow_desc *desc, long N) 
 }
 
 // The ELBO forward of a training step fuses into ONE launch (draws + chain + target + partial sums)
-// when the draws are in-library, the nets are LDS-resident and the target is the diagonal Gaussian.
+// when the draws are in-library, the nets are LDS-resident and the target is one of the built-in kinds with valid
+// arguments (nf_target_check: the diagonal Gaussian's two vectors, d = 2 for WarpedGauss / Cross, ...).  A target that
+// fails the check keeps the generic sequence, whose target launch reports it.
 static inline bool elbo_fusable(const nf_flow_desc *desc, const nf_target *target, const void *xs) {
   const bool resident = (desc->kind == NF_KIND_REALNVP && nf_affine_supported(desc) && nf_affine_fused_ok(desc)) ||
                         (desc->kind == NF_KIND_NSF && nf_rqs_supported(desc));
-  return !xs && desc->dtype == NF_DTYPE_F32 && resident && target->kind == NF_TARGET_DIAGGAUSS && target->p0 && target->p1;
+  return !xs && desc->dtype == NF_DTYPE_F32 && resident && nf_target_check(target, desc->d) == NF_OK;
 }
 // the fused forward launch (draws + chain + target + ELBO partial sums) of the two LDS-resident coupling families
 static int fused_chain_elbo(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, long N, uint64_t seed,
                             uint64_t off, uint32_t stream_id, float *yt, float *gt, double gscale, double *partial,
-                            double pscale, float *stash = nullptr) {
+                            double pscale, float *stash = nullptr, const uint32_t *stream_ptr = nullptr) {
   if (desc->kind == NF_KIND_NSF)  // `stash`: the spline tape (nf_rqs_tape_bytes)
-    return nf_rqs_chain_elbo(ctx, desc, N, seed, off, stream_id, (const float *)target->p0, (const float *)target->p1, yt, gt,
-                             gscale, partial, pscale, stash);
-  return nf_affine_chain_elbo(ctx, desc, N, seed, off, stream_id, (const float *)target->p0, (const float *)target->p1, yt, gt,
-                              gscale, partial, pscale, stash);
+    return nf_rqs_chain_elbo(ctx, desc, N, seed, off, stream_id, target, yt, gt, gscale, partial, pscale, stash, stream_ptr);
+  return nf_affine_chain_elbo(ctx, desc, N, seed, off, stream_id, target, yt, gt, gscale, partial, pscale, stash, stream_ptr);
 }
 // The LDS-resident RealNVP training step keeps the forward's activations for the reverse pass (nf_coupling.hip,
 // "activation stash") while they fit the budget: 46 KiB per 32-sample tile and coupling at d = 64 / hidden 64.  NF_AFFINE_STASH_MAX_MB (default 4096) bounds it; beyond, or with
@@ -1946,7 +1946,7 @@ extern "C" int nf_sgd_update(nf_ctx *ctx, int32_t dtype, void *theta, const void
 
 // ---- the fused training step of the LDS-resident RealNVP path -----------------------------------------------------
 // nf_elbo_step for cfg-2-like flows is three launches plus a one-block finish: k_affine_chain<FUSED, STASH> (draws + chain +
-// target + ELBO sums, leaving the activation stash), k_affine_bwd_stashed (reverse pass of every coupling), k_affine_epilogue
+// target + ELBO sums, leaving the activation stash; k_affine_chain_tgt for the Banana / Funnel / WarpedGauss / Cross targets), k_affine_bwd_stashed (reverse pass of every coupling), k_affine_epilogue
 // (slab sum -> gradient, loss, Adam, partials of ||g||^2, packed weight images of the UPDATED theta) and k_finish_sum (||g||).
 // The packed images survive from one step to the next: no k_pack_net_images, no separate slab-reduction / Adam launches.  With a communicator on the
 // context (nf_comm_init_*) the step is the data-parallel one: this rank draws samples [rank N, (rank + 1) N) of a global
@@ -2019,7 +2019,7 @@ static int elbo_step_fused(nf_ctx *ctx, const nf_flow_desc *desc, const nf_targe
   for (long o = 0; o < N; o += stash_nc) {
     const long nc = N - o < stash_nc ? N - o : stash_nc;
     const int gc = coupling_bwd_grid(ctx, desc, nc);
-    NF_TRY(nf_affine_chain_elbo(ctx, desc, nc, seed, off0 + (uint64_t)o, step_val, (const float *)target->p0, (const float *)target->p1,
+    NF_TRY(nf_affine_chain_elbo(ctx, desc, nc, seed, off0 + (uint64_t)o, step_val, target,
                                 xt + o * desc->d, gt + o * desc->d, -inv, partial + npart, -inv, stash, step_ptr));
     NF_TRY(nf_affine_bwd_stashed(ctx, desc, stash, gt + o * desc->d, nullptr, (float)(-inv), nc, slab + nslab * stride, stride, gc));
     nslab += gc;
@@ -2043,7 +2043,7 @@ static int elbo_step_fused(nf_ctx *ctx, const nf_flow_desc *desc, const nf_targe
 }
 
 // The same for LDS-resident spline couplings on ONE rank (round 6): fused forward (draws + chain + target + loss partials, leaving the
-// spline tape), one reverse launch per coupling, and nf_rqs_epilogue (loss, slab reduction, Adam, the updated images) -- four launches
+// spline tape; k_rqs_chain<FUSED> for the diagonal Gaussian, k_rqs_chain_tgt for the other built-in targets; step_ptr as above), one reverse launch per coupling, and nf_rqs_epilogue (loss, slab reduction, Adam, the updated images) -- four launches
 // fewer than nf_elbo_value_and_grad + nf_adam_update + the next step's pack.  Multi-rank contexts keep the generic sequence (the
 // all-reduce sits between the reduction and Adam).
 static bool step_fusable_rqs(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target) {
@@ -2062,7 +2062,7 @@ static size_t step_fused_need_rqs(nf_ctx *ctx, const nf_flow_desc *desc, long N)
          carve_bytes((size_t)nf_rqs_epilogue_blocks(desc) * 8);
 }
 static int elbo_step_fused_rqs(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, float *theta, float *m, float *v, long N,
-                               uint64_t seed, uint32_t step_val, double lr, double beta1, double beta2, double eps) {
+                               uint64_t seed, uint32_t step_val, uint32_t *step_ptr, double lr, double beta1, double beta2, double eps) {
   const long P = nf_param_count(desc);
   const double inv = 1.0 / (double)N;
   const size_t te = tiled_elems(desc, N);
@@ -2083,12 +2083,13 @@ static int elbo_step_fused_rqs(nf_ctx *ctx, const nf_flow_desc *desc, const nf_t
   // packed images: those the previous step's epilogue left (only under nf_ctx_set_weight_cache(ctx, 1)), or a fresh pack
   if (!ctx->wimg_cache || !(ctx->wimg && ctx->wimg_owner == (const void *)theta && ctx->wimg_sig == flow_sig(desc)))
     NF_TRY(coupling_pack(ctx, desc, theta));
-  NF_TRY(fused_chain_elbo(ctx, desc, target, N, seed, 0, step_val, xt, gt, -inv, partial, -inv, (float *)tape));
+  NF_TRY(fused_chain_elbo(ctx, desc, target, N, seed, 0, step_val, xt, gt, -inv, partial, -inv, (float *)tape, step_ptr));
   const int nc = 2 * desc->nlayers;
   for (int k = 0; k < nc; ++k) NF_TRY(nf_rqs_bwd(ctx, desc, k, xt, gt, nullptr, (float)(-inv), N, slab, stride, grid, false, tape));
   NF_TRY(nf_rqs_epilogue(ctx, desc, slab, grid, gbuf, partial, (int)fused_chain_grid(ctx, desc, N), theta, m, v, lr, beta1, beta2, eps,
-                         step_val, gpart));
-  NF_TRY(nf_launch_finish_sum(ctx, gpart, eblocks, 1, nullptr, gbuf + P + 1, nullptr, nullptr));
+                         step_val, gpart, step_ptr));
+  // norm(g); in the graph-replay form also the step counter's increment, as the RealNVP step does it
+  NF_TRY(nf_launch_finish_sum(ctx, gpart, eblocks, 1, nullptr, gbuf + P + 1, nullptr, step_ptr));
   ctx->wimg_owner = theta;
   ctx->wimg_sig = flow_sig(desc);
   return NF_OK;
@@ -2163,7 +2164,7 @@ extern "C" int nf_elbo_step(nf_ctx *ctx, const nf_flow_desc *desc, const nf_targ
   if (step_fusable(ctx, desc, target, N)) {
     NF_TRY(elbo_step_fused(ctx, desc, target, (float *)theta, (float *)m, (float *)v, N, seed, step, nullptr, lr, beta1, beta2, eps));
   } else if (step_fusable_rqs(ctx, desc, target)) {
-    NF_TRY(elbo_step_fused_rqs(ctx, desc, target, (float *)theta, (float *)m, (float *)v, N, seed, step, lr, beta1, beta2, eps));
+    NF_TRY(elbo_step_fused_rqs(ctx, desc, target, (float *)theta, (float *)m, (float *)v, N, seed, step, nullptr, lr, beta1, beta2, eps));
   } else {
     const int world = ctx->comm ? ctx->comm_size : 1;
     const uint64_t off = (uint64_t)(ctx->comm ? ctx->comm_rank : 0) * (uint64_t)N;
@@ -2215,9 +2216,13 @@ extern "C" int nf_elbo_step_enqueue(nf_ctx *ctx, const nf_flow_desc *desc, const
   NF_TRY(check_desc(desc));
   NF_HIP(hipSetDevice(ctx->device));
   const long P = nf_param_count(desc);
-  if (!step_fusable(ctx, desc, target, N)) return NF_ERR_UNSUPPORTED;
+  const bool affine = step_fusable(ctx, desc, target, N);
+  if (!affine && !step_fusable_rqs(ctx, desc, target)) return NF_ERR_UNSUPPORTED;
   NF_TRY(gbuf_reserve(ctx, gbuf_need(P, 4)));
-  NF_TRY(elbo_step_fused(ctx, desc, target, (float *)theta, (float *)m, (float *)v, N, seed, 0, step_device, lr, beta1, beta2, eps));
+  if (affine)
+    NF_TRY(elbo_step_fused(ctx, desc, target, (float *)theta, (float *)m, (float *)v, N, seed, 0, step_device, lr, beta1, beta2, eps));
+  else
+    NF_TRY(elbo_step_fused_rqs(ctx, desc, target, (float *)theta, (float *)m, (float *)v, N, seed, 0, step_device, lr, beta1, beta2, eps));
   if (out_loss_gnorm_device)
     NF_HIP(hipMemcpyAsync(out_loss_gnorm_device, (char *)ctx->gbuf + (size_t)P * 4, 8, hipMemcpyDeviceToDevice, ctx->stream));
   return NF_OK;

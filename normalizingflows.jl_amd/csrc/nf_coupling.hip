@@ -26,6 +26,9 @@
 #include "nf_mfma.h"
 #include "nf_pack.h"
 #include "nf_philox.h"
+#include "nf_target_epilogue.h"
+
+int nf_target_check(const nf_target *t, int d);  // nf_elementwise.hip
 
 struct CouplingArgs {
   const float *theta;
@@ -410,6 +413,8 @@ struct FusedArgs {
   double pscale;
   float *stash;           // STASH: [tile][coupling][StashGeo<G>::SIZE] out
   long long *trace;       // NF_KERNEL_TRACE builds: clock stamps for tools/trace_chain.py, else unused
+  int tkind;              // k_affine_chain_tgt: NF_TARGET_BANANA / FUNNEL / WARPED / CROSS and the target's two scalars
+  float ts0, ts1;
 };
 
 // B6 (round 4, the default): the conditioner GEMMs on the bf16 matrix cores with six-term products (nf_mfma.h), 2.67 x
@@ -418,9 +423,12 @@ struct FusedArgs {
 // s(c0), t(c0), s(c1), ... lives in slot i mod 3; the phase of image i starts with a workgroup barrier (image i complete,
 // everybody done with image i - 1) and then requests image i + 2 into the slot image i - 1 just left.
 // NW: wavefronts (= tiles of a group) per workgroup; 12 (three per SIMD) where the instantiation fits 168 registers (round 6)
-template <class G, bool INVERSE, bool FUSED = false, bool STASH = false, bool SLIM = false, bool B6 = false, int NW = 8>
-__global__ __launch_bounds__(64 * NW) void k_affine_chain(ChainArgs a, float *xt, float *__restrict__ ladj, FusedArgs fa) {
+// TGT (the body of k_affine_chain_tgt, FUSED forward only): the epilogue evaluates one of the other four built-in targets
+// (fa.tkind, nf_target_epilogue.h) instead of the diagonal Gaussian; everything before it is the same code.
+template <class G, bool INVERSE, bool FUSED, bool STASH, bool SLIM, bool B6, int NW, bool TGT>
+__device__ __forceinline__ void affine_chain_body(ChainArgs a, float *xt, float *__restrict__ ladj, FusedArgs fa) {
   static_assert(STASH || !SLIM, "SLIM is a stash layout");
+  static_assert(!TGT || (FUSED && !INVERSE), "the target switch belongs to the fused ELBO forward");
   static_assert(!FUSED || !INVERSE || STASH, "the fused forward-KL chain leaves the stash of its reverse pass");
   static_assert(G::MB == G::CB, "parity blocks must have equal padded size");
   constexpr bool FKL = FUSED && INVERSE;  // forward-KL mode; FUSED && !INVERSE is the ELBO forward
@@ -471,7 +479,7 @@ __global__ __launch_bounds__(64 * NW) void k_affine_chain(ChainArgs a, float *xt
   constexpr int TP = 64 * G::CB;  // padded feature count (E and O halves)
   float *tmu = lds + (B6 ? 3 * B6F : 2 * IMG2), *tiv = tmu + TP, *tc0 = tiv + TP;
   double *wsum = reinterpret_cast<double *>(tc0 + 2);  // [NW] per-wave partial sums (8-byte aligned: TP even)
-  if (FUSED && !FKL) {
+  if (FUSED && !FKL && !TGT) {
     for (int i = tid; i < TP; i += 64 * NW) {
       tmu[i] = i < a.d ? fa.mu[i] : 0.f;
       tiv[i] = i < a.d ? 1.f / fa.var[i] : 0.f;
@@ -705,7 +713,30 @@ __global__ __launch_bounds__(64 * NW) void k_affine_chain(ChainArgs a, float *xt
       }
       __syncthreads();
     }
-    if (FUSED && !FKL) {
+    if constexpr (TGT) {
+      // elbo_j = log p(y_j) - log q0(x_j) + ladj_j ;  ybar = gscale * grad log p(y), p one of Banana / Funnel / WarpedGauss / Cross
+      const TileIO gio = make_tile_io(fa.gt ? fa.gt : xt, tl, a.d, l31, hi);
+      nf_tile_isolate<G::CB>(E, O);
+      const float logp = nf_tile_target<G::CB, NF_TGT_ALL4>(fa.tkind, E, O, a.d, fa.ts0, fa.ts1, l31, hi, gio, fa.gt && live, valid, fa.gscale);
+      zz += __shfl_xor(zz, 32);
+      double contrib = 0.0;
+      if (hi == 0 && valid) {
+        const float logq = (float)(-0.5 * 1.8378770664093453 * a.d) - 0.5f * zz;
+        const float e = logp - logq + lsum;
+        contrib = fa.pscale * (double)e;
+      }
+#pragma unroll
+      for (int sft = 16; sft >= 1; sft >>= 1) contrib += __shfl_xor(contrib, sft);  // lanes 0..31 carry the terms
+      if (lane == 0) wsum[wave] = contrib;
+      __syncthreads();
+      if (tid == 0) {
+        double sgrp = 0.0;
+        for (int w = 0; w < NW; ++w) sgrp += wsum[w];
+        wg_total += sgrp;
+      }
+      __syncthreads();
+    }
+    if (FUSED && !FKL && !TGT) {
       // elbo_j = log p(y_j) - log q0(x_j) + ladj_j ;  ybar = gscale * grad log p(y)
       const TileIO gio = make_tile_io(fa.gt ? fa.gt : xt, tl, a.d, l31, hi);
       float t = 0.f;
@@ -743,6 +774,16 @@ __global__ __launch_bounds__(64 * NW) void k_affine_chain(ChainArgs a, float *xt
     }
   }
   if (FUSED && tid == 0) fa.partial[blockIdx.x] = wg_total;
+}
+template <class G, bool INVERSE, bool FUSED = false, bool STASH = false, bool SLIM = false, bool B6 = false, int NW = 8>
+__global__ __launch_bounds__(64 * NW) void k_affine_chain(ChainArgs a, float *xt, float *__restrict__ ladj, FusedArgs fa) {
+  affine_chain_body<G, INVERSE, FUSED, STASH, SLIM, B6, NW, false>(a, xt, ladj, fa);
+}
+// The fused ELBO forward for the Banana, Funnel, WarpedGauss and Cross targets: k_affine_chain<G, false, true, STASH, SLIM, B6>'s
+// draws, chain and stash with the target switch as its epilogue (one instantiation per geometry serves the four kinds).
+template <class G, bool STASH, bool SLIM = false, bool B6 = false, int NW = 8>
+__global__ __launch_bounds__(64 * NW) void k_affine_chain_tgt(ChainArgs a, float *xt, FusedArgs fa) {
+  affine_chain_body<G, false, true, STASH, SLIM, B6, NW, true>(a, xt, nullptr, fa);
 }
 
 // ------------------------------------------------------------------------------------
@@ -2569,6 +2610,12 @@ static int launch_chain(nf_ctx *ctx, const nf_flow_desc *desc, bool inverse, flo
 // cfg 5 1.72 against 1.63 ms (profiles/r6u_chain_dual.txt): with one wave per SIMD nothing covers the layer boundaries
 #endif
   constexpr int NWP = B6 ? NF_CHAIN_NW : 8;  // waves per workgroup of the plain chains below
+  // k_affine_chain_tgt (the fused forward for the Banana / Funnel / WarpedGauss / Cross targets): eight waves per workgroup
+  // where the instantiation fits 256 registers without scratch, four (one per SIMD, 512 registers) where it does not -- the
+  // six-term forms at hidden 64 without a stash (44 bytes at eight) and with the slim stash (12 bytes); by
+  // tools/kernel_resources.py, held by tests/test_elbo_targets_cpu.py.  The grid does not depend on it (the tile-group loop strides).
+  constexpr bool H64G = G::H1B == 2;
+  constexpr int NWT_S = (H64G && B6 && SLIM) ? 4 : 8, NWT_P = (H64G && B6) ? 4 : 8;
   static AttrOnce attr_once;  // once per device: a context on another GPU needs its own
   NF_TRY(attr_once.run(ctx->device, [&]() -> int {
     NF_HIP(hipFuncSetAttribute((const void *)k_affine_chain<G, false, false, false, false, B6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -2577,6 +2624,8 @@ static int launch_chain(nf_ctx *ctx, const nf_flow_desc *desc, bool inverse, flo
     NF_HIP(hipFuncSetAttribute((const void *)k_affine_chain<G, false, true, true, SLIM, B6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     NF_HIP(hipFuncSetAttribute((const void *)k_affine_chain<G, false, false, true, SLIM, B6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     NF_HIP(hipFuncSetAttribute((const void *)k_affine_chain<G, true, false, true, SLIM, B6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    NF_HIP(hipFuncSetAttribute((const void *)k_affine_chain_tgt<G, true, SLIM, B6, NWT_S>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    NF_HIP(hipFuncSetAttribute((const void *)k_affine_chain_tgt<G, false, false, B6, NWT_P>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     if (B6 && NF_CHAIN_DUAL) {
       NF_HIP(hipFuncSetAttribute((const void *)k_affine_chain_dual<G, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       NF_HIP(hipFuncSetAttribute((const void *)k_affine_chain_dual<G, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -2597,10 +2646,15 @@ static int launch_chain(nf_ctx *ctx, const nf_flow_desc *desc, bool inverse, flo
   const long ngroups = ((N + NF_TILE - 1) / NF_TILE + 7) / 8;
   long grid = ngroups < ctx->num_cu ? ngroups : ctx->num_cu;
   if (grid < 1) grid = 1;
-  ProfScope ps(ctx, "affine_chain");
+  const bool tgt = fused && fused->tkind != NF_TARGET_DIAGGAUSS;  // the other built-in targets: k_affine_chain_tgt, profiled under its own name
+  ProfScope ps(ctx, tgt ? "affine_chain_tgt" : "affine_chain");
   FusedArgs none{};
   none.trace = (long long *)ctx->trace;
-  if (fused && fused->stash)
+  if (tgt && fused->stash)
+    hipLaunchKernelGGL((k_affine_chain_tgt<G, true, SLIM, B6, NWT_S>), dim3((unsigned)grid), dim3(64 * NWT_S), lds, ctx->stream, a, xt, *fused);
+  else if (tgt)
+    hipLaunchKernelGGL((k_affine_chain_tgt<G, false, false, B6, NWT_P>), dim3((unsigned)grid), dim3(64 * NWT_P), lds, ctx->stream, a, xt, *fused);
+  else if (fused && fused->stash)
     hipLaunchKernelGGL((k_affine_chain<G, false, true, true, SLIM, B6>), dim3((unsigned)grid), dim3(512), lds, ctx->stream, a, xt, ladj, *fused);
   else if (fused)
     hipLaunchKernelGGL((k_affine_chain<G, false, true, false, false, B6>), dim3((unsigned)grid), dim3(512), lds, ctx->stream, a, xt, ladj, *fused);
@@ -2635,15 +2689,19 @@ long nf_affine_chain_grid(nf_ctx *ctx, long N) {
   return grid < 1 ? 1 : grid;
 }
 
-// base draws + whole chain forward + diagonal-Gaussian target + ELBO partial sums in one launch
+// base draws + whole chain forward + built-in target + ELBO partial sums in one launch
 // (packed images must be current).  yt <- flow output (tiled), gt <- gscale * grad log p(y) (or null),
-// partial[nf_affine_chain_grid] <- sums of pscale * elbo_j.
+// partial[nf_affine_chain_grid] <- sums of pscale * elbo_j.  The diagonal Gaussian runs k_affine_chain<FUSED>, the other
+// four kinds k_affine_chain_tgt; WarpedGauss / Cross with d != 2 and a diagonal Gaussian without parameters are refused here.
 int nf_affine_chain_elbo(nf_ctx *ctx, const nf_flow_desc *desc, long N, uint64_t seed, uint64_t off, uint32_t stream,
-                         const float *mu, const float *var, float *yt, float *gt, double gscale, double *partial,
+                         const nf_target *target, float *yt, float *gt, double gscale, double *partial,
                          double pscale, float *stash, const uint32_t *stream_ptr) {
   const int size = geo_size(desc);
   if (!size || !ctx->wimg) return NF_ERR_UNSUPPORTED;
+  NF_TRY(nf_target_check(target, desc->d));
+  const float *mu = (const float *)target->p0, *var = (const float *)target->p1;
   FusedArgs fa;
+  fa.tkind = target->kind; fa.ts0 = (float)target->s0; fa.ts1 = (float)target->s1;
   fa.stash = stash;
   fa.trace = (long long *)ctx->trace;
   fa.stream_ptr = stream_ptr;

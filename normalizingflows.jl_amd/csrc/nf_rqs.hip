@@ -36,6 +36,9 @@
 #define RQS6_MFMA_W(a, b, c) nf_mfma_bf16(a, b, c)
 #define RQS6_SETTLE(c) ((void)0)
 #include "nf_philox.h"
+#include "nf_target_epilogue.h"
+
+int nf_target_check(const nf_target *t, int d);  // nf_elementwise.hip
 
 template <int MB_, int H1B_, int H2B_, int K_, int NCH_, int QCH_ = 2>
 struct RqsGeo {
@@ -433,6 +436,9 @@ struct RqsFusedArgs {
   float gscale;
   double *partial;        // [gridDim.x] out
   double pscale;
+  const uint32_t *stream_ptr;  // non-null: the Philox stream id is read from device memory (hipGraph replay of the step)
+  int tkind;              // k_rqs_chain_tgt: NF_TARGET_BANANA / FUNNEL / WARPED / CROSS and the target's two scalars
+  float ts0, ts1;
 };
 
 // LDS map of the chain kernel, in floats: the weight area, then (FUSED) the target parameters and the per-wave sums.
@@ -450,8 +456,11 @@ struct RqsChainLds {
   static constexpr int WAREA = B6 ? 2 * SMALL + 4 * F_U4 : 2 * G::SIZE;
   static constexpr size_t BYTES = (size_t)(WAREA + 2 * 64 * G::CB + 2) * sizeof(float) + 8 * sizeof(double);
 };
-template <class G, bool INVERSE, bool FUSED = false, bool B6 = false>
-__global__ __launch_bounds__(512) void k_rqs_chain(RqsChainArgs a, float *xt, float *__restrict__ ladj, RqsFusedArgs fa) {
+// TGT != 0 (the body of k_rqs_chain_tgt, FUSED forward only; a set of NF_TGT_* bits): the epilogue evaluates one of the other
+// four built-in targets (fa.tkind, nf_target_epilogue.h) instead of the diagonal Gaussian.  Everything else is the same code.
+template <class G, bool INVERSE, bool FUSED, bool B6, int TGT, int NW>
+__device__ __forceinline__ void rqs_chain_body(RqsChainArgs a, float *xt, float *__restrict__ ladj, RqsFusedArgs fa) {
+  static_assert(!TGT || (FUSED && !INVERSE), "the target switch belongs to the fused ELBO forward");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   using CL = RqsChainLds<G, B6>;
   constexpr bool FKL = FUSED && INVERSE;  // forward-KL mode; FUSED && !INVERSE is the ELBO forward
@@ -460,7 +469,7 @@ __global__ __launch_bounds__(512) void k_rqs_chain(RqsChainArgs a, float *xt, fl
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, hi = lane >> 5;
   const long ntiles = (a.N + NF_TILE - 1) / NF_TILE;
-  const long ngroups = (ntiles + 7) / 8;
+  const long ngroups = (ntiles + NW - 1) / NW;
   auto coupling_at = [&](int s) { return INVERSE ? s : a.ncoup - 1 - s; };
   // global -> LDS by DMA (buffer_load ... lds), 1 KB pieces dealt round-robin to the eight waves; complete at the issuing wave's
   // next vmcnt(0) + a workgroup barrier
@@ -468,7 +477,7 @@ __global__ __launch_bounds__(512) void k_rqs_chain(RqsChainArgs a, float *xt, fl
   auto dma = [&](float *dst, const void *src, int nbytes) {
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(src), 0, nbytes, 0x00020000);
     const int np = (nbytes + 1023) / 1024;
-    for (int p = wave; p < np; p += 8)
+    for (int p = wave; p < np; p += NW)
       if (p * 1024 + lane * 16 < nbytes)  // the last piece may be partial: its idle lanes must not write
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void_t *)(dst + p * 256), 16, lane * 16, p * 1024, 0, 0);
   };
@@ -483,14 +492,14 @@ __global__ __launch_bounds__(512) void k_rqs_chain(RqsChainArgs a, float *xt, fl
   } else {
     const float4 *src = reinterpret_cast<const float4 *>(a.wimg + (long)coupling_at(0) * G::SIZE);
     float4 *dst = reinterpret_cast<float4 *>(lds);
-    for (int i = tid; i < NV4; i += 512) dst[i] = src[i];
+    for (int i = tid; i < NV4; i += 64 * NW) dst[i] = src[i];
   }
   // FUSED: target parameters by feature, zero padded: tmu[f], tiv[f] = 1/var[f]; tc0 = d log 2pi + sum log var
   constexpr int TP = 64 * G::CB;
   float *tmu = lds + CL::WAREA, *tiv = tmu + TP, *tc0 = tiv + TP;
   double *wsum = reinterpret_cast<double *>(tc0 + 2);  // [8] per-wave partial sums (G::SIZE and TP are even)
-  if (FUSED && !FKL) {
-    for (int i = tid; i < TP; i += 512) {
+  if (FUSED && !FKL && !TGT) {
+    for (int i = tid; i < TP; i += 64 * NW) {
       tmu[i] = i < a.d ? fa.mu[i] : 0.f;
       tiv[i] = i < a.d ? 1.f / fa.var[i] : 0.f;
     }
@@ -499,6 +508,12 @@ __global__ __launch_bounds__(512) void k_rqs_chain(RqsChainArgs a, float *xt, fl
       for (int i = 0; i < a.d; ++i) c += logf(fa.var[i]);
       tc0[0] = c;
     }
+  }
+  // the Philox stream id: a kernel argument, or read from device memory (the graph-replayable step) -- ONCE, here: nothing in
+  // this launch writes the counter, and read inside the tile loop it costs the K = 8 kernel twelve registers and 28 bytes of scratch
+  uint32_t pstream = fa.stream;
+  if constexpr (FUSED && !FKL) {
+    if (fa.stream_ptr) pstream = __builtin_amdgcn_readfirstlane(*fa.stream_ptr);
   }
   double wg_total = 0.0;
   __syncthreads();
@@ -511,7 +526,7 @@ __global__ __launch_bounds__(512) void k_rqs_chain(RqsChainArgs a, float *xt, fl
       a.trace[64 + 28 * (int)((grp - blockIdx.x) / gridDim.x)] = clock64();
     }
 #endif
-    const long tile = grp * 8 + wave;
+    const long tile = grp * NW + wave;
     const bool live = tile < ntiles;
     const long tl = live ? tile : 0;
     const long j = tl * NF_TILE + l31;
@@ -559,7 +574,7 @@ __global__ __launch_bounds__(512) void k_rqs_chain(RqsChainArgs a, float *xt, fl
 #pragma unroll
           for (int h = 0; h < 2; ++h) {
             const int g = base / 4 + h;
-            U4 c = {(uint32_t)gj, (uint32_t)(gj >> 32), (uint32_t)g, fa.stream};
+            U4 c = {(uint32_t)gj, (uint32_t)(gj >> 32), (uint32_t)g, pstream};
             const U4 rr = philox4x32_10(c, fa.k0, fa.k1);
             float z[4];
             box_muller<float>(rr.x, rr.y, z[0], z[1]);
@@ -659,12 +674,33 @@ __global__ __launch_bounds__(512) void k_rqs_chain(RqsChainArgs a, float *xt, fl
       __syncthreads();
       if (tid == 0) {
         double sgrp = 0.0;
-        for (int w = 0; w < 8; ++w) sgrp += wsum[w];
+        for (int w = 0; w < NW; ++w) sgrp += wsum[w];
         wg_total += sgrp;
       }
       __syncthreads();
     }
-    if (FUSED && !FKL) {
+    if constexpr (TGT != 0) {
+      // elbo_j = log p(y_j) - log q0(x_j) + ladj_j ;  ybar = gscale * grad log p(y), p one of Banana / Funnel / WarpedGauss / Cross
+      const TileIO gio = make_tile_io(fa.gt ? fa.gt : xt, tl, a.d, l31, hi);
+      nf_tile_isolate<G::CB>(E, O);
+      const float logp = nf_tile_target<G::CB, TGT>(fa.tkind, E, O, a.d, fa.ts0, fa.ts1, l31, hi, gio, fa.gt && live, valid, fa.gscale);
+      zz += __shfl_xor(zz, 32);
+      const float logq = (float)(-0.5 * 1.8378770664093453 * a.d) - 0.5f * zz;
+      const float e = logp - logq + lsum;
+      double contrib = 0.0;
+      if (hi == 0 && valid) contrib = fa.pscale * (double)e;
+#pragma unroll
+      for (int sft = 16; sft >= 1; sft >>= 1) contrib += __shfl_xor(contrib, sft);  // lanes 0..31 carry the terms
+      if (lane == 0) wsum[wave] = contrib;
+      __syncthreads();
+      if (tid == 0) {
+        double sgrp = 0.0;
+        for (int w = 0; w < NW; ++w) sgrp += wsum[w];
+        wg_total += sgrp;
+      }
+      __syncthreads();
+    }
+    if (FUSED && !FKL && !TGT) {
       // elbo_j = log p(y_j) - log q0(x_j) + ladj_j ;  ybar = gscale * grad log p(y)
       const TileIO gio = make_tile_io(fa.gt ? fa.gt : xt, tl, a.d, l31, hi);
       float t = 0.f;
@@ -700,7 +736,7 @@ __global__ __launch_bounds__(512) void k_rqs_chain(RqsChainArgs a, float *xt, fl
       __syncthreads();
       if (tid == 0) {
         double sgrp = 0.0;
-        for (int w = 0; w < 8; ++w) sgrp += wsum[w];
+        for (int w = 0; w < NW; ++w) sgrp += wsum[w];
         wg_total += sgrp;
       }
       __syncthreads();
@@ -708,6 +744,17 @@ __global__ __launch_bounds__(512) void k_rqs_chain(RqsChainArgs a, float *xt, fl
     RC_STAMP(27);
   }
   if (FUSED && tid == 0) fa.partial[blockIdx.x] = wg_total;
+}
+template <class G, bool INVERSE, bool FUSED = false, bool B6 = false>
+__global__ __launch_bounds__(512) void k_rqs_chain(RqsChainArgs a, float *xt, float *__restrict__ ladj, RqsFusedArgs fa) {
+  rqs_chain_body<G, INVERSE, FUSED, B6, 0, 8>(a, xt, ladj, fa);
+}
+// The fused ELBO forward for the Banana, Funnel, WarpedGauss and Cross targets: k_rqs_chain<G, false, true, B6>'s draws, chain
+// and tape with the target switch as its epilogue.  One instantiation per set of kinds (TGT): Banana + Funnel, and the two
+// two-dimensional kinds, whose sinf / cosf / atan2f cost ten registers; NW: wavefronts per workgroup, see rqs_tgt_nw.
+template <class G, bool B6, int TGT, int NW>
+__global__ __launch_bounds__(64 * NW) void k_rqs_chain_tgt(RqsChainArgs a, float *xt, RqsFusedArgs fa) {
+  rqs_chain_body<G, false, true, B6, TGT, NW>(a, xt, nullptr, fa);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2053,6 +2100,36 @@ bool nf_rqs_chain_fkl_ok(const nf_flow_desc *desc) {
   const int id = rqs_geo_id(desc);
   return id == 1 || id == 2;
 }
+// Wavefronts per workgroup of k_rqs_chain_tgt<G, B6, TGT>: eight (two per SIMD, 256 registers each) where the instantiation
+// fits them without scratch, four (one per SIMD, 512 registers) where it does not -- decided by tools/kernel_resources.py,
+// held by tests/test_elbo_targets_cpu.py.  At eight: K = 10, d <= 16 (231 / 241 registers) and K = 8 with the six-term output
+// layer (242 / 252: the default of cfg-3-like flows) fit; K = 8 with the fp32 output layer (NF_RQS_FWD_FP32: 208 bytes of
+// scratch; its diagonal-Gaussian kernel carries 152) and K = 10, d <= 32 (708 bytes; 624) do not.  The grid and the partial
+// sums do not depend on NW (the tile-group loop strides).
+template <class G, bool B6, int TGT>
+constexpr int rqs_tgt_nw() {
+  return (std::is_same<G, GeoK10>::value || (std::is_same<G, GeoK8>::value && B6)) ? 8 : 4;
+}
+template <class G, bool B6, int TGT>
+static int launch_rqs_tgt_set(nf_ctx *ctx, const RqsChainArgs &a, float *xt, const RqsFusedArgs &fa, long grid, size_t lds) {
+  constexpr int NW = rqs_tgt_nw<G, B6, TGT>();
+  static AttrOnce attr_once;  // once per device
+  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
+    NF_HIP(hipFuncSetAttribute((const void *)k_rqs_chain_tgt<G, B6, TGT, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return NF_OK;
+  }));
+  hipLaunchKernelGGL((k_rqs_chain_tgt<G, B6, TGT, NW>), dim3((unsigned)grid), dim3(64 * NW), lds, ctx->stream, a, xt, fa);
+  return (int)hipGetLastError();
+}
+// one instantiation per set of kinds: Banana, Funnel | the two-dimensional kinds
+template <class G, bool B6>
+static int launch_rqs_tgt(nf_ctx *ctx, const RqsChainArgs &a, float *xt, const RqsFusedArgs &fa, long grid, size_t lds) {
+  switch (fa.tkind) {
+    case NF_TARGET_BANANA:
+    case NF_TARGET_FUNNEL: return launch_rqs_tgt_set<G, B6, NF_TGT_BANANA | NF_TGT_FUNNEL>(ctx, a, xt, fa, grid, lds);
+    default: return launch_rqs_tgt_set<G, B6, NF_TGT_WARPED | NF_TGT_CROSS>(ctx, a, xt, fa, grid, lds);
+  }
+}
 template <class G>
 static int launch_rqs_chain(nf_ctx *ctx, const nf_flow_desc *desc, bool inverse, float *xt, long N, float *ladj,
                             int k_only, const RqsFusedArgs *fused = nullptr, void *tape = nullptr) {
@@ -2066,6 +2143,8 @@ static int launch_rqs_chain(nf_ctx *ctx, const nf_flow_desc *desc, bool inverse,
   long grid = ngroups < ctx->num_cu ? ngroups : ctx->num_cu;
   if (grid < 1) grid = 1;
   RqsFusedArgs none{};
+  // the ELBO forward for the built-in targets other than the diagonal Gaussian: k_rqs_chain_tgt, profiled under its own name
+  const bool tgt = fused && !inverse && fused->tkind != NF_TARGET_DIAGGAUSS;
   // whole-chain launches of the K = 8 geometry (cfg 3): the output layer as six-term bf16 products from the triple images
   if constexpr (std::is_same<G, GeoK8>::value) {
     if (k_only < 0 && rqs_fwd_b6()) {
@@ -2080,8 +2159,10 @@ static int launch_rqs_chain(nf_ctx *ctx, const nf_flow_desc *desc, bool inverse,
       }));
       NF_TRY(rqs_b6_refresh<G>(ctx, desc));
       a.wimg6 = (const nf_u32x4 *)((const char *)ctx->wimg + rqs_fp32_bytes(desc));
-      ProfScope ps(ctx, fused && inverse ? "rqs_chain_fkl" : "rqs_chain");
-      if (fused && inverse)  // forward-KL training step (nf_rqs_chain_fkl)
+      ProfScope ps(ctx, tgt ? "rqs_chain_tgt" : fused && inverse ? "rqs_chain_fkl" : "rqs_chain");
+      if (tgt)
+        return launch_rqs_tgt<G, true>(ctx, a, xt, *fused, grid, lds6);
+      else if (fused && inverse)  // forward-KL training step (nf_rqs_chain_fkl)
         hipLaunchKernelGGL((k_rqs_chain<G, true, true, true>), dim3((unsigned)grid), dim3(512), lds6, ctx->stream, a, xt, ladj, *fused);
       else if (fused)
         hipLaunchKernelGGL((k_rqs_chain<G, false, true, true>), dim3((unsigned)grid), dim3(512), lds6, ctx->stream, a, xt, ladj, *fused);
@@ -2103,8 +2184,10 @@ static int launch_rqs_chain(nf_ctx *ctx, const nf_flow_desc *desc, bool inverse,
       NF_HIP(hipFuncSetAttribute((const void *)k_rqs_chain<G, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     return NF_OK;
   }));
-  ProfScope ps(ctx, fused && inverse ? "rqs_chain_fkl" : "rqs_chain");
-  if (fused && inverse) {
+  ProfScope ps(ctx, tgt ? "rqs_chain_tgt" : fused && inverse ? "rqs_chain_fkl" : "rqs_chain");
+  if (tgt)
+    return launch_rqs_tgt<G, false>(ctx, a, xt, *fused, grid, lds);
+  else if (fused && inverse) {
     if constexpr (rqs_fkl_built<G>)
       hipLaunchKernelGGL((k_rqs_chain<G, true, true>), dim3((unsigned)grid), dim3(512), lds, ctx->stream, a, xt, ladj, *fused);
     else
@@ -2124,17 +2207,21 @@ long nf_rqs_chain_grid(nf_ctx *ctx, long N) {
   return grid < 1 ? 1 : grid;
 }
 
-// base draws + whole chain forward + diagonal-Gaussian target + ELBO partial sums in one launch (packed images must
+// base draws + whole chain forward + built-in target + ELBO partial sums in one launch (packed images must
 // be current).  yt <- flow output (tiled), gt <- gscale * grad log p(y) (or null), partial[nf_rqs_chain_grid] <- sums
-// of pscale * elbo_j.
+// of pscale * elbo_j.  The diagonal Gaussian runs k_rqs_chain<FUSED>, the other four kinds k_rqs_chain_tgt; stream_ptr
+// (optional): the Philox stream id in device memory (the graph-replayable step).
 int nf_rqs_chain_elbo(nf_ctx *ctx, const nf_flow_desc *desc, long N, uint64_t seed, uint64_t off, uint32_t stream,
-                      const float *mu, const float *var, float *yt, float *gt, double gscale, double *partial,
-                      double pscale, void *tape) {
+                      const nf_target *target, float *yt, float *gt, double gscale, double *partial,
+                      double pscale, void *tape, const uint32_t *stream_ptr) {
   const int id = rqs_geo_id(desc);
   if (!id || !ctx->wimg) return NF_ERR_UNSUPPORTED;
+  NF_TRY(nf_target_check(target, desc->d));
   RqsFusedArgs fa;
   fa.k0 = (uint32_t)seed; fa.k1 = (uint32_t)(seed >> 32); fa.stream = stream; fa.off = off;
-  fa.mu = mu; fa.var = var; fa.gt = gt; fa.gscale = (float)gscale; fa.partial = partial; fa.pscale = pscale;
+  fa.stream_ptr = stream_ptr;
+  fa.tkind = target->kind; fa.ts0 = (float)target->s0; fa.ts1 = (float)target->s1;
+  fa.mu = (const float *)target->p0; fa.var = (const float *)target->p1; fa.gt = gt; fa.gscale = (float)gscale; fa.partial = partial; fa.pscale = pscale;
 #define RQS_CALL(G) launch_rqs_chain<G>(ctx, desc, false, yt, N, nullptr, -1, &fa, tape)
   return RQS_DISPATCH(id, RQS_CALL);
 #undef RQS_CALL

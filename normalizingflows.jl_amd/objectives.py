@@ -390,7 +390,9 @@ def _optimize_fused(flow: Flow, theta0: torch.Tensor, reconstruct, rng: PhiloxRN
                     optimiser: Adam, show_progress: bool = False, callback=None, hasconverged=None, all_reduce=None,
                     state=None):
     """The loop of `optimize` (src/optimize.jl:85-104) with each iteration ONE library call: nf_elbo_step = draws,
-    forward, reverse pass, Adam, norm(g) (three launches for the LDS-resident RealNVP shapes, what bench.py times).  The
+    forward, reverse pass, Adam, norm(g) (three launches for the LDS-resident RealNVP shapes, what bench.py times; fused
+    forward + one reverse launch per coupling + fused epilogue for LDS-resident spline couplings -- with ANY built-in target:
+    DiagGaussTarget, BananaTarget, FunnelTarget and, at d = 2, WarpedGaussTarget and CrossTarget).  The
     loop owns theta between steps, so it opts in to the library's packed-weight cache (nf_ctx_set_weight_cache) and out
     again on return; a user `hasconverged` sees the live theta and is followed by nf_ctx_weights_changed.  Same numbers
     as `optimize` over value_and_gradient + update (tests/test_gpu_tape.py)."""
@@ -436,7 +438,8 @@ def train_flow(*args, max_iters: int = 1000, optimiser: Adam = None, ADbackend=N
 
     `ADbackend` is accepted for signature compatibility; gradients come from the library's
     hand-derived reverse pass (the role a custom ADTypes backend plays in the reference).  Reverse-KL runs on a
-    built-in target with Adam go through nf_elbo_step, one library call per iteration (`_optimize_fused`), forward-KL
+    built-in target (the diagonal Gaussian, Banana, Funnel, WarpedGauss, Cross: the demos' targets take the same fused
+    kernels as the benchmark's) with Adam go through nf_elbo_step, one library call per iteration (`_optimize_fused`), forward-KL
     runs with Adam through nf_loglikelihood_step (`_optimize_fused_fkl`); everything else through `optimize` over
     value_and_gradient + update."""
     if isinstance(args[0], PhiloxRNG):

@@ -54,7 +54,7 @@ size_t nf_affine_stash_floats(const nf_flow_desc *desc, long N);
 bool nf_affine_stash_pays(const nf_flow_desc *desc);
 bool nf_affine_fused_ok(const nf_flow_desc *desc);
 int nf_affine_bwd_stashed(nf_ctx *, const nf_flow_desc *, float *stash, float *ybar, const float *lbar, float lbar_const, long N,
-                          float *slab, long slab_stride, int grid, bool inv_dir = false);
+                          float *slab, long slab_stride, int grid, bool inv_dir = false, bool no_xbar = false);
 long nf_affine_slab_floats(const nf_flow_desc *desc);
 int nf_affine_reduce_slabs(nf_ctx *, const nf_flow_desc *, const float *slab, int nslab, float *g,
                            const double *lpart = nullptr, int nlpart = 0, float *lout = nullptr);
@@ -1265,7 +1265,7 @@ extern "C" int nf_loglikelihood_value_and_grad(nf_ctx *ctx, const nf_flow_desc *
         NF_TRY(nf_launch_target_tiled(ctx, &q0, desc->d, nc, zt + o * desc->d, nullptr, (const float *)ladj + o, gt + o * desc->d, -inv,
                                       nullptr, partial + npart, -inv));
         NF_TRY(nf_affine_bwd_stashed(ctx, desc, stash, gt + o * desc->d, nullptr, (float)(-inv), nc, (float *)slab + nslab * stride,
-                                     stride, gc, true));
+                                     stride, gc, true, true));  // (a training step: nobody reads the cotangent of ys)
         nslab += gc;
         npart += nf_target_tiled_nblocks(nc);
       }
@@ -1788,10 +1788,12 @@ extern "C" int nf_elbo_value_and_grad(nf_ctx *ctx, const nf_flow_desc *desc, con
       for (long o = 0; o < N; o += stash_nc) {
         const long nc = N - o < stash_nc ? N - o : stash_nc;
         const int gc = coupling_bwd_grid(ctx, desc, nc);
-        NF_TRY(fused_chain_elbo(ctx, desc, target, nc, seed, sample_offset + (uint64_t)o, stream_id, xt + o * desc->d,
+        // (y itself is not written: the stashed reverse pass reads gt and the stash, and nothing else follows; nor is the
+        // cotangent of the draws, which a training step does not read)
+        NF_TRY(fused_chain_elbo(ctx, desc, target, nc, seed, sample_offset + (uint64_t)o, stream_id, nullptr,
                                 gt + o * desc->d, -inv, partial + npart, -inv, stash));
         NF_TRY(nf_affine_bwd_stashed(ctx, desc, stash, gt + o * desc->d, nullptr, (float)(-inv), nc,
-                                     (float *)slab + nslab * stride, stride, gc));
+                                     (float *)slab + nslab * stride, stride, gc, false, true));
         nslab += gc;
         npart += nf_affine_chain_grid(ctx, nc);
       }
@@ -1846,7 +1848,7 @@ extern "C" int nf_elbo_value_and_grad(nf_ctx *ctx, const nf_flow_desc *desc, con
         NF_TRY(nf_launch_target_tiled(ctx, target, desc->d, nc, xt + o * desc->d, (const float *)logq + o, (const float *)ladj + o,
                                       gt + o * desc->d, -inv, nullptr, partial + npart, -inv));
         NF_TRY(nf_affine_bwd_stashed(ctx, desc, stash, gt + o * desc->d, nullptr, (float)(-inv), nc,
-                                     (float *)slab + nslab * stride, stride, gc));
+                                     (float *)slab + nslab * stride, stride, gc, false, true));
         nslab += gc;
         npart += nf_target_tiled_nblocks(nc);
       }
@@ -1978,7 +1980,7 @@ static size_t step_fused_need(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
   const long nb = nf_target_tiled_nblocks(N);
   const long nb_alloc = nb < ctx->num_cu ? ctx->num_cu : nb;
   const long snc = affine_stash_chunk(ctx, desc, N);
-  return 2 * carve_bytes(te * 4) + carve_bytes((size_t)nb_alloc * 8) +
+  return carve_bytes(te * 4) + carve_bytes((size_t)nb_alloc * 8) +
          carve_bytes(chunked_slab_floats(ctx, desc, N, snc, coupling_slab_floats(ctx, desc, N)) * 4) +
          carve_bytes(snc ? affine_stash_bytes(ctx, desc, snc) : 0) + carve_bytes((size_t)nf_affine_epilogue_blocks(desc) * 8);
 }
@@ -2000,8 +2002,7 @@ static int elbo_step_fused(nf_ctx *ctx, const nf_flow_desc *desc, const nf_targe
   const long eblocks = nf_affine_epilogue_blocks(desc);
   NF_TRY(nf_ws_reserve(ctx, step_fused_need(ctx, desc, N)));
   Carver cv(ctx->ws);
-  float *xt = cv.take<float>(te);
-  float *gt = cv.take<float>(te);
+  float *gt = cv.take<float>(te);  // (no buffer for y: the forward keeps it in registers, the reverse pass reads gt and the stash)
   double *partial = cv.take<double>(nb_alloc);
   float *slab = cv.take<float>(slabf);
   float *stash = cv.take<float>(stash_b / 4);
@@ -2020,8 +2021,9 @@ static int elbo_step_fused(nf_ctx *ctx, const nf_flow_desc *desc, const nf_targe
     const long nc = N - o < stash_nc ? N - o : stash_nc;
     const int gc = coupling_bwd_grid(ctx, desc, nc);
     NF_TRY(nf_affine_chain_elbo(ctx, desc, nc, seed, off0 + (uint64_t)o, step_val, target,
-                                xt + o * desc->d, gt + o * desc->d, -inv, partial + npart, -inv, stash, step_ptr));
-    NF_TRY(nf_affine_bwd_stashed(ctx, desc, stash, gt + o * desc->d, nullptr, (float)(-inv), nc, slab + nslab * stride, stride, gc));
+                                nullptr, gt + o * desc->d, -inv, partial + npart, -inv, stash, step_ptr));
+    NF_TRY(nf_affine_bwd_stashed(ctx, desc, stash, gt + o * desc->d, nullptr, (float)(-inv), nc, slab + nslab * stride, stride, gc,
+                                 false, true));
     nslab += gc;
     npart += nf_affine_chain_grid(ctx, nc);
   }
@@ -2322,7 +2324,8 @@ static int fkl_step_fused(nf_ctx *ctx, const nf_flow_desc *desc, float *theta, f
     const long nc = N - o < stash_nc ? N - o : stash_nc;
     const int gc = coupling_bwd_grid(ctx, desc, nc);
     NF_TRY(nf_affine_chain_fkl(ctx, desc, ys + o * desc->d, nc, gt + o * desc->d, -inv, partial + npart, -inv, stash));
-    NF_TRY(nf_affine_bwd_stashed(ctx, desc, stash, gt + o * desc->d, nullptr, (float)(-inv), nc, slab + nslab * stride, stride, gc, true));
+    NF_TRY(nf_affine_bwd_stashed(ctx, desc, stash, gt + o * desc->d, nullptr, (float)(-inv), nc, slab + nslab * stride, stride, gc, true,
+                                 true));
     nslab += gc;
     npart += nf_affine_chain_grid(ctx, nc);
   }

@@ -11,6 +11,7 @@
 // the fp32 matrix pipe in registers (nf_mfma.h); weights of the coupling live in LDS.
 #include <cmath>
 #include <cstdlib>
+#include <type_traits>
 
 #include "nf_common.h"
 // A/B seams of this translation unit only (tools/ab_build.py): the split's subtractions / the leaky-ReLU slopes as scalar f32 instructions.
@@ -666,7 +667,9 @@ __device__ __forceinline__ void affine_chain_body(ChainArgs a, float *xt, float 
       }
     }
     if (live) {
-      if constexpr (!FKL) {
+      // the fused ELBO forward of a stashed training step is called with xt == nullptr: the reverse pass reads the stash and gt
+      // only, so the flow output stays in the registers (the epilogue below) -- as the forward-KL form's z always does
+      if (!FKL && (!(FUSED && STASH) || xt != nullptr)) {
 #pragma unroll
         for (int b = 0; b < G::CB; ++b)
 #pragma unroll
@@ -1251,6 +1254,8 @@ struct BwdAllArgs {
   long long *trace;
   int d, ncoup;
   long N;
+  int no_xbar;  // pair kernel: the caller does not read ybar after the launch (a training step), so the coupling processed last
+                // skips dX1 and its tile stores.  0 wherever the input cotangent is an output (nf_flow_bwd*, the tape pullbacks)
 };
 template <class G, bool FULL, bool INVD>
 __global__ __launch_bounds__(256, 1) void k_affine_bwd_all(BwdAllArgs aa, float *__restrict__ y, float *__restrict__ ybar,
@@ -1779,14 +1784,36 @@ struct BwdPairLds {
   static constexpr size_t BYTES = (size_t)FLOATS * sizeof(float);  // the fold at the end of a phase needs 4 images
 };
 
+// Cotangent residency (forward direction; the inverse direction, whose phase S runs first, parks nothing).  A pair owns the same
+// tiles in both phases of a coupling, and between the two the tile's cotangent used to make a round trip through memory: phase T
+// loaded both halves and stored conditioner half + g2t, phase S loaded both again.  For the first NF_PAIR_PARK tiles of a pair the
+// producer keeps them instead: phase T parks g2t (W1^T d1 of the t net) and, for the first NF_PAIR_PARK_G1 tiles, the transformed
+// half's cotangent, and does not touch the conditioner half at all; phase S builds d3 from the parked registers, asks for the
+// conditioner half behind B3, where only the closing stores need it, and stores (half + g2t) + g2s -- the two additions in the
+// order the round trip gave them, so the bits do not change.  The producer has the registers: the kernel is allocated 256 per wave
+// for the consumer's sake.  Tiles beyond the parked ones (more than two rounds) keep the round trip, in the body they always had.
+// 2 x 16 + 1 x 16 parked registers: with the second tile's g1 as well the unparked body (64 parked + its own early conditioner
+// half) no longer fits -- 56 / 80 bytes of scratch in the whole-batch / ragged forms (tests/test_cotangent_residency_cpu.py).
+#define NF_PAIR_PARK 2
+#define NF_PAIR_PARK_G1 1
+template <class G>
+struct PairPark {
+  f32x16 g1[NF_PAIR_PARK_G1][G::CB], g2[NF_PAIR_PARK][G::MB];
+};
+
 // FULL: d = 64 and N a multiple of the tile (no sample / feature masks).  INVD: reverse pass of the INVERSE coupling
 // (forward-KL training; algebra of bwd_tile_stashed: phase S first, the UV slot holds w1).  live: this pair has a tile in
 // this round of the workgroup's tile loop -- a pair without one only keeps the barrier count.
-template <class G, bool PHASE_S, bool FULL, bool INVD, bool SLIM, bool PB6 = false, bool DW6 = false>
+// SLOT: the tile's parked registers (< 0: none, the cotangent goes through memory as it always did -- the body is then the one
+// this kernel had before parking; the inverse direction has no other).  A template parameter, so that every body knows which
+// parked registers are live around it.  last: nobody reads this coupling's input cotangent (BwdAllArgs::no_xbar, coupling
+// processed last): no dX1 and no tile stores -- the closing ones behind one wave-uniform branch, phase S's x1bar through a
+// descriptor of extent 0, which the hardware drops, so that the tile's prologue stays free of branches.
+template <class G, bool PHASE_S, bool FULL, bool INVD, bool SLIM, bool PB6, bool DW6, int SLOT>
 __device__ __forceinline__ void pair_produce(const CouplingArgs &a, const float *__restrict__ img, float *__restrict__ sp,
-                                             StashFirst<G> &f, float *stash, int k, int ncoup, float *__restrict__ ybar,
-                                             const float *__restrict__ lbar, float lbar_const, long tile, long next_tile,
-                                             bool live, int l31, int hi, int par, long long *tr = nullptr) {
+                                             StashFirst<G> &f, PairPark<G> &pk, bool last, float *stash, int k, int ncoup,
+                                             float *__restrict__ ybar, const float *__restrict__ lbar, float lbar_const, long tile,
+                                             long next_tile, bool live, int l31, int hi, int par, long long *tr = nullptr) {
   using SG = StashGeo<G, SLIM>;
   using L = BwdPairLds<G, PB6, DW6>;
   char *bufa = reinterpret_cast<char *>(sp) + par * NF_PAIR_BUF, *bufb = reinterpret_cast<char *>(sp) + (par ^ 1) * NF_PAIR_BUF;  // DW6
@@ -1803,17 +1830,31 @@ __device__ __forceinline__ void pair_produce(const CouplingArgs &a, const float 
   const TileIO gio = make_tile_io(ybar, tile, a.d, l31, hi);
   const StashIO st = make_stash_io(stash, tile * ncoup + k, SG::SIZE, true, l31, hi);
   constexpr int nbase = SG::NET0 + (PHASE_S ? 0 : SG::NETSZ);
+  static_assert(!INVD || SLOT < 0, "the inverse direction parks nothing");
+  constexpr bool FIRST = PHASE_S == INVD;  // the coupling's first phase
+  constexpr bool parked = SLOT >= 0, parked1 = SLOT >= 0 && SLOT < NF_PAIR_PARK_G1;
+  constexpr int S2 = SLOT < 0 ? 0 : SLOT, S1 = parked1 ? SLOT : 0;
   f32x16 g1[G::CB];
+  if constexpr (FIRST || !parked1) {
 #pragma unroll
-  for (int b = 0; b < G::CB; ++b)
+    for (int b = 0; b < G::CB; ++b)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) g1[b][r] = tile_load(gio, tile_soff(b, r, a.par_t));
+      for (int r = 0; r < 16; ++r) g1[b][r] = tile_load(gio, tile_soff(b, r, a.par_t));
+  } else {
+#pragma unroll
+    for (int b = 0; b < G::CB; ++b) g1[b] = pk.g1[S1][b];
+  }
   const u32x4 mk = __builtin_amdgcn_raw_buffer_load_b128(st.rs, (hi * 32 + l31) * 16, (nbase + SG::MSK) * 4, 0);
   f32x16 gold[G::MB];
+  if constexpr (!parked) {
 #pragma unroll
-  for (int b = 0; b < G::MB; ++b)
+    for (int b = 0; b < G::MB; ++b)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) gold[b][r] = tile_load(gio, tile_soff(b, r, par_c));
+      for (int r = 0; r < 16; ++r) gold[b][r] = tile_load(gio, tile_soff(b, r, par_c));
+  }
+  TileIO gx = gio;  // phase S (forward direction): where x1bar goes -- nowhere for the last coupling of a training step
+  if constexpr (PHASE_S && !INVD)
+    gx.rs = __builtin_amdgcn_make_buffer_rsrc(ybar + tile * a.d * NF_TILE, 0, last ? 0 : a.d * NF_TILE * 4, 0x00020000);
   const float lb = valid ? (lbar ? lbar[FULL ? j : (j < a.N ? j : 0)] : lbar_const) : 0.f;
   f32x16 d3[G::CB];
 #pragma unroll
@@ -1826,14 +1867,18 @@ __device__ __forceinline__ void pair_produce(const CouplingArgs &a, const float 
         d3[b][r] = ok ? (INVD ? -gv : gv) : 0.f;  // T-bar = ybar1 (inverse: -v1bar)
       } else if (INVD) {
         const float sv = f.sv[b][r];
-        tile_store(gio, tile_soff(b, r, a.par_t), nf_fdiv(gv, nf_exp(sv)));  // v1bar
+        tile_store(gio, tile_soff(b, r, a.par_t), nf_fdiv(gv, nf_exp(sv)));  // v1bar (phase T's seed: stored by the last coupling, too)
         d3[b][r] = ok ? -(gv * f.uv[b][r] + lb) * (1.f - sv * sv) : 0.f;    // S-bar through tanh (uv = w1)
       } else {
         const float sv = f.sv[b][r];
-        tile_store(gio, tile_soff(b, r, a.par_t), gv * nf_exp(sv));        // x1bar
+        tile_store(gx, tile_soff(b, r, a.par_t), gv * nf_exp(sv));        // x1bar
         d3[b][r] = ok ? (gv * f.uv[b][r] + lb) * (1.f - sv * sv) : 0.f;  // S-bar through tanh
       }
     }
+  if constexpr (FIRST && parked1) {  // the bits the second phase would load: phase T never writes these slots
+#pragma unroll
+    for (int b = 0; b < G::CB; ++b) pk.g1[S1][b] = g1[b];
+  }
   SplitC<DW6 ? G::CB : 1> s3;
   if constexpr (DW6) {
     split_C<G::CB>(d3, s3);
@@ -1917,14 +1962,34 @@ __device__ __forceinline__ void pair_produce(const CouplingArgs &a, const float 
   __syncthreads();  // B3
   NF_TS_STAMP(6);
   if (PHASE_S && next_tile >= 0) stash_issue_first<G, SLIM>(f, stash, k, ncoup, next_tile, l31, hi);
+  if (last) {  // the input cotangent of the whole flow: not read by the training step that set no_xbar
+    NF_TS_STAMP(7);
+    return;
+  }
+  if constexpr (!FIRST && parked) {  // the conditioner half's cotangent, needed by the closing stores only: in flight behind the GEMM
+#pragma unroll
+    for (int b = 0; b < G::MB; ++b)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) gold[b][r] = tile_load(gio, tile_soff(b, r, par_c));
+  }
   f32x16 g2[G::MB];
   if constexpr (DW6) dense_bwd_x_b6s<G::MB, G::H1B>(wt + B6TGeo<G>::T1, s1, g2, l31, hi);
   else if constexpr (PB6) dense_bwd_x_b6<G::MB, G::H1B>(wt + B6TGeo<G>::T1, d1, g2, l31, hi);
   else dense_bwd_x<G::MB, G::H1B>(img + G::W1, d1, g2, l31, hi);
+  if constexpr (!parked) {
 #pragma unroll
-  for (int b = 0; b < G::MB; ++b)
+    for (int b = 0; b < G::MB; ++b)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) tile_store(gio, tile_soff(b, r, par_c), gold[b][r] + g2[b][r]);
+      for (int r = 0; r < 16; ++r) tile_store(gio, tile_soff(b, r, par_c), gold[b][r] + g2[b][r]);
+  } else if constexpr (FIRST) {
+#pragma unroll
+    for (int b = 0; b < G::MB; ++b) pk.g2[S2][b] = g2[b];
+  } else {
+#pragma unroll
+    for (int b = 0; b < G::MB; ++b)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) tile_store(gio, tile_soff(b, r, par_c), (gold[b][r] + pk.g2[S2][b][r]) + g2[b][r]);
+  }
   NF_TS_STAMP(7);
 }
 
@@ -2232,6 +2297,8 @@ __global__ __launch_bounds__(512) void k_affine_bwd_pair(BwdAllArgs aa, float *s
 #pragma unroll 1
     for (int step = 0; step < aa.ncoup; ++step) {
       const int k = INVD ? aa.ncoup - 1 - step : step;  // the inverse chain's reverse pass runs in execution order
+      const bool last = aa.no_xbar != 0 && step + 1 == aa.ncoup;
+      PairPark<G> pk;  // written in the coupling's first phase, read in its second
       CouplingArgs a;
       a.theta = nullptr;
       a.img_s = aa.wimg + (size_t)(2 * k) * G::SIZE;
@@ -2253,8 +2320,8 @@ __global__ __launch_bounds__(512) void k_affine_bwd_pair(BwdAllArgs aa, float *s
         NF_TSB(1);
         __syncthreads();
         NF_TSB(2);
-#pragma unroll 1
-        for (int it = 0; it < rounds; ++it) {
+        auto produce = [&](int it, auto slot) {
+          constexpr int SLOT = decltype(slot)::value;
           const long tile = tile0 + (long)it * tstride;
           const long nt = tile + tstride < ntiles ? tile + tstride : -1;
 #ifdef NF_KERNEL_TRACE  // tools/trace_bwd_pair.py: block 0, pair 0, first coupling; producer stamps [phase 16 + tile 8 + 0..7]
@@ -2262,9 +2329,19 @@ __global__ __launch_bounds__(512) void k_affine_bwd_pair(BwdAllArgs aa, float *s
 #else
           long long *tr = nullptr;
 #endif
-          if (!is_s) pair_produce<G, false, FULL, INVD, SLIM, PB6, DW6>(a, img, sp, f, stash, k, aa.ncoup, ybar, lbar, lbar_const, tile, nt, tile < ntiles, l31, hi, it & 1, tr);
-          else pair_produce<G, true, FULL, INVD, SLIM, PB6, DW6>(a, img, sp, f, stash, k, aa.ncoup, ybar, lbar, lbar_const, tile, nt, tile < ntiles, l31, hi, it & 1, tr);
+          if (!is_s) pair_produce<G, false, FULL, INVD, SLIM, PB6, DW6, SLOT>(a, img, sp, f, pk, last, stash, k, aa.ncoup, ybar, lbar, lbar_const, tile, nt, tile < ntiles, l31, hi, it & 1, tr);
+          else pair_produce<G, true, FULL, INVD, SLIM, PB6, DW6, SLOT>(a, img, sp, f, pk, last, stash, k, aa.ncoup, ybar, lbar, lbar_const, tile, nt, tile < ntiles, l31, hi, it & 1, tr);
+        };
+        // the first NF_PAIR_PARK rounds with their parked registers (one body per slot), the rest through memory
+        int it0 = 0;
+        if constexpr (!INVD) {
+          static_assert(NF_PAIR_PARK == 2, "one call per slot");
+          if (rounds > 0) produce(0, std::integral_constant<int, 0>{});
+          if (rounds > 1) produce(1, std::integral_constant<int, 1>{});
+          it0 = NF_PAIR_PARK;
         }
+#pragma unroll 1
+        for (int it = it0; it < rounds; ++it) produce(it, std::integral_constant<int, -1>{});
         NF_TSB(3);
         __syncthreads();  // every wave is done with the weight image and the delta tiles
         NF_TSB(4);
@@ -2690,7 +2767,8 @@ long nf_affine_chain_grid(nf_ctx *ctx, long N) {
 }
 
 // base draws + whole chain forward + built-in target + ELBO partial sums in one launch
-// (packed images must be current).  yt <- flow output (tiled), gt <- gscale * grad log p(y) (or null),
+// (packed images must be current).  yt <- flow output (tiled; may be null WITH a stash: the output is then not written, the
+// stashed reverse pass does not read it), gt <- gscale * grad log p(y) (or null),
 // partial[nf_affine_chain_grid] <- sums of pscale * elbo_j.  The diagonal Gaussian runs k_affine_chain<FUSED>, the other
 // four kinds k_affine_chain_tgt; WarpedGauss / Cross with d != 2 and a diagonal Gaussian without parameters are refused here.
 int nf_affine_chain_elbo(nf_ctx *ctx, const nf_flow_desc *desc, long N, uint64_t seed, uint64_t off, uint32_t stream,
@@ -2698,6 +2776,7 @@ int nf_affine_chain_elbo(nf_ctx *ctx, const nf_flow_desc *desc, long N, uint64_t
                          double pscale, float *stash, const uint32_t *stream_ptr) {
   const int size = geo_size(desc);
   if (!size || !ctx->wimg) return NF_ERR_UNSUPPORTED;
+  if (!yt && !stash) return NF_ERR_ARG;
   NF_TRY(nf_target_check(target, desc->d));
   const float *mu = (const float *)target->p0, *var = (const float *)target->p1;
   FusedArgs fa;
@@ -2834,6 +2913,7 @@ int nf_affine_bwd_all(nf_ctx *ctx, const nf_flow_desc *desc, float *y, float *yb
   aa.d = desc->d;
   aa.ncoup = 2 * desc->nlayers;
   aa.N = N;
+  aa.no_xbar = 0;
   const bool h64 = size != NetGeo<1, 1, 1, 1>::SIZE;
   const bool full = desc->d == 64 && N % NF_TILE == 0;  // both partitions fill their 32-row block
   if (inv_dir) {
@@ -2920,9 +3000,10 @@ static int launch_bwd_pair(nf_ctx *ctx, const nf_flow_desc *desc, const BwdAllAr
 }
 
 // reverse pass of all couplings from the stash nf_affine_chain_elbo(..., stash) left (same slab layout as
-// nf_affine_bwd_all; ybar: cotangent of the flow output on entry, of the flow input on exit)
+// nf_affine_bwd_all; ybar: cotangent of the flow output on entry, of the flow input on exit -- unless no_xbar: the caller,
+// a training step, does not read it, and the two-wave kernel then leaves the last coupling's share of it unwritten)
 int nf_affine_bwd_stashed(nf_ctx *ctx, const nf_flow_desc *desc, float *stash, float *ybar, const float *lbar, float lbar_const,
-                          long N, float *slab, long slab_stride, int grid, bool inv_dir) {
+                          long N, float *slab, long slab_stride, int grid, bool inv_dir, bool no_xbar) {
   const int size = geo_size(desc);
   if (!size || !ctx->wimg || desc->n_hidden != 2 || !stash) return NF_ERR_UNSUPPORTED;
   BwdAllArgs aa;
@@ -2932,6 +3013,7 @@ int nf_affine_bwd_stashed(nf_ctx *ctx, const nf_flow_desc *desc, float *stash, f
   aa.d = desc->d;
   aa.ncoup = 2 * desc->nlayers;
   aa.N = N;
+  aa.no_xbar = no_xbar ? 1 : 0;
   const bool h64 = size != NetGeo<1, 1, 1, 1>::SIZE;
   const bool full = desc->d == 64 && N % NF_TILE == 0;
   // hidden 33-64: the two-waves-per-tile kernel (both directions, ragged batches and d < 64 included)

@@ -148,11 +148,11 @@ int nf_hf_bwd_inv(nf_ctx *, const nf_flow_desc *, const void *theta, const void 
                   long N, void *gtheta_out, void *ws);
 
 // ---- helpers -----------------------------------------------------------------------------
+// Every entry point's intermediates are ONE layout: a struct whose constructor takes its buffers from a Carver.  It runs over a
+// measuring Carver for nf_ws_reserve, then over ctx->ws (ws_carve); ws_need_bound() is the maximum of the same layouts.
 static size_t ws_need_bound(nf_ctx *ctx, const nf_flow_desc *desc, long N);
-static size_t flow_bwd_need(nf_ctx *ctx, const nf_flow_desc *desc, long N);
-static size_t step_fused_need(nf_ctx *ctx, const nf_flow_desc *desc, long N);
-static size_t vg_composite_need(nf_ctx *ctx, const nf_flow_desc *desc, long N);
-static size_t base_extra_bytes(const nf_flow_desc *desc, long N);
+static size_t composite_inner_need(nf_ctx *ctx, const nf_flow_desc *desc, long N);
+static long seg_theta_off(const nf_flow_desc *desc, int s);
 static inline size_t esize(int dtype) { return dtype == NF_DTYPE_F64 ? 8 : 4; }
 
 // general MvNormal(mu, Sigma) base of a flow, or nullptr for the standard normal
@@ -465,27 +465,44 @@ static int read_scalar(nf_ctx *ctx, const double *dev, double *host) {
 }
 
 // buffers and helpers of the general-base wrappers (defined with the objectives below)
-struct BaseBufs {
-  char *x, *corr, *tmp, *z;
-  double *partial, *result;
-  long nb;
-};
-static int base_bufs(nf_ctx *ctx, const nf_flow_desc *desc, const nf_flow_desc *inner, long N, BaseBufs *bb) {
-  const nf_base *b = flow_base(desc);
-  const size_t es = esize(desc->dtype);
-  const size_t in_need = ws_need_bound(ctx, inner, N);
-  NF_TRY(nf_ws_reserve(ctx, in_need + base_extra_bytes(desc, N)));
-  Carver cv((char *)ctx->ws + in_need);
-  bb->x = cv.take<char>((size_t)N * desc->d * es);
-  bb->z = b->kind == NF_BASE_DENSE ? cv.take<char>((size_t)N * desc->d * es) : nullptr;
-  bb->corr = cv.take<char>((size_t)N * es);
-  bb->tmp = cv.take<char>((size_t)N * es);
-  bb->nb = nf_sum2_nblocks(N);
-  bb->partial = cv.take<double>(bb->nb);
-  bb->result = cv.take<double>(8);
-  ctx->ws_guard = in_need;  // the inner entry point must stay in front of these buffers
+// reserve layout L(ctx, a...) in the context workspace and carve it
+template <class L, class... A>
+static int ws_carve(nf_ctx *ctx, L *out, A... a) {
+  NF_TRY(nf_ws_reserve(ctx, layout_bytes<L>(ctx, a...)));
+  Carver cv(ctx->ws);
+  *out = L(cv, ctx, a...);
   return NF_OK;
 }
+// the same for a wrapper: its own buffers lie behind its inner entry points' intermediates (L::in_need bytes), and the guard
+// keeps those in front of them until the caller's GuardReset puts the enclosing guard back
+template <class L, class... A>
+static int ws_carve_guarded(nf_ctx *ctx, L *out, A... a) {
+  NF_TRY(ws_carve(ctx, out, a...));
+  if (out->in_need) ctx->ws_guard = out->in_need;
+  return NF_OK;
+}
+// what the general-base wrappers keep behind the inner entry point's intermediates: x (N x d), the substitution scratch
+// of a dense base, the per-sample correction, block partials and a result slot
+struct BaseBufs {
+  size_t in_need;
+  char *x, *z, *corr, *tmp;
+  double *partial, *result;
+  long nb;
+  BaseBufs() {}
+  BaseBufs(Carver &cv, nf_ctx *ctx, const nf_flow_desc *desc, long N) {
+    const size_t es = esize(desc->dtype);
+    nf_flow_desc inner = *desc;
+    inner.base = nullptr;
+    cv.skip(in_need = ws_need_bound(ctx, &inner, N));
+    x = cv.take<char>((size_t)N * desc->d * es);
+    z = flow_base(desc)->kind == NF_BASE_DENSE ? cv.take<char>((size_t)N * desc->d * es) : nullptr;
+    corr = cv.take<char>((size_t)N * es);
+    tmp = cv.take<char>((size_t)N * es);
+    nb = nf_sum2_nblocks(N);
+    partial = cv.take<double>(nb);
+    result = cv.take<double>(8);
+  }
+};
 struct GuardReset {  // puts the enclosing wrapper's guard (or none) back on every exit path
   nf_ctx *ctx;
   size_t prev;
@@ -500,11 +517,27 @@ static int base_draw(nf_ctx *ctx, const nf_flow_desc *desc, long N, uint64_t see
 }
 
 
+// standard-layout buffers of a composition's entry points, behind its segments' intermediates
 struct CompBufs {
+  size_t in_need;
   char *y, *gbar, *logq, *ladj, *tmp, *lbar, *spare;
   double *partial_t, *partial_s, *result;
+  CompBufs() {}
+  CompBufs(Carver &cv, nf_ctx *ctx, const nf_flow_desc *desc, long N) {
+    const size_t es = esize(desc->dtype);
+    cv.skip(in_need = composite_inner_need(ctx, desc, N));
+    y = cv.take<char>((size_t)N * desc->d * es);
+    gbar = cv.take<char>((size_t)N * desc->d * es);
+    logq = cv.take<char>((size_t)N * es);
+    ladj = cv.take<char>((size_t)N * es);
+    tmp = cv.take<char>((size_t)N * es);
+    lbar = cv.take<char>((size_t)N * es);
+    spare = cv.take<char>((size_t)N * es);
+    partial_t = cv.take<double>(nf_target_nblocks(N));
+    partial_s = cv.take<double>(nf_sum2_nblocks(N));
+    result = cv.take<double>(8);
+  }
 };
-static int composite_bufs(nf_ctx *ctx, const nf_flow_desc *desc, long N, CompBufs *cb);
 static int composite_chain(nf_ctx *ctx, const nf_flow_desc *desc, bool inverse, const void *theta, const void *x_in, long N,
                            void *y_out, void *ladj, CompBufs &cb);
 static int elbo_forward_general_base(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, const void *theta,
@@ -522,7 +555,6 @@ static int value_and_grad_general_base(nf_ctx *ctx, const nf_flow_desc *desc, co
                                        uint32_t stream_id, void *out);
 static int fkl_general(nf_ctx *ctx, const nf_flow_desc *desc, const void *theta, const void *ys, int64_t N_local,
                        int64_t N_global, void *out);
-static size_t fkl_general_need(nf_ctx *ctx, const nf_flow_desc *desc, long N);
 
 // ---- base distribution ---------------------------------------------------------------------
 extern "C" int nf_base_sample_logpdf(nf_ctx *ctx, int32_t dtype, int32_t d, int64_t N, uint64_t seed,
@@ -601,10 +633,11 @@ static long coupling_slab_floats(nf_ctx *ctx, const nf_flow_desc *desc, long N) 
 // when the draws are in-library, the nets are LDS-resident and the target is one of the built-in kinds with valid
 // arguments (nf_target_check: the diagonal Gaussian's two vectors, d = 2 for WarpedGauss / Cross, ...).  A target that
 // fails the check keeps the generic sequence, whose target launch reports it.
-static inline bool elbo_fusable(const nf_flow_desc *desc, const nf_target *target, const void *xs) {
+// sizing (nf_workspace_bytes): any target
+static inline bool elbo_fusable(const nf_flow_desc *desc, const nf_target *target, const void *xs, bool sizing = false) {
   const bool resident = (desc->kind == NF_KIND_REALNVP && nf_affine_supported(desc) && nf_affine_fused_ok(desc)) ||
                         (desc->kind == NF_KIND_NSF && nf_rqs_supported(desc));
-  return !xs && desc->dtype == NF_DTYPE_F32 && resident && nf_target_check(target, desc->d) == NF_OK;
+  return !xs && desc->dtype == NF_DTYPE_F32 && resident && (sizing || nf_target_check(target, desc->d) == NF_OK);
 }
 // the fused forward launch (draws + chain + target + ELBO partial sums) of the two LDS-resident coupling families
 static int fused_chain_elbo(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, long N, uint64_t seed,
@@ -656,7 +689,6 @@ static long affine_stash_chunk(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
   return lo * unit * NF_STASH_TILE;
 }
 // floats of gradient slabs a chunked step writes: every chunk's workgroups leave one slab each
-static int coupling_bwd_grid(nf_ctx *ctx, const nf_flow_desc *desc, long N);
 static size_t chunked_slab_floats(nf_ctx *ctx, const nf_flow_desc *desc, long N, long chunk, long stride) {
   if (!chunk || chunk >= N) return (size_t)coupling_bwd_grid(ctx, desc, N) * stride;
   const long full = N / chunk, rem = N - full * chunk;
@@ -728,6 +760,15 @@ extern "C" int nf_flow_inv(nf_ctx *ctx, const nf_flow_desc *desc, const void *th
   return apply_std(ctx, desc, true, -1, theta, y_in, N, x_out, ladj_out);
 }
 
+// nf_flow_rand on the tiled path: the state and a log-det scratch (nf_flow_fwd / inv / layer_apply use the state alone)
+struct RandBufs {
+  float *xt, *ladj;
+  RandBufs() {}
+  RandBufs(Carver &cv, nf_ctx *, const nf_flow_desc *desc, long N) {
+    xt = cv.take<float>(tiled_elems(desc, N));
+    ladj = cv.take<float>((size_t)N);
+  }
+};
 // rand(rng, flow, n) / _device_specific_rand(rng, flow, n): N base draws (Philox, as nf_base_sample_logpdf with the
 // same seed / offset / stream) pushed through the transform
 extern "C" int nf_flow_rand(nf_ctx *ctx, const nf_flow_desc *desc, const void *theta, int64_t N, uint64_t seed,
@@ -740,28 +781,24 @@ extern "C" int nf_flow_rand(nf_ctx *ctx, const nf_flow_desc *desc, const void *t
     nf_flow_desc inner = *desc;
     inner.base = nullptr;
     BaseBufs bb;
-    const size_t prev_guard = ctx->ws_guard;
-    NF_TRY(base_bufs(ctx, desc, &inner, N, &bb));
-    GuardReset gr{ctx, prev_guard};
+    GuardReset gr{ctx, ctx->ws_guard};
+    NF_TRY(ws_carve_guarded(ctx, &bb, desc, N));
     NF_TRY(base_draw(ctx, desc, N, seed, sample_offset, stream_id, y_out, nullptr));
     return apply_std(ctx, &inner, false, -1, theta, y_out, N, y_out, bb.tmp);
   }
   if (is_composite(desc)) {  // draws into y_out, then the chain in place
     CompBufs cb;
-    const size_t prev_guard = ctx->ws_guard;
-    NF_TRY(composite_bufs(ctx, desc, N, &cb));
-    GuardReset gr{ctx, prev_guard};
+    GuardReset gr{ctx, ctx->ws_guard};
+    NF_TRY(ws_carve_guarded(ctx, &cb, desc, N));
     NF_TRY(nf_launch_base_sample(ctx, desc->dtype, desc->d, N, seed, sample_offset, stream_id, y_out, nullptr));
     return composite_chain(ctx, desc, false, theta, y_out, N, y_out, cb.ladj, cb);
   }
   if (is_coupling(desc)) {
-    NF_TRY(nf_ws_reserve(ctx, carve_bytes(tiled_elems(desc, N) * 4) + carve_bytes((size_t)N * 4)));
-    Carver cv(ctx->ws);
-    float *xt = cv.take<float>(tiled_elems(desc, N));
-    float *ladj = cv.take<float>((size_t)N);
-    NF_TRY(nf_launch_base_sample_tiled(ctx, desc->d, N, seed, sample_offset, stream_id, xt, nullptr));
-    NF_TRY(coupling_chain_tiled(ctx, desc, false, (const float *)theta, xt, N, ladj, -1));
-    return nf_launch_layout_convert(ctx, desc->d, N, xt, (float *)y_out, 0);
+    RandBufs b;
+    NF_TRY(ws_carve(ctx, &b, desc, N));
+    NF_TRY(nf_launch_base_sample_tiled(ctx, desc->d, N, seed, sample_offset, stream_id, b.xt, nullptr));
+    NF_TRY(coupling_chain_tiled(ctx, desc, false, (const float *)theta, b.xt, N, b.ladj, -1));
+    return nf_launch_layout_convert(ctx, desc->d, N, b.xt, (float *)y_out, 0);
   }
   if (!is_g64(desc) && desc->kind != NF_KIND_HAMILTONIAN)
     return nf_simple_rand(ctx, desc, theta, N, seed, sample_offset, stream_id, y_out);
@@ -804,7 +841,6 @@ static int realnvp_bwd(nf_ctx *ctx, const nf_flow_desc *desc, const float *theta
 
 // reverse pass of the INVERSE coupling chain on tiled buffers (forward-KL training): `state` holds
 // T^-1(data) on entry and the data on exit, `gbar` the cotangent of z; couplings in forward execution order
-static inline bool coupling_inv_bwd_tiled(const nf_flow_desc *desc) { return is_coupling(desc); }
 static int coupling_inv_bwd(nf_ctx *ctx, const nf_flow_desc *desc, const float *theta, float *state, float *gbar,
                             float lbar_const, long N, float *slab, int grid, float *g_out, void *rqs_tape = nullptr) {
   (void)theta;
@@ -823,7 +859,6 @@ static int coupling_inv_bwd(nf_ctx *ctx, const nf_flow_desc *desc, const float *
   return NF_ERR_UNSUPPORTED;
 }
 
-static long seg_theta_off(const nf_flow_desc *desc, int s);
 // ---- the tape: what a forward pass keeps for its pullback -------------------------------------------------------
 // The reference differentiates the forward's own tape (Zygote on src/objectives/elbo.jl:65-70 under
 // src/optimize.jl:12-14; MonotonicSplines' rrules, test/ad.jl:126-127).  nf_flow_fwd_keep writes that tape into
@@ -871,29 +906,63 @@ static size_t tape_bytes_of(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
 static size_t tape_fwd_need_seg(nf_ctx *, const nf_flow_desc *g, long N) {
   return is_coupling(g) ? carve_bytes(tiled_elems(g, N) * 4) : 0;
 }
-static size_t tape_bwd_need_seg(nf_ctx *ctx, const nf_flow_desc *g, long N) {
-  const size_t tb = is_coupling(g) ? carve_bytes(tiled_elems(g, N) * 4) : 0;
-  switch (tape_kind(ctx, g, N)) {
-    case TAPE_X: return flat_bwd_ws_bytes(ctx, g, N);
-    case TAPE_AFFINE_STASH: return tb + carve_bytes((size_t)coupling_bwd_grid(ctx, g, N) * coupling_slab_floats(ctx, g, N) * 4);
-    case TAPE_TILED_Y: return 2 * tb + carve_bytes((size_t)coupling_bwd_grid(ctx, g, N) * coupling_slab_floats(ctx, g, N) * 4);
-    case TAPE_WIDE: return 2 * tb + carve_bytes(nf_wide_train_scratch_floats(ctx, g, N) * 4);
+// pullback of one segment: the flat kernels' own workspace, or the tiled cotangent with what the tape's kind adds (the
+// state the reverse pass walks back, gradient slabs, the wide path's scratch)
+struct TapeBwdBufs {
+  TapeKind tk;
+  int grid = 0;
+  long stride = 0;
+  float *gt = nullptr, *state = nullptr, *slab = nullptr, *scratch = nullptr;
+  TapeBwdBufs() {}
+  TapeBwdBufs(Carver &cv, nf_ctx *ctx, const nf_flow_desc *g, long N) {
+    tk = tape_kind(ctx, g, N);
+    if (tk == TAPE_X) {
+      cv.skip(flat_bwd_ws_bytes(ctx, g, N));
+      return;
+    }
+    const size_t te = tiled_elems(g, N);
+    gt = cv.take<float>(te);
+    state = tk == TAPE_AFFINE_STASH ? nullptr : cv.take<float>(te);
+    if (tk == TAPE_WIDE) {
+      scratch = cv.take<float>(nf_wide_train_scratch_floats(ctx, g, N));
+      return;
+    }
+    grid = coupling_bwd_grid(ctx, g, N);
+    stride = coupling_slab_floats(ctx, g, N);
+    slab = cv.take<float>((size_t)grid * stride);
   }
-  return 0;
-}
-// a composition keeps a log-det scratch vector and the block partials nf_launch_sum2 insists on behind its segments' needs
-static size_t tape_comp_extra(const nf_flow_desc *desc, long N) {
-  return carve_bytes((size_t)N * esize(desc->dtype)) + carve_bytes((size_t)nf_sum2_nblocks(N) * 8);
-}
+};
+// a composition's forward keeps a log-det scratch vector and the block partials nf_launch_sum2 insists on behind its
+// segments' needs
+struct TapeFwdCompBufs {
+  size_t in_need = 0;
+  char *tmp;
+  double *partial;
+  TapeFwdCompBufs() {}
+  TapeFwdCompBufs(Carver &cv, nf_ctx *ctx, const nf_flow_desc *desc, long N) {
+    for (int s = 0; s < desc->nsegments; ++s) {
+      const size_t v = tape_fwd_need_seg(ctx, &desc->segments[s], N);
+      if (v > in_need) in_need = v;
+    }
+    cv.skip(in_need);
+    tmp = cv.take<char>((size_t)N * esize(desc->dtype));
+    partial = cv.take<double>(nf_sum2_nblocks(N));
+  }
+};
 static size_t tape_need(nf_ctx *ctx, const nf_flow_desc *desc, long N, bool bwd) {
-  if (!is_composite(desc)) return bwd ? tape_bwd_need_seg(ctx, desc, N) : tape_fwd_need_seg(ctx, desc, N);
+  if (!is_composite(desc)) return bwd ? layout_bytes<TapeBwdBufs>(ctx, desc, N) : tape_fwd_need_seg(ctx, desc, N);
+  if (!bwd) return layout_bytes<TapeFwdCompBufs>(ctx, desc, N);
   size_t m = 0;
   for (int s = 0; s < desc->nsegments; ++s) {
-    const nf_flow_desc *g = &desc->segments[s];
-    const size_t v = bwd ? tape_bwd_need_seg(ctx, g, N) : tape_fwd_need_seg(ctx, g, N);
+    const size_t v = layout_bytes<TapeBwdBufs>(ctx, &desc->segments[s], N);
     if (v > m) m = v;
   }
-  return m + (bwd ? 0 : tape_comp_extra(desc, N));
+  return m;
+}
+// what the forward and the pullback of a tape need in front of a wrapper's own buffers
+static size_t tape_inner_need(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
+  const size_t a = tape_need(ctx, desc, N, false), b = tape_need(ctx, desc, N, true);
+  return a > b ? a : b;
 }
 
 // forward of ONE homogeneous segment, leaving its tape; y_out may alias x_in
@@ -927,37 +996,26 @@ static int tape_fwd_seg(nf_ctx *ctx, const nf_flow_desc *g, const void *theta, c
 // log-det cotangent is lbar_const.  The tape is left intact (a pullback may be called more than once).
 static int tape_bwd_seg(nf_ctx *ctx, const nf_flow_desc *g, const void *theta, const void *tape, const void *ybar,
                         const void *lbar, double lbar_const, long N, void *xbar_out, void *gtheta_out) {
-  const TapeKind tk = tape_kind(ctx, g, N);
-  if (tk == TAPE_X) {
-    NF_TRY(nf_ws_reserve(ctx, flat_bwd_ws_bytes(ctx, g, N)));
-    return flat_bwd(ctx, g, theta, tape, ybar, lbar, lbar_const, N, xbar_out, gtheta_out, ctx->ws);
-  }
+  TapeBwdBufs b;
+  NF_TRY(ws_carve(ctx, &b, g, N));
+  const TapeKind tk = b.tk;
+  if (tk == TAPE_X) return flat_bwd(ctx, g, theta, tape, ybar, lbar, lbar_const, N, xbar_out, gtheta_out, ctx->ws);
   const size_t te = tiled_elems(g, N);
-  NF_TRY(nf_ws_reserve(ctx, tape_bwd_need_seg(ctx, g, N)));
-  Carver cv(ctx->ws);
-  float *gt = cv.take<float>(te);
+  float *gt = b.gt, *state = b.state, *slab = b.slab;
   NF_TRY(coupling_pack(ctx, g, (const float *)theta));
   NF_TRY(nf_launch_layout_convert(ctx, g->d, N, (const float *)ybar, gt, 1));
   if (tk == TAPE_AFFINE_STASH) {
-    const int grid = coupling_bwd_grid(ctx, g, N);
-    const long stride = coupling_slab_floats(ctx, g, N);
-    float *slab = cv.take<float>((size_t)grid * stride);
     NF_TRY(nf_affine_bwd_stashed(ctx, g, (float *)const_cast<void *>(tape), gt, (const float *)lbar, (float)lbar_const, N, slab,
-                                 stride, grid));
-    NF_TRY(nf_affine_reduce_slabs(ctx, g, slab, grid, (float *)gtheta_out));
+                                 b.stride, b.grid));
+    NF_TRY(nf_affine_reduce_slabs(ctx, g, slab, b.grid, (float *)gtheta_out));
   } else if (tk == TAPE_WIDE) {
-    float *state = cv.take<float>(te);
-    float *scratch = cv.take<float>(nf_wide_train_scratch_floats(ctx, g, N));
     const char *ty = (const char *)tape + carve_bytes(nf_wide_fwd_stash_floats(ctx, g, N) * 4);
     NF_HIP(hipMemcpyAsync(state, ty, te * 4, hipMemcpyDeviceToDevice, ctx->stream));
     NF_TRY(nf_wide_train_backward(ctx, g, state, gt, (const float *)lbar, (float)lbar_const, N,
-                                  (float *)const_cast<void *>(tape), (float *)gtheta_out, scratch));
+                                  (float *)const_cast<void *>(tape), (float *)gtheta_out, b.scratch));
   } else {
-    float *state = cv.take<float>(te);
-    const int grid = coupling_bwd_grid(ctx, g, N);
-    float *slab = cv.take<float>((size_t)grid * coupling_slab_floats(ctx, g, N));
     NF_HIP(hipMemcpyAsync(state, tape, te * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    NF_TRY(realnvp_bwd(ctx, g, (const float *)theta, state, gt, (const float *)lbar, (float)lbar_const, N, slab, grid,
+    NF_TRY(realnvp_bwd(ctx, g, (const float *)theta, state, gt, (const float *)lbar, (float)lbar_const, N, slab, b.grid,
                        (float *)gtheta_out, nullptr, 0, nullptr,
                        rqs_tape_b(g, N) ? (char *)const_cast<void *>(tape) + carve_bytes(te * 4) : nullptr));
   }
@@ -971,20 +1029,14 @@ static int tape_fwd(nf_ctx *ctx, const nf_flow_desc *desc, const void *theta, co
   if (!is_composite(desc)) return tape_fwd_seg(ctx, desc, theta, x_in, N, y_out, ladj, tape);
   const size_t es = esize(desc->dtype);
   const int ns = desc->nsegments;
-  size_t in_need = 0, toff[65];
+  size_t toff[65];
   toff[0] = 0;
-  for (int s = 0; s < ns; ++s) {
-    const size_t v = tape_fwd_need_seg(ctx, &desc->segments[s], N);
-    if (v > in_need) in_need = v;
-    toff[s + 1] = toff[s] + tape_seg_bytes(ctx, &desc->segments[s], N);
-  }
-  const size_t prev_guard = ctx->ws_guard;
-  NF_TRY(nf_ws_reserve(ctx, in_need + tape_comp_extra(desc, N)));
-  GuardReset gr{ctx, prev_guard};
-  Carver cv((char *)ctx->ws + in_need);
-  char *tmp = cv.take<char>((size_t)N * es);
-  double *partial = cv.take<double>(nf_sum2_nblocks(N));
-  if (in_need) ctx->ws_guard = in_need;
+  for (int s = 0; s < ns; ++s) toff[s + 1] = toff[s] + tape_seg_bytes(ctx, &desc->segments[s], N);
+  GuardReset gr{ctx, ctx->ws_guard};
+  TapeFwdCompBufs b;
+  NF_TRY(ws_carve_guarded(ctx, &b, desc, N));
+  char *tmp = b.tmp;
+  double *partial = b.partial;
   const void *cur = x_in;
   for (int i = 0; i < ns; ++i) {
     const int s = ns - 1 - i;
@@ -1045,11 +1097,18 @@ extern "C" int nf_flow_bwd_kept(nf_ctx *ctx, const nf_flow_desc *desc, const voi
 
 // The pullback for callers that kept only x: the forward is run again FROM x with its tape in the context workspace
 // (not reconstructed from y -- y is accepted for the signature of the rrule and not read), then the tape is pulled back.
-static size_t flow_bwd_need(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
-  const size_t a = tape_need(ctx, desc, N, false), b = tape_need(ctx, desc, N, true);
-  return (a > b ? a : b) + tape_bytes_of(ctx, desc, N) + carve_bytes((size_t)N * desc->d * esize(desc->dtype)) +
-         carve_bytes((size_t)N * esize(desc->dtype));
-}
+struct FlowBwdBufs {
+  size_t in_need;
+  char *tape, *yscr, *lscr;
+  FlowBwdBufs() {}
+  FlowBwdBufs(Carver &cv, nf_ctx *ctx, const nf_flow_desc *desc, long N) {
+    const size_t es = esize(desc->dtype);
+    cv.skip(in_need = tape_inner_need(ctx, desc, N));
+    tape = cv.take<char>(tape_bytes_of(ctx, desc, N));
+    yscr = cv.take<char>((size_t)N * desc->d * es);
+    lscr = cv.take<char>((size_t)N * es);
+  }
+};
 extern "C" int nf_flow_bwd(nf_ctx *ctx, const nf_flow_desc *desc, const void *theta, const void *x, const void *y,
                            const void *ybar, const void *lbar, int64_t N, void *xbar_out, void *gtheta_out) {
   if (!ctx || !theta || !x || !y || !ybar || !lbar || !xbar_out || !gtheta_out || N < 0) return NF_ERR_ARG;
@@ -1057,19 +1116,11 @@ extern "C" int nf_flow_bwd(nf_ctx *ctx, const nf_flow_desc *desc, const void *th
   NF_HIP(hipSetDevice(ctx->device));
   const long P = nf_param_count(desc);
   if (N == 0) return nf_launch_fill(ctx, desc->dtype, gtheta_out, P, 0.0);
-  const size_t es = esize(desc->dtype);
-  const size_t a = tape_need(ctx, desc, N, false), b = tape_need(ctx, desc, N, true);
-  const size_t in_need = a > b ? a : b;
-  const size_t prev_guard = ctx->ws_guard;
-  NF_TRY(nf_ws_reserve(ctx, flow_bwd_need(ctx, desc, N)));
-  GuardReset gr{ctx, prev_guard};
-  Carver cv((char *)ctx->ws + in_need);
-  char *tape = cv.take<char>(tape_bytes_of(ctx, desc, N));
-  char *yscr = cv.take<char>((size_t)N * desc->d * es);
-  char *lscr = cv.take<char>((size_t)N * es);
-  if (in_need) ctx->ws_guard = in_need;
-  NF_TRY(tape_fwd(ctx, desc, theta, x, N, yscr, lscr, tape));
-  return tape_bwd(ctx, desc, theta, tape, ybar, lbar, 0.0, N, xbar_out, gtheta_out);
+  GuardReset gr{ctx, ctx->ws_guard};
+  FlowBwdBufs b;
+  NF_TRY(ws_carve_guarded(ctx, &b, desc, (long)N));
+  NF_TRY(tape_fwd(ctx, desc, theta, x, N, b.yscr, b.lscr, b.tape));
+  return tape_bwd(ctx, desc, theta, b.tape, ybar, lbar, 0.0, N, xbar_out, gtheta_out);
 }
 
 // ---- targets -------------------------------------------------------------------------------
@@ -1082,6 +1133,26 @@ extern "C" int nf_target_logp(nf_ctx *ctx, int32_t dtype, const nf_target *targe
 }
 
 // ---- objectives ----------------------------------------------------------------------------
+// loss partials an ELBO entry point leaves: the target kernel's blocks, or one per workgroup of the fused forward
+static long elbo_npartial(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
+  const long nb = is_coupling(desc) ? nf_target_tiled_nblocks(N) : nf_target_nblocks(N);
+  return nb < ctx->num_cu ? ctx->num_cu : nb;
+}
+// value-only objectives (nf_elbo_batch(_rng), nf_loglikelihood): the state (tiled for coupling flows), log q0 and the
+// log-det per sample, `npartial` block partials and a result slot
+struct ValueBufs {
+  char *x, *logq, *ladj;
+  double *partial, *result;
+  ValueBufs() {}
+  ValueBufs(Carver &cv, nf_ctx *, const nf_flow_desc *desc, long N, long npartial) {
+    const size_t es = esize(desc->dtype);
+    x = cv.take<char>((is_coupling(desc) ? tiled_elems(desc, N) : (size_t)N * desc->d) * es);
+    logq = cv.take<char>((size_t)N * es);
+    ladj = cv.take<char>((size_t)N * es);
+    partial = cv.take<double>(npartial);
+    result = cv.take<double>(8);
+  }
+};
 static int elbo_forward_composite(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, const void *theta,
                                   const void *xs, long N, uint64_t seed, uint64_t off, uint32_t stream_id, void *elbos_out,
                                   double *elbo_host);
@@ -1092,16 +1163,10 @@ static int elbo_forward(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *
   const size_t es = esize(desc->dtype);
   const bool cp = is_coupling(desc);
   const long nb = cp ? nf_target_tiled_nblocks(N) : nf_target_nblocks(N);
-  const long nb_alloc = nb < ctx->num_cu ? ctx->num_cu : nb;  // the fused forward leaves one partial per workgroup
-  const size_t xe = cp ? tiled_elems(desc, N) : (size_t)N * desc->d;
-  const size_t need = carve_bytes(xe * es) + 2 * carve_bytes((size_t)N * es) + carve_bytes((size_t)nb_alloc * 8) + carve_bytes(64);
-  NF_TRY(nf_ws_reserve(ctx, need));
-  Carver cv(ctx->ws);
-  char *x = cv.take<char>(xe * es);
-  char *logq = cv.take<char>((size_t)N * es);
-  char *ladj = cv.take<char>((size_t)N * es);
-  double *partial = cv.take<double>(nb_alloc);
-  double *result = cv.take<double>(8);
+  ValueBufs b;
+  NF_TRY(ws_carve(ctx, &b, desc, N, elbo_npartial(ctx, desc, N)));
+  char *x = b.x, *logq = b.logq, *ladj = b.ladj;
+  double *partial = b.partial, *result = b.result;
   if (cp && !elbos_out && elbo_fusable(desc, target, xs)) {
     NF_TRY(coupling_pack(ctx, desc, (const float *)theta));
     NF_TRY(fused_chain_elbo(ctx, desc, target, N, seed, off, stream_id, (float *)x, nullptr, 0.0, partial, 1.0 / (double)N));
@@ -1169,18 +1234,12 @@ extern "C" int nf_loglikelihood(nf_ctx *ctx, const nf_flow_desc *desc, const voi
   NF_HIP(hipSetDevice(ctx->device));
   if (flow_base(desc)) return loglikelihood_general_base(ctx, desc, theta, ys, N, logliks_out, ll_host);
   if (is_composite(desc)) return loglikelihood_composite(ctx, desc, theta, ys, N, logliks_out, ll_host);
-  const size_t es = esize(desc->dtype);
   const bool cp = is_coupling(desc);
   const long nb = nf_sum2_nblocks(N);
-  const size_t xe = cp ? tiled_elems(desc, N) : (size_t)N * desc->d;
-  const size_t need = carve_bytes(xe * es) + 2 * carve_bytes((size_t)N * es) + carve_bytes((size_t)nb * 8) + carve_bytes(64);
-  NF_TRY(nf_ws_reserve(ctx, need));
-  Carver cv(ctx->ws);
-  char *x = cv.take<char>(xe * es);
-  char *logq = cv.take<char>((size_t)N * es);
-  char *ladj = cv.take<char>((size_t)N * es);
-  double *partial = cv.take<double>(nb);
-  double *result = cv.take<double>(8);
+  ValueBufs b;
+  NF_TRY(ws_carve(ctx, &b, desc, (long)N, nb));
+  char *x = b.x, *logq = b.logq, *ladj = b.ladj;
+  double *partial = b.partial, *result = b.result;
   if (cp) {
     float *xt = (float *)x;
     NF_TRY(nf_launch_layout_convert(ctx, desc->d, N, (const float *)ys, xt, 1));
@@ -1200,6 +1259,67 @@ extern "C" int nf_loglikelihood(nf_ctx *ctx, const nf_flow_desc *desc, const voi
 // the INVERSE chain: layers in forward execution order, each with the implicit-function form of its inverse
 // (cotangent of z: z / Ng; cotangent of every ladj_inv: -1 / Ng).  The standard-normal base density and its
 // gradient come from the diagonal-Gaussian target kernel with mu = 0, var = 1.
+
+// The chunked stash loop of an LDS-resident RealNVP step (affine_stash_chunk): per chunk of stash_nc samples, fwd(o, nc, npart,
+// &left) runs the forward that fills the stash and the cotangent tile gt + o d and says how many loss partials it left from
+// partial + npart on; the stashed reverse pass follows (nobody reads the flow input's cotangent), one gradient slab per workgroup.
+struct ChunkCounts { long nslab = 0, npart = 0; };
+template <class F>
+static int stash_chunk_loop(nf_ctx *ctx, const nf_flow_desc *desc, long N, long stash_nc, float *stash, float *gt, double inv,
+                            float *slab, bool inv_dir, ChunkCounts *cc, F fwd) {
+  const long stride = coupling_slab_floats(ctx, desc, N);
+  for (long o = 0; o < N; o += stash_nc) {
+    const long nc = N - o < stash_nc ? N - o : stash_nc;
+    const int gc = coupling_bwd_grid(ctx, desc, nc);
+    long left = 0;
+    NF_TRY(fwd(o, nc, cc->npart, &left));
+    NF_TRY(nf_affine_bwd_stashed(ctx, desc, stash, gt + o * desc->d, nullptr, (float)(-inv), nc, slab + cc->nslab * stride, stride,
+                                 gc, inv_dir, true));
+    cc->nslab += gc;
+    cc->npart += left;
+  }
+  return NF_OK;
+}
+
+// shapes nf_loglikelihood_value_and_grad differentiates: everything but couplings neither MFMA path nor general kernel builds
+static inline bool fkl_supported(const nf_flow_desc *desc) {
+  const bool coupling_kind = desc->kind == NF_KIND_REALNVP || desc->kind == NF_KIND_NSF;
+  return !coupling_kind || is_coupling(desc) || nf_g64_supported(desc);
+}
+struct FklBufs {
+  bool coupling_kind, hf, tiled;
+  long nb, stash_nc;  // loss partials; samples per stash chunk (0: no stash)
+  int grid;
+  char *z, *gbar, *ladj, *q0par, *slab, *fws;
+  double *partial;
+  float *stash;
+  void *rqs_tape;
+  FklBufs() {}
+  FklBufs(Carver &cv, nf_ctx *ctx, const nf_flow_desc *desc, long N) {
+    const size_t es = esize(desc->dtype);
+    coupling_kind = desc->kind == NF_KIND_REALNVP || desc->kind == NF_KIND_NSF;
+    hf = desc->kind == NF_KIND_HAMILTONIAN;
+    tiled = is_coupling(desc);
+    nb = tiled ? nf_target_tiled_nblocks(N) : nf_target_nblocks(N);
+    grid = tiled ? coupling_bwd_grid(ctx, desc, N) : 0;
+    const size_t flat_ws = tiled ? 0 : hf ? nf_hf_bwd_ws_bytes(desc, N) : coupling_kind ? nf_g64_bwd_inv_ws_bytes(desc, N)
+                                                                                         : nf_simple_bwd_ws_bytes(ctx, desc, N);
+    const size_t xe = tiled ? tiled_elems(desc, N) : (size_t)N * desc->d;
+    // LDS-resident RealNVP: activation stash of the inverse chain, the batch in chunks beyond the budget
+    stash_nc = tiled ? affine_stash_chunk(ctx, desc, N) : 0;
+    const size_t stash_b = stash_nc ? affine_stash_bytes(ctx, desc, stash_nc) : 0;
+    const size_t rqs_b = tiled ? rqs_tape_b(desc, N) : 0;
+    z = cv.take<char>(xe * es);
+    gbar = cv.take<char>(xe * es);
+    ladj = cv.take<char>((size_t)N * es);
+    partial = cv.take<double>(nb);
+    q0par = cv.take<char>(2 * (size_t)desc->d * es);
+    slab = cv.take<char>((tiled ? chunked_slab_floats(ctx, desc, N, stash_nc, coupling_slab_floats(ctx, desc, N)) : 0) * es);
+    fws = cv.take<char>(flat_ws);
+    stash = stash_b ? cv.take<float>(stash_b / 4) : nullptr;
+    rqs_tape = rqs_b ? (void *)cv.take<char>(rqs_b) : nullptr;
+  }
+};
 extern "C" int nf_loglikelihood_value_and_grad(nf_ctx *ctx, const nf_flow_desc *desc, const void *theta, const void *ys,
                                                int64_t N_local, int64_t N_global, void *out) {
   if (!ctx || !theta || !out || N_local < 0 || N_global < 1 || (N_local > 0 && !ys)) return NF_ERR_ARG;
@@ -1213,36 +1333,15 @@ extern "C" int nf_loglikelihood_value_and_grad(nf_ctx *ctx, const nf_flow_desc *
   const size_t es = esize(dt);
   if (N == 0) return nf_launch_fill(ctx, dt, out, P + 1, 0.0);
   const double inv = 1.0 / (double)N_global;
-  const bool coupling_kind = desc->kind == NF_KIND_REALNVP || desc->kind == NF_KIND_NSF;
-  const bool hf = desc->kind == NF_KIND_HAMILTONIAN;
-  const bool tiled = is_coupling(desc) && coupling_inv_bwd_tiled(desc);
-  if (coupling_kind && !tiled && !nf_g64_supported(desc)) return NF_ERR_UNSUPPORTED;
-  const long nb = tiled ? nf_target_tiled_nblocks(N) : nf_target_nblocks(N);
-  const int grid = tiled ? coupling_bwd_grid(ctx, desc, N) : 0;
-  const size_t slabf = tiled ? (size_t)grid * coupling_slab_floats(ctx, desc, N) : 0;
-  const size_t flat_ws = tiled ? 0 : hf ? nf_hf_bwd_ws_bytes(desc, N) : coupling_kind ? nf_g64_bwd_inv_ws_bytes(desc, N)
-                                                                                       : nf_simple_bwd_ws_bytes(ctx, desc, N);
-  const size_t xe = tiled ? tiled_elems(desc, N) : (size_t)N * desc->d;
-  // LDS-resident RealNVP: activation stash of the inverse chain, the batch in chunks beyond the budget
-  const long stash_nc = tiled ? affine_stash_chunk(ctx, desc, N) : 0;
-  const int stash_nch = stash_nc ? (int)((N + stash_nc - 1) / stash_nc) : 0;
-  const size_t stash_b = stash_nc ? affine_stash_bytes(ctx, desc, stash_nc) : 0;
-  const size_t slabf_all = tiled ? chunked_slab_floats(ctx, desc, N, stash_nc, coupling_slab_floats(ctx, desc, N)) : 0;
-  (void)slabf; (void)stash_nch;
-  const size_t rqs_b = tiled ? rqs_tape_b(desc, N) : 0;
-  const size_t need = 2 * carve_bytes(xe * es) + carve_bytes((size_t)N * es) + carve_bytes((size_t)nb * 8) +
-                      carve_bytes(2 * (size_t)desc->d * es) + carve_bytes(slabf_all * es) + carve_bytes(flat_ws) + carve_bytes(stash_b) + rqs_b;
-  NF_TRY(nf_ws_reserve(ctx, need));
-  Carver cv(ctx->ws);
-  char *z = cv.take<char>(xe * es);
-  char *gbar = cv.take<char>(xe * es);
-  char *ladj = cv.take<char>((size_t)N * es);
-  double *partial = cv.take<double>(nb);
-  char *q0par = cv.take<char>(2 * (size_t)desc->d * es);
-  char *slab = cv.take<char>(slabf_all * es);
-  char *fws = cv.take<char>(flat_ws);
-  float *stash = stash_b ? cv.take<float>(stash_b / 4) : nullptr;
-  void *rqs_tape = rqs_b ? (void *)cv.take<char>(rqs_b) : nullptr;
+  if (!fkl_supported(desc)) return NF_ERR_UNSUPPORTED;
+  FklBufs b;
+  NF_TRY(ws_carve(ctx, &b, desc, N));
+  const bool coupling_kind = b.coupling_kind, hf = b.hf, tiled = b.tiled;
+  const long nb = b.nb;
+  char *z = b.z, *gbar = b.gbar, *ladj = b.ladj, *q0par = b.q0par, *slab = b.slab, *fws = b.fws;
+  double *partial = b.partial;
+  float *stash = b.stash;
+  void *rqs_tape = b.rqs_tape;
   nf_target q0;
   q0.kind = NF_TARGET_DIAGGAUSS;
   q0.p0 = q0par;
@@ -1256,26 +1355,20 @@ extern "C" int nf_loglikelihood_value_and_grad(nf_ctx *ctx, const nf_flow_desc *
     NF_TRY(nf_launch_layout_convert(ctx, desc->d, N, (const float *)ys, zt, 1));
     if (stash) {  // the inverse chain leaves the operands of its own reverse pass (nf_coupling.hip, "activation stash")
       NF_TRY(coupling_pack(ctx, desc, (const float *)theta));
-      const long stride = coupling_slab_floats(ctx, desc, N);
-      long nslab = 0, npart = 0;
-      for (long o = 0; o < N; o += stash_nc) {
-        const long nc = N - o < stash_nc ? N - o : stash_nc;
-        const int gc = coupling_bwd_grid(ctx, desc, nc);
+      ChunkCounts cc;
+      NF_TRY(stash_chunk_loop(ctx, desc, N, b.stash_nc, stash, gt, inv, (float *)slab, true, &cc, [&](long o, long nc, long npart, long *left) {
         NF_TRY(nf_affine_chain(ctx, desc, true, zt + o * desc->d, nc, (float *)ladj + o, stash));
-        NF_TRY(nf_launch_target_tiled(ctx, &q0, desc->d, nc, zt + o * desc->d, nullptr, (const float *)ladj + o, gt + o * desc->d, -inv,
-                                      nullptr, partial + npart, -inv));
-        NF_TRY(nf_affine_bwd_stashed(ctx, desc, stash, gt + o * desc->d, nullptr, (float)(-inv), nc, (float *)slab + nslab * stride,
-                                     stride, gc, true, true));  // (a training step: nobody reads the cotangent of ys)
-        nslab += gc;
-        npart += nf_target_tiled_nblocks(nc);
-      }
-      NF_TRY(nf_launch_finish_sum(ctx, partial, npart, 0, nullptr, (float *)out + P, nullptr));
-      return nf_affine_reduce_slabs(ctx, desc, (const float *)slab, (int)nslab, (float *)out);
+        *left = nf_target_tiled_nblocks(nc);
+        return nf_launch_target_tiled(ctx, &q0, desc->d, nc, zt + o * desc->d, nullptr, (const float *)ladj + o, gt + o * desc->d, -inv,
+                                      nullptr, partial + npart, -inv);
+      }));
+      NF_TRY(nf_launch_finish_sum(ctx, partial, cc.npart, 0, nullptr, (float *)out + P, nullptr));
+      return nf_affine_reduce_slabs(ctx, desc, (const float *)slab, (int)cc.nslab, (float *)out);
     }
     NF_TRY(coupling_chain_tiled(ctx, desc, true, (const float *)theta, zt, N, (float *)ladj, -1, rqs_tape));
     NF_TRY(nf_launch_target_tiled(ctx, &q0, desc->d, N, zt, nullptr, (const float *)ladj, gt, -inv, nullptr, partial, -inv));
     NF_TRY(nf_launch_finish_sum(ctx, partial, nb, 0, nullptr, (float *)out + P, nullptr));
-    return coupling_inv_bwd(ctx, desc, (const float *)theta, zt, gt, (float)(-inv), N, (float *)slab, grid, (float *)out, rqs_tape);
+    return coupling_inv_bwd(ctx, desc, (const float *)theta, zt, gt, (float)(-inv), N, (float *)slab, b.grid, (float *)out, rqs_tape);
   }
   if (hf) {  // every inverse layer of the Hamiltonian flow is explicit: differentiated directly (nf_hamiltonian.hip)
     NF_TRY(nf_hf_apply(ctx, desc, 0, nf_layer_count(desc), true, theta, ys, N, z, ladj));
@@ -1301,54 +1394,63 @@ extern "C" int nf_loglikelihood_value_and_grad(nf_ctx *ctx, const nf_flow_desc *
 // the standard normal goes through the diagonal-Gaussian target kernel as above); then the reverse pass of each
 // segment's inverse, last segment first.  A single-family flow over a general base is the one-segment case.
 
-static size_t composite_inner_need(nf_ctx *ctx, const nf_flow_desc *desc, long N);
-static long seg_theta_off(const nf_flow_desc *desc, int s);
+// inv_bwd_std.  Tiled path: state, cotangent, gradient slabs; spline couplings add their tape and a log-det scratch.
+// Standard layout: the reverse kernels' own workspace; planar / radial / mean-field add a log-det scratch behind it.
+struct InvBwdBufs {
+  int grid = 0;
+  float *state = nullptr, *gt = nullptr, *slab = nullptr, *scr_ladj = nullptr;
+  void *rqs_tape = nullptr;
+  char *flat_ladj = nullptr;
+  InvBwdBufs() {}
+  InvBwdBufs(Carver &cv, nf_ctx *ctx, const nf_flow_desc *g, long N) {
+    if (!is_coupling(g)) {
+      if (g->kind == NF_KIND_HAMILTONIAN) cv.skip(nf_hf_bwd_ws_bytes(g, N));
+      else if (is_g64(g)) cv.skip(nf_g64_bwd_inv_ws_bytes(g, N));
+      else {
+        cv.take<char>(nf_simple_bwd_ws_bytes(ctx, g, N));
+        flat_ladj = cv.take<char>((size_t)N * esize(g->dtype));
+      }
+      return;
+    }
+    const size_t te = tiled_elems(g, N), rqs_b = rqs_tape_b(g, N);
+    grid = coupling_bwd_grid(ctx, g, N);
+    state = cv.take<float>(te);
+    gt = cv.take<float>(te);
+    slab = cv.take<float>((size_t)grid * coupling_slab_floats(ctx, g, N));
+    rqs_tape = rqs_b ? (void *)cv.take<char>(rqs_b) : nullptr;
+    scr_ladj = rqs_b ? cv.take<float>((size_t)N) : nullptr;
+  }
+};
 
 // reverse pass of ONE homogeneous segment's inverse: yin = the segment's inverse input, zout = its inverse output
 // (clobbered), gbar = cotangent of zout on entry, of yin on exit; gtheta_out = the segment's parameter gradient.
 // Intermediates come from the front of the context workspace.
 static int inv_bwd_std(nf_ctx *ctx, const nf_flow_desc *g, const void *theta, const void *yin, void *zout, void *gbar,
                        double lbar_const, long N, void *gtheta_out) {
-  const size_t es = esize(g->dtype);
+  InvBwdBufs b;
+  NF_TRY(ws_carve(ctx, &b, g, N));
   if (is_coupling(g)) {
-    const int grid = coupling_bwd_grid(ctx, g, N);
-    const size_t te = tiled_elems(g, N);
-    const size_t slabf = (size_t)grid * coupling_slab_floats(ctx, g, N);
-    const size_t rqs_b = rqs_tape_b(g, N);
-    NF_TRY(nf_ws_reserve(ctx, 2 * carve_bytes(te * 4) + carve_bytes(slabf * 4) + rqs_b + (rqs_b ? carve_bytes((size_t)N * 4) : 0)));
-    Carver cv(ctx->ws);
-    float *state = cv.take<float>(te);
-    float *gt = cv.take<float>(te);
-    float *slab = cv.take<float>(slabf);
+    float *state = b.state, *gt = b.gt, *slab = b.slab;
+    void *rqs_tape = b.rqs_tape;
     NF_TRY(coupling_pack(ctx, g, (const float *)theta));
-    void *rqs_tape = nullptr;
-    if (rqs_b) {
+    if (rqs_tape) {
       // spline couplings: the reverse pass differentiates the inverse chain's own bins (RqsTape, nf_rqs.hip), so the
       // segment's inverse runs again from its input, leaving its output in the tiled state AND the tape
-      rqs_tape = cv.take<char>(rqs_b);
-      float *scr_ladj = cv.take<float>((size_t)N);
       NF_TRY(nf_launch_layout_convert(ctx, g->d, N, (const float *)yin, state, 1));
-      NF_TRY(nf_rqs_chain(ctx, g, true, state, N, scr_ladj, -1, rqs_tape));
+      NF_TRY(nf_rqs_chain(ctx, g, true, state, N, b.scr_ladj, -1, rqs_tape));
     } else {
       NF_TRY(nf_launch_layout_convert(ctx, g->d, N, (const float *)zout, state, 1));
     }
     NF_TRY(nf_launch_layout_convert(ctx, g->d, N, (const float *)gbar, gt, 1));
-    NF_TRY(coupling_inv_bwd(ctx, g, (const float *)theta, state, gt, (float)lbar_const, N, slab, grid, (float *)gtheta_out, rqs_tape));
+    NF_TRY(coupling_inv_bwd(ctx, g, (const float *)theta, state, gt, (float)lbar_const, N, slab, b.grid, (float *)gtheta_out, rqs_tape));
     return nf_launch_layout_convert(ctx, g->d, N, gt, (float *)gbar, 0);
   }
   if (g->kind == NF_KIND_HAMILTONIAN) {  // single-segment only (check_composite): the data cotangent is not needed
-    NF_TRY(nf_ws_reserve(ctx, nf_hf_bwd_ws_bytes(g, N)));
     return nf_hf_bwd_inv(ctx, g, theta, yin, gbar, lbar_const, N, gtheta_out, ctx->ws);
   }
-  if (is_g64(g)) {
-    NF_TRY(nf_ws_reserve(ctx, nf_g64_bwd_inv_ws_bytes(g, N)));
-    return nf_g64_bwd_inv(ctx, g, theta, zout, gbar, lbar_const, N, gtheta_out, ctx->ws);
-  }
+  if (is_g64(g)) return nf_g64_bwd_inv(ctx, g, theta, zout, gbar, lbar_const, N, gtheta_out, ctx->ws);
   // planar / radial / mean-field: the inverse again with every layer's point stashed (the same z), then the reverse pass
-  const size_t sw = nf_simple_bwd_ws_bytes(ctx, g, N);
-  NF_TRY(nf_ws_reserve(ctx, carve_bytes(sw) + carve_bytes((size_t)N * es)));
-  char *scr_ladj = (char *)ctx->ws + carve_bytes(sw);
-  NF_TRY(nf_simple_apply_stash(ctx, g, theta, yin, N, zout, scr_ladj, ctx->ws, true));
+  NF_TRY(nf_simple_apply_stash(ctx, g, theta, yin, N, zout, b.flat_ladj, ctx->ws, true));
   return nf_simple_bwd(ctx, g, theta, zout, gbar, nullptr, lbar_const, N, gbar, gtheta_out, ctx->ws, true, true);
 }
 
@@ -1356,23 +1458,30 @@ static inline long fkl_general_nb(long N) {
   const long a = nf_target_nblocks(N), b = nf_sum2_nblocks(N);
   return a > b ? a : b;
 }
-static size_t fkl_general_extra(const nf_flow_desc *desc, long N) {
-  const size_t es = esize(desc->dtype);
-  const nf_base *b = flow_base(desc);
-  const int ns = is_composite(desc) ? desc->nsegments : 1;
-  const size_t xb = carve_bytes((size_t)N * desc->d * es), cn = carve_bytes((size_t)N * es);
-  return (size_t)(ns + 1 + (b && b->kind == NF_BASE_DENSE ? 1 : 0)) * xb + 3 * cn + carve_bytes((size_t)fkl_general_nb(N) * 8) +
-         carve_bytes(2 * (size_t)desc->d * es);
-}
-static size_t fkl_general_inner(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
-  if (is_composite(desc)) return composite_inner_need(ctx, desc, N);
-  nf_flow_desc inner = *desc;
-  inner.base = nullptr;
-  return ws_need_bound(ctx, &inner, N);
-}
-static size_t fkl_general_need(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
-  return fkl_general_inner(ctx, desc, N) + fkl_general_extra(desc, N);
-}
+// every segment's inverse output, the cotangent, a dense base's substitution scratch, three per-sample vectors, block
+// partials and the standard normal's two parameter vectors -- behind the segments' own intermediates
+struct FklGeneralBufs {
+  size_t in_need;
+  char *z[65], *gbar, *zbuf, *ladj, *tmp, *logq, *q0par;
+  double *partial;
+  FklGeneralBufs() {}
+  FklGeneralBufs(Carver &cv, nf_ctx *ctx, const nf_flow_desc *desc, long N) {
+    const size_t es = esize(desc->dtype), xe = (size_t)N * desc->d;
+    const nf_base *b = flow_base(desc);
+    nf_flow_desc inner = *desc;
+    inner.base = nullptr;
+    cv.skip(in_need = is_composite(desc) ? composite_inner_need(ctx, desc, N) : ws_need_bound(ctx, &inner, N));
+    const int ns = is_composite(desc) ? desc->nsegments : 1;
+    for (int s = 1; s <= ns; ++s) z[s] = cv.take<char>(xe * es);
+    gbar = cv.take<char>(xe * es);
+    zbuf = (b && b->kind == NF_BASE_DENSE) ? cv.take<char>(xe * es) : nullptr;
+    ladj = cv.take<char>((size_t)N * es);
+    tmp = cv.take<char>((size_t)N * es);
+    logq = cv.take<char>((size_t)N * es);
+    partial = cv.take<double>(fkl_general_nb(N));
+    q0par = cv.take<char>(2 * (size_t)desc->d * es);
+  }
+};
 
 static int fkl_general(nf_ctx *ctx, const nf_flow_desc *desc, const void *theta, const void *ys, int64_t N_local,
                        int64_t N_global, void *out) {
@@ -1388,26 +1497,12 @@ static int fkl_general(nf_ctx *ctx, const nf_flow_desc *desc, const void *theta,
   const bool comp = is_composite(desc);
   const nf_flow_desc *segs = comp ? desc->segments : &single;
   const int ns = comp ? desc->nsegments : 1;
-  if (!comp) {  // the shapes the single-family entry point refuses
-    const bool coupling_kind = single.kind == NF_KIND_REALNVP || single.kind == NF_KIND_NSF;
-    if (coupling_kind && !is_coupling(&single) && !nf_g64_supported(&single)) return NF_ERR_UNSUPPORTED;
-  }
-  const size_t in_need = fkl_general_inner(ctx, desc, N);
-  const size_t prev_guard = ctx->ws_guard;
-  NF_TRY(nf_ws_reserve(ctx, in_need + fkl_general_extra(desc, N)));
-  GuardReset gr{ctx, prev_guard};
-  Carver cv((char *)ctx->ws + in_need);
-  const size_t xe = (size_t)N * desc->d;
-  char *z[65];
-  for (int s = 1; s <= ns; ++s) z[s] = cv.take<char>(xe * es);
-  char *gbar = cv.take<char>(xe * es);
-  char *zbuf = (b && b->kind == NF_BASE_DENSE) ? cv.take<char>(xe * es) : nullptr;
-  char *ladj = cv.take<char>((size_t)N * es);
-  char *tmp = cv.take<char>((size_t)N * es);
-  char *logq = cv.take<char>((size_t)N * es);
-  double *partial = cv.take<double>(fkl_general_nb(N));
-  char *q0par = cv.take<char>(2 * (size_t)desc->d * es);
-  ctx->ws_guard = in_need;  // the segments' own intermediates stay in front of these buffers
+  if (!comp && !fkl_supported(&single)) return NF_ERR_UNSUPPORTED;  // the shapes the single-family entry point refuses
+  GuardReset gr{ctx, ctx->ws_guard};
+  FklGeneralBufs fb;
+  NF_TRY(ws_carve_guarded(ctx, &fb, desc, N));  // the segments' own intermediates stay in front of these buffers
+  char **z = fb.z, *gbar = fb.gbar, *zbuf = fb.zbuf, *ladj = fb.ladj, *tmp = fb.tmp, *logq = fb.logq, *q0par = fb.q0par;
+  double *partial = fb.partial;
 
   auto seg_theta = [&](int s) -> const char * {
     return comp ? (const char *)theta + (size_t)seg_theta_off(desc, s) * es : (const char *)theta;
@@ -1457,33 +1552,10 @@ static size_t composite_inner_need(nf_ctx *ctx, const nf_flow_desc *desc, long N
   }
   return m;
 }
-static size_t composite_extra_bytes(const nf_flow_desc *desc, long N) {
-  const size_t es = esize(desc->dtype);
-  return 2 * carve_bytes((size_t)N * desc->d * es) + 5 * carve_bytes((size_t)N * es) +
-         carve_bytes((size_t)nf_target_nblocks(N) * 8) + carve_bytes((size_t)nf_sum2_nblocks(N) * 8) + carve_bytes(64);
-}
 static long seg_theta_off(const nf_flow_desc *desc, int s) {
   long off = 0;
   for (int t = 0; t < s; ++t) off += nf_param_count(&desc->segments[t]);
   return off;
-}
-static int composite_bufs(nf_ctx *ctx, const nf_flow_desc *desc, long N, CompBufs *cb) {
-  const size_t es = esize(desc->dtype);
-  const size_t in_need = composite_inner_need(ctx, desc, N);
-  NF_TRY(nf_ws_reserve(ctx, in_need + composite_extra_bytes(desc, N)));
-  Carver cv((char *)ctx->ws + in_need);
-  cb->y = cv.take<char>((size_t)N * desc->d * es);
-  cb->gbar = cv.take<char>((size_t)N * desc->d * es);
-  cb->logq = cv.take<char>((size_t)N * es);
-  cb->ladj = cv.take<char>((size_t)N * es);
-  cb->tmp = cv.take<char>((size_t)N * es);
-  cb->lbar = cv.take<char>((size_t)N * es);
-  cb->spare = cv.take<char>((size_t)N * es);
-  cb->partial_t = cv.take<double>(nf_target_nblocks(N));
-  cb->partial_s = cv.take<double>(nf_sum2_nblocks(N));
-  cb->result = cv.take<double>(8);
-  ctx->ws_guard = in_need;
-  return NF_OK;
 }
 
 // forward: the LAST segment is applied first; inverse: the first.  layer >= 0: one bijector, flat index over the segments.
@@ -1520,9 +1592,8 @@ static int composite_apply(nf_ctx *ctx, const nf_flow_desc *desc, bool inverse, 
     return NF_ERR_ARG;
   }
   CompBufs cb;
-  const size_t prev_guard = ctx->ws_guard;
-  NF_TRY(composite_bufs(ctx, desc, N, &cb));
-  GuardReset gr{ctx, prev_guard};
+  GuardReset gr{ctx, ctx->ws_guard};
+  NF_TRY(ws_carve_guarded(ctx, &cb, desc, N));
   return composite_chain(ctx, desc, inverse, theta, x_in, N, y_out, ladj, cb);
 }
 
@@ -1531,9 +1602,8 @@ static int elbo_forward_composite(nf_ctx *ctx, const nf_flow_desc *desc, const n
                                   double *elbo_host) {
   const size_t es = esize(desc->dtype);
   CompBufs cb;
-  const size_t prev_guard = ctx->ws_guard;
-  NF_TRY(composite_bufs(ctx, desc, N, &cb));
-  GuardReset gr{ctx, prev_guard};
+  GuardReset gr{ctx, ctx->ws_guard};
+  NF_TRY(ws_carve_guarded(ctx, &cb, desc, N));
   if (xs) {
     NF_HIP(hipMemcpyAsync(cb.y, xs, (size_t)N * desc->d * es, hipMemcpyDeviceToDevice, ctx->stream));
     NF_TRY(nf_launch_base_logpdf(ctx, desc->dtype, desc->d, N, cb.y, cb.logq));
@@ -1549,15 +1619,22 @@ static int elbo_forward_composite(nf_ctx *ctx, const nf_flow_desc *desc, const n
 
 // training step of a composition: forward with every segment's tape kept (behind the segments' intermediates), target
 // and seed, then the segments' pullbacks from their tapes, last applied first
-static size_t vg_composite_extra(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
-  const size_t es = esize(desc->dtype);
-  return tape_bytes_of(ctx, desc, N) + 2 * carve_bytes((size_t)N * desc->d * es) + 2 * carve_bytes((size_t)N * es) +
-         carve_bytes((size_t)nf_target_nblocks(N) * 8);
-}
-static size_t vg_composite_need(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
-  const size_t a = tape_need(ctx, desc, N, false), b = tape_need(ctx, desc, N, true);
-  return (a > b ? a : b) + vg_composite_extra(ctx, desc, N);
-}
+struct VgCompositeBufs {
+  size_t in_need;
+  char *y, *gbar, *logq, *ladj, *tape;
+  double *partial;
+  VgCompositeBufs() {}
+  VgCompositeBufs(Carver &cv, nf_ctx *ctx, const nf_flow_desc *desc, long N) {
+    const size_t es = esize(desc->dtype);
+    cv.skip(in_need = tape_inner_need(ctx, desc, N));
+    y = cv.take<char>((size_t)N * desc->d * es);
+    gbar = cv.take<char>((size_t)N * desc->d * es);
+    logq = cv.take<char>((size_t)N * es);
+    ladj = cv.take<char>((size_t)N * es);
+    partial = cv.take<double>(nf_target_nblocks(N));
+    tape = cv.take<char>(tape_bytes_of(ctx, desc, N));
+  }
+};
 static int value_and_grad_composite(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, const void *theta,
                                     const void *xs, int64_t N_local, int64_t N_global, uint64_t seed, uint64_t sample_offset,
                                     uint32_t stream_id, void *out) {
@@ -1567,19 +1644,11 @@ static int value_and_grad_composite(nf_ctx *ctx, const nf_flow_desc *desc, const
   const size_t es = esize(dt);
   if (N == 0) return nf_launch_fill(ctx, dt, out, P + 1, 0.0);
   const double inv = 1.0 / (double)N_global;
-  const size_t a = tape_need(ctx, desc, N, false), b = tape_need(ctx, desc, N, true);
-  const size_t in_need = a > b ? a : b;
-  const size_t prev_guard = ctx->ws_guard;
-  NF_TRY(nf_ws_reserve(ctx, in_need + vg_composite_extra(ctx, desc, N)));
-  GuardReset gr{ctx, prev_guard};
-  Carver cv((char *)ctx->ws + in_need);
-  char *y = cv.take<char>((size_t)N * desc->d * es);
-  char *gbar = cv.take<char>((size_t)N * desc->d * es);
-  char *logq = cv.take<char>((size_t)N * es);
-  char *ladj = cv.take<char>((size_t)N * es);
-  double *partial = cv.take<double>(nf_target_nblocks(N));
-  char *tape = cv.take<char>(tape_bytes_of(ctx, desc, N));
-  if (in_need) ctx->ws_guard = in_need;
+  GuardReset gr{ctx, ctx->ws_guard};
+  VgCompositeBufs vb;
+  NF_TRY(ws_carve_guarded(ctx, &vb, desc, N));
+  char *y = vb.y, *gbar = vb.gbar, *logq = vb.logq, *ladj = vb.ladj, *tape = vb.tape;
+  double *partial = vb.partial;
   if (xs) {
     NF_HIP(hipMemcpyAsync(y, xs, (size_t)N * desc->d * es, hipMemcpyDeviceToDevice, ctx->stream));
     NF_TRY(nf_launch_base_logpdf(ctx, dt, desc->d, N, y, logq));
@@ -1597,9 +1666,8 @@ static int value_and_grad_composite(nf_ctx *ctx, const nf_flow_desc *desc, const
 static int loglikelihood_composite(nf_ctx *ctx, const nf_flow_desc *desc, const void *theta, const void *ys, long N,
                                    void *logliks_out, double *ll_host) {
   CompBufs cb;
-  const size_t prev_guard = ctx->ws_guard;
-  NF_TRY(composite_bufs(ctx, desc, N, &cb));
-  GuardReset gr{ctx, prev_guard};
+  GuardReset gr{ctx, ctx->ws_guard};
+  NF_TRY(ws_carve_guarded(ctx, &cb, desc, N));
   NF_TRY(composite_chain(ctx, desc, true, theta, ys, N, cb.y, cb.ladj, cb));
   NF_TRY(nf_launch_base_logpdf(ctx, desc->dtype, desc->d, N, cb.y, cb.logq));
   NF_TRY(nf_launch_sum2(ctx, desc->dtype, N, cb.logq, cb.ladj, logliks_out, cb.partial_s, 1.0 / (double)N));
@@ -1612,12 +1680,6 @@ static int loglikelihood_composite(nf_ctx *ctx, const nf_flow_desc *desc, const 
 // x = mu + L eps, and (ii) log q0(x).  The wrappers below produce x in a buffer of their own, run the standard-normal
 // entry point on it as caller-supplied xs (every fused / MFMA kernel untouched), and add the exact per-sample
 // correction  log N(x; 0, I) - log q0(x)  to the ELBO terms; gradients with respect to theta are unaffected.
-static int elbo_forward(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, const void *theta,
-                        const void *xs, long N, uint64_t seed, uint64_t off, uint32_t stream_id, void *elbos_out,
-                        double *elbo_host);
-extern "C" int nf_base_logpdf_general(nf_ctx *ctx, int32_t dtype, const nf_base *base, int32_t d, int64_t N, const void *x,
-                                      void *logq_out);
-
 static int elbo_forward_general_base(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, const void *theta,
                                      const void *xs, long N, uint64_t seed, uint64_t off, uint32_t stream_id,
                                      void *elbos_out, double *elbo_host) {
@@ -1625,9 +1687,8 @@ static int elbo_forward_general_base(nf_ctx *ctx, const nf_flow_desc *desc, cons
   nf_flow_desc inner = *desc;
   inner.base = nullptr;
   BaseBufs bb;
-  const size_t prev_guard = ctx->ws_guard;
-  NF_TRY(base_bufs(ctx, desc, &inner, N, &bb));
-  GuardReset gr{ctx, prev_guard};
+  GuardReset gr{ctx, ctx->ws_guard};
+  NF_TRY(ws_carve_guarded(ctx, &bb, desc, N));
   const void *x = xs;
   if (!xs) {
     NF_TRY(base_draw(ctx, desc, N, seed, off, stream_id, bb.x, nullptr));
@@ -1659,9 +1720,8 @@ static int value_and_grad_general_base(nf_ctx *ctx, const nf_flow_desc *desc, co
   nf_flow_desc inner = *desc;
   inner.base = nullptr;
   BaseBufs bb;
-  const size_t prev_guard = ctx->ws_guard;
-  NF_TRY(base_bufs(ctx, desc, &inner, N, &bb));
-  GuardReset gr{ctx, prev_guard};
+  GuardReset gr{ctx, ctx->ws_guard};
+  NF_TRY(ws_carve_guarded(ctx, &bb, desc, N));
   const void *x = xs;
   if (!xs) {
     NF_TRY(base_draw(ctx, desc, N, seed, sample_offset, stream_id, bb.x, nullptr));
@@ -1684,9 +1744,8 @@ static int loglikelihood_general_base(nf_ctx *ctx, const nf_flow_desc *desc, con
   nf_flow_desc inner = *desc;
   inner.base = nullptr;
   BaseBufs bb;
-  const size_t prev_guard = ctx->ws_guard;
-  NF_TRY(base_bufs(ctx, desc, &inner, N, &bb));
-  GuardReset gr{ctx, prev_guard};
+  GuardReset gr{ctx, ctx->ws_guard};
+  NF_TRY(ws_carve_guarded(ctx, &bb, desc, N));
   // z = T^-1 y and ladj_inv with the public inverse, then log q0(z) with the general density
   NF_TRY(nf_flow_inv(ctx, &inner, theta, ys, N, bb.x, bb.tmp));
   NF_TRY(nf_launch_base_general_logpdf(ctx, desc->dtype, b->kind, desc->d, N, b->mu, b->scale, b->logdet, bb.x, bb.corr, nullptr, bb.z));
@@ -1725,6 +1784,46 @@ extern "C" int nf_base_logpdf_general(nf_ctx *ctx, int32_t dtype, const nf_base 
 }
 
 // ---- training step -------------------------------------------------------------------------
+struct VgBufs {
+  bool cp, wide, simple_kind, simple_step;
+  long nb, stash_nc;  // the target kernel's loss partials; samples per stash chunk (0: no stash)
+  int grid;
+  char *x, *gbar, *x0, *logq, *ladj, *slab, *sws;
+  double *partial;
+  float *stash;
+  void *rqs_tape;
+  VgBufs() {}
+  VgBufs(Carver &cv, nf_ctx *ctx, const nf_flow_desc *desc, long N) {
+    const size_t es = esize(desc->dtype);
+    cp = is_coupling(desc);
+    wide = cp && is_wide(desc);
+    nb = cp ? nf_target_tiled_nblocks(N) : nf_target_nblocks(N);
+    grid = cp ? coupling_bwd_grid(ctx, desc, N) : 0;
+    simple_kind = !cp && !is_g64(desc) && desc->kind != NF_KIND_HAMILTONIAN;
+    // planar / radial / mean-field within the register budget: the whole step in one launch, nothing stashed
+    simple_step = simple_kind && nf_simple_step_supported(desc);
+    const size_t simple_ws = cp ? 0 : simple_step ? nf_simple_step_ws_bytes(ctx, desc, N) : flat_bwd_ws_bytes(ctx, desc, N);
+    // LDS-resident RealNVP: activation stash for the reverse pass, the batch in chunks if it exceeds the budget (in-library
+    // draws; caller-supplied draws take one chunk or the recompute kernel)
+    stash_nc = cp ? affine_stash_chunk(ctx, desc, N) : 0;
+    const size_t stash_b = stash_nc ? affine_stash_bytes(ctx, desc, stash_nc) : 0;
+    const size_t slabf = wide ? nf_wide_train_ws_floats(ctx, desc, N)
+                              : cp ? chunked_slab_floats(ctx, desc, N, stash_nc, coupling_slab_floats(ctx, desc, N)) : 0;
+    const size_t xe = cp ? tiled_elems(desc, N) : simple_step ? 0 : (size_t)N * desc->d;
+    const size_t rqs_b = cp ? rqs_tape_b(desc, N) : 0;
+    x = cv.take<char>(xe * es);
+    gbar = cv.take<char>(xe * es);
+    x0 = cv.take<char>(xe * es);  // flow input kept for the non-invertible (planar/radial) recompute
+    logq = cv.take<char>((size_t)N * es);
+    ladj = cv.take<char>((size_t)N * es);
+    partial = cv.take<double>(elbo_npartial(ctx, desc, N));
+    cv.take<double>(8);  // (a result slot no path reads: kept so that every buffer behind it keeps its offset)
+    slab = cv.take<char>(slabf * es);
+    sws = cv.take<char>(simple_ws);
+    stash = stash_b ? cv.take<float>(stash_b / 4) : nullptr;
+    rqs_tape = rqs_b ? (void *)cv.take<char>(rqs_b) : nullptr;  // spline couplings: the forward's bins and xi
+  }
+};
 extern "C" int nf_elbo_value_and_grad(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target,
                                       const void *theta, const void *xs, int64_t N_local, int64_t N_global,
                                       uint64_t seed, uint64_t sample_offset, uint32_t stream_id, void *out) {
@@ -1741,63 +1840,29 @@ extern "C" int nf_elbo_value_and_grad(nf_ctx *ctx, const nf_flow_desc *desc, con
   const size_t es = esize(dt);
   if (N == 0) return nf_launch_fill(ctx, dt, out, P + 1, 0.0);
   const double inv = 1.0 / (double)N_global;
-  const bool cp = is_coupling(desc);
-  const long nb = cp ? nf_target_tiled_nblocks(N) : nf_target_nblocks(N);
-  const long nb_alloc = nb < ctx->num_cu ? ctx->num_cu : nb;  // the fused forward leaves one partial per workgroup
-  const int grid = cp ? coupling_bwd_grid(ctx, desc, N) : 0;
-  const bool simple_kind = !cp && !is_g64(desc) && desc->kind != NF_KIND_HAMILTONIAN;
-  // planar / radial / mean-field within the register budget: the whole step in one launch, nothing stashed
-  constexpr bool no_step = false;  // (round 6: the NF_SIMPLE_STASH A/B switch is retired -- its question is answered, README "switches")
-  const bool simple_step = simple_kind && !no_step && nf_simple_step_supported(desc);
-  const size_t simple_ws = cp ? 0 : simple_step ? nf_simple_step_ws_bytes(ctx, desc, N) : flat_bwd_ws_bytes(ctx, desc, N);
-  // LDS-resident RealNVP: activation stash for the reverse pass, the batch in chunks if it exceeds the budget (in-library
-  // draws; caller-supplied draws take one chunk or the recompute kernel)
-  const bool fusable = cp && elbo_fusable(desc, target, xs);
-  const long stash_nc = cp ? affine_stash_chunk(ctx, desc, N) : 0;
-  const int stash_nch = stash_nc ? (int)((N + stash_nc - 1) / stash_nc) : 0;
-  const size_t stash_b = stash_nc ? affine_stash_bytes(ctx, desc, stash_nc) : 0;
-  const bool wide = cp && is_wide(desc);
-  (void)stash_nch;
-  const size_t slabf = wide ? nf_wide_train_ws_floats(ctx, desc, N)
-                            : cp ? chunked_slab_floats(ctx, desc, N, stash_nc, coupling_slab_floats(ctx, desc, N)) : 0;
-  const size_t xe = cp ? tiled_elems(desc, N) : simple_step ? 0 : (size_t)N * desc->d;
-  const size_t rqs_b = cp ? rqs_tape_b(desc, N) : 0;
-  const size_t need = 3 * carve_bytes(xe * es) + 2 * carve_bytes((size_t)N * es) + carve_bytes((size_t)nb_alloc * 8) +
-                      carve_bytes(64) + carve_bytes(slabf * es) + carve_bytes(simple_ws) + carve_bytes(stash_b) + rqs_b;
-  NF_TRY(nf_ws_reserve(ctx, need));
-  Carver cv(ctx->ws);
-  char *x = cv.take<char>(xe * es);
-  char *gbar = cv.take<char>(xe * es);
-  char *x0 = cv.take<char>(xe * es);  // flow input kept for the non-invertible (planar/radial) recompute
-  char *logq = cv.take<char>((size_t)N * es);
-  char *ladj = cv.take<char>((size_t)N * es);
-  double *partial = cv.take<double>(nb_alloc);
-  double *result = cv.take<double>(8);
-  (void)result;
-  char *slab = cv.take<char>(slabf * es);
-  char *sws = cv.take<char>(simple_ws);
-  float *stash = stash_b ? cv.take<float>(stash_b / 4) : nullptr;
-  void *rqs_tape = rqs_b ? (void *)cv.take<char>(rqs_b) : nullptr;  // spline couplings: the forward's bins and xi
+  VgBufs b;
+  NF_TRY(ws_carve(ctx, &b, desc, N));
+  const bool cp = b.cp, simple_kind = b.simple_kind, simple_step = b.simple_step, wide = b.wide;
+  const long nb = b.nb;
+  const int grid = b.grid;
+  char *x = b.x, *gbar = b.gbar, *x0 = b.x0, *logq = b.logq, *ladj = b.ladj, *slab = b.slab, *sws = b.sws;
+  double *partial = b.partial;
+  float *stash = b.stash;
+  void *rqs_tape = b.rqs_tape;
 
-  if (fusable) {
+  if (cp && elbo_fusable(desc, target, xs)) {
     float *xt = (float *)x, *gt = (float *)gbar;
     NF_TRY(coupling_pack(ctx, desc, (const float *)theta));
     if (stash) {  // forward with stash + reverse pass from it, chunk by chunk: no recompute, the state is not touched
-      const long stride = coupling_slab_floats(ctx, desc, N);
-      long nslab = 0, npart = 0;
-      for (long o = 0; o < N; o += stash_nc) {
-        const long nc = N - o < stash_nc ? N - o : stash_nc;
-        const int gc = coupling_bwd_grid(ctx, desc, nc);
+      ChunkCounts cc;
+      NF_TRY(stash_chunk_loop(ctx, desc, N, b.stash_nc, stash, gt, inv, (float *)slab, false, &cc, [&](long o, long nc, long npart, long *left) {
         // (y itself is not written: the stashed reverse pass reads gt and the stash, and nothing else follows; nor is the
         // cotangent of the draws, which a training step does not read)
-        NF_TRY(fused_chain_elbo(ctx, desc, target, nc, seed, sample_offset + (uint64_t)o, stream_id, nullptr,
-                                gt + o * desc->d, -inv, partial + npart, -inv, stash));
-        NF_TRY(nf_affine_bwd_stashed(ctx, desc, stash, gt + o * desc->d, nullptr, (float)(-inv), nc,
-                                     (float *)slab + nslab * stride, stride, gc, false, true));
-        nslab += gc;
-        npart += nf_affine_chain_grid(ctx, nc);
-      }
-      return nf_affine_reduce_slabs(ctx, desc, (const float *)slab, (int)nslab, (float *)out, partial, (int)npart, (float *)out + P);
+        *left = nf_affine_chain_grid(ctx, nc);
+        return fused_chain_elbo(ctx, desc, target, nc, seed, sample_offset + (uint64_t)o, stream_id, nullptr, gt + o * desc->d, -inv,
+                                partial + npart, -inv, stash);
+      }));
+      return nf_affine_reduce_slabs(ctx, desc, (const float *)slab, (int)cc.nslab, (float *)out, partial, (int)cc.npart, (float *)out + P);
     }
     NF_TRY(fused_chain_elbo(ctx, desc, target, N, seed, sample_offset, stream_id, xt, gt, -inv, partial, -inv,
                             is_nsf(desc) ? (float *)rqs_tape : nullptr));
@@ -1838,22 +1903,16 @@ extern "C" int nf_elbo_value_and_grad(nf_ctx *ctx, const nf_flow_desc *desc, con
       // LDS-resident RealNVP with caller-supplied draws or a target other than the diagonal Gaussian: the plain forward
       // chain leaves the stash, too -- chunk by chunk through the stash buffer like the fused form above
       NF_TRY(coupling_pack(ctx, desc, (const float *)theta));
-      const long stride = coupling_slab_floats(ctx, desc, N);
-      long nslab = 0, npart = 0;
-      for (long o = 0; o < N; o += stash_nc) {
-        const long nc = N - o < stash_nc ? N - o : stash_nc;
-        const int gc = coupling_bwd_grid(ctx, desc, nc);
+      ChunkCounts cc;
+      NF_TRY(stash_chunk_loop(ctx, desc, N, b.stash_nc, stash, gt, inv, (float *)slab, false, &cc, [&](long o, long nc, long npart, long *left) {
         NF_TRY(nf_affine_chain(ctx, desc, false, xt + o * desc->d, nc, (float *)ladj + o, stash));
         // gt = d(-elbo/Ng)/dy = -(1/Ng) grad logp(y);  partial sums of -elbo_j/Ng
-        NF_TRY(nf_launch_target_tiled(ctx, target, desc->d, nc, xt + o * desc->d, (const float *)logq + o, (const float *)ladj + o,
-                                      gt + o * desc->d, -inv, nullptr, partial + npart, -inv));
-        NF_TRY(nf_affine_bwd_stashed(ctx, desc, stash, gt + o * desc->d, nullptr, (float)(-inv), nc,
-                                     (float *)slab + nslab * stride, stride, gc, false, true));
-        nslab += gc;
-        npart += nf_target_tiled_nblocks(nc);
-      }
-      NF_TRY(nf_launch_finish_sum(ctx, partial, npart, 0, nullptr, (float *)out + P, nullptr));
-      return nf_affine_reduce_slabs(ctx, desc, (const float *)slab, (int)nslab, (float *)out);
+        *left = nf_target_tiled_nblocks(nc);
+        return nf_launch_target_tiled(ctx, target, desc->d, nc, xt + o * desc->d, (const float *)logq + o, (const float *)ladj + o,
+                                      gt + o * desc->d, -inv, nullptr, partial + npart, -inv);
+      }));
+      NF_TRY(nf_launch_finish_sum(ctx, partial, cc.npart, 0, nullptr, (float *)out + P, nullptr));
+      return nf_affine_reduce_slabs(ctx, desc, (const float *)slab, (int)cc.nslab, (float *)out);
     }
     NF_TRY(coupling_chain_tiled(ctx, desc, false, (const float *)theta, xt, N, (float *)ladj, -1, rqs_tape));
     // gt = d(-elbo/Ng)/dy = -(1/Ng) grad logp(y);  partial sums of -elbo_j/Ng
@@ -1968,132 +2027,156 @@ static inline unsigned long long flow_sig(const nf_flow_desc *d) {
   for (int i = 0; i < d->n_hidden && i < 4; ++i) mix((unsigned long long)d->hdims[i]);
   return h | (1ull << 63);
 }
-static bool step_fusable(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, long N) {
-  constexpr bool off = false;  // (round 6: the NF_STEP_UNFUSED A/B switch is retired -- its question is answered, README "switches")
-  if (off || flow_base(desc) || is_composite(desc) || desc->dtype != NF_DTYPE_F32) return false;
-  if (!(desc->kind == NF_KIND_REALNVP && nf_affine_supported(desc))) return false;
-  if (!elbo_fusable(desc, target, nullptr)) return false;
-  return affine_stash_chunk(ctx, desc, N) > 0;
+// packed images: those the previous step's epilogue left, or a fresh pack
+// (ONLY under nf_ctx_set_weight_cache(ctx, 1): by default every step packs from theta, one 8 us launch, so a theta
+// that was edited in place, or freed and re-allocated at the same address, can never meet stale images)
+static int step_images_ensure(nf_ctx *ctx, const nf_flow_desc *desc, const float *theta) {
+  if (ctx->wimg_cache && ctx->wimg && ctx->wimg_owner == (const void *)theta && ctx->wimg_sig == flow_sig(desc)) return NF_OK;
+  return coupling_pack(ctx, desc, theta);
 }
-static size_t step_fused_need(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
-  const size_t te = tiled_elems(desc, N);
-  const long nb = nf_target_tiled_nblocks(N);
-  const long nb_alloc = nb < ctx->num_cu ? ctx->num_cu : nb;
-  const long snc = affine_stash_chunk(ctx, desc, N);
-  return carve_bytes(te * 4) + carve_bytes((size_t)nb_alloc * 8) +
-         carve_bytes(chunked_slab_floats(ctx, desc, N, snc, coupling_slab_floats(ctx, desc, N)) * 4) +
-         carve_bytes(snc ? affine_stash_bytes(ctx, desc, snc) : 0) + carve_bytes((size_t)nf_affine_epilogue_blocks(desc) * 8);
-}
-static int elbo_step_fused(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, float *theta, float *m, float *v,
-                           long N, uint64_t seed, uint32_t step_val, uint32_t *step_ptr, double lr, double beta1, double beta2,
-                           double eps) {
-  const long P = nf_param_count(desc);
-  const int world = ctx->comm ? ctx->comm_size : 1;
-  const long Ng = N * world;
-  const uint64_t off0 = (uint64_t)(ctx->comm ? ctx->comm_rank : 0) * (uint64_t)N;
-  const double inv = 1.0 / (double)Ng;
-  const size_t te = tiled_elems(desc, N);
-  const long nb = nf_target_tiled_nblocks(N);
-  const long nb_alloc = nb < ctx->num_cu ? ctx->num_cu : nb;
-  const long stash_nc = affine_stash_chunk(ctx, desc, N);
-  const long stride = coupling_slab_floats(ctx, desc, N);
-  const size_t slabf = chunked_slab_floats(ctx, desc, N, stash_nc, stride);
-  const size_t stash_b = affine_stash_bytes(ctx, desc, stash_nc);
-  const long eblocks = nf_affine_epilogue_blocks(desc);
-  NF_TRY(nf_ws_reserve(ctx, step_fused_need(ctx, desc, N)));
-  Carver cv(ctx->ws);
-  float *gt = cv.take<float>(te);  // (no buffer for y: the forward keeps it in registers, the reverse pass reads gt and the stash)
-  double *partial = cv.take<double>(nb_alloc);
-  float *slab = cv.take<float>(slabf);
-  float *stash = cv.take<float>(stash_b / 4);
-  double *gpart = cv.take<double>(eblocks);
-  float *gbuf = (float *)ctx->gbuf;
-  // packed images: those the previous step's epilogue left, or a fresh pack
-  // (ONLY under nf_ctx_set_weight_cache(ctx, 1): by default every step packs from theta, one 8 us launch, so a theta
-  // that was edited in place, or freed and re-allocated at the same address, can never meet stale images)
-  constexpr bool repack = false;  // (round 6: the NF_STEP_REPACK A/B switch is retired -- its question is answered, README "switches")
-  if (repack || !ctx->wimg_cache ||
-      !(ctx->wimg && ctx->wimg_owner == (const void *)theta && ctx->wimg_sig == flow_sig(desc))) {
-    NF_TRY(coupling_pack(ctx, desc, theta));
-  }
-  long nslab = 0, npart = 0;
-  for (long o = 0; o < N; o += stash_nc) {
-    const long nc = N - o < stash_nc ? N - o : stash_nc;
-    const int gc = coupling_bwd_grid(ctx, desc, nc);
-    NF_TRY(nf_affine_chain_elbo(ctx, desc, nc, seed, off0 + (uint64_t)o, step_val, target,
-                                nullptr, gt + o * desc->d, -inv, partial + npart, -inv, stash, step_ptr));
-    NF_TRY(nf_affine_bwd_stashed(ctx, desc, stash, gt + o * desc->d, nullptr, (float)(-inv), nc, slab + nslab * stride, stride, gc,
-                                 false, true));
-    nslab += gc;
-    npart += nf_affine_chain_grid(ctx, nc);
-  }
-  if (world == 1) {
-    NF_TRY(nf_affine_epilogue(ctx, desc, 3, slab, (int)nslab, gbuf, partial, (int)npart, theta, m, v, lr, beta1, beta2, eps, step_val,
-                              step_ptr, gpart));
-  } else {
-    NF_TRY(nf_affine_epilogue(ctx, desc, 1, slab, (int)nslab, gbuf, partial, (int)npart, nullptr, nullptr, nullptr, lr, beta1, beta2,
-                              eps, step_val, nullptr, gpart));
-    NF_TRY(nf_allreduce_grad_loss(ctx, NF_DTYPE_F32, gbuf, P + 1));
-    NF_TRY(nf_affine_epilogue(ctx, desc, 2, nullptr, 0, gbuf, nullptr, 0, theta, m, v, lr, beta1, beta2, eps, step_val, step_ptr,
-                              gpart));
-  }
-  // norm(g) = sqrt of the epilogue's block partials (and, in the graph-replay form, the step counter's increment)
-  NF_TRY(nf_launch_finish_sum(ctx, gpart, eblocks, 1, nullptr, gbuf + P + 1, nullptr, step_ptr));
+// the step's epilogue has written the images of the UPDATED theta
+static void step_images_written(nf_ctx *ctx, const nf_flow_desc *desc, const float *theta) {
   ctx->wimg_owner = theta;
   ctx->wimg_sig = flow_sig(desc);
+}
+
+// One training-step call.  target: the ELBO step on in-library draws; ys (target == nullptr): the forward-KL step on data.
+// step_device != nullptr: the graph-capturable form (step is 0 then).
+struct StepCall {
+  const nf_target *target;
+  const float *ys;
+  long N, Ng;
+  uint64_t seed;
+  float *theta, *m, *v;
+  uint32_t step, *step_device;
+  double lr, beta1, beta2, eps;
+};
+
+// sizing (nf_workspace_bytes): any target
+static bool step_fusable(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, long N, bool sizing = false) {
+  if (flow_base(desc) || is_composite(desc) || desc->dtype != NF_DTYPE_F32) return false;
+  if (!(desc->kind == NF_KIND_REALNVP && nf_affine_supported(desc))) return false;
+  if (!elbo_fusable(desc, target, nullptr, sizing)) return false;
+  return affine_stash_chunk(ctx, desc, N) > 0;
+}
+static bool fkl_step_fusable(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
+  if (N < 1 || flow_base(desc) || is_composite(desc) || desc->dtype != NF_DTYPE_F32) return false;
+  if (!(desc->kind == NF_KIND_REALNVP && nf_affine_supported(desc) && nf_affine_chain_fkl_ok(desc))) return false;
+  return affine_stash_chunk(ctx, desc, N) > 0;
+}
+// loss partials of a chunked forward-KL step: one per workgroup of every chunk's chain launch
+static long fkl_step_npart(nf_ctx *ctx, long N, long chunk) {
+  long n = 0;
+  for (long o = 0; o < N; o += chunk) n += nf_affine_chain_grid(ctx, N - o < chunk ? N - o : chunk);
+  return n;
+}
+// cotangent tiles (no buffer for y: the forward keeps it in registers, the reverse pass reads gt and the stash), `npartial`
+// loss partials, every chunk's gradient slabs, one chunk's stash, the epilogue's block partials of ||g||^2
+struct AffineStepBufs {
+  long stash_nc, eblocks;
+  float *gt, *slab, *stash;
+  double *partial, *gpart;
+  AffineStepBufs() {}
+  AffineStepBufs(Carver &cv, nf_ctx *ctx, const nf_flow_desc *desc, long N, long npartial) {
+    stash_nc = affine_stash_chunk(ctx, desc, N);
+    eblocks = nf_affine_epilogue_blocks(desc);
+    gt = cv.take<float>(tiled_elems(desc, N));
+    partial = cv.take<double>(npartial);
+    slab = cv.take<float>(chunked_slab_floats(ctx, desc, N, stash_nc, coupling_slab_floats(ctx, desc, N)));
+    stash = cv.take<float>(affine_stash_bytes(ctx, desc, stash_nc) / 4);
+    gpart = cv.take<double>(eblocks);
+  }
+};
+// the step tail: slab sum -> gradient and loss, Adam and the updated images in one epilogue launch, or split around ONE
+// all-reduce of [grad ; loss] (P + 1 floats) under a communicator; then norm(g) = sqrt of the epilogue's block partials
+// (and, in the graph-replay form, the step counter's increment)
+static int affine_step_tail(nf_ctx *ctx, const nf_flow_desc *desc, const StepCall &c, const AffineStepBufs &b, const ChunkCounts &cc) {
+  const long P = nf_param_count(desc);
+  float *gbuf = (float *)ctx->gbuf;
+  if (!ctx->comm || ctx->comm_size == 1) {
+    NF_TRY(nf_affine_epilogue(ctx, desc, 3, b.slab, (int)cc.nslab, gbuf, b.partial, (int)cc.npart, c.theta, c.m, c.v, c.lr, c.beta1, c.beta2,
+                              c.eps, c.step, c.step_device, b.gpart));
+  } else {
+    NF_TRY(nf_affine_epilogue(ctx, desc, 1, b.slab, (int)cc.nslab, gbuf, b.partial, (int)cc.npart, nullptr, nullptr, nullptr, c.lr, c.beta1,
+                              c.beta2, c.eps, c.step, nullptr, b.gpart));
+    NF_TRY(nf_allreduce_grad_loss(ctx, NF_DTYPE_F32, gbuf, P + 1));
+    NF_TRY(nf_affine_epilogue(ctx, desc, 2, nullptr, 0, gbuf, nullptr, 0, c.theta, c.m, c.v, c.lr, c.beta1, c.beta2, c.eps, c.step,
+                              c.step_device, b.gpart));
+  }
+  return nf_launch_finish_sum(ctx, b.gpart, b.eblocks, 1, nullptr, gbuf + P + 1, nullptr, c.step_device);
+}
+// fwd(o, nc, gt, partial, stash): the fused forward of the chunk of nc samples at o (one partial per workgroup of its launch)
+template <class F>
+static int affine_step_fused(nf_ctx *ctx, const nf_flow_desc *desc, const StepCall &c, long npartial, bool inv_dir, F fwd) {
+  AffineStepBufs b;
+  NF_TRY(ws_carve(ctx, &b, desc, c.N, npartial));
+  NF_TRY(step_images_ensure(ctx, desc, c.theta));
+  ChunkCounts cc;
+  NF_TRY(stash_chunk_loop(ctx, desc, c.N, b.stash_nc, b.stash, b.gt, 1.0 / (double)c.Ng, b.slab, inv_dir, &cc,
+                          [&](long o, long nc, long npart, long *left) {
+                            *left = nf_affine_chain_grid(ctx, nc);
+                            return fwd(o, nc, b.gt + o * desc->d, b.partial + npart, b.stash);
+                          }));
+  NF_TRY(affine_step_tail(ctx, desc, c, b, cc));
+  step_images_written(ctx, desc, c.theta);
   return NF_OK;
 }
 
-// The same for LDS-resident spline couplings on ONE rank (round 6): fused forward (draws + chain + target + loss partials, leaving the
-// spline tape; k_rqs_chain<FUSED> for the diagonal Gaussian, k_rqs_chain_tgt for the other built-in targets; step_ptr as above), one reverse launch per coupling, and nf_rqs_epilogue (loss, slab reduction, Adam, the updated images) -- four launches
-// fewer than nf_elbo_value_and_grad + nf_adam_update + the next step's pack.  Multi-rank contexts keep the generic sequence (the
-// all-reduce sits between the reduction and Adam).
-static bool step_fusable_rqs(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target) {
+// The same for LDS-resident spline couplings on ONE rank: fused forward (draws + chain + target + loss partials, or the
+// inverse chain on data with the seed z / N_global; either leaves the spline tape), one reverse launch per coupling, and
+// nf_rqs_epilogue (loss, slab reduction, Adam, the updated images) -- four launches fewer than the split sequence + the next
+// step's pack.  Multi-rank contexts keep the split sequence (the all-reduce sits between the reduction and Adam).
+// sizing (nf_workspace_bytes): any target, whatever the communicator
+static bool step_fusable_rqs(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, bool sizing = false) {
 #ifdef NF_STEP_RQS_UNFUSED  // A/B builds (tools/ab_build.py): the generic sequence
   return false;
 #endif
-  if (ctx->comm || flow_base(desc) || is_composite(desc) || desc->dtype != NF_DTYPE_F32) return false;
-  return desc->kind == NF_KIND_NSF && nf_rqs_supported(desc) && elbo_fusable(desc, target, nullptr);
+  if ((ctx->comm && !sizing) || flow_base(desc) || is_composite(desc) || desc->dtype != NF_DTYPE_F32) return false;
+  return desc->kind == NF_KIND_NSF && nf_rqs_supported(desc) && elbo_fusable(desc, target, nullptr, sizing);
 }
-static size_t step_fused_need_rqs(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
-  const size_t te = tiled_elems(desc, N);
-  const long nb = nf_target_tiled_nblocks(N);
-  const long nb_alloc = nb < ctx->num_cu ? ctx->num_cu : nb;
-  return 2 * carve_bytes(te * 4) + carve_bytes((size_t)nb_alloc * 8) +
-         carve_bytes((size_t)coupling_bwd_grid(ctx, desc, N) * coupling_slab_floats(ctx, desc, N) * 4) + rqs_tape_b(desc, N) +
-         carve_bytes((size_t)nf_rqs_epilogue_blocks(desc) * 8);
+// the LDS-resident geometries with a forward-KL chain kernel
+static bool fkl_step_fusable_rqs(nf_ctx *ctx, const nf_flow_desc *desc, long N, bool sizing = false) {
+  if (N < 1 || (ctx->comm && !sizing) || flow_base(desc) || is_composite(desc) || desc->dtype != NF_DTYPE_F32) return false;
+  return desc->kind == NF_KIND_NSF && nf_rqs_supported(desc) && nf_rqs_chain_fkl_ok(desc);
 }
-static int elbo_step_fused_rqs(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, float *theta, float *m, float *v, long N,
-                               uint64_t seed, uint32_t step_val, uint32_t *step_ptr, double lr, double beta1, double beta2, double eps) {
+struct RqsStepBufs {
+  int grid;
+  long stride, eblocks;
+  float *xt, *gt, *slab;
+  double *partial, *gpart;
+  void *tape;
+  RqsStepBufs() {}
+  RqsStepBufs(Carver &cv, nf_ctx *ctx, const nf_flow_desc *desc, long N, long npartial) {
+    grid = coupling_bwd_grid(ctx, desc, N);
+    stride = coupling_slab_floats(ctx, desc, N);
+    eblocks = nf_rqs_epilogue_blocks(desc);
+    xt = cv.take<float>(tiled_elems(desc, N));
+    gt = cv.take<float>(tiled_elems(desc, N));
+    partial = cv.take<double>(npartial);
+    slab = cv.take<float>((size_t)grid * stride);
+    tape = (void *)cv.take<char>(rqs_tape_b(desc, N));
+    gpart = cv.take<double>(eblocks);
+  }
+};
+// fwd(xt, gt, partial, tape): the fused forward of the whole batch (one partial per workgroup of the chain launch)
+template <class F>
+static int rqs_step_fused(nf_ctx *ctx, const nf_flow_desc *desc, const StepCall &c, long npartial, bool inv_dir, F fwd) {
   const long P = nf_param_count(desc);
-  const double inv = 1.0 / (double)N;
-  const size_t te = tiled_elems(desc, N);
-  const long nb = nf_target_tiled_nblocks(N);
-  const long nb_alloc = nb < ctx->num_cu ? ctx->num_cu : nb;
-  const int grid = coupling_bwd_grid(ctx, desc, N);
-  const long stride = coupling_slab_floats(ctx, desc, N);
-  const long eblocks = nf_rqs_epilogue_blocks(desc);
-  NF_TRY(nf_ws_reserve(ctx, step_fused_need_rqs(ctx, desc, N)));
-  Carver cv(ctx->ws);
-  float *xt = cv.take<float>(te);
-  float *gt = cv.take<float>(te);
-  double *partial = cv.take<double>(nb_alloc);
-  float *slab = cv.take<float>((size_t)grid * stride);
-  void *tape = (void *)cv.take<char>(rqs_tape_b(desc, N));
-  double *gpart = cv.take<double>(eblocks);
+  const double inv = 1.0 / (double)c.Ng;
+  RqsStepBufs b;
+  NF_TRY(ws_carve(ctx, &b, desc, c.N, npartial));
   float *gbuf = (float *)ctx->gbuf;
-  // packed images: those the previous step's epilogue left (only under nf_ctx_set_weight_cache(ctx, 1)), or a fresh pack
-  if (!ctx->wimg_cache || !(ctx->wimg && ctx->wimg_owner == (const void *)theta && ctx->wimg_sig == flow_sig(desc)))
-    NF_TRY(coupling_pack(ctx, desc, theta));
-  NF_TRY(fused_chain_elbo(ctx, desc, target, N, seed, 0, step_val, xt, gt, -inv, partial, -inv, (float *)tape, step_ptr));
+  NF_TRY(step_images_ensure(ctx, desc, c.theta));
+  NF_TRY(fwd(b.xt, b.gt, b.partial, b.tape));
   const int nc = 2 * desc->nlayers;
-  for (int k = 0; k < nc; ++k) NF_TRY(nf_rqs_bwd(ctx, desc, k, xt, gt, nullptr, (float)(-inv), N, slab, stride, grid, false, tape));
-  NF_TRY(nf_rqs_epilogue(ctx, desc, slab, grid, gbuf, partial, (int)fused_chain_grid(ctx, desc, N), theta, m, v, lr, beta1, beta2, eps,
-                         step_val, gpart, step_ptr));
+  for (int s = 0; s < nc; ++s)  // the inverse chain's reverse pass: forward execution order, as coupling_inv_bwd
+    NF_TRY(nf_rqs_bwd(ctx, desc, inv_dir ? nc - 1 - s : s, b.xt, b.gt, nullptr, (float)(-inv), c.N, b.slab, b.stride, b.grid, inv_dir,
+                      b.tape));
+  NF_TRY(nf_rqs_epilogue(ctx, desc, b.slab, b.grid, gbuf, b.partial, (int)nf_rqs_chain_grid(ctx, c.N), c.theta, c.m, c.v, c.lr, c.beta1,
+                         c.beta2, c.eps, c.step, b.gpart, c.step_device));
   // norm(g); in the graph-replay form also the step counter's increment, as the RealNVP step does it
-  NF_TRY(nf_launch_finish_sum(ctx, gpart, eblocks, 1, nullptr, gbuf + P + 1, nullptr, step_ptr));
-  ctx->wimg_owner = theta;
-  ctx->wimg_sig = flow_sig(desc);
+  NF_TRY(nf_launch_finish_sum(ctx, b.gpart, b.eblocks, 1, nullptr, gbuf + P + 1, nullptr, c.step_device));
+  step_images_written(ctx, desc, c.theta);
   return NF_OK;
 }
 
@@ -2153,57 +2236,105 @@ extern "C" int nf_comm_bucket_count(nf_ctx *ctx, const nf_flow_desc *desc) {
   return (2 * desc->nlayers + cpb - 1) / cpb;
 }
 
+// the split sequence of a step: value and gradient, the all-reduce under a communicator, Adam
+static int step_split(nf_ctx *ctx, const nf_flow_desc *desc, const StepCall &c) {
+  const long P = nf_param_count(desc);
+  const size_t es = esize(desc->dtype);
+  const int world = ctx->comm ? ctx->comm_size : 1;
+  void *gbuf = ctx->gbuf;
+  char *gnorm_dev = (char *)gbuf + (size_t)(P + 1) * es;
+  if (!c.target) {
+    NF_TRY(nf_loglikelihood_value_and_grad(ctx, desc, c.theta, c.ys, c.N, c.Ng, gbuf));
+    if (world > 1) NF_TRY(nf_allreduce_grad_loss(ctx, desc->dtype, gbuf, P + 1));
+    return nf_adam_update(ctx, desc->dtype, c.theta, gbuf, c.m, c.v, P, c.lr, c.beta1, c.beta2, c.eps, (int64_t)c.step + 1, gnorm_dev);
+  }
+  const uint64_t off = (uint64_t)(ctx->comm ? ctx->comm_rank : 0) * (uint64_t)c.N;
+  // weight-streaming RealNVP with many parameters (cfg 4: 16.9 MB): the all-reduce goes out in buckets of whole couplings
+  // on the second stream as the reverse pass produces them (nf_comm.hip); everything else: one message after the gradient
+  const int cpb = comm_bucket_couplings(ctx, desc);
+  ctx->bucket.on = cpb > 0;
+  ctx->bucket.couplings = cpb;
+  ctx->bucket.issued = 0;
+  const int st_vg = nf_elbo_value_and_grad(ctx, desc, c.target, c.theta, nullptr, c.N, c.Ng, c.seed, off, c.step, gbuf);
+  ctx->bucket.on = false;
+  if (cpb > 0) {
+    // Join whatever was issued even when the gradient failed on this rank: the compute stream must not run ahead
+    // of collectives still in flight on the second stream, and the caller must learn that the step's buckets are incomplete
+    // -- the peers have enqueued ALL of theirs and will wait in RCCL for the ones this rank never issued.  That state is not
+    // recoverable inside the library: the error is returned, the context's communicator is unusable from here on
+    // (nf_comm_destroy + a new nf_comm_init_rank on every rank), which the header says of any failed collective call.
+    const int st_join = nf_comm_bucket_join(ctx);
+    const int want = (2 * desc->nlayers + cpb - 1) / cpb;
+    // whatever else went wrong, a rank that issued fewer messages than nf_comm_bucket_count promises leaves its
+    // peers waiting in RCCL -- that is a property of the COMMUNICATOR, reported as NF_ERR_RCCL and remembered (every later
+    // collective call on this context fails until nf_comm_destroy); a local failure with a complete sequence keeps its code
+    if (ctx->bucket.issued != want) {
+      ctx->comm_poisoned = true;
+      return NF_ERR_RCCL;
+    }
+    if (st_vg != NF_OK) return st_vg;
+    NF_TRY(st_join);
+  } else {
+    NF_TRY(st_vg);
+    if (world > 1) NF_TRY(nf_allreduce_grad_loss(ctx, desc->dtype, gbuf, P + 1));
+  }
+  return nf_adam_update(ctx, desc->dtype, c.theta, gbuf, c.m, c.v, P, c.lr, c.beta1, c.beta2, c.eps, (int64_t)c.step + 1, gnorm_dev);
+}
+
+// What the four step entry points share behind their argument checks: the fused form the flow has (the graph-capturable calls
+// have no other), the device buffer, the step, and the finish -- [loss ; norm] read back, or copied on the device (out_device).
+// The forward-KL fused forms compute every element of z, ladj and the seed as nf_loglikelihood_value_and_grad computes it, so
+// theta, m and v equal the split calls' bits.  Their loss is not bit-equal: the per-sample log q0(z) is evaluated as the fused
+// ELBO forward does (-d log(2 pi) / 2 - ||z||^2 / 2, not the target kernel's per-feature sum) and the double partials are
+// grouped by workgroup; it agrees to float rounding.
+static int step_run(nf_ctx *ctx, const nf_flow_desc *desc, const StepCall &c, double *loss_host, double *gnorm_host, void *out_device) {
+  NF_TRY(check_desc(desc));
+  NF_HIP(hipSetDevice(ctx->device));
+  if (c.Ng < 1) return NF_ERR_ARG;
+  const long P = nf_param_count(desc), N = c.N;
+  const bool elbo = c.target != nullptr;
+  const bool affine = elbo ? step_fusable(ctx, desc, c.target, N) : fkl_step_fusable(ctx, desc, N);
+  const bool rqs = !affine && (elbo ? step_fusable_rqs(ctx, desc, c.target) : fkl_step_fusable_rqs(ctx, desc, N));
+  if (c.step_device && !affine && !rqs) return NF_ERR_UNSUPPORTED;
+  NF_TRY(gbuf_reserve(ctx, gbuf_need(P, esize(desc->dtype))));
+  const double inv = 1.0 / (double)c.Ng;
+  if (affine && elbo) {  // this rank draws samples [rank N, (rank + 1) N) of the global batch
+    const uint64_t off0 = (uint64_t)(ctx->comm ? ctx->comm_rank : 0) * (uint64_t)N;
+    NF_TRY(affine_step_fused(ctx, desc, c, elbo_npartial(ctx, desc, N), false, [&](long o, long nc, float *gt, double *partial, float *stash) {
+      return nf_affine_chain_elbo(ctx, desc, nc, c.seed, off0 + (uint64_t)o, c.step, c.target, nullptr, gt, -inv, partial, -inv, stash,
+                                  c.step_device);
+    }));
+  } else if (affine) {  // ys read in place
+    NF_TRY(affine_step_fused(ctx, desc, c, fkl_step_npart(ctx, N, affine_stash_chunk(ctx, desc, N)), true,
+                             [&](long o, long nc, float *gt, double *partial, float *stash) {
+                               return nf_affine_chain_fkl(ctx, desc, c.ys + o * desc->d, nc, gt, -inv, partial, -inv, stash);
+                             }));
+  } else if (rqs && elbo) {
+    NF_TRY(rqs_step_fused(ctx, desc, c, elbo_npartial(ctx, desc, N), false, [&](float *xt, float *gt, double *partial, void *tape) {
+      return fused_chain_elbo(ctx, desc, c.target, N, c.seed, 0, c.step, xt, gt, -inv, partial, -inv, (float *)tape, c.step_device);
+    }));
+  } else if (rqs) {
+    NF_TRY(rqs_step_fused(ctx, desc, c, nf_rqs_chain_grid(ctx, N), true, [&](float *zt, float *gt, double *partial, void *tape) {
+      return nf_rqs_chain_fkl(ctx, desc, c.ys, N, zt, gt, -inv, partial, -inv, tape);
+    }));
+  } else {
+    NF_TRY(step_split(ctx, desc, c));
+  }
+  if (c.step_device) {
+    if (out_device) NF_HIP(hipMemcpyAsync(out_device, (char *)ctx->gbuf + (size_t)P * 4, 8, hipMemcpyDeviceToDevice, ctx->stream));
+    return NF_OK;
+  }
+  if (loss_host || gnorm_host) return step_readback(ctx, desc, P, loss_host, gnorm_host);
+  return NF_OK;
+}
+
 extern "C" int nf_elbo_step(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, void *theta, void *m,
                             void *v, int64_t N, uint64_t seed, uint32_t step, double lr, double beta1, double beta2,
                             double eps, double *loss_host, double *gnorm_host) {
   if (!ctx || !target || !theta || !m || !v || N < 1) return NF_ERR_ARG;
-  NF_TRY(check_desc(desc));
-  NF_HIP(hipSetDevice(ctx->device));
-  const long P = nf_param_count(desc);
-  const size_t es = esize(desc->dtype);
-  NF_TRY(gbuf_reserve(ctx, gbuf_need(P, es)));
-  void *gbuf = ctx->gbuf;
-  if (step_fusable(ctx, desc, target, N)) {
-    NF_TRY(elbo_step_fused(ctx, desc, target, (float *)theta, (float *)m, (float *)v, N, seed, step, nullptr, lr, beta1, beta2, eps));
-  } else if (step_fusable_rqs(ctx, desc, target)) {
-    NF_TRY(elbo_step_fused_rqs(ctx, desc, target, (float *)theta, (float *)m, (float *)v, N, seed, step, nullptr, lr, beta1, beta2, eps));
-  } else {
-    const int world = ctx->comm ? ctx->comm_size : 1;
-    const uint64_t off = (uint64_t)(ctx->comm ? ctx->comm_rank : 0) * (uint64_t)N;
-    // weight-streaming RealNVP with many parameters (cfg 4: 16.9 MB): the all-reduce goes out in buckets of whole couplings
-    // on the second stream as the reverse pass produces them (nf_comm.hip); everything else: one message after the gradient
-    const int cpb = comm_bucket_couplings(ctx, desc);
-    ctx->bucket.on = cpb > 0;
-    ctx->bucket.couplings = cpb;
-    ctx->bucket.issued = 0;
-    const int st_vg = nf_elbo_value_and_grad(ctx, desc, target, theta, nullptr, N, N * world, seed, off, step, gbuf);
-    ctx->bucket.on = false;
-    if (cpb > 0) {
-      // Join whatever was issued even when the gradient failed on this rank: the compute stream must not run ahead
-      // of collectives still in flight on the second stream, and the caller must learn that the step's buckets are incomplete
-      // -- the peers have enqueued ALL of theirs and will wait in RCCL for the ones this rank never issued.  That state is not
-      // recoverable inside the library: the error is returned, the context's communicator is unusable from here on
-      // (nf_comm_destroy + a new nf_comm_init_rank on every rank), which the header says of any failed collective call.
-      const int st_join = nf_comm_bucket_join(ctx);
-      const int want = (2 * desc->nlayers + cpb - 1) / cpb;
-      // whatever else went wrong, a rank that issued fewer messages than nf_comm_bucket_count promises leaves its
-      // peers waiting in RCCL -- that is a property of the COMMUNICATOR, reported as NF_ERR_RCCL and remembered (every later
-      // collective call on this context fails until nf_comm_destroy); a local failure with a complete sequence keeps its code
-      if (ctx->bucket.issued != want) {
-        ctx->comm_poisoned = true;
-        return NF_ERR_RCCL;
-      }
-      if (st_vg != NF_OK) return st_vg;
-      NF_TRY(st_join);
-    } else {
-      NF_TRY(st_vg);
-      if (world > 1) NF_TRY(nf_allreduce_grad_loss(ctx, desc->dtype, gbuf, P + 1));
-    }
-    char *gnorm_dev = (char *)gbuf + (size_t)(P + 1) * es;
-    NF_TRY(nf_adam_update(ctx, desc->dtype, theta, gbuf, m, v, P, lr, beta1, beta2, eps, (int64_t)step + 1, gnorm_dev));
-  }
-  if (loss_host || gnorm_host) return step_readback(ctx, desc, P, loss_host, gnorm_host);
-  return NF_OK;
+  const StepCall c{target, nullptr, (long)N, (long)N * (ctx->comm ? ctx->comm_size : 1), seed, (float *)theta, (float *)m, (float *)v,
+                   step, nullptr, lr, beta1, beta2, eps};
+  return step_run(ctx, desc, c, loss_host, gnorm_host, nullptr);
 }
 
 // The graph-capturable form: no host-side value changes from step to step.  *step_device (a uint32 in device memory,
@@ -2215,19 +2346,9 @@ extern "C" int nf_elbo_step_enqueue(nf_ctx *ctx, const nf_flow_desc *desc, const
                                     int64_t N, uint64_t seed, uint32_t *step_device, double lr, double beta1, double beta2,
                                     double eps, void *out_loss_gnorm_device) {
   if (!ctx || !target || !theta || !m || !v || !step_device || N < 1) return NF_ERR_ARG;
-  NF_TRY(check_desc(desc));
-  NF_HIP(hipSetDevice(ctx->device));
-  const long P = nf_param_count(desc);
-  const bool affine = step_fusable(ctx, desc, target, N);
-  if (!affine && !step_fusable_rqs(ctx, desc, target)) return NF_ERR_UNSUPPORTED;
-  NF_TRY(gbuf_reserve(ctx, gbuf_need(P, 4)));
-  if (affine)
-    NF_TRY(elbo_step_fused(ctx, desc, target, (float *)theta, (float *)m, (float *)v, N, seed, 0, step_device, lr, beta1, beta2, eps));
-  else
-    NF_TRY(elbo_step_fused_rqs(ctx, desc, target, (float *)theta, (float *)m, (float *)v, N, seed, 0, step_device, lr, beta1, beta2, eps));
-  if (out_loss_gnorm_device)
-    NF_HIP(hipMemcpyAsync(out_loss_gnorm_device, (char *)ctx->gbuf + (size_t)P * 4, 8, hipMemcpyDeviceToDevice, ctx->stream));
-  return NF_OK;
+  const StepCall c{target, nullptr, (long)N, (long)N * (ctx->comm ? ctx->comm_size : 1), seed, (float *)theta, (float *)m, (float *)v,
+                   0, step_device, lr, beta1, beta2, eps};
+  return step_run(ctx, desc, c, nullptr, nullptr, out_loss_gnorm_device);
 }
 
 // ---- the forward-KL training step -----------------------------------------------------------------------------------
@@ -2237,141 +2358,15 @@ extern "C" int nf_elbo_step_enqueue(nf_ctx *ctx, const nf_flow_desc *desc, const
 // layout conversion, the separate base-density launch, the slab reduction and Adam of the split calls are folded away, and
 // so is the next step's pack under the weight cache.  LDS-resident spline couplings on one rank: k_rqs_chain<INVERSE, FUSED>
 // (the same tail, leaving z and the spline tape), the inverse-direction reverse launch per coupling, k_rqs_epilogue and
-// k_finish_sum.  Every element of z, ladj and the seed is computed as nf_loglikelihood_value_and_grad computes it, so theta, m
-// and v equal the split calls' bits.  The loss is not bit-equal: the per-sample log q0(z) is evaluated as the fused ELBO
-// forward does (-d log(2 pi) / 2 - ||z||^2 / 2, not the target kernel's per-feature sum) and the double partials are grouped
-// by workgroup; it agrees to float rounding.  Every other flow runs the split sequence inside the call.
-static bool fkl_step_fusable(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
-  if (N < 1 || flow_base(desc) || is_composite(desc) || desc->dtype != NF_DTYPE_F32) return false;
-  if (!(desc->kind == NF_KIND_REALNVP && nf_affine_supported(desc) && nf_affine_chain_fkl_ok(desc))) return false;
-  return affine_stash_chunk(ctx, desc, N) > 0;
-}
-// loss partials of a chunked step: one per workgroup of every chunk's chain launch
-static long fkl_step_npart(nf_ctx *ctx, long N, long chunk) {
-  long n = 0;
-  for (long o = 0; o < N; o += chunk) n += nf_affine_chain_grid(ctx, N - o < chunk ? N - o : chunk);
-  return n;
-}
-static size_t fkl_step_need(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
-  const long snc = affine_stash_chunk(ctx, desc, N);
-  if (!snc) return 0;
-  return carve_bytes(tiled_elems(desc, N) * 4) + carve_bytes((size_t)fkl_step_npart(ctx, N, snc) * 8) +
-         carve_bytes(chunked_slab_floats(ctx, desc, N, snc, coupling_slab_floats(ctx, desc, N)) * 4) +
-         carve_bytes(affine_stash_bytes(ctx, desc, snc)) + carve_bytes((size_t)nf_affine_epilogue_blocks(desc) * 8);
-}
-// spline couplings: one rank (as step_fusable_rqs), the LDS-resident geometries with a forward-KL chain kernel
-static bool fkl_step_fusable_rqs(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
-  if (N < 1 || ctx->comm || flow_base(desc) || is_composite(desc) || desc->dtype != NF_DTYPE_F32) return false;
-  return desc->kind == NF_KIND_NSF && nf_rqs_supported(desc) && nf_rqs_chain_fkl_ok(desc);
-}
-static size_t fkl_step_need_rqs(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
-  const size_t te = tiled_elems(desc, N);
-  return 2 * carve_bytes(te * 4) + carve_bytes((size_t)nf_rqs_chain_grid(ctx, N) * 8) +
-         carve_bytes((size_t)coupling_bwd_grid(ctx, desc, N) * coupling_slab_floats(ctx, desc, N) * 4) + rqs_tape_b(desc, N) +
-         carve_bytes((size_t)nf_rqs_epilogue_blocks(desc) * 8);
-}
-static int fkl_step_fused_rqs(nf_ctx *ctx, const nf_flow_desc *desc, float *theta, float *m, float *v, const float *ys, long N,
-                              long Ng, uint32_t step_val, uint32_t *step_ptr, double lr, double beta1, double beta2, double eps) {
-  const long P = nf_param_count(desc);
-  const double inv = 1.0 / (double)Ng;
-  const size_t te = tiled_elems(desc, N);
-  const int grid = coupling_bwd_grid(ctx, desc, N);
-  const long stride = coupling_slab_floats(ctx, desc, N);
-  const long npart = nf_rqs_chain_grid(ctx, N);
-  const long eblocks = nf_rqs_epilogue_blocks(desc);
-  NF_TRY(nf_ws_reserve(ctx, fkl_step_need_rqs(ctx, desc, N)));
-  Carver cv(ctx->ws);
-  float *zt = cv.take<float>(te);
-  float *gt = cv.take<float>(te);
-  double *partial = cv.take<double>(npart);
-  float *slab = cv.take<float>((size_t)grid * stride);
-  void *tape = (void *)cv.take<char>(rqs_tape_b(desc, N));
-  double *gpart = cv.take<double>(eblocks);
-  float *gbuf = (float *)ctx->gbuf;
-  if (!ctx->wimg_cache || !(ctx->wimg && ctx->wimg_owner == (const void *)theta && ctx->wimg_sig == flow_sig(desc)))
-    NF_TRY(coupling_pack(ctx, desc, theta));
-  NF_TRY(nf_rqs_chain_fkl(ctx, desc, ys, N, zt, gt, -inv, partial, -inv, tape));
-  for (int k = 2 * desc->nlayers - 1; k >= 0; --k)  // forward execution order, as coupling_inv_bwd
-    NF_TRY(nf_rqs_bwd(ctx, desc, k, zt, gt, nullptr, (float)(-inv), N, slab, stride, grid, true, tape));
-  NF_TRY(nf_rqs_epilogue(ctx, desc, slab, grid, gbuf, partial, (int)npart, theta, m, v, lr, beta1, beta2, eps, step_val, gpart,
-                         step_ptr));
-  NF_TRY(nf_launch_finish_sum(ctx, gpart, eblocks, 1, nullptr, gbuf + P + 1, nullptr, step_ptr));
-  ctx->wimg_owner = theta;
-  ctx->wimg_sig = flow_sig(desc);
-  return NF_OK;
-}
-static int fkl_step_fused(nf_ctx *ctx, const nf_flow_desc *desc, float *theta, float *m, float *v, const float *ys, long N, long Ng,
-                          uint32_t step_val, uint32_t *step_ptr, double lr, double beta1, double beta2, double eps) {
-  const long P = nf_param_count(desc);
-  const int world = ctx->comm ? ctx->comm_size : 1;
-  const double inv = 1.0 / (double)Ng;
-  const long stash_nc = affine_stash_chunk(ctx, desc, N);
-  const long stride = coupling_slab_floats(ctx, desc, N);
-  const long eblocks = nf_affine_epilogue_blocks(desc);
-  NF_TRY(nf_ws_reserve(ctx, fkl_step_need(ctx, desc, N)));
-  Carver cv(ctx->ws);
-  float *gt = cv.take<float>(tiled_elems(desc, N));
-  double *partial = cv.take<double>(fkl_step_npart(ctx, N, stash_nc));
-  float *slab = cv.take<float>(chunked_slab_floats(ctx, desc, N, stash_nc, stride));
-  float *stash = cv.take<float>(affine_stash_bytes(ctx, desc, stash_nc) / 4);
-  double *gpart = cv.take<double>(eblocks);
-  float *gbuf = (float *)ctx->gbuf;
-  // packed images: those the previous step's epilogue left (only under nf_ctx_set_weight_cache(ctx, 1)), or a fresh pack
-  if (!ctx->wimg_cache || !(ctx->wimg && ctx->wimg_owner == (const void *)theta && ctx->wimg_sig == flow_sig(desc)))
-    NF_TRY(coupling_pack(ctx, desc, theta));
-  long nslab = 0, npart = 0;
-  for (long o = 0; o < N; o += stash_nc) {
-    const long nc = N - o < stash_nc ? N - o : stash_nc;
-    const int gc = coupling_bwd_grid(ctx, desc, nc);
-    NF_TRY(nf_affine_chain_fkl(ctx, desc, ys + o * desc->d, nc, gt + o * desc->d, -inv, partial + npart, -inv, stash));
-    NF_TRY(nf_affine_bwd_stashed(ctx, desc, stash, gt + o * desc->d, nullptr, (float)(-inv), nc, slab + nslab * stride, stride, gc, true,
-                                 true));
-    nslab += gc;
-    npart += nf_affine_chain_grid(ctx, nc);
-  }
-  if (world == 1) {
-    NF_TRY(nf_affine_epilogue(ctx, desc, 3, slab, (int)nslab, gbuf, partial, (int)npart, theta, m, v, lr, beta1, beta2, eps, step_val,
-                              step_ptr, gpart));
-  } else {
-    NF_TRY(nf_affine_epilogue(ctx, desc, 1, slab, (int)nslab, gbuf, partial, (int)npart, nullptr, nullptr, nullptr, lr, beta1, beta2,
-                              eps, step_val, nullptr, gpart));
-    NF_TRY(nf_allreduce_grad_loss(ctx, NF_DTYPE_F32, gbuf, P + 1));
-    NF_TRY(nf_affine_epilogue(ctx, desc, 2, nullptr, 0, gbuf, nullptr, 0, theta, m, v, lr, beta1, beta2, eps, step_val, step_ptr,
-                              gpart));
-  }
-  NF_TRY(nf_launch_finish_sum(ctx, gpart, eblocks, 1, nullptr, gbuf + P + 1, nullptr, step_ptr));
-  ctx->wimg_owner = theta;
-  ctx->wimg_sig = flow_sig(desc);
-  return NF_OK;
-}
-
+// k_finish_sum.  Every other flow runs the split sequence inside the call.
 extern "C" int nf_loglikelihood_step(nf_ctx *ctx, const nf_flow_desc *desc, void *theta, void *m, void *v, const void *ys,
                                      int64_t N_local, int64_t N_global, uint32_t step, double lr, double beta1, double beta2,
                                      double eps, double *loss_host, double *gnorm_host) {
   if (!ctx || !theta || !m || !v || !ys || N_local < 0) return NF_ERR_ARG;
-  NF_TRY(check_desc(desc));
-  NF_HIP(hipSetDevice(ctx->device));
-  const long P = nf_param_count(desc);
-  const size_t es = esize(desc->dtype);
-  const int world = ctx->comm ? ctx->comm_size : 1;
-  const long Ng = N_global > 0 ? (long)N_global : (long)N_local * world;
-  if (Ng < 1) return NF_ERR_ARG;
-  NF_TRY(gbuf_reserve(ctx, gbuf_need(P, es)));
-  if (fkl_step_fusable(ctx, desc, N_local)) {
-    NF_TRY(fkl_step_fused(ctx, desc, (float *)theta, (float *)m, (float *)v, (const float *)ys, N_local, Ng, step, nullptr, lr, beta1,
-                          beta2, eps));
-  } else if (fkl_step_fusable_rqs(ctx, desc, N_local)) {
-    NF_TRY(fkl_step_fused_rqs(ctx, desc, (float *)theta, (float *)m, (float *)v, (const float *)ys, N_local, Ng, step, nullptr, lr,
-                              beta1, beta2, eps));
-  } else {  // the split sequence: value and gradient, the all-reduce under a communicator, Adam
-    void *gbuf = ctx->gbuf;
-    NF_TRY(nf_loglikelihood_value_and_grad(ctx, desc, theta, ys, N_local, Ng, gbuf));
-    if (world > 1) NF_TRY(nf_allreduce_grad_loss(ctx, desc->dtype, gbuf, P + 1));
-    NF_TRY(nf_adam_update(ctx, desc->dtype, theta, gbuf, m, v, P, lr, beta1, beta2, eps, (int64_t)step + 1,
-                          (char *)gbuf + (size_t)(P + 1) * es));
-  }
-  if (loss_host || gnorm_host) return step_readback(ctx, desc, P, loss_host, gnorm_host);
-  return NF_OK;
+  const long Ng = N_global > 0 ? (long)N_global : (long)N_local * (ctx->comm ? ctx->comm_size : 1);
+  const StepCall c{nullptr, (const float *)ys, (long)N_local, Ng, 0, (float *)theta, (float *)m, (float *)v, step, nullptr, lr, beta1,
+                   beta2, eps};
+  return step_run(ctx, desc, c, loss_host, gnorm_host, nullptr);
 }
 
 // The graph-capturable form, as nf_elbo_step_enqueue: Adam's t - 1 comes from *step_device, which the step increments.
@@ -2379,110 +2374,56 @@ extern "C" int nf_loglikelihood_step_enqueue(nf_ctx *ctx, const nf_flow_desc *de
                                              int64_t N_local, int64_t N_global, uint32_t *step_device, double lr, double beta1,
                                              double beta2, double eps, void *out_loss_gnorm_device) {
   if (!ctx || !theta || !m || !v || !ys || !step_device || N_local < 0) return NF_ERR_ARG;
-  NF_TRY(check_desc(desc));
-  NF_HIP(hipSetDevice(ctx->device));
-  const long P = nf_param_count(desc);
-  const int world = ctx->comm ? ctx->comm_size : 1;
-  const long Ng = N_global > 0 ? (long)N_global : (long)N_local * world;
-  if (Ng < 1) return NF_ERR_ARG;
-  const bool affine = fkl_step_fusable(ctx, desc, N_local);
-  if (!affine && !fkl_step_fusable_rqs(ctx, desc, N_local)) return NF_ERR_UNSUPPORTED;
-  NF_TRY(gbuf_reserve(ctx, gbuf_need(P, 4)));
-  if (affine)
-    NF_TRY(fkl_step_fused(ctx, desc, (float *)theta, (float *)m, (float *)v, (const float *)ys, N_local, Ng, 0, step_device, lr, beta1,
-                          beta2, eps));
-  else
-    NF_TRY(fkl_step_fused_rqs(ctx, desc, (float *)theta, (float *)m, (float *)v, (const float *)ys, N_local, Ng, 0, step_device, lr,
-                              beta1, beta2, eps));
-  if (out_loss_gnorm_device)
-    NF_HIP(hipMemcpyAsync(out_loss_gnorm_device, (char *)ctx->gbuf + (size_t)P * 4, 8, hipMemcpyDeviceToDevice, ctx->stream));
-  return NF_OK;
+  const long Ng = N_global > 0 ? (long)N_global : (long)N_local * (ctx->comm ? ctx->comm_size : 1);
+  const StepCall c{nullptr, (const float *)ys, (long)N_local, Ng, 0, (float *)theta, (float *)m, (float *)v, 0, step_device, lr, beta1,
+                   beta2, eps};
+  return step_run(ctx, desc, c, nullptr, nullptr, out_loss_gnorm_device);
 }
 
 // ---- arena sizing ------------------------------------------------------------------------------
 // Upper bound, over EVERY compute entry point called with this flow and up to N samples, of the device memory the
-// context needs: the intermediates arena (the per-entry-point `need` formulas above, restated here -- the arena-mode
-// GPU test runs every entry point against exactly this bound, so a formula that drifts fails loudly with
-// NF_ERR_WORKSPACE), the optimiser's norm partials, the packed weight images and the nf_elbo_step buffer.
+// context needs: the intermediates arena (the maximum over the entry points' layouts, measured by the code that carves
+// them), the optimiser's norm partials, the packed weight images and the nf_elbo_step buffer.
 size_t nf_affine_wimg_bytes(const nf_flow_desc *desc);
 size_t nf_l64_scratch_bytes(const nf_flow_desc *desc, long N);
 size_t nf_rqs_wimg_bytes(const nf_flow_desc *desc);
 size_t nf_wide_wimg_bytes(nf_ctx *, const nf_flow_desc *desc);
 
-// intermediates only (what nf_ws_reserve is asked for), standard-normal base
-static size_t composite_inner_need(nf_ctx *ctx, const nf_flow_desc *desc, long N);
-static size_t composite_extra_bytes(const nf_flow_desc *desc, long N);
-static size_t ws_need_bound(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
-  if (is_composite(desc)) {
-    size_t need = composite_inner_need(ctx, desc, N) + composite_extra_bytes(desc, N);
-    const size_t v = vg_composite_need(ctx, desc, N), f = flow_bwd_need(ctx, desc, N);
-    if (v > need) need = v;
-    if (f > need) need = f;
-    return need;
-  }
-  const size_t es = esize(desc->dtype);
-  const bool cp = is_coupling(desc);
-  const size_t te = cp ? tiled_elems(desc, N) : 0;
-  const size_t xe = cp ? te : (size_t)N * desc->d;
-  const size_t cn = carve_bytes((size_t)N * es);
-  size_t need = 0;
-  auto upd = [&](size_t v) { if (v > need) need = v; };
-  // nf_flow_fwd / inv / layer_apply, nf_flow_rand
-  upd(cp ? carve_bytes(te * 4) + carve_bytes((size_t)N * 4) : cn);
-  // nf_flow_bwd (its own forward + tape), nf_flow_fwd_keep / nf_flow_bwd_kept (tape in the caller's memory)
-  const int grid = cp ? coupling_bwd_grid(ctx, desc, N) : 0;
-  const size_t slab_pull = cp ? (size_t)grid * coupling_slab_floats(ctx, desc, N) : 0;
-  upd(flow_bwd_need(ctx, desc, N));
-  // nf_elbo_batch(_rng), nf_loglikelihood
-  const long nbt = cp ? nf_target_tiled_nblocks(N) : nf_target_nblocks(N);
-  const long nb_alloc = nbt < ctx->num_cu ? ctx->num_cu : nbt;
-  upd(carve_bytes(xe * es) + 2 * cn + carve_bytes((size_t)nb_alloc * 8) + carve_bytes(64));
-  upd(carve_bytes(xe * es) + 2 * cn + carve_bytes((size_t)nf_sum2_nblocks(N) * 8) + carve_bytes(64));
-  // nf_loglikelihood_value_and_grad
-  {
-    const bool coupling_kind = desc->kind == NF_KIND_REALNVP || desc->kind == NF_KIND_NSF;
-    const bool hf = desc->kind == NF_KIND_HAMILTONIAN;
-    const bool tiled = cp && coupling_inv_bwd_tiled(desc);
-    if (!(coupling_kind && !tiled && !nf_g64_supported(desc))) {
-      const long snc = tiled ? affine_stash_chunk(ctx, desc, N) : 0;
-      const size_t slabf = tiled ? chunked_slab_floats(ctx, desc, N, snc, coupling_slab_floats(ctx, desc, N)) : 0;
-      const size_t flat_ws = tiled ? 0 : hf ? nf_hf_bwd_ws_bytes(desc, N) : coupling_kind ? nf_g64_bwd_inv_ws_bytes(desc, N)
-                                                                                       : nf_simple_bwd_ws_bytes(ctx, desc, N);
-      upd(2 * carve_bytes(xe * es) + cn + carve_bytes((size_t)nbt * 8) + carve_bytes(2 * (size_t)desc->d * es) +
-          carve_bytes(slabf * es) + carve_bytes(flat_ws) + carve_bytes(snc ? affine_stash_bytes(ctx, desc, snc) : 0) +
-          (tiled ? rqs_tape_b(desc, N) : 0));
-    }
-  }
-  // nf_elbo_value_and_grad / nf_elbo_step (both the stash-free and the stash form of the simple flows)
-  {
-    const bool wide = cp && is_wide(desc);
-    const long snc = cp ? affine_stash_chunk(ctx, desc, N) : 0;
-    const size_t slabf = wide ? nf_wide_train_ws_floats(ctx, desc, N)
-                              : cp ? chunked_slab_floats(ctx, desc, N, snc, coupling_slab_floats(ctx, desc, N)) : 0;
-    size_t simple_ws = cp ? 0 : flat_bwd_ws_bytes(ctx, desc, N);
-    if (!cp && !is_g64(desc) && desc->kind != NF_KIND_HAMILTONIAN && nf_simple_step_supported(desc)) {
-      const size_t sw = nf_simple_step_ws_bytes(ctx, desc, N);
-      if (sw > simple_ws) simple_ws = sw;
-    }
-    upd(3 * carve_bytes(xe * es) + 2 * cn + carve_bytes((size_t)nb_alloc * 8) + carve_bytes(64) +
-        carve_bytes(slabf * es) + carve_bytes(simple_ws) + carve_bytes(snc ? affine_stash_bytes(ctx, desc, snc) : 0) +
-        (cp ? rqs_tape_b(desc, N) : 0));
-    // forward-KL over a general base / inside a composition: inv_bwd_std's own intermediates (spline couplings re-run
-    // their inverse chain with the tape)
-    if (cp) upd(2 * carve_bytes(te * 4) + carve_bytes(slab_pull * 4) + rqs_tape_b(desc, N) + cn);
-  }
-  return need;
+// behind the intermediates: nf_adam_update / nf_sgd_update's gradient-norm partials (tail of the intermediates arena), the
+// packed weight images and nf_elbo_step's [grad ; loss ; norm] buffer
+static size_t ws_tail_bytes(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
+  const long P = nf_param_count(desc);
+  auto wimg_of = [&](const nf_flow_desc *g) -> size_t {
+    if (!is_coupling(g)) return nf_l64_scratch_bytes(g, N);  // general Float32 couplings: the MFMA MLP's activation tiles
+    return is_wide(g) ? nf_wide_wimg_bytes(ctx, g) : is_nsf(g) ? nf_rqs_wimg_bytes(g) : nf_affine_wimg_bytes(g);
+  };
+  size_t wimg = is_composite(desc) ? 0 : wimg_of(desc);
+  for (int s = 0; is_composite(desc) && s < desc->nsegments; ++s)
+    wimg += carve_bytes(wimg_of(&desc->segments[s]));  // grow-only tail carves: a later, larger segment carves again
+  return carve_bytes((size_t)nf_adam_nblocks(P) * 8) + carve_bytes(wimg) + carve_bytes(gbuf_need(P, esize(desc->dtype))) + 4096;
 }
 
-// what the general-base wrappers keep behind the inner entry point's intermediates: x (N x d), the per-sample
-// correction, the substitution scratch of a dense base, block partials and a result slot
-static size_t base_extra_bytes(const nf_flow_desc *desc, long N) {
-  const nf_base *b = flow_base(desc);
-  if (!b) return 0;
-  const size_t es = esize(desc->dtype);
-  const size_t xb = carve_bytes((size_t)N * desc->d * es);
-  return xb + (b->kind == NF_BASE_DENSE ? xb : 0) + 2 * carve_bytes((size_t)N * es) +
-         carve_bytes((size_t)nf_sum2_nblocks(N) * 8) + carve_bytes(64);
+// intermediates only (what nf_ws_reserve is asked for), standard-normal base, without the fused forms of the two steps
+static size_t ws_need_bound(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
+  // nf_flow_bwd (its own forward + tape; nf_flow_fwd_keep / nf_flow_bwd_kept, tape in the caller's memory, need its front)
+  size_t need = layout_bytes<FlowBwdBufs>(ctx, desc, N);
+  auto upd = [&](size_t v) { if (v > need) need = v; };
+  if (is_composite(desc)) {
+    upd(layout_bytes<CompBufs>(ctx, desc, N));
+    upd(layout_bytes<VgCompositeBufs>(ctx, desc, N));
+    return need;
+  }
+  // nf_flow_fwd / inv / layer_apply, nf_flow_rand
+  upd(is_coupling(desc) ? layout_bytes<RandBufs>(ctx, desc, N) : carve_bytes((size_t)N * esize(desc->dtype)));
+  // nf_elbo_batch(_rng), nf_loglikelihood
+  upd(layout_bytes<ValueBufs>(ctx, desc, N, elbo_npartial(ctx, desc, N)));
+  upd(layout_bytes<ValueBufs>(ctx, desc, N, nf_sum2_nblocks(N)));
+  // nf_loglikelihood_value_and_grad; over a general base / inside a composition: inv_bwd_std's own intermediates
+  if (fkl_supported(desc)) upd(layout_bytes<FklBufs>(ctx, desc, N));
+  upd(layout_bytes<InvBwdBufs>(ctx, desc, N));
+  // nf_elbo_value_and_grad, the split form of nf_elbo_step
+  upd(layout_bytes<VgBufs>(ctx, desc, N));
+  return need;
 }
 
 extern "C" int64_t nf_workspace_bytes(nf_ctx *ctx, const nf_flow_desc *desc, int64_t N) {
@@ -2490,51 +2431,17 @@ extern "C" int64_t nf_workspace_bytes(nf_ctx *ctx, const nf_flow_desc *desc, int
   const int st = check_desc(desc);
   if (st != NF_OK) return st;
   if (N == 0) N = 1;
-  const size_t es = esize(desc->dtype);
-  const bool cp = is_coupling(desc);
-  const long P = nf_param_count(desc);
-  size_t need = ws_need_bound(ctx, desc, N) + base_extra_bytes(desc, N);
-  if (flow_base(desc) || is_composite(desc)) {  // nf_loglikelihood_value_and_grad's segment-wise form
-    const size_t f = fkl_general_need(ctx, desc, N);
-    if (f > need) need = f;
-  }
-  // nf_elbo_step's three-launch form
-  if (desc->kind == NF_KIND_REALNVP && desc->dtype == NF_DTYPE_F32 && !is_composite(desc) && nf_affine_supported(desc) &&
-      affine_stash_chunk(ctx, desc, N) > 0) {
-    const size_t f = step_fused_need(ctx, desc, N);
-    if (f > need) need = f;
-  }
-  if (desc->kind == NF_KIND_NSF && desc->dtype == NF_DTYPE_F32 && !is_composite(desc) && !flow_base(desc) && nf_rqs_supported(desc)) {
-    const size_t f = step_fused_need_rqs(ctx, desc, N);
-    if (f > need) need = f;
-  }
-  // nf_loglikelihood_step's fused forms (its split form is covered above; the spline form is sized whatever the communicator)
-  if (fkl_step_fusable(ctx, desc, N)) {
-    const size_t f = fkl_step_need(ctx, desc, N);
-    if (f > need) need = f;
-  }
-  if (desc->kind == NF_KIND_NSF && desc->dtype == NF_DTYPE_F32 && !is_composite(desc) && !flow_base(desc) && nf_rqs_supported(desc) &&
-      nf_rqs_chain_fkl_ok(desc)) {
-    const size_t f = fkl_step_need_rqs(ctx, desc, N);
-    if (f > need) need = f;
-  }
-  // nf_adam_update / nf_sgd_update: gradient-norm partials at the tail of the intermediates arena
-  need += carve_bytes((size_t)nf_adam_nblocks(P) * 8);
-  // packed weight images, nf_elbo_step's [grad ; loss ; norm] buffer
-  size_t wimg = 0;
-  auto wimg_of = [&](const nf_flow_desc *g) -> size_t {
-    if (!is_coupling(g)) return nf_l64_scratch_bytes(g, N);  // general Float32 couplings: the MFMA MLP's activation tiles
-    return is_wide(g) ? nf_wide_wimg_bytes(ctx, g) : is_nsf(g) ? nf_rqs_wimg_bytes(g) : nf_affine_wimg_bytes(g);
-  };
-  if (is_composite(desc)) {
-    for (int sgi = 0; sgi < desc->nsegments; ++sgi) {
-      wimg += carve_bytes(wimg_of(&desc->segments[sgi]));  // grow-only tail carves: a later, larger segment carves again
-    }
-  } else {
-    wimg = wimg_of(desc);
-  }
-  need += carve_bytes(wimg) + carve_bytes(gbuf_need(P, es)) + 4096;
-  return (int64_t)need;
+  size_t need = flow_base(desc) ? layout_bytes<BaseBufs>(ctx, desc, (long)N) : ws_need_bound(ctx, desc, N);
+  auto upd = [&](size_t v) { if (v > need) need = v; };
+  // nf_loglikelihood_value_and_grad's segment-wise form
+  if (flow_base(desc) || is_composite(desc)) upd(layout_bytes<FklGeneralBufs>(ctx, desc, (long)N));
+  // the fused forms of nf_elbo_step and nf_loglikelihood_step (the spline forms are sized whatever the communicator)
+  if (step_fusable(ctx, desc, nullptr, N, true)) upd(layout_bytes<AffineStepBufs>(ctx, desc, (long)N, elbo_npartial(ctx, desc, N)));
+  if (step_fusable_rqs(ctx, desc, nullptr, true)) upd(layout_bytes<RqsStepBufs>(ctx, desc, (long)N, elbo_npartial(ctx, desc, N)));
+  if (fkl_step_fusable(ctx, desc, N))
+    upd(layout_bytes<AffineStepBufs>(ctx, desc, (long)N, fkl_step_npart(ctx, N, affine_stash_chunk(ctx, desc, N))));
+  if (fkl_step_fusable_rqs(ctx, desc, N, true)) upd(layout_bytes<RqsStepBufs>(ctx, desc, (long)N, nf_rqs_chain_grid(ctx, N)));
+  return (int64_t)(need + ws_tail_bytes(ctx, desc, N));
 }
 
 // ---- measurement support -------------------------------------------------------------------

@@ -99,19 +99,28 @@ int nf_ws_reserve(nf_ctx *ctx, size_t bytes);
 // packed weight images (ctx->wimg) of at least `bytes`: grow-only allocation, or a tail carve of the caller's arena
 int nf_wimg_reserve(nf_ctx *ctx, size_t bytes);
 
-// carve helper over the arena: returns 256-byte aligned sub-buffers
+inline size_t carve_bytes(size_t nbytes) { return ((nbytes + 255) / 256) * 256; }
+// carve helper over the arena: returns 256-byte aligned sub-buffers.  Without a base it MEASURES: take() only advances `off`
+// and returns null, so the bytes a layout needs are the `off` of a measuring pass over the code that carves it.
 struct Carver {
-  char *base;
+  char *base = nullptr;
   size_t off = 0;
-  explicit Carver(void *b) : base((char *)b) {}
+  explicit Carver(void *b = nullptr) : base((char *)b) {}
   template <class T>
   T *take(size_t n) {
-    T *p = (T *)(base + off);
-    off += ((n * sizeof(T) + 255) / 256) * 256;
+    T *p = base ? (T *)(base + off) : nullptr;
+    off += carve_bytes(n * sizeof(T));
     return p;
   }
+  void skip(size_t bytes) { off += bytes; }  // an inner entry point's intermediates, in front of a wrapper's own buffers
 };
-inline size_t carve_bytes(size_t nbytes) { return ((nbytes + 255) / 256) * 256; }
+// bytes of layout L (a struct whose constructor carves its buffers from a Carver &) for the given arguments
+template <class L, class... A>
+inline size_t layout_bytes(A... a) {
+  Carver m;
+  L l(m, a...);
+  return m.off;
+}
 
 // profiling bracket: records a pair of pooled HIP events on ctx->stream around a launch.
 // prof_mode 1 brackets only the dominant kernel ("affine_bwd" / "rqs_bwd" / "wide_bwd"), 2 brackets all,

@@ -5,6 +5,7 @@
 // and run WITHOUT a GPU: no kernel is launched and no HIP call is made; the context is a hand-made struct whose arena
 // is a fake device address that is never dereferenced (the carving code only does pointer arithmetic on it).
 // This TU includes nf_api.hip to reach its file-local functions.
+// argv[1]: tests/golden/workspace_sizes.json, the sizes of the hand-written formulas the layouts replaced (same loop; -1: n/a).
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -45,7 +46,32 @@ static long mlp(int nin, std::initializer_list<int> hd, int nout) {
   return n + (long)prev * nout + nout;
 }
 
-int main() {
+// the fixture's "rows": every integer after that key, kNCol per row
+enum { C_BUDGET, C_FLOW, C_N, C_TOTAL, C_TAPE, C_BOUND, C_FLOW_BWD, C_TAPE_FWD, C_TAPE_BWD, C_VG_COMP, C_FKL_GENERAL, C_STEP, C_STEP_RQS,
+       C_FKL_STEP, C_FKL_STEP_RQS, kNCol };
+static std::vector<long long> read_rows(const char *path) {
+  std::vector<long long> v;
+  std::FILE *f = std::fopen(path, "rb");
+  if (!f) return v;
+  std::string s;
+  char buf[4096];
+  for (size_t n; (n = std::fread(buf, 1, sizeof buf, f)) > 0;) s.append(buf, n);
+  std::fclose(f);
+  size_t i = s.find("\"rows\"");
+  if (i == std::string::npos) return v;
+  for (i += 6; i < s.size(); ++i)
+    if (s[i] == '-' || (s[i] >= '0' && s[i] <= '9')) {
+      char *end;
+      v.push_back(std::strtoll(s.c_str() + i, &end, 10));
+      i = (size_t)(end - s.c_str());
+    }
+  return v;
+}
+
+int main(int argc, char **argv) {
+  const std::vector<long long> golden = read_rows(argc > 1 ? argv[1] : "tests/golden/workspace_sizes.json");
+  CHECK(!golden.empty() && golden.size() % kNCol == 0);
+  size_t row = 0;
   // ---- parameter counts against the closed forms of Optimisers.destructure ------------------------
   {
     nf_flow_desc a = mk(NF_KIND_REALNVP, NF_DTYPE_F32, 64, 4, {64, 64});
@@ -144,10 +170,53 @@ int main() {
         prev = total;
         const size_t bound = ws_need_bound(&ctx, &g, N);
         CHECK(bound % 256 == 0);
-        CHECK(bound >= flow_bwd_need(&ctx, &g, N));
+        CHECK(bound >= layout_bytes<FlowBwdBufs>(&ctx, &g, N));
         CHECK(bound >= tape_need(&ctx, &g, N, true) && bound >= tape_need(&ctx, &g, N, false));
-        if (is_composite(&g)) CHECK(bound >= vg_composite_need(&ctx, &g, N));
+        if (is_composite(&g)) CHECK(bound >= layout_bytes<VgCompositeBufs>(&ctx, &g, N));
         const int64_t tb = nf_tape_bytes(&ctx, &g, N);
+        // every entry point's measured front need + the tails fits the arena (fused steps: under their sizing predicates)
+        const bool comp = is_composite(&g);
+        const bool st_a = step_fusable(&ctx, &g, nullptr, N, true), st_r = step_fusable_rqs(&ctx, &g, nullptr, true);
+        const bool fk_a = fkl_step_fusable(&ctx, &g, N), fk_r = fkl_step_fusable_rqs(&ctx, &g, N, true);
+        const size_t n_step = st_a ? layout_bytes<AffineStepBufs>(&ctx, &g, N, elbo_npartial(&ctx, &g, N)) : 0;
+        const size_t n_step_rqs = st_r ? layout_bytes<RqsStepBufs>(&ctx, &g, N, elbo_npartial(&ctx, &g, N)) : 0;
+        const size_t n_fkl_step = fk_a ? layout_bytes<AffineStepBufs>(&ctx, &g, N, fkl_step_npart(&ctx, N, affine_stash_chunk(&ctx, &g, N))) : 0;
+        const size_t n_fkl_step_rqs = fk_r ? layout_bytes<RqsStepBufs>(&ctx, &g, N, nf_rqs_chain_grid(&ctx, N)) : 0;
+        {
+          std::vector<size_t> fronts = {layout_bytes<FlowBwdBufs>(&ctx, &g, N), tape_need(&ctx, &g, N, true), tape_need(&ctx, &g, N, false),
+                                        n_step, n_step_rqs, n_fkl_step, n_fkl_step_rqs};
+          if (comp) {
+            fronts.insert(fronts.end(), {layout_bytes<CompBufs>(&ctx, &g, N), layout_bytes<VgCompositeBufs>(&ctx, &g, N),
+                                         layout_bytes<FklGeneralBufs>(&ctx, &g, N)});
+          } else {
+            fronts.insert(fronts.end(), {is_coupling(&g) ? layout_bytes<RandBufs>(&ctx, &g, N) : carve_bytes((size_t)N * esize(g.dtype)),
+                                         layout_bytes<ValueBufs>(&ctx, &g, N, elbo_npartial(&ctx, &g, N)),
+                                         layout_bytes<ValueBufs>(&ctx, &g, N, nf_sum2_nblocks(N)), layout_bytes<InvBwdBufs>(&ctx, &g, N),
+                                         layout_bytes<VgBufs>(&ctx, &g, N), fkl_supported(&g) ? layout_bytes<FklBufs>(&ctx, &g, N) : 0});
+          }
+          for (size_t f : fronts) CHECK((size_t)total >= f + ws_tail_bytes(&ctx, &g, N));
+        }
+        // recorded sizes: per-entry sizes and the tape EQUAL (pins every offset); the two bounds not larger (over-counts went)
+        if (row < golden.size() / kNCol) {
+          const long long *r = &golden[row * kNCol];
+          CHECK(r[C_BUDGET] == budget && r[C_FLOW] == (long long)(&g - flows.data()) && r[C_N] == N);
+          CHECK(total <= r[C_TOTAL] && (long long)bound <= r[C_BOUND]);
+          CHECK(tb == r[C_TAPE]);
+          CHECK((long long)layout_bytes<FlowBwdBufs>(&ctx, &g, N) == r[C_FLOW_BWD]);
+          CHECK((long long)tape_need(&ctx, &g, N, false) == r[C_TAPE_FWD] && (long long)tape_need(&ctx, &g, N, true) == r[C_TAPE_BWD]);
+          CHECK(comp == (r[C_VG_COMP] >= 0) && comp == (r[C_FKL_GENERAL] >= 0));
+          if (comp) {
+            CHECK((long long)layout_bytes<VgCompositeBufs>(&ctx, &g, N) == r[C_VG_COMP]);
+            CHECK((long long)layout_bytes<FklGeneralBufs>(&ctx, &g, N) == r[C_FKL_GENERAL]);
+          }
+          // a fused form the new predicates size was sized before, with the same bytes
+          if (st_a) CHECK((long long)n_step == r[C_STEP]);
+          if (st_r) CHECK((long long)n_step_rqs == r[C_STEP_RQS]);
+          if (fk_a) CHECK((long long)n_fkl_step == r[C_FKL_STEP]);
+          if (fk_r) CHECK((long long)n_fkl_step_rqs == r[C_FKL_STEP_RQS]);
+          CHECK(st_r == (r[C_STEP_RQS] >= 0) && fk_a == (r[C_FKL_STEP] >= 0) && fk_r == (r[C_FKL_STEP_RQS] >= 0));
+        }
+        ++row;
         CHECK(tb > 0 && tb % 256 == 0);
         if (is_composite(&g)) {
           int64_t s = 0;
@@ -161,7 +230,7 @@ int main() {
             CHECK(chunk == N || chunk % 32 == 0);
             const size_t sb = affine_stash_bytes(&ctx, &g, chunk);
             CHECK(sb > 0 && (budget <= 0 || sb <= (size_t)budget));
-            CHECK((size_t)total >= step_fused_need(&ctx, &g, N) + carve_bytes(nf_affine_wimg_bytes(&g)));  // nf_elbo_step's own form
+            if (st_a) CHECK((size_t)total >= n_step + carve_bytes(nf_affine_wimg_bytes(&g)));  // nf_elbo_step's own form
             // slabs of a chunked step: never more than one slab per workgroup of every chunk
             const long stride = coupling_slab_floats(&ctx, &g, N);
             const size_t sf = chunked_slab_floats(&ctx, &g, N, chunk, stride);
@@ -219,6 +288,7 @@ int main() {
       }
     }
   }
+  CHECK(row * kNCol == golden.size());  // every recorded row was met
   // ---- null / range checks of public entry points that must fail before touching a device -----------------------------
   {
     nf_flow_desc g = mk(NF_KIND_REALNVP, NF_DTYPE_F32, 64, 4, {64, 64});

@@ -103,7 +103,8 @@ def test_api_host_side_under_asan_ubsan(tmp_path):
     clangxx = os.path.join(os.path.dirname(os.path.realpath(HIPCC)), "..", "lib", "llvm", "bin", "clang++")
     r = subprocess.run([clangxx, *SAN, "-o", exe, *objs, stub_obj, "-ldl", "-lpthread"], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
-    r = subprocess.run([exe], capture_output=True, text=True, env=ENV, timeout=300)
+    golden = os.path.join(ROOT, "tests", "golden", "workspace_sizes.json")  # the sizes before the layouts: equal, bounds no larger
+    r = subprocess.run([exe, golden], capture_output=True, text=True, env=ENV, timeout=300)
     assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
     assert "nf_api host check: ok" in r.stdout
     assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]

@@ -1794,11 +1794,28 @@ struct BwdPairLds {
 // for the consumer's sake.  Tiles beyond the parked ones (more than two rounds) keep the round trip, in the body they always had.
 // 2 x 16 + 1 x 16 parked registers: with the second tile's g1 as well the unparked body (64 parked + its own early conditioner
 // half) no longer fits -- 56 / 80 bytes of scratch in the whole-batch / ragged forms (tests/test_cotangent_residency_cpu.py).
+// Carry across the coupling boundary (forward direction).  The masks alternate and a pair's tiles never change hands, so the
+// conditioner half's outgoing cotangent (half + g2t) + g2s that phase S of coupling k stores is the transformed half's cotangent g1
+// that the same wave loads at the head of phase T of coupling k + 1.  For the parked tiles it stays in registers instead: slot 0's
+// goes straight into g1[0] of the next coupling (and is not stored while another coupling follows in the launch: its phase S
+// takes g1 from there as well); slot 1's into `cy`, which dies at the head of the next phase T's slot-1 body, before g2[1] is
+// born (its phase S still re-reads the half from memory, so its store stays) -- the live peak stays 48 registers.  The first
+// processed coupling's g1 of both tiles is loaded into the same registers in front of the coupling loop, so that no body has a
+// run-time branch around its prologue loads.  The same bits either way: the value kept is the value stored.
+#ifndef NF_PAIR_CARRY
+#define NF_PAIR_CARRY 2  // how many of the parked slots carry (A/B builds: 0 none, 1 slot 0 only)
+#endif
+// Whole batches at d = 64 (FULL) only: in the ragged / d < 64 form the masks' state no longer fits beside a carried tile, which
+// phase S's slot-1 body holds on top of its own parked registers -- 20 bytes of scratch with both slots carried, 12 with slot 0
+// alone.  That form keeps the round trip between couplings.
+template <bool FULL>
+constexpr int pair_carry() { return FULL ? NF_PAIR_CARRY : 0; }
 #define NF_PAIR_PARK 2
 #define NF_PAIR_PARK_G1 1
 template <class G>
 struct PairPark {
   f32x16 g1[NF_PAIR_PARK_G1][G::CB], g2[NF_PAIR_PARK][G::MB];
+  f32x16 cy[G::CB];  // slot 1's carry (NF_PAIR_CARRY > 1)
 };
 
 // FULL: d = 64 and N a multiple of the tile (no sample / feature masks).  INVD: reverse pass of the INVERSE coupling
@@ -1808,10 +1825,11 @@ struct PairPark {
 // this kernel had before parking; the inverse direction has no other).  A template parameter, so that every body knows which
 // parked registers are live around it.  last: nobody reads this coupling's input cotangent (BwdAllArgs::no_xbar, coupling
 // processed last): no dX1 and no tile stores -- the closing ones behind one wave-uniform branch, phase S's x1bar through a
-// descriptor of extent 0, which the hardware drops, so that the tile's prologue stays free of branches.
+// descriptor of extent 0, which the hardware drops, so that the tile's prologue stays free of branches.  more: another coupling
+// follows in this launch (a carried slot 0 then keeps its closing value and does not store it).
 template <class G, bool PHASE_S, bool FULL, bool INVD, bool SLIM, bool PB6, bool DW6, int SLOT>
 __device__ __forceinline__ void pair_produce(const CouplingArgs &a, const float *__restrict__ img, float *__restrict__ sp,
-                                             StashFirst<G> &f, PairPark<G> &pk, bool last, float *stash, int k, int ncoup,
+                                             StashFirst<G> &f, PairPark<G> &pk, bool last, bool more, float *stash, int k, int ncoup,
                                              float *__restrict__ ybar, const float *__restrict__ lbar, float lbar_const, long tile,
                                              long next_tile, bool live, int l31, int hi, int par, long long *tr = nullptr) {
   using SG = StashGeo<G, SLIM>;
@@ -1834,8 +1852,13 @@ __device__ __forceinline__ void pair_produce(const CouplingArgs &a, const float 
   constexpr bool FIRST = PHASE_S == INVD;  // the coupling's first phase
   constexpr bool parked = SLOT >= 0, parked1 = SLOT >= 0 && SLOT < NF_PAIR_PARK_G1;
   constexpr int S2 = SLOT < 0 ? 0 : SLOT, S1 = parked1 ? SLOT : 0;
+  constexpr bool carried = !INVD && SLOT >= 0 && SLOT < pair_carry<FULL>();  // g1 of phase T arrives in registers, phase S leaves the next one
+  static_assert(!carried || (G::CB == G::MB && SLOT < 2 && NF_PAIR_CARRY <= NF_PAIR_PARK), "a conditioner half becomes a transformed half");
   f32x16 g1[G::CB];
-  if constexpr (FIRST || !parked1) {
+  if constexpr (carried && !PHASE_S) {
+#pragma unroll
+    for (int b = 0; b < G::CB; ++b) g1[b] = SLOT == 0 ? pk.g1[0][b] : pk.cy[b];
+  } else if constexpr (FIRST || !parked1) {
 #pragma unroll
     for (int b = 0; b < G::CB; ++b)
 #pragma unroll
@@ -1875,7 +1898,7 @@ __device__ __forceinline__ void pair_produce(const CouplingArgs &a, const float 
         d3[b][r] = ok ? (gv * f.uv[b][r] + lb) * (1.f - sv * sv) : 0.f;  // S-bar through tanh
       }
     }
-  if constexpr (FIRST && parked1) {  // the bits the second phase would load: phase T never writes these slots
+  if constexpr (FIRST && parked1 && !carried) {  // the bits the second phase would load: phase T never writes these slots
 #pragma unroll
     for (int b = 0; b < G::CB; ++b) pk.g1[S1][b] = g1[b];
   }
@@ -1984,6 +2007,21 @@ __device__ __forceinline__ void pair_produce(const CouplingArgs &a, const float 
   } else if constexpr (FIRST) {
 #pragma unroll
     for (int b = 0; b < G::MB; ++b) pk.g2[S2][b] = g2[b];
+  } else if constexpr (carried) {  // the next coupling's g1: kept, and stored where somebody reads it from memory
+#pragma unroll
+    for (int b = 0; b < G::MB; ++b)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float nv = (gold[b][r] + pk.g2[S2][b][r]) + g2[b][r];
+        if constexpr (SLOT == 0) pk.g1[0][b][r] = nv;
+        else pk.cy[b][r] = nv;
+      }
+    if (SLOT != 0 || !more) {  // slot 0: only the coupling processed last (the pullback's input cotangent)
+#pragma unroll
+      for (int b = 0; b < G::MB; ++b)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) tile_store(gio, tile_soff(b, r, par_c), SLOT == 0 ? pk.g1[0][b][r] : pk.cy[b][r]);
+    }
   } else {
 #pragma unroll
     for (int b = 0; b < G::MB; ++b)
@@ -2294,11 +2332,28 @@ __global__ __launch_bounds__(512) void k_affine_bwd_pair(BwdAllArgs aa, float *s
   if (role == 0) {
     StashFirst<G> f;
     if (INVD && tile0 < ntiles) stash_issue_first<G, SLIM>(f, stash, aa.ncoup - 1, aa.ncoup, tile0, l31, hi);  // S runs first
+    PairPark<G> pk;  // g1 / g2: written in the coupling's first phase, read in its second; g1[0] / cy: carried to the next coupling
+    if constexpr (!INVD && pair_carry<FULL>() > 0) {  // the first coupling's g1 of the carried tiles (coupling 0 transforms the even half)
+#pragma unroll
+      for (int s = 0; s < pair_carry<FULL>(); ++s) {
+        const long tile = tile0 + s * tstride;
+        if (tile < ntiles) {
+          const TileIO gio = make_tile_io(ybar, tile, aa.d, l31, hi);
+#pragma unroll
+          for (int b = 0; b < G::CB; ++b)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+              const float v = tile_load(gio, tile_soff(b, r, 0));
+              if (s == 0) pk.g1[0][b][r] = v;
+              else pk.cy[b][r] = v;
+            }
+        }
+      }
+    }
 #pragma unroll 1
     for (int step = 0; step < aa.ncoup; ++step) {
       const int k = INVD ? aa.ncoup - 1 - step : step;  // the inverse chain's reverse pass runs in execution order
-      const bool last = aa.no_xbar != 0 && step + 1 == aa.ncoup;
-      PairPark<G> pk;  // written in the coupling's first phase, read in its second
+      const bool last = aa.no_xbar != 0 && step + 1 == aa.ncoup, more = step + 1 < aa.ncoup;
       CouplingArgs a;
       a.theta = nullptr;
       a.img_s = aa.wimg + (size_t)(2 * k) * G::SIZE;
@@ -2329,8 +2384,8 @@ __global__ __launch_bounds__(512) void k_affine_bwd_pair(BwdAllArgs aa, float *s
 #else
           long long *tr = nullptr;
 #endif
-          if (!is_s) pair_produce<G, false, FULL, INVD, SLIM, PB6, DW6, SLOT>(a, img, sp, f, pk, last, stash, k, aa.ncoup, ybar, lbar, lbar_const, tile, nt, tile < ntiles, l31, hi, it & 1, tr);
-          else pair_produce<G, true, FULL, INVD, SLIM, PB6, DW6, SLOT>(a, img, sp, f, pk, last, stash, k, aa.ncoup, ybar, lbar, lbar_const, tile, nt, tile < ntiles, l31, hi, it & 1, tr);
+          if (!is_s) pair_produce<G, false, FULL, INVD, SLIM, PB6, DW6, SLOT>(a, img, sp, f, pk, last, more, stash, k, aa.ncoup, ybar, lbar, lbar_const, tile, nt, tile < ntiles, l31, hi, it & 1, tr);
+          else pair_produce<G, true, FULL, INVD, SLIM, PB6, DW6, SLOT>(a, img, sp, f, pk, last, more, stash, k, aa.ncoup, ybar, lbar, lbar_const, tile, nt, tile < ntiles, l31, hi, it & 1, tr);
         };
         // the first NF_PAIR_PARK rounds with their parked registers (one body per slot), the rest through memory
         int it0 = 0;
@@ -2481,9 +2536,11 @@ int nf_affine_epilogue(nf_ctx *ctx, const nf_flow_desc *desc, int mode, const fl
   a.c2 = (float)(1.0 - pow(b2, (double)t_val + 1.0));
   const unsigned grid = (unsigned)nf_affine_epilogue_blocks(desc);
   if (mode != 1) ctx->wimg_gen++;  // the fp32 images are rewritten (Adam's theta): B6 copies are stale
-  // (Measured and removed: the epilogue refreshing the B6T images element by element as well, which saves the next step its 7 us
-  // conversion launch -- the reverse kernel then stages images that were written a whole forward kernel earlier instead of a
-  // moment ago and runs 4-5 us slower: 0.594 against 0.594 ms per step.)
+  // (Measured and removed, twice: the epilogue refreshing the B6T images element by element as well, which saves the next step its
+  // conversion launch.  First with one thread per 16-byte row -- the reverse kernel then stages images that were written a whole
+  // forward kernel earlier instead of a moment ago and runs 4-5 us slower: 0.594 against 0.594 ms per step.  Then in the Adam
+  // thread's own index, a quad of lanes gathering 8 bytes per part: 0.5665 [0.5652-0.5693] against 0.5655 [0.5646-0.5707] ms,
+  // five alternating pairs on one box (profiles/cotangent_carry_ab.txt).)
   ProfScope ps(ctx, mode == 2 ? "adam" : "reduce_slabs");
   const bool h64 = size != NetGeo<1, 1, 1, 1>::SIZE;
 #define NF_EPI(GEO)                                                                                                          \

@@ -314,8 +314,11 @@ int nf_sgd_update(nf_ctx *ctx, int32_t dtype, void *theta, const void *g, void *
  * LDS-resident RealNVP flows with any built-in target (the diagonal Gaussian of BASELINE cfg 2; Banana, Funnel, and at
  * d = 2 WarpedGauss and Cross) run as three launches -- fused forward (draws, chain, target, ELBO sums), reverse pass, fused
  * epilogue (slab sum, loss, Adam, norm, and the packed weight images of the UPDATED theta for the next step); LDS-resident
- * spline couplings on one rank as fused forward, one reverse launch per coupling and the same kind of epilogue.  Either
- * way theta, m and v are bit for bit those of nf_elbo_value_and_grad + nf_adam_update.  Every other flow, and a target
+ * spline couplings on one rank as fused forward, one reverse launch per coupling and the same kind of epilogue.  Planar,
+ * radial and mean-field flows whose whole step is one forward-and-reverse launch (Float32 or Float64, standard-normal base,
+ * not a composition), on ONE rank, with any built-in target: three launches -- that launch, a fused epilogue (per layer: slab
+ * sum and chain rule, Adam on the layer's parameters, its share of norm(g)^2; the loss) and the one-block finish of the norm.
+ * In every case theta, m and v are bit for bit those of nf_elbo_value_and_grad + nf_adam_update.  Every other flow, and a target
  * whose arguments fail their check (NF_ERR_ARG from the target launch), runs the split sequence inside the call.  BY DEFAULT every call packs its weight images from theta (one small launch): whatever happened to theta
  * between two calls -- an in-place edit, a free and a re-allocation at the same address -- the step runs on the weights
  * theta holds now.  A training loop that OWNS theta (src/optimize.jl:85-99 does: nobody else touches theta between
@@ -339,8 +342,9 @@ int nf_ctx_set_weight_cache(nf_ctx *ctx, int32_t enable);
  * warm-up call (workspace sizing and kernel attributes are not capturable; use nf_ctx_set_arena or the warm-up's
  * grow-only allocation), capture a call between hipStreamBeginCapture / hipStreamEndCapture on the context's stream
  * and replay the graph.  Accepted: Float32 LDS-resident RealNVP flows (with or without a communicator) and, on a context
- * without a communicator, Float32 LDS-resident spline couplings -- each with any of the five built-in targets (valid
- * arguments: WarpedGauss and Cross need d = 2).  NF_ERR_UNSUPPORTED for everything else. */
+ * without a communicator, Float32 LDS-resident spline couplings and the planar, radial and mean-field flows nf_elbo_step
+ * runs in three launches (Float32 or Float64) -- each with any of the five built-in targets (valid arguments: WarpedGauss
+ * and Cross need d = 2).  NF_ERR_UNSUPPORTED for everything else. */
 int nf_elbo_step_enqueue(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, void *theta, void *m, void *v,
                          int64_t N, uint64_t seed, uint32_t *step_device, double lr, double beta1, double beta2,
                          double eps, void *out_loss_gnorm_device);

@@ -118,7 +118,10 @@ bool nf_simple_step_supported(const nf_flow_desc *desc);
 size_t nf_simple_step_ws_bytes(nf_ctx *, const nf_flow_desc *, long N);
 int nf_simple_elbo_step(nf_ctx *, const nf_flow_desc *, const nf_target *, const void *theta, const void *xs, long N,
                         uint64_t seed, uint64_t off, uint32_t stream_id, double gscale, double lbar_const, double *partial,
-                        double pscale, void *ws, void *gtheta_out, long *npartial);
+                        double pscale, void *ws, void *gtheta_out, long *npartial, const uint32_t *step_device);
+int nf_simple_epilogue_blocks(const nf_flow_desc *desc);
+int nf_simple_epilogue(nf_ctx *, const nf_flow_desc *, const void *slabs, int nblk, void *g, const double *lpart, void *theta, void *m,
+                       void *v, double lr, double b1, double b2, double eps, unsigned t_val, const unsigned *t_ptr, double *gpart);
 int nf_simple_rand(nf_ctx *, const nf_flow_desc *, const void *theta, long N, uint64_t seed, uint64_t off, uint32_t stream_id,
                    void *y);
 
@@ -1928,7 +1931,7 @@ extern "C" int nf_elbo_value_and_grad(nf_ctx *ctx, const nf_flow_desc *desc, con
       NF_TRY(nf_target_check(target, desc->d));
       long np = 0;
       NF_TRY(nf_simple_elbo_step(ctx, desc, target, theta, xs, N, seed, sample_offset, stream_id, -inv, -inv, partial, -inv, sws,
-                                 out, &np));
+                                 out, &np, nullptr));
       if (dt == NF_DTYPE_F32) return nf_launch_finish_sum(ctx, partial, np, 0, nullptr, (float *)out + P, nullptr);
       return nf_launch_finish_sum(ctx, partial, np, 0, (double *)out + P, nullptr, nullptr);
     }
@@ -2047,7 +2050,7 @@ struct StepCall {
   const float *ys;
   long N, Ng;
   uint64_t seed;
-  float *theta, *m, *v;
+  void *theta, *m, *v;  // of the flow's element type
   uint32_t step, *step_device;
   double lr, beta1, beta2, eps;
 };
@@ -2092,15 +2095,15 @@ struct AffineStepBufs {
 // (and, in the graph-replay form, the step counter's increment)
 static int affine_step_tail(nf_ctx *ctx, const nf_flow_desc *desc, const StepCall &c, const AffineStepBufs &b, const ChunkCounts &cc) {
   const long P = nf_param_count(desc);
-  float *gbuf = (float *)ctx->gbuf;
+  float *gbuf = (float *)ctx->gbuf, *theta = (float *)c.theta, *m = (float *)c.m, *v = (float *)c.v;
   if (!ctx->comm || ctx->comm_size == 1) {
-    NF_TRY(nf_affine_epilogue(ctx, desc, 3, b.slab, (int)cc.nslab, gbuf, b.partial, (int)cc.npart, c.theta, c.m, c.v, c.lr, c.beta1, c.beta2,
+    NF_TRY(nf_affine_epilogue(ctx, desc, 3, b.slab, (int)cc.nslab, gbuf, b.partial, (int)cc.npart, theta, m, v, c.lr, c.beta1, c.beta2,
                               c.eps, c.step, c.step_device, b.gpart));
   } else {
     NF_TRY(nf_affine_epilogue(ctx, desc, 1, b.slab, (int)cc.nslab, gbuf, b.partial, (int)cc.npart, nullptr, nullptr, nullptr, c.lr, c.beta1,
                               c.beta2, c.eps, c.step, nullptr, b.gpart));
     NF_TRY(nf_allreduce_grad_loss(ctx, NF_DTYPE_F32, gbuf, P + 1));
-    NF_TRY(nf_affine_epilogue(ctx, desc, 2, nullptr, 0, gbuf, nullptr, 0, c.theta, c.m, c.v, c.lr, c.beta1, c.beta2, c.eps, c.step,
+    NF_TRY(nf_affine_epilogue(ctx, desc, 2, nullptr, 0, gbuf, nullptr, 0, theta, m, v, c.lr, c.beta1, c.beta2, c.eps, c.step,
                               c.step_device, b.gpart));
   }
   return nf_launch_finish_sum(ctx, b.gpart, b.eblocks, 1, nullptr, gbuf + P + 1, nullptr, c.step_device);
@@ -2110,7 +2113,7 @@ template <class F>
 static int affine_step_fused(nf_ctx *ctx, const nf_flow_desc *desc, const StepCall &c, long npartial, bool inv_dir, F fwd) {
   AffineStepBufs b;
   NF_TRY(ws_carve(ctx, &b, desc, c.N, npartial));
-  NF_TRY(step_images_ensure(ctx, desc, c.theta));
+  NF_TRY(step_images_ensure(ctx, desc, (const float *)c.theta));
   ChunkCounts cc;
   NF_TRY(stash_chunk_loop(ctx, desc, c.N, b.stash_nc, b.stash, b.gt, 1.0 / (double)c.Ng, b.slab, inv_dir, &cc,
                           [&](long o, long nc, long npart, long *left) {
@@ -2118,7 +2121,7 @@ static int affine_step_fused(nf_ctx *ctx, const nf_flow_desc *desc, const StepCa
                             return fwd(o, nc, b.gt + o * desc->d, b.partial + npart, b.stash);
                           }));
   NF_TRY(affine_step_tail(ctx, desc, c, b, cc));
-  step_images_written(ctx, desc, c.theta);
+  step_images_written(ctx, desc, (const float *)c.theta);
   return NF_OK;
 }
 
@@ -2166,18 +2169,59 @@ static int rqs_step_fused(nf_ctx *ctx, const nf_flow_desc *desc, const StepCall 
   RqsStepBufs b;
   NF_TRY(ws_carve(ctx, &b, desc, c.N, npartial));
   float *gbuf = (float *)ctx->gbuf;
-  NF_TRY(step_images_ensure(ctx, desc, c.theta));
+  NF_TRY(step_images_ensure(ctx, desc, (const float *)c.theta));
   NF_TRY(fwd(b.xt, b.gt, b.partial, b.tape));
   const int nc = 2 * desc->nlayers;
   for (int s = 0; s < nc; ++s)  // the inverse chain's reverse pass: forward execution order, as coupling_inv_bwd
     NF_TRY(nf_rqs_bwd(ctx, desc, inv_dir ? nc - 1 - s : s, b.xt, b.gt, nullptr, (float)(-inv), c.N, b.slab, b.stride, b.grid, inv_dir,
                       b.tape));
-  NF_TRY(nf_rqs_epilogue(ctx, desc, b.slab, b.grid, gbuf, b.partial, (int)nf_rqs_chain_grid(ctx, c.N), c.theta, c.m, c.v, c.lr, c.beta1,
-                         c.beta2, c.eps, c.step, b.gpart, c.step_device));
+  NF_TRY(nf_rqs_epilogue(ctx, desc, b.slab, b.grid, gbuf, b.partial, (int)nf_rqs_chain_grid(ctx, c.N), (float *)c.theta, (float *)c.m,
+                         (float *)c.v, c.lr, c.beta1, c.beta2, c.eps, c.step, b.gpart, c.step_device));
   // norm(g); in the graph-replay form also the step counter's increment, as the RealNVP step does it
   NF_TRY(nf_launch_finish_sum(ctx, b.gpart, b.eblocks, 1, nullptr, gbuf + P + 1, nullptr, c.step_device));
-  step_images_written(ctx, desc, c.theta);
+  step_images_written(ctx, desc, (const float *)c.theta);
   return NF_OK;
+}
+
+// The same for planar, radial and mean-field flows whose whole step is one forward-and-reverse launch (k_simple_step /
+// k_planar_step / k_radial_step), Float32 or Float64, on ONE rank: that launch, k_simple_epilogue (slab sum and chain rule per
+// layer, the loss, Adam on the layer's slice, the layer's partial of ||g||^2) and k_finish_sum (||g||, and the counter's
+// increment in the graph-replay form) -- three launches where the split sequence has five.
+// sizing (nf_workspace_bytes): any target, whatever the communicator
+static bool step_fusable_simple(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, bool sizing = false) {
+  if ((ctx->comm && !sizing) || flow_base(desc) || is_composite(desc)) return false;
+  if (desc->kind != NF_KIND_PLANAR && desc->kind != NF_KIND_RADIAL && desc->kind != NF_KIND_MEANFIELD) return false;
+  if (desc->dtype != NF_DTYPE_F32 && desc->dtype != NF_DTYPE_F64) return false;
+  if (!nf_simple_step_supported(desc)) return false;
+  return sizing || nf_target_check(target, desc->d) == NF_OK;
+}
+// the step launch's loss partials, its gradient slabs (one per workgroup and layer), the epilogue's block partials of ||g||^2
+struct SimpleStepBufs {
+  long eblocks;
+  double *partial, *gpart;
+  char *slabs;
+  SimpleStepBufs() {}
+  SimpleStepBufs(Carver &cv, nf_ctx *ctx, const nf_flow_desc *desc, long N) {
+    eblocks = nf_simple_epilogue_blocks(desc);
+    partial = cv.take<double>(elbo_npartial(ctx, desc, N));
+    slabs = cv.take<char>(nf_simple_step_ws_bytes(ctx, desc, N));
+    gpart = cv.take<double>(eblocks);
+  }
+};
+static int simple_step_fused(nf_ctx *ctx, const nf_flow_desc *desc, const StepCall &c) {
+  const long P = nf_param_count(desc);
+  const double inv = 1.0 / (double)c.Ng;
+  SimpleStepBufs b;
+  NF_TRY(ws_carve(ctx, &b, desc, c.N));
+  long np = 0;
+  NF_TRY(nf_simple_elbo_step(ctx, desc, c.target, c.theta, nullptr, c.N, c.seed, 0, c.step, -inv, -inv, b.partial, -inv, b.slabs, nullptr,
+                             &np, c.step_device));
+  NF_TRY(nf_simple_epilogue(ctx, desc, b.slabs, (int)np, ctx->gbuf, b.partial, c.theta, c.m, c.v, c.lr, c.beta1, c.beta2, c.eps, c.step,
+                            c.step_device, b.gpart));
+  // norm(g); in the graph-replay form also the step counter's increment, as the RealNVP step does it
+  if (desc->dtype == NF_DTYPE_F32)
+    return nf_launch_finish_sum(ctx, b.gpart, b.eblocks, 1, nullptr, (float *)ctx->gbuf + P + 1, nullptr, c.step_device);
+  return nf_launch_finish_sum(ctx, b.gpart, b.eblocks, 1, (double *)ctx->gbuf + P + 1, nullptr, nullptr, c.step_device);
 }
 
 extern "C" int nf_ctx_weights_changed(nf_ctx *ctx) {
@@ -2295,7 +2339,8 @@ static int step_run(nf_ctx *ctx, const nf_flow_desc *desc, const StepCall &c, do
   const bool elbo = c.target != nullptr;
   const bool affine = elbo ? step_fusable(ctx, desc, c.target, N) : fkl_step_fusable(ctx, desc, N);
   const bool rqs = !affine && (elbo ? step_fusable_rqs(ctx, desc, c.target) : fkl_step_fusable_rqs(ctx, desc, N));
-  if (c.step_device && !affine && !rqs) return NF_ERR_UNSUPPORTED;
+  const bool simple = elbo && !affine && !rqs && step_fusable_simple(ctx, desc, c.target);
+  if (c.step_device && !affine && !rqs && !simple) return NF_ERR_UNSUPPORTED;
   NF_TRY(gbuf_reserve(ctx, gbuf_need(P, esize(desc->dtype))));
   const double inv = 1.0 / (double)c.Ng;
   if (affine && elbo) {  // this rank draws samples [rank N, (rank + 1) N) of the global batch
@@ -2317,11 +2362,14 @@ static int step_run(nf_ctx *ctx, const nf_flow_desc *desc, const StepCall &c, do
     NF_TRY(rqs_step_fused(ctx, desc, c, nf_rqs_chain_grid(ctx, N), true, [&](float *zt, float *gt, double *partial, void *tape) {
       return nf_rqs_chain_fkl(ctx, desc, c.ys, N, zt, gt, -inv, partial, -inv, tape);
     }));
+  } else if (simple) {
+    NF_TRY(simple_step_fused(ctx, desc, c));
   } else {
     NF_TRY(step_split(ctx, desc, c));
   }
   if (c.step_device) {
-    if (out_device) NF_HIP(hipMemcpyAsync(out_device, (char *)ctx->gbuf + (size_t)P * 4, 8, hipMemcpyDeviceToDevice, ctx->stream));
+    const size_t es = esize(desc->dtype);  // [loss ; norm] of the flow's element type
+    if (out_device) NF_HIP(hipMemcpyAsync(out_device, (char *)ctx->gbuf + (size_t)P * es, 2 * es, hipMemcpyDeviceToDevice, ctx->stream));
     return NF_OK;
   }
   if (loss_host || gnorm_host) return step_readback(ctx, desc, P, loss_host, gnorm_host);
@@ -2332,7 +2380,7 @@ extern "C" int nf_elbo_step(nf_ctx *ctx, const nf_flow_desc *desc, const nf_targ
                             void *v, int64_t N, uint64_t seed, uint32_t step, double lr, double beta1, double beta2,
                             double eps, double *loss_host, double *gnorm_host) {
   if (!ctx || !target || !theta || !m || !v || N < 1) return NF_ERR_ARG;
-  const StepCall c{target, nullptr, (long)N, (long)N * (ctx->comm ? ctx->comm_size : 1), seed, (float *)theta, (float *)m, (float *)v,
+  const StepCall c{target, nullptr, (long)N, (long)N * (ctx->comm ? ctx->comm_size : 1), seed, theta, m, v,
                    step, nullptr, lr, beta1, beta2, eps};
   return step_run(ctx, desc, c, loss_host, gnorm_host, nullptr);
 }
@@ -2346,7 +2394,7 @@ extern "C" int nf_elbo_step_enqueue(nf_ctx *ctx, const nf_flow_desc *desc, const
                                     int64_t N, uint64_t seed, uint32_t *step_device, double lr, double beta1, double beta2,
                                     double eps, void *out_loss_gnorm_device) {
   if (!ctx || !target || !theta || !m || !v || !step_device || N < 1) return NF_ERR_ARG;
-  const StepCall c{target, nullptr, (long)N, (long)N * (ctx->comm ? ctx->comm_size : 1), seed, (float *)theta, (float *)m, (float *)v,
+  const StepCall c{target, nullptr, (long)N, (long)N * (ctx->comm ? ctx->comm_size : 1), seed, theta, m, v,
                    0, step_device, lr, beta1, beta2, eps};
   return step_run(ctx, desc, c, nullptr, nullptr, out_loss_gnorm_device);
 }
@@ -2364,7 +2412,7 @@ extern "C" int nf_loglikelihood_step(nf_ctx *ctx, const nf_flow_desc *desc, void
                                      double eps, double *loss_host, double *gnorm_host) {
   if (!ctx || !theta || !m || !v || !ys || N_local < 0) return NF_ERR_ARG;
   const long Ng = N_global > 0 ? (long)N_global : (long)N_local * (ctx->comm ? ctx->comm_size : 1);
-  const StepCall c{nullptr, (const float *)ys, (long)N_local, Ng, 0, (float *)theta, (float *)m, (float *)v, step, nullptr, lr, beta1,
+  const StepCall c{nullptr, (const float *)ys, (long)N_local, Ng, 0, theta, m, v, step, nullptr, lr, beta1,
                    beta2, eps};
   return step_run(ctx, desc, c, loss_host, gnorm_host, nullptr);
 }
@@ -2375,7 +2423,7 @@ extern "C" int nf_loglikelihood_step_enqueue(nf_ctx *ctx, const nf_flow_desc *de
                                              double beta2, double eps, void *out_loss_gnorm_device) {
   if (!ctx || !theta || !m || !v || !ys || !step_device || N_local < 0) return NF_ERR_ARG;
   const long Ng = N_global > 0 ? (long)N_global : (long)N_local * (ctx->comm ? ctx->comm_size : 1);
-  const StepCall c{nullptr, (const float *)ys, (long)N_local, Ng, 0, (float *)theta, (float *)m, (float *)v, 0, step_device, lr, beta1,
+  const StepCall c{nullptr, (const float *)ys, (long)N_local, Ng, 0, theta, m, v, 0, step_device, lr, beta1,
                    beta2, eps};
   return step_run(ctx, desc, c, nullptr, nullptr, out_loss_gnorm_device);
 }
@@ -2438,6 +2486,7 @@ extern "C" int64_t nf_workspace_bytes(nf_ctx *ctx, const nf_flow_desc *desc, int
   // the fused forms of nf_elbo_step and nf_loglikelihood_step (the spline forms are sized whatever the communicator)
   if (step_fusable(ctx, desc, nullptr, N, true)) upd(layout_bytes<AffineStepBufs>(ctx, desc, (long)N, elbo_npartial(ctx, desc, N)));
   if (step_fusable_rqs(ctx, desc, nullptr, true)) upd(layout_bytes<RqsStepBufs>(ctx, desc, (long)N, elbo_npartial(ctx, desc, N)));
+  if (step_fusable_simple(ctx, desc, nullptr, true)) upd(layout_bytes<SimpleStepBufs>(ctx, desc, (long)N));
   if (fkl_step_fusable(ctx, desc, N))
     upd(layout_bytes<AffineStepBufs>(ctx, desc, (long)N, fkl_step_npart(ctx, N, affine_stash_chunk(ctx, desc, N))));
   if (fkl_step_fusable_rqs(ctx, desc, N, true)) upd(layout_bytes<RqsStepBufs>(ctx, desc, (long)N, nf_rqs_chain_grid(ctx, N)));

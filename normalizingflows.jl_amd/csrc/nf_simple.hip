@@ -324,17 +324,22 @@ struct SimpleFused {
   double s0, s1, gscale, pscale;
   void *gbar;       // [N][d]
   double *partial;  // [gridDim.x]
+  const uint32_t *step_device;  // non-null: the Philox stream id is read from device memory (hipGraph replay of the step)
 };
+// the Philox stream id of this launch: the host-supplied index, or the device-resident step counter (wave-uniform)
+__device__ __forceinline__ uint32_t fused_stream(const SimpleFused &fu) {
+  return fu.step_device ? *fu.step_device : fu.stream;
+}
 
 template <class T, int DPL>
-__device__ __forceinline__ void draw_row(const SimpleFused &fu, long j, int i0, int d, T (&z)[DPL]) {
+__device__ __forceinline__ void draw_row(const SimpleFused &fu, uint32_t stream, long j, int i0, int d, T (&z)[DPL]) {
   const uint64_t gj = fu.off + (uint64_t)j;
   constexpr int NG = DPL >= 4 ? DPL / 4 : 1;
 #pragma unroll
   for (int m = 0; m < NG; ++m) {
     const int g = i0 / 4 + m;
     T n4[4] = {(T)0, (T)0, (T)0, (T)0};
-    if (4 * g < d) philox_normals4<T>(gj, (uint32_t)g, fu.stream, fu.k0, fu.k1, n4);
+    if (4 * g < d) philox_normals4<T>(gj, (uint32_t)g, stream, fu.k0, fu.k1, n4);
     if constexpr (DPL >= 4) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) z[4 * m + e] = (i0 + 4 * m + e < d) ? n4[e] : (T)0;
@@ -369,7 +374,7 @@ __global__ __launch_bounds__(SB) void k_simple_apply(SimpleArgs a, const T *__re
   // a 16-lane group shares j, so it is converged for the shuffles
   for (long j = (long)blockIdx.x * SPB + threadIdx.x / LPS; j < a.N; j += (long)gridDim.x * SPB) {
     T z[DPL];
-    if (fu.draw) draw_row<T, DPL>(fu, j, i0, d, z);
+    if (fu.draw) draw_row<T, DPL>(fu, fu.stream, j, i0, d, z);
     else row_load<T, DPL>(x + j * d, i0, d, vec, z);
     T logq = 0;
     if (fu.on) {
@@ -800,12 +805,17 @@ __global__ __launch_bounds__(SB, 2) void k_simple_step(SimpleArgs a, const T *__
     for (int k = 0; k < DPL; ++k) acc0[l][k] = acc1[l][k] = (T)0;
   }
   double contrib = 0.0;
+  // the draws' stream id is read once, ahead of the loop (inside it the kernel-argument fetch sits in front of every sample's
+  // Philox rounds: + 0.5-0.8 us of 18-20 at cfg 1) -- except for mean-field, where one more value live across the loop
+  // spills at DPL = 2
+  constexpr bool STREAM_AHEAD = KIND != NF_KIND_MEANFIELD;
+  const uint32_t pstream = STREAM_AHEAD ? fused_stream(fu) : 0u;
   for (long j = (long)blockIdx.x * SPB + threadIdx.x / LPS; j < a.N; j += (long)gridDim.x * SPB) {
     // The layer caches are loop-invariant LDS data; with the layer loops unrolled hipcc would hoist every row of every
     // layer out of the sample loop (2 * DPL registers per layer) and spill.  The clobber keeps the reads inside.
     asm volatile("" ::: "memory");
     T z[DPL];
-    if (fu.draw) draw_row<T, DPL>(fu, j, i0, d, z);
+    if (fu.draw) draw_row<T, DPL>(fu, STREAM_AHEAD ? pstream : fused_stream(fu), j, i0, d, z);
     else row_load<T, DPL>(xs + j * d, i0, d, vec, z);
     T ss = 0;
 #pragma unroll
@@ -1146,6 +1156,7 @@ __global__ __launch_bounds__(SB, (PG::NLR <= 6 ? 2 : 1)) void k_planar_step(Simp
       for (int cb = 0; cb < PG::GCB; ++cb) G[rb][cb][r] = 0.f;
   }
   double contrib = 0.0;
+  const uint32_t pstream = fused_stream(fu);
   // layer rows this lane fetches as A / B operands (clamped rows feed output columns nobody reads)
   const int s16 = lane & 15, lg = lane >> 4;
   const int erow = s16 < NL ? s16 : NL - 1;
@@ -1166,7 +1177,7 @@ __global__ __launch_bounds__(SB, (PG::NLR <= 6 ? 2 : 1)) void k_planar_step(Simp
         float n4[4] = {0.f, 0.f, 0.f, 0.f};
         if (f0 < d && valid) {
           if (fu.draw) {
-            philox_normals4<float>(fu.off + (uint64_t)j, (uint32_t)(f0 >> 2), fu.stream, fu.k0, fu.k1, n4);
+            philox_normals4<float>(fu.off + (uint64_t)j, (uint32_t)(f0 >> 2), pstream, fu.k0, fu.k1, n4);
           } else {
             const float *row = xs + j * d + f0;
             if (a.vec) {
@@ -1520,6 +1531,7 @@ __global__ __launch_bounds__(SB, 2) void k_radial_step(SimpleArgs a, const float
 #pragma unroll
   for (int l = 0; l < NL; ++l) acc[l] = sab[l] = 0.f;
   double contrib = 0.0;
+  const uint32_t pstream = fused_stream(fu);
   const float dm1 = (float)(d - 1);
   const long ntiles = (a.N + 31) / 32;
   for (long tile = (long)blockIdx.x * 4 + wave; tile < ntiles; tile += (long)gridDim.x * 4) {
@@ -1536,7 +1548,7 @@ __global__ __launch_bounds__(SB, 2) void k_radial_step(SimpleArgs a, const float
         float n4[4] = {0.f, 0.f, 0.f, 0.f};
         if (f0 < d && valid) {
           if (fu.draw) {
-            philox_normals4<float>(fu.off + (uint64_t)j, (uint32_t)(f0 >> 2), fu.stream, fu.k0, fu.k1, n4);
+            philox_normals4<float>(fu.off + (uint64_t)j, (uint32_t)(f0 >> 2), pstream, fu.k0, fu.k1, n4);
           } else {
             const float *row = xs + j * d + f0;
             if (a.vec) {
@@ -1739,11 +1751,10 @@ __global__ __launch_bounds__(SB, 2) void k_radial_step(SimpleArgs a, const float
 // row groups each sum every (FB/64)-th slab with 64 consecutive columns per wave (coalesced, independent loads),
 // then the row groups are added in a fixed order (deterministic).
 #define FB 512
+// (the body of k_simple_finalize and the first half of k_simple_epilogue: layer blockIdx.x's gradient -> gtheta)
 template <class T>
-__global__ __launch_bounds__(FB) void k_simple_finalize(SimpleArgs a, const T *__restrict__ theta,
-                                                        const T *__restrict__ slabs, int nblk_bwd,
-                                                        T *__restrict__ gtheta) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+__device__ __forceinline__ void simple_finalize_layer(const SimpleArgs &a, const T *__restrict__ theta, const T *__restrict__ slabs,
+                                                      int nblk_bwd, T *__restrict__ gtheta, char *smem) {
   const int d = a.d, LP = lp_of(d);
   T *sum = (T *)smem;  // LP
   T *red = sum + LP;   // [FB / 64][LP]
@@ -1799,6 +1810,85 @@ __global__ __launch_bounds__(FB) void k_simple_finalize(SimpleArgs a, const T *_
     for (int i = threadIdx.x; i < d; i += FB) g[i] = sum[i];
   } else {
     for (int i = threadIdx.x; i < d; i += FB) g[i] = sum[i] + sum[2 * d] / p[i];
+  }
+}
+template <class T>
+__global__ __launch_bounds__(FB) void k_simple_finalize(SimpleArgs a, const T *__restrict__ theta,
+                                                        const T *__restrict__ slabs, int nblk_bwd,
+                                                        T *__restrict__ gtheta) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  simple_finalize_layer<T>(a, theta, slabs, nblk_bwd, gtheta, smem);
+}
+
+// The tail of the fused training step (nf_elbo_step for planar / radial / mean-field flows): k_simple_finalize's slab sum
+// and chain rule for layer blockIdx.x (gradient -> g[0, P)), then Adam on that layer's slice of theta / m / v through the
+// element function of k_adam, and the block's partial of sum g^2 (finished by k_finish_sum, which takes the root).  A
+// layer's update needs only that layer's gradient: nothing crosses blocks.  Block 0 also sums the step kernel's loss
+// partials into g[P], in k_finish_sum's order.  Adam's t - 1 is t_val or, for hipGraph replay, the device counter *t_ptr
+// (incremented by the finishing launch, after every block of this one has read it).
+template <class T>
+struct SimpleEpiArgs {
+  const T *slabs;
+  int nblk_bwd;
+  T *g;                 // [P + 2]: gradient, loss, gradient norm
+  long P;
+  const double *lpart;  // loss partials of the step launch, finished into g[P]
+  int nlpart;
+  T *theta, *m, *v;
+  T lr, b1, b2, eps, c1, c2;  // c1 = 1 - b1^t, c2 = 1 - b2^t, computed on the host as nf_launch_adam does (t_ptr == nullptr)
+  double b1d, b2d;
+  const unsigned *t_ptr;
+  double *gpart;        // [gridDim.x] partial sums of g^2
+};
+template <class T>
+__global__ __launch_bounds__(FB) void k_simple_epilogue(SimpleArgs a, SimpleEpiArgs<T> e) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  __shared__ double sm[FB / 64];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (blockIdx.x == 0) {  // the loss: 256 strided accumulators, wave sums, the four waves in order (k_finish_sum)
+    double c = 0.0;
+    if (threadIdx.x < 256)
+      for (int i = threadIdx.x; i < e.nlpart; i += 256) c += e.lpart[i];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    if (lane == 0) sm[wave] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      double t = 0.0;
+      for (int w = 0; w < 4; ++w) t += sm[w];
+      e.g[e.P] = (T)t;
+    }
+    __syncthreads();
+  }
+  simple_finalize_layer<T>(a, e.theta, e.slabs, e.nblk_bwd, e.g, smem);
+  __syncthreads();  // the layer's gradient, written by this block, is read back below
+  const long off = layer_off(a.kind, a.d, blockIdx.x);
+  const int np = (int)(layer_off(a.kind, a.d, blockIdx.x + 1) - off);
+  T c1 = e.c1, c2 = e.c2;
+  if (e.t_ptr) {  // graph replay: the step count lives on the device
+    const double t = (double)(*e.t_ptr + 1u);
+    c1 = (T)(1.0 - pow(e.b1d, t));
+    c2 = (T)(1.0 - pow(e.b2d, t));
+  }
+  double gg = 0.0;
+  for (int i = threadIdx.x; i < np; i += FB) {
+    const T gi = e.g[off + i];
+    T th = e.theta[off + i], mi = e.m[off + i], vi = e.v[off + i];
+    nf_adam_elem<T>(th, mi, vi, gi, e.lr, e.b1, e.b2, e.eps, c1, c2);
+    e.m[off + i] = mi;
+    e.v[off + i] = vi;
+    e.theta[off + i] = th;
+    gg += (double)gi * (double)gi;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) gg += __shfl_xor(gg, o, 64);
+  if (lane == 0) sm[wave] = gg;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+#pragma unroll
+    for (int w = 0; w < FB / 64; ++w) t += sm[w];
+    e.gpart[blockIdx.x] = t;
   }
 }
 
@@ -2202,11 +2292,12 @@ size_t nf_simple_step_ws_bytes(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
 
 // loss partials (pscale * elbo_j, *npartial block sums in `partial`) and the gradient of the step in two launches:
 // k_simple_step (draws or xs, chain, target, reverse pass, slabs) and k_simple_finalize.  gscale / lbar_const are the
-// cotangents: -1 / N_global for loss = -elbo_batch.
+// cotangents: -1 / N_global for loss = -elbo_batch.  gtheta_out == nullptr: the first launch only -- the *npartial slabs per
+// layer stay in `ws` for nf_simple_epilogue.  step_device != nullptr: the draws' stream id is read from it (stream_id unused).
 template <class T>
 static int step_t(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, const void *theta, const void *xs, long N,
                   uint64_t seed, uint64_t off, uint32_t stream_id, double gscale, double lbar_const, double *partial,
-                  double pscale, void *ws, void *gtheta_out, long *npartial) {
+                  double pscale, void *ws, void *gtheta_out, long *npartial, const uint32_t *step_device) {
   const int nl = desc->kind == NF_KIND_MEANFIELD ? 2 : desc->nlayers;
   SimpleArgs a = make_sargs(desc, 0, nl, false, N);
   a.vec = vec_ok<T>(a.d, dpl_for(a.d), {xs});
@@ -2217,6 +2308,7 @@ static int step_t(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target
   fu.k0 = (uint32_t)seed; fu.k1 = (uint32_t)(seed >> 32); fu.stream = stream_id; fu.off = off;
   fu.mu = target->p0; fu.var = target->p1; fu.s0 = target->s0; fu.s1 = target->s1;
   fu.gscale = gscale; fu.pscale = pscale; fu.gbar = nullptr; fu.partial = partial;
+  fu.step_device = step_device;
   T *slabs = (T *)ws;
   int nb = 0;
   int st;
@@ -2225,6 +2317,7 @@ static int step_t(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target
       NF_TRY(planar_mfma_ok(desc) ? planar_step(ctx, a, theta, xs, fu, lbar_const, slabs, &nb)
                                   : radial_step(ctx, a, theta, xs, fu, lbar_const, slabs, &nb));
       *npartial = nb;
+      if (!gtheta_out) return NF_OK;
       ProfScope pf(ctx, "simple_finalize");
       hipLaunchKernelGGL(k_simple_finalize<T>, dim3(nl), dim3(FB), (size_t)(1 + FB / 64) * lp_of(a.d) * sizeof(T), ctx->stream, a,
                          (const T *)theta, (const T *)slabs, nb, (T *)gtheta_out);
@@ -2236,6 +2329,7 @@ static int step_t(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target
   else st = step_kind<T, NF_KIND_MEANFIELD>(ctx, a, theta, xs, fu, lbar_const, slabs, &nb);
   NF_TRY(st);
   *npartial = nb;
+  if (!gtheta_out) return NF_OK;
   const size_t LP = lp_of(a.d);
   ProfScope pf(ctx, "simple_finalize");
   hipLaunchKernelGGL(k_simple_finalize<T>, dim3(nl), dim3(FB), (size_t)(1 + FB / 64) * LP * sizeof(T), ctx->stream, a,
@@ -2245,11 +2339,41 @@ static int step_t(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target
 
 int nf_simple_elbo_step(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, const void *theta, const void *xs,
                         long N, uint64_t seed, uint64_t off, uint32_t stream_id, double gscale, double lbar_const,
-                        double *partial, double pscale, void *ws, void *gtheta_out, long *npartial) {
+                        double *partial, double pscale, void *ws, void *gtheta_out, long *npartial, const uint32_t *step_device) {
   if (N <= 0) return NF_OK;
   if (desc->dtype == NF_DTYPE_F32)
     return step_t<float>(ctx, desc, target, theta, xs, N, seed, off, stream_id, gscale, lbar_const, partial, pscale, ws,
-                         gtheta_out, npartial);
+                         gtheta_out, npartial, step_device);
   return step_t<double>(ctx, desc, target, theta, xs, N, seed, off, stream_id, gscale, lbar_const, partial, pscale, ws,
-                        gtheta_out, npartial);
+                        gtheta_out, npartial, step_device);
+}
+
+// ---- the fused step's tail (k_simple_epilogue) -----------------------------------------------------------------------
+// slabs: what nf_simple_elbo_step(gtheta_out == nullptr) left (nblk per layer); g: [grad (P) ; loss ; norm] of the flow's element
+// type; lpart: the step launch's nblk loss partials; gpart: one double per layer.  t_val / t_ptr: Adam's t - 1.
+template <class T>
+static int epilogue_t(nf_ctx *ctx, const nf_flow_desc *desc, const void *slabs, int nblk, void *g, long P, const double *lpart,
+                      void *theta, void *m, void *v, double lr, double b1, double b2, double eps, unsigned t_val,
+                      const unsigned *t_ptr, double *gpart) {
+  const int nl = desc->kind == NF_KIND_MEANFIELD ? 2 : desc->nlayers;
+  const SimpleArgs a = make_sargs(desc, 0, nl, false, 0);
+  SimpleEpiArgs<T> e;
+  e.slabs = (const T *)slabs; e.nblk_bwd = nblk; e.g = (T *)g; e.P = P; e.lpart = lpart; e.nlpart = nblk;
+  e.theta = (T *)theta; e.m = (T *)m; e.v = (T *)v;
+  e.lr = (T)lr; e.b1 = (T)b1; e.b2 = (T)b2; e.eps = (T)eps;
+  e.c1 = (T)(1.0 - pow(b1, (double)t_val + 1.0));
+  e.c2 = (T)(1.0 - pow(b2, (double)t_val + 1.0));
+  e.b1d = b1; e.b2d = b2; e.t_ptr = t_ptr; e.gpart = gpart;
+  ProfScope ps(ctx, "simple_epilogue");
+  hipLaunchKernelGGL(k_simple_epilogue<T>, dim3(nl), dim3(FB), (size_t)(1 + FB / 64) * lp_of(a.d) * sizeof(T), ctx->stream, a, e);
+  return (int)hipGetLastError();
+}
+int nf_simple_epilogue_blocks(const nf_flow_desc *desc) { return desc->kind == NF_KIND_MEANFIELD ? 2 : desc->nlayers; }
+int nf_simple_epilogue(nf_ctx *ctx, const nf_flow_desc *desc, const void *slabs, int nblk, void *g, const double *lpart, void *theta,
+                       void *m, void *v, double lr, double b1, double b2, double eps, unsigned t_val, const unsigned *t_ptr,
+                       double *gpart) {
+  const long P = layer_off(desc->kind, desc->d, nf_simple_epilogue_blocks(desc));
+  if (desc->dtype == NF_DTYPE_F32)
+    return epilogue_t<float>(ctx, desc, slabs, nblk, g, P, lpart, theta, m, v, lr, b1, b2, eps, t_val, t_ptr, gpart);
+  return epilogue_t<double>(ctx, desc, slabs, nblk, g, P, lpart, theta, m, v, lr, b1, b2, eps, t_val, t_ptr, gpart);
 }

@@ -392,7 +392,9 @@ def _optimize_fused(flow: Flow, theta0: torch.Tensor, reconstruct, rng: PhiloxRN
     """The loop of `optimize` (src/optimize.jl:85-104) with each iteration ONE library call: nf_elbo_step = draws,
     forward, reverse pass, Adam, norm(g) (three launches for the LDS-resident RealNVP shapes, what bench.py times; fused
     forward + one reverse launch per coupling + fused epilogue for LDS-resident spline couplings -- with ANY built-in target:
-    DiagGaussTarget, BananaTarget, FunnelTarget and, at d = 2, WarpedGaussTarget and CrossTarget).  The
+    DiagGaussTarget, BananaTarget, FunnelTarget and, at d = 2, WarpedGaussTarget and CrossTarget; planar, radial and
+    mean-field flows whose step is one forward-and-reverse launch, Float32 or Float64: that launch, the fused epilogue
+    k_simple_epilogue and the norm's finish -- three launches; every other flow: the split sequence inside the call).  The
     loop owns theta between steps, so it opts in to the library's packed-weight cache (nf_ctx_set_weight_cache) and out
     again on return; a user `hasconverged` sees the live theta and is followed by nf_ctx_weights_changed.  Same numbers
     as `optimize` over value_and_gradient + update (tests/test_gpu_tape.py)."""
@@ -439,7 +441,8 @@ def train_flow(*args, max_iters: int = 1000, optimiser: Adam = None, ADbackend=N
     `ADbackend` is accepted for signature compatibility; gradients come from the library's
     hand-derived reverse pass (the role a custom ADTypes backend plays in the reference).  Reverse-KL runs on a
     built-in target (the diagonal Gaussian, Banana, Funnel, WarpedGauss, Cross: the demos' targets take the same fused
-    kernels as the benchmark's) with Adam go through nf_elbo_step, one library call per iteration (`_optimize_fused`), forward-KL
+    kernels as the benchmark's; planar, radial and mean-field flows the three-launch fused step) with Adam go through
+    nf_elbo_step, one library call per iteration (`_optimize_fused`), forward-KL
     runs with Adam through nf_loglikelihood_step (`_optimize_fused_fkl`); everything else through `optimize` over
     value_and_gradient + update."""
     if isinstance(args[0], PhiloxRNG):

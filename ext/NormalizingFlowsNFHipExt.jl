@@ -52,6 +52,7 @@ end
 
 const NF_KIND_PLANAR, NF_KIND_RADIAL, NF_KIND_REALNVP, NF_KIND_NSF, NF_KIND_MEANFIELD = Int32(0), Int32(1), Int32(2), Int32(3), Int32(4)
 const NF_TARGET_DIAGGAUSS, NF_TARGET_BANANA, NF_TARGET_FUNNEL, NF_TARGET_WARPED, NF_TARGET_CROSS = Int32(0), Int32(1), Int32(2), Int32(3), Int32(4)
+const NF_TARGET_DENSEGAUSS, NF_TARGET_LOGREG = Int32(5), Int32(6)   # linear-predictor targets (nfhip.h)
 dtype_code(::Type{Float32}) = Int32(0)
 dtype_code(::Type{Float64}) = Int32(1)
 
@@ -217,6 +218,39 @@ struct CrossTarget <: NFHipTarget                     # Cross(μ, σ), 2-dimensi
         σ > 0 || error("σ must be > 0")
         return new(μ, σ)
     end
+end
+# Linear-predictor targets.  The device reads a ROW-major matrix [rows × d]: a Julia (column-major) d × rows array, i.e.
+# the transpose, stored as `At`.  Coupling flows only (nf_elbo_* answer NF_ERR_UNSUPPORTED for planar / radial /
+# mean-field / Hamiltonian flows with these kinds).
+struct DenseGaussTarget{V<:ROCVector,M<:ROCMatrix} <: NFHipTarget   # logpdf(MvNormal(μ, Σ), z), Σ = L L'
+    μ::V
+    Wt::M            # transpose of W = inv(L): column-major d × d = W row-major
+    logdetW::Float64
+end
+function DenseGaussTarget(μ::ROCVector{T}, Σ::AbstractMatrix) where {T}
+    L = LinearAlgebra.cholesky(LinearAlgebra.Symmetric(Matrix{Float64}(Σ))).L   # throws PosDefException when Σ is not SPD
+    W = inv(LinearAlgebra.LowerTriangular(Matrix(L)))
+    return DenseGaussTarget(μ, ROCArray(Matrix{T}(transpose(W))), -sum(log, LinearAlgebra.diag(L)))
+end
+struct LogRegTarget{M<:ROCMatrix,S} <: NFHipTarget   # Bayesian logistic regression, prior N(0, σ² I)
+    At::M            # d × n, column i = t_i x_i (row-major n × d for the device)
+    σ::Float64
+    shift::S         # nothing or a ROCVector (d)
+end
+function LogRegTarget(X::AbstractMatrix{T}, t::AbstractVector, σ::Real=1.0; shift=nothing) where {T}
+    σ > 0 || error("nfhip: prior σ must be > 0")
+    s = all(in((-1, 1)), t) ? Float64.(t) : all(in((0, 1)), t) ? 2.0 .* t .- 1.0 : error("nfhip: labels must be in {-1, +1} or {0, 1}")
+    size(X, 1) == length(s) || error("nfhip: one label per row of X")
+    return LogRegTarget(ROCArray(Matrix{T}(transpose(X .* T.(s)))), Float64(σ), shift)
+end
+c_target(t::DenseGaussTarget) = NFTarget(NF_TARGET_DENSEGAUSS, devptr(t.μ), devptr(t.Wt), t.logdetW, 0.0)
+c_target(t::LogRegTarget) = NFTarget(NF_TARGET_LOGREG, t.shift === nothing ? C_NULL : devptr(t.shift), devptr(t.At), Float64(size(t.At, 2)), t.σ)
+function check_target(t::DenseGaussTarget, ::Type{T}, d) where {T}
+    (eltype(t.μ) === T && eltype(t.Wt) === T && length(t.μ) == d && size(t.Wt) == (d, d)) || error("nfhip: target must be a length-$d MvNormal in $T")
+end
+function check_target(t::LogRegTarget, ::Type{T}, d) where {T}
+    (eltype(t.At) === T && size(t.At, 1) == d && (t.shift === nothing || (eltype(t.shift) === T && length(t.shift) == d))) ||
+        error("nfhip: target must hold $d-dimensional data rows in $T")
 end
 c_target(t::DiagGaussTarget) = NFTarget(NF_TARGET_DIAGGAUSS, devptr(t.μ), devptr(t.σ²), 0.0, 0.0)
 c_target(t::BananaTarget) = NFTarget(NF_TARGET_BANANA, C_NULL, C_NULL, t.b, t.var)

@@ -84,6 +84,22 @@ extern "C" {
 #define NF_TARGET_FUNNEL 2    /* Funnel(d, mu, sigma), example/targets/neal_funnel.jl:53-72 (s0 = mu, s1 = sigma) */
 #define NF_TARGET_WARPED 3    /* WarpedGauss(s1, s2), d = 2, example/targets/warped_gaussian.jl:51-87 (s0, s1) */
 #define NF_TARGET_CROSS 4     /* Cross(mu, sigma), d = 2, example/targets/cross.jl:30-37 (s0 = mu, s1 = sigma) */
+/* Linear-predictor targets: log p(y) = c + sum_i phi(u_i) + prior(y), u = A (y - mu), evaluated as two GEMMs per tile of
+ * samples on the matrix pipe (d <= 256, any number of rows).  All device pointers are in the flow's element type.
+ *   NF_TARGET_DENSEGAUSS  MvNormal(mu, Sigma), Sigma = L L'.  p0 = mu[d]; p1 = W[d x d] row-major, W = inv(L) (lower
+ *       triangular, stored dense with its zeros), so u = W (y - mu) ~ N(0, I); s0 = log|det W| = -sum(log(diag(L))); s1 unused.
+ *       log p = -d/2 log(2 pi) + s0 - |u|^2 / 2,  grad = -W' u.
+ *   NF_TARGET_LOGREG      posterior of logistic-regression weights y in R^d under the prior N(0, s1^2 I), data rows x_i and
+ *       labels t_i in {-1, +1}.  p0 = NULL (or a shift mu[d]); p1 = A[n x d] row-major with A_i = t_i x_i (the host folds the
+ *       labels into the rows); s0 = n (an integer value, 1 <= n < 2^31); s1 = prior sigma > 0.
+ *       log p = sum_i log sigmoid(u_i) - |y|^2 / (2 s1^2) - d/2 log(2 pi s1^2),  grad = A' sigmoid(-u) - y / s1^2,
+ *       with log sigmoid(u) evaluated as min(u, 0) - log1p(exp(-|u|)).
+ * Served by nf_target_logp and, as ELBO targets, by RealNVP / NSF flows (either element type), general bases and
+ * compositions.  Planar, radial, mean-field and Hamiltonian flows answer NF_ERR_UNSUPPORTED to every ELBO entry point with
+ * these kinds (their kernels evaluate the target one feature at a time); a Hamiltonian descriptor cannot use them as its
+ * score either.  nf_elbo_step runs the split sequence (value and gradient, then Adam) for them. */
+#define NF_TARGET_DENSEGAUSS 5
+#define NF_TARGET_LOGREG 6
 
 #define NF_MAX_HIDDEN 4
 
@@ -344,7 +360,8 @@ int nf_ctx_set_weight_cache(nf_ctx *ctx, int32_t enable);
  * and replay the graph.  Accepted: Float32 LDS-resident RealNVP flows (with or without a communicator) and, on a context
  * without a communicator, Float32 LDS-resident spline couplings and the planar, radial and mean-field flows nf_elbo_step
  * runs in three launches (Float32 or Float64) -- each with any of the five built-in targets (valid arguments: WarpedGauss
- * and Cross need d = 2).  NF_ERR_UNSUPPORTED for everything else. */
+ * and Cross need d = 2).  NF_ERR_UNSUPPORTED for everything else, the linear-predictor targets (NF_TARGET_DENSEGAUSS,
+ * NF_TARGET_LOGREG) on every flow included: theta and *step_device are left as they were. */
 int nf_elbo_step_enqueue(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, void *theta, void *m, void *v,
                          int64_t N, uint64_t seed, uint32_t *step_device, double lr, double beta1, double beta2,
                          double eps, void *out_loss_gnorm_device);

@@ -5,6 +5,7 @@
 #include <cstdlib>
 
 #include "nf_common.h"
+#include "nf_targets.h"
 
 // ---- kernels' host launchers (other translation units) ---------------------------------
 int nf_launch_base_sample(nf_ctx *, int, int, long, uint64_t, uint64_t, uint32_t, void *, void *);
@@ -640,7 +641,16 @@ static long coupling_slab_floats(nf_ctx *ctx, const nf_flow_desc *desc, long N) 
 static inline bool elbo_fusable(const nf_flow_desc *desc, const nf_target *target, const void *xs, bool sizing = false) {
   const bool resident = (desc->kind == NF_KIND_REALNVP && nf_affine_supported(desc) && nf_affine_fused_ok(desc)) ||
                         (desc->kind == NF_KIND_NSF && nf_rqs_supported(desc));
+  // the linear-predictor kinds have no epilogue in the chain kernels: the generic sequence and its target launch serve them
+  if (target && target_is_linpred(target->kind)) return false;
   return !xs && desc->dtype == NF_DTYPE_F32 && resident && (sizing || nf_target_check(target, desc->d) == NF_OK);
+}
+// Planar, radial and mean-field flows evaluate the target inside their forward / step kernels, one feature at a time, and a
+// Hamiltonian flow's joint density does too: with a linear-predictor target every ELBO entry point refuses them before any launch.
+static inline bool linpred_refused(const nf_flow_desc *desc, const nf_target *target) {
+  if (!target || !target_is_linpred(target->kind)) return false;
+  return desc->kind == NF_KIND_PLANAR || desc->kind == NF_KIND_RADIAL || desc->kind == NF_KIND_MEANFIELD ||
+         desc->kind == NF_KIND_HAMILTONIAN;
 }
 // the fused forward launch (draws + chain + target + ELBO partial sums) of the two LDS-resident coupling families
 static int fused_chain_elbo(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, long N, uint64_t seed,
@@ -1131,6 +1141,7 @@ extern "C" int nf_target_logp(nf_ctx *ctx, int32_t dtype, const nf_target *targe
                               void *logp_out, void *grad_out) {
   if (!ctx || !target || !y || d < 1 || N < 0) return NF_ERR_ARG;
   if (dtype != NF_DTYPE_F32 && dtype != NF_DTYPE_F64) return NF_ERR_ARG;
+  NF_TRY(nf_target_check(target, d));  // the target's own argument conventions, before any device work
   NF_HIP(hipSetDevice(ctx->device));
   return nf_launch_target(ctx, dtype, target, d, N, y, nullptr, nullptr, logp_out, grad_out, 1.0, nullptr, nullptr, 0.0, 0);
 }
@@ -1214,6 +1225,7 @@ extern "C" int nf_elbo_batch(nf_ctx *ctx, const nf_flow_desc *desc, const nf_tar
                              const void *xs, int64_t N, void *elbos_out, double *elbo_host) {
   if (!ctx || !target || !theta || !xs || !elbo_host || N < 1) return NF_ERR_ARG;
   NF_TRY(check_desc(desc));
+  if (linpred_refused(desc, target)) return NF_ERR_UNSUPPORTED;
   NF_HIP(hipSetDevice(ctx->device));
   if (flow_base(desc)) return elbo_forward_general_base(ctx, desc, target, theta, xs, N, 0, 0, 0, elbos_out, elbo_host);
   return elbo_forward(ctx, desc, target, theta, xs, N, 0, 0, 0, elbos_out, elbo_host);
@@ -1224,6 +1236,7 @@ extern "C" int nf_elbo_batch_rng(nf_ctx *ctx, const nf_flow_desc *desc, const nf
                                  double *elbo_host) {
   if (!ctx || !target || !theta || !elbo_host || N < 1) return NF_ERR_ARG;
   NF_TRY(check_desc(desc));
+  if (linpred_refused(desc, target)) return NF_ERR_UNSUPPORTED;
   NF_HIP(hipSetDevice(ctx->device));
   if (flow_base(desc))
     return elbo_forward_general_base(ctx, desc, target, theta, nullptr, N, seed, sample_offset, stream_id, nullptr, elbo_host);
@@ -1832,6 +1845,7 @@ extern "C" int nf_elbo_value_and_grad(nf_ctx *ctx, const nf_flow_desc *desc, con
                                       uint64_t seed, uint64_t sample_offset, uint32_t stream_id, void *out) {
   if (!ctx || !target || !theta || !out || N_local < 0 || N_global < 1) return NF_ERR_ARG;
   NF_TRY(check_desc(desc));
+  if (linpred_refused(desc, target)) return NF_ERR_UNSUPPORTED;
   NF_HIP(hipSetDevice(ctx->device));
   if (flow_base(desc))
     return value_and_grad_general_base(ctx, desc, target, theta, xs, N_local, N_global, seed, sample_offset, stream_id, out);
@@ -2193,6 +2207,7 @@ static bool step_fusable_simple(nf_ctx *ctx, const nf_flow_desc *desc, const nf_
   if (desc->kind != NF_KIND_PLANAR && desc->kind != NF_KIND_RADIAL && desc->kind != NF_KIND_MEANFIELD) return false;
   if (desc->dtype != NF_DTYPE_F32 && desc->dtype != NF_DTYPE_F64) return false;
   if (!nf_simple_step_supported(desc)) return false;
+  if (target && target_is_linpred(target->kind)) return false;
   return sizing || nf_target_check(target, desc->d) == NF_OK;
 }
 // the step launch's loss partials, its gradient slabs (one per workgroup and layer), the epilogue's block partials of ||g||^2
@@ -2333,6 +2348,7 @@ static int step_split(nf_ctx *ctx, const nf_flow_desc *desc, const StepCall &c) 
 // grouped by workgroup; it agrees to float rounding.
 static int step_run(nf_ctx *ctx, const nf_flow_desc *desc, const StepCall &c, double *loss_host, double *gnorm_host, void *out_device) {
   NF_TRY(check_desc(desc));
+  if (linpred_refused(desc, c.target)) return NF_ERR_UNSUPPORTED;
   NF_HIP(hipSetDevice(ctx->device));
   if (c.Ng < 1) return NF_ERR_ARG;
   const long P = nf_param_count(desc), N = c.N;

@@ -654,17 +654,31 @@ int nf_target_check(const nf_target *t, int d) {
     case NF_TARGET_FUNNEL: return (d >= 2 && t->s1 > 0) ? NF_OK : NF_ERR_ARG;       // neal_funnel.jl:31-35
     case NF_TARGET_WARPED: return (d == 2 && t->s0 > 0 && t->s1 > 0) ? NF_OK : NF_ERR_ARG;  // warped_gaussian.jl:29-33,79
     case NF_TARGET_CROSS: return (d == 2 && t->s1 > 0) ? NF_OK : NF_ERR_ARG;
+    case NF_TARGET_DENSEGAUSS: return (t->p0 && t->p1) ? NF_OK : NF_ERR_ARG;
+    case NF_TARGET_LOGREG:  // s0 = the number of data rows, an integer value that fits an int
+      return (t->p1 && t->s1 > 0 && t->s0 >= 1 && t->s0 < 2147483648.0 && t->s0 == (double)(long)t->s0) ? NF_OK : NF_ERR_ARG;
     default: return NF_ERR_ARG;
   }
 }
 
 long nf_target_nblocks(long N) { return nblk(N, SPB); }
 
+// nf_linpred.hip: the linear-predictor kinds, same outputs and partial counts as k_target / k_target_tiled
+int nf_launch_target_linpred(nf_ctx *, int dtype, const nf_target *, int d, long N, const void *y, const void *logq,
+                             const void *ladj, void *logp_out, void *grad_out, double gscale, void *elbos_out, double *partial,
+                             double pscale);
+int nf_launch_target_linpred_tiled(nf_ctx *, const nf_target *, int d, long N, const float *yt, const float *logq,
+                                   const float *ladj, float *gt, double gscale, float *elbos_out, double *partial, double pscale);
+
 int nf_launch_target(nf_ctx *ctx, int dtype, const nf_target *t, int d, long N, const void *y, const void *logq,
                      const void *ladj, void *logp_out, void *grad_out, double gscale, void *elbos_out, double *partial,
                      double pscale, int joint_d) {
   if (N <= 0) return NF_OK;
   NF_TRY(nf_target_check(t, joint_d > 0 ? joint_d : d));
+  if (target_is_linpred(t->kind)) {
+    if (joint_d > 0) return NF_ERR_UNSUPPORTED;  // (the ELBO entry points refuse Hamiltonian flows with these kinds first)
+    return nf_launch_target_linpred(ctx, dtype, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
+  }
   ProfScope ps(ctx, "target");
   if (dtype == NF_DTYPE_F32)
     hipLaunchKernelGGL(k_target<float>, dim3(nblk(N, SPB)), dim3(EW_BLOCK), 0, ctx->stream, t->kind, d, N,
@@ -781,6 +795,8 @@ int nf_launch_target_tiled(nf_ctx *ctx, const nf_target *t, int d, long N, const
                            double pscale) {
   if (N <= 0) return NF_OK;
   NF_TRY(nf_target_check(t, d));
+  if (target_is_linpred(t->kind))
+    return nf_launch_target_linpred_tiled(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
   ProfScope ps(ctx, "target");
   hipLaunchKernelGGL(k_target_tiled, dim3((unsigned)nf_target_tiled_nblocks(N)), dim3(EW_BLOCK), 0, ctx->stream,
                      t->kind, d, N, yt, (const float *)t->p0, (const float *)t->p1, (float)t->s0, (float)t->s1, logq,

@@ -1,0 +1,384 @@
+// nf_linpred.hip -- the linear-predictor targets (NF_TARGET_DENSEGAUSS, NF_TARGET_LOGREG; gfx950):
+//     log p(y) = c + sum_i phi(u_i) - pw |y|^2 / 2,   u = A (y - mu),   grad = A' phi'(u) - pw y
+// with A [rows x d] row-major: MvNormal(mu, Sigma) through W = inv(chol(Sigma)), Bayesian logistic regression through the
+// label-folded data matrix.  Two kernels, each templated on the row function phi (nf_linpred.h):
+//   k_target_linpred_tiled  Float32, tiled layout, drop-in for k_target_tiled: both GEMMs on v_mfma_f32_32x32x2_f32
+//   k_target_linpred        flat layout, float / double, drop-in for k_target: vector pipe (Float64 flows, nf_target_logp)
+#include "nf_common.h"
+#include "nf_linpred.h"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// tiled kernel
+// ---------------------------------------------------------------------------------------------------------------------
+// One workgroup of four waves per 32-sample tile (one double partial per tile, as k_target_tiled leaves).  The centred
+// tile Y - mu sits in LDS once, [feature][sample], features >= d and padding samples zero.  Each wave takes the row blocks
+// rb = wave, wave + 4, ... of A (32 rows each) and stages its block into an LDS image of its own (no workgroup barrier
+// inside the row loop):
+//   GEMM 1   U[i][j] = sum_f A[i][f] Y[f][j]      A operand: lane <-> row i, B operand: lane <-> sample j, k-step t
+//                                                 contracts features 2 t + hi
+//   phi      in the accumulator registers: register r of a lane of half `hi` is row nf_row(r, hi) of sample l & 31
+//   GEMM 2   G[f][j] += sum_i A[i][f] phi'(U)[i][j]   k-step t contracts the row pair nf_row(t, 0) / nf_row(t, 1): its B
+//                                                 operand IS accumulator register t of GEMM 1 (the register chaining of
+//                                                 nf_mfma.h), so U never passes through LDS or a shuffle
+// Rows >= rows of the last block are masked after phi: a zero row of A gives u = 0, and phi(0) = log 1/2 for LOGREG.
+// Feature chunks: the image holds at most 128 features of the 32 rows (16.5 KB per wave); a wider target (DB = 8) runs
+// GEMM 1 chunk by chunk and stages each chunk a second time for GEMM 2.
+#define LP_BLOCK 256
+#define LP_WAVES 4
+
+template <int DB>
+struct LpGeo {
+  static constexpr int CB = DB < 4 ? DB : 4;  // 32-feature blocks per staged chunk
+  static constexpr int NCH = DB / CB;         // chunks
+  static constexpr int CW = 32 * CB;          // features per chunk
+  static constexpr int S = CW + 1;            // row stride of the image: odd, so that GEMM 1 (lanes along rows) and GEMM 2 (lanes
+                                              // along features) both read it without bank conflicts
+  static constexpr int IMG = 32 * S;          // floats per wave
+  static constexpr int YT = 32 * DB * 32;     // the centred tile; reused for the reduction of G over the four waves
+  static constexpr int FLOATS = YT + LP_WAVES * IMG + LP_WAVES * 64;
+};
+
+// rows [i0, i0 + 32) x features [f0, f0 + CW) of A -> the wave's image, zero beyond the matrix
+template <int DB>
+__device__ __forceinline__ void lp_stage(float *__restrict__ img, const float *__restrict__ A, int i0, int f0, int rows, int d,
+                                         int lane) {
+  using G = LpGeo<DB>;
+  const int l31 = lane & 31, hi = lane >> 5;
+  // whole 32-feature blocks that hold a real feature; a half-wave copies 32 consecutive features of one row (128 bytes)
+  for (int cb = 0; cb < G::CB && f0 + cb * 32 < d; ++cb) {
+    const int col = cb * 32 + l31, f = f0 + col;
+    float v[16];
+#pragma unroll
+    for (int rp = 0; rp < 16; ++rp) {
+      const int i = i0 + 2 * rp + hi;
+      v[rp] = (i < rows && f < d) ? A[(long)i * d + f] : 0.f;
+    }
+#pragma unroll
+    for (int rp = 0; rp < 16; ++rp) img[(2 * rp + hi) * G::S + col] = v[rp];
+  }
+}
+
+template <int DB, class PHI>
+__global__ __launch_bounds__(LP_BLOCK) void k_target_linpred_tiled(int d, int rows, long N, const float *__restrict__ yt,
+                                                                   const float *__restrict__ mu, const float *__restrict__ A,
+                                                                   float c0, float pw, const float *__restrict__ logq,
+                                                                   const float *__restrict__ ladj, float *__restrict__ gt,
+                                                                   float gscale, float *__restrict__ elbos_out,
+                                                                   double *__restrict__ partial, double pscale) {
+  using G = LpGeo<DB>;
+  extern __shared__ float lp_sm[];
+  float *sY = lp_sm;
+  float *sA = lp_sm + G::YT;
+  float *sL = sA + LP_WAVES * G::IMG;  // [wave][lane] log-p partial sums
+  __shared__ float red[LP_BLOCK / 32][32];
+  __shared__ double sm[LP_WAVES];
+  const long tile = blockIdx.x;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l31 = lane & 31, hi = lane >> 5;
+  const float *yb = yt + tile * d * 32;
+
+  {  // every load of the tile is issued before the first LDS store: one memory latency, not one per element
+    constexpr int PER = G::YT / LP_BLOCK;
+    float yv[PER];
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+      const int idx = threadIdx.x + k * LP_BLOCK, f = idx >> 5, s = idx & 31;
+      yv[k] = (f < d && tile * 32 + s < N) ? yb[idx] - (mu ? mu[f] : 0.f) : 0.f;
+    }
+#pragma unroll
+    for (int k = 0; k < PER; ++k) sY[threadIdx.x + k * LP_BLOCK] = yv[k];
+  }
+  __syncthreads();
+
+  float *img = sA + wave * G::IMG;
+  f32x16 Gacc[DB];
+#pragma unroll
+  for (int b = 0; b < DB; ++b)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) Gacc[b][r] = 0.f;
+  float lp = 0.f;
+  const int nrb = (rows + 31) >> 5;
+  for (int rb = wave; rb < nrb; rb += LP_WAVES) {
+    const int i0 = rb * 32;
+    f32x16 U;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) U[r] = 0.f;
+#pragma unroll
+    for (int ch = 0; ch < G::NCH; ++ch) {
+      const int f0 = ch * G::CW;
+      if (f0 < d) {  // (wave-uniform)
+        lp_stage<DB>(img, A, i0, f0, rows, d, lane);
+        wave_lds_fence();
+        const int nf = d - f0 < G::CW ? d - f0 : G::CW;
+        const int ng = (nf + 7) >> 3;  // groups of four k-steps = eight features; features >= d are zero on both sides
+        const float *pa = img + l31 * G::S + hi;
+        const float *pb = sY + (f0 + hi) * 32 + l31;
+        for (int g = 0; g < ng; ++g) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            U = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[8 * g + 2 * e], pb[(8 * g + 2 * e) * 32], U, 0, 0, 0);
+        }
+        if (G::NCH > 1) wave_lds_fence();  // the image is restaged
+      }
+    }
+    const bool ragged = i0 + 32 > rows;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      float ph, dp;
+      PHI::eval(U[r], ph, dp);
+      if (ragged && i0 + nf_row(r, hi) >= rows) ph = 0.f, dp = 0.f;
+      lp += ph;
+      U[r] = dp;
+    }
+#pragma unroll
+    for (int ch = 0; ch < G::NCH; ++ch) {
+      const int f0 = ch * G::CW;
+      if (f0 < d) {
+        if (G::NCH > 1) {
+          lp_stage<DB>(img, A, i0, f0, rows, d, lane);
+          wave_lds_fence();
+        }
+#pragma unroll
+        for (int cb = 0; cb < G::CB; ++cb) {
+          if (f0 + cb * 32 < d) {
+            const float *pa = img + (4 * hi) * G::S + cb * 32 + l31;
+#pragma unroll
+            for (int t = 0; t < 16; ++t)
+              Gacc[ch * G::CB + cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[((t & 3) + 8 * (t >> 2)) * G::S], U[t], Gacc[ch * G::CB + cb], 0, 0, 0);
+          }
+        }
+        wave_lds_fence();  // the next staging overwrites the image
+      }
+    }
+  }
+
+  // the four waves' G and log-p sums, combined in wave order
+  sL[wave * 64 + lane] = lp;
+  for (int w = 0; w < LP_WAVES; ++w) {
+    __syncthreads();  // (first pass: every wave is done reading the tile)
+    if (wave == w) {
+#pragma unroll
+      for (int b = 0; b < DB; ++b)
+        if (b * 32 < d) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            float *p = sY + (b * 32 + nf_row(r, hi)) * 32 + l31;
+            *p = w == 0 ? Gacc[b][r] : *p + Gacc[b][r];
+          }
+        }
+    }
+  }
+  __syncthreads();
+
+  // epilogue in k_target_tiled's thread layout: thread (q, s) owns features q, q + 8, ... of sample s
+  const int s = threadIdx.x & 31, q = threadIdx.x >> 5;
+  const long j = tile * 32 + s;
+  const bool valid = j < N;
+  float yy = 0.f;
+  {
+    constexpr int PER = 4 * DB;  // features per thread: q, q + 8, ...
+    float yv[PER];
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+      const int i = q + k * (LP_BLOCK / 32);
+      yv[k] = (valid && i < d) ? yb[i * 32 + s] : 0.f;
+    }
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+      const int i = q + k * (LP_BLOCK / 32);
+      yy += yv[k] * yv[k];
+      if (gt && i < d) gt[tile * d * 32 + i * 32 + s] = valid ? gscale * (sY[i * 32 + s] - pw * yv[k]) : 0.f;
+    }
+  }
+  red[q][s] = yy;
+  __syncthreads();
+  double contrib = 0.0;
+  if (q == 0 && valid) {
+    float t = 0.f, l = 0.f;
+#pragma unroll
+    for (int k = 0; k < LP_BLOCK / 32; ++k) t += red[k][s];
+#pragma unroll
+    for (int w = 0; w < LP_WAVES; ++w) l += sL[w * 64 + s] + sL[w * 64 + 32 + s];
+    float e = c0 + l - 0.5f * pw * t;
+    if (logq) e -= logq[j];
+    if (ladj) e += ladj[j];
+    if (elbos_out) elbos_out[j] = e;
+    contrib = pscale * (double)e;
+  }
+  if (partial) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) contrib += __shfl_xor(contrib, o, 64);
+    if (lane == 0) sm[wave] = contrib;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// flat kernel (vector pipe)
+// ---------------------------------------------------------------------------------------------------------------------
+// k_target's thread layout: 16 lanes per sample, 16 samples per block, one partial per block.  A passes through LDS in
+// blocks of 16 rows: lane q of a sample takes row q (u, phi, phi'), phi' goes through LDS, and lane q then owns the
+// features q, q + 16, ... of the gradient.
+#define LPF_LANES 16
+#define LPF_SPB (LP_BLOCK / LPF_LANES)
+#define LPF_RB 16
+#define LPF_MAXD 256
+
+template <class T>
+__device__ __forceinline__ T lp_group16_sum(T v) {
+  v += __shfl_xor(v, 8, 16);
+  v += __shfl_xor(v, 4, 16);
+  v += __shfl_xor(v, 2, 16);
+  v += __shfl_xor(v, 1, 16);
+  return v;
+}
+
+template <class T, class PHI>
+__global__ __launch_bounds__(LP_BLOCK) void k_target_linpred(int d, int rows, long N, const T *__restrict__ y,
+                                                             const T *__restrict__ mu, const T *__restrict__ A, T c0, T pw,
+                                                             const T *__restrict__ logq, const T *__restrict__ ladj,
+                                                             T *__restrict__ logp_out, T *__restrict__ grad_out, T gscale,
+                                                             T *__restrict__ elbos_out, double *__restrict__ partial,
+                                                             double pscale) {
+  extern __shared__ double lpf_sm[];
+  T *sY = (T *)lpf_sm;                  // [sample][d + 1] centred
+  T *sA = sY + LPF_SPB * (d + 1);       // [row][d + 1]
+  T *sD = sA + LPF_RB * (d + 1);        // [sample][17] phi'
+  __shared__ double sm[LP_BLOCK / 64];
+  const int q = threadIdx.x & (LPF_LANES - 1), sl = threadIdx.x / LPF_LANES;
+  const long j = (long)blockIdx.x * LPF_SPB + sl;
+  const bool valid = j < N;
+  const int S = d + 1;
+  for (int idx = threadIdx.x; idx < LPF_SPB * d; idx += LP_BLOCK) {
+    const int si = idx / d, f = idx - si * d;
+    const long jj = (long)blockIdx.x * LPF_SPB + si;
+    sY[si * S + f] = jj < N ? y[jj * d + f] - (mu ? mu[f] : (T)0) : (T)0;
+  }
+  T g[LPF_MAXD / LPF_LANES];
+#pragma unroll
+  for (int k = 0; k < LPF_MAXD / LPF_LANES; ++k) g[k] = (T)0;
+  T lp = 0;
+  for (int i0 = 0; i0 < rows; i0 += LPF_RB) {
+    __syncthreads();  // the tile (first pass); the previous block's readers
+    for (int idx = threadIdx.x; idx < LPF_RB * d; idx += LP_BLOCK) {
+      const int row = idx / d, f = idx - row * d;
+      sA[row * S + f] = i0 + row < rows ? A[(long)(i0 + row) * d + f] : (T)0;
+    }
+    __syncthreads();
+    T u = 0;
+    for (int f = 0; f < d; ++f) u += sA[q * S + f] * sY[sl * S + f];
+    T ph, dp;
+    PHI::eval(u, ph, dp);
+    if (i0 + q >= rows) ph = (T)0, dp = (T)0;
+    lp += ph;
+    sD[sl * (LPF_RB + 1) + q] = dp;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < LPF_MAXD / LPF_LANES; ++k) {
+      const int f = k * LPF_LANES + q;
+      if (f < d) {
+        T a = g[k];
+#pragma unroll
+        for (int r = 0; r < LPF_RB; ++r) a += sA[r * S + f] * sD[sl * (LPF_RB + 1) + r];
+        g[k] = a;
+      }
+    }
+  }
+  T yy = 0;
+#pragma unroll
+  for (int k = 0; k < LPF_MAXD / LPF_LANES; ++k) {
+    const int f = k * LPF_LANES + q;
+    if (f < d && valid) {
+      const T yv = y[j * d + f];
+      yy += yv * yv;
+      if (grad_out) grad_out[j * d + f] = gscale * (g[k] - pw * yv);
+    }
+  }
+  lp = lp_group16_sum(lp);
+  yy = lp_group16_sum(yy);
+  double contrib = 0.0;
+  if (valid && q == 0) {
+    T e = c0 + lp - (T)0.5 * pw * yy;
+    if (logp_out) logp_out[j] = e;
+    if (logq) e -= logq[j];
+    if (ladj) e += ladj[j];
+    if (elbos_out) elbos_out[j] = e;
+    contrib = pscale * (double)e;
+  }
+  if (partial) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) contrib += __shfl_xor(contrib, o, 64);
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = contrib;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// launchers (called by nf_launch_target / nf_launch_target_tiled after nf_target_check)
+// ---------------------------------------------------------------------------------------------------------------------
+template <int DB, class PHI>
+static int launch_tiled(nf_ctx *ctx, const nf_target *t, int d, long N, const float *yt, const float *logq, const float *ladj,
+                        float *gt, double gscale, float *elbos_out, double *partial, double pscale) {
+  const size_t lds = (size_t)LpGeo<DB>::FLOATS * sizeof(float);
+  static AttrOnce attr_once;  // once per device
+  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
+    NF_HIP(hipFuncSetAttribute((const void *)k_target_linpred_tiled<DB, PHI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return NF_OK;
+  }));
+  const LinpredConsts k = linpred_consts(t, d);
+  ProfScope ps(ctx, "target_linpred");
+  hipLaunchKernelGGL((k_target_linpred_tiled<DB, PHI>), dim3((unsigned)((N + 31) / 32)), dim3(LP_BLOCK), lds, ctx->stream, d,
+                     (int)k.rows, N, yt, (const float *)t->p0, (const float *)t->p1, (float)k.c, (float)k.pw, logq, ladj, gt,
+                     (float)gscale, elbos_out, partial, pscale);
+  return (int)hipGetLastError();
+}
+
+template <class PHI>
+static int launch_tiled_phi(nf_ctx *ctx, const nf_target *t, int d, long N, const float *yt, const float *logq,
+                            const float *ladj, float *gt, double gscale, float *elbos_out, double *partial, double pscale) {
+  if (d <= 32) return launch_tiled<1, PHI>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
+  if (d <= 64) return launch_tiled<2, PHI>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
+  if (d <= 128) return launch_tiled<4, PHI>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
+  return launch_tiled<8, PHI>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
+}
+
+int nf_launch_target_linpred_tiled(nf_ctx *ctx, const nf_target *t, int d, long N, const float *yt, const float *logq,
+                                   const float *ladj, float *gt, double gscale, float *elbos_out, double *partial,
+                                   double pscale) {
+  if (d > LPF_MAXD) return NF_ERR_UNSUPPORTED;
+  if (t->kind == NF_TARGET_DENSEGAUSS)
+    return launch_tiled_phi<PhiHalfSquare>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
+  return launch_tiled_phi<PhiLogSigmoid>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
+}
+
+template <class T, class PHI>
+static int launch_flat(nf_ctx *ctx, const nf_target *t, int d, long N, const void *y, const void *logq, const void *ladj,
+                       void *logp_out, void *grad_out, double gscale, void *elbos_out, double *partial, double pscale) {
+  const size_t lds = (size_t)((LPF_SPB + LPF_RB) * (d + 1) + LPF_SPB * (LPF_RB + 1)) * sizeof(T);
+  static AttrOnce attr_once;
+  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
+    const size_t most = (size_t)((LPF_SPB + LPF_RB) * (LPF_MAXD + 1) + LPF_SPB * (LPF_RB + 1)) * sizeof(T);
+    NF_HIP(hipFuncSetAttribute((const void *)k_target_linpred<T, PHI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)most));
+    return NF_OK;
+  }));
+  const LinpredConsts k = linpred_consts(t, d);
+  ProfScope ps(ctx, "target_linpred");
+  const long nb = (N + LPF_SPB - 1) / LPF_SPB;
+  hipLaunchKernelGGL((k_target_linpred<T, PHI>), dim3((unsigned)nb), dim3(LP_BLOCK), lds, ctx->stream, d, (int)k.rows, N,
+                     (const T *)y, (const T *)t->p0, (const T *)t->p1, (T)k.c, (T)k.pw, (const T *)logq, (const T *)ladj,
+                     (T *)logp_out, (T *)grad_out, (T)gscale, (T *)elbos_out, partial, pscale);
+  return (int)hipGetLastError();
+}
+
+int nf_launch_target_linpred(nf_ctx *ctx, int dtype, const nf_target *t, int d, long N, const void *y, const void *logq,
+                             const void *ladj, void *logp_out, void *grad_out, double gscale, void *elbos_out,
+                             double *partial, double pscale) {
+  if (d > LPF_MAXD) return NF_ERR_UNSUPPORTED;
+  const bool gauss = t->kind == NF_TARGET_DENSEGAUSS;
+  if (dtype == NF_DTYPE_F32)
+    return gauss ? launch_flat<float, PhiHalfSquare>(ctx, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale)
+                 : launch_flat<float, PhiLogSigmoid>(ctx, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
+  return gauss ? launch_flat<double, PhiHalfSquare>(ctx, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale)
+               : launch_flat<double, PhiLogSigmoid>(ctx, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
+}

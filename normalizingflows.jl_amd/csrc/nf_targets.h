@@ -77,3 +77,7 @@ __device__ __forceinline__ T target_term(int d, int i, T v, T y0, T y1, T s2, co
   return log((T)0.25) + m + log(sw);
 }
 __host__ __device__ inline bool target_needs_d2(int kind) { return kind == NF_TARGET_WARPED || kind == NF_TARGET_CROSS; }
+// The linear-predictor kinds (NF_TARGET_DENSEGAUSS, NF_TARGET_LOGREG) couple every feature with every other through a
+// matrix: target_term cannot express them.  They have kernels of their own (nf_linpred.hip), reached through
+// nf_launch_target / nf_launch_target_tiled; every path that evaluates target_term inside a fused kernel refuses them.
+__host__ __device__ inline bool target_is_linpred(int kind) { return kind == NF_TARGET_DENSEGAUSS || kind == NF_TARGET_LOGREG; }

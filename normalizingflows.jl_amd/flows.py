@@ -553,10 +553,105 @@ class CrossTarget:
         return target_logp(self, ys)
 
 
+class _LinpredLogp(torch.autograd.Function):
+    """logp(ys) of a linear-predictor target as a torch-autograd node whose backward is the DEVICE score
+    (nf_target_logp with the gradient): what the closure branch of value_and_gradient differentiates."""
+
+    @staticmethod
+    def forward(ctx, target, ys):
+        lp, grad = target_logp(target, ys.detach(), with_grad=True)
+        ctx.save_for_backward(grad)
+        ctx.vec = ys.dim() == 1
+        return lp
+
+    @staticmethod
+    def backward(ctx, lbar):
+        (grad,) = ctx.saved_tensors
+        g = grad[:, 0] * lbar if ctx.vec else grad * lbar.unsqueeze(0)
+        return None, g
+
+
+class _LinpredTarget:
+    """What MvNormalTarget and LogisticRegressionTarget share: the matrix `A` [rows, d] and the optional shift `mu`,
+    kept alive for the descriptor's device pointers, and the checks DiagGaussTarget makes (the ABI reads p0 / p1 untyped)."""
+
+    def check_compatible(self, dtype, device, d=None):
+        if self.A.dtype != dtype:
+            raise NFHipError(f"target parameters are {self.A.dtype} but the flow computes in {dtype}: "
+                             "build the target in the flow's element type")
+        dv = torch.device(device)
+        if self.A.device.type != dv.type or (dv.index is not None and self.A.device.index is not None and dv.index != self.A.device.index):
+            raise NFHipError(f"target parameters live on {self.A.device}, the flow on {device}")
+        if d is not None and self.d != d:
+            raise NFHipError(f"target has dimension {self.d}, expected {d}")
+
+    def __call__(self, ys):
+        if ys.requires_grad:
+            return _LinpredLogp.apply(self, ys)
+        return target_logp(self, ys)
+
+
+class MvNormalTarget(_LinpredTarget):
+    """logp(z) = logpdf(MvNormal(mu, Sigma), z) with a full covariance (the correlated form of test/flow.jl:43-46).
+    Sigma = L L' is factored on the host in float64; the device reads W = inv(L), u = W (z - mu) ~ N(0, I)."""
+
+    def __init__(self, mu: torch.Tensor, Sigma: torch.Tensor):
+        if mu.dim() != 1 or Sigma.dim() != 2 or Sigma.shape != (mu.numel(), mu.numel()):
+            raise NFHipError("MvNormalTarget: mu (d,), Sigma (d, d)")
+        if mu.dtype != Sigma.dtype or mu.device != Sigma.device or mu.dtype not in (torch.float32, torch.float64):
+            raise NFHipError("MvNormalTarget: mu and Sigma must share one element type (Float32 or Float64) and one device")
+        S64 = Sigma.detach().to("cpu", torch.float64)
+        if not bool(torch.isfinite(S64).all()) or not torch.allclose(S64, S64.T, rtol=1e-6, atol=1e-12 * float(S64.abs().max() + 1)):
+            raise NFHipError("MvNormalTarget: Sigma is not symmetric")
+        L, info = torch.linalg.cholesky_ex(S64)
+        if int(info) != 0:
+            raise NFHipError("MvNormalTarget: Sigma is not positive definite")
+        d = mu.numel()
+        W64 = torch.linalg.solve_triangular(L, torch.eye(d, dtype=torch.float64), upper=False)
+        self.d = d
+        self.mu = mu.detach().contiguous()
+        self.A = torch.tril(W64).to(mu.dtype).to(mu.device).contiguous()
+        self.W = self.A
+        self.logdet_w = float(-torch.log(torch.diagonal(L)).sum())
+        self.c = Target(_lib.NF_TARGET_DENSEGAUSS, self.mu.data_ptr(), self.A.data_ptr(), self.logdet_w, 0.0)
+
+
+class LogisticRegressionTarget(_LinpredTarget):
+    """Posterior of Bayesian logistic regression over the weights z in R^d: data rows X [n, d], labels t in {-1, +1} (or
+    {0, 1}, mapped to them), prior N(0, prior_sigma^2 I):
+        logp(z) = sum_i log sigmoid(t_i x_i . (z - shift)) - |z|^2 / (2 prior_sigma^2) - d/2 log(2 pi prior_sigma^2).
+    The labels are folded into the rows on the host (A_i = t_i x_i)."""
+
+    def __init__(self, X: torch.Tensor, t: torch.Tensor, prior_sigma: float = 1.0, shift: torch.Tensor = None):
+        if X.dim() != 2 or X.shape[0] < 1 or X.shape[1] < 1 or X.dtype not in (torch.float32, torch.float64):
+            raise NFHipError("LogisticRegressionTarget: X must be a Float32 or Float64 matrix [n, d] with n >= 1")
+        n, d = X.shape
+        if t.dim() != 1 or t.numel() != n:
+            raise NFHipError("LogisticRegressionTarget: one label per row of X")
+        if not prior_sigma > 0:
+            raise NFHipError("LogisticRegressionTarget: prior_sigma must be > 0")
+        tv = t.detach().to("cpu", torch.float64)
+        if bool(((tv == 1) | (tv == -1)).all()):
+            sign = tv
+        elif bool(((tv == 0) | (tv == 1)).all()):
+            sign = 2.0 * tv - 1.0
+        else:
+            raise NFHipError("LogisticRegressionTarget: labels must all be in {-1, +1} or all in {0, 1}")
+        if shift is not None and (shift.dim() != 1 or shift.numel() != d or shift.dtype != X.dtype or shift.device != X.device):
+            raise NFHipError("LogisticRegressionTarget: shift must be a vector (d,) of X's element type and device")
+        self.d, self.n, self.prior_sigma = d, n, float(prior_sigma)
+        self.A = (X.detach() * sign.to(X.dtype).to(X.device).unsqueeze(1)).contiguous()
+        self.mu = shift.detach().contiguous() if shift is not None else None
+        self.c = Target(_lib.NF_TARGET_LOGREG, self.mu.data_ptr() if self.mu is not None else 0, self.A.data_ptr(), float(n),
+                        self.prior_sigma)
+
+
 def check_target(target, dtype, device=None, d=None):
     """Element-type / device / dimension agreement between a built-in target and the flow that will read it."""
     if isinstance(target, DiagGaussTarget):
         target.check_compatible(dtype, device if device is not None else target.mu.device, d)
+    elif isinstance(target, _LinpredTarget):
+        target.check_compatible(dtype, device if device is not None else target.A.device, d)
 
 
 def target_logp(target, ys: torch.Tensor, with_grad: bool = False):

@@ -12,10 +12,14 @@ from typing import Callable, Optional
 import torch
 
 from ._lib import NFHipError, check
-from .flows import (BananaTarget, CrossTarget, DiagGaussTarget, FunnelTarget, WarpedGaussTarget, Flow, PhiloxRNG, _dtype_code, _ptr, as_batch, base_logpdf,
+from .flows import (BananaTarget, CrossTarget, DiagGaussTarget, FunnelTarget, LogisticRegressionTarget, MvNormalTarget, WarpedGaussTarget, Flow, PhiloxRNG, _dtype_code, _ptr, as_batch, base_logpdf,
                     check_target, device_specific_rand, new_batch, rrule_with_logabsdet_jacobian, with_logabsdet_jacobian)
 
-_BUILTIN = (DiagGaussTarget, BananaTarget, FunnelTarget, WarpedGaussTarget, CrossTarget)
+_BUILTIN = (DiagGaussTarget, BananaTarget, FunnelTarget, WarpedGaussTarget, CrossTarget, MvNormalTarget, LogisticRegressionTarget)
+# linear-predictor targets: the library serves them for coupling flows (and general bases / compositions) only; planar, radial,
+# mean-field and Hamiltonian flows evaluate the target inside their own kernels and answer NF_ERR_UNSUPPORTED
+_LINPRED = (MvNormalTarget, LogisticRegressionTarget)
+_NO_LINPRED_KINDS = ("planar", "radial", "meanfield", "hamiltonian")
 
 
 def _target_dim(flow: Flow) -> int:
@@ -28,6 +32,8 @@ def _builtin(flow: Flow, logp) -> bool:
     if not isinstance(logp, _BUILTIN):
         return False
     check_target(logp, flow.theta.dtype, flow.theta.device, _target_dim(flow))
+    if isinstance(logp, _LINPRED) and flow.kind in _NO_LINPRED_KINDS:
+        return False  # the closure route: the target's own autograd node supplies the device score
     return True
 
 
@@ -148,7 +154,9 @@ def loglikelihood_step(flow: Flow, xs: torch.Tensor, opt: "Adam", st: "AdamState
 def value_and_gradient(vo, flow: Flow, logp, xs_or_n, rng: Optional[PhiloxRNG] = None, n_global: Optional[int] = None):
     """(loss, grad) of loss(theta) = -vo(rng, re(theta), logp, ...) (src/NormalizingFlows.jl:69).
 
-    Built-in targets run the whole step inside the library (nf_elbo_value_and_grad).  An
+    Built-in targets run the whole step inside the library (nf_elbo_value_and_grad) -- except MvNormalTarget /
+    LogisticRegressionTarget on planar, radial, mean-field and Hamiltonian flows, which the library refuses: those take
+    the branch below, where the target's autograd node hands back the device score.  An
     arbitrary `logp` callable takes the split path: library forward that keeps its tape
     (nf_flow_fwd_keep), the callable's own torch-autograd gradient w.r.t. ys, library pullback
     from that tape (nf_flow_bwd_kept) -- the same reverse kernels as the built-in step.

@@ -1,0 +1,148 @@
+"""Reverse-KL training on the linear-predictor targets (MvNormalTarget with a full covariance, LogisticRegressionTarget): per case
+one JSON line with
+  linpred_ms        -- ms per "target_linpred" launch (HIP events around the launch, nf_prof_read) inside nf_elbo_step,
+  linpred_roofline  -- its fraction of the fp32-MFMA roofline: 4 r d N flop (two GEMMs) over 157.3 TFLOP/s,
+  step_ms           -- ms per nf_elbo_step with the built-in target (asynchronous: no host read),
+  closure_ms        -- ms per iteration of the CLOSURE route on the same box and in the same process: value_and_gradient with an
+                       ordinary torch `logp` doing the same matmul (library forward that keeps its tape, torch autograd for the
+                       score, library pullback) plus adam_update -- the only way to train on such a target without the kinds.
+The two timed loops are interleaved (step, closure, step, closure, ...) after a clock ramp of --ramp seconds; every figure is the
+median of --runs loops, with the spread (max - min) next to it.
+Cases: (a) the cfg-2 flow (RealNVP d = 64, hidden [64, 64], 8 couplings, 65 536 samples) on a dense Gaussian, (b) the same flow on
+logistic regression with 1 024 data rows, (c) the cfg-3 flow (NSF d = 32, K = 8, 131 072 samples) on a dense Gaussian.
+usage: python tools/bench_linpred_targets.py [--runs 5] [--case a,b,c]"""
+import argparse
+import ctypes as C
+import json
+import math
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from __graft_entry__ import load_package  # noqa: E402
+
+LR, B1, B2, EPS = 1e-3, 0.9, 0.999, 1e-8
+MFMA_F32_TFLOPS = 157.3
+
+
+def timed(fn, seconds=0.25, min_iters=5):
+    """ms per call over a loop sized to last about `seconds`"""
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    iters = max(min_iters, min(2000, int(seconds / max(time.perf_counter() - t0, 1e-6))))
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3 / iters
+
+
+def dense_gauss(nf, d, gen):
+    Q, _ = torch.linalg.qr(torch.randn(d, d, generator=gen, dtype=torch.float64))
+    lam = 0.5 + 1.5 * torch.rand(d, generator=gen, dtype=torch.float64)
+    Sigma = (Q * lam) @ Q.T
+    Sigma = 0.5 * (Sigma + Sigma.T)
+    mu = 0.5 * torch.randn(d, generator=gen, dtype=torch.float64)
+    tgt = nf.MvNormalTarget(mu.float().cuda(), Sigma.float().cuda())
+    W, m, c = tgt.W, tgt.mu, -0.5 * d * math.log(2 * math.pi) + tgt.logdet_w
+
+    def logp(ys):  # (d, N) -> (N,)
+        u = W @ (ys - m[:, None])
+        return c - 0.5 * (u * u).sum(0)
+
+    return tgt, logp, d
+
+
+def logreg(nf, d, rows, gen, sigma=2.0):
+    X = torch.randn(rows, d, generator=gen, dtype=torch.float64) / math.sqrt(d)
+    t = torch.randint(0, 2, (rows,), generator=gen)
+    tgt = nf.LogisticRegressionTarget(X.float().cuda(), t.cuda(), prior_sigma=sigma)
+    A, c = tgt.A, -0.5 * d * math.log(2 * math.pi * sigma * sigma)
+
+    def logp(ys):
+        return torch.nn.functional.logsigmoid(A @ ys).sum(0) - (ys * ys).sum(0) / (2 * sigma * sigma) + c
+
+    return tgt, logp, rows
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--ramp", type=float, default=1.0)
+    ap.add_argument("--case", default="")
+    args = ap.parse_args()
+    nf = load_package()
+    lib = nf.load_library()
+    q = lambda d: nf.MvNormal(d)  # noqa: E731
+    f32 = torch.float32
+    gen = torch.Generator().manual_seed(1)
+    cases = [
+        ("a_cfg2_realnvp_d64_h64x8", "densegauss", lambda: nf.realnvp(q(64), (64, 64), 4, paramtype=f32, seed=1), lambda: dense_gauss(nf, 64, gen), 65536),
+        ("b_cfg2_realnvp_d64_h64x8", "logreg_n1024", lambda: nf.realnvp(q(64), (64, 64), 4, paramtype=f32, seed=1), lambda: logreg(nf, 64, 1024, gen), 65536),
+        ("c_cfg3_nsf_d32_k8x8", "densegauss", lambda: nf.nsf(q(32), (32, 32), 8, 5.0, 4, paramtype=f32, seed=1), lambda: dense_gauss(nf, 32, gen), 131072),
+    ]
+    want = [c for c in args.case.split(",") if c]
+    vp = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    for name, tname, make, make_tgt, n in cases:
+        if want and name[0] not in want:
+            continue
+        flow = make()
+        tgt, torch_logp, rows = make_tgt()
+        d = flow.dist.d
+        theta0, re = flow.destructure()
+        row = {"flow": name, "target": tname, "N": n, "d": d, "rows": rows}
+        ctx = flow.ctx
+        th = theta0.clone()
+        m, v = torch.zeros_like(th), torch.zeros_like(th)
+        k = [0]
+
+        def step():
+            nf._lib.check(lib.nf_elbo_step(ctx.ptr, C.byref(flow.desc), C.byref(tgt.c), vp(th), vp(m), vp(v), n, 7, k[0], LR, B1, B2, EPS, None, None))
+            k[0] += 1
+
+        th2 = theta0.clone()
+        st = nf.setup(nf.Adam(LR), th2)
+        rng = nf.PhiloxRNG(7)
+
+        def closure():
+            _, g = nf.value_and_gradient(nf.elbo_batch, re(th2), torch_logp, n, rng)
+            nf.update(nf.Adam(LR), st, th2, g, want_norm=True)
+
+        step()
+        closure()
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < args.ramp:  # clock ramp
+            step()
+        torch.cuda.synchronize()
+        a, b = [], []
+        for _ in range(args.runs):  # interleaved A/B
+            a.append(timed(step))
+            b.append(timed(closure))
+        row["step_ms"], row["step_spread"] = round(statistics.median(a), 4), round(max(a) - min(a), 4)
+        row["closure_ms"], row["closure_spread"] = round(statistics.median(b), 4), round(max(b) - min(b), 4)
+        row["closure_over_step"] = round(row["closure_ms"] / row["step_ms"], 3)
+        # the target launch alone, from events around it (a run of its own: the events perturb the step's timing)
+        nf._lib.check(lib.nf_prof_enable(ctx.ptr, 2))
+        for _ in range(20):
+            step()
+        torch.cuda.synchronize()
+        ms, cnt = C.c_double(0.0), C.c_int64(0)
+        nf._lib.check(lib.nf_prof_read(ctx.ptr, b"target_linpred", C.byref(ms), C.byref(cnt)))
+        nf._lib.check(lib.nf_prof_enable(ctx.ptr, 0))
+        row["linpred_ms"], row["linpred_launches"] = round(ms.value, 5), cnt.value
+        flop = 4.0 * rows * d * n
+        row["linpred_gflop"] = round(flop / 1e9, 3)
+        row["linpred_roofline"] = round(flop / (ms.value * 1e-3) / (MFMA_F32_TFLOPS * 1e12), 4) if ms.value > 0 else None
+        print(json.dumps(row), flush=True)
+        del flow, th, m, v, th2
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()

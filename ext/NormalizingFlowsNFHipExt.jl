@@ -53,6 +53,7 @@ end
 const NF_KIND_PLANAR, NF_KIND_RADIAL, NF_KIND_REALNVP, NF_KIND_NSF, NF_KIND_MEANFIELD = Int32(0), Int32(1), Int32(2), Int32(3), Int32(4)
 const NF_TARGET_DIAGGAUSS, NF_TARGET_BANANA, NF_TARGET_FUNNEL, NF_TARGET_WARPED, NF_TARGET_CROSS = Int32(0), Int32(1), Int32(2), Int32(3), Int32(4)
 const NF_TARGET_DENSEGAUSS, NF_TARGET_LOGREG = Int32(5), Int32(6)   # linear-predictor targets (nfhip.h)
+const NF_TARGET_GAUSSMIX = Int32(8)                                  # Gaussian mixture (nfhip.h; kind 7 is unassigned)
 dtype_code(::Type{Float32}) = Int32(0)
 dtype_code(::Type{Float64}) = Int32(1)
 
@@ -242,6 +243,44 @@ function LogRegTarget(X::AbstractMatrix{T}, t::AbstractVector, σ::Real=1.0; shi
     s = all(in((-1, 1)), t) ? Float64.(t) : all(in((0, 1)), t) ? 2.0 .* t .- 1.0 : error("nfhip: labels must be in {-1, +1} or {0, 1}")
     size(X, 1) == length(s) || error("nfhip: one label per row of X")
     return LogRegTarget(ROCArray(Matrix{T}(transpose(X .* T.(s)))), Float64(σ), shift)
+end
+# MixtureModel([MvNormal(μ_k, Σ_k)], π): the W_k = inv(L_k) stacked (row-major K d × d for the device = the column-major
+# d × K d array `At` whose block k is transpose(W_k)), and one buffer p0 = m̄ | b | c with m̄ = Σ π_k μ_k,
+# b_k = W_k (μ_k − m̄), c_k = log π_k + log|det W_k| − d/2 log 2π.  Factored on the host in Float64; zero-weight components
+# are dropped.  Same flows as the linear-predictor targets; Float32 coupling flows need d ≤ 64.
+struct GaussMixTarget{V<:ROCVector,M<:ROCMatrix} <: NFHipTarget
+    At::M            # d × K d
+    p0::V            # d + K d + K
+    K::Int
+end
+function GaussMixTarget(::Type{T}, ws::AbstractVector, μs::AbstractVector, Σs::AbstractVector) where {T}
+    (length(ws) == length(μs) == length(Σs) && length(ws) >= 1) || error("nfhip: one weight, mean and covariance per component")
+    (all(>=(0), ws) && abs(sum(ws) - 1) <= 1e-6) || error("nfhip: weights must be >= 0 and sum to 1")
+    w = Float64.(ws) ./ sum(Float64.(ws))
+    keep = findall(>(0), w)
+    d = length(μs[1])
+    all(k -> length(μs[k]) == d && size(Σs[k]) == (d, d), keep) || error("nfhip: every component needs a length-$d mean and a $d × $d covariance")
+    m̄ = zeros(Float64, d)
+    for k in keep
+        m̄ .+= w[k] .* Float64.(μs[k])
+    end
+    nk = length(keep)
+    At = Matrix{Float64}(undef, d, d * nk)
+    b = Matrix{Float64}(undef, d, nk)
+    c = Vector{Float64}(undef, nk)
+    for (i, k) in enumerate(keep)
+        L = LinearAlgebra.cholesky(LinearAlgebra.Symmetric(Matrix{Float64}(Σs[k]))).L   # throws PosDefException for component k
+        W = Matrix(inv(LinearAlgebra.LowerTriangular(Matrix(L))))
+        At[:, ((i - 1) * d + 1):(i * d)] = transpose(W)
+        b[:, i] = W * (Float64.(μs[k]) .- m̄)
+        c[i] = log(w[k]) - sum(log, LinearAlgebra.diag(L)) - d / 2 * log(2 * Base.pi)
+    end
+    return GaussMixTarget(ROCArray(Matrix{T}(At)), ROCArray(Vector{T}(vcat(m̄, vec(b), c))), nk)
+end
+c_target(t::GaussMixTarget) = NFTarget(NF_TARGET_GAUSSMIX, devptr(t.p0), devptr(t.At), Float64(t.K), 0.0)
+function check_target(t::GaussMixTarget, ::Type{T}, d) where {T}
+    (eltype(t.At) === T && eltype(t.p0) === T && size(t.At) == (d, d * t.K) && length(t.p0) == d + d * t.K + t.K) ||
+        error("nfhip: target must be a $d-dimensional Gaussian mixture in $T")
 end
 c_target(t::DenseGaussTarget) = NFTarget(NF_TARGET_DENSEGAUSS, devptr(t.μ), devptr(t.Wt), t.logdetW, 0.0)
 c_target(t::LogRegTarget) = NFTarget(NF_TARGET_LOGREG, t.shift === nothing ? C_NULL : devptr(t.shift), devptr(t.At), Float64(size(t.At, 2)), t.σ)

@@ -100,6 +100,26 @@ extern "C" {
  * score either.  nf_elbo_step runs the split sequence (value and gradient, then Adam) for them. */
 #define NF_TARGET_DENSEGAUSS 5
 #define NF_TARGET_LOGREG 6
+/* Gaussian mixture: MixtureModel([MvNormal(mu_k, Sigma_k)], pi), K components with Sigma_k = L_k L_k' (what
+ * example/targets/cross.jl:31-37 builds for Cross).  Kind 7 stays unassigned (callers may rely on it being "no such kind").
+ *   With W_k = inv(L_k) and ONE common centre mbar = sum_k pi_k mu_k (the device centres a tile of samples once):
+ *       u_k = W_k (y - mbar) - b_k,  b_k = W_k (mu_k - mbar),
+ *       q_k = c_k - |u_k|^2 / 2,     c_k = log pi_k + log|det W_k| - d/2 log(2 pi),
+ *       log p = logsumexp_k q_k,     grad = -sum_k r_k W_k' u_k,  r_k = exp(q_k - log p).
+ *   p1 = A[K d x d] row-major: the W_k stacked, each lower triangular and stored dense with its zeros;
+ *   p0 = ONE buffer [d + K d + K]: mbar | b | c;  s0 = K (an integer value, K >= 1, K d < 2^31);  s1 unused, must be 0.
+ *   All device pointers are in the flow's element type.  NF_ERR_ARG for a NULL p0 / p1, s0 < 1, a non-integral or too
+ *   large s0, or s1 != 0 -- before any device work.
+ * Evaluated in one pass over the components with a running log-sum-exp (never (-inf) - (-inf); a sample far from every
+ * component keeps a finite log p and score).  Served like the linear-predictor kinds: nf_target_logp (d <= 256), RealNVP /
+ * NSF flows of either element type, general bases and compositions as ELBO targets; planar, radial, mean-field and
+ * Hamiltonian flows answer NF_ERR_UNSUPPORTED at every ELBO entry point (a Hamiltonian descriptor cannot use it as its
+ * score either); nf_elbo_step runs the split sequence, nf_elbo_step_enqueue answers NF_ERR_UNSUPPORTED.
+ * Float32 RealNVP / NSF flows on the tiled path take the matrix-pipe kernel, which is built for d <= 64 (every LDS-resident
+ * coupling flow); with 64 < d (the weight-streaming shapes) those flows answer NF_ERR_UNSUPPORTED at every ELBO entry
+ * point before any launch -- there is no chunked form.  A general base does not change this: it runs the same flow's
+ * standard-base path on draws of its own. */
+#define NF_TARGET_GAUSSMIX 8
 
 #define NF_MAX_HIDDEN 4
 
@@ -361,7 +381,7 @@ int nf_ctx_set_weight_cache(nf_ctx *ctx, int32_t enable);
  * without a communicator, Float32 LDS-resident spline couplings and the planar, radial and mean-field flows nf_elbo_step
  * runs in three launches (Float32 or Float64) -- each with any of the five built-in targets (valid arguments: WarpedGauss
  * and Cross need d = 2).  NF_ERR_UNSUPPORTED for everything else, the linear-predictor targets (NF_TARGET_DENSEGAUSS,
- * NF_TARGET_LOGREG) on every flow included: theta and *step_device are left as they were. */
+ * NF_TARGET_LOGREG) and the Gaussian mixture (NF_TARGET_GAUSSMIX) on every flow included: theta and *step_device are left as they were. */
 int nf_elbo_step_enqueue(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, void *theta, void *m, void *v,
                          int64_t N, uint64_t seed, uint32_t *step_device, double lr, double beta1, double beta2,
                          double eps, void *out_loss_gnorm_device);

@@ -17,6 +17,9 @@ NF_TARGET_DIAGGAUSS, NF_TARGET_BANANA, NF_TARGET_FUNNEL, NF_TARGET_WARPED, NF_TA
 # linear-predictor targets (include/nfhip.h): p0 = mu[d] (optional for LOGREG), p1 = the row-major matrix;
 # DENSEGAUSS: s0 = log|det W|; LOGREG: s0 = number of rows, s1 = prior sigma
 NF_TARGET_DENSEGAUSS, NF_TARGET_LOGREG = 5, 6
+# Gaussian mixture: p1 = the W_k = inv(L_k) stacked [K d, d]; p0 = one buffer mbar[d] | b[K d] | c[K]; s0 = K; s1 = 0.
+# (kind 7 is unassigned)
+NF_TARGET_GAUSSMIX = 8
 NF_MAX_HIDDEN = 4
 NF_ERR_NONFINITE = -4
 

@@ -641,14 +641,18 @@ static long coupling_slab_floats(nf_ctx *ctx, const nf_flow_desc *desc, long N) 
 static inline bool elbo_fusable(const nf_flow_desc *desc, const nf_target *target, const void *xs, bool sizing = false) {
   const bool resident = (desc->kind == NF_KIND_REALNVP && nf_affine_supported(desc) && nf_affine_fused_ok(desc)) ||
                         (desc->kind == NF_KIND_NSF && nf_rqs_supported(desc));
-  // the linear-predictor kinds have no epilogue in the chain kernels: the generic sequence and its target launch serve them
-  if (target && target_is_linpred(target->kind)) return false;
+  // the linear-predictor kinds and the mixture have no epilogue in the chain kernels: the generic sequence and its target launch serve them
+  if (target && target_has_own_kernel(target->kind)) return false;
   return !xs && desc->dtype == NF_DTYPE_F32 && resident && (sizing || nf_target_check(target, desc->d) == NF_OK);
 }
 // Planar, radial and mean-field flows evaluate the target inside their forward / step kernels, one feature at a time, and a
-// Hamiltonian flow's joint density does too: with a linear-predictor target every ELBO entry point refuses them before any launch.
-static inline bool linpred_refused(const nf_flow_desc *desc, const nf_target *target) {
-  if (!target || !target_is_linpred(target->kind)) return false;
+// Hamiltonian flow's joint density does too: with a linear-predictor or mixture target every ELBO entry point refuses them before
+// any launch.  The mixture's tiled kernel stops at d = 64: Float32 coupling flows beyond it (the weight-streaming shapes) are
+// refused here too -- with a general base as well, whose wrappers run the standard-base entry point of the same flow (the tiled
+// path) on draws of their own.
+static inline bool target_refused(const nf_flow_desc *desc, const nf_target *target) {
+  if (!target || !target_has_own_kernel(target->kind)) return false;
+  if (target->kind == NF_TARGET_GAUSSMIX && desc->d > NF_MIXTURE_TILED_MAXD && is_coupling(desc)) return true;
   return desc->kind == NF_KIND_PLANAR || desc->kind == NF_KIND_RADIAL || desc->kind == NF_KIND_MEANFIELD ||
          desc->kind == NF_KIND_HAMILTONIAN;
 }
@@ -1225,7 +1229,7 @@ extern "C" int nf_elbo_batch(nf_ctx *ctx, const nf_flow_desc *desc, const nf_tar
                              const void *xs, int64_t N, void *elbos_out, double *elbo_host) {
   if (!ctx || !target || !theta || !xs || !elbo_host || N < 1) return NF_ERR_ARG;
   NF_TRY(check_desc(desc));
-  if (linpred_refused(desc, target)) return NF_ERR_UNSUPPORTED;
+  if (target_refused(desc, target)) return NF_ERR_UNSUPPORTED;
   NF_HIP(hipSetDevice(ctx->device));
   if (flow_base(desc)) return elbo_forward_general_base(ctx, desc, target, theta, xs, N, 0, 0, 0, elbos_out, elbo_host);
   return elbo_forward(ctx, desc, target, theta, xs, N, 0, 0, 0, elbos_out, elbo_host);
@@ -1236,7 +1240,7 @@ extern "C" int nf_elbo_batch_rng(nf_ctx *ctx, const nf_flow_desc *desc, const nf
                                  double *elbo_host) {
   if (!ctx || !target || !theta || !elbo_host || N < 1) return NF_ERR_ARG;
   NF_TRY(check_desc(desc));
-  if (linpred_refused(desc, target)) return NF_ERR_UNSUPPORTED;
+  if (target_refused(desc, target)) return NF_ERR_UNSUPPORTED;
   NF_HIP(hipSetDevice(ctx->device));
   if (flow_base(desc))
     return elbo_forward_general_base(ctx, desc, target, theta, nullptr, N, seed, sample_offset, stream_id, nullptr, elbo_host);
@@ -1845,7 +1849,7 @@ extern "C" int nf_elbo_value_and_grad(nf_ctx *ctx, const nf_flow_desc *desc, con
                                       uint64_t seed, uint64_t sample_offset, uint32_t stream_id, void *out) {
   if (!ctx || !target || !theta || !out || N_local < 0 || N_global < 1) return NF_ERR_ARG;
   NF_TRY(check_desc(desc));
-  if (linpred_refused(desc, target)) return NF_ERR_UNSUPPORTED;
+  if (target_refused(desc, target)) return NF_ERR_UNSUPPORTED;
   NF_HIP(hipSetDevice(ctx->device));
   if (flow_base(desc))
     return value_and_grad_general_base(ctx, desc, target, theta, xs, N_local, N_global, seed, sample_offset, stream_id, out);
@@ -2207,7 +2211,7 @@ static bool step_fusable_simple(nf_ctx *ctx, const nf_flow_desc *desc, const nf_
   if (desc->kind != NF_KIND_PLANAR && desc->kind != NF_KIND_RADIAL && desc->kind != NF_KIND_MEANFIELD) return false;
   if (desc->dtype != NF_DTYPE_F32 && desc->dtype != NF_DTYPE_F64) return false;
   if (!nf_simple_step_supported(desc)) return false;
-  if (target && target_is_linpred(target->kind)) return false;
+  if (target && target_has_own_kernel(target->kind)) return false;
   return sizing || nf_target_check(target, desc->d) == NF_OK;
 }
 // the step launch's loss partials, its gradient slabs (one per workgroup and layer), the epilogue's block partials of ||g||^2
@@ -2348,7 +2352,7 @@ static int step_split(nf_ctx *ctx, const nf_flow_desc *desc, const StepCall &c) 
 // grouped by workgroup; it agrees to float rounding.
 static int step_run(nf_ctx *ctx, const nf_flow_desc *desc, const StepCall &c, double *loss_host, double *gnorm_host, void *out_device) {
   NF_TRY(check_desc(desc));
-  if (linpred_refused(desc, c.target)) return NF_ERR_UNSUPPORTED;
+  if (target_refused(desc, c.target)) return NF_ERR_UNSUPPORTED;
   NF_HIP(hipSetDevice(ctx->device));
   if (c.Ng < 1) return NF_ERR_ARG;
   const long P = nf_param_count(desc), N = c.N;

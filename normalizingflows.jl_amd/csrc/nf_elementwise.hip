@@ -657,6 +657,9 @@ int nf_target_check(const nf_target *t, int d) {
     case NF_TARGET_DENSEGAUSS: return (t->p0 && t->p1) ? NF_OK : NF_ERR_ARG;
     case NF_TARGET_LOGREG:  // s0 = the number of data rows, an integer value that fits an int
       return (t->p1 && t->s1 > 0 && t->s0 >= 1 && t->s0 < 2147483648.0 && t->s0 == (double)(long)t->s0) ? NF_OK : NF_ERR_ARG;
+    case NF_TARGET_GAUSSMIX:  // s0 = the number of components, an integer value with K d rows that fit an int; s1 unused
+      return (t->p0 && t->p1 && t->s1 == 0 && t->s0 >= 1 && t->s0 * (double)(d > 0 ? d : 1) < 2147483648.0 &&
+              t->s0 == (double)(long)t->s0) ? NF_OK : NF_ERR_ARG;
     default: return NF_ERR_ARG;
   }
 }
@@ -669,14 +672,22 @@ int nf_launch_target_linpred(nf_ctx *, int dtype, const nf_target *, int d, long
                              double pscale);
 int nf_launch_target_linpred_tiled(nf_ctx *, const nf_target *, int d, long N, const float *yt, const float *logq,
                                    const float *ladj, float *gt, double gscale, float *elbos_out, double *partial, double pscale);
+// nf_mixture.hip: the Gaussian mixture, the same contract
+int nf_launch_target_mixture(nf_ctx *, int dtype, const nf_target *, int d, long N, const void *y, const void *logq,
+                             const void *ladj, void *logp_out, void *grad_out, double gscale, void *elbos_out, double *partial,
+                             double pscale);
+int nf_launch_target_mixture_tiled(nf_ctx *, const nf_target *, int d, long N, const float *yt, const float *logq,
+                                   const float *ladj, float *gt, double gscale, float *elbos_out, double *partial, double pscale);
 
 int nf_launch_target(nf_ctx *ctx, int dtype, const nf_target *t, int d, long N, const void *y, const void *logq,
                      const void *ladj, void *logp_out, void *grad_out, double gscale, void *elbos_out, double *partial,
                      double pscale, int joint_d) {
   if (N <= 0) return NF_OK;
   NF_TRY(nf_target_check(t, joint_d > 0 ? joint_d : d));
-  if (target_is_linpred(t->kind)) {
+  if (target_has_own_kernel(t->kind)) {
     if (joint_d > 0) return NF_ERR_UNSUPPORTED;  // (the ELBO entry points refuse Hamiltonian flows with these kinds first)
+    if (t->kind == NF_TARGET_GAUSSMIX)
+      return nf_launch_target_mixture(ctx, dtype, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
     return nf_launch_target_linpred(ctx, dtype, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
   }
   ProfScope ps(ctx, "target");
@@ -795,6 +806,8 @@ int nf_launch_target_tiled(nf_ctx *ctx, const nf_target *t, int d, long N, const
                            double pscale) {
   if (N <= 0) return NF_OK;
   NF_TRY(nf_target_check(t, d));
+  if (t->kind == NF_TARGET_GAUSSMIX)
+    return nf_launch_target_mixture_tiled(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
   if (target_is_linpred(t->kind))
     return nf_launch_target_linpred_tiled(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
   ProfScope ps(ctx, "target");

@@ -81,3 +81,8 @@ __host__ __device__ inline bool target_needs_d2(int kind) { return kind == NF_TA
 // matrix: target_term cannot express them.  They have kernels of their own (nf_linpred.hip), reached through
 // nf_launch_target / nf_launch_target_tiled; every path that evaluates target_term inside a fused kernel refuses them.
 __host__ __device__ inline bool target_is_linpred(int kind) { return kind == NF_TARGET_DENSEGAUSS || kind == NF_TARGET_LOGREG; }
+// The Gaussian mixture (NF_TARGET_GAUSSMIX, nf_mixture.hip) is routed like them: a kernel of its own behind
+// nf_launch_target / nf_launch_target_tiled, refused wherever target_term would have to evaluate it.
+__host__ __device__ inline bool target_has_own_kernel(int kind) { return target_is_linpred(kind) || kind == NF_TARGET_GAUSSMIX; }
+// widest flow the mixture's tiled kernel serves (two U and two G blocks in registers); the flat kernel goes to 256
+#define NF_MIXTURE_TILED_MAXD 64

@@ -646,6 +646,55 @@ class LogisticRegressionTarget(_LinpredTarget):
                         self.prior_sigma)
 
 
+class MixtureTarget(_LinpredTarget):
+    """logp(z) = logpdf(MixtureModel([MvNormal(mus[k], Sigmas[k]) for k], weights), z): K full-covariance Gaussians
+    (example/targets/cross.jl:31-37 builds Cross this way).  weights (K,), mus (K, d), Sigmas (K, d, d), one element type
+    and device.  Every Sigma_k = L_k L_k' is factored on the host in float64; the device reads the W_k = inv(L_k) stacked
+    (`A` [K d, d]) and one buffer `p0` = mbar | b | c with the common centre mbar = sum_k pi_k mu_k,
+    b_k = W_k (mu_k - mbar) and c_k = log pi_k + log|det W_k| - d/2 log(2 pi).  Weights are renormalised in float64;
+    zero-weight components are dropped."""
+
+    def __init__(self, weights: torch.Tensor, mus: torch.Tensor, Sigmas: torch.Tensor):
+        if weights.dim() != 1 or mus.dim() != 2 or Sigmas.dim() != 3 or weights.numel() < 1 or mus.shape[1] < 1 or \
+                mus.shape[0] != weights.numel() or tuple(Sigmas.shape) != (mus.shape[0], mus.shape[1], mus.shape[1]):
+            raise NFHipError("MixtureTarget: weights (K,), mus (K, d), Sigmas (K, d, d) with K >= 1")
+        if not (weights.dtype == mus.dtype == Sigmas.dtype) or not (weights.device == mus.device == Sigmas.device) or \
+                mus.dtype not in (torch.float32, torch.float64):
+            raise NFHipError("MixtureTarget: weights, mus and Sigmas must share one element type (Float32 or Float64) and one device")
+        w64 = weights.detach().to("cpu", torch.float64)
+        if not bool(torch.isfinite(w64).all()) or bool((w64 < 0).any()) or abs(float(w64.sum()) - 1.0) > 1e-6:
+            raise NFHipError("MixtureTarget: weights must be >= 0 and sum to 1 (within 1e-6)")
+        w64 = w64 / w64.sum()
+        keep = [k for k in range(w64.numel()) if float(w64[k]) > 0.0]
+        d = mus.shape[1]
+        m64 = mus.detach().to("cpu", torch.float64)
+        S64 = Sigmas.detach().to("cpu", torch.float64)
+        if not bool(torch.isfinite(m64).all()):
+            raise NFHipError("MixtureTarget: mus must be finite")
+        eye = torch.eye(d, dtype=torch.float64)
+        Ws, logdets = [], []
+        for k in keep:
+            Sk = S64[k]
+            if not bool(torch.isfinite(Sk).all()) or not torch.allclose(Sk, Sk.T, rtol=1e-6, atol=1e-12 * float(Sk.abs().max() + 1)):
+                raise NFHipError(f"MixtureTarget: Sigma of component {k} is not symmetric")
+            L, info = torch.linalg.cholesky_ex(Sk)
+            if int(info) != 0:
+                raise NFHipError(f"MixtureTarget: Sigma of component {k} is not positive definite")
+            Ws.append(torch.tril(torch.linalg.solve_triangular(L, eye, upper=False)))
+            logdets.append(-torch.log(torch.diagonal(L)).sum())
+        pi = w64[keep]
+        mk = m64[keep]
+        W = torch.stack(Ws)                                     # [K, d, d]
+        mbar = (pi[:, None] * mk).sum(0)
+        b = torch.einsum("kij,kj->ki", W, mk - mbar[None, :])   # [K, d]
+        c = torch.log(pi) + torch.stack(logdets) - 0.5 * d * math.log(2.0 * math.pi)
+        self.d, self.K = d, len(keep)
+        self.weights = pi
+        self.A = W.reshape(self.K * d, d).to(mus.dtype).to(mus.device).contiguous()
+        self.p0 = torch.cat([mbar, b.reshape(-1), c]).to(mus.dtype).to(mus.device).contiguous()
+        self.c = Target(_lib.NF_TARGET_GAUSSMIX, self.p0.data_ptr(), self.A.data_ptr(), float(self.K), 0.0)
+
+
 def check_target(target, dtype, device=None, d=None):
     """Element-type / device / dimension agreement between a built-in target and the flow that will read it."""
     if isinstance(target, DiagGaussTarget):

@@ -220,7 +220,7 @@ __device__ void g64_build(const T *raw, int K, T B, G64Spline<T> &sp) {
 }
 template <class T>
 __device__ __forceinline__ int g64_bin(const T *p, int K, T v, bool &inside) {
-  inside = (v >= p[0]) && (v < p[K]);
+  inside = (v >= p[0]) && (v < -p[0]);  // [-B, B) itself (p[0] = -B exactly); p[K] as computed may differ from B by an ulp
   int k = 0;
   for (int j = 1; j < K; ++j) k += (v >= p[j]) ? 1 : 0;
   return k;
@@ -1013,7 +1013,7 @@ __device__ __forceinline__ L64Bin l64_find(const float (&r)[KM], int K, float B,
   L64Bin b{-1, 0.f, 0.f, 0.f};
   float cs = 0.f, left = -B;
   int k = 0;
-  float x0 = -B, x1 = -B, smk = 0.f, pK = -B;
+  float x0 = -B, x1 = -B, smk = 0.f;
 #pragma unroll
   for (int i = 0; i < KM; ++i)
     if (i < K) {
@@ -1024,9 +1024,11 @@ __device__ __forceinline__ L64Bin l64_find(const float (&r)[KM], int K, float B,
       const bool take = (i == 0 || v >= left) && (i == K - 1 || !(v >= right));
       if (take) { k = i; x0 = left; x1 = right; smk = sm; }
       left = right;
-      pK = right;
     }
-  if (v >= -B && v < pK) { b.k = k; b.x0 = x0; b.x1 = x1; b.sm = smk; }
+  // the box is [-B, B) itself, as in nf_rqs_elem.h's find_bin: the last knot as computed (-B + 2B * (a float sum of the softmax))
+  // can sit an ulp or two above B, and an element between the two would be taken through the last bin instead of coming back
+  // bit-identical; one between a last knot below B and B belongs to the last bin, whose k, x0, x1 the loop has already selected
+  if (v >= -B && v < B) { b.k = k; b.x0 = x0; b.x1 = x1; b.sm = smk; }
   return b;
 }
 // knots k, k + 1 of the OTHER axis for a known bin

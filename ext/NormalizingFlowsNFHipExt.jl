@@ -54,6 +54,9 @@ const NF_KIND_PLANAR, NF_KIND_RADIAL, NF_KIND_REALNVP, NF_KIND_NSF, NF_KIND_MEAN
 const NF_TARGET_DIAGGAUSS, NF_TARGET_BANANA, NF_TARGET_FUNNEL, NF_TARGET_WARPED, NF_TARGET_CROSS = Int32(0), Int32(1), Int32(2), Int32(3), Int32(4)
 const NF_TARGET_DENSEGAUSS, NF_TARGET_LOGREG = Int32(5), Int32(6)   # linear-predictor targets (nfhip.h)
 const NF_TARGET_GAUSSMIX = Int32(8)                                  # Gaussian mixture (nfhip.h; kind 7 is unassigned)
+# generalised linear-predictor targets (nfhip.h): row offsets, row weights, a linear term, a family parameter
+const NF_TARGET_GLM_LOGIT, NF_TARGET_GLM_PROBIT, NF_TARGET_GLM_POISSON, NF_TARGET_GLM_STUDENT, NF_TARGET_GLM_NORMAL =
+    Int32(9), Int32(10), Int32(11), Int32(12), Int32(13)
 dtype_code(::Type{Float32}) = Int32(0)
 dtype_code(::Type{Float64}) = Int32(1)
 
@@ -281,6 +284,38 @@ c_target(t::GaussMixTarget) = NFTarget(NF_TARGET_GAUSSMIX, devptr(t.p0), devptr(
 function check_target(t::GaussMixTarget, ::Type{T}, d) where {T}
     (eltype(t.At) === T && eltype(t.p0) === T && size(t.At) == (d, d * t.K) && length(t.p0) == d + d * t.K + t.K) ||
         error("nfhip: target must be a $d-dimensional Gaussian mixture in $T")
+end
+# The generalised form  log p(z) = const + Σ_i wt_i φ(u_i; param) + lin·z − |z|²/(2σ²) − d/2 log(2πσ²),  u = A z + off, with
+# family ∈ (:logit, :probit, :poisson, :student, :normal).  The device reads A row-major (the column-major d × rows array `At`)
+# and ONE buffer p0 = lin[d] | off[rows] | wt[rows] | (param, const).  σ = Inf is the flat prior.  Same flows as the other
+# linear-predictor targets.
+struct GLMTarget{V<:ROCVector,M<:ROCMatrix} <: NFHipTarget
+    kind::Int32
+    At::M            # d × rows
+    p0::V            # d + 2 rows + 2
+    σ::Float64
+end
+const GLM_KINDS = Dict(:logit => NF_TARGET_GLM_LOGIT, :probit => NF_TARGET_GLM_PROBIT, :poisson => NF_TARGET_GLM_POISSON,
+                       :student => NF_TARGET_GLM_STUDENT, :normal => NF_TARGET_GLM_NORMAL)
+function GLMTarget(family::Symbol, A::AbstractMatrix{T}; offset=nothing, weights=nothing, lin=nothing, constant::Real=0.0, param::Real=0.0,
+                   σ::Real=1.0) where {T}
+    haskey(GLM_KINDS, family) || error("nfhip: family must be one of $(sort(collect(keys(GLM_KINDS))))")
+    rows, d = size(A)
+    (rows >= 1 && d >= 1 && all(isfinite, A)) || error("nfhip: A must be a finite rows × d matrix")
+    off = offset === nothing ? zeros(Float64, rows) : Float64.(offset)
+    wt = weights === nothing ? ones(Float64, rows) : Float64.(weights)
+    ln = lin === nothing ? zeros(Float64, d) : Float64.(lin)
+    (length(off) == rows && length(wt) == rows && length(ln) == d) || error("nfhip: offset and weights have one entry per row, lin one per column")
+    (all(isfinite, off) && all(isfinite, ln) && all(w -> isfinite(w) && w >= 0, wt)) || error("nfhip: offsets and lin must be finite, weights finite and >= 0")
+    (isfinite(constant) && isfinite(param) && (family !== :student || param > 0)) || error("nfhip: constant and param must be finite, ν > 0")
+    (σ > 0 && !isnan(σ)) || error("nfhip: prior σ must be > 0 (Inf: flat prior)")
+    p0 = vcat(ln, off, wt, Float64[param, constant])
+    return GLMTarget(GLM_KINDS[family], ROCArray(Matrix{T}(transpose(A))), ROCArray(Vector{T}(p0)), Float64(σ))
+end
+c_target(t::GLMTarget) = NFTarget(t.kind, devptr(t.p0), devptr(t.At), Float64(size(t.At, 2)), t.σ)
+function check_target(t::GLMTarget, ::Type{T}, d) where {T}
+    (eltype(t.At) === T && eltype(t.p0) === T && size(t.At, 1) == d && length(t.p0) == d + 2 * size(t.At, 2) + 2) ||
+        error("nfhip: target must hold $d-dimensional data rows in $T")
 end
 c_target(t::DenseGaussTarget) = NFTarget(NF_TARGET_DENSEGAUSS, devptr(t.μ), devptr(t.Wt), t.logdetW, 0.0)
 c_target(t::LogRegTarget) = NFTarget(NF_TARGET_LOGREG, t.shift === nothing ? C_NULL : devptr(t.shift), devptr(t.At), Float64(size(t.At, 2)), t.σ)

@@ -120,6 +120,31 @@ extern "C" {
  * point before any launch -- there is no chunked form.  A general base does not change this: it runs the same flow's
  * standard-base path on draws of its own. */
 #define NF_TARGET_GAUSSMIX 8
+/* Generalised linear-predictor targets: the regression posteriors that need a per-row offset, a per-row weight, a linear
+ * term or a family parameter.  One form, five row functions:
+ *       log p(y) = par[1] + sum_i wt_i phi(u_i; par[0]) + lin . y - |y|^2 / (2 s1^2) - d/2 log(2 pi s1^2),   u = A y + off,
+ *       grad     = A' (wt o phi'(u)) + lin - y / s1^2.
+ *   p1 = A[rows x d] row-major;  p0 = ONE buffer of d + 2 rows + 2 elements: lin[d] | off[rows] | wt[rows] | par[2], with
+ *   par[0] the family parameter (nu > 0 for STUDENT, ignored by the others) and par[1] the additive constant the host folded
+ *   (log-factorials, normalisers);  s0 = rows (an integer value, 1 <= rows < 2^31);  s1 = the prior sigma > 0, where +inf
+ *   is the flat prior (both prior terms vanish).  All device pointers are in the flow's element type.  NF_ERR_ARG for a
+ *   NULL p0 / p1, a bad s0, s1 <= 0 or a NaN s1 -- before any device work.
+ *   NF_TARGET_GLM_LOGIT    phi = log sigmoid(u)                    phi' = sigmoid(-u)       (binomial / Bernoulli, logit link)
+ *   NF_TARGET_GLM_PROBIT   phi = log Phi(u)                        phi' = phi_N(u) / Phi(u) (through erfcx on the left tail)
+ *   NF_TARGET_GLM_POISSON  phi = -exp(u)                           phi' = -exp(u)           (log link; k u sits in lin / par[1])
+ *   NF_TARGET_GLM_STUDENT  phi = -(nu + 1)/2 log1p(u^2 / nu)       phi' = -(nu + 1) u / (nu + u^2)
+ *   NF_TARGET_GLM_NORMAL   phi = -u^2 / 2                          phi' = -u
+ * A row with wt_i == 0 contributes exactly 0 to the value and the gradient (by select: a subsampling mask may sit over a
+ * row whose phi overflows).  Nothing is clamped: a POISSON predictor beyond exp's range gives a non-finite value, which
+ * nf_elbo_step reports as NF_ERR_NONFINITE.  Served exactly like NF_TARGET_DENSEGAUSS / NF_TARGET_LOGREG: nf_target_logp
+ * (d <= 256), RealNVP / NSF flows of either element type including the weight-streaming shapes, general bases and
+ * compositions; nf_elbo_step runs the split sequence, nf_elbo_step_enqueue answers NF_ERR_UNSUPPORTED; planar, radial,
+ * mean-field and Hamiltonian flows answer NF_ERR_UNSUPPORTED at every ELBO entry point, a Hamiltonian score included. */
+#define NF_TARGET_GLM_LOGIT 9
+#define NF_TARGET_GLM_PROBIT 10
+#define NF_TARGET_GLM_POISSON 11
+#define NF_TARGET_GLM_STUDENT 12
+#define NF_TARGET_GLM_NORMAL 13
 
 #define NF_MAX_HIDDEN 4
 
@@ -381,7 +406,7 @@ int nf_ctx_set_weight_cache(nf_ctx *ctx, int32_t enable);
  * without a communicator, Float32 LDS-resident spline couplings and the planar, radial and mean-field flows nf_elbo_step
  * runs in three launches (Float32 or Float64) -- each with any of the five built-in targets (valid arguments: WarpedGauss
  * and Cross need d = 2).  NF_ERR_UNSUPPORTED for everything else, the linear-predictor targets (NF_TARGET_DENSEGAUSS,
- * NF_TARGET_LOGREG) and the Gaussian mixture (NF_TARGET_GAUSSMIX) on every flow included: theta and *step_device are left as they were. */
+ * NF_TARGET_LOGREG, NF_TARGET_GLM_*) and the Gaussian mixture (NF_TARGET_GAUSSMIX) on every flow included: theta and *step_device are left as they were. */
 int nf_elbo_step_enqueue(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, void *theta, void *m, void *v,
                          int64_t N, uint64_t seed, uint32_t *step_device, double lr, double beta1, double beta2,
                          double eps, void *out_loss_gnorm_device);

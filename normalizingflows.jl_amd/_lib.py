@@ -20,6 +20,9 @@ NF_TARGET_DENSEGAUSS, NF_TARGET_LOGREG = 5, 6
 # Gaussian mixture: p1 = the W_k = inv(L_k) stacked [K d, d]; p0 = one buffer mbar[d] | b[K d] | c[K]; s0 = K; s1 = 0.
 # (kind 7 is unassigned)
 NF_TARGET_GAUSSMIX = 8
+# generalised linear-predictor targets: p1 = A[rows, d]; p0 = one buffer lin[d] | off[rows] | wt[rows] | par[2]
+# (par[0] = family parameter, par[1] = folded constant); s0 = rows; s1 = prior sigma (+inf: flat prior)
+NF_TARGET_GLM_LOGIT, NF_TARGET_GLM_PROBIT, NF_TARGET_GLM_POISSON, NF_TARGET_GLM_STUDENT, NF_TARGET_GLM_NORMAL = 9, 10, 11, 12, 13
 NF_MAX_HIDDEN = 4
 NF_ERR_NONFINITE = -4
 

@@ -660,6 +660,12 @@ int nf_target_check(const nf_target *t, int d) {
     case NF_TARGET_GAUSSMIX:  // s0 = the number of components, an integer value with K d rows that fit an int; s1 unused
       return (t->p0 && t->p1 && t->s1 == 0 && t->s0 >= 1 && t->s0 * (double)(d > 0 ? d : 1) < 2147483648.0 &&
               t->s0 == (double)(long)t->s0) ? NF_OK : NF_ERR_ARG;
+    case NF_TARGET_GLM_LOGIT:
+    case NF_TARGET_GLM_PROBIT:
+    case NF_TARGET_GLM_POISSON:
+    case NF_TARGET_GLM_STUDENT:
+    case NF_TARGET_GLM_NORMAL:  // s0 = the number of rows, as for LOGREG; s1 = the prior sigma, +inf for the flat prior (NaN fails s1 > 0)
+      return (t->p0 && t->p1 && t->s1 > 0 && t->s0 >= 1 && t->s0 < 2147483648.0 && t->s0 == (double)(long)t->s0) ? NF_OK : NF_ERR_ARG;
     default: return NF_ERR_ARG;
   }
 }

@@ -1,10 +1,20 @@
-// nf_linpred.h -- the row functions of the linear-predictor targets (nf_linpred.hip).
+// nf_linpred.h -- the row functions and the row data of the linear-predictor targets (nf_linpred.hip).
 //
-// A linear-predictor target is  log p(y) = c + sum_i phi(u_i) - pw |y|^2 / 2,  u = A (y - mu),  with gradient
-// A' phi'(u) - pw y.  The two built-in kinds differ in phi, in the constant c and in the prior weight pw only:
-//   DENSEGAUSS  phi(u) = -u^2 / 2        c = -d/2 log(2 pi) + log|det W|     pw = 0           (A = W = inv(L))
-//   LOGREG      phi(u) = log sigmoid(u)  c = -d/2 log(2 pi sigma^2)          pw = 1 / sigma^2 (A_i = t_i x_i)
-// A row function returns phi(u) and phi'(u) of ONE element; both target kernels are templated on it.
+// A linear-predictor target is a sum of ONE scalar function over the rows of a matrix product plus a Gaussian prior.  Two
+// forms share the kernels:
+//   centred (kinds 5, 6)   log p(y) = c + sum_i phi(u_i) - pw |y|^2 / 2,   u = A (y - mu),   grad = A' phi'(u) - pw y
+//     DENSEGAUSS  phi(u) = -u^2 / 2        c = -d/2 log(2 pi) + log|det W|     pw = 0           (A = W = inv(L))
+//     LOGREG      phi(u) = log sigmoid(u)  c = -d/2 log(2 pi sigma^2)          pw = 1 / sigma^2 (A_i = t_i x_i)
+//   generalised (kinds 9..13, NF_TARGET_GLM_*)
+//                          log p(y) = par[1] + c + sum_i wt_i phi(u_i; par[0]) + lin . y - pw |y|^2 / 2,   u = A y + off,
+//                          grad = A' (wt o phi'(u)) + lin - pw y,   c = -d/2 log(2 pi sigma^2), pw = 1 / sigma^2 (both 0
+//                          for the flat prior sigma = +inf), with the row data in ONE device buffer
+//                          p0 = lin[d] | off[rows] | wt[rows] | par[2]   (GlmRows below).
+//     LOGIT log sigmoid(u) | PROBIT log Phi(u) | POISSON -exp(u) | STUDENT -(nu + 1)/2 log1p(u^2 / nu) | NORMAL -u^2 / 2
+// A row function returns phi(u; par) and phi'(u; par) of ONE element; both target kernels are templated on it and on the
+// form (a bool: the centred instantiations compile the row data away).  par is the family parameter par[0], read once per
+// launch (nu for STUDENT; the other families ignore it).  A row of weight 0 contributes exactly 0 by SELECT, whatever phi
+// returns there (a subsampling mask may sit over a row whose phi overflows); nothing is clamped.
 #pragma once
 #include "nf_common.h"
 #include "nf_mfma.h"
@@ -12,7 +22,7 @@
 
 struct PhiHalfSquare {  // -u^2 / 2 ; -u
   template <class T>
-  static __device__ __forceinline__ void eval(T u, T &phi, T &dphi) {
+  static __device__ __forceinline__ void eval(T u, T, T &phi, T &dphi) {
     phi = (T)-0.5 * u * u;
     dphi = -u;
   }
@@ -20,20 +30,86 @@ struct PhiHalfSquare {  // -u^2 / 2 ; -u
 
 // log sigmoid(u) = min(u, 0) - log1p(exp(-|u|)) ; sigmoid(-u).  e = exp(-|u|) is in (0, 1]: nothing overflows for any finite u.
 struct PhiLogSigmoid {
-  static __device__ __forceinline__ void eval(double u, double &phi, double &dphi) {
+  static __device__ __forceinline__ void eval(double u, double, double &phi, double &dphi) {
     const double e = exp(-fabs(u));
     phi = fmin(u, 0.0) - log1p(e);
     dphi = (u >= 0.0 ? e : 1.0) / (1.0 + e);
   }
   // float: the hardware exponential and logarithm (1 ulp each).  1 + e is in (1, 2], so log(1 + e) has an ABSOLUTE error of
   // at most one float ulp of 1 -- of the size of the rounding of the sum the term is added to.
-  static __device__ __forceinline__ void eval(float u, float &phi, float &dphi) {
+  static __device__ __forceinline__ void eval(float u, float, float &phi, float &dphi) {
     const float e = nf_exp(-fabsf(u));
     const float s = 1.f + e;
     phi = fminf(u, 0.f) - nf_log(s);
     dphi = nf_fdiv(u >= 0.f ? e : 1.f, s);
   }
 };
+
+// the library's own transcendentals by element type (erfcx has no float overload to resolve to: it would promote to double)
+__device__ __forceinline__ float lp_exp(float x) { return expf(x); }
+__device__ __forceinline__ double lp_exp(double x) { return exp(x); }
+__device__ __forceinline__ float lp_log(float x) { return logf(x); }
+__device__ __forceinline__ double lp_log(double x) { return log(x); }
+__device__ __forceinline__ float lp_log1p(float x) { return log1pf(x); }
+__device__ __forceinline__ double lp_log1p(double x) { return log1p(x); }
+__device__ __forceinline__ float lp_erfc(float x) { return erfcf(x); }
+__device__ __forceinline__ double lp_erfc(double x) { return erfc(x); }
+__device__ __forceinline__ float lp_erfcx(float x) { return erfcxf(x); }
+__device__ __forceinline__ double lp_erfcx(double x) { return erfcx(x); }
+
+// log Phi(u) ; phi_N(u) / Phi(u)  (probit).  The left tail goes through the scaled complementary error function,
+// Phi(u) = exp(-u^2 / 2) erfcx(-u / sqrt 2) / 2, so neither the value nor the ratio meets 0 / 0 or log 0:
+//   u <  0   log Phi = -u^2 / 2 + log(erfcx(-u / sqrt 2) / 2),   phi' = sqrt(2 / pi) / erfcx(-u / sqrt 2)
+//   u >= 0   c = erfc(u / sqrt 2) / 2 in (0, 1/2],   log Phi = log1p(-c),   phi' = phi_N(u) / (1 - c)
+// The library's own exp / log / erfc / erfcx (no hardware approximations: the tails are the point of this form).
+struct PhiLogNormCdf {
+  template <class T>
+  static __device__ __forceinline__ void eval(T u, T, T &phi, T &dphi) {
+    const T RSQRT2 = (T)0.70710678118654752440, SQRT_2_PI = (T)0.79788456080286535588, RSQRT_2PI = (T)0.39894228040143267794;
+    if (u < (T)0) {
+      const T t = lp_erfcx(-u * RSQRT2);
+      phi = (T)-0.5 * u * u + lp_log((T)0.5 * t);
+      dphi = SQRT_2_PI / t;
+    } else {
+      const T c = (T)0.5 * lp_erfc(u * RSQRT2);
+      phi = lp_log1p(-c);
+      dphi = RSQRT_2PI * lp_exp((T)-0.5 * u * u) / ((T)1 - c);
+    }
+  }
+};
+
+// -exp(u) ; -exp(u)  (Poisson with the log link; the k u term is linear in y and sits in `lin` / par[1]).  The library's
+// expf: the hardware exponential's error grows with |u| (the rounding of u log2 e), and u reaches tens here.  Not clamped:
+// a predictor beyond exp's range gives -inf, and the step reports NF_ERR_NONFINITE.
+struct PhiNegExp {
+  template <class T>
+  static __device__ __forceinline__ void eval(T u, T, T &phi, T &dphi) {
+    phi = dphi = -lp_exp(u);
+  }
+};
+
+// -(nu + 1)/2 log1p(u^2 / nu) ; -(nu + 1) u / (nu + u^2)  (Student-t residual u, nu = par > 0)
+struct PhiStudent {
+  template <class T>
+  static __device__ __forceinline__ void eval(T u, T nu, T &phi, T &dphi) {
+    const T u2 = u * u;
+    phi = (T)-0.5 * (nu + (T)1) * lp_log1p(u2 / nu);
+    dphi = -(nu + (T)1) * u / (nu + u2);
+  }
+};
+
+// The row data of the generalised form, addressed inside the one buffer p0 = lin[d] | off[rows] | wt[rows] | par[2].
+template <class T>
+struct GlmRows {
+  const T *lin, *off, *wt, *par;
+  __device__ __forceinline__ GlmRows(const T *p0, int d, int rows) : lin(p0), off(p0 + d), wt(p0 + d + rows), par(p0 + d + 2 * (long)rows) {}
+};
+// one row's phi and phi' under its weight: exactly 0 for weight 0, by select
+template <class T>
+__device__ __forceinline__ void glm_weigh(T w, T &phi, T &dphi) {
+  phi = w == (T)0 ? (T)0 : w * phi;
+  dphi = w == (T)0 ? (T)0 : w * dphi;
+}
 
 // the constant and the prior weight of a checked target (host side, in double)
 struct LinpredConsts {
@@ -43,5 +119,6 @@ struct LinpredConsts {
 inline LinpredConsts linpred_consts(const nf_target *t, int d) {
   const double L2PI = 1.8378770664093453;
   if (t->kind == NF_TARGET_DENSEGAUSS) return {-0.5 * d * L2PI + t->s0, 0.0, (long)d};
+  if (target_is_glm(t->kind) && std::isinf(t->s1)) return {0.0, 0.0, (long)t->s0};  // flat prior: both prior terms vanish
   return {-0.5 * d * (L2PI + 2.0 * std::log(t->s1)), 1.0 / (t->s1 * t->s1), (long)t->s0};
 }

@@ -1,9 +1,15 @@
-// nf_linpred.hip -- the linear-predictor targets (NF_TARGET_DENSEGAUSS, NF_TARGET_LOGREG; gfx950):
-//     log p(y) = c + sum_i phi(u_i) - pw |y|^2 / 2,   u = A (y - mu),   grad = A' phi'(u) - pw y
+// nf_linpred.hip -- the linear-predictor targets (NF_TARGET_DENSEGAUSS, NF_TARGET_LOGREG, NF_TARGET_GLM_*; gfx950):
+//     centred      log p(y) = c + sum_i phi(u_i) - pw |y|^2 / 2,   u = A (y - mu),   grad = A' phi'(u) - pw y
+//     generalised  log p(y) = par[1] + c + sum_i wt_i phi(u_i; par[0]) + lin . y - pw |y|^2 / 2,   u = A y + off,
+//                  grad = A' (wt o phi'(u)) + lin - pw y
 // with A [rows x d] row-major: MvNormal(mu, Sigma) through W = inv(chol(Sigma)), Bayesian logistic regression through the
-// label-folded data matrix.  Two kernels, each templated on the row function phi (nf_linpred.h):
-//   k_target_linpred_tiled  Float32, tiled layout, drop-in for k_target_tiled: both GEMMs on v_mfma_f32_32x32x2_f32
-//   k_target_linpred        flat layout, float / double, drop-in for k_target: vector pipe (Float64 flows, nf_target_logp)
+// label-folded data matrix, and the regression posteriors with exposures, trial counts, subsampling weights and a family
+// parameter through the generalised form.  Two kernel bodies, each templated on the row function phi and on the form
+// (nf_linpred.h); the centred instantiations compile every line of the row data away:
+//   lp_tiled_body  Float32, tiled layout, drop-in for k_target_tiled: both GEMMs on v_mfma_f32_32x32x2_f32
+//                  (k_target_linpred_tiled: centred, k_target_glm_tiled: generalised)
+//   lp_flat_body   flat layout, float / double, drop-in for k_target: vector pipe (Float64 flows, nf_target_logp)
+//                  (k_target_linpred, k_target_glm)
 #include "nf_common.h"
 #include "nf_linpred.h"
 
@@ -21,6 +27,10 @@
 //                                                 operand IS accumulator register t of GEMM 1 (the register chaining of
 //                                                 nf_mfma.h), so U never passes through LDS or a shuffle
 // Rows >= rows of the last block are masked after phi: a zero row of A gives u = 0, and phi(0) = log 1/2 for LOGREG.
+// Generalised form: the tile is staged uncentred; a lane's 16 offsets and 16 weights of a row block are requested with the
+// block's staging loads (before the first of them, so they are in by the time the image is); the offsets ARE the initial
+// accumulator of GEMM 1, the weights multiply phi and phi' in the accumulator registers (0 by select), and rows >= rows
+// read off = 0, wt = 0, which masks them.  lin enters the epilogue beside pw y.
 // Feature chunks: the image holds at most 128 features of the 32 rows (16.5 KB per wave); a wider target (DB = 8) runs
 // GEMM 1 chunk by chunk and stages each chunk a second time for GEMM 2.
 #define LP_BLOCK 256
@@ -58,19 +68,21 @@ __device__ __forceinline__ void lp_stage(float *__restrict__ img, const float *_
   }
 }
 
-template <int DB, class PHI>
-__global__ __launch_bounds__(LP_BLOCK) void k_target_linpred_tiled(int d, int rows, long N, const float *__restrict__ yt,
-                                                                   const float *__restrict__ mu, const float *__restrict__ A,
-                                                                   float c0, float pw, const float *__restrict__ logq,
-                                                                   const float *__restrict__ ladj, float *__restrict__ gt,
-                                                                   float gscale, float *__restrict__ elbos_out,
-                                                                   double *__restrict__ partial, double pscale) {
+// p0: the shift mu[d] (or NULL) of the centred form, the row-data buffer of the generalised one
+template <int DB, class PHI, bool GLM>
+__device__ __forceinline__ void lp_tiled_body(int d, int rows, long N, const float *__restrict__ yt, const float *__restrict__ p0,
+                                              const float *__restrict__ A, float c0, float pw, const float *__restrict__ logq,
+                                              const float *__restrict__ ladj, float *__restrict__ gt, float gscale,
+                                              float *__restrict__ elbos_out, double *__restrict__ partial, double pscale) {
   using G = LpGeo<DB>;
+  const GlmRows<float> rd(p0, d, rows);
+  const float par0 = GLM ? rd.par[0] : 0.f;
   extern __shared__ float lp_sm[];
   float *sY = lp_sm;
   float *sA = lp_sm + G::YT;
   float *sL = sA + LP_WAVES * G::IMG;  // [wave][lane] log-p partial sums
   __shared__ float red[LP_BLOCK / 32][32];
+  __shared__ float redl[GLM ? LP_BLOCK / 32 : 1][32];  // lin . y partial sums (unused, and removed, in the centred form)
   __shared__ double sm[LP_WAVES];
   const long tile = blockIdx.x;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l31 = lane & 31, hi = lane >> 5;
@@ -82,7 +94,10 @@ __global__ __launch_bounds__(LP_BLOCK) void k_target_linpred_tiled(int d, int ro
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
       const int idx = threadIdx.x + k * LP_BLOCK, f = idx >> 5, s = idx & 31;
-      yv[k] = (f < d && tile * 32 + s < N) ? yb[idx] - (mu ? mu[f] : 0.f) : 0.f;
+      if (GLM)
+        yv[k] = (f < d && tile * 32 + s < N) ? yb[idx] : 0.f;
+      else
+        yv[k] = (f < d && tile * 32 + s < N) ? yb[idx] - (p0 ? p0[f] : 0.f) : 0.f;
     }
 #pragma unroll
     for (int k = 0; k < PER; ++k) sY[threadIdx.x + k * LP_BLOCK] = yv[k];
@@ -100,8 +115,13 @@ __global__ __launch_bounds__(LP_BLOCK) void k_target_linpred_tiled(int d, int ro
   for (int rb = wave; rb < nrb; rb += LP_WAVES) {
     const int i0 = rb * 32;
     f32x16 U;
+    float wt[16];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) U[r] = 0.f;
+    for (int r = 0; r < 16; ++r) {
+      const int i = i0 + nf_row(r, hi);
+      U[r] = (GLM && i < rows) ? rd.off[i] : 0.f;
+      wt[r] = (GLM && i < rows) ? rd.wt[i] : 0.f;
+    }
 #pragma unroll
     for (int ch = 0; ch < G::NCH; ++ch) {
       const int f0 = ch * G::CW;
@@ -124,8 +144,11 @@ __global__ __launch_bounds__(LP_BLOCK) void k_target_linpred_tiled(int d, int ro
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       float ph, dp;
-      PHI::eval(U[r], ph, dp);
-      if (ragged && i0 + nf_row(r, hi) >= rows) ph = 0.f, dp = 0.f;
+      PHI::eval(U[r], par0, ph, dp);
+      if (GLM)
+        glm_weigh(wt[r], ph, dp);
+      else if (ragged && i0 + nf_row(r, hi) >= rows)
+        ph = 0.f, dp = 0.f;
       lp += ph;
       U[r] = dp;
     }
@@ -173,23 +196,29 @@ __global__ __launch_bounds__(LP_BLOCK) void k_target_linpred_tiled(int d, int ro
   const int s = threadIdx.x & 31, q = threadIdx.x >> 5;
   const long j = tile * 32 + s;
   const bool valid = j < N;
-  float yy = 0.f;
+  float yy = 0.f, ly = 0.f;
   {
     constexpr int PER = 4 * DB;  // features per thread: q, q + 8, ...
-    float yv[PER];
+    float yv[PER], lv[PER];
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
       const int i = q + k * (LP_BLOCK / 32);
       yv[k] = (valid && i < d) ? yb[i * 32 + s] : 0.f;
+      lv[k] = (GLM && i < d) ? rd.lin[i] : 0.f;
     }
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
       const int i = q + k * (LP_BLOCK / 32);
       yy += yv[k] * yv[k];
-      if (gt && i < d) gt[tile * d * 32 + i * 32 + s] = valid ? gscale * (sY[i * 32 + s] - pw * yv[k]) : 0.f;
+      if (GLM) {
+        ly += lv[k] * yv[k];
+        if (gt && i < d) gt[tile * d * 32 + i * 32 + s] = valid ? gscale * (sY[i * 32 + s] + lv[k] - pw * yv[k]) : 0.f;
+      } else if (gt && i < d)
+        gt[tile * d * 32 + i * 32 + s] = valid ? gscale * (sY[i * 32 + s] - pw * yv[k]) : 0.f;
     }
   }
   red[q][s] = yy;
+  if (GLM) redl[q][s] = ly;
   __syncthreads();
   double contrib = 0.0;
   if (q == 0 && valid) {
@@ -199,6 +228,12 @@ __global__ __launch_bounds__(LP_BLOCK) void k_target_linpred_tiled(int d, int ro
 #pragma unroll
     for (int w = 0; w < LP_WAVES; ++w) l += sL[w * 64 + s] + sL[w * 64 + 32 + s];
     float e = c0 + l - 0.5f * pw * t;
+    if (GLM) {
+      float tl = 0.f;
+#pragma unroll
+      for (int k = 0; k < LP_BLOCK / 32; ++k) tl += redl[k][s];
+      e = (rd.par[1] + c0) + l + tl - 0.5f * pw * t;
+    }
     if (logq) e -= logq[j];
     if (ladj) e += ladj[j];
     if (elbos_out) elbos_out[j] = e;
@@ -211,6 +246,25 @@ __global__ __launch_bounds__(LP_BLOCK) void k_target_linpred_tiled(int d, int ro
     __syncthreads();
     if (threadIdx.x == 0) partial[blockIdx.x] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
   }
+}
+
+template <int DB, class PHI>
+__global__ __launch_bounds__(LP_BLOCK) void k_target_linpred_tiled(int d, int rows, long N, const float *__restrict__ yt,
+                                                                   const float *__restrict__ mu, const float *__restrict__ A,
+                                                                   float c0, float pw, const float *__restrict__ logq,
+                                                                   const float *__restrict__ ladj, float *__restrict__ gt,
+                                                                   float gscale, float *__restrict__ elbos_out,
+                                                                   double *__restrict__ partial, double pscale) {
+  lp_tiled_body<DB, PHI, false>(d, rows, N, yt, mu, A, c0, pw, logq, ladj, gt, gscale, elbos_out, partial, pscale);
+}
+template <int DB, class PHI>
+__global__ __launch_bounds__(LP_BLOCK) void k_target_glm_tiled(int d, int rows, long N, const float *__restrict__ yt,
+                                                               const float *__restrict__ rowdata, const float *__restrict__ A,
+                                                               float c0, float pw, const float *__restrict__ logq,
+                                                               const float *__restrict__ ladj, float *__restrict__ gt,
+                                                               float gscale, float *__restrict__ elbos_out,
+                                                               double *__restrict__ partial, double pscale) {
+  lp_tiled_body<DB, PHI, true>(d, rows, N, yt, rowdata, A, c0, pw, logq, ladj, gt, gscale, elbos_out, partial, pscale);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -233,13 +287,13 @@ __device__ __forceinline__ T lp_group16_sum(T v) {
   return v;
 }
 
-template <class T, class PHI>
-__global__ __launch_bounds__(LP_BLOCK) void k_target_linpred(int d, int rows, long N, const T *__restrict__ y,
-                                                             const T *__restrict__ mu, const T *__restrict__ A, T c0, T pw,
-                                                             const T *__restrict__ logq, const T *__restrict__ ladj,
-                                                             T *__restrict__ logp_out, T *__restrict__ grad_out, T gscale,
-                                                             T *__restrict__ elbos_out, double *__restrict__ partial,
-                                                             double pscale) {
+template <class T, class PHI, bool GLM>
+__device__ __forceinline__ void lp_flat_body(int d, int rows, long N, const T *__restrict__ y, const T *__restrict__ p0,
+                                             const T *__restrict__ A, T c0, T pw, const T *__restrict__ logq,
+                                             const T *__restrict__ ladj, T *__restrict__ logp_out, T *__restrict__ grad_out,
+                                             T gscale, T *__restrict__ elbos_out, double *__restrict__ partial, double pscale) {
+  const GlmRows<T> rd(p0, d, rows);
+  const T par0 = GLM ? rd.par[0] : (T)0;
   extern __shared__ double lpf_sm[];
   T *sY = (T *)lpf_sm;                  // [sample][d + 1] centred
   T *sA = sY + LPF_SPB * (d + 1);       // [row][d + 1]
@@ -252,24 +306,32 @@ __global__ __launch_bounds__(LP_BLOCK) void k_target_linpred(int d, int rows, lo
   for (int idx = threadIdx.x; idx < LPF_SPB * d; idx += LP_BLOCK) {
     const int si = idx / d, f = idx - si * d;
     const long jj = (long)blockIdx.x * LPF_SPB + si;
-    sY[si * S + f] = jj < N ? y[jj * d + f] - (mu ? mu[f] : (T)0) : (T)0;
+    if (GLM)
+      sY[si * S + f] = jj < N ? y[jj * d + f] : (T)0;
+    else
+      sY[si * S + f] = jj < N ? y[jj * d + f] - (p0 ? p0[f] : (T)0) : (T)0;
   }
   T g[LPF_MAXD / LPF_LANES];
 #pragma unroll
   for (int k = 0; k < LPF_MAXD / LPF_LANES; ++k) g[k] = (T)0;
   T lp = 0;
   for (int i0 = 0; i0 < rows; i0 += LPF_RB) {
+    const bool live = i0 + q < rows;
+    const T ov = (GLM && live) ? rd.off[i0 + q] : (T)0, wv = (GLM && live) ? rd.wt[i0 + q] : (T)0;  // (requested with the block of A)
     __syncthreads();  // the tile (first pass); the previous block's readers
     for (int idx = threadIdx.x; idx < LPF_RB * d; idx += LP_BLOCK) {
       const int row = idx / d, f = idx - row * d;
       sA[row * S + f] = i0 + row < rows ? A[(long)(i0 + row) * d + f] : (T)0;
     }
     __syncthreads();
-    T u = 0;
+    T u = ov;
     for (int f = 0; f < d; ++f) u += sA[q * S + f] * sY[sl * S + f];
     T ph, dp;
-    PHI::eval(u, ph, dp);
-    if (i0 + q >= rows) ph = (T)0, dp = (T)0;
+    PHI::eval(u, par0, ph, dp);
+    if (GLM)
+      glm_weigh(wv, ph, dp);
+    else if (!live)
+      ph = (T)0, dp = (T)0;
     lp += ph;
     sD[sl * (LPF_RB + 1) + q] = dp;
     __syncthreads();
@@ -284,21 +346,28 @@ __global__ __launch_bounds__(LP_BLOCK) void k_target_linpred(int d, int rows, lo
       }
     }
   }
-  T yy = 0;
+  T yy = 0, ly = 0;
 #pragma unroll
   for (int k = 0; k < LPF_MAXD / LPF_LANES; ++k) {
     const int f = k * LPF_LANES + q;
     if (f < d && valid) {
       const T yv = y[j * d + f];
       yy += yv * yv;
-      if (grad_out) grad_out[j * d + f] = gscale * (g[k] - pw * yv);
+      if (GLM) {
+        const T lv = rd.lin[f];
+        ly += lv * yv;
+        if (grad_out) grad_out[j * d + f] = gscale * (g[k] + lv - pw * yv);
+      } else if (grad_out)
+        grad_out[j * d + f] = gscale * (g[k] - pw * yv);
     }
   }
   lp = lp_group16_sum(lp);
   yy = lp_group16_sum(yy);
+  if (GLM) ly = lp_group16_sum(ly);
   double contrib = 0.0;
   if (valid && q == 0) {
     T e = c0 + lp - (T)0.5 * pw * yy;
+    if (GLM) e = (rd.par[1] + c0) + lp + ly - (T)0.5 * pw * yy;
     if (logp_out) logp_out[j] = e;
     if (logq) e -= logq[j];
     if (ladj) e += ladj[j];
@@ -314,58 +383,104 @@ __global__ __launch_bounds__(LP_BLOCK) void k_target_linpred(int d, int rows, lo
   }
 }
 
+template <class T, class PHI>
+__global__ __launch_bounds__(LP_BLOCK) void k_target_linpred(int d, int rows, long N, const T *__restrict__ y,
+                                                             const T *__restrict__ mu, const T *__restrict__ A, T c0, T pw,
+                                                             const T *__restrict__ logq, const T *__restrict__ ladj,
+                                                             T *__restrict__ logp_out, T *__restrict__ grad_out, T gscale,
+                                                             T *__restrict__ elbos_out, double *__restrict__ partial,
+                                                             double pscale) {
+  lp_flat_body<T, PHI, false>(d, rows, N, y, mu, A, c0, pw, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
+}
+template <class T, class PHI>
+__global__ __launch_bounds__(LP_BLOCK) void k_target_glm(int d, int rows, long N, const T *__restrict__ y,
+                                                         const T *__restrict__ rowdata, const T *__restrict__ A, T c0, T pw,
+                                                         const T *__restrict__ logq, const T *__restrict__ ladj,
+                                                         T *__restrict__ logp_out, T *__restrict__ grad_out, T gscale,
+                                                         T *__restrict__ elbos_out, double *__restrict__ partial,
+                                                         double pscale) {
+  lp_flat_body<T, PHI, true>(d, rows, N, y, rowdata, A, c0, pw, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // launchers (called by nf_launch_target / nf_launch_target_tiled after nf_target_check)
 // ---------------------------------------------------------------------------------------------------------------------
-template <int DB, class PHI>
+// the kernel of a form (only the one asked for is instantiated)
+template <int DB, class PHI, bool GLM>
+static auto tiled_kernel() {
+  if constexpr (GLM)
+    return &k_target_glm_tiled<DB, PHI>;
+  else
+    return &k_target_linpred_tiled<DB, PHI>;
+}
+template <class T, class PHI, bool GLM>
+static auto flat_kernel() {
+  if constexpr (GLM)
+    return &k_target_glm<T, PHI>;
+  else
+    return &k_target_linpred<T, PHI>;
+}
+
+template <int DB, class PHI, bool GLM>
 static int launch_tiled(nf_ctx *ctx, const nf_target *t, int d, long N, const float *yt, const float *logq, const float *ladj,
                         float *gt, double gscale, float *elbos_out, double *partial, double pscale) {
   const size_t lds = (size_t)LpGeo<DB>::FLOATS * sizeof(float);
+  const auto kern = tiled_kernel<DB, PHI, GLM>();
   static AttrOnce attr_once;  // once per device
   NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    NF_HIP(hipFuncSetAttribute((const void *)k_target_linpred_tiled<DB, PHI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    NF_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     return NF_OK;
   }));
   const LinpredConsts k = linpred_consts(t, d);
   ProfScope ps(ctx, "target_linpred");
-  hipLaunchKernelGGL((k_target_linpred_tiled<DB, PHI>), dim3((unsigned)((N + 31) / 32)), dim3(LP_BLOCK), lds, ctx->stream, d,
+  hipLaunchKernelGGL(kern, dim3((unsigned)((N + 31) / 32)), dim3(LP_BLOCK), lds, ctx->stream, d,
                      (int)k.rows, N, yt, (const float *)t->p0, (const float *)t->p1, (float)k.c, (float)k.pw, logq, ladj, gt,
                      (float)gscale, elbos_out, partial, pscale);
   return (int)hipGetLastError();
 }
 
-template <class PHI>
+template <class PHI, bool GLM>
 static int launch_tiled_phi(nf_ctx *ctx, const nf_target *t, int d, long N, const float *yt, const float *logq,
                             const float *ladj, float *gt, double gscale, float *elbos_out, double *partial, double pscale) {
-  if (d <= 32) return launch_tiled<1, PHI>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
-  if (d <= 64) return launch_tiled<2, PHI>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
-  if (d <= 128) return launch_tiled<4, PHI>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
-  return launch_tiled<8, PHI>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
+  if (d <= 32) return launch_tiled<1, PHI, GLM>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
+  if (d <= 64) return launch_tiled<2, PHI, GLM>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
+  if (d <= 128) return launch_tiled<4, PHI, GLM>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
+  return launch_tiled<8, PHI, GLM>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
 }
 
 int nf_launch_target_linpred_tiled(nf_ctx *ctx, const nf_target *t, int d, long N, const float *yt, const float *logq,
                                    const float *ladj, float *gt, double gscale, float *elbos_out, double *partial,
                                    double pscale) {
   if (d > LPF_MAXD) return NF_ERR_UNSUPPORTED;
-  if (t->kind == NF_TARGET_DENSEGAUSS)
-    return launch_tiled_phi<PhiHalfSquare>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
-  return launch_tiled_phi<PhiLogSigmoid>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
+#define LP_TILED(PHI, GLM) launch_tiled_phi<PHI, GLM>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale)
+  switch (t->kind) {
+    case NF_TARGET_DENSEGAUSS: return LP_TILED(PhiHalfSquare, false);
+    case NF_TARGET_LOGREG: return LP_TILED(PhiLogSigmoid, false);
+    case NF_TARGET_GLM_LOGIT: return LP_TILED(PhiLogSigmoid, true);
+    case NF_TARGET_GLM_PROBIT: return LP_TILED(PhiLogNormCdf, true);
+    case NF_TARGET_GLM_POISSON: return LP_TILED(PhiNegExp, true);
+    case NF_TARGET_GLM_STUDENT: return LP_TILED(PhiStudent, true);
+    case NF_TARGET_GLM_NORMAL: return LP_TILED(PhiHalfSquare, true);
+    default: return NF_ERR_ARG;
+  }
+#undef LP_TILED
 }
 
-template <class T, class PHI>
+template <class T, class PHI, bool GLM>
 static int launch_flat(nf_ctx *ctx, const nf_target *t, int d, long N, const void *y, const void *logq, const void *ladj,
                        void *logp_out, void *grad_out, double gscale, void *elbos_out, double *partial, double pscale) {
   const size_t lds = (size_t)((LPF_SPB + LPF_RB) * (d + 1) + LPF_SPB * (LPF_RB + 1)) * sizeof(T);
+  const auto kern = flat_kernel<T, PHI, GLM>();
   static AttrOnce attr_once;
   NF_TRY(attr_once.run(ctx->device, [&]() -> int {
     const size_t most = (size_t)((LPF_SPB + LPF_RB) * (LPF_MAXD + 1) + LPF_SPB * (LPF_RB + 1)) * sizeof(T);
-    NF_HIP(hipFuncSetAttribute((const void *)k_target_linpred<T, PHI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)most));
+    NF_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)most));
     return NF_OK;
   }));
   const LinpredConsts k = linpred_consts(t, d);
   ProfScope ps(ctx, "target_linpred");
   const long nb = (N + LPF_SPB - 1) / LPF_SPB;
-  hipLaunchKernelGGL((k_target_linpred<T, PHI>), dim3((unsigned)nb), dim3(LP_BLOCK), lds, ctx->stream, d, (int)k.rows, N,
+  hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(LP_BLOCK), lds, ctx->stream, d, (int)k.rows, N,
                      (const T *)y, (const T *)t->p0, (const T *)t->p1, (T)k.c, (T)k.pw, (const T *)logq, (const T *)ladj,
                      (T *)logp_out, (T *)grad_out, (T)gscale, (T *)elbos_out, partial, pscale);
   return (int)hipGetLastError();
@@ -375,10 +490,19 @@ int nf_launch_target_linpred(nf_ctx *ctx, int dtype, const nf_target *t, int d, 
                              const void *ladj, void *logp_out, void *grad_out, double gscale, void *elbos_out,
                              double *partial, double pscale) {
   if (d > LPF_MAXD) return NF_ERR_UNSUPPORTED;
-  const bool gauss = t->kind == NF_TARGET_DENSEGAUSS;
-  if (dtype == NF_DTYPE_F32)
-    return gauss ? launch_flat<float, PhiHalfSquare>(ctx, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale)
-                 : launch_flat<float, PhiLogSigmoid>(ctx, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
-  return gauss ? launch_flat<double, PhiHalfSquare>(ctx, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale)
-               : launch_flat<double, PhiLogSigmoid>(ctx, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
+#define LP_FLAT(PHI, GLM)                                                                                                        \
+  (dtype == NF_DTYPE_F32                                                                                                       \
+       ? launch_flat<float, PHI, GLM>(ctx, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale)     \
+       : launch_flat<double, PHI, GLM>(ctx, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale))
+  switch (t->kind) {
+    case NF_TARGET_DENSEGAUSS: return LP_FLAT(PhiHalfSquare, false);
+    case NF_TARGET_LOGREG: return LP_FLAT(PhiLogSigmoid, false);
+    case NF_TARGET_GLM_LOGIT: return LP_FLAT(PhiLogSigmoid, true);
+    case NF_TARGET_GLM_PROBIT: return LP_FLAT(PhiLogNormCdf, true);
+    case NF_TARGET_GLM_POISSON: return LP_FLAT(PhiNegExp, true);
+    case NF_TARGET_GLM_STUDENT: return LP_FLAT(PhiStudent, true);
+    case NF_TARGET_GLM_NORMAL: return LP_FLAT(PhiHalfSquare, true);
+    default: return NF_ERR_ARG;
+  }
+#undef LP_FLAT
 }

@@ -80,7 +80,12 @@ __host__ __device__ inline bool target_needs_d2(int kind) { return kind == NF_TA
 // The linear-predictor kinds (NF_TARGET_DENSEGAUSS, NF_TARGET_LOGREG) couple every feature with every other through a
 // matrix: target_term cannot express them.  They have kernels of their own (nf_linpred.hip), reached through
 // nf_launch_target / nf_launch_target_tiled; every path that evaluates target_term inside a fused kernel refuses them.
-__host__ __device__ inline bool target_is_linpred(int kind) { return kind == NF_TARGET_DENSEGAUSS || kind == NF_TARGET_LOGREG; }
+// The generalised kinds (NF_TARGET_GLM_LOGIT .. NF_TARGET_GLM_NORMAL: row offsets, row weights, a linear term and a family
+// parameter) are linear-predictor kinds served by the same two kernels.
+__host__ __device__ inline bool target_is_glm(int kind) { return kind >= NF_TARGET_GLM_LOGIT && kind <= NF_TARGET_GLM_NORMAL; }
+__host__ __device__ inline bool target_is_linpred(int kind) {
+  return kind == NF_TARGET_DENSEGAUSS || kind == NF_TARGET_LOGREG || target_is_glm(kind);
+}
 // The Gaussian mixture (NF_TARGET_GAUSSMIX, nf_mixture.hip) is routed like them: a kernel of its own behind
 // nf_launch_target / nf_launch_target_tiled, refused wherever target_term would have to evaluate it.
 __host__ __device__ inline bool target_has_own_kernel(int kind) { return target_is_linpred(kind) || kind == NF_TARGET_GAUSSMIX; }

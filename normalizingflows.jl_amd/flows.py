@@ -572,7 +572,7 @@ class _LinpredLogp(torch.autograd.Function):
 
 
 class _LinpredTarget:
-    """What MvNormalTarget and LogisticRegressionTarget share: the matrix `A` [rows, d] and the optional shift `mu`,
+    """What MvNormalTarget, LogisticRegressionTarget, MixtureTarget and the GLM targets share: the matrix `A` [rows, d] and the optional shift `mu`,
     kept alive for the descriptor's device pointers, and the checks DiagGaussTarget makes (the ABI reads p0 / p1 untyped)."""
 
     def check_compatible(self, dtype, device, d=None):
@@ -693,6 +693,167 @@ class MixtureTarget(_LinpredTarget):
         self.A = W.reshape(self.K * d, d).to(mus.dtype).to(mus.device).contiguous()
         self.p0 = torch.cat([mbar, b.reshape(-1), c]).to(mus.dtype).to(mus.device).contiguous()
         self.c = Target(_lib.NF_TARGET_GAUSSMIX, self.p0.data_ptr(), self.A.data_ptr(), float(self.K), 0.0)
+
+
+_GLM_KINDS = {"logit": _lib.NF_TARGET_GLM_LOGIT, "probit": _lib.NF_TARGET_GLM_PROBIT, "poisson": _lib.NF_TARGET_GLM_POISSON,
+              "student": _lib.NF_TARGET_GLM_STUDENT, "normal": _lib.NF_TARGET_GLM_NORMAL}
+
+
+def _glm_matrix(name, X):
+    if not isinstance(X, torch.Tensor) or X.dim() != 2 or X.shape[0] < 1 or X.shape[1] < 1 or X.dtype not in (torch.float32, torch.float64):
+        raise NFHipError(f"{name}: the data matrix must be a Float32 or Float64 tensor [rows, d] with rows >= 1 and d >= 1")
+    X64 = X.detach().to("cpu", torch.float64)
+    if not bool(torch.isfinite(X64).all()):
+        raise NFHipError(f"{name}: the data matrix must be finite")
+    return X64
+
+
+def _glm_vector(name, what, v, like, n, default=None, nonneg=False, positive=False):
+    """a per-row (or per-feature) vector as float64 on the host: `like`'s element type (integer tensors are taken as counts /
+    labels), `like`'s device, length n, finite"""
+    if v is None:
+        return torch.full((n,), float(default), dtype=torch.float64)
+    if not isinstance(v, torch.Tensor) or v.dim() != 1 or v.numel() != n:
+        raise NFHipError(f"{name}: {what} must be a vector of length {n}")
+    if v.device != like.device or (v.dtype.is_floating_point and v.dtype != like.dtype) or v.dtype.is_complex or v.dtype == torch.bool:
+        raise NFHipError(f"{name}: {what} must be on the data matrix's device and of its element type (or an integer tensor)")
+    v64 = v.detach().to("cpu", torch.float64)
+    if not bool(torch.isfinite(v64).all()):
+        raise NFHipError(f"{name}: {what} must be finite")
+    if (nonneg and bool((v64 < 0).any())) or (positive and bool((v64 <= 0).any())):
+        raise NFHipError(f"{name}: {what} must be {'> 0' if positive else '>= 0'}")
+    return v64
+
+
+def _glm_scalar(name, what, x, positive=True, allow_inf=False):
+    x = float(x)
+    if math.isnan(x) or (math.isinf(x) and not (allow_inf and x > 0)) or (positive and not x > 0):
+        raise NFHipError(f"{name}: {what} must be a finite number" + (" > 0" if positive else "") + (" (or +inf)" if allow_inf else ""))
+    return x
+
+
+class GLMTarget(_LinpredTarget):
+    """The generalised linear-predictor target (NF_TARGET_GLM_*), with u = A z + offset:
+        logp(z) = const + sum_i weights_i phi(u_i; param) + lin . z - |z|^2 / (2 prior_sigma^2) - d/2 log(2 pi prior_sigma^2)
+    family: "logit" (phi = log sigmoid), "probit" (log Phi), "poisson" (-exp), "student" (-(nu+1)/2 log1p(u^2/nu), nu = param)
+    or "normal" (-u^2/2).  A [rows, d]; offset, weights (>= 0; 0 drops the row exactly) per row; lin per feature; all of A's
+    element type and device.  prior_sigma = math.inf is the flat prior.  The device reads `A` and ONE buffer
+    `p0` = lin | offset | weights | (param, const); both are kept alive here."""
+
+    def __init__(self, family, A, offset=None, weights=None, lin=None, const=0.0, param=0.0, prior_sigma=1.0, _name="GLMTarget"):
+        if family not in _GLM_KINDS:
+            raise NFHipError(f"{_name}: family must be one of {sorted(_GLM_KINDS)}")
+        A64 = _glm_matrix(_name, A)
+        rows, d = A64.shape
+        off = _glm_vector(_name, "offset", offset, A, rows, 0.0)
+        wt = _glm_vector(_name, "weights", weights, A, rows, 1.0, nonneg=True)
+        ln = _glm_vector(_name, "lin", lin, A, d, 0.0)
+        const = _glm_scalar(_name, "const", const, positive=False)
+        param = _glm_scalar(_name, "param", param, positive=family == "student")
+        self.prior_sigma = _glm_scalar(_name, "prior_sigma", prior_sigma, allow_inf=True)
+        self.family, self.d, self.rows, self.param, self.const = family, d, rows, param, const
+        self.A = A.detach().contiguous()
+        self.p0 = torch.cat([ln, off, wt, torch.tensor([param, const], dtype=torch.float64)]).to(A.dtype).to(A.device).contiguous()
+        self.c = Target(_GLM_KINDS[family], self.p0.data_ptr(), self.A.data_ptr(), float(rows), self.prior_sigma)
+
+
+
+class PoissonRegressionTarget(GLMTarget):
+    """Posterior of Poisson regression (log link) over the weights z: counts k_i ~ Poisson(exposure_i exp(x_i . z)), prior
+    N(0, prior_sigma^2 I), each row's log-likelihood under weight w_i.  Folds to the "poisson" family with A = X,
+    offset = log exposure, lin = sum_i w_i k_i x_i and const = sum_i w_i (k_i offset_i - lgamma(k_i + 1))."""
+
+    def __init__(self, X, counts, exposure=None, weights=None, prior_sigma=1.0):
+        nm = "PoissonRegressionTarget"
+        X64 = _glm_matrix(nm, X)
+        n = X64.shape[0]
+        k = _glm_vector(nm, "counts", counts, X, n, nonneg=True)
+        if bool((k != torch.round(k)).any()):
+            raise NFHipError(f"{nm}: counts must be integers")
+        off = torch.log(_glm_vector(nm, "exposure", exposure, X, n, 1.0, positive=True))
+        w = _glm_vector(nm, "weights", weights, X, n, 1.0, nonneg=True)
+        lin = (w * k) @ X64
+        const = float((w * (k * off - torch.lgamma(k + 1.0))).sum())
+        to = lambda t: t.to(X.dtype).to(X.device)
+        super().__init__("poisson", X, to(off), to(w), to(lin), const, 0.0, prior_sigma, _name=nm)
+
+
+class BinomialRegressionTarget(GLMTarget):
+    """Posterior of binomial (logit-link) regression: successes k_i ~ Binomial(trials n_i, sigmoid(x_i . z + offset_i)).
+    With eta = x . z + offset:  k log sigmoid(eta) + (n - k) log sigmoid(-eta) = k eta + n log sigmoid(-eta), so it folds
+    to the "logit" family with A = -X, offset -> -offset, weights -> w n, lin = sum_i w_i k_i x_i and
+    const = sum_i w_i (k_i offset_i + log C(n_i, k_i))."""
+
+    def __init__(self, X, successes, trials, offset=None, weights=None, prior_sigma=1.0):
+        nm = "BinomialRegressionTarget"
+        X64 = _glm_matrix(nm, X)
+        n = X64.shape[0]
+        k = _glm_vector(nm, "successes", successes, X, n, nonneg=True)
+        nt = _glm_vector(nm, "trials", trials, X, n, nonneg=True)
+        if bool((k != torch.round(k)).any()) or bool((nt != torch.round(nt)).any()) or bool((k > nt).any()):
+            raise NFHipError(f"{nm}: successes and trials must be integers with 0 <= successes <= trials")
+        off = _glm_vector(nm, "offset", offset, X, n, 0.0)
+        w = _glm_vector(nm, "weights", weights, X, n, 1.0, nonneg=True)
+        lin = (w * k) @ X64
+        logc = torch.lgamma(nt + 1.0) - torch.lgamma(k + 1.0) - torch.lgamma(nt - k + 1.0)
+        const = float((w * (k * off + logc)).sum())
+        to = lambda t: t.to(X.dtype).to(X.device)
+        super().__init__("logit", to(-X64), to(-off), to(w * nt), to(lin), const, 0.0, prior_sigma, _name=nm)
+
+
+class ProbitRegressionTarget(GLMTarget):
+    """Posterior of probit regression: P(t_i = +1) = Phi(x_i . z + offset_i); labels as LogisticRegressionTarget takes them
+    ({-1, +1} or {0, 1}).  The labels are folded into the rows: A_i = t_i x_i, offset_i -> t_i offset_i."""
+
+    def __init__(self, X, t, offset=None, weights=None, prior_sigma=1.0):
+        nm = "ProbitRegressionTarget"
+        X64 = _glm_matrix(nm, X)
+        n = X64.shape[0]
+        tv = _glm_vector(nm, "labels", t, X, n)
+        if bool(((tv == 1) | (tv == -1)).all()):
+            sign = tv
+        elif bool(((tv == 0) | (tv == 1)).all()):
+            sign = 2.0 * tv - 1.0
+        else:
+            raise NFHipError(f"{nm}: labels must all be in {{-1, +1}} or all in {{0, 1}}")
+        off = _glm_vector(nm, "offset", offset, X, n, 0.0)
+        w = _glm_vector(nm, "weights", weights, X, n, 1.0, nonneg=True)
+        to = lambda t_: t_.to(X.dtype).to(X.device)
+        super().__init__("probit", to(X64 * sign[:, None]), to(sign * off), to(w), None, 0.0, 0.0, prior_sigma, _name=nm)
+
+
+class RobustRegressionTarget(GLMTarget):
+    """Posterior of linear regression with Student-t noise: (y_i - x_i . z) / scale ~ t_nu.  Folds to the "student" family
+    with A = X / scale, offset = -y / scale, param = nu and
+    const = sum_i w_i (lgamma((nu+1)/2) - lgamma(nu/2) - log(nu pi)/2 - log scale)."""
+
+    def __init__(self, X, y, nu, scale, weights=None, prior_sigma=1.0):
+        nm = "RobustRegressionTarget"
+        X64 = _glm_matrix(nm, X)
+        n = X64.shape[0]
+        yv = _glm_vector(nm, "y", y, X, n)
+        nu = _glm_scalar(nm, "nu", nu)
+        scale = _glm_scalar(nm, "scale", scale)
+        w = _glm_vector(nm, "weights", weights, X, n, 1.0, nonneg=True)
+        const = float(w.sum()) * (math.lgamma(0.5 * (nu + 1.0)) - math.lgamma(0.5 * nu) - 0.5 * math.log(nu * math.pi) - math.log(scale))
+        to = lambda t: t.to(X.dtype).to(X.device)
+        super().__init__("student", to(X64 / scale), to(-yv / scale), to(w), None, const, nu, prior_sigma, _name=nm)
+
+
+class LinearRegressionTarget(GLMTarget):
+    """Posterior of Gaussian linear regression with known noise: y_i ~ N(x_i . z, noise_sigma^2).  Folds to the "normal"
+    family with A = X / noise_sigma, offset = -y / noise_sigma and const = sum_i w_i (-log(2 pi)/2 - log noise_sigma)."""
+
+    def __init__(self, X, y, noise_sigma, weights=None, prior_sigma=1.0):
+        nm = "LinearRegressionTarget"
+        X64 = _glm_matrix(nm, X)
+        n = X64.shape[0]
+        yv = _glm_vector(nm, "y", y, X, n)
+        sn = _glm_scalar(nm, "noise_sigma", noise_sigma)
+        w = _glm_vector(nm, "weights", weights, X, n, 1.0, nonneg=True)
+        const = float(w.sum()) * (-0.5 * math.log(2.0 * math.pi) - math.log(sn))
+        to = lambda t: t.to(X.dtype).to(X.device)
+        super().__init__("normal", to(X64 / sn), to(-yv / sn), to(w), None, const, 0.0, prior_sigma, _name=nm)
 
 
 def check_target(target, dtype, device=None, d=None):

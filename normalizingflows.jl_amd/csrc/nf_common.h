@@ -213,6 +213,40 @@ __device__ __forceinline__ void nf_adam_elem(T &theta, T &m, T &v, T g, T lr, T 
   theta = theta - lr * (mi / c1) / (sqrt(vi / c2) + eps);
 }
 
+// Sum over the 16 lanes of a sample group (xor 8, 4, 2, 1), result in every lane.  nf_simple.hip's g16sum adds in another
+// order (DPP: 1, 2, half-mirror, mirror) and gives different bits: the two are not interchangeable.
+template <class T>
+__device__ __forceinline__ T group16_sum(T v) {
+  v += __shfl_xor(v, 8, 16);
+  v += __shfl_xor(v, 4, 16);
+  v += __shfl_xor(v, 2, 16);
+  v += __shfl_xor(v, 1, 16);
+  return v;
+}
+
+// deterministic block-wide sum of one double per thread -> thread 0 (0 elsewhere): wave sums by shuffles, then the first NW
+// waves' sums in order through sm (NW = 0: all blockDim.x / 64 of them).  BARRIER: ends on a barrier, so that sm may be reused
+// at once; a kernel whose last statement this is passes false.
+template <int NW = 0, bool BARRIER = true>
+__device__ __forceinline__ double block_sum(double v, double *sm) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (lane == 0) sm[wave] = v;
+  __syncthreads();
+  double r = 0.0;
+  if (threadIdx.x == 0) {
+    if constexpr (NW > 0) {
+#pragma unroll
+      for (int w = 0; w < NW; ++w) r += sm[w];
+    } else {
+      for (int w = 0; w < (int)(blockDim.x >> 6); ++w) r += sm[w];
+    }
+  }
+  if (BARRIER) __syncthreads();
+  return r;
+}
+
 // layer bookkeeping shared by host code --------------------------------------------
 struct CouplingInfo {
   long theta_off;   // offset of this coupling's parameters in theta

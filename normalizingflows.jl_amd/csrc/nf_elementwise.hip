@@ -6,8 +6,6 @@
 // LPS = 16 lanes per sample: lane q of a sample group owns features q, q+16, q+32, ... so a
 // 16-lane group reads 64 contiguous bytes per step, and per-sample sums (||x||^2, log p)
 // are 4-step DPP/shuffle reductions inside the group.
-#include <type_traits>
-
 #include "nf_common.h"
 #include "nf_philox.h"
 #include "nf_targets.h"
@@ -16,29 +14,7 @@
 #define EW_BLOCK 256
 #define SPB (EW_BLOCK / LPS)  // samples per block
 
-template <class T>
-__device__ __forceinline__ T group16_sum(T v) {
-  v += __shfl_xor(v, 8, 16);
-  v += __shfl_xor(v, 4, 16);
-  v += __shfl_xor(v, 2, 16);
-  v += __shfl_xor(v, 1, 16);
-  return v;
-}
-
-// block-wide sum of one double per thread -> thread 0 (EW_BLOCK threads)
-__device__ __forceinline__ double block_sum(double v, double *sm) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 0) sm[wave] = v;
-  __syncthreads();
-  double r = 0.0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) r += sm[w];
-  __syncthreads();
-  return r;
-}
-
+// group16_sum, block_sum: nf_common.h
 
 // x ~ N(0, I), logq = logpdf(MvNormal(0, I), x).  Reference seam: _device_specific_rand
 // (src/NormalizingFlows.jl:109-115; device version ext/NormalizingFlowsCUDAExt.jl:43-48).
@@ -276,13 +252,7 @@ __global__ __launch_bounds__(EW_BLOCK) void k_target(int kind, int d, long N, co
         if (grad_out) grad_out[j * d + i] = gscale * g;
       }
     };
-    switch (kind) {
-      case NF_TARGET_DIAGGAUSS: run(std::integral_constant<int, NF_TARGET_DIAGGAUSS>{}); break;
-      case NF_TARGET_BANANA: run(std::integral_constant<int, NF_TARGET_BANANA>{}); break;
-      case NF_TARGET_FUNNEL: run(std::integral_constant<int, NF_TARGET_FUNNEL>{}); break;
-      case NF_TARGET_WARPED: run(std::integral_constant<int, NF_TARGET_WARPED>{}); break;
-      default: run(std::integral_constant<int, NF_TARGET_CROSS>{}); break;
-    }
+    nf_with_target_kind(kind, run);
   }
   acc = group16_sum(acc);
   double contrib = 0.0;
@@ -550,13 +520,7 @@ __global__ __launch_bounds__(EW_BLOCK) void k_target_tiled(int kind, int d, long
         if (gb) gb[(long)i * TL] = valid ? gscale * g : 0.f;
       }
     };
-    switch (kind) {
-      case NF_TARGET_DIAGGAUSS: run(std::integral_constant<int, NF_TARGET_DIAGGAUSS>{}); break;
-      case NF_TARGET_BANANA: run(std::integral_constant<int, NF_TARGET_BANANA>{}); break;
-      case NF_TARGET_FUNNEL: run(std::integral_constant<int, NF_TARGET_FUNNEL>{}); break;
-      case NF_TARGET_WARPED: run(std::integral_constant<int, NF_TARGET_WARPED>{}); break;
-      default: run(std::integral_constant<int, NF_TARGET_CROSS>{}); break;
-    }
+    nf_with_target_kind(kind, run);
   }
   red[q][s] = acc;
   __syncthreads();

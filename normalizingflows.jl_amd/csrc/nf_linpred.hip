@@ -278,15 +278,6 @@ __global__ __launch_bounds__(LP_BLOCK) void k_target_glm_tiled(int d, int rows, 
 #define LPF_RB 16
 #define LPF_MAXD 256
 
-template <class T>
-__device__ __forceinline__ T lp_group16_sum(T v) {
-  v += __shfl_xor(v, 8, 16);
-  v += __shfl_xor(v, 4, 16);
-  v += __shfl_xor(v, 2, 16);
-  v += __shfl_xor(v, 1, 16);
-  return v;
-}
-
 template <class T, class PHI, bool GLM>
 __device__ __forceinline__ void lp_flat_body(int d, int rows, long N, const T *__restrict__ y, const T *__restrict__ p0,
                                              const T *__restrict__ A, T c0, T pw, const T *__restrict__ logq,
@@ -361,9 +352,9 @@ __device__ __forceinline__ void lp_flat_body(int d, int rows, long N, const T *_
         grad_out[j * d + f] = gscale * (g[k] - pw * yv);
     }
   }
-  lp = lp_group16_sum(lp);
-  yy = lp_group16_sum(yy);
-  if (GLM) ly = lp_group16_sum(ly);
+  lp = group16_sum(lp);
+  yy = group16_sum(yy);
+  if (GLM) ly = group16_sum(ly);
   double contrib = 0.0;
   if (valid && q == 0) {
     T e = c0 + lp - (T)0.5 * pw * yy;

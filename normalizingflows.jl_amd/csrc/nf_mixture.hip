@@ -241,15 +241,6 @@ __global__ __launch_bounds__(MX_BLOCK) void k_target_mixture_tiled(int d, int K,
 #define MXF_MAXD 256
 
 template <class T>
-__device__ __forceinline__ T mx_group16_sum(T v) {
-  v += __shfl_xor(v, 8, 16);
-  v += __shfl_xor(v, 4, 16);
-  v += __shfl_xor(v, 2, 16);
-  v += __shfl_xor(v, 1, 16);
-  return v;
-}
-
-template <class T>
 __global__ __launch_bounds__(MX_BLOCK) void k_target_mixture(int d, int K, long N, const T *__restrict__ y,
                                                              const T *__restrict__ p0, const T *__restrict__ A,
                                                              const T *__restrict__ logq, const T *__restrict__ ladj,
@@ -306,7 +297,7 @@ __global__ __launch_bounds__(MX_BLOCK) void k_target_mixture(int d, int K, long 
         }
       }
     }
-    ss = mx_group16_sum(ss);
+    ss = group16_sum(ss);
     T sc, w;
     mx_take(cv[kc] - (T)0.5 * ss, M, Ssum, sc, w);
 #pragma unroll

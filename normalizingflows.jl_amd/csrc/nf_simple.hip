@@ -428,17 +428,8 @@ __global__ __launch_bounds__(SB) void k_simple_apply(SimpleArgs a, const T *__re
   }
   if (fu.on) {  // deterministic block sum of the ELBO terms
     __shared__ double sm[SB / 64];
-    double c = contrib;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      double t = 0.0;
-#pragma unroll
-      for (int w = 0; w < SB / 64; ++w) t += sm[w];
-      fu.partial[blockIdx.x] = t;
-    }
+    const double t = block_sum<SB / 64, false>(contrib, sm);
+    if (threadIdx.x == 0) fu.partial[blockIdx.x] = t;
   }
 }
 
@@ -1028,6 +1019,16 @@ __device__ __forceinline__ float planar_xhalf_sum(float v) {
   return lo + hi;
 }
 
+// The diagonal-Gaussian table of the two tile kernels' DIAG instantiations (k_planar_step, k_radial_step) in LDS: tg = mu[FD] | 1/var[FD] | log 2pi + log var[FD], zero beyond d
+template <int FD>
+__device__ __forceinline__ void tile_diag_table(float *tg, const SimpleFused &fu, int d) {
+  for (int i = threadIdx.x; i < FD; i += SB) {
+    const float vv = i < d ? ((const float *)fu.var)[i] : 1.f;
+    tg[i] = i < d ? ((const float *)fu.mu)[i] : 0.f;
+    tg[FD + i] = i < d ? 1.f / vv : 0.f;
+    tg[2 * FD + i] = i < d ? 1.8378770664093453f + logf(vv) : 0.f;
+  }
+}
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ f32x4 planar_mfma16(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 // the contraction order of the K = samples GEMMs: k-step t, lane group g <-> sample planar_s(t) + 4 g
@@ -1123,13 +1124,7 @@ __global__ __launch_bounds__(SB, (PG::NLR <= 6 ? 2 : 1)) void k_planar_step(Simp
     sh[PG::OFF_B + i] = i < nl ? cache[i * LP + 2 * d] : 0.f;
     sh[PG::OFF_SP + i] = i < nl ? cache[i * LP + 2 * d + 1] : 1.f;
   }
-  if (DIAG)
-    for (int i = tid; i < FD; i += SB) {
-      const float vv = i < d ? ((const float *)fu.var)[i] : 1.f;
-      sh[PG::OFF_TG + i] = i < d ? ((const float *)fu.mu)[i] : 0.f;
-      sh[PG::OFF_TG + FD + i] = i < d ? 1.f / vv : 0.f;
-      sh[PG::OFF_TG + 2 * FD + i] = i < d ? 1.8378770664093453f + logf(vv) : 0.f;
-    }
+  if (DIAG) tile_diag_table<FD>(sh + PG::OFF_TG, fu, d);
   __syncthreads();
   // wave-uniform scalars of the recurrences, read once: SGPRs (readfirstlane marks them uniform; both sweeps use the
   // strict upper triangle of C only).  (Round 5: with the 32 hoisted "feature < d" lane masks they overflow the scalar file and
@@ -1422,17 +1417,8 @@ __global__ __launch_bounds__(SB, (PG::NLR <= 6 ? 2 : 1)) void k_planar_step(Simp
   }
   {  // deterministic block sum of the ELBO terms
     __shared__ double sm[SB / 64];
-    double c = contrib;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-    if (lane == 0) sm[wave] = c;
-    __syncthreads();
-    if (tid == 0) {
-      double t = 0.0;
-#pragma unroll
-      for (int w = 0; w < SB / 64; ++w) t += sm[w];
-      fu.partial[blockIdx.x] = t;
-    }
+    const double t = block_sum<SB / 64, false>(contrib, sm);
+    if (threadIdx.x == 0) fu.partial[blockIdx.x] = t;
   }
 }
 
@@ -1514,13 +1500,7 @@ __global__ __launch_bounds__(SB, 2) void k_radial_step(SimpleArgs a, const float
     sh[RG::OFF_A + i] = i < nl ? cache[i * LP + d] : 1.f;
     sh[RG::OFF_BH + i] = i < nl ? cache[i * LP + d + 1] : 0.f;
   }
-  if (DIAG)
-    for (int i = tid; i < FD; i += SB) {
-      const float vv = i < d ? ((const float *)fu.var)[i] : 1.f;
-      sh[RG::OFF_TG + i] = i < d ? ((const float *)fu.mu)[i] : 0.f;
-      sh[RG::OFF_TG + FD + i] = i < d ? 1.f / vv : 0.f;
-      sh[RG::OFF_TG + 2 * FD + i] = i < d ? 1.8378770664093453f + logf(vv) : 0.f;
-    }
+  if (DIAG) tile_diag_table<FD>(sh + RG::OFF_TG, fu, d);
   __syncthreads();
   auto sc = [&](int off) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, sh[off]))); };
   // (alpha_l, beta_hat_l are fetched where they are used, inside the tile loop: held in 2 NL registers across it they were what
@@ -1732,17 +1712,8 @@ __global__ __launch_bounds__(SB, 2) void k_radial_step(SimpleArgs a, const float
   }
   {  // deterministic block sum of the ELBO terms
     __shared__ double sm[SB / 64];
-    double c = contrib;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-    if (lane == 0) sm[wave] = c;
-    __syncthreads();
-    if (tid == 0) {
-      double t = 0.0;
-#pragma unroll
-      for (int w = 0; w < SB / 64; ++w) t += sm[w];
-      fu.partial[blockIdx.x] = t;
-    }
+    const double t = block_sum<SB / 64, false>(contrib, sm);
+    if (threadIdx.x == 0) fu.partial[blockIdx.x] = t;
   }
 }
 
@@ -1844,21 +1815,12 @@ template <class T>
 __global__ __launch_bounds__(FB) void k_simple_epilogue(SimpleArgs a, SimpleEpiArgs<T> e) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ double sm[FB / 64];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (blockIdx.x == 0) {  // the loss: 256 strided accumulators, wave sums, the four waves in order (k_finish_sum)
+  if (blockIdx.x == 0) {  // the loss: 256 strided accumulators, then block_sum (k_finish_sum's order; waves 4 .. 7 add zeros)
     double c = 0.0;
     if (threadIdx.x < 256)
       for (int i = threadIdx.x; i < e.nlpart; i += 256) c += e.lpart[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-    if (lane == 0) sm[wave] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      double t = 0.0;
-      for (int w = 0; w < 4; ++w) t += sm[w];
-      e.g[e.P] = (T)t;
-    }
-    __syncthreads();
+    const double t = block_sum<4>(c, sm);
+    if (threadIdx.x == 0) e.g[e.P] = (T)t;
   }
   simple_finalize_layer<T>(a, e.theta, e.slabs, e.nblk_bwd, e.g, smem);
   __syncthreads();  // the layer's gradient, written by this block, is read back below
@@ -1880,16 +1842,8 @@ __global__ __launch_bounds__(FB) void k_simple_epilogue(SimpleArgs a, SimpleEpiA
     e.theta[off + i] = th;
     gg += (double)gi * (double)gi;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) gg += __shfl_xor(gg, o, 64);
-  if (lane == 0) sm[wave] = gg;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = 0.0;
-#pragma unroll
-    for (int w = 0; w < FB / 64; ++w) t += sm[w];
-    e.gpart[blockIdx.x] = t;
-  }
+  const double t = block_sum<FB / 64, false>(gg, sm);
+  if (threadIdx.x == 0) e.gpart[blockIdx.x] = t;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1912,11 +1866,14 @@ static int vec_ok(int d, int dpl, std::initializer_list<const void *> ptrs) {
   return 1;
 }
 
+// flat layers of the flow (mean-field: Shift o Scale)
+static inline int simple_nl(const nf_flow_desc *desc) { return desc->kind == NF_KIND_MEANFIELD ? 2 : desc->nlayers; }
+
 bool nf_simple_supported(const nf_flow_desc *desc) {
   if (desc->d > 256) return false;
   const long LP = lp_of(desc->d);
   const long es = desc->dtype == NF_DTYPE_F64 ? 8 : 4;
-  const int nl = desc->kind == NF_KIND_MEANFIELD ? 2 : desc->nlayers;
+  const int nl = simple_nl(desc);
   return (long)nl * LP * es <= 64 * 1024;
 }
 
@@ -1924,7 +1881,7 @@ static SimpleArgs make_sargs(const nf_flow_desc *desc, int lo, int hi, bool inve
   SimpleArgs a;
   a.kind = desc->kind;
   a.d = desc->d;
-  a.nl = desc->kind == NF_KIND_MEANFIELD ? 2 : desc->nlayers;
+  a.nl = simple_nl(desc);
   a.lo = lo;
   a.hi = hi;
   a.inverse = inverse ? 1 : 0;
@@ -2000,7 +1957,7 @@ static inline int bwd_blocks(nf_ctx *ctx, long N) {
 
 size_t nf_simple_bwd_ws_bytes(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
   const size_t es = desc->dtype == NF_DTYPE_F64 ? 8 : 4;
-  const int nl = desc->kind == NF_KIND_MEANFIELD ? 2 : desc->nlayers;
+  const int nl = simple_nl(desc);
   const size_t LP = lp_of(desc->d);
   return carve_bytes((size_t)nl * N * desc->d * es) + carve_bytes((size_t)N * desc->d * es) +
          carve_bytes((size_t)nl * bwd_blocks(ctx, N) * LP * es);
@@ -2011,7 +1968,7 @@ size_t nf_simple_bwd_ws_bytes(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
 int nf_simple_apply_stash(nf_ctx *ctx, const nf_flow_desc *desc, const void *theta, const void *x, long N, void *y,
                           void *ladj, void *ws, bool inverse) {
   if (N <= 0) return NF_OK;
-  const int nl = desc->kind == NF_KIND_MEANFIELD ? 2 : desc->nlayers;
+  const int nl = simple_nl(desc);
   SimpleArgs a = make_sargs(desc, 0, nl, inverse, N);
   Carver cv(ws);
   if (desc->dtype == NF_DTYPE_F32) return apply_t<float>(ctx, a, theta, x, y, ladj, cv.take<float>((size_t)nl * N * desc->d));
@@ -2026,7 +1983,7 @@ int nf_simple_elbo_forward(nf_ctx *ctx, const nf_flow_desc *desc, const nf_targe
                            long N, uint64_t seed, uint64_t off, uint32_t stream_id, void *gbar, double gscale, double *partial,
                            double pscale, void *ws, long *npartial) {
   if (N <= 0) return NF_OK;
-  const int nl = desc->kind == NF_KIND_MEANFIELD ? 2 : desc->nlayers;
+  const int nl = simple_nl(desc);
   SimpleArgs a = make_sargs(desc, 0, nl, false, N);
   SimpleFused fu{};
   fu.on = 1;
@@ -2049,7 +2006,7 @@ int nf_simple_elbo_forward(nf_ctx *ctx, const nf_flow_desc *desc, const nf_targe
 int nf_simple_rand(nf_ctx *ctx, const nf_flow_desc *desc, const void *theta, long N, uint64_t seed, uint64_t off,
                    uint32_t stream_id, void *y) {
   if (N <= 0) return NF_OK;
-  const int nl = desc->kind == NF_KIND_MEANFIELD ? 2 : desc->nlayers;
+  const int nl = simple_nl(desc);
   SimpleArgs a = make_sargs(desc, 0, nl, false, N);
   SimpleFused fu{};
   fu.draw = 1;
@@ -2063,7 +2020,7 @@ static int bwd_t(nf_ctx *ctx, const nf_flow_desc *desc, const void *theta, const
                  const void *lbar, double lbar_const, long N, void *xbar_out, void *gtheta_out, void *ws,
                  bool have_stash, bool inv) {
   if (inv && !have_stash) return NF_ERR_ARG;  // the inverse chain's points come from nf_simple_apply_stash(inverse)
-  const int nl = desc->kind == NF_KIND_MEANFIELD ? 2 : desc->nlayers;
+  const int nl = simple_nl(desc);
   const int d = desc->d;
   const size_t LP = lp_of(d);
   const int nb = bwd_blocks(ctx, N);
@@ -2121,29 +2078,39 @@ int nf_simple_bwd(nf_ctx *ctx, const nf_flow_desc *desc, const void *theta, cons
   return bwd_t<double>(ctx, desc, theta, x, ybar, lbar, lbar_const, N, xbar_out, gtheta_out, ws, have_stash, inv);
 }
 
-// ---- the stash-free training step (k_simple_step) ----------------------------------------------------------------
-template <class T, int DPL, int KIND, int NLMAX>
-static int step_launch(nf_ctx *ctx, SimpleArgs a, const void *theta, const void *xs, const SimpleFused &fu, double lbar_const,
-                       T *slabs, int *nb_out) {
-  const size_t LP = lp_of(a.d);
-  const size_t lds = (size_t)(1 + SB / 64) * a.nl * LP * sizeof(T);
+// ---- the fused training steps: one launcher, three kernels -----------------------------------------------------------
+// One launch of a step kernel (k_simple_step, k_planar_step, k_radial_step: the same argument list): the dynamic-LDS attribute
+// once per kernel instantiation (KERNEL is a template argument, so the static below is its own) and device, the grid of `nb`
+// blocks clamped to what is resident at once (-> *nb_out, the slab count per layer), the profiling scope, the launch.
+template <auto KERNEL, class T>
+static int launch_step_kernel(nf_ctx *ctx, size_t lds, long nb, const char *prof_name, const SimpleArgs &a, const void *theta,
+                              const void *xs, const SimpleFused &fu, double lbar_const, T *slabs, int *nb_out) {
   static AttrOnce attr_once;  // once per device
   NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    NF_HIP(hipFuncSetAttribute((const void *)k_simple_step<T, DPL, KIND, NLMAX>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+    NF_HIP(hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
     return NF_OK;
   }));
-  long nb = (a.N + SPB - 1) / SPB;
-  const long res = resident_blocks(ctx, k_simple_step<T, DPL, KIND, NLMAX>, lds);
+  const long res = resident_blocks(ctx, KERNEL, lds);
   if (nb > res) nb = res;
   if (nb < 1) nb = 1;
   *nb_out = (int)nb;
-  ProfScope ps(ctx, "simple_step");
-  hipLaunchKernelGGL((k_simple_step<T, DPL, KIND, NLMAX>), dim3((unsigned)nb), dim3(SB), lds, ctx->stream, a, (const T *)theta,
-                     (const T *)xs, fu, (T)lbar_const, slabs, (long)nb * (long)LP);
+  ProfScope ps(ctx, prof_name);
+  hipLaunchKernelGGL(KERNEL, dim3((unsigned)nb), dim3(SB), lds, ctx->stream, a, (const T *)theta, (const T *)xs, fu, (T)lbar_const,
+                     slabs, nb * (long)lp_of(a.d));
   return (int)hipGetLastError();
 }
 
-// ---- the planar step on the matrix pipe (k_planar_step) ------------------------------------------------------------
+// ---- the stash-free training step (k_simple_step) ----------------------------------------------------------------
+template <class T, int DPL, int KIND, int NLMAX>
+static int step_launch(nf_ctx *ctx, const SimpleArgs &a, const void *theta, const void *xs, const SimpleFused &fu, double lbar_const,
+                       T *slabs, int *nb_out) {
+  const size_t lds = (size_t)(1 + SB / 64) * a.nl * lp_of(a.d) * sizeof(T);
+  return launch_step_kernel<k_simple_step<T, DPL, KIND, NLMAX>>(ctx, lds, (a.N + SPB - 1) / SPB, "simple_step", a, theta, xs, fu,
+                                                                lbar_const, slabs, nb_out);
+}
+
+// ---- the planar step on the matrix pipe (k_planar_step), the radial step with one lane per (sample, feature half)
+//      (k_radial_step): d <= 64, up to 16 layers, Float32 -----------------------------------------------------------------
 #ifndef NF_PLANAR_MFMA_MIN_D
 #define NF_PLANAR_MFMA_MIN_D 2
 #endif
@@ -2152,84 +2119,45 @@ static bool planar_mfma_ok(const nf_flow_desc *desc) {
   return !off && desc->kind == NF_KIND_PLANAR && desc->dtype == NF_DTYPE_F32 && desc->d >= NF_PLANAR_MFMA_MIN_D && desc->d <= 64 &&
          desc->nlayers >= 1 && desc->nlayers <= 16;
 }
-template <class PG, bool DIAG>
-static int planar_launch_t(nf_ctx *ctx, SimpleArgs a, const void *theta, const void *xs, const SimpleFused &fu, double lbar_const,
-                         float *slabs, int *nb_out) {
-  const size_t LP = lp_of(a.d);
-  const size_t lds = PG::lds_floats(a.nl, (int)LP) * sizeof(float);
-  static AttrOnce attr_once;  // once per device
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    NF_HIP(hipFuncSetAttribute((const void *)k_planar_step<PG, DIAG>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    return NF_OK;
-  }));
-  a.vec = (xs && a.d % 4 == 0 && (uintptr_t)xs % 16 == 0) ? 1 : 0;
-  long nb = ((a.N + 31) / 32 + 3) / 4;
-  const long res = resident_blocks(ctx, k_planar_step<PG, DIAG>, lds);
-  if (nb > res) nb = res;
-  if (nb < 1) nb = 1;
-  *nb_out = (int)nb;
-  ProfScope ps(ctx, "planar_step");
-  hipLaunchKernelGGL((k_planar_step<PG, DIAG>), dim3((unsigned)nb), dim3(SB), lds, ctx->stream, a, (const float *)theta, (const float *)xs, fu,
-                     (float)lbar_const, slabs, (long)nb * (long)LP);
-  return (int)hipGetLastError();
-}
-template <class PG>
-static int planar_launch(nf_ctx *ctx, const SimpleArgs &a, const void *theta, const void *xs, const SimpleFused &fu, double lbar_const,
-                         float *slabs, int *nb_out) {
-  return fu.tkind == NF_TARGET_DIAGGAUSS ? planar_launch_t<PG, true>(ctx, a, theta, xs, fu, lbar_const, slabs, nb_out)
-                                         : planar_launch_t<PG, false>(ctx, a, theta, xs, fu, lbar_const, slabs, nb_out);
-}
-static int planar_step(nf_ctx *ctx, const SimpleArgs &a, const void *theta, const void *xs, const SimpleFused &fu, double lbar_const,
-                       float *slabs, int *nb_out) {
-  const bool wide = a.d > 32;
-  if (a.nl <= 10)
-    return wide ? planar_launch<PlanarGeo<2, 6>>(ctx, a, theta, xs, fu, lbar_const, slabs, nb_out)
-                : planar_launch<PlanarGeo<1, 6>>(ctx, a, theta, xs, fu, lbar_const, slabs, nb_out);
-  return wide ? planar_launch<PlanarGeo<2, 8>>(ctx, a, theta, xs, fu, lbar_const, slabs, nb_out)
-              : planar_launch<PlanarGeo<1, 8>>(ctx, a, theta, xs, fu, lbar_const, slabs, nb_out);
-}
-
-// ---- the radial step, one lane per (sample, feature half) (k_radial_step) -------------------------------------------
 static bool radial_lane_ok(const nf_flow_desc *desc) {
   static const bool off = std::getenv("NF_RADIAL_NO_LANE") != nullptr;  // A/B switch: k_simple_step
   return !off && desc->kind == NF_KIND_RADIAL && desc->dtype == NF_DTYPE_F32 && desc->d >= 8 && desc->d <= 64 &&
          desc->nlayers >= 1 && desc->nlayers <= 16;
 }
-template <class RG, bool DIAG>
-static int radial_launch_t(nf_ctx *ctx, SimpleArgs a, const void *theta, const void *xs, const SimpleFused &fu, double lbar_const,
-                           float *slabs, int *nb_out) {
-  const size_t LP = lp_of(a.d);
-  const size_t lds = RG::lds_floats(a.nl, (int)LP) * sizeof(float);
-  static AttrOnce attr_once;  // once per device
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    NF_HIP(hipFuncSetAttribute((const void *)k_radial_step<RG, DIAG>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    return NF_OK;
-  }));
-  a.vec = (xs && a.d % 4 == 0 && (uintptr_t)xs % 16 == 0) ? 1 : 0;
-  long nb = ((a.N + 31) / 32 + 3) / 4;
-  const long res = resident_blocks(ctx, k_radial_step<RG, DIAG>, lds);
-  if (nb > res) nb = res;
-  if (nb < 1) nb = 1;
-  *nb_out = (int)nb;
-  ProfScope ps(ctx, "radial_step");
-  hipLaunchKernelGGL((k_radial_step<RG, DIAG>), dim3((unsigned)nb), dim3(SB), lds, ctx->stream, a, (const float *)theta, (const float *)xs,
-                     fu, (float)lbar_const, slabs, (long)nb * (long)LP);
-  return (int)hipGetLastError();
-}
-template <class RG>
-static int radial_launch(nf_ctx *ctx, const SimpleArgs &a, const void *theta, const void *xs, const SimpleFused &fu, double lbar_const,
+// what the chooser below needs of a tile kernel: its geometry for DB feature blocks and up to ten / sixteen layers, its
+// instantiations, its profiling name
+struct PlanarStep {
+  template <int DB, bool MANY> using Geo = PlanarGeo<DB, MANY ? 8 : 6>;
+  template <class G, bool DIAG> static constexpr auto kernel = k_planar_step<G, DIAG>;
+  static constexpr const char *name = "planar_step";
+};
+struct RadialStep {
+  template <int DB, bool MANY> using Geo = RadialGeo<DB, MANY ? 16 : 10>;
+  template <class G, bool DIAG> static constexpr auto kernel = k_radial_step<G, DIAG>;
+  static constexpr const char *name = "radial_step";
+};
+template <class S, int DB, bool MANY>
+static int tile_step_geo(nf_ctx *ctx, SimpleArgs a, const void *theta, const void *xs, const SimpleFused &fu, double lbar_const,
                          float *slabs, int *nb_out) {
-  return fu.tkind == NF_TARGET_DIAGGAUSS ? radial_launch_t<RG, true>(ctx, a, theta, xs, fu, lbar_const, slabs, nb_out)
-                                         : radial_launch_t<RG, false>(ctx, a, theta, xs, fu, lbar_const, slabs, nb_out);
+  using G = typename S::template Geo<DB, MANY>;
+  const size_t lds = G::lds_floats(a.nl, lp_of(a.d)) * sizeof(float);
+  a.vec = (xs && a.d % 4 == 0 && (uintptr_t)xs % 16 == 0) ? 1 : 0;
+  const long nb = ((a.N + 31) / 32 + 3) / 4;  // four 32-sample tiles per block
+  // the diagonal Gaussian has instantiations of its own (k_planar_step)
+  return fu.tkind == NF_TARGET_DIAGGAUSS
+             ? launch_step_kernel<S::template kernel<G, true>>(ctx, lds, nb, S::name, a, theta, xs, fu, lbar_const, slabs, nb_out)
+             : launch_step_kernel<S::template kernel<G, false>>(ctx, lds, nb, S::name, a, theta, xs, fu, lbar_const, slabs, nb_out);
 }
-static int radial_step(nf_ctx *ctx, const SimpleArgs &a, const void *theta, const void *xs, const SimpleFused &fu, double lbar_const,
-                       float *slabs, int *nb_out) {
+// geometry by width (d > 32: two feature blocks) and depth (more than ten layers)
+template <class S>
+static int tile_step(nf_ctx *ctx, const SimpleArgs &a, const void *theta, const void *xs, const SimpleFused &fu, double lbar_const,
+                     float *slabs, int *nb_out) {
   const bool wide = a.d > 32;
   if (a.nl <= 10)
-    return wide ? radial_launch<RadialGeo<2, 10>>(ctx, a, theta, xs, fu, lbar_const, slabs, nb_out)
-                : radial_launch<RadialGeo<1, 10>>(ctx, a, theta, xs, fu, lbar_const, slabs, nb_out);
-  return wide ? radial_launch<RadialGeo<2, 16>>(ctx, a, theta, xs, fu, lbar_const, slabs, nb_out)
-              : radial_launch<RadialGeo<1, 16>>(ctx, a, theta, xs, fu, lbar_const, slabs, nb_out);
+    return wide ? tile_step_geo<S, 2, false>(ctx, a, theta, xs, fu, lbar_const, slabs, nb_out)
+                : tile_step_geo<S, 1, false>(ctx, a, theta, xs, fu, lbar_const, slabs, nb_out);
+  return wide ? tile_step_geo<S, 2, true>(ctx, a, theta, xs, fu, lbar_const, slabs, nb_out)
+              : tile_step_geo<S, 1, true>(ctx, a, theta, xs, fu, lbar_const, slabs, nb_out);
 }
 
 // smallest unroll bound that holds nl layers
@@ -2275,7 +2203,7 @@ static int step_nlmax(const nf_flow_desc *desc) {
 bool nf_simple_step_supported(const nf_flow_desc *desc) {
   if (planar_mfma_ok(desc) || radial_lane_ok(desc)) return true;
   if (!nf_simple_supported(desc) || dpl_for(desc->d) > 16) return false;
-  const int nl = desc->kind == NF_KIND_MEANFIELD ? 2 : desc->nlayers;
+  const int nl = simple_nl(desc);
   const size_t es = desc->dtype == NF_DTYPE_F64 ? 8 : 4;
   if (nl > step_nlmax(desc)) return false;
   return (size_t)(1 + SB / 64) * nl * lp_of(desc->d) * es <= 144 * 1024;
@@ -2283,7 +2211,7 @@ bool nf_simple_step_supported(const nf_flow_desc *desc) {
 
 size_t nf_simple_step_ws_bytes(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
   const size_t es = desc->dtype == NF_DTYPE_F64 ? 8 : 4;
-  const int nl = desc->kind == NF_KIND_MEANFIELD ? 2 : desc->nlayers;
+  const int nl = simple_nl(desc);
   long nb = (N + SPB - 1) / SPB;
   const long cap = 16L * ctx->num_cu;  // upper bound of the resident-block count
   if (nb > cap) nb = cap;
@@ -2298,7 +2226,7 @@ template <class T>
 static int step_t(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, const void *theta, const void *xs, long N,
                   uint64_t seed, uint64_t off, uint32_t stream_id, double gscale, double lbar_const, double *partial,
                   double pscale, void *ws, void *gtheta_out, long *npartial, const uint32_t *step_device) {
-  const int nl = desc->kind == NF_KIND_MEANFIELD ? 2 : desc->nlayers;
+  const int nl = simple_nl(desc);
   SimpleArgs a = make_sargs(desc, 0, nl, false, N);
   a.vec = vec_ok<T>(a.d, dpl_for(a.d), {xs});
   SimpleFused fu{};
@@ -2312,27 +2240,16 @@ static int step_t(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target
   T *slabs = (T *)ws;
   int nb = 0;
   int st;
-  if constexpr (std::is_same<T, float>::value) {
-    if (planar_mfma_ok(desc) || radial_lane_ok(desc)) {
-      NF_TRY(planar_mfma_ok(desc) ? planar_step(ctx, a, theta, xs, fu, lbar_const, slabs, &nb)
-                                  : radial_step(ctx, a, theta, xs, fu, lbar_const, slabs, &nb));
-      *npartial = nb;
-      if (!gtheta_out) return NF_OK;
-      ProfScope pf(ctx, "simple_finalize");
-      hipLaunchKernelGGL(k_simple_finalize<T>, dim3(nl), dim3(FB), (size_t)(1 + FB / 64) * lp_of(a.d) * sizeof(T), ctx->stream, a,
-                         (const T *)theta, (const T *)slabs, nb, (T *)gtheta_out);
-      return (int)hipGetLastError();
-    }
-  }
-  if (desc->kind == NF_KIND_PLANAR) st = step_kind<T, NF_KIND_PLANAR>(ctx, a, theta, xs, fu, lbar_const, slabs, &nb);
+  if (planar_mfma_ok(desc)) st = tile_step<PlanarStep>(ctx, a, theta, xs, fu, lbar_const, (float *)slabs, &nb);  // (Float32 only)
+  else if (radial_lane_ok(desc)) st = tile_step<RadialStep>(ctx, a, theta, xs, fu, lbar_const, (float *)slabs, &nb);
+  else if (desc->kind == NF_KIND_PLANAR) st = step_kind<T, NF_KIND_PLANAR>(ctx, a, theta, xs, fu, lbar_const, slabs, &nb);
   else if (desc->kind == NF_KIND_RADIAL) st = step_kind<T, NF_KIND_RADIAL>(ctx, a, theta, xs, fu, lbar_const, slabs, &nb);
   else st = step_kind<T, NF_KIND_MEANFIELD>(ctx, a, theta, xs, fu, lbar_const, slabs, &nb);
   NF_TRY(st);
   *npartial = nb;
   if (!gtheta_out) return NF_OK;
-  const size_t LP = lp_of(a.d);
   ProfScope pf(ctx, "simple_finalize");
-  hipLaunchKernelGGL(k_simple_finalize<T>, dim3(nl), dim3(FB), (size_t)(1 + FB / 64) * LP * sizeof(T), ctx->stream, a,
+  hipLaunchKernelGGL(k_simple_finalize<T>, dim3(nl), dim3(FB), (size_t)(1 + FB / 64) * lp_of(a.d) * sizeof(T), ctx->stream, a,
                      (const T *)theta, (const T *)slabs, nb, (T *)gtheta_out);
   return (int)hipGetLastError();
 }
@@ -2355,7 +2272,7 @@ template <class T>
 static int epilogue_t(nf_ctx *ctx, const nf_flow_desc *desc, const void *slabs, int nblk, void *g, long P, const double *lpart,
                       void *theta, void *m, void *v, double lr, double b1, double b2, double eps, unsigned t_val,
                       const unsigned *t_ptr, double *gpart) {
-  const int nl = desc->kind == NF_KIND_MEANFIELD ? 2 : desc->nlayers;
+  const int nl = simple_nl(desc);
   const SimpleArgs a = make_sargs(desc, 0, nl, false, 0);
   SimpleEpiArgs<T> e;
   e.slabs = (const T *)slabs; e.nblk_bwd = nblk; e.g = (T *)g; e.P = P; e.lpart = lpart; e.nlpart = nblk;
@@ -2368,7 +2285,7 @@ static int epilogue_t(nf_ctx *ctx, const nf_flow_desc *desc, const void *slabs, 
   hipLaunchKernelGGL(k_simple_epilogue<T>, dim3(nl), dim3(FB), (size_t)(1 + FB / 64) * lp_of(a.d) * sizeof(T), ctx->stream, a, e);
   return (int)hipGetLastError();
 }
-int nf_simple_epilogue_blocks(const nf_flow_desc *desc) { return desc->kind == NF_KIND_MEANFIELD ? 2 : desc->nlayers; }
+int nf_simple_epilogue_blocks(const nf_flow_desc *desc) { return simple_nl(desc); }
 int nf_simple_epilogue(nf_ctx *ctx, const nf_flow_desc *desc, const void *slabs, int nblk, void *g, const double *lpart, void *theta,
                        void *m, void *v, double lr, double b1, double b2, double eps, unsigned t_val, const unsigned *t_ptr,
                        double *gpart) {

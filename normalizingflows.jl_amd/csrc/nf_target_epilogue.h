@@ -1,7 +1,8 @@
 // nf_target_epilogue.h -- the target epilogue of the fused ELBO forwards (k_affine_chain_tgt of nf_coupling.hip,
 // k_rqs_chain_tgt of nf_rqs.hip) for the built-in targets other than the diagonal Gaussian: log p(y_j) and
 // ybar = gscale * grad log p(y) straight from the registers the last coupling left, through target_term (nf_targets.h) --
-// the function k_target_tiled and nf_simple.hip evaluate, not a second transcription of the densities.
+// the function k_target_tiled and nf_simple.hip evaluate, not a second transcription of the densities.  The NF_TGT_* sets of
+// kinds (template argument KSET / TGT) are defined in nf_targets.h.
 #pragma once
 #include "nf_mfma.h"
 #include "nf_targets.h"
@@ -74,13 +75,6 @@ __device__ __forceinline__ void nf_tile_isolate(f32x16 (&E)[CB], f32x16 (&O)[CB]
       O[b][r] = o;
     }
 }
-
-// Sets of kinds one kernel instantiation serves (template argument TGT of the chain bodies; 0: the diagonal-Gaussian kernel)
-#define NF_TGT_BANANA 1
-#define NF_TGT_FUNNEL 2
-#define NF_TGT_WARPED 4
-#define NF_TGT_CROSS 8
-#define NF_TGT_ALL4 15
 
 // kind: wave-uniform (a kernel argument), one of the kinds in KSET -- the host launches nothing else here
 template <int CB, int KSET>

@@ -1,6 +1,10 @@
 // nf_targets.h -- the built-in target log-densities, one feature at a time (shared by the stand-alone
-// target kernels of nf_elementwise.hip and the fused ELBO forward of nf_simple.hip).
+// target kernels of nf_elementwise.hip, the fused ELBO forwards and steps of nf_simple.hip and, through
+// nf_target_epilogue.h, the chain kernels), the NF_TGT_* sets of kinds a kernel instantiation serves, and
+// nf_with_target_kind, the one place a run-time kind becomes a compile-time one.
 #pragma once
+#include <type_traits>
+
 #include "nf_common.h"
 
 // Built-in targets.  target_term returns feature i's additive share of log p(y) (their sum over
@@ -75,6 +79,46 @@ __device__ __forceinline__ T target_term(int d, int i, T v, T y0, T y1, T s2, co
   g = gw / sw;
   if (i != 0) return (T)0;
   return log((T)0.25) + m + log(sw);
+}
+
+// Sets of kinds one kernel instantiation serves.  Two users: the chain bodies' template argument TGT (nf_target_epilogue.h,
+// nf_coupling.hip, nf_rqs.hip) holds the four non-Gaussian bits only, and TGT == 0 there means the diagonal-Gaussian kernel;
+// nf_with_target_kind's KSET may hold NF_TGT_DIAG as well (NF_TGT_ALL5: every kind behind one dispatch).
+#define NF_TGT_BANANA 1
+#define NF_TGT_FUNNEL 2
+#define NF_TGT_WARPED 4
+#define NF_TGT_CROSS 8
+#define NF_TGT_ALL4 15
+#define NF_TGT_DIAG 16
+#define NF_TGT_ALL5 31
+constexpr int nf_tgt_bit(int kind) {
+  return kind == NF_TARGET_DIAGGAUSS ? NF_TGT_DIAG : kind == NF_TARGET_BANANA ? NF_TGT_BANANA : kind == NF_TARGET_FUNNEL ? NF_TGT_FUNNEL
+         : kind == NF_TARGET_WARPED ? NF_TGT_WARPED : NF_TGT_CROSS;
+}
+constexpr int nf_tgt_last(int kset) {  // the set's last member in the order DiagGauss, Banana, Funnel, WarpedGauss, Cross
+  return kset & NF_TGT_CROSS ? NF_TARGET_CROSS : kset & NF_TGT_WARPED ? NF_TARGET_WARPED : kset & NF_TGT_FUNNEL ? NF_TARGET_FUNNEL
+         : kset & NF_TGT_BANANA ? NF_TARGET_BANANA : NF_TARGET_DIAGGAUSS;
+}
+
+// Calls f(std::integral_constant<int, KIND>{}) for the run-time `kind` (wave-uniform), so that f's body is compiled once per
+// kind with the kind a constant.  KSET leaves arms out: `kind` must be a member -- the host launches nothing else -- and every
+// value without an arm of its own takes the set's last member's (with all five: Cross, the `default:` this replaces).
+template <int KSET = NF_TGT_ALL5, class F>
+__device__ __forceinline__ void nf_with_target_kind(int kind, F &&f) {
+  constexpr int LAST = nf_tgt_last(KSET);
+#define NF_TGT_ARM(K) \
+  case K:             \
+    if constexpr ((KSET & nf_tgt_bit(K)) && K != LAST) return f(std::integral_constant<int, K>{}); \
+    break;
+  switch (kind) {
+    NF_TGT_ARM(NF_TARGET_DIAGGAUSS)
+    NF_TGT_ARM(NF_TARGET_BANANA)
+    NF_TGT_ARM(NF_TARGET_FUNNEL)
+    NF_TGT_ARM(NF_TARGET_WARPED)
+    default: break;
+  }
+#undef NF_TGT_ARM
+  f(std::integral_constant<int, LAST>{});
 }
 __host__ __device__ inline bool target_needs_d2(int kind) { return kind == NF_TARGET_WARPED || kind == NF_TARGET_CROSS; }
 // The linear-predictor kinds (NF_TARGET_DENSEGAUSS, NF_TARGET_LOGREG) couple every feature with every other through a

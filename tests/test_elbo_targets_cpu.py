@@ -34,7 +34,7 @@ RQ8, RQ10, RQ10L = "RqsGeo<1, 1, 1, 8, 4, 2>", "RqsGeo<1, 1, 1, 10, 2, 2>", "Rqs
 AFFINE = [f"void k_affine_chain_tgt<{g}, {v}, " for g in (H32, H64) for v in ("true, false, false", "false, false, true")]
 # k_rqs_chain_tgt<G, B6, TGT, NW>: every spline geometry; K = 8 also with the six-term output layer (its default)
 RQS = [f"void k_rqs_chain_tgt<{g}, false, " for g in (RQ8, RQ10, RQ10L)] + [f"void k_rqs_chain_tgt<{RQ8}, true, "]
-# TGT is a set of kinds (nf_target_epilogue.h: Banana 1, Funnel 2, WarpedGauss 4, Cross 8); every geometry serves all four
+# TGT is a set of kinds (nf_targets.h: Banana 1, Funnel 2, WarpedGauss 4, Cross 8); every geometry serves all four
 ALL_KINDS = 15
 
 

@@ -701,6 +701,51 @@ def test_planar_radial_lane_per_sample_steps_against_oracle(nf, kind, d, nl, n, 
     assert torch.equal(g, nf.value_and_gradient(nf.elbo_batch, flow, tgt, xs)[1]) and torch.equal(g2, nf.value_and_gradient(nf.elbo_batch, flow, tgt, n, rng=nf.PhiloxRNG(17))[1])
 
 
+TILE_N = 33  # two 32-sample tiles, the second with one valid lane
+TILE_CASES = [
+    ("planar", 2, 3, "warped"), ("planar", 2, 3, "cross"),      # PlanarGeo<1, 6>, the d = 2 kinds
+    ("planar", 2, 11, "warped"), ("planar", 2, 11, "cross"),    # PlanarGeo<1, 8>, the d = 2 kinds beyond three layers
+    ("planar", 8, 12, "banana"), ("planar", 8, 12, "funnel"),   # PlanarGeo<1, 8>
+    ("radial", 8, 12, "banana"), ("radial", 8, 12, "funnel"),   # RadialGeo<1, 16>
+]
+
+
+def tile_case(nf, kind, d, nl, tname):
+    """(flow, target, oracle target, spec, theta as the oracle takes it) of a TILE_CASES entry (also tools/simple_step_digest.py)"""
+    tgt, otgt = {"warped": (nf.WarpedGaussTarget(1.0, 0.12), ("warped", 1.0, 0.12)), "cross": (nf.CrossTarget(2.0, 0.15), ("cross", 2.0, 0.15)),
+                 "banana": (nf.BananaTarget(d, 0.3, 4.0), ("banana", 0.3, 4.0)), "funnel": (nf.FunnelTarget(d, -1.0, 1.5), ("funnel", -1.0, 1.5))}[tname]
+    spec = o.FlowSpec(kind, d, nl)
+    th64 = o.init_params(spec, np.random.default_rng(3)) * 0.3
+    flow = nf.Flow(kind, nf.MvNormal(d), nl, dtype=torch.float32, device="cuda", theta=torch.tensor(th64, dtype=torch.float32, device="cuda"))
+    return flow, tgt, otgt, spec, th64
+
+
+@pytest.mark.parametrize("kind,d,nl,tname", TILE_CASES)
+def test_planar_radial_tile_steps_reach_every_narrow_geometry(nf, kind, d, nl, tname):
+    """The one-block geometries the cases above do not reach (more than ten layers at d <= 32) and the two-dimensional
+    kinds in the tile kernels' target stage, at N = 33: two 32-sample tiles, the second with one valid lane.  Loss and
+    gradient against the oracle in both draw forms, the two forms' gradients bit for bit.  The float32 oracle errs by at
+    most 3.1e-7 (loss) and 6.6e-7 of |g|inf (gradient) against the float64 one on these inputs, so the 3 x float32-oracle
+    allowance of P.gradient is not what passes: the plain tolerances are asserted as well."""
+    n = TILE_N
+    flow, tgt, otgt, spec, th64 = tile_case(nf, kind, d, nl, tname)
+    xs = nf.device_specific_rand(nf.PhiloxRNG(17), flow.dist, n)
+    xs64 = xs.cpu().numpy().astype(np.float64)
+    lo, go = o.neg_elbo_value_and_grad(spec, th64, otgt, xs64)
+    _, g32 = o.neg_elbo_value_and_grad(spec, P.f32(th64), P.f32(otgt), P.f32(xs64))
+    got = {}
+    for form, arg in (("rng", n), ("xs", xs)):
+        loss, g = nf.value_and_gradient(nf.elbo_batch, flow, tgt, arg, rng=nf.PhiloxRNG(17))
+        tag = f"{kind} d{d} x{nl} n{n} {tname} ({form})"
+        print(f"{tag}: loss {loss!r} oracle {lo!r}")
+        P.scalar(f"{tag}: tile step loss", loss, lo)
+        gerr = P.gradient(f"{tag}: tile step grad", g, go, floor=g32)
+        print(f"{tag}: gradient error {gerr:.3e} of |g|inf")
+        assert gerr <= P.GRAD_RTOL, (tag, gerr)
+        got[form] = g
+    assert torch.equal(got["rng"], got["xs"])
+
+
 @pytest.mark.parametrize("kind,d,hd,nl,K,n", [
     ("nsf", 32, (64, 64), 2, 8, 333),       # the reference docstring's nsf(q0, [64, 64], 8, 3.0, .) widths (neuralspline.jl:215)
     ("nsf", 9, (48,), 1, 5, 1000),          # one hidden layer, K outside {8, 10}

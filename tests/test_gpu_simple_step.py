@@ -287,15 +287,19 @@ def _refused(nf, name):
         var = torch.tensor([0.8, 1.3, 1.1], dtype=torch.float64, device="cuda")
         f = nf.planarflow(nf.MvNormal(mu, var), 4, paramtype=torch.float64, seed=2)
         return f.with_theta(f.theta * 0.3), nf.BananaTarget(3, 1.0, 10.0), 97, NF_ERR_UNSUPPORTED, 0
+    if name == "warped_radial_d8":  # the same at a shape k_radial_step serves
+        f = nf.radialflow(nf.MvNormal(8), 4, paramtype=torch.float32, seed=2)
+        return f.with_theta(f.theta * 0.3), nf.WarpedGaussTarget(1.0, 0.12), 300, NF_ERR_UNSUPPORTED, NF_ERR_ARG
     f = nf.planarflow(nf.MvNormal(3), 4, paramtype=torch.float32, seed=2)  # WarpedGauss is two-dimensional
     return f.with_theta(f.theta * 0.3), nf.WarpedGaussTarget(1.0, 0.12), 300, NF_ERR_UNSUPPORTED, NF_ERR_ARG
 
 
-@pytest.mark.parametrize("name", ["planar_d200x30_f32", "hamiltonian", "planar_general_base", "warped_planar_d3"])
+@pytest.mark.parametrize("name", ["planar_d200x30_f32", "hamiltonian", "planar_general_base", "warped_planar_d3", "warped_radial_d8"])
 def test_flows_and_targets_without_the_fused_form_are_refused_by_the_graph_form(nf, name):
     """A planar flow beyond the one-launch step, a Hamiltonian flow, a planar flow over a general base: nf_elbo_step_enqueue
     answers NF_ERR_UNSUPPORTED with theta untouched and the counter at 0, and nf_elbo_step equals the split calls, loss and norm
-    included, bit for bit.  WarpedGauss at d = 3: NF_ERR_UNSUPPORTED from the graph form, NF_ERR_ARG from nf_elbo_step."""
+    included, bit for bit.  WarpedGauss at d = 3 (planar) and d = 8 (radial): NF_ERR_UNSUPPORTED from the graph form, NF_ERR_ARG from
+    nf_elbo_step, theta untouched."""
     lib = nf.load_library()
     flow, tgt, n, code_enqueue, code_step = _refused(nf, name)
     dt = flow.theta.dtype

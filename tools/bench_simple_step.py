@@ -4,7 +4,9 @@
   graph  -- replay of a captured nf_elbo_step_enqueue (None where the library answers NF_ERR_UNSUPPORTED).
 Shapes: (a) BASELINE cfg 1 -- planarflow d = 2, 10 layers, Float64, 1024 samples, Banana(2, 1, 10); (b) the same flow at the 32
 samples of example/demo_planar_flow.jl; (c) radialflow d = 2, 10 layers, Float64, 32 samples (example/demo_radial_flow.jl);
-(d) planarflow d = 64, 10 layers, Float32, 65 536 samples.
+(d) planarflow d = 64, 10 layers, Float32, 65 536 samples, Banana(64, 1, 10); (e) radialflow d = 64, 10 layers, Float32, 65 536 samples,
+Banana(64, 1, 10): a two-block k_radial_step outside the diagonal-Gaussian instantiation; (f) the planar flow of (d) with the
+Banana target named in the case (the shape of (d), whose target is Banana already: a second reading of that shape).
 Every figure is the median of --runs timed loops after a clock ramp of --ramp seconds of steps (bench.py's pre-warm convention);
 the spread (max - min) is printed next to it.  --lib PATH times another build of libnfhip.so (an A/B against an older commit:
 build it in a separate checkout and pass its library here; it is loaded instead of the in-tree one, never copied over it).
@@ -63,6 +65,8 @@ def main():
         ("b_demo_planar_d2x10_f64", lambda: scaled(nf.planarflow(q(2), 10, paramtype=f64, seed=1)), lambda: nf.BananaTarget(2, 1.0, 10.0), 32),
         ("c_demo_radial_d2x10_f64", lambda: scaled(nf.radialflow(q(2), 10, paramtype=f64, seed=1)), lambda: nf.BananaTarget(2, 1.0, 10.0), 32),
         ("d_planar_d64x10_f32", lambda: scaled(nf.planarflow(q(64), 10, paramtype=f32, seed=1)), lambda: nf.BananaTarget(64, 1.0, 10.0), 65536),
+        ("e_radial_d64x10_f32_banana", lambda: scaled(nf.radialflow(q(64), 10, paramtype=f32, seed=1)), lambda: nf.BananaTarget(64, 1.0, 10.0), 65536),
+        ("f_planar_d64x10_f32_banana", lambda: scaled(nf.planarflow(q(64), 10, paramtype=f32, seed=1)), lambda: nf.BananaTarget(64, 1.0, 10.0), 65536),
     ]
     want = [c for c in args.case.split(",") if c]
     vp = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731

@@ -66,7 +66,10 @@ extern "C" {
                                  log_eps(d/2)] -- the reference distribution's affine map FIRST (destructure of
                                  a TransformedDistribution whose `dist` is q0 = transformed(MvNormal, Shift o
                                  Scale), demo :135-137).  nf_param_count cannot detect a permuted theta: bind
-                                 by name, see INTEGRATION.md "theta order of the Hamiltonian demo flow" */
+                                 by name, see INTEGRATION.md "theta order of the Hamiltonian demo flow".
+                                 Limits (NF_ERR_UNSUPPORTED beyond them): d / 2 <= 32 (HF_MAXD), K <= 16 (HF_MAXL), and
+                                 the reverse kernels' gradient row of nf_param_count elements must fit 128 KiB of LDS:
+                                 at most 16 384 parameters in Float64, 32 768 in Float32. */
 
 #define NF_KIND_COMPOSITE 6 /* create_flow((L1, ..., Ln), q0) with MIXED bijector families (src/flows/utils.jl:23-26:
                                any list of bijectors composes).  `segments` lists the maximal runs of one family in FLAT

@@ -17,6 +17,9 @@
 #define HF_MAXD 32  // position dimensions (joint dimension 2D <= 64)
 #define HF_MAXL 16  // leapfrog steps per block
 #define HF_BLOCK 64
+// The reverse kernels keep one gradient row of P = 4D + 3Dn elements in dynamic LDS: the launch paths opt in to this many
+// bytes (the default limit is 64 KiB; a CU has 160 KiB) and nf_hf_supported refuses descriptors whose row is larger.
+#define HF_MAX_ROW_BYTES (128 * 1024)
 
 struct HfArgs {
   int D, n, L, tkind;
@@ -307,6 +310,8 @@ bool nf_hf_supported(const nf_flow_desc *desc) {
   if (desc->kind != NF_KIND_HAMILTONIAN) return false;
   if (desc->d < 2 || (desc->d & 1) || desc->d / 2 > HF_MAXD || desc->nlayers < 1) return false;
   if (desc->K < 1 || desc->K > HF_MAXL || !desc->score) return false;
+  const size_t row = (size_t)(2L * desc->d + 3L * (desc->d / 2) * desc->nlayers) * (desc->dtype == NF_DTYPE_F64 ? 8 : 4);
+  if (row > HF_MAX_ROW_BYTES) return false;  // the reverse kernels' LDS gradient row
   const int tk = desc->score->kind;
   if (tk == NF_TARGET_DIAGGAUSS) return desc->score->p0 && desc->score->p1;
   if (tk == NF_TARGET_BANANA) return desc->d / 2 >= 2 && desc->score->s1 > 0;
@@ -347,6 +352,16 @@ size_t nf_hf_bwd_ws_bytes(const nf_flow_desc *desc, long N) {
   return hf_stash_bytes(desc, N) + (size_t)hf_bwd_grid(N) * (size_t)hf_param_count(desc) * sizeof(double);
 }
 int nf_launch_reduce_slabs(nf_ctx *ctx, int dtype, const void *slab, int nslab, long P, void *g);
+// dynamic LDS beyond the default 64 KiB has to be asked for, once per kernel and device
+template <class T>
+static int hf_bwd_opt_in(nf_ctx *ctx) {
+  static AttrOnce attr_once;
+  return attr_once.run(ctx->device, [&]() -> int {
+    NF_HIP(hipFuncSetAttribute((const void *)k_hf_bwd<T>, hipFuncAttributeMaxDynamicSharedMemorySize, HF_MAX_ROW_BYTES));
+    NF_HIP(hipFuncSetAttribute((const void *)k_hf_bwd_inv<T>, hipFuncAttributeMaxDynamicSharedMemorySize, HF_MAX_ROW_BYTES));
+    return NF_OK;
+  });
+}
 
 int nf_hf_bwd(nf_ctx *ctx, const nf_flow_desc *desc, const void *theta, const void *x, const void *ybar, const void *lbar,
               double lbar_const, long N, void *xbar_out, void *gtheta_out, void *ws) {
@@ -360,6 +375,7 @@ int nf_hf_bwd(nf_ctx *ctx, const nf_flow_desc *desc, const void *theta, const vo
   const HfArgs a = make_hf_args(desc, N);
   const unsigned grid = hf_bwd_grid(N);
   char *slab = (char *)ws + hf_stash_bytes(desc, N);
+  NF_TRY(desc->dtype == NF_DTYPE_F64 ? hf_bwd_opt_in<double>(ctx) : hf_bwd_opt_in<float>(ctx));
   {
     ProfScope ps(ctx, "hf_bwd");
     if (desc->dtype == NF_DTYPE_F64)
@@ -385,6 +401,7 @@ int nf_hf_bwd_inv(nf_ctx *ctx, const nf_flow_desc *desc, const void *theta, cons
   const HfArgs a = make_hf_args(desc, N);
   const unsigned grid = hf_bwd_grid(N);
   char *slab = (char *)ws + hf_stash_bytes(desc, N);
+  NF_TRY(desc->dtype == NF_DTYPE_F64 ? hf_bwd_opt_in<double>(ctx) : hf_bwd_opt_in<float>(ctx));
   {
     ProfScope ps(ctx, "hf_bwd");
     if (desc->dtype == NF_DTYPE_F64)

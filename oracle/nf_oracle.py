@@ -1242,47 +1242,100 @@ def hflow_joint_logp(D, target, z):
     return target_logp(target, z[:D]) + std_normal_logpdf(z[D:])
 
 
-def hflow_neg_elbo_value_and_grad(D, n, L, theta, target, x0):
-    """loss = -mean_j [logp_joint(z_j) - log N(x0_j) + ladj_j] and its gradient, hand-derived: the LeapFrog
-    reverse pass needs Hessian-vector products of log p (target_hvp)."""
+def _leapfrog_bwd(target, eps, L, tr, xbar, vbar):
+    """Reverse pass of `_leapfrog` from its kept states tr[s] = (x_s, v_s, g(x_s)), s = 0..L: cotangents of (x_L, v_L)
+    in, cotangents of (x_0, rho) and of eps (per dimension and sample) out.  eps carries the sign of the time direction."""
+    ebar = np.zeros_like(xbar)
+    xs_, _, gs_ = tr[L]  # v_L = v_{L-1} + eps/2 g(x_L);  x_L = x_{L-1} + eps v_{L-1}
+    xbar = xbar + target_hvp(target, xs_, 0.5 * eps * vbar)
+    ebar += 0.5 * vbar * gs_
+    ebar += xbar * tr[L - 1][1]
+    vbar = vbar + eps * xbar
+    for s in range(L - 1, 0, -1):  # v_s = v_{s-1} + eps g(x_s);  x_s = x_{s-1} + eps v_{s-1}
+        xs_, _, gs_ = tr[s]
+        xbar = xbar + target_hvp(target, xs_, eps * vbar)
+        ebar += vbar * gs_
+        ebar += xbar * tr[s - 1][1]
+        vbar = vbar + eps * xbar
+    xs_, _, gs_ = tr[0]  # v_0 = rho + eps/2 g(x_0)
+    xbar = xbar + target_hvp(target, xs_, 0.5 * eps * vbar)
+    ebar += 0.5 * vbar * gs_
+    return xbar, vbar, ebar
+
+
+def hflow_bwd(D, n, L, theta, target, x0, ybar, lbar):
+    """Reverse pass of `hflow_fwd` at the flow input x0 for an output cotangent ybar (2D x N) and a per-sample log-det
+    cotangent lbar (N): (xbar, gtheta), hand-derived -- the LeapFrog reverse pass needs Hessian-vector products of
+    log p (target_hvp)."""
     N = x0.shape[1]
     keep = []
-    z, ladj = hflow_fwd(D, n, L, theta, target, x0, keep)
-    loss = -np.mean(hflow_joint_logp(D, target, z) - std_normal_logpdf(x0) + ladj)
+    hflow_fwd(D, n, L, theta, target, x0, keep)
     sh0, sc0, blocks = _hflow_views(D, n, theta)
     grad = np.zeros_like(theta)
-    zbar = np.concatenate([target_grad(target, z[:D]), -z[D:]], axis=0) * (-1.0 / N)
-    lbar = -1.0  # d loss / d (sum_j ladj_j / N) per sample, constant terms handled per parameter below
-    off_of = lambda bi: 4 * D + 3 * D * bi  # noqa: E731
+    zbar = np.asarray(ybar, dtype=theta.dtype)
+    lsum = np.broadcast_to(np.asarray(lbar, dtype=theta.dtype), (N,)).sum()  # ladj is the same function of theta for every sample
     for bi, zin, tr, vout in keep[::-1]:  # reverse of execution order = flat order bi = 0 .. n-1
         shr, scr, leps = blocks[bi]
         eps = np.exp(leps)[:, None]
-        o0 = off_of(bi)
-        xbar, rbar = zbar[:D].copy(), zbar[D:].copy()
+        o0 = 4 * D + 3 * D * bi
+        xbar, rbar = zbar[:D], zbar[D:]
         # momentum layer: rho' = shr + scr * v
         grad[o0 : o0 + D] += rbar.sum(axis=1)
-        grad[o0 + D : o0 + 2 * D] += (rbar * vout).sum(axis=1) + lbar / scr
-        vbar = rbar * scr[:, None]
-        # LeapFrog reverse (states tr[s] = (x_s, v_s, g(x_s)), s = 0..L)
-        ebar = np.zeros((D, N))
-        xs_, vs_, gs_ = tr[L]
-        xbar = xbar + target_hvp(target, xs_, 0.5 * eps * vbar)
-        ebar += 0.5 * vbar * gs_
-        vprev = tr[L - 1][1]
-        ebar += xbar * vprev
-        vbar = vbar + eps * xbar
-        for s in range(L - 1, 0, -1):
-            xs_, vs_, gs_ = tr[s]
-            xbar = xbar + target_hvp(target, xs_, eps * vbar)
-            ebar += vbar * gs_
-            vprev = tr[s - 1][1]
-            ebar += xbar * vprev
-            vbar = vbar + eps * xbar
-        xs_, vs_, gs_ = tr[0]
-        xbar = xbar + target_hvp(target, xs_, 0.5 * eps * vbar)
-        ebar += 0.5 * vbar * gs_
+        grad[o0 + D : o0 + 2 * D] += (rbar * vout).sum(axis=1) + lsum / scr
+        xbar, vbar, ebar = _leapfrog_bwd(target, eps, L, tr, xbar, rbar * scr[:, None])
         grad[o0 + 2 * D : o0 + 3 * D] += (ebar * eps).sum(axis=1)
         zbar = np.concatenate([xbar, vbar], axis=0)
     grad[: 2 * D] += zbar.sum(axis=1)
-    grad[2 * D : 4 * D] += (zbar * x0).sum(axis=1) + lbar / sc0
+    grad[2 * D : 4 * D] += (zbar * x0).sum(axis=1) + lsum / sc0
+    return zbar * sc0[:, None], grad
+
+
+def hflow_neg_elbo_value_and_grad(D, n, L, theta, target, x0):
+    """loss = -mean_j [logp_joint(z_j) - log N(x0_j) + ladj_j] and its gradient: `hflow_bwd` with
+    ybar = -(1/N) [grad log p(x); -rho] and lbar = -1/N."""
+    N = x0.shape[1]
+    z, ladj = hflow_fwd(D, n, L, theta, target, x0)
+    loss = -np.mean(hflow_joint_logp(D, target, z) - std_normal_logpdf(x0) + ladj)
+    ybar = np.concatenate([target_grad(target, z[:D]), -z[D:]], axis=0) * (-1.0 / N)
+    _, grad = hflow_bwd(D, n, L, theta, target, x0, ybar, np.full(N, -1.0 / N, dtype=theta.dtype))
+    return float(loss), grad
+
+
+def hflow_nll_value_and_grad(D, n, L, theta, target, us, n_global=None):
+    """loss = -(1/n_global) sum_j [log N(x0_j) + ladj_inv_j], (x0, ladj_inv) = hflow_inv(us), and its gradient: the
+    hand-derived reverse pass of the inverse chain (every inverse layer is explicit: the affine inverses and LeapFrog
+    with -eps).  n_global (default: the columns of us) is the sharded convention of loglikelihood_value_and_gradient."""
+    N = us.shape[1]
+    ng = N if n_global is None else n_global
+    sh0, sc0, blocks = _hflow_views(D, n, theta)
+    z, ladj = us, np.zeros(N, dtype=theta.dtype)
+    keep = []
+    for bi in range(n):
+        shr, scr, leps = blocks[bi]
+        rp = (z[D:] - shr[:, None]) / scr[:, None]
+        ladj = ladj - np.log(np.abs(scr)).sum()
+        tr = []
+        x, v = _leapfrog(target, -np.exp(leps)[:, None], L, z[:D], rp, tr)
+        keep.append((rp, tr))
+        z = np.concatenate([x, v], axis=0)
+    x0 = (z - sh0[:, None]) / sc0[:, None]
+    ladj = ladj - np.log(np.abs(sc0)).sum()
+    loss = -(std_normal_logpdf(x0) + ladj).sum() / ng
+    grad = np.zeros_like(theta)
+    lsum = -float(N) / ng  # sum over samples of d loss / d ladj_inv
+    b = (x0 / ng) / sc0[:, None]  # d loss / d x0 = x0 / n_global;  x0 = (z - sh0) / sc0
+    grad[: 2 * D] -= b.sum(axis=1)
+    grad[2 * D : 4 * D] -= (b * x0).sum(axis=1) + lsum / sc0
+    zbar = b
+    for bi in range(n - 1, -1, -1):
+        shr, scr, leps = blocks[bi]
+        rp, tr = keep[bi]
+        eps = -np.exp(leps)[:, None]
+        o0 = 4 * D + 3 * D * bi
+        xbar, vbar, ebar = _leapfrog_bwd(target, eps, L, tr, zbar[:D], zbar[D:])
+        grad[o0 + 2 * D : o0 + 3 * D] += (ebar * eps).sum(axis=1)  # d(-exp(log_eps)) / d log_eps = eps (signed)
+        b = vbar / scr[:, None]  # rho' = (rho - shr) / scr
+        grad[o0 : o0 + D] -= b.sum(axis=1)
+        grad[o0 + D : o0 + 2 * D] -= (b * rp).sum(axis=1) + lsum / scr
+        zbar = np.concatenate([xbar, b], axis=0)
     return float(loss), grad

@@ -108,10 +108,16 @@ def relerr(a, b):
     return float(np.linalg.norm(a - b) / den) if den > 0 else 0.0
 
 
-def scalar(key, got, ref, rtol=LOSS_RTOL, atol=0.0):
+def scalar(key, got, ref, rtol=LOSS_RTOL, atol=0.0, floor=None):
+    """relative error of a loss; with `floor` (the float32 oracle's value) the accepted relative error is
+    max(rtol, CFLOOR * the float32 oracle's own), as in `gradient`."""
     got, ref = float(got), float(ref)
     err = abs(got - ref) / max(abs(ref), 1e-300)
     record(key + " [rel err]", err)
+    if floor is not None:
+        ferr = abs(float(floor) - ref) / max(abs(ref), 1e-300)
+        record(key + " [fp32-oracle floor, rel err]", ferr)
+        rtol = max(rtol, CFLOOR * ferr)
     assert abs(got - ref) <= atol + rtol * abs(ref), f"{key}: {got} vs {ref} (rel {err:.3e} > {rtol})"
     return err
 

@@ -289,6 +289,82 @@ def test_hamiltonian_flow_oracle(tname):
     assert np.abs(g - gn).max() <= 1e-7 * max(1.0, np.abs(gn).max())
 
 
+HFLOW_REVERSE_CASES = [(tn, 3, 2, L, 7) for tn in ("funnel", "banana", "diaggauss") for L in (1, 3)] + [("diaggauss", 1, 2, 3, 7)]
+
+
+def _hflow_case(tname, D, n, seed):
+    rng = np.random.default_rng(seed)
+    tgt = {"funnel": ("funnel", -2.0, 3.0), "banana": ("banana", 1.0, 10.0),
+           "diaggauss": ("diaggauss", rng.standard_normal(D), rng.uniform(size=D) + 0.5)}[tname]
+    th = np.concatenate([0.1 * rng.standard_normal(2 * D), 1 + 0.1 * rng.standard_normal(2 * D)]
+                        + [np.concatenate([0.1 * rng.standard_normal(D), 1 + 0.1 * rng.standard_normal(D),
+                                           np.log(0.05) + 0.1 * rng.standard_normal(D)]) for _ in range(n)])
+    assert th.size == o.hflow_param_count(D, n)
+    return rng, tgt, th
+
+
+def _central(f, v, h=1e-6):
+    g = np.zeros(v.size)
+    for i in range(v.size):
+        vp, vm = v.copy().ravel(), v.copy().ravel()
+        vp[i] += h
+        vm[i] -= h
+        g[i] = (f(vp.reshape(v.shape)) - f(vm.reshape(v.shape))) / (2 * h)
+    return g.reshape(v.shape)
+
+
+@pytest.mark.parametrize("tname,D,n,L,N", HFLOW_REVERSE_CASES)
+def test_hamiltonian_flow_pullback_matches_finite_differences(tname, D, n, L, N):
+    """hflow_bwd for an arbitrary output cotangent ybar and per-sample log-det cotangent lbar: gtheta and xbar against
+    central differences of sum(ybar . z) + sum(lbar . ladj) in theta and in x0 (L = 1: the integrator's two half steps
+    meet with no whole step between them), at the step and tolerance of test_hamiltonian_flow_oracle."""
+    rng, tgt, th = _hflow_case(tname, D, n, 7)
+    x0 = rng.standard_normal((2 * D, N))
+    ybar, lbar = rng.standard_normal((2 * D, N)), rng.standard_normal(N)
+
+    def f(t, x):
+        z, ladj = o.hflow_fwd(D, n, L, t, tgt, x)
+        return (ybar * z).sum() + (lbar * ladj).sum()
+
+    xbar, g = o.hflow_bwd(D, n, L, th, tgt, x0, ybar, lbar)
+    assert xbar.shape == x0.shape and g.shape == th.shape
+    gn = _central(lambda t: f(t, x0), th)
+    assert np.abs(g - gn).max() <= 1e-7 * max(1.0, np.abs(gn).max())
+    xn = _central(lambda x: f(th, x), x0)
+    assert np.abs(xbar - xn).max() <= 1e-7 * max(1.0, np.abs(xn).max())
+
+
+@pytest.mark.parametrize("tname,D,n,L,N", HFLOW_REVERSE_CASES)
+def test_hamiltonian_flow_forward_kl_gradient_matches_finite_differences(tname, D, n, L, N):
+    """hflow_nll_value_and_grad (the reverse pass of the inverse chain) against central differences of its own loss, for a
+    whole batch and for a shard of a larger one (n_global)."""
+    rng, tgt, th = _hflow_case(tname, D, n, 8)
+    us = 0.7 * rng.standard_normal((2 * D, N))
+    for ng in (None, 19):
+        loss, g = o.hflow_nll_value_and_grad(D, n, L, th, tgt, us, n_global=ng)
+        x0, ladj = o.hflow_inv(D, n, L, th, tgt, us)
+        assert loss == pytest.approx(-(o.std_normal_logpdf(x0) + ladj).sum() / (ng or N), rel=1e-13)
+        gn = _central(lambda t: o.hflow_nll_value_and_grad(D, n, L, t, tgt, us, n_global=ng)[0], th)
+        assert np.abs(g - gn).max() <= 1e-7 * max(1.0, np.abs(gn).max())
+
+
+def test_hamiltonian_flow_neg_elbo_is_a_caller_of_the_pullback():
+    """hflow_neg_elbo_value_and_grad = hflow_bwd with ybar = -(1/N) [grad log p(x); -rho], lbar = -1/N; and the oracle stays
+    dtype-generic: float32 in, float32 out."""
+    D, n, L, N = 3, 2, 3, 7
+    rng, tgt, th = _hflow_case("banana", D, n, 9)
+    x0 = rng.standard_normal((2 * D, N))
+    z, _ = o.hflow_fwd(D, n, L, th, tgt, x0)
+    ybar = np.concatenate([o.target_grad(tgt, z[:D]), -z[D:]]) * (-1.0 / N)
+    _, g = o.hflow_bwd(D, n, L, th, tgt, x0, ybar, np.full(N, -1.0 / N))
+    np.testing.assert_array_equal(g, o.hflow_neg_elbo_value_and_grad(D, n, L, th, tgt, x0)[1])
+    th32, x32 = th.astype(np.float32), x0.astype(np.float32)
+    xb32, g32 = o.hflow_bwd(D, n, L, th32, tgt, x32, ybar.astype(np.float32), np.full(N, -1.0 / N, dtype=np.float32))
+    assert xb32.dtype == g32.dtype == np.float32
+    assert o.hflow_nll_value_and_grad(D, n, L, th32, tgt, x32)[1].dtype == np.float32
+    assert np.abs(g32 - g).max() <= 1e-4 * np.abs(g).max()
+
+
 @pytest.mark.parametrize("kind", list(SPECS))
 def test_loglikelihood_gradient_matches_finite_differences(kind):
     """Forward-KL training (train_flow(loglikelihood, ...)): the implicit-function reverse pass of the

@@ -2149,9 +2149,6 @@ static int affine_step_fused(nf_ctx *ctx, const nf_flow_desc *desc, const StepCa
 // step's pack.  Multi-rank contexts keep the split sequence (the all-reduce sits between the reduction and Adam).
 // sizing (nf_workspace_bytes): any target, whatever the communicator
 static bool step_fusable_rqs(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, bool sizing = false) {
-#ifdef NF_STEP_RQS_UNFUSED  // A/B builds (tools/ab_build.py): the generic sequence
-  return false;
-#endif
   if ((ctx->comm && !sizing) || flow_base(desc) || is_composite(desc) || desc->dtype != NF_DTYPE_F32) return false;
   return desc->kind == NF_KIND_NSF && nf_rqs_supported(desc) && elbo_fusable(desc, target, nullptr, sizing);
 }

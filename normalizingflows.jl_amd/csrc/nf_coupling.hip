@@ -14,16 +14,6 @@
 #include <type_traits>
 
 #include "nf_common.h"
-// A/B seams of this translation unit only (tools/ab_build.py): the split's subtractions / the leaky-ReLU slopes as scalar f32 instructions.
-// Packed f32 instructions do not overlap a matrix instruction in flight (tools/probe/mfma_valu_overlap_probe.hip: eight v_pk_add_f32
-// behind an MFMA cost 79.6 clocks against 42.4 for eight v_sub_f32), but here two scalar instructions per packed one buy nothing:
-// step 0.6042 / 0.6036 against 0.6040 ms over six alternating runs (profiles/r6l_pair_scalar_forms_ab2.txt)
-#ifdef NF_COUPLING_SPLIT_SCALAR
-#define NF_SPLIT_SCALAR
-#endif
-#ifdef NF_COUPLING_SLOPE_SCALAR
-#define NF_SLOPE_SCALAR
-#endif
 #include "nf_mfma.h"
 #include "nf_pack.h"
 #include "nf_philox.h"
@@ -133,12 +123,6 @@ struct ChainArgs {
 
 // the conditioner net on the bf16 matrix cores (nf_mfma.h "B6"): same layers, the image is a B6Geo<G> image
 // PIPE: the layers as software pipelines (dense_fwd_b6p); false: the plain form, 44 registers less (three waves per SIMD)
-#ifndef NF_CHAIN_LRIN
-#define NF_CHAIN_LRIN 1
-#endif
-#ifndef NF_CHAIN_LEAN
-#define NF_CHAIN_LEAN false  // the plain form without its operand double buffer (12 registers less)
-#endif
 template <class G, bool PIPE = true>
 __device__ __forceinline__ void net_forward_b6(const float *__restrict__ img, const f32x16 (&x)[G::MB], f32x16 (&out)[G::CB],
                                                int l31, int hi) {
@@ -146,22 +130,19 @@ __device__ __forceinline__ void net_forward_b6(const float *__restrict__ img, co
   const nf_u32x4 *w = reinterpret_cast<const nf_u32x4 *>(img);
   const float *bias = reinterpret_cast<const float *>(w + B::BIAS);
   f32x16 a1[G::H1B], a2[G::H2B];
-  if constexpr (PIPE && NF_CHAIN_LRIN) {  // the leaky ReLUs inside the next layer's splits (dense_fwd_b6p<..., LRIN>): same values, same bits
+  if constexpr (PIPE) {  // the leaky ReLUs inside the next layer's splits (dense_fwd_b6p<..., LRIN>): same values, same bits
     dense_fwd_b6p<G::MB, G::H1B>(w + B::L1, bias + B::B1, x, a1, l31, hi);
     dense_fwd_b6p<G::H1B, G::H2B, true>(w + B::L2, bias + B::B2, a1, a2, l31, hi);
     dense_fwd_b6p<G::H2B, G::CB, true>(w + B::L3, bias + B::B3, a2, out, l31, hi);
-    return;
+  } else {
+    dense_fwd_b6<G::MB, G::H1B>(w + B::L1, bias + B::B1, x, a1, l31, hi);
+#pragma unroll
+    for (int b = 0; b < G::H1B; ++b) nf_lrelu16(a1[b]);
+    dense_fwd_b6<G::H1B, G::H2B>(w + B::L2, bias + B::B2, a1, a2, l31, hi);
+#pragma unroll
+    for (int b = 0; b < G::H2B; ++b) nf_lrelu16(a2[b]);
+    dense_fwd_b6<G::H2B, G::CB>(w + B::L3, bias + B::B3, a2, out, l31, hi);
   }
-  if constexpr (PIPE) dense_fwd_b6p<G::MB, G::H1B>(w + B::L1, bias + B::B1, x, a1, l31, hi);
-  else dense_fwd_b6<G::MB, G::H1B, NoSideJob, NF_CHAIN_LEAN>(w + B::L1, bias + B::B1, x, a1, l31, hi);
-#pragma unroll
-  for (int b = 0; b < G::H1B; ++b) nf_lrelu16(a1[b]);
-  if constexpr (PIPE) dense_fwd_b6p<G::H1B, G::H2B>(w + B::L2, bias + B::B2, a1, a2, l31, hi);
-  else dense_fwd_b6<G::H1B, G::H2B, NoSideJob, NF_CHAIN_LEAN>(w + B::L2, bias + B::B2, a1, a2, l31, hi);
-#pragma unroll
-  for (int b = 0; b < G::H2B; ++b) nf_lrelu16(a2[b]);
-  if constexpr (PIPE) dense_fwd_b6p<G::H2B, G::CB>(w + B::L3, bias + B::B3, a2, out, l31, hi);
-  else dense_fwd_b6<G::H2B, G::CB, NoSideJob, NF_CHAIN_LEAN>(w + B::L3, bias + B::B3, a2, out, l31, hi);
 }
 
 struct NoBetween {
@@ -423,7 +404,7 @@ struct FusedArgs {
 // holds THREE of them and rotates per NET instead of two (s, t) pairs per coupling: image i of the workgroup's sequence
 // s(c0), t(c0), s(c1), ... lives in slot i mod 3; the phase of image i starts with a workgroup barrier (image i complete,
 // everybody done with image i - 1) and then requests image i + 2 into the slot image i - 1 just left.
-// NW: wavefronts (= tiles of a group) per workgroup; 12 (three per SIMD) where the instantiation fits 168 registers (round 6)
+// NW: wavefronts (= tiles of a group) per workgroup: 8, or 4 for the k_affine_chain_tgt forms that do not fit 256 registers (launch_chain)
 // TGT (the body of k_affine_chain_tgt, FUSED forward only): the epilogue evaluates one of the other four built-in targets
 // (fa.tkind, nf_target_epilogue.h) instead of the diagonal Gaussian; everything before it is the same code.
 template <class G, bool INVERSE, bool FUSED, bool STASH, bool SLIM, bool B6, int NW, bool TGT>
@@ -575,14 +556,12 @@ __device__ __forceinline__ void affine_chain_body(ChainArgs a, float *xt, float 
           // t net and tile), so "at most 60 operations outstanding" already implies the DMA is done, while __syncthreads()
           // (vmcnt(0)) would drain the stores to HBM twice per coupling.  Kernels without a stash wait for everything.
           auto phase_barrier = [&](bool first_of_group = false) {
-#ifndef NF_B6_FULL_DRAIN
             if (STASH && !first_of_group) {  // (a tile group's first image may have nothing but the DMA behind it)
               __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
               __builtin_amdgcn_s_waitcnt(0xC07C);  // vmcnt(60) lgkmcnt(0)
               __builtin_amdgcn_s_barrier();
               __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             } else
-#endif
               __syncthreads();
           };
           phase_barrier(s == 0 && half == 0);  // this coupling's s image is complete, every wave is done with the image before it
@@ -778,154 +757,15 @@ __device__ __forceinline__ void affine_chain_body(ChainArgs a, float *xt, float 
   }
   if (FUSED && tid == 0) fa.partial[blockIdx.x] = wg_total;
 }
-template <class G, bool INVERSE, bool FUSED = false, bool STASH = false, bool SLIM = false, bool B6 = false, int NW = 8>
-__global__ __launch_bounds__(64 * NW) void k_affine_chain(ChainArgs a, float *xt, float *__restrict__ ladj, FusedArgs fa) {
-  affine_chain_body<G, INVERSE, FUSED, STASH, SLIM, B6, NW, false>(a, xt, ladj, fa);
+template <class G, bool INVERSE, bool FUSED = false, bool STASH = false, bool SLIM = false, bool B6 = false>
+__global__ __launch_bounds__(512) void k_affine_chain(ChainArgs a, float *xt, float *__restrict__ ladj, FusedArgs fa) {
+  affine_chain_body<G, INVERSE, FUSED, STASH, SLIM, B6, 8, false>(a, xt, ladj, fa);
 }
 // The fused ELBO forward for the Banana, Funnel, WarpedGauss and Cross targets: k_affine_chain<G, false, true, STASH, SLIM, B6>'s
 // draws, chain and stash with the target switch as its epilogue (one instantiation per geometry serves the four kinds).
 template <class G, bool STASH, bool SLIM = false, bool B6 = false, int NW = 8>
 __global__ __launch_bounds__(64 * NW) void k_affine_chain_tgt(ChainArgs a, float *xt, FusedArgs fa) {
   affine_chain_body<G, false, true, STASH, SLIM, B6, NW, true>(a, xt, nullptr, fa);
-}
-
-// ------------------------------------------------------------------------------------
-// the six-term chain WITHOUT a stash, two tiles per wavefront (round 6)
-// ------------------------------------------------------------------------------------
-// tools/trace_chain_b6.py on k_affine_chain<..., B6> at cfg 5: the two waves of a SIMD do not overlap -- the older one runs its net
-// in 5.4 k clocks (96 MFMAs = 3.1 k) and then waits 5 k at the phase barrier for the younger one, which only gets the issue slots the
-// older leaves (9-10 k per net): a phase is the SUM of the two.  Here ONE wave per SIMD (256 threads, up to 512 registers) carries two
-// tiles through every net with their instruction streams interleaved by construction (dense_fwd_b6p2): one tile's splits and layer
-// boundaries ride in the other's matrix instructions, the weight operands are read from LDS once for both.  Same images, same rotation
-// (three LDS slots, one per net), same per-accumulator term order as k_affine_chain (parity suite green with NF_CHAIN_DUAL=1).
-template <class G>
-__device__ __forceinline__ void net_forward_b6_dual(const float *__restrict__ img, const f32x16 (&x0)[G::MB], const f32x16 (&x1)[G::MB],
-                                                    f32x16 (&out0)[G::CB], f32x16 (&out1)[G::CB], int l31, int hi) {
-  using B = B6Geo<G>;
-  const nf_u32x4 *w = reinterpret_cast<const nf_u32x4 *>(img);
-  const float *bias = reinterpret_cast<const float *>(w + B::BIAS);
-  f32x16 a10[G::H1B], a11[G::H1B], a20[G::H2B], a21[G::H2B];
-  dense_fwd_b6p2<G::MB, G::H1B>(w + B::L1, bias + B::B1, x0, x1, a10, a11, l31, hi);
-#pragma unroll
-  for (int b = 0; b < G::H1B; ++b) { nf_lrelu16(a10[b]); nf_lrelu16(a11[b]); }
-  dense_fwd_b6p2<G::H1B, G::H2B>(w + B::L2, bias + B::B2, a10, a11, a20, a21, l31, hi);
-#pragma unroll
-  for (int b = 0; b < G::H2B; ++b) { nf_lrelu16(a20[b]); nf_lrelu16(a21[b]); }
-  dense_fwd_b6p2<G::H2B, G::CB>(w + B::L3, bias + B::B3, a20, a21, out0, out1, l31, hi);
-}
-
-template <class G, bool INVERSE>
-__global__ __launch_bounds__(256, 1) void k_affine_chain_dual(ChainArgs a, float *xt, float *__restrict__ ladj) {
-  static_assert(G::MB == G::CB, "parity blocks must have equal padded size");
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l31 = lane & 31, hi = lane >> 5;
-  const long ntiles = (a.N + NF_TILE - 1) / NF_TILE;
-  const long ngroups = (ntiles + 7) / 8;
-  auto coupling_at = [&](int s) { return INVERSE ? s : a.ncoup - 1 - s; };
-  using BG = B6Geo<G>;
-  constexpr int B6F = BG::BYTES / 4;
-  const int my_groups = (long)blockIdx.x < ngroups ? (int)((ngroups - blockIdx.x + gridDim.x - 1) / gridDim.x) : 0;
-  const int my_images = my_groups * 2 * a.ncoup;
-  int req = 0, req_idx = 0, req_slot = 0;
-  auto b6_request_next = [&]() {  // as k_affine_chain's: image i of the sequence s(c0), t(c0), s(c1), ... -> slot i mod 3 by LDS-DMA
-    if (req >= my_images) return;
-    typedef __attribute__((address_space(3))) void lds_void_t;
-    const int kk = coupling_at(req_idx >> 1);
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<unsigned char *>(a.wimg_b6) + (size_t)(2 * kk + (req_idx & 1)) * BG::BYTES, 0, BG::BYTES, 0x00020000);
-    float *dstb = lds + req_slot * B6F;
-    constexpr int NP = (BG::BYTES + 1023) / 1024;
-    for (int p = wave; p < NP; p += 4)
-      if (p * 1024 + lane * 16 < BG::BYTES)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void_t *)(dstb + p * 256), 16, lane * 16, p * 1024, 0, 0);
-    ++req;
-    req_idx = req_idx + 1 == 2 * a.ncoup ? 0 : req_idx + 1;
-    req_slot = req_slot == 2 ? 0 : req_slot + 1;
-  };
-  int cur_slot = 0;
-  b6_request_next();
-  b6_request_next();
-  for (long grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
-    f32x16 E[2][G::CB], O[2][G::MB];
-    TileIO io[2];
-    bool live[2], valid[2];
-    long jj[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const long tile = grp * 8 + 2 * wave + t;
-      live[t] = tile < ntiles;  // wave-uniform
-      const long tl = live[t] ? tile : 0;
-      jj[t] = tl * NF_TILE + l31;
-      valid[t] = live[t] && jj[t] < a.N;
-      io[t] = make_tile_io(xt, tl, a.d, l31, hi);
-#pragma unroll
-      for (int b = 0; b < G::CB; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float e = tile_load(io[t], tile_soff(b, r, 0));  // features >= d read as 0
-          const float o = tile_load(io[t], tile_soff(b, r, 1));
-          E[t][b][r] = valid[t] ? e : 0.f;
-          O[t][b][r] = valid[t] ? o : 0.f;
-        }
-    }
-    float lsum[2] = {0.f, 0.f};
-#pragma unroll 1
-    for (int s = 0; s < a.ncoup; s += 2) {
-#pragma unroll
-      for (int half = 0; half < 2; ++half) {
-        __syncthreads();    // this coupling's s image is complete, every wave is done with the image before it
-        b6_request_next();  // the image after next, into the slot just vacated
-        const int slot_t = cur_slot == 2 ? 0 : cur_slot + 1;
-        const float *img_s = lds + cur_slot * B6F, *img_t = lds + slot_t * B6F;
-        const bool x1_is_O = INVERSE ? (half == 1) : (half == 0);
-        f32x16 (&x10)[G::CB] = x1_is_O ? O[0] : E[0];
-        f32x16 (&x11)[G::CB] = x1_is_O ? O[1] : E[1];
-        const f32x16 (&xb0)[G::MB] = x1_is_O ? E[0] : O[0];
-        const f32x16 (&xb1)[G::MB] = x1_is_O ? E[1] : O[1];
-        f32x16 S0[G::CB], S1[G::CB], T0[G::CB], T1[G::CB];
-        float ls0 = 0.f, ls1 = 0.f;  // per coupling first, as coupling_step returns it: the same bits in ladj
-        net_forward_b6_dual<G>(img_s, xb0, xb1, S0, S1, l31, hi);
-        __syncthreads();  // the t image is complete, every wave is done with the s image
-        b6_request_next();
-        net_forward_b6_dual<G>(img_t, xb0, xb1, T0, T1, l31, hi);
-#pragma unroll
-        for (int b = 0; b < G::CB; ++b)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            // rows >= c have zero weights and biases in the packed image: s = 0, T = 0, x1 stays 0
-            const float s0 = nf_tanh(S0[b][r]), s1 = nf_tanh(S1[b][r]);
-            if (INVERSE) {
-              x10[b][r] = nf_fdiv(x10[b][r] - T0[b][r], nf_exp(s0));
-              x11[b][r] = nf_fdiv(x11[b][r] - T1[b][r], nf_exp(s1));
-            } else {
-              x10[b][r] = x10[b][r] * nf_exp(s0) + T0[b][r];
-              x11[b][r] = x11[b][r] * nf_exp(s1) + T1[b][r];
-            }
-            ls0 += s0;
-            ls1 += s1;
-          }
-        lsum[0] += ls0;
-        lsum[1] += ls1;
-        cur_slot = slot_t == 2 ? 0 : slot_t + 1;
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      if (!live[t]) continue;
-#pragma unroll
-      for (int b = 0; b < G::CB; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          tile_store(io[t], tile_soff(b, r, 0), E[t][b][r]);
-          tile_store(io[t], tile_soff(b, r, 1), O[t][b][r]);
-        }
-      float ls = lsum[t];
-      ls += __shfl_xor(ls, 32);
-      if (hi == 0 && valid[t]) ladj[jj[t]] = INVERSE ? -ls : ls;
-    }
-  }
 }
 
 // ------------------------------------------------------------------------------------
@@ -1721,63 +1561,24 @@ __global__ __launch_bounds__(256, 1) void k_affine_bwd_stashed(BwdAllArgs aa, fl
 //   consumer: a2 loads  | B1 | dW3 (d3)       | B2 | dW2 (d2)       | B3 | dW1 (d1)
 // One buffer per delta suffices: d3 of the next tile is written after B3, when dW3 has long read it (before B2), etc.
 // Whole tiles only (d = 64, N a multiple of 32) and every pair the same number of tiles (barriers inside the tile loop).
-#ifndef NF_PAIR_DW_B6
-#define NF_PAIR_DW_B6 0  // bit mask: which of the consumer's dW GEMMs (1: dW3, 2: dW2, 4: dW1) run on the bf16 matrix cores as well.
-// Measured (profiles/r4m_pair_b6_ab.txt): 7 -> 613 us per launch (392 bytes of scratch: the consumer holds 128 accumulators and the
-// split operands do not fit the remaining registers), 6 -> 591, 4 -> 338, 0 -> 334 (the producer's dX GEMMs only; fp32: 365).
-#endif
 // PB6 (round 4): the producer's three dX GEMMs on the bf16 matrix cores (dense_bwd_x_b6); the LDS then holds the net's
 // B6T image instead of the fp32 one -- nobody else reads weights in this kernel (the consumer contracts activations with
 // deltas), except the SLIM stash's a1 recompute, which therefore keeps the fp32 image.
 // DW6 (with PB6): the consumer's dW GEMMs on the bf16 cores as well.  The producer splits every cotangent once (it needs the
-// triples for its own dX GEMM), leaves them in LDS transposed (split_to_lds) instead of the fp32 tile, and the consumer splits
-// only the stashed activations.  Two triple buffers per pair, used alternately (d3 | d2 | d1 | next d3 | ...): a buffer is
-// rewritten two barriers after the GEMM that read it.
-#ifndef NF_PAIR_CONS_PRIO
-#define NF_PAIR_CONS_PRIO 0  // s_setprio of the consumer waves (A/B builds).  Measured (profiles/r6h_pair_consumer_prio_ab.txt): 1 and 3 alike
-// 331-338 us against 316-322 -- the consumer's stages shorten (dW3 3.7 -> 2.6 k clocks, dW2 5.3 -> 4.55 k) and the producer's grow by
-// more (prologue 3.6 -> 7.4 k, dX2 3.2 -> 5.4 k): the arbitration is all or nothing, and the two waves' issue work in a stage adds up
-#endif
+// triples for its own dX GEMM), leaves them in LDS (split_to_lds_tr: the consumer's ds_read_b64_tr_b16 transposes them, nf_mfma.h)
+// instead of the fp32 tile, and the consumer splits only the stashed activations.  Two triple buffers per pair, used alternately
+// (d3 | d2 | d1 | next d3 | ...): a buffer is rewritten two barriers after the GEMM that read it.
+// Both roles of the DW6 form run in ANTI-PHASE: the producer's stages are [matrix burst | vector burst], the consumer's
+// [vector burst | matrix burst] -- two mixed streams on one SIMD add up, a matrix burst and a vector burst overlap
+// (tools/probe/mfma_valu_overlap_probe.hip; the woven forms it replaced: tools/experiments/README.md).
 #ifndef NF_TRACE_PAIR
 #define NF_TRACE_PAIR 0  // trace builds: which of the workgroup's four pairs tools/trace_bwd_pair.py sees
-#endif
-#ifndef NF_PAIR_SPREAD
-#define NF_PAIR_SPREAD 0
-#endif
-#ifndef NF_PAIR_MSPLIT
-#define NF_PAIR_MSPLIT 0  // bit 1: the anti-phase consumer's splits through nf_split16_mfma
-#endif
-#ifndef NF_PAIR_ANTI
-#define NF_PAIR_ANTI 3  // bit 0: the producer's stages as [matrix burst | vector burst]; bit 1: the consumer's as [vector burst | matrix burst]
-// -- ANTI-PHASE instead of woven streams (the probe: two mixed streams on one SIMD add up, a matrix burst and a vector burst overlap).
-// Measured (profiles/r6w_pair_anti_phase_ab*.txt, alternating on one box): kernel 314.3 (0) / 320.5 (1) / 310.7 (2) / 307.7 us (3), step
-// 0.5775 -> 0.5737 ms over eight pairs of runs (3 against 0).  Far less than the probe's ideal: the consumer's stage is its own serial
-// [split 1.9 k | TR reads, 48 MFMAs, dots 2.6 k clocks] whatever the producer does beside it.  Same operations in the same order per
-// accumulator: bit-identical results.
-#endif
-#ifndef NF_PAIR_WEAVE
-#define NF_PAIR_WEAVE 1  // the consumer's splits of a1 / x2 in the issue shadows of dW3's / dW2's last matrix instructions (SplitTJob,
-// nf_mfma.h) instead of behind them: 301.7-305.3 against 305.7-309.8 us alternating on one box (profiles/r6j_pair_weave_ab.txt); the
-// same instructions on the same values, results bit-identical.  The traced stages barely move (dW3 3.7 k, dW2 5.1-5.3 k clocks): a
-// stage's length is the two waves' matrix instructions taking turns on the pipe, not either wave's vector work
-#endif
-#ifndef NF_PAIR_TR
-#define NF_PAIR_TR 1  // the producer -> consumer hand-over of the cotangent triples through ds_read_b64_tr_b16 (nf_mfma.h, round 6); 0: split_to_lds
-#endif
-#if NF_PAIR_TR
-#define NF_PAIR_BUF TR_BUF
-#define NF_PAIR_PUT(NB, buf, s) split_to_lds_tr<NB>(buf, s, l31, hi)
-#define NF_PAIR_DW(IB, OB, as, buf, w, b) dw_accumulate_tr6<IB, OB>(as, buf, w, b, l31, hi)
-#else
-#define NF_PAIR_BUF D6_BUF
-#define NF_PAIR_PUT(NB, buf, s) split_to_lds<NB>(buf, s, l31, hi)
-#define NF_PAIR_DW(IB, OB, as, buf, w, b) dw_accumulate_t6<IB, OB>(as, buf, w, b, l31, hi)
 #endif
 template <class G, bool PB6 = false, bool DW6 = false>
 struct BwdPairLds {
   static_assert(!DW6 || (PB6 && G::CB <= 2 && G::H1B <= 2 && G::H2B <= 2), "triple buffers hold two blocks");
   static constexpr int D3 = 0, D2 = D3 + G::CB * 32 * NF_TS, D1 = D2 + G::H2B * 32 * NF_TS;
-  static constexpr int PAIR = DW6 ? 2 * NF_PAIR_BUF / 4 : D1 + G::H1B * 32 * NF_TS;
+  static constexpr int PAIR = DW6 ? 2 * TR_BUF / 4 : D1 + G::H1B * 32 * NF_TS;
   static constexpr int PAIRS = 4;
   static constexpr int IMG = PB6 ? B6TGeo<G>::BYTES / 4 : G::SIZE;  // floats of the staged weight image
   static constexpr int FLOATS = (IMG + PAIRS * PAIR) > PAIRS * G::SIZE ? (IMG + PAIRS * PAIR) : PAIRS * G::SIZE;
@@ -1802,20 +1603,15 @@ struct BwdPairLds {
 // born (its phase S still re-reads the half from memory, so its store stays) -- the live peak stays 48 registers.  The first
 // processed coupling's g1 of both tiles is loaded into the same registers in front of the coupling loop, so that no body has a
 // run-time branch around its prologue loads.  The same bits either way: the value kept is the value stored.
-#ifndef NF_PAIR_CARRY
-#define NF_PAIR_CARRY 2  // how many of the parked slots carry (A/B builds: 0 none, 1 slot 0 only)
-#endif
-// Whole batches at d = 64 (FULL) only: in the ragged / d < 64 form the masks' state no longer fits beside a carried tile, which
+// Both parked slots carry, in whole batches at d = 64 (FULL) only: in the ragged / d < 64 form the masks' state no longer fits beside a carried tile, which
 // phase S's slot-1 body holds on top of its own parked registers -- 20 bytes of scratch with both slots carried, 12 with slot 0
 // alone.  That form keeps the round trip between couplings.
-template <bool FULL>
-constexpr int pair_carry() { return FULL ? NF_PAIR_CARRY : 0; }
 #define NF_PAIR_PARK 2
 #define NF_PAIR_PARK_G1 1
 template <class G>
 struct PairPark {
   f32x16 g1[NF_PAIR_PARK_G1][G::CB], g2[NF_PAIR_PARK][G::MB];
-  f32x16 cy[G::CB];  // slot 1's carry (NF_PAIR_CARRY > 1)
+  f32x16 cy[G::CB];  // slot 1's carry
 };
 
 // FULL: d = 64 and N a multiple of the tile (no sample / feature masks).  INVD: reverse pass of the INVERSE coupling
@@ -1834,7 +1630,7 @@ __device__ __forceinline__ void pair_produce(const CouplingArgs &a, const float 
                                              long next_tile, bool live, int l31, int hi, int par, long long *tr = nullptr) {
   using SG = StashGeo<G, SLIM>;
   using L = BwdPairLds<G, PB6, DW6>;
-  char *bufa = reinterpret_cast<char *>(sp) + par * NF_PAIR_BUF, *bufb = reinterpret_cast<char *>(sp) + (par ^ 1) * NF_PAIR_BUF;  // DW6
+  char *bufa = reinterpret_cast<char *>(sp) + par * TR_BUF, *bufb = reinterpret_cast<char *>(sp) + (par ^ 1) * TR_BUF;  // DW6
   if (!live) {
     __syncthreads();
     __syncthreads();
@@ -1852,8 +1648,8 @@ __device__ __forceinline__ void pair_produce(const CouplingArgs &a, const float 
   constexpr bool FIRST = PHASE_S == INVD;  // the coupling's first phase
   constexpr bool parked = SLOT >= 0, parked1 = SLOT >= 0 && SLOT < NF_PAIR_PARK_G1;
   constexpr int S2 = SLOT < 0 ? 0 : SLOT, S1 = parked1 ? SLOT : 0;
-  constexpr bool carried = !INVD && SLOT >= 0 && SLOT < pair_carry<FULL>();  // g1 of phase T arrives in registers, phase S leaves the next one
-  static_assert(!carried || (G::CB == G::MB && SLOT < 2 && NF_PAIR_CARRY <= NF_PAIR_PARK), "a conditioner half becomes a transformed half");
+  constexpr bool carried = !INVD && SLOT >= 0 && SLOT < (FULL ? 2 : 0);  // g1 of phase T arrives in registers, phase S leaves the next one
+  static_assert(!carried || (G::CB == G::MB && SLOT < 2), "a conditioner half becomes a transformed half");
   f32x16 g1[G::CB];
   if constexpr (carried && !PHASE_S) {
 #pragma unroll
@@ -1905,7 +1701,7 @@ __device__ __forceinline__ void pair_produce(const CouplingArgs &a, const float 
   SplitC<DW6 ? G::CB : 1> s3;
   if constexpr (DW6) {
     split_C<G::CB>(d3, s3);
-    NF_PAIR_PUT(G::CB, bufa, s3);
+    split_to_lds_tr<G::CB>(bufa, s3, l31, hi);
   } else {
     tile_to_scratch<G::CB>(sp + L::D3, d3, l31, hi);
   }
@@ -1920,66 +1716,37 @@ __device__ __forceinline__ void pair_produce(const CouplingArgs &a, const float 
   f32x16 d2[G::H2B];
   const nf_u32x4 *wt = reinterpret_cast<const nf_u32x4 *>(img);  // PB6: the staged image is the net's B6T image
   SplitC<DW6 ? G::H2B : 1> s2;
-#if NF_PAIR_TR
-  // (round 6) the GEMM block by block: what follows a finished block of d2 -- slopes, split, hand-over stores -- rides in the
-  // issue shadows of the next block's matrix instructions; only the last block's share is left behind the GEMM
+  // DW6: the lane's two chunk addresses in the pair's first hand-over buffer (split_to_lds_tr's)
   const int xw = (l31 >> 2) & 3;
   char *const pw0 = reinterpret_cast<char *>(sp) + l31 * 32 + 8 * (hi ^ xw), *const pw1 = reinterpret_cast<char *>(sp) + l31 * 32 + 8 * ((2 + hi) ^ xw);
-  if constexpr (DW6) {
+  if constexpr (DW6) {  // the GEMM as ONE burst of matrix instructions, then ONE burst of vector work: slopes, split, hand-over stores
     const PairPost<G::H2B> post{d2, m2, s2, pw0 + (bufb - reinterpret_cast<char *>(sp)), pw1 + (bufb - reinterpret_cast<char *>(sp))};
-#if NF_PAIR_ANTI & 1  // the GEMM as ONE burst of matrix instructions, then ONE burst of vector work (see NF_PAIR_ANTI)
     dense_bwd_x_b6s<G::H2B, G::CB>(wt + B6TGeo<G>::T3, s3, d2, l31, hi);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int b = 0; b < G::H2B; ++b) post.all(b);
-#else
-    dense_bwd_x_b6s_blocks<G::H2B, G::CB>(wt + B6TGeo<G>::T3, s3, d2, l31, hi, [&](int ib, int i) { if (ib > 0) post.template at_hook<24 * G::CB>(ib - 1, i); });
-    post.all(G::H2B - 1);
-#endif
-  } else
-#endif
-  {
-  if constexpr (DW6) dense_bwd_x_b6s<G::H2B, G::CB>(wt + B6TGeo<G>::T3, s3, d2, l31, hi);
-  else if constexpr (PB6) dense_bwd_x_b6<G::H2B, G::CB>(wt + B6TGeo<G>::T3, d3, d2, l31, hi);
-  else dense_bwd_x<G::H2B, G::CB>(img + G::W3, d3, d2, l31, hi);
-  apply_lrelu_grad<G::H2B>(d2, m2);
-  if constexpr (DW6) {
-    split_C<G::H2B>(d2, s2);
-    NF_PAIR_PUT(G::H2B, bufb, s2);
   } else {
+    if constexpr (PB6) dense_bwd_x_b6<G::H2B, G::CB>(wt + B6TGeo<G>::T3, d3, d2, l31, hi);
+    else dense_bwd_x<G::H2B, G::CB>(img + G::W3, d3, d2, l31, hi);
+    apply_lrelu_grad<G::H2B>(d2, m2);
     tile_to_scratch<G::H2B>(sp + L::D2, d2, l31, hi);
-  }
   }
   NF_TS_STAMP(3);
   __syncthreads();  // B2
   NF_TS_STAMP(4);
   f32x16 d1[G::H1B];
   SplitC<DW6 ? G::H1B : 1> s1;
-#if NF_PAIR_TR
   if constexpr (DW6) {
     const PairPost<G::H1B> post{d1, m1, s1, pw0 + (bufa - reinterpret_cast<char *>(sp)), pw1 + (bufa - reinterpret_cast<char *>(sp))};
-#if NF_PAIR_ANTI & 1
     dense_bwd_x_b6s<G::H1B, G::H2B>(wt + B6TGeo<G>::T2, s2, d1, l31, hi);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int b = 0; b < G::H1B; ++b) post.all(b);
-#else
-    dense_bwd_x_b6s_blocks<G::H1B, G::H2B>(wt + B6TGeo<G>::T2, s2, d1, l31, hi, [&](int ib, int i) { if (ib > 0) post.template at_hook<24 * G::H2B>(ib - 1, i); });
-    post.all(G::H1B - 1);
-#endif
-  } else
-#endif
-  {
-  if constexpr (DW6) dense_bwd_x_b6s<G::H1B, G::H2B>(wt + B6TGeo<G>::T2, s2, d1, l31, hi);
-  else if constexpr (PB6) dense_bwd_x_b6<G::H1B, G::H2B>(wt + B6TGeo<G>::T2, d2, d1, l31, hi);
-  else dense_bwd_x<G::H1B, G::H2B>(img + G::W2, d2, d1, l31, hi);
-  apply_lrelu_grad<G::H1B>(d1, m1);
-  if constexpr (DW6) {
-    split_C<G::H1B>(d1, s1);
-    NF_PAIR_PUT(G::H1B, bufa, s1);
   } else {
+    if constexpr (PB6) dense_bwd_x_b6<G::H1B, G::H2B>(wt + B6TGeo<G>::T2, d2, d1, l31, hi);
+    else dense_bwd_x<G::H1B, G::H2B>(img + G::W2, d2, d1, l31, hi);
+    apply_lrelu_grad<G::H1B>(d1, m1);
     tile_to_scratch<G::H1B>(sp + L::D1, d1, l31, hi);
-  }
   }
   NF_TS_STAMP(5);
   __syncthreads();  // B3
@@ -2031,36 +1798,13 @@ __device__ __forceinline__ void pair_produce(const CouplingArgs &a, const float 
   NF_TS_STAMP(7);
 }
 
-// split_T of one operand with the 4 NB requests of the next operand spread between its 2 NA k-group splits (NF_PAIR_SPREAD)
-template <int NA, int NB>
-__device__ __forceinline__ void consumer_split_and_request(const StashIO &st, int base, int voff, const float (&at)[NA][16], SplitT<NA> &s,
-                                                           float (&bt)[NB][16]) {
-  constexpr int NS = 2 * NA, NL = 4 * NB;
-#pragma unroll
-  for (int i = 0; i < NS; ++i) {
-    const int ib = i >> 1, g = i & 1;
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = at[ib][8 * g + j];
-#pragma unroll
-    for (int l = i * NL / NS; l < (i + 1) * NL / NS; ++l) {  // this k-group's share of the requests, in front of its split
-      const int b = l >> 2, q = l & 3;
-      const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(st.rs, voff, (base + b * 1024) * 4 + q * 16, 0);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const unsigned bits = w[e];
-        bt[b][4 * q + e] = __builtin_bit_cast(float, bits);
-      }
-    }
-    nf_split8(v, s.h[ib][g], s.m[ib][g], s.l[ib][g]);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
 // (Round 6, measured and removed: the consumer held back by s_sleep behind each barrier -- 256 / 512 / 768 clocks in stage 1,
 // twice that in stage 2 -- so that its matrix instructions would run beside the producer's vector tail instead of beside its
 // GEMM: 323.2-325.2 against 325.5 us on one box, nothing.  The older wave already wins the arbitration.)
 // (Measured and removed: dW1 of a tile moved in front of the NEXT tile's first barrier, where the producer issues no
 // MFMAs -- 374-379 us against 366 in one process; and the producer's next-unit operands requested behind B3 -- 370.)
+// (Measured and removed: the NEXT tile's a2 requested behind B3 -- 32 more registers across the loop's back edge, which
+// hipcc spills to scratch right behind the loads: 428 us per launch against 345.)
 template <class G, bool SLIM, bool PB6 = false, bool DW6 = false>
 // (`sp` is NOT __restrict__: the DW6 triple buffers are rewritten by the producer between this wave's GEMMs, and through a
 // const restrict pointer hipcc reuses the registers of an earlier read of the same address across the barriers.)
@@ -2080,130 +1824,45 @@ __device__ __forceinline__ void pair_consume(const float *__restrict__ img, cons
   const StashIO st = make_stash_io(stash, tile * ncoup + k, SG::SIZE, true, l31, hi);
   const int vT = (l31 * 32 + hi * 16) * 4;
   if constexpr (DW6) {
-    const char *bufa = reinterpret_cast<const char *>(sp) + par * NF_PAIR_BUF, *bufb = reinterpret_cast<const char *>(sp) + (par ^ 1) * NF_PAIR_BUF;
-    float a1t[G::H1B][16];
-#if (NF_PAIR_ANTI & 2) && NF_PAIR_TR
+    const char *bufa = reinterpret_cast<const char *>(sp) + par * TR_BUF, *bufb = reinterpret_cast<const char *>(sp) + (par ^ 1) * TR_BUF;
     // ANTI-PHASE (round 6): two MIXED matrix + vector streams on one SIMD add up, a matrix burst and a vector burst overlap
     // (tools/probe/mfma_valu_overlap_probe.hip).  So every stage of this wave is [split the stage's own activation operand | dW GEMM],
     // the producer's [dX GEMM | slopes, split, hand-over stores]: while one wave is in its matrix burst the other is in its vector
-    // burst.  The operand of stage k + 1 is requested at the head of stage k; only one operand's triples are live at a time.
+    // burst.  The operand of stage k + 1 is requested at the head of stage k, in front of stage k's split; only one operand's
+    // triples are live at a time.
+    float a1t[G::H1B][16], x2t[G::MB][16];
     {
-#if NF_PAIR_MSPLIT & 2  // the consumer's splits with their subtractions on the matrix pipe (nf_split16_mfma): a third of the vector work
-      const SplitSel sel = nf_split_sel(l31, hi);
-#define NF_CONS_SPLIT(NB, at, xs)                                              \
-  _Pragma("unroll") for (int ib_ = 0; ib_ < NB; ++ib_) {                       \
-    f32x16 v_;                                                               \
-    _Pragma("unroll") for (int r_ = 0; r_ < 16; ++r_) v_[r_] = at[ib_][r_];    \
-    nf_split16_mfma(sel, v_, xs.h[ib_], xs.m[ib_], xs.l[ib_]);               \
-  }
-#else
-#define NF_CONS_SPLIT(NB, at, xs) split_T<NB>(at, xs)
-#endif
-      // the NEXT stage's operand is requested while this stage's is split.  NF_PAIR_SPREAD: its 16-byte requests go out one by one
-      // between the split's k-groups instead of in one batch behind the barrier -- there all eight waves of the CU issue theirs within
-      // the same few hundred clocks and a wave is held 590-780 clocks at ISSUE (64 bytes per clock and CU; tools/trace_bwd_pair.py)
-#if NF_PAIR_SPREAD
-#define NF_CONS_REQ_SPLIT(NA, at, xs, NBQ, baseq, bt) consumer_split_and_request<NA, NBQ>(st, baseq, vT, at, xs, bt)
-#else
-#define NF_CONS_REQ_SPLIT(NA, at, xs, NBQ, baseq, bt) \
-  do { stash_get_T<NBQ>(st, baseq, vT, bt); NF_CONS_SPLIT(NA, at, xs); } while (0)
-#endif
-      float x2t[G::MB][16];
-      {
-        float a2t[G::H2B][16];
-        stash_get_T<G::H2B>(st, nbase + SG::A2, vT, a2t);
-        NF_TS_STAMP(1);
-        __syncthreads();  // B1
-        NF_TS_STAMP(2);
-        SplitT<G::H2B> a2s;
-        NF_CONS_REQ_SPLIT(G::H2B, a2t, a2s, G::H1B, nbase + SG::A1, a1t);
-        __builtin_amdgcn_sched_barrier(0);
-        NF_PAIR_DW(G::H2B, G::CB, a2s, bufa, acc.w3, acc.b3);
-      }
-      NF_TS_STAMP(3);
-      __syncthreads();  // B2
-      NF_TS_STAMP(4);
-      {
-        SplitT<G::H1B> a1s;
-        NF_CONS_REQ_SPLIT(G::H1B, a1t, a1s, G::MB, SG::XT, x2t);
-        __builtin_amdgcn_sched_barrier(0);
-        NF_PAIR_DW(G::H1B, G::H2B, a1s, bufb, acc.w2, acc.b2);
-      }
-      NF_TS_STAMP(5);
-      __syncthreads();  // B3
-      NF_TS_STAMP(6);
-      {
-        SplitT<G::MB> x2s;
-        NF_CONS_SPLIT(G::MB, x2t, x2s);
-        __builtin_amdgcn_sched_barrier(0);
-        NF_PAIR_DW(G::MB, G::H1B, x2s, bufa, acc.w1, acc.b1);
-      }
-      NF_TS_STAMP(7);
-      return;
-    }
-#endif
-    {
-      // (Measured and removed: the NEXT tile's a2 requested behind B3 -- 32 more registers across the loop's back edge, which
-      // hipcc spills to scratch right behind the loads: 428 us per launch against 345.)
-      SplitT<G::H2B> a2s;
-      {
-        float a2t[G::H2B][16];
-        stash_get_T<G::H2B>(st, nbase + SG::A2, vT, a2t);
-        split_T<G::H2B>(a2t, a2s);
-      }
-      stash_get_T<G::H1B>(st, nbase + SG::A1, vT, a1t);  // in flight behind dW3
+      float a2t[G::H2B][16];
+      stash_get_T<G::H2B>(st, nbase + SG::A2, vT, a2t);
       NF_TS_STAMP(1);
       __syncthreads();  // B1
       NF_TS_STAMP(2);
-#if NF_PAIR_WEAVE && NF_PAIR_TR
-      // a1's split in the issue shadows of dW3's second half (24 matrix instructions, a1 arrives during the first)
-      SplitT<G::H1B> a1s;
-      {
-        constexpr int NH = 12 * G::H2B * G::CB, F1 = NH > 8 * G::H1B ? NH - 8 * G::H1B : 0;
-        const SplitTJob<G::H1B, F1, 1> job{a1t, a1s};
-        dw_accumulate_tr6<G::H2B, G::CB>(a2s, bufa, acc.w3, acc.b3, l31, hi, job);
-        job.template finish<NH>();
-      }
-      float x2t[G::MB][16];
-      stash_get_T<G::MB>(st, SG::XT, vT, x2t);
-      NF_TS_STAMP(3);
-      __syncthreads();  // B2
-      NF_TS_STAMP(4);
-      SplitT<G::MB> x2s;
-      {
-        constexpr int NH = 12 * G::H1B * G::H2B, F2 = NH > 16 * G::MB ? NH - 16 * G::MB : 0;
-        const SplitTJob<G::MB, F2, 2> job{x2t, x2s};
-        dw_accumulate_tr6<G::H1B, G::H2B>(a1s, bufb, acc.w2, acc.b2, l31, hi, job);
-        job.template finish<NH>();
-      }
-      NF_TS_STAMP(5);
-      __syncthreads();  // B3
-      NF_TS_STAMP(6);
-      NF_PAIR_DW(G::MB, G::H1B, x2s, bufa, acc.w1, acc.b1);
-      NF_TS_STAMP(7);
-      return;
-#endif
-      NF_PAIR_DW(G::H2B, G::CB, a2s, bufa, acc.w3, acc.b3);
+      SplitT<G::H2B> a2s;
+      stash_get_T<G::H1B>(st, nbase + SG::A1, vT, a1t);
+      split_T<G::H2B>(a2t, a2s);
+      __builtin_amdgcn_sched_barrier(0);
+      dw_accumulate_tr6<G::H2B, G::CB>(a2s, bufa, acc.w3, acc.b3, l31, hi);
     }
-    float x2t[G::MB][16];
+    NF_TS_STAMP(3);
+    __syncthreads();  // B2
+    NF_TS_STAMP(4);
     {
       SplitT<G::H1B> a1s;
-      split_T<G::H1B>(a1t, a1s);
       stash_get_T<G::MB>(st, SG::XT, vT, x2t);
-      NF_TS_STAMP(3);
-      __syncthreads();  // B2
-      NF_TS_STAMP(4);
-      NF_PAIR_DW(G::H1B, G::H2B, a1s, bufb, acc.w2, acc.b2);
+      split_T<G::H1B>(a1t, a1s);
+      __builtin_amdgcn_sched_barrier(0);
+      dw_accumulate_tr6<G::H1B, G::H2B>(a1s, bufb, acc.w2, acc.b2, l31, hi);
     }
+    NF_TS_STAMP(5);
+    __syncthreads();  // B3
+    NF_TS_STAMP(6);
     {
       SplitT<G::MB> x2s;
       split_T<G::MB>(x2t, x2s);
-      NF_TS_STAMP(5);
-      __syncthreads();  // B3
-      NF_TS_STAMP(6);
-      NF_PAIR_DW(G::MB, G::H1B, x2s, bufa, acc.w1, acc.b1);
-      NF_TS_STAMP(7);
+      __builtin_amdgcn_sched_barrier(0);
+      dw_accumulate_tr6<G::MB, G::H1B>(x2s, bufa, acc.w1, acc.b1, l31, hi);
     }
+    NF_TS_STAMP(7);
     return;  // (the dW1 block below belongs to the two fp32-tile forms)
   } else if constexpr (SLIM) {
     // a1 is not in the stash: rebuilt here, in this wave's MFMA-free prologue (the producer is in its own: operand loads,
@@ -2225,59 +1884,30 @@ __device__ __forceinline__ void pair_consume(const float *__restrict__ img, cons
     NF_TS_STAMP(4);
     dw_accumulate_reg<G::H1B, G::H2B, NoSideJob, true>(a1t, sp + L::D2, acc.w2, acc.b2, l31, hi);
   } else {
-  {
-    float a2t[G::H2B][16];
-    stash_get_T<G::H2B>(st, nbase + SG::A2, vT, a2t);
-    if constexpr (PB6 && (NF_PAIR_DW_B6 & 1)) {
-      SplitT<G::H2B> a2s;
-      split_T<G::H2B>(a2t, a2s);
+    {
+      float a2t[G::H2B][16];
+      stash_get_T<G::H2B>(st, nbase + SG::A2, vT, a2t);
       NF_TS_STAMP(1);
       __syncthreads();  // B1
       NF_TS_STAMP(2);
-      dw_accumulate_reg_b6<G::H2B, G::CB>(a2s, sp + L::D3, acc.w3, acc.b3, l31, hi);
-    } else {
-    NF_TS_STAMP(1);
-    __syncthreads();  // B1
-    NF_TS_STAMP(2);
-    dw_accumulate_reg<G::H2B, G::CB>(a2t, sp + L::D3, acc.w3, acc.b3, l31, hi);
+      dw_accumulate_reg<G::H2B, G::CB>(a2t, sp + L::D3, acc.w3, acc.b3, l31, hi);
     }
-  }
-  if constexpr (PB6 && NF_PAIR_DW_B6 != 0) __builtin_amdgcn_sched_barrier(0);  // the next operand block is requested AFTER this GEMM: registers
-  {
-    float a1t[G::H1B][16];
-    stash_get_T<G::H1B>(st, nbase + SG::A1, vT, a1t);
-    if constexpr (PB6 && (NF_PAIR_DW_B6 & 2)) {
-      SplitT<G::H1B> a1s;
-      split_T<G::H1B>(a1t, a1s);
+    {
+      float a1t[G::H1B][16];
+      stash_get_T<G::H1B>(st, nbase + SG::A1, vT, a1t);
       NF_TS_STAMP(3);
       __syncthreads();  // B2
       NF_TS_STAMP(4);
-      dw_accumulate_reg_b6<G::H1B, G::H2B>(a1s, sp + L::D2, acc.w2, acc.b2, l31, hi);
-    } else {
-    NF_TS_STAMP(3);
-    __syncthreads();  // B2
-    NF_TS_STAMP(4);
-    dw_accumulate_reg<G::H1B, G::H2B>(a1t, sp + L::D2, acc.w2, acc.b2, l31, hi);
+      dw_accumulate_reg<G::H1B, G::H2B>(a1t, sp + L::D2, acc.w2, acc.b2, l31, hi);
     }
   }
-  }
-  if constexpr (PB6 && NF_PAIR_DW_B6 != 0) __builtin_amdgcn_sched_barrier(0);
   {
     float x2t[G::MB][16];
     stash_get_T<G::MB>(st, SG::XT, vT, x2t);
-    if constexpr (PB6 && (NF_PAIR_DW_B6 & 4)) {
-      SplitT<G::MB> x2s;
-      split_T<G::MB>(x2t, x2s);
-      NF_TS_STAMP(5);
-      __syncthreads();  // B3
-      NF_TS_STAMP(6);
-      dw_accumulate_reg_b6<G::MB, G::H1B>(x2s, sp + L::D1, acc.w1, acc.b1, l31, hi);
-    } else {
     NF_TS_STAMP(5);
     __syncthreads();  // B3
     NF_TS_STAMP(6);
     dw_accumulate_reg<G::MB, G::H1B>(x2t, sp + L::D1, acc.w1, acc.b1, l31, hi);
-    }
     NF_TS_STAMP(7);
   }
 }
@@ -2333,9 +1963,9 @@ __global__ __launch_bounds__(512) void k_affine_bwd_pair(BwdAllArgs aa, float *s
     StashFirst<G> f;
     if (INVD && tile0 < ntiles) stash_issue_first<G, SLIM>(f, stash, aa.ncoup - 1, aa.ncoup, tile0, l31, hi);  // S runs first
     PairPark<G> pk;  // g1 / g2: written in the coupling's first phase, read in its second; g1[0] / cy: carried to the next coupling
-    if constexpr (!INVD && pair_carry<FULL>() > 0) {  // the first coupling's g1 of the carried tiles (coupling 0 transforms the even half)
+    if constexpr (!INVD && FULL) {  // the first coupling's g1 of the carried tiles (coupling 0 transforms the even half)
 #pragma unroll
-      for (int s = 0; s < pair_carry<FULL>(); ++s) {
+      for (int s = 0; s < 2; ++s) {
         const long tile = tile0 + s * tstride;
         if (tile < ntiles) {
           const TileIO gio = make_tile_io(ybar, tile, aa.d, l31, hi);
@@ -2414,9 +2044,6 @@ __global__ __launch_bounds__(512) void k_affine_bwd_pair(BwdAllArgs aa, float *s
       }
     }
   } else {
-#if NF_PAIR_CONS_PRIO
-    __builtin_amdgcn_s_setprio(NF_PAIR_CONS_PRIO);
-#endif
 #pragma unroll 1
     for (int step = 0; step < aa.ncoup; ++step) {
       const int k = INVD ? aa.ncoup - 1 - step : step;
@@ -2731,19 +2358,6 @@ static int launch_chain(nf_ctx *ctx, const nf_flow_desc *desc, bool inverse, flo
   // two double-buffered (s,t) image pairs (B6: three single images) + target parameters and per-wave sums of the fused variant
   const size_t lds = (B6 ? (size_t)3 * B6Geo<G>::BYTES : 4 * (size_t)G::SIZE * sizeof(float)) + (2 * 64 * G::CB + 2) * sizeof(float) +
                      12 * sizeof(double);
-  // (round 6, measured: NOT the default) the six-term chains WITHOUT a stash (nf_flow_fwd / nf_flow_inv, nf_loglikelihood: BASELINE cfg 5)
-  // with THREE wavefronts per SIMD -- twelve tiles per workgroup, NF_CHAIN_NW=12 at build time: the kernel is a serial chain per wave
-  // (GEMM -> split -> GEMM ...) at 53 % of the matrix pipe with two.  At hidden 64 the instantiation needs 212 registers; held to the 168
-  // of three waves it spills 180 bytes and cfg 5 runs 1.893 against 1.624 ms; with the plain GEMM form (PIPE = false: 68 bytes) 1.747
-  // against 1.675 (profiles/r6r_chain_nw.txt).  Hidden 32 fits (156).
-#ifndef NF_CHAIN_NW
-#define NF_CHAIN_NW 8
-#endif
-#ifndef NF_CHAIN_DUAL
-#define NF_CHAIN_DUAL 0  // 1: the plain six-term chains on k_affine_chain_dual (one wave per SIMD, two tiles per wave) -- measured slower:
-// cfg 5 1.72 against 1.63 ms (profiles/r6u_chain_dual.txt): with one wave per SIMD nothing covers the layer boundaries
-#endif
-  constexpr int NWP = B6 ? NF_CHAIN_NW : 8;  // waves per workgroup of the plain chains below
   // k_affine_chain_tgt (the fused forward for the Banana / Funnel / WarpedGauss / Cross targets): eight waves per workgroup
   // where the instantiation fits 256 registers without scratch, four (one per SIMD, 512 registers) where it does not -- the
   // six-term forms at hidden 64 without a stash (44 bytes at eight) and with the slim stash (12 bytes); by
@@ -2760,14 +2374,6 @@ static int launch_chain(nf_ctx *ctx, const nf_flow_desc *desc, bool inverse, flo
     NF_HIP(hipFuncSetAttribute((const void *)k_affine_chain<G, true, false, true, SLIM, B6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     NF_HIP(hipFuncSetAttribute((const void *)k_affine_chain_tgt<G, true, SLIM, B6, NWT_S>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     NF_HIP(hipFuncSetAttribute((const void *)k_affine_chain_tgt<G, false, false, B6, NWT_P>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (B6 && NF_CHAIN_DUAL) {
-      NF_HIP(hipFuncSetAttribute((const void *)k_affine_chain_dual<G, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      NF_HIP(hipFuncSetAttribute((const void *)k_affine_chain_dual<G, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    }
-    if (NWP != 8) {
-      NF_HIP(hipFuncSetAttribute((const void *)k_affine_chain<G, false, false, false, false, B6, NWP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      NF_HIP(hipFuncSetAttribute((const void *)k_affine_chain<G, true, false, false, false, B6, NWP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    }
     return NF_OK;
   }));
   if (B6) NF_TRY(b6_refresh<G>(ctx, desc));
@@ -2795,23 +2401,17 @@ static int launch_chain(nf_ctx *ctx, const nf_flow_desc *desc, bool inverse, flo
   else if (inverse && stash_plain) {  // forward-KL training: the inverse chain leaves the stash of ITS reverse pass
     none.stash = stash_plain;
     hipLaunchKernelGGL((k_affine_chain<G, true, false, true, SLIM, B6>), dim3((unsigned)grid), dim3(512), lds, ctx->stream, a, xt, ladj, none);
-  } else if (inverse && B6 && NF_CHAIN_DUAL) {
-    hipLaunchKernelGGL((k_affine_chain_dual<G, true>), dim3((unsigned)grid), dim3(256), lds, ctx->stream, a, xt, ladj);
-  } else if (!inverse && !stash_plain && B6 && NF_CHAIN_DUAL) {
-    hipLaunchKernelGGL((k_affine_chain_dual<G, false>), dim3((unsigned)grid), dim3(256), lds, ctx->stream, a, xt, ladj);
   } else if (inverse) {
-    const long g12 = (((N + NF_TILE - 1) / NF_TILE + NWP - 1) / NWP);
-    const long gridp = g12 < 1 ? 1 : g12 < ctx->num_cu ? g12 : ctx->num_cu;
-    hipLaunchKernelGGL((k_affine_chain<G, true, false, false, false, B6, NWP>), dim3((unsigned)gridp), dim3(64 * NWP), lds, ctx->stream, a, xt, ladj, none);
-  }
-  else if (stash_plain) {  // caller-supplied draws: the plain forward chain, leaving the stash behind
+    const long g8 = ((N + NF_TILE - 1) / NF_TILE + 7) / 8;
+    const long gridp = g8 < 1 ? 1 : g8 < ctx->num_cu ? g8 : ctx->num_cu;
+    hipLaunchKernelGGL((k_affine_chain<G, true, false, false, false, B6>), dim3((unsigned)gridp), dim3(512), lds, ctx->stream, a, xt, ladj, none);
+  } else if (stash_plain) {  // caller-supplied draws: the plain forward chain, leaving the stash behind
     none.stash = stash_plain;
     hipLaunchKernelGGL((k_affine_chain<G, false, false, true, SLIM, B6>), dim3((unsigned)grid), dim3(512), lds, ctx->stream, a, xt, ladj, none);
-  }
-  else {
-    const long g12 = (((N + NF_TILE - 1) / NF_TILE + NWP - 1) / NWP);
-    const long gridp = g12 < 1 ? 1 : g12 < ctx->num_cu ? g12 : ctx->num_cu;
-    hipLaunchKernelGGL((k_affine_chain<G, false, false, false, false, B6, NWP>), dim3((unsigned)gridp), dim3(64 * NWP), lds, ctx->stream, a, xt, ladj, none);
+  } else {
+    const long g8 = ((N + NF_TILE - 1) / NF_TILE + 7) / 8;
+    const long gridp = g8 < 1 ? 1 : g8 < ctx->num_cu ? g8 : ctx->num_cu;
+    hipLaunchKernelGGL((k_affine_chain<G, false, false, false, false, B6>), dim3((unsigned)gridp), dim3(512), lds, ctx->stream, a, xt, ladj, none);
   }
   return (int)hipGetLastError();
 }

@@ -32,9 +32,6 @@ __device__ __forceinline__ int nf_row(int r, int hi) { return (r & 3) + 8 * (r >
 // hipcc: IEEE mode makes it quiet a possible signalling NaN first (`v_max_f32 z, z, z`), 128 of them per coupling in the
 // cfg-2 forward; the instruction itself is what is wanted.
 __device__ __forceinline__ float nf_vmax(float a, float b) {
-#ifdef NF_LRELU_FMAX  // A/B switch: the compiler's own three-instruction form
-  return fmaxf(a, b);
-#endif
   float r;
   asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
   return r;
@@ -78,14 +75,6 @@ __device__ __forceinline__ float nf_fdiv(float x, float y) { return x * __builti
 // that bias was the larger part of cfg 4's ladj error (mean -0.21 of the tolerance for fp32 MFMAs against +0.002 for
 // numpy's float32; tools/parity_ab.py).
 __device__ __forceinline__ float nf_tanh(float x) {
-#ifdef NF_TANH_ACCURATE
-  return tanhf(x);
-#endif
-#ifdef NF_TANH_EXP2  // the rounds-1-4 form (A/B)
-  const float xe = fminf(fmaxf(x, -10.f), 10.f);
-  const float e2 = __expf(2.f * xe);
-  return nf_fdiv(e2 - 1.f, e2 + 1.f);
-#endif
   const float xc = __builtin_amdgcn_fmed3f(x, -8.124f, 8.124f);  // beyond x^2 = 66 the reference returns sign(x); the rational is 1 - 2e-7 there
   const float z = xc * xc;
   const float n = fmaf(fmaf(fmaf(fmaf(1.587199e-8f, z, 2.2332108e-5f), z, 0.0035974074f), z, 0.1346604f), z, 1.f);
@@ -108,12 +97,8 @@ __device__ __forceinline__ unsigned nf_sign_mask16(const f32x16 &v) {
 // bit patterns with it (v_bfi_b32): two instructions, no VCC round trip (the select form costs v_and + v_cmp + s_nop +
 // v_cndmask per element)
 __device__ __forceinline__ float nf_mask_slope(unsigned mask, int r) {
-#ifdef NF_SLOPE_SELECT  // the round-1 form, kept for A/B measurements
-  return ((mask >> (15 - r)) & 1u) ? 0.01f : 1.f;
-#else
   const unsigned t = (unsigned)__builtin_amdgcn_sbfe((int)mask, 15 - r, 1);
   return __builtin_bit_cast(float, (t & 0x3C23D70Au) | (~t & 0x3F800000u));
-#endif
 }
 __device__ __forceinline__ float nf_exp(float x) { return __expf(x); }
 // a whole cotangent block times its slopes, 2.5 instructions per element and no more: v_bfe_i32 (0 / -1 from the element's mask
@@ -133,12 +118,7 @@ __device__ __forceinline__ void nf_lrelu_grad16(f32x16 &d, unsigned mask) {
     asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x6c" : "=v"(s1) : "v"(t1), "v"(one), "v"(flip));
     f32x2_t v = {d[2 * p], d[2 * p + 1]};
     const f32x2_t sl = {__builtin_bit_cast(float, s0), __builtin_bit_cast(float, s1)};
-#ifdef NF_SLOPE_SCALAR  // two v_mul_f32: a packed f32 instruction does not overlap a matrix instruction in flight (tools/probe/mfma_valu_overlap_probe.hip)
-    asm("v_mul_f32 %0, %1, %2" : "=v"(v.x) : "v"(v.x), "v"(sl.x));
-    asm("v_mul_f32 %0, %1, %2" : "=v"(v.y) : "v"(v.y), "v"(sl.y));
-#else
     asm("v_pk_mul_f32 %0, %1, %2" : "=v"(v) : "v"(v), "v"(sl));
-#endif
     d[2 * p] = v.x;
     d[2 * p + 1] = v.y;
   }
@@ -167,17 +147,10 @@ struct DenseLds {
 // Row padding of every LDS weight image, in floats.  4 keeps rows 16-byte aligned, so the transposed (dX) operand fetch
 // is ONE ds_read_b128 per four k-steps (lane <-> row: 8 consecutive rows cover the 32 banks), while the forward fetch
 // (lanes along a row, rows 4 apart for the two half-waves: 4 * S = 16 banks apart) stays conflict-free with ds_read_b32.
-// 1 is the rounds-1/2 odd stride (four ds_read_b32 per four k-steps in the dX GEMMs), kept for A/B measurements.
-#ifndef NF_IMG_PAD
 #define NF_IMG_PAD 4
-#endif
 template <int S>
 __device__ __forceinline__ void nf_ld4(const float *__restrict__ p, float &a, float &b, float &c, float &d) {
-#ifdef NF_LD4_SCALAR
-  if constexpr (false) {
-#else
   if constexpr (S % 4 == 0) {
-#endif
     const float4 v = *reinterpret_cast<const float4 *>(p);
     a = v.x; b = v.y; c = v.z; d = v.w;
   } else {
@@ -665,14 +638,7 @@ __device__ __forceinline__ void nf_split2(float x0, float x1, unsigned &h, unsig
 // round-trip error of the 1 M-sample inverse / forward pair of cfg 5.
 #pragma clang fp contract(off)
   const nf_f32x2 x = {x0, x1};
-#ifdef NF_SPLIT_TRUNC  // the round-4 split (A/B of the arithmetic; tools/split_ab.sh)
-  const nf_u32x2 xb = __builtin_bit_cast(nf_u32x2, x);
-  const nf_f32x2 r = x - __builtin_bit_cast(nf_f32x2, xb & 0xFFFF0000u);
-  const nf_u32x2 rb = __builtin_bit_cast(nf_u32x2, r);
-  const nf_f32x2 lo = r - __builtin_bit_cast(nf_f32x2, rb & 0xFFFF0000u);
-  h = __builtin_amdgcn_perm(xb.y, xb.x, 0x07060302u);
-  m = __builtin_amdgcn_perm(rb.y, rb.x, 0x07060302u);
-#elif defined(NF_SPLIT_SCALAR)  // A/B: the two subtractions as scalar v_sub_f32 pairs instead of v_pk_add_f32
+#ifdef NF_SPLIT_SCALAR  // a per-file choice (nf_wide.hip): the two subtractions as scalar v_sub_f32 pairs instead of v_pk_add_f32
   h = nf_cvt_pk_bf16(x);
   const nf_f32x2 hw = nf_widen_pk_bf16(h);
   float r0 = x0 - hw.x, r1 = x1 - hw.y;
@@ -706,71 +672,10 @@ __device__ __forceinline__ void nf_split8(const float (&v)[8], nf_u32x4 &h, nf_u
     unsigned ph, pm, pl;
     nf_split2(v[2 * p], v[2 * p + 1], ph, pm, pl);
     h[p] = ph; m[p] = pm; l[p] = pl;
-#ifdef NF_SPLIT_PINNED
-    __builtin_amdgcn_sched_barrier(0);  // (a pair at a time: 6 temporaries instead of 24)
-#endif
   }
 }
 __device__ __forceinline__ f32x16 nf_mfma_bf16(nf_u32x4 a, nf_u32x4 b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(nf_bf16x8, a), __builtin_bit_cast(nf_bf16x8, b), c, 0, 0, 0);
-}
-
-// ---- the split with its two exact subtractions ON THE MATRIX PIPE (round 6) -----------------------------------------------
-// nf_split2 spends 4.5 vector instructions per value, two thirds of them on r = x - h and l = r - m (widen h: shl + and per
-// pair, then v_pk_add_f32; the same for m).  Both differences are exact, and an MFMA computes exact differences for free:
-//     D = C + A B   with C = the fp32 block x (16 registers per lane, C layout), B = its packed bf16 part h (the very
-//                   registers the split produces), A = MINUS the selection matrix that maps B's k-order onto C's rows
-// gives D = x - h for the whole 32 x 32 block: every output is ONE product (-1 x h, exact) plus C, and x - h is a multiple
-// of ulp(x) below 2^-8 |x|, so the instruction's adder has nothing to drop (tools/probe/split_mfma_probe.hip compares all
-// three parts bit for bit with nf_split2 on random, tie, subnormal-adjacent and huge inputs).  A block of 16 values then
-// costs 8 + 8 + 8 conversions (1.5 instructions per value) and four v_mfma_f32_32x32x16_bf16 (two k-groups x two levels).
-// MEASURED (round 6): bit-identical, halves the vector instructions of the cfg-2 reverse kernel -- and buys
-// nothing there, in the cfg-5 chain or in k_rqs_bwd_coop6 (the split's MFMAs join the dependent chain of the wave that was
-// already the slower of its SIMD's two; these kernels are not bound by vector issue).  The primitive and its probe stay for
-// the next kernel that IS; the call sites that were tried are tools/experiments/pair_chain_split_on_matrix_pipe.patch.
-// The selection operand: hardware k = 8 hi + j of k-group g is C row 16 g + (j & 3) + 8 (j >> 2) + 4 hi (nf_row(8 g + j, hi)),
-// so lane (row i = l31, half hi) holds -1 at element j iff i - 16 g - 4 hi = (j & 3) + 8 (j >> 2), zeros elsewhere.
-struct SplitSel {
-  nf_u32x4 a[2];  // A operands of the two k-groups
-};
-__device__ __forceinline__ SplitSel nf_split_sel(int l31, int hi) {
-  SplitSel s;
-#pragma unroll
-  for (int g = 0; g < 2; ++g) {
-    const int q = l31 - 16 * g - 4 * hi;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const int j0 = 2 * p, j1 = 2 * p + 1;
-      const unsigned lo = q == (j0 & 3) + 8 * (j0 >> 2) ? 0xBF80u : 0u, hv = q == (j1 & 3) + 8 * (j1 >> 2) ? 0xBF800000u : 0u;
-      s.a[g][p] = lo | hv;
-    }
-  }
-  // pinned: hipcc otherwise rematerialises the eight compares + selects in front of every use
-  asm volatile("" : "+v"(s.a[0]), "+v"(s.a[1]));
-  return s;
-}
-// one C-layout block (16 values per lane) -> its triples per k-group g = register >> 3: h[g], m[g], l[g]
-__device__ __forceinline__ void nf_split16_mfma(const SplitSel &sel, const f32x16 &x, nf_u32x4 (&h)[2], nf_u32x4 (&m)[2],
-                                                nf_u32x4 (&l)[2]) {
-#pragma unroll
-  for (int g = 0; g < 2; ++g)
-#pragma unroll
-    for (int p = 0; p < 4; ++p) h[g][p] = nf_cvt_pk_bf16(nf_f32x2{x[8 * g + 2 * p], x[8 * g + 2 * p + 1]});
-  f32x16 r = nf_mfma_bf16(sel.a[0], h[0], x);
-  r = nf_mfma_bf16(sel.a[1], h[1], r);  // r = x - h
-#pragma unroll
-  for (int g = 0; g < 2; ++g)
-#pragma unroll
-    for (int p = 0; p < 4; ++p) m[g][p] = nf_cvt_pk_bf16(nf_f32x2{r[8 * g + 2 * p], r[8 * g + 2 * p + 1]});
-  f32x16 lo = nf_mfma_bf16(sel.a[0], m[0], r);
-  lo = nf_mfma_bf16(sel.a[1], m[1], lo);  // lo = r - m: at most 8 significant bits, its upper half IS the value
-#pragma unroll
-  for (int g = 0; g < 2; ++g)
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const float e0 = lo[8 * g + 2 * p], e1 = lo[8 * g + 2 * p + 1];  // (scalars first: bit_cast of a vector element, see nf_coupling.hip)
-      l[g][p] = __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, e1), __builtin_bit_cast(unsigned, e0), 0x07060302u);
-    }
 }
 
 // B6 image of one net (geometry G = NetGeo<..>), in 16-byte units: per layer [k-group][component h|m|l][half][row][8 bf16],
@@ -914,78 +819,6 @@ __device__ __forceinline__ void dense_fwd_b6p(const nf_u32x4 *__restrict__ w, co
   }
 }
 
-// dense_fwd_b6p for TWO tiles at once (round 6; k_affine_chain_dual): the unit's weight operands are read from LDS once and serve both
-// tiles, 2 OB accumulators alternate term by term, and the two next-k-group splits (72 vector instructions) ride behind 12 OB matrix
-// instructions instead of 6 OB.  Per accumulator the order of the terms is dense_fwd_b6's: bit-identical results.
-template <int IB, int OB>
-__device__ __forceinline__ void dense_fwd_b6p2(const nf_u32x4 *__restrict__ w, const float *__restrict__ b, const f32x16 (&in0)[IB],
-                                               const f32x16 (&in1)[IB], f32x16 (&out0)[OB], f32x16 (&out1)[OB], int l31, int hi) {
-  constexpr int ROWS = 32 * OB, NKG = 2 * IB;
-#pragma unroll
-  for (int ob = 0; ob < OB; ++ob)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) out0[ob][r] = out1[ob][r] = b[ob * 32 + nf_row(r, hi)];
-  const nf_u32x4 *wl = w + hi * ROWS + l31;
-  nf_u32x4 an[OB][3], xn0[3], xn1[3];
-  {
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = in0[0][j];
-    nf_split8(v, xn0[0], xn0[1], xn0[2]);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = in1[0][j];
-    nf_split8(v, xn1[0], xn1[1], xn1[2]);
-#pragma unroll
-    for (int ob = 0; ob < OB; ++ob)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) an[ob][c] = wl[c * 2 * ROWS + ob * 32];
-  }
-#pragma unroll
-  for (int kg = 0; kg < NKG; ++kg) {
-    nf_u32x4 ac[OB][3], xc0[3], xc1[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      xc0[c] = xn0[c];
-      xc1[c] = xn1[c];
-#pragma unroll
-      for (int ob = 0; ob < OB; ++ob) ac[ob][c] = an[ob][c];
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    if (kg + 1 < NKG) {
-#pragma unroll
-      for (int ob = 0; ob < OB; ++ob)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) an[ob][c] = wl[((kg + 1) * 3 + c) * 2 * ROWS + ob * 32];
-      float v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = in0[(kg + 1) >> 1][8 * ((kg + 1) & 1) + j];
-      nf_split8(v, xn0[0], xn0[1], xn0[2]);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = in1[(kg + 1) >> 1][8 * ((kg + 1) & 1) + j];
-      nf_split8(v, xn1[0], xn1[1], xn1[2]);
-    }
-    // smallest terms first: wl xh, wh xl, wm xm, wm xh, wh xm, wh xh (components: 0 = h, 1 = m, 2 = l)
-#pragma unroll
-    for (int term = 0; term < 6; ++term)
-#pragma unroll
-      for (int ob = 0; ob < OB; ++ob) {
-        const nf_u32x4 &av = term == 0 ? ac[ob][2] : (term == 2 || term == 3) ? ac[ob][1] : ac[ob][0];
-        const int xi = term == 1 ? 2 : (term == 2 || term == 4) ? 1 : 0;
-        out0[ob] = nf_mfma_bf16(av, xc0[xi], out0[ob]);
-        out1[ob] = nf_mfma_bf16(av, xc1[xi], out1[ob]);
-      }
-    if (kg + 1 < NKG) {
-      __builtin_amdgcn_sched_group_barrier(0x100, 3 * OB, 0);  // the next k-group's weights: requested first
-#pragma unroll
-      for (int i = 0; i < 12 * OB; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);               // one MFMA
-        __builtin_amdgcn_sched_group_barrier(0x002, OB == 1 ? 8 : 4, 0);  // its shadow: a slice of the two next splits
-      }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
 // The transposed counterpart for the dX GEMMs of the reverse pass (din = W^T delta): rows = the layer's INPUT features, the
 // k-groups run over its OUTPUT features, in the order the cotangent's C-layout registers hold them (same mapping as above).
 // Per layer [k-group][component][half][row][8 bf16]; no biases.  T3 serves dX3 (rows: a2 features), T2 dX2, T1 dX1.
@@ -1090,68 +923,14 @@ __device__ __forceinline__ void dense_bwd_x_b6s(const nf_u32x4 *__restrict__ w, 
   }
 }
 
-// dense_bwd_x_b6s with the OUTPUT BLOCKS one after the other (round 6): block ib's matrix instructions carry a side job --
-// sj(ib, i), i = 0 .. 12 NKG - 1, two calls behind every MFMA -- so that what follows a finished block (leaky-ReLU slopes,
-// split, hand-over stores: PairPost below) runs in the issue shadows of the NEXT block's instructions instead of behind the
-// whole GEMM.  The same terms in the same order per accumulator as dense_bwd_x_b6s: identical bits.
-template <int IB, int OB, class SJ>
-__device__ __forceinline__ void dense_bwd_x_b6s_blocks(const nf_u32x4 *__restrict__ w, const SplitC<OB> &ds, f32x16 (&din)[IB], int l31,
-                                                       int hi, SJ sj) {
-  constexpr int ROWS = 32 * IB, NKG = 2 * OB, NU = NKG * IB;
-#pragma unroll
-  for (int ib = 0; ib < IB; ++ib)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) din[ib][r] = 0.f;
-  const nf_u32x4 *wl = w + hi * ROWS + l31;
-  nf_u32x4 an[3], ac[3];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) an[c] = wl[c * 2 * ROWS];
-#pragma unroll
-  for (int u = 0; u < NU; ++u) {
-    const int ib = u / NKG, kg = u % NKG;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) ac[c] = an[c];
-    if (u + 1 < NU) {
-      const int ib1 = (u + 1) / NKG, kg1 = (u + 1) % NKG;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) an[c] = wl[(kg1 * 3 + c) * 2 * ROWS + ib1 * 32];
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    din[ib] = nf_mfma_bf16(ac[2], ds.h[kg], din[ib]); sj(ib, 12 * kg + 0); sj(ib, 12 * kg + 1);
-    din[ib] = nf_mfma_bf16(ac[0], ds.l[kg], din[ib]); sj(ib, 12 * kg + 2); sj(ib, 12 * kg + 3);
-    din[ib] = nf_mfma_bf16(ac[1], ds.m[kg], din[ib]); sj(ib, 12 * kg + 4); sj(ib, 12 * kg + 5);
-    din[ib] = nf_mfma_bf16(ac[1], ds.h[kg], din[ib]); sj(ib, 12 * kg + 6); sj(ib, 12 * kg + 7);
-    din[ib] = nf_mfma_bf16(ac[0], ds.m[kg], din[ib]); sj(ib, 12 * kg + 8); sj(ib, 12 * kg + 9);
-    din[ib] = nf_mfma_bf16(ac[0], ds.h[kg], din[ib]); sj(ib, 12 * kg + 10); sj(ib, 12 * kg + 11);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
-// The transposed hand-over of such triples: the dW GEMM contracts over SAMPLES, so its delta operand wants lane <-> feature
+// The transposed layout of such triples (k_wide_dw_b6, nf_wide.hip; the pair kernel's round-4 hand-over, whose writer and reader
+// live on in tools/probe/d6_probe.hip): the dW GEMM contracts over SAMPLES, so its delta operand wants lane <-> feature
 // and a lane's eight k-values = eight samples.  LDS tile of one cotangent tensor: row = feature (D6_ROW bytes: three
 // components x 64 bytes + 16 of padding -- 52 dwords, so eight consecutive rows' 16-byte reads cover the 32 banks once),
 // inside a component [sample group g][sample parity][j] x 2 bytes with sample = 2 (8 g + j) + parity: the order the T layout
 // of the stash gives the activation operand (dw_accumulate_reg_b6).  The writer holds a sample per lane and two features
 // per packed register: one ds_write_b16 for the low half, one ds_write_b16_d16_hi for the high half, no unpacking.
-constexpr int D6_ROW = 208, D6_BUF = 64 * D6_ROW;
-template <int NB>
-__device__ __forceinline__ void split_to_lds(char *__restrict__ buf, const SplitC<NB> &s, int l31, int hi) {
-  const int t = l31 >> 1;
-  char *p = buf + (4 * hi) * D6_ROW + (t >> 3) * 32 + (l31 & 1) * 16 + (t & 7) * 2;
-#pragma unroll
-  for (int kg = 0; kg < 2 * NB; ++kg)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const nf_u32x4 &v = c == 0 ? s.h[kg] : c == 1 ? s.m[kg] : s.l[kg];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int j0 = 2 * q, j1 = 2 * q + 1;
-        const int f0 = 16 * kg + (j0 & 3) + 8 * (j0 >> 2), f1 = 16 * kg + (j1 & 3) + 8 * (j1 >> 2);
-        *reinterpret_cast<unsigned short *>(p + f0 * D6_ROW + c * 64) = (unsigned short)v[q];
-        *reinterpret_cast<unsigned short *>(p + f1 * D6_ROW + c * 64) = (unsigned short)(v[q] >> 16);
-      }
-    }
-}
+constexpr int D6_ROW = 208;
 
 // The activation operand of a dW GEMM (T layout of the stash: at[ib][t] = a[feature ib * 32 + l31][sample 2 t + hi]) as triples
 template <int IB>
@@ -1172,62 +951,17 @@ __device__ __forceinline__ void split_T(const float (&at)[IB][16], SplitT<IB> &s
     }
 }
 
-// Both operands arrive split: the activation from split_T, the cotangent as the bf16 triples the PRODUCER wave made for its own
-// dX GEMM and left in LDS transposed (split_to_lds, nf_mfma.h): three ds_read_b128 per (sample group, delta block) and no
-// VALU work on the cotangent at all.  The bias gradient is the sum of the triples' components: v_dot2c_f32_bf16 against
-// (1, 1) adds two bf16 values into an fp32 register per instruction.  Inline asm: with the literal as an operand hipcc 7.0's
+// The bias gradient of a dW GEMM whose cotangent arrives as triples is the sum of the triples' components: v_dot2c_f32_bf16
+// against (1, 1) adds two bf16 values into an fp32 register per instruction.  Inline asm: with the literal as an operand hipcc 7.0's
 // __builtin_amdgcn_fdot2_f32_bf16 emits the FIRST register of a vector for all four of its elements (seen in the ISA, and as
 // NaN gradients on the device).
 __device__ __forceinline__ float nf_dot2_bf16(unsigned x, unsigned y, float acc) {
   asm("v_dot2c_f32_bf16 %0, %1, %2" : "+v"(acc) : "v"(x), "v"(y));
   return acc;
 }
-template <int IB, int OB, bool LEAN = false>
-__device__ __forceinline__ void dw_accumulate_t6(const SplitT<IB> &as, const char *buf, f32x16 (&acc)[IB][OB],
-                                                 float (&bsum)[OB], int l31, int hi) {
-  const nf_u32x4 *pd = reinterpret_cast<const nf_u32x4 *>(buf + l31 * D6_ROW + hi * 16);
-  constexpr int NU = 2 * OB, RB = 32 * D6_ROW / 16;  // 16-byte units per block of 32 rows
-  nf_u32x4 dn[3], dc[3];
-  const unsigned ones = 0x3F803F80u;  // bf16 (1, 1)
-  if (!LEAN) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) dn[c] = pd[c * 4];
-  }
-#pragma unroll
-  for (int u = 0; u < NU; ++u) {
-    const int g = u / OB, ob = u % OB;
-    if (LEAN) {  // no operand double buffer: 12 registers less, the LDS latency is left to the other wave of the SIMD
-#pragma unroll
-      for (int c = 0; c < 3; ++c) dc[c] = pd[ob * RB + c * 4 + g * 2];
-    } else {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) dc[c] = dn[c];
-      if (u + 1 < NU) {
-        const int g1 = (u + 1) / OB, ob1 = (u + 1) % OB;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) dn[c] = pd[ob1 * RB + c * 4 + g1 * 2];
-      }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int term = 0; term < 6; ++term)
-#pragma unroll
-      for (int ib = 0; ib < IB; ++ib) {
-        const nf_u32x4 &a = term == 0 ? as.l[ib][g] : (term == 2 || term == 3) ? as.m[ib][g] : as.h[ib][g];
-        const nf_u32x4 &d = term == 1 ? dc[2] : (term == 2 || term == 4) ? dc[1] : dc[0];
-        acc[ib][ob] = nf_mfma_bf16(a, d, acc[ib][ob]);
-        if (term * IB + ib < 6) {  // the twelve bias-sum instructions ride between the unit's first MFMAs
-          const int i0 = 2 * (term * IB + ib);
-#pragma unroll
-          for (int i = i0; i < i0 + 2; ++i) bsum[ob] = nf_dot2_bf16(dc[2 - i / 4][i % 4], ones, bsum[ob]);
-        }
-      }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
 
-// ---- the same hand-over through gfx950's transposing LDS read (round 6) ------------------------------------------------
-// split_to_lds transposes on the WRITE side: 8 two-byte stores per (k-group, component) and lane, 96 store instructions for a
+// ---- the pair kernel's hand-over through gfx950's transposing LDS read (round 6) ----------------------------------------
+// The D6 layout above transposes on the WRITE side (split_to_lds, tools/probe/d6_probe.hip): 8 two-byte stores per (k-group, component) and lane, 96 store instructions for a
 // 64-feature cotangent -- at the end of the producer's stage, on the pair kernel's critical path, through a store path four
 // producers share.  ds_read_b64_tr_b16 transposes on the READ side for free: within a 16-lane group, lane c receives element
 // (c & 3) of what lane 4 j + (c >> 2) read, j = 0..3 (tools/probe/ds_read_tr_probe.hip) -- a 4 x 16 tile handed over
@@ -1278,7 +1012,7 @@ __device__ __forceinline__ TrLane nf_tr_lane(const char *buf, int l31, int hi) {
   return TrLane{buf + (l31 >> 4) * TR_TILE + r0 * 32 + 8 * (q ^ ((r0 >> 2) & 3)), buf + (l31 >> 4) * TR_TILE + r1 * 32 + 8 * (q ^ ((r1 >> 2) & 3))};
 }
 // What the pair kernel's producer does with a finished 32-feature block of a cotangent, in twenty steps of a few instructions
-// each (the side job of dense_bwd_x_b6s_blocks): steps 0..7 pair p of the block -- its two leaky-ReLU slopes from the mask
+// each (all of them behind its dX GEMM: one vector burst): steps 0..7 pair p of the block -- its two leaky-ReLU slopes from the mask
 // (nf_lrelu_grad16's form), the product, the three-way split of the pair; steps 8..19 the twelve 8-byte hand-over stores of
 // the block's two k-groups (split_to_lds_tr's).  Steps beyond 19 do nothing.  `i` is a constant after unrolling.
 template <int NB>
@@ -1300,12 +1034,7 @@ struct PairPost {
       asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x6c" : "=v"(s1) : "v"(t1), "v"(one), "v"(flip));
       f32x2_t v = {d[b][2 * p], d[b][2 * p + 1]};
       const f32x2_t sl = {__builtin_bit_cast(float, s0), __builtin_bit_cast(float, s1)};
-#ifdef NF_SLOPE_SCALAR
-      asm("v_mul_f32 %0, %1, %2" : "=v"(v.x) : "v"(v.x), "v"(sl.x));
-      asm("v_mul_f32 %0, %1, %2" : "=v"(v.y) : "v"(v.y), "v"(sl.y));
-#else
       asm("v_pk_mul_f32 %0, %1, %2" : "=v"(v) : "v"(v), "v"(sl));
-#endif
       unsigned h, m, l;
       nf_split2(v.x, v.y, h, m, l);
       s.h[kg][e] = h; s.m[kg][e] = m; s.l[kg][e] = l;
@@ -1320,18 +1049,6 @@ struct PairPost {
 #pragma unroll
     for (int i = 0; i < 20; ++i) step(b, i);
   }
-  // hook h of NH (two behind every matrix instruction of the next block): the eight pair steps (14 instructions each) spread over
-  // the whole block, a k-group's six stores behind its fourth pair
-  template <int NH>
-  static constexpr int hook_of(int i) {
-    return i < 8 ? i * NH / 9 : i < 14 ? NH / 3 + 1 + (i - 8) * (NH / 3 - 1) / 6 : 7 * NH / 9 + 1 + (i - 14) * (NH - 7 * NH / 9 - 2) / 6;
-  }
-  template <int NH>
-  __device__ __forceinline__ void at_hook(int b, int h) const {
-#pragma unroll
-    for (int i = 0; i < 20; ++i)
-      if (hook_of<NH>(i) == h) step(b, i);
-  }
 };
 // one MFMA operand: the lane's feature column over the eight samples of sample group g (two transposing reads)
 __device__ __forceinline__ nf_u32x4 nf_tr_operand(const char *p0, const char *p1, int off) {
@@ -1341,40 +1058,12 @@ __device__ __forceinline__ nf_u32x4 nf_tr_operand(const char *p0, const char *p1
   const nf_u32x2 lo = __builtin_bit_cast(nf_u32x2, a), hi2 = __builtin_bit_cast(nf_u32x2, b);
   return nf_u32x4{lo.x, lo.y, hi2.x, hi2.y};
 }
-// The split of the consumer's NEXT activation operand, a pair of values (nine vector instructions) per call, for the issue shadows of
-// the GEMM that runs while it arrives: pair p of `at` at hook FIRST + EVERY p.  finish() splits what the hooks did not reach.
-template <int IB, int FIRST, int EVERY>
-struct SplitTJob {
-  const float (&at)[IB][16];
-  SplitT<IB> &s;
-  __device__ __forceinline__ void pair(int p) const {
-    const int ib = p >> 3, g = (p >> 2) & 1, e = p & 3;
-    unsigned h, m, l;
-    nf_split2(at[ib][8 * g + 2 * e], at[ib][8 * g + 2 * e + 1], h, m, l);
-    s.h[ib][g][e] = h; s.m[ib][g][e] = m; s.l[ib][g][e] = l;
-  }
-  __device__ __forceinline__ void operator()(int i) const {
-    if (i >= FIRST && (i - FIRST) % EVERY == 0 && (i - FIRST) / EVERY < 8 * IB) {
-      pair((i - FIRST) / EVERY);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-  template <int NH>  // NH: number of hooks the GEMM offered
-  __device__ __forceinline__ void finish() const {
-    constexpr int done = NH <= FIRST ? 0 : (NH - 1 - FIRST) / EVERY + 1;
-#pragma unroll
-    for (int p = done < 8 * IB ? done : 8 * IB; p < 8 * IB; ++p) pair(p);
-  }
-};
-// dw_accumulate_t6 on a cotangent left by split_to_lds_tr
-#ifndef NF_DW_DBUF
-#define NF_DW_DBUF 0
-#endif
-// (`sj(i)` is called behind the i-th of the 12 IB OB matrix instructions: the consumer's side job is the split of its NEXT
-// activation operand, SplitTJob below)
-template <int IB, int OB, class SJ = NoSideJob>
+// The dW GEMM with both operands split: the activation from split_T, the cotangent as the bf16 triples the PRODUCER wave made
+// for its own dX GEMM and left in LDS (split_to_lds_tr): six transposing reads per (sample group, delta block) and no VALU
+// work on the cotangent at all.  Pipeline unit = (sample group g, delta block ob).
+template <int IB, int OB>
 __device__ __forceinline__ void dw_accumulate_tr6(const SplitT<IB> &as, const char *buf, f32x16 (&acc)[IB][OB],
-                                                  float (&bsum)[OB], int l31, int hi, SJ sj = SJ()) {
+                                                  float (&bsum)[OB], int l31, int hi) {
   // lane offsets of the two reads: row hi + 2 jj (+ 8 for the second), chunk q at its swizzled position, the lane's tile of the pair
   const int c16 = l31 & 15, jj = c16 >> 2, q = c16 & 3, r0 = hi + 2 * jj, r1 = r0 + 8;
   const char *p0 = buf + (l31 >> 4) * TR_TILE + r0 * 32 + 8 * (q ^ ((r0 >> 2) & 3));
@@ -1382,27 +1071,13 @@ __device__ __forceinline__ void dw_accumulate_tr6(const SplitT<IB> &as, const ch
   constexpr int NU = 2 * OB;
   nf_u32x4 dc[3];
   const unsigned ones = 0x3F803F80u;  // bf16 (1, 1)
-#if NF_DW_DBUF  // the next unit's operands requested behind the current unit's matrix instructions (a second operand set: 12 registers)
-  nf_u32x4 dn[3];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) dn[c] = nf_tr_operand(p0, p1, (c * 4) * TR_TILE);
-#endif
 #pragma unroll
   for (int u = 0; u < NU; ++u) {
     const int g = u / OB, ob = u % OB;
-#if NF_DW_DBUF
-#pragma unroll
-    for (int c = 0; c < 3; ++c) dc[c] = dn[c];
-    if (u + 1 < NU) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) dn[c] = nf_tr_operand(p0, p1, (c * 4 + 2 * ((u + 1) % OB)) * TR_TILE + 512 * ((u + 1) / OB));
-    }
-#else
     // (no operand double buffer: with the woven consumer of round 6's first half the twelve registers of a second operand set cost
     // 28 bytes of scratch around the tile loop, the exposed LDS round trip per unit nothing measurable)
 #pragma unroll
     for (int c = 0; c < 3; ++c) dc[c] = nf_tr_operand(p0, p1, (c * 4 + 2 * ob) * TR_TILE + 512 * g);
-#endif
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int term = 0; term < 6; ++term)
@@ -1418,7 +1093,6 @@ __device__ __forceinline__ void dw_accumulate_tr6(const SplitT<IB> &as, const ch
           // four-instruction widen-and-add form that does costs the consumer 92-200 bytes of scratch: 370 against 330 us)
           for (int i = i0; i < i0 + 2; ++i) bsum[ob] = nf_dot2_bf16(dc[2 - i / 4][i % 4], ones, bsum[ob]);
         }
-        sj(u * 6 * IB + term * IB + ib);
       }
     __builtin_amdgcn_sched_barrier(0);
   }

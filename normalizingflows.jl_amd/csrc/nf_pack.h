@@ -113,9 +113,7 @@ __global__ __launch_bounds__(256) void k_b6t_from_images(int nimg, const float *
 // g[theta index] = sum over workgroup slabs of the image-layout partial gradients
 // Block 0 can also finish a deterministic sum of `nlpart` double partials into *lout (the step's loss:
 // saves a separate one-block launch in the training step).
-#ifndef NF_REDUCE_WAVES
 #define NF_REDUCE_WAVES 4
-#endif
 template <class G>
 __global__ __launch_bounds__(64 * NF_REDUCE_WAVES) void k_reduce_image_slabs(PackArgs p, const float *__restrict__ slab, int nslab,
                                                             long slab_stride, float *__restrict__ g,

@@ -32,9 +32,7 @@
 // kernel was linked at (an unrelated kernel removed from the file; identical ISA, tools/isa_stats.py).  hipcc's hazard
 // recognizer does not look inside inline asm, so every wait state between a vector instruction and a matrix instruction that
 // shares a register with it is the author's to supply, and the set nf_mfma_settle() supplied (12 states behind an accumulation
-// chain) was evidently not the whole set.  Not shipped: the builtin, whose hazards the compiler handles.
-#define RQS6_MFMA_W(a, b, c) nf_mfma_bf16(a, b, c)
-#define RQS6_SETTLE(c) ((void)0)
+// chain) was evidently not the whole set.  Not shipped: the builtin (nf_mfma_bf16), whose hazards the compiler handles.
 #include "nf_philox.h"
 #include "nf_target_epilogue.h"
 
@@ -340,11 +338,7 @@ __device__ __forceinline__ float rqs_coupling_step(const float *__restrict__ img
   f32x16 a2[G::H2B];
   {
     f32x16 a1[G::H1B];
-#ifdef RQS_COOP_R3
-    dense_fwd<G::MB, G::H1B>(img + G::W1, img + G::B1, xb, a1, l31, hi);
-#else
     dense_fwd_dyn<G::MB, G::H1B>(img + G::W1, img + G::B1, xb, a1, l31, hi, (m + 7) >> 3);
-#endif
 #pragma unroll
     for (int b = 0; b < G::H1B; ++b)
       nf_lrelu16(a1[b]);
@@ -831,15 +825,9 @@ __device__ __forceinline__ void rqs_fold(float *__restrict__ w, float *__restric
   }
 }
 
-#ifndef RQS_BWD_LAZY
 #define RQS_BWD_LAZY false
-#endif
-#ifndef RQS_DX3_SPLIT
 #define RQS_DX3_SPLIT 2  // independent accumulators of the cooperative kernel's dX3 GEMM (1 = the single chain)
-#endif
-#ifndef RQS_COOP_LAZY
 #define RQS_COOP_LAZY true  // the cooperative kernel has the registers for the lazy knot derivatives
-#endif
 // INVD: reverse pass of the INVERSE coupling at its output (forward-KL training): `y` holds w and is advanced
 // to coupling(w); `ybar` the cotangent of w -> that of the inverse's input; lbar the cotangent of ladj_inv.
 template <class G, bool INVD = false>
@@ -951,11 +939,9 @@ __device__ __forceinline__ void rqs_bwd_tile(const RqsBwdArgs &a, const float *_
       chunk_put<G>(out, ql, thb);
       tile_store(yio, tile_soff(q / 16, q % 16, a.par_t), xv);    // coupling input x1
       tile_store(gio, tile_soff(q / 16, q % 16, a.par_t), xbar);  // its cotangent
-#ifndef NF_RQS_NO_ELEM_FENCE
       // one element at a time: interleaving the two elements of a chunk doubles the live temporaries, and this kernel
       // sits at the register wall (224 dW accumulators in AGPRs + the chunk's 48 raw outputs + knots)
       __builtin_amdgcn_sched_barrier(0);
-#endif
     }
     // unused slots of the chunk (beyond QCH * P) carry raw outputs of zero-weight rows: clear them
 #pragma unroll
@@ -1108,13 +1094,9 @@ struct RqsCoopLds {
 // overtake it).  wave_lds_fence() (nf_mfma.h) additionally makes the wave WAIT for its outstanding LDS traffic
 // (s_waitcnt lgkmcnt(0)), which the transpose round trips below do not need: the consumer of the read has its own wait.
 __device__ __forceinline__ void wave_lds_order() {
-#ifdef RQS_COOP_R3
-  wave_lds_fence();
-#else
   asm volatile("" ::: "memory");
   __builtin_amdgcn_wave_barrier();
   asm volatile("" ::: "memory");
-#endif
 }
 
 // dW3^T of one (tile, chunk): acc[ib][pc] += a2^T x delta_pc^T for the chunk's OBC blocks of delta (`out` after the spline's
@@ -1187,13 +1169,8 @@ __device__ __forceinline__ void rqs_bwd_coop_coupling(const RqsBwdArgs &a, float
   // 16-bit byte offset; with the 60 KB image in front (round 3) the rows of a transpose tile straddled the 64 KB mark and
   // hipcc materialised a separate address register for most of them (131 v_add_u32 in the kernel, 59 per tile of the chunk
   // phase).  The image is addressed through one per-lane pointer plus row offsets below 50 KB wherever it sits.
-#ifdef RQS_COOP_R3
-  float *img = lds;
-  float *sc_all = lds + G::SIZE;
-#else
   float *sc_all = lds;
   float *img = lds + 4 * L::SCRATCH + 4 * L::NSETS * L::SLOT;
-#endif
   float *sc = sc_all + wave * L::SCRATCH;          // this wave's tiles
   float *slots = sc_all + 4 * L::SCRATCH;          // [NSETS][4][SLOT]
   float *sd = sc + L::OFF_D;
@@ -1224,16 +1201,10 @@ __device__ __forceinline__ void rqs_bwd_coop_coupling(const RqsBwdArgs &a, float
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const float v = tile_load(yio_, tile_soff(b, r, par_c));
-#ifdef RQS_COOP_R3
-        xb[b][r] = (live_ && tl_ * NF_TILE + l31 < a.N) ? v : 0.f;
-#else
         xb[b][r] = v;
-#endif
       }
   };
-#ifndef RQS_NO_PREFETCH
   if ((long)blockIdx.x < ngroups) load_home(blockIdx.x);
-#endif
 #ifdef NF_KERNEL_TRACE
   long long *tr = (a.trace && blockIdx.x == 0 && tid == 0) ? a.trace : nullptr;
   if (tr) { tr[100] = clock64(); tr[101] = wall_clock64(); }  // shader clock against the constant 100 MHz counter: the clock the kernel ran at
@@ -1254,23 +1225,14 @@ __device__ __forceinline__ void rqs_bwd_coop_coupling(const RqsBwdArgs &a, float
     const TileIO gio = make_tile_io(ybar, tl, a.d, l31, hi);
     unsigned m1[G::H1B], m2[G::H2B];
     (void)yio;
-#ifdef RQS_NO_PREFETCH
-    load_home(grp);
-#endif
     if (live) {
-#ifndef RQS_COOP_R3
 #pragma unroll
       for (int b = 0; b < G::MB; ++b)
 #pragma unroll
         for (int r = 0; r < 16; ++r) xb[b][r] = valid ? xb[b][r] : 0.f;
-#endif
       tile_to_scratch<G::MB>(sc + L::OFF_X, xb, l31, hi);
       f32x16 a1[G::H1B];
-#ifdef RQS_COOP_R3
-      dense_fwd<G::MB, G::H1B>(img + G::W1, img + G::B1, xb, a1, l31, hi);
-#else
       dense_fwd_dyn<G::MB, G::H1B>(img + G::W1, img + G::B1, xb, a1, l31, hi, (a.m + 7) >> 3);
-#endif
 #pragma unroll
       for (int b = 0; b < G::H1B; ++b) {
         nf_lrelu16(a1[b]);
@@ -1369,11 +1331,7 @@ __device__ __forceinline__ void rqs_bwd_coop_coupling(const RqsBwdArgs &a, float
         // this chunk's share of dX3 -> the home wave's slot
         {
           f32x16 d2p[G::H2B];
-#ifdef RQS_OLD_DX3
-          dense_bwd_x<G::H2B, G::OBC, G::S3>(img + G::W3 + ch * G::OBC * 32, out, d2p, l31, hi);
-#else
           dense_bwd_x_split<G::H2B, G::OBC, G::S3, RQS_DX3_SPLIT>(img + G::W3 + ch * G::OBC * 32, out, d2p, l31, hi);
-#endif
           float *mys = slots + ((L::NSETS == 2 ? (t & 1) : 0) * 4 + wave) * L::SLOT;
 #pragma unroll
           for (int b = 0; b < G::H2B; ++b)
@@ -1382,18 +1340,7 @@ __device__ __forceinline__ void rqs_bwd_coop_coupling(const RqsBwdArgs &a, float
         }
         COOP_STAMP(5 + 6 * t);
         // this chunk's columns of dW3^T: one block of delta at a time through the wave's own transpose tile
-#if defined(RQS_COOP_R3) || defined(RQS_COOP_OLD_DW3)
-#pragma unroll
-        for (int pc = 0; pc < G::OBC; ++pc) {
-          f32x16 one[1] = {out[pc]};
-          tile_to_scratch<1>(sd, one, l31, hi);
-          wave_lds_fence();
-          dw_accumulate_at<G::H2B, 1, G::OBC>(sct + L::OFF_A2, sd, acc.w3, acc.b3, pc, l31, hi);
-          wave_lds_fence();
-        }
-#else
         rqs_dw3_chunk<G>(sct + L::OFF_A2, sd, out, acc.w3, acc.b3, l31, hi);
-#endif
         COOP_STAMP(6 + 6 * t);
       }
       __syncthreads();  // B1: the four partial d2 of tile t are in the slots
@@ -1414,9 +1361,7 @@ __device__ __forceinline__ void rqs_bwd_coop_coupling(const RqsBwdArgs &a, float
     }
 
     // ---------------- home phase: layers 2 and 1 of this wave's own tile ----------------
-#ifndef RQS_NO_PREFETCH
     if (grp + gridDim.x < ngroups) load_home(grp + gridDim.x);  // in flight behind the 64 MFMAs of this phase
-#endif
     if (live) {
 #pragma unroll
       for (int b = 0; b < G::H2B; ++b)
@@ -1427,7 +1372,6 @@ __device__ __forceinline__ void rqs_bwd_coop_coupling(const RqsBwdArgs &a, float
       dw_accumulate<G::H1B, G::H2B>(sc + L::OFF_A1, sd, acc.w2, acc.b2, l31, hi);
       f32x16 d1[G::H1B];
       dense_bwd_x<G::H1B, G::H2B>(img + G::W2, d2, d1, l31, hi);
-#if !defined(RQS_COOP_R3) && !defined(RQS_COOP_GOLD_LATE)
       // the conditioner half of the cotangent tile is the accumulator the dX1 GEMM starts from.  Requested here, two GEMMs
       // ahead of its use (d2 is dead now; held from the start of the phase it cost 250-320 bytes of scratch spills)
       f32x16 g2[G::MB];
@@ -1435,7 +1379,6 @@ __device__ __forceinline__ void rqs_bwd_coop_coupling(const RqsBwdArgs &a, float
       for (int b = 0; b < G::MB; ++b)
 #pragma unroll
         for (int r = 0; r < 16; ++r) g2[b][r] = tile_load(gio, tile_soff(b, r, par_c));
-#endif
 #pragma unroll
       for (int b = 0; b < G::H1B; ++b)
 #pragma unroll
@@ -1444,26 +1387,12 @@ __device__ __forceinline__ void rqs_bwd_coop_coupling(const RqsBwdArgs &a, float
       tile_to_scratch<G::H1B>(sd, d1, l31, hi);
       wave_lds_order();
       dw_accumulate<G::MB, G::H1B>(sc + L::OFF_X, sd, acc.w1, acc.b1, l31, hi);
-#if defined(RQS_COOP_R3) || defined(RQS_COOP_GOLD_LATE)
-      f32x16 g2[G::MB], gold[G::MB];
-#pragma unroll
-      for (int b = 0; b < G::MB; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) gold[b][r] = tile_load(gio, tile_soff(b, r, par_c));
-      dense_bwd_x<G::MB, G::H1B>(img + G::W1, d1, g2, l31, hi);
-      wave_lds_order();
-#pragma unroll
-      for (int b = 0; b < G::MB; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) tile_store(gio, tile_soff(b, r, par_c), gold[b][r] + g2[b][r]);
-#else
       dense_bwd_x<G::MB, G::H1B, G::S1, true>(img + G::W1, d1, g2, l31, hi);
       wave_lds_order();
 #pragma unroll
       for (int b = 0; b < G::MB; ++b)
 #pragma unroll
         for (int r = 0; r < 16; ++r) tile_store(gio, tile_soff(b, r, par_c), g2[b][r]);
-#endif
     }
     COOP_STAMP(27);
     // no barrier here: the next group's home phase writes only this wave's own tiles, which the other waves stopped
@@ -1499,9 +1428,7 @@ __device__ __forceinline__ void rqs_bwd_coop_coupling(const RqsBwdArgs &a, float
 // VGPRs (234 used, no scratch): declaring a budget of two waves per SIMD makes hipcc select the VGPR form of the MFMAs and
 // drop the AGPR file altogether -- 3 062 instructions instead of 3 399.  (LDS still admits one workgroup per CU; the
 // second argument is a register budget here, not an occupancy.)  K = 10 would spill 88 bytes per lane and keeps the split.
-#ifndef RQS_COOP_WAVES_PER_SIMD
 #define RQS_COOP_WAVES_PER_SIMD(G) (G::K <= 8 ? 2 : 1)
-#endif
 template <class G, bool INVD>
 __global__ __launch_bounds__(256, RQS_COOP_WAVES_PER_SIMD(G)) void k_rqs_bwd_coop(RqsBwdArgs a, float *__restrict__ y, float *__restrict__ ybar,
                                                          const float *__restrict__ lbar, float lbar_const,
@@ -1719,15 +1646,14 @@ __device__ __forceinline__ void rqs_bwd_coop6_coupling(const RqsBwdArgs &a, floa
             const nf_u32x4 xh = pa[(kg * 3 + 0) * 64], xm = pa[(kg * 3 + 1) * 64], xl = pa[(kg * 3 + 2) * 64];
 #pragma unroll
             for (int ob = 0; ob < G::OBC; ++ob) {  // smallest terms first, as dense_fwd_b6
-              out[ob] = RQS6_MFMA_W(W.f[kg][ob][2], xh, out[ob]);
-              out[ob] = RQS6_MFMA_W(W.f[kg][ob][0], xl, out[ob]);
-              out[ob] = RQS6_MFMA_W(W.f[kg][ob][1], xm, out[ob]);
-              out[ob] = RQS6_MFMA_W(W.f[kg][ob][1], xh, out[ob]);
-              out[ob] = RQS6_MFMA_W(W.f[kg][ob][0], xm, out[ob]);
-              out[ob] = RQS6_MFMA_W(W.f[kg][ob][0], xh, out[ob]);
+              out[ob] = nf_mfma_bf16(W.f[kg][ob][2], xh, out[ob]);
+              out[ob] = nf_mfma_bf16(W.f[kg][ob][0], xl, out[ob]);
+              out[ob] = nf_mfma_bf16(W.f[kg][ob][1], xm, out[ob]);
+              out[ob] = nf_mfma_bf16(W.f[kg][ob][1], xh, out[ob]);
+              out[ob] = nf_mfma_bf16(W.f[kg][ob][0], xm, out[ob]);
+              out[ob] = nf_mfma_bf16(W.f[kg][ob][0], xh, out[ob]);
             }
           }
-          RQS6_SETTLE(out);
         }
         // ---- the spline and its reverse pass, in place (as k_rqs_bwd_coop)
 #pragma unroll
@@ -1802,12 +1728,12 @@ __device__ __forceinline__ void rqs_bwd_coop6_coupling(const RqsBwdArgs &a, floa
 #pragma unroll
               for (int ib = 0; ib < G::H2B; ++ib) {
                 f32x16 &dd = d2p[ib];
-                dd = RQS6_MFMA_W(W.t[kg][ib][2], dh, dd);
-                dd = RQS6_MFMA_W(W.t[kg][ib][0], dl, dd);
-                dd = RQS6_MFMA_W(W.t[kg][ib][1], dm, dd);
-                dd = RQS6_MFMA_W(W.t[kg][ib][1], dh, dd);
-                dd = RQS6_MFMA_W(W.t[kg][ib][0], dm, dd);
-                dd = RQS6_MFMA_W(W.t[kg][ib][0], dh, dd);
+                dd = nf_mfma_bf16(W.t[kg][ib][2], dh, dd);
+                dd = nf_mfma_bf16(W.t[kg][ib][0], dl, dd);
+                dd = nf_mfma_bf16(W.t[kg][ib][1], dm, dd);
+                dd = nf_mfma_bf16(W.t[kg][ib][1], dh, dd);
+                dd = nf_mfma_bf16(W.t[kg][ib][0], dm, dd);
+                dd = nf_mfma_bf16(W.t[kg][ib][0], dh, dd);
               }
             }
             wave_lds_order();
@@ -1836,7 +1762,6 @@ __device__ __forceinline__ void rqs_bwd_coop6_coupling(const RqsBwdArgs &a, floa
             }
             wave_lds_order();
           }
-          RQS6_SETTLE(d2p);
           float *mys = slots + ((t & 1) * 4 + wave) * L::SLOT;
 #pragma unroll
           for (int b = 0; b < G::H2B; ++b)

@@ -163,11 +163,7 @@ __device__ __forceinline__ float rq_logderiv(float s, float d0, float d1, float 
   const float den = s + (d1 + d0 - 2.f * s) * xi * om;
   // 2 log s + log(nd) - 2 log den as ONE logarithm: log(s^2 nd / den^2) (one v_rcp + one v_log instead of three logs)
   const float nd = d1 * xi * xi + 2.f * s * xi * om + d0 * om * om;
-#ifdef RQS_THREE_LOGS
-  return 2.f * nf_log(s) + nf_log(nd) - 2.f * nf_log(den);
-#else
   return nf_log(nf_fdiv(s * s * nd, den * den));
-#endif
 }
 
 // rqs_forward for one element: returns y, adds log dy/dx to logd

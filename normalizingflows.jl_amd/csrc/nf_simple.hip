@@ -2111,9 +2111,7 @@ static int step_launch(nf_ctx *ctx, const SimpleArgs &a, const void *theta, cons
 
 // ---- the planar step on the matrix pipe (k_planar_step), the radial step with one lane per (sample, feature half)
 //      (k_radial_step): d <= 64, up to 16 layers, Float32 -----------------------------------------------------------------
-#ifndef NF_PLANAR_MFMA_MIN_D
 #define NF_PLANAR_MFMA_MIN_D 2
-#endif
 static bool planar_mfma_ok(const nf_flow_desc *desc) {
   static const bool off = std::getenv("NF_PLANAR_NO_MFMA") != nullptr;  // A/B switch: k_simple_step
   return !off && desc->kind == NF_KIND_PLANAR && desc->dtype == NF_DTYPE_F32 && desc->d >= NF_PLANAR_MFMA_MIN_D && desc->d <= 64 &&

@@ -42,7 +42,7 @@ def test_every_pair_kernel_instantiation_is_register_resident(table):
 
 def test_stashing_fused_forward_entries_keep_their_resources(table):
     """the y store became a run-time branch (xt == nullptr): the default stashing forward and its target-switch twin stay scratch-free"""
-    for prefix in (f"void k_affine_chain<{H64}, false, true, true, false, false, 8>(", f"void k_affine_chain_tgt<{H64}, true, false, false, 8>("):
+    for prefix in (f"void k_affine_chain<{H64}, false, true, true, false, false>(", f"void k_affine_chain_tgt<{H64}, true, false, false, 8>("):
         hit = [r for r in table if r[0].startswith(prefix)]
         assert hit, prefix
         assert all(r[4] == 0 and r[2] <= 256 for r in hit), [(r[0][:90], r[2], r[4]) for r in hit]

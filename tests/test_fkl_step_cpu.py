@@ -71,8 +71,8 @@ def test_null_pointers_and_negative_sizes_are_argument_errors(nf):
 # the forward-KL chain kernels: k_affine_chain<G, INVERSE, FUSED, STASH, ...> and k_rqs_chain<G, INVERSE, FUSED, ...> with
 # INVERSE and FUSED both set (demangled names, as tools/kernel_resources.py prints them)
 FKL_KERNELS = (
-    "void k_affine_chain<NetGeo<1, 1, 1, 1, 4>, true, true, true, false, false, 8>(",
-    "void k_affine_chain<NetGeo<1, 2, 2, 1, 4>, true, true, true, false, false, 8>(",
+    "void k_affine_chain<NetGeo<1, 1, 1, 1, 4>, true, true, true, false, false>(",
+    "void k_affine_chain<NetGeo<1, 2, 2, 1, 4>, true, true, true, false, false>(",
     "void k_rqs_chain<RqsGeo<1, 1, 1, 8, 4, 2>, true, true, true>(",
     "void k_rqs_chain<RqsGeo<1, 1, 1, 8, 4, 2>, true, true, false>(",
     "void k_rqs_chain<RqsGeo<1, 1, 1, 10, 2, 2>, true, true, false>(",

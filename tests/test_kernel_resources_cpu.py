@@ -7,6 +7,7 @@ other role's loops), and nothing watched it.  ZERO lists the instantiations the 
 non-zero private_segment_fixed_size there fails the suite.  KNOWN lists the ones that still spill, each with the reason and
 a ceiling, so that they cannot get worse unnoticed either."""
 import os
+import re
 import sys
 
 import pytest
@@ -20,12 +21,12 @@ RQ8 = "RqsGeo<1, 1, 1, 8, 4, 2>"
 # kernel-name prefixes (demangled, as c++filt prints them) that must not use scratch
 ZERO = [
     # cfg 2: fused forward with the activation stash; reverse pass (FULL, forward direction, six-term products in both waves); epilogue
-    f"void k_affine_chain<{H64}, false, true, true, false, false, 8>(",
+    f"void k_affine_chain<{H64}, false, true, true, false, false>(",
     f"void k_affine_bwd_pair<{H64}, true, false, false, true, true>(",
     f"void k_affine_bwd_pair<{H64}, false, false, false, true, true>(",  # ragged batches / d < 64
     f"void k_affine_epilogue<{H64}, ",
     # cfg 5: the six-term inverse chain; forward-KL's reverse pass of the inverse chain
-    f"void k_affine_chain<{H64}, true, false, false, false, true, 8>(",
+    f"void k_affine_chain<{H64}, true, false, false, false, true>(",
     f"void k_affine_bwd_pair<{H64}, true, true, false, true, true>(",
     # cfg 3: fused forward chain (six-term output layer); the cooperative reverse kernel is in KNOWN
     f"void k_rqs_chain<{RQ8}, false, true, true>(",
@@ -45,7 +46,7 @@ KNOWN = [
     (f"void k_rqs_bwd_coop6<{RQ8}, ", 24,
      "512 registers: the wave's 144 weight registers + accumulators + the spline's state.  Four or five accumulator dwords are stored once "
      "before the tile-group loop and re-loaded in its closing phase (not in the chunk loop).  Zero with the weights as inline-asm AGPR "
-     "operands, which is not shipped (a matrix-instruction hazard hipcc does not cover inside asm: nf_rqs.hip, RQS6_MFMA_W)"),
+     "operands, which is not shipped (a matrix-instruction hazard hipcc does not cover inside asm: the note at the top of nf_rqs.hip)"),
     ("void k_deep_bwd<DeepGeo<3, 2>, ", 348,
      "three hidden layers of 64: 192 weight-gradient accumulators + the recompute's operands exceed 512 registers; the other DeepGeo shapes are scratch-free"),
     ("void k_g64m_bwd<G64M<1, 2, 6>, true>(", 1056,
@@ -95,3 +96,24 @@ def test_register_budgets_of_the_two_wave_kernels(table):
     for prefix in (f"void k_affine_bwd_pair<{H64}, ", f"void k_affine_chain<{H64}, ", f"void k_rqs_chain<{RQ8}, "):
         for r in _match(table, prefix):
             assert r[2] <= 256, (r[0][:100], r[1], r[2])
+
+
+# Names a preprocessor conditional in csrc may test: the tracing switches (tools/trace_*.py build with them) and the split
+# form nf_wide.hip chooses for itself before it includes nf_mfma.h.  Everything else is one path per kernel: a measured and
+# rejected variant is a patch under tools/experiments/, not an arm behind a macro that no build sets.
+SEAM_ALLOWED = {"NF_KERNEL_TRACE", "NF_TRACE_HIDDEN", "NF_TRACE_PAIR", "NF_SPLIT_SCALAR"}
+
+
+def test_no_build_time_variant_seams_in_the_kernel_sources():
+    csrc = os.path.join(ROOT, "normalizingflows.jl_amd", "csrc")
+    files = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".h")))
+    assert len(files) > 10, files
+    bad = []
+    for f in files:
+        with open(os.path.join(csrc, f)) as fh:
+            for i, line in enumerate(fh, 1):
+                m = re.match(r"\s*#\s*(?:if|ifdef|ifndef|elif)\b(.*)", line)
+                if m:
+                    bad += [f"{f}:{i}: {name}" for name in re.findall(r"\b(?:NF|RQS6?)_\w+", m.group(1).split("//")[0])
+                            if name not in SEAM_ALLOWED]
+    assert not bad, f"build-time seams on macros outside the allow-list: {bad}"

@@ -10,6 +10,18 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = "/opt/rocm/lib/llvm/bin/"
 
 
+def code_objects(bdir, tmp):
+    """The gfx950 code object of every object file under `bdir`, extracted into `tmp`: yields (object file name, path)."""
+    for obj in sorted(f for f in os.listdir(bdir) if f.endswith(".o")):
+        fb, co = os.path.join(tmp, obj + ".fatbin"), os.path.join(tmp, obj + ".co")
+        r = subprocess.run([LLVM + "llvm-objcopy", "--dump-section", f".hip_fatbin={fb}", os.path.join(bdir, obj)], capture_output=True)
+        if r.returncode:
+            continue
+        subprocess.run([LLVM + "clang-offload-bundler", "--unbundle", "--type=o", f"--input={fb}",
+                        "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"], check=True)
+        yield obj, co
+
+
 def kernel_table(bdir=None):
     """[(demangled name, agpr, vgpr, sgpr, scratch bytes, static LDS bytes)] of every kernel in the objects under `bdir`
     (default: the in-tree build directory).  Needs only the LLVM binutils of the ROCm image: runs in the build container."""
@@ -17,13 +29,7 @@ def kernel_table(bdir=None):
     rows = []
     # a private directory per call: a fixed path under /tmp may belong to another user, and then every object is skipped
     with tempfile.TemporaryDirectory(prefix="nfhip_co_") as tmp:
-        for obj in sorted(f for f in os.listdir(bdir) if f.endswith(".o")):
-            fb, co = os.path.join(tmp, obj + ".fatbin"), os.path.join(tmp, obj + ".co")
-            r = subprocess.run([LLVM + "llvm-objcopy", "--dump-section", f".hip_fatbin={fb}", os.path.join(bdir, obj)], capture_output=True)
-            if r.returncode:
-                continue
-            subprocess.run([LLVM + "clang-offload-bundler", "--unbundle", "--type=o", f"--input={fb}",
-                            "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"], check=True)
+        for _, co in code_objects(bdir, tmp):
             out = subprocess.run([LLVM + "llvm-readelf", "--notes", co], capture_output=True, text=True).stdout
             for blk in out.split("- .agpr_count:")[1:]:
                 g = lambda k: (re.search(rf"\.{k}:\s*(\S+)", blk) or [None, "?"])[1]

@@ -1,5 +1,6 @@
 // Probe (design aid, not part of the library): the transposed hand-over of bf16 triples between the two waves of the pair
-// kernel (split_C -> split_to_lds -> ds_read_b128, nf_mfma.h).  One wave writes a known tile as the producer does, reads it
+// kernel (split_C -> split_to_lds -> ds_read_b128: the round-4 form, below -- this file is its home since the kernel hands over through
+// ds_read_b64_tr_b16; the D6 row layout itself lives on in k_wide_dw_b6, nf_mfma.h: D6_ROW).  One wave writes a known tile as the producer does, reads it
 // back as the consumer does, rebuilds h + m + l per (feature, sample) and compares with the input; also checks
 // v_dot2c_f32_bf16 against (1, 1) as a sum of two bf16 values.
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I normalizingflows.jl_amd/csrc -I include tools/probe/d6_probe.hip -o tools/probe/d6_probe
@@ -9,6 +10,74 @@
 #include <vector>
 #include "nf_common.h"
 #include "nf_mfma.h"
+
+// the writer: a sample per lane and two features per packed register (the layout: nf_mfma.h, D6_ROW)
+constexpr int D6_BUF = 64 * D6_ROW;
+template <int NB>
+__device__ __forceinline__ void split_to_lds(char *__restrict__ buf, const SplitC<NB> &s, int l31, int hi) {
+  const int t = l31 >> 1;
+  char *p = buf + (4 * hi) * D6_ROW + (t >> 3) * 32 + (l31 & 1) * 16 + (t & 7) * 2;
+#pragma unroll
+  for (int kg = 0; kg < 2 * NB; ++kg)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const nf_u32x4 &v = c == 0 ? s.h[kg] : c == 1 ? s.m[kg] : s.l[kg];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int j0 = 2 * q, j1 = 2 * q + 1;
+        const int f0 = 16 * kg + (j0 & 3) + 8 * (j0 >> 2), f1 = 16 * kg + (j1 & 3) + 8 * (j1 >> 2);
+        *reinterpret_cast<unsigned short *>(p + f0 * D6_ROW + c * 64) = (unsigned short)v[q];
+        *reinterpret_cast<unsigned short *>(p + f1 * D6_ROW + c * 64) = (unsigned short)(v[q] >> 16);
+      }
+    }
+}
+
+// Both operands arrive split: the activation from split_T, the cotangent as the bf16 triples the PRODUCER wave made for its own
+// dX GEMM and left in LDS transposed (split_to_lds): three ds_read_b128 per (sample group, delta block) and no
+// VALU work on the cotangent at all.  The bias gradient is the sum of the triples' components (nf_dot2_bf16, nf_mfma.h).
+template <int IB, int OB, bool LEAN = false>
+__device__ __forceinline__ void dw_accumulate_t6(const SplitT<IB> &as, const char *buf, f32x16 (&acc)[IB][OB],
+                                                 float (&bsum)[OB], int l31, int hi) {
+  const nf_u32x4 *pd = reinterpret_cast<const nf_u32x4 *>(buf + l31 * D6_ROW + hi * 16);
+  constexpr int NU = 2 * OB, RB = 32 * D6_ROW / 16;  // 16-byte units per block of 32 rows
+  nf_u32x4 dn[3], dc[3];
+  const unsigned ones = 0x3F803F80u;  // bf16 (1, 1)
+  if (!LEAN) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) dn[c] = pd[c * 4];
+  }
+#pragma unroll
+  for (int u = 0; u < NU; ++u) {
+    const int g = u / OB, ob = u % OB;
+    if (LEAN) {  // no operand double buffer: 12 registers less, the LDS latency is left to the other wave of the SIMD
+#pragma unroll
+      for (int c = 0; c < 3; ++c) dc[c] = pd[ob * RB + c * 4 + g * 2];
+    } else {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) dc[c] = dn[c];
+      if (u + 1 < NU) {
+        const int g1 = (u + 1) / OB, ob1 = (u + 1) % OB;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) dn[c] = pd[ob1 * RB + c * 4 + g1 * 2];
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int term = 0; term < 6; ++term)
+#pragma unroll
+      for (int ib = 0; ib < IB; ++ib) {
+        const nf_u32x4 &a = term == 0 ? as.l[ib][g] : (term == 2 || term == 3) ? as.m[ib][g] : as.h[ib][g];
+        const nf_u32x4 &d = term == 1 ? dc[2] : (term == 2 || term == 4) ? dc[1] : dc[0];
+        acc[ib][ob] = nf_mfma_bf16(a, d, acc[ib][ob]);
+        if (term * IB + ib < 6) {  // the twelve bias-sum instructions ride between the unit's first MFMAs
+          const int i0 = 2 * (term * IB + ib);
+#pragma unroll
+          for (int i = i0; i < i0 + 2; ++i) bsum[ob] = nf_dot2_bf16(dc[2 - i / 4][i % 4], ones, bsum[ob]);
+        }
+      }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
 
 __device__ __host__ inline float val(int f, int s) { return __uint_as_float(0x3F800000u + 7919u * (unsigned)(f * 32 + s) + ((unsigned)(f & 3) << 23)); }  // bit patterns: no arithmetic to contract
 

@@ -1,5 +1,5 @@
 // Probe (design aid, not part of the library): is the split whose two subtractions run on the matrix pipe (nf_split16_mfma,
-// nf_mfma.h: D = x - h as C + (-selection) x h) BIT-IDENTICAL to the vector-instruction split nf_split2 / nf_split8?
+// below -- this file is its home since no shipped kernel calls it: D = x - h as C + (-selection) x h) BIT-IDENTICAL to the vector-instruction split nf_split2 / nf_split8?
 // Every wave takes 32 x 32 blocks of inputs -- normal draws over 80 binades, values on and next to bf16 rounding ties,
 // values whose residual is subnormal, +-0, the largest finite floats -- splits them both ways and counts differing words.
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I normalizingflows.jl_amd/csrc -I include tools/probe/split_mfma_probe.hip -o tools/probe/split_mfma_probe
@@ -12,6 +12,64 @@
 #include <vector>
 #include "nf_common.h"
 #include "nf_mfma.h"
+
+// ---- the split with its two exact subtractions ON THE MATRIX PIPE (round 6) -----------------------------------------------
+// nf_split2 spends 4.5 vector instructions per value, two thirds of them on r = x - h and l = r - m (widen h: shl + and per
+// pair, then v_pk_add_f32; the same for m).  Both differences are exact, and an MFMA computes exact differences for free:
+//     D = C + A B   with C = the fp32 block x (16 registers per lane, C layout), B = its packed bf16 part h (the very
+//                   registers the split produces), A = MINUS the selection matrix that maps B's k-order onto C's rows
+// gives D = x - h for the whole 32 x 32 block: every output is ONE product (-1 x h, exact) plus C, and x - h is a multiple
+// of ulp(x) below 2^-8 |x|, so the instruction's adder has nothing to drop (tools/probe/split_mfma_probe.hip compares all
+// three parts bit for bit with nf_split2 on random, tie, subnormal-adjacent and huge inputs).  A block of 16 values then
+// costs 8 + 8 + 8 conversions (1.5 instructions per value) and four v_mfma_f32_32x32x16_bf16 (two k-groups x two levels).
+// MEASURED (round 6): bit-identical, halves the vector instructions of the cfg-2 reverse kernel -- and buys
+// nothing there, in the cfg-5 chain or in k_rqs_bwd_coop6 (the split's MFMAs join the dependent chain of the wave that was
+// already the slower of its SIMD's two; these kernels are not bound by vector issue).  The primitive stays here, with its probe, for
+// the next kernel that IS; the call sites that were tried are tools/experiments/pair_chain_split_on_matrix_pipe.patch.
+// The selection operand: hardware k = 8 hi + j of k-group g is C row 16 g + (j & 3) + 8 (j >> 2) + 4 hi (nf_row(8 g + j, hi)),
+// so lane (row i = l31, half hi) holds -1 at element j iff i - 16 g - 4 hi = (j & 3) + 8 (j >> 2), zeros elsewhere.
+struct SplitSel {
+  nf_u32x4 a[2];  // A operands of the two k-groups
+};
+__device__ __forceinline__ SplitSel nf_split_sel(int l31, int hi) {
+  SplitSel s;
+#pragma unroll
+  for (int g = 0; g < 2; ++g) {
+    const int q = l31 - 16 * g - 4 * hi;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      const int j0 = 2 * p, j1 = 2 * p + 1;
+      const unsigned lo = q == (j0 & 3) + 8 * (j0 >> 2) ? 0xBF80u : 0u, hv = q == (j1 & 3) + 8 * (j1 >> 2) ? 0xBF800000u : 0u;
+      s.a[g][p] = lo | hv;
+    }
+  }
+  // pinned: hipcc otherwise rematerialises the eight compares + selects in front of every use
+  asm volatile("" : "+v"(s.a[0]), "+v"(s.a[1]));
+  return s;
+}
+// one C-layout block (16 values per lane) -> its triples per k-group g = register >> 3: h[g], m[g], l[g]
+__device__ __forceinline__ void nf_split16_mfma(const SplitSel &sel, const f32x16 &x, nf_u32x4 (&h)[2], nf_u32x4 (&m)[2],
+                                                nf_u32x4 (&l)[2]) {
+#pragma unroll
+  for (int g = 0; g < 2; ++g)
+#pragma unroll
+    for (int p = 0; p < 4; ++p) h[g][p] = nf_cvt_pk_bf16(nf_f32x2{x[8 * g + 2 * p], x[8 * g + 2 * p + 1]});
+  f32x16 r = nf_mfma_bf16(sel.a[0], h[0], x);
+  r = nf_mfma_bf16(sel.a[1], h[1], r);  // r = x - h
+#pragma unroll
+  for (int g = 0; g < 2; ++g)
+#pragma unroll
+    for (int p = 0; p < 4; ++p) m[g][p] = nf_cvt_pk_bf16(nf_f32x2{r[8 * g + 2 * p], r[8 * g + 2 * p + 1]});
+  f32x16 lo = nf_mfma_bf16(sel.a[0], m[0], r);
+  lo = nf_mfma_bf16(sel.a[1], m[1], lo);  // lo = r - m: at most 8 significant bits, its upper half IS the value
+#pragma unroll
+  for (int g = 0; g < 2; ++g)
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      const float e0 = lo[8 * g + 2 * p], e1 = lo[8 * g + 2 * p + 1];  // (scalars first: bit_cast of a vector element, see nf_coupling.hip)
+      l[g][p] = __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, e1), __builtin_bit_cast(unsigned, e0), 0x07060302u);
+    }
+}
 
 __global__ void k(const float *in, int nblocks, unsigned long long *bad, unsigned *first) {
   const int lane = threadIdx.x & 63, l31 = lane & 31, hi = lane >> 5;

@@ -135,6 +135,9 @@ function desc_of(flow::Bijectors.TransformedDistribution)
         return NFDesc(NF_KIND_PLANAR, dtype_code(T), d, Int32(length(Ls)), 0, nohid, 0, 0.0f0, C_NULL, C_NULL, Int32(0), C_NULL)
     elseif all(l -> l isa Bijectors.RadialLayer, Ls)
         return NFDesc(NF_KIND_RADIAL, dtype_code(T), d, Int32(length(Ls)), 0, nohid, 0, 0.0f0, C_NULL, C_NULL, Int32(0), C_NULL)
+    elseif length(Ls) == 2 && Ls[1] isa Bijectors.Shift && Ls[2] isa Bijectors.Scale{<:LinearAlgebra.LowerTriangular}
+        # full-rank family: theta = [shift ; the LowerTriangular's parent matrix, column-major] (its upper triangle is never read)
+        return NFDesc(NF_KIND_FULLRANK, dtype_code(T), d, Int32(1), 0, nohid, 0, 0.0f0, C_NULL, C_NULL, Int32(0), C_NULL)
     elseif length(Ls) == 2 && Ls[1] isa Bijectors.Shift && Ls[2] isa Bijectors.Scale
         return NFDesc(NF_KIND_MEANFIELD, dtype_code(T), d, Int32(1), 0, nohid, 0, 0.0f0, C_NULL, C_NULL, Int32(0), C_NULL)
     elseif all(l -> l isa AffineCoupling, Ls)
@@ -154,6 +157,7 @@ end
 # segment list (keyed by the segments' own bits -- desc_of runs on every rand / nfhip(flow) call, and a push-only list
 # would grow without bound in a sampling loop).
 const NF_KIND_COMPOSITE = Int32(6)
+const NF_KIND_FULLRANK = Int32(7)
 const SEGMENT_ROOTS = Dict{Vector{NFDesc},Vector{NFDesc}}()
 family(l) = l isa Bijectors.PlanarLayer ? :planar : l isa Bijectors.RadialLayer ? :radial : l isa AffineCoupling ? :realnvp :
             l isa NeuralSplineCoupling ? :nsf : error("nfhip: no device kernels for a $(typeof(l)) layer")

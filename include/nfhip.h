@@ -71,6 +71,22 @@ extern "C" {
                                  the reverse kernels' gradient row of nf_param_count elements must fit 128 KiB of LDS:
                                  at most 16 384 parameters in Float64, 32 768 in Float32. */
 
+#define NF_KIND_FULLRANK 7 /* Shift o Scale of test/interface.jl:22-25 with a LowerTriangular scale (a matrix where the reference
+                              passes a vector; built through create_flow, src/flows/utils.jl:23-26): y = mu + L x,
+                              ladj = sum_i log|L_ii| -- the full-rank Gaussian family of ADVI.  theta = [mu(d) ; L as a d x d
+                              column-major matrix] (shift first, as test/interface.jl:47-48 pins for the diagonal family), so
+                              nf_param_count = d + d^2 and nf_layer_count = 2 (flat order: Shift, Scale).  The strict upper
+                              triangle of L belongs to theta (the parent matrix of LowerTriangular) and is never read: every
+                              output has the same bits whatever it holds (NaN included), its gradient is exactly 0.0, Adam
+                              leaves it where it was.  Diagonal entries may be negative; zero is invalid.  nlayers must be 1
+                              (NF_ERR_ARG otherwise); n_hidden, K, B and score are ignored.  Limits: 1 <= d <= 256
+                              (NF_ERR_UNSUPPORTED beyond).  Served: nf_flow_fwd / inv / rand, nf_layer_apply, the tape pair
+                              and nf_flow_bwd, nf_elbo_batch(_rng), nf_elbo_value_and_grad, nf_elbo_step (the split sequence,
+                              with or without a communicator), general bases -- with EVERY built-in target, the linear-predictor
+                              kinds and the mixture included (Float32: the mixture up to d = 64, as for the coupling flows).
+                              NF_ERR_UNSUPPORTED: nf_loglikelihood, nf_loglikelihood_value_and_grad, nf_loglikelihood_step(_enqueue),
+                              nf_elbo_step_enqueue, and as a segment of NF_KIND_COMPOSITE. */
+
 #define NF_KIND_COMPOSITE 6 /* create_flow((L1, ..., Ln), q0) with MIXED bijector families (src/flows/utils.jl:23-26:
                                any list of bijectors composes).  `segments` lists the maximal runs of one family in FLAT
                                order (segment 0 = outermost = applied last), each a descriptor of one of the kinds above

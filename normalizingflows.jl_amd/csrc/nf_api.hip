@@ -151,6 +151,19 @@ int nf_hf_bwd(nf_ctx *, const nf_flow_desc *, const void *theta, const void *x, 
 int nf_hf_bwd_inv(nf_ctx *, const nf_flow_desc *, const void *theta, const void *u, const void *gbar, double lbar_const,
                   long N, void *gtheta_out, void *ws);
 
+// full-rank Gaussian family, Shift o Scale(LowerTriangular) (nf_fullrank.hip)
+bool nf_fr_supported(const nf_flow_desc *desc);
+size_t nf_fr_apply_ws_bytes(const nf_flow_desc *desc, bool inverse);
+int nf_fr_apply(nf_ctx *, const nf_flow_desc *, int lo, int hi, bool inverse, const void *theta, const void *x, long N, void *y,
+                void *ladj);
+size_t nf_fr_bwd_ws_bytes(nf_ctx *, const nf_flow_desc *, long N);
+int nf_fr_bwd(nf_ctx *, const nf_flow_desc *, const void *theta, const void *x, const void *ybar, const void *lbar,
+              double lbar_const, long N, void *xbar_out, void *gtheta_out, void *ws);
+int nf_fr_bwd_grid(nf_ctx *, long N);
+int nf_fr_fwd_tiled(nf_ctx *, const nf_flow_desc *, const float *theta, const float *xt, long N, float *yt, float *ladj);
+int nf_fr_grad(nf_ctx *, const nf_flow_desc *, const float *theta, const float *x, int x_tiled, const float *ybar, int y_tiled,
+               const float *lbar, float lbar_const, long N, float *slabs, float *gtheta_out);
+
 // ---- helpers -----------------------------------------------------------------------------
 // Every entry point's intermediates are ONE layout: a struct whose constructor takes its buffers from a Carver.  It runs over a
 // measuring Carver for nf_ws_reserve, then over ctx->ws (ws_carve); ws_need_bound() is the maximum of the same layouts.
@@ -170,12 +183,16 @@ static int check_base(const nf_base *b) {
 }
 
 static inline bool is_composite(const nf_flow_desc *d) { return d->kind == NF_KIND_COMPOSITE; }
+static inline bool is_fr(const nf_flow_desc *d) { return d->kind == NF_KIND_FULLRANK; }
+// the full-rank family in Float32: tiled batches, matrix-pipe kernels and the tiled target launchers
+static inline bool is_fr_tiled(const nf_flow_desc *d) { return is_fr(d) && d->dtype == NF_DTYPE_F32; }
 static int check_desc(const nf_flow_desc *d);
 static int check_composite(const nf_flow_desc *d) {
   if (d->nsegments < 1 || d->nsegments > 64 || !d->segments) return NF_ERR_ARG;
   for (int s = 0; s < d->nsegments; ++s) {
     const nf_flow_desc *g = &d->segments[s];
     if (g->kind == NF_KIND_COMPOSITE || g->kind == NF_KIND_HAMILTONIAN) return NF_ERR_ARG;
+    if (g->kind == NF_KIND_FULLRANK) return NF_ERR_UNSUPPORTED;  // not a segment yet
     if (g->d != d->d || g->dtype != d->dtype || g->base) return NF_ERR_ARG;  // q0 belongs to the composition
     NF_TRY(check_desc(g));
   }
@@ -200,6 +217,9 @@ static int check_desc(const nf_flow_desc *d) {
       if (d->d < 2) return NF_ERR_ARG;
       if (d->dtype != NF_DTYPE_F32) return nf_g64_supported(d) ? NF_OK : NF_ERR_UNSUPPORTED;
       return (nf_affine_supported(d) || nf_wide_supported(d) || nf_g64_supported(d)) ? NF_OK : NF_ERR_UNSUPPORTED;
+    case NF_KIND_FULLRANK:
+      if (d->nlayers != 1) return NF_ERR_ARG;
+      return nf_fr_supported(d) ? NF_OK : NF_ERR_UNSUPPORTED;
     case NF_KIND_HAMILTONIAN:
       if (d->d < 2 || (d->d & 1) || d->K < 1 || !d->score) return NF_ERR_ARG;
       return nf_hf_supported(d) ? NF_OK : NF_ERR_UNSUPPORTED;
@@ -257,6 +277,7 @@ extern "C" int64_t nf_param_count(const nf_flow_desc *d) {
     case NF_KIND_PLANAR: return (int64_t)d->nlayers * (2 * d->d + 1);
     case NF_KIND_RADIAL: return (int64_t)d->nlayers * (d->d + 2);
     case NF_KIND_MEANFIELD: return 2 * (int64_t)d->d;
+    case NF_KIND_FULLRANK: return (int64_t)d->d + (int64_t)d->d * d->d;  // shift, then the scale's parent matrix
     case NF_KIND_HAMILTONIAN: return 2 * (int64_t)d->d + 3 * (int64_t)(d->d / 2) * d->nlayers;
     case NF_KIND_REALNVP:
     case NF_KIND_NSF: {
@@ -283,7 +304,8 @@ extern "C" int32_t nf_layer_count(const nf_flow_desc *d) {
   switch (d->kind) {
     case NF_KIND_PLANAR:
     case NF_KIND_RADIAL: return d->nlayers;
-    case NF_KIND_MEANFIELD: return 2;
+    case NF_KIND_MEANFIELD:
+    case NF_KIND_FULLRANK: return 2;
     case NF_KIND_HAMILTONIAN: return d->nlayers + 1;  // blocks, then the reference's affine map
     case NF_KIND_REALNVP:
     case NF_KIND_NSF: return 2 * d->nlayers;
@@ -595,18 +617,21 @@ static inline bool is_g64(const nf_flow_desc *desc) {
 static int flat_apply(nf_ctx *ctx, const nf_flow_desc *desc, int lo, int hi, bool inverse, const void *theta,
                       const void *x, long N, void *y, void *ladj) {
   if (desc->kind == NF_KIND_HAMILTONIAN) return nf_hf_apply(ctx, desc, lo, hi, inverse, theta, x, N, y, ladj);
+  if (is_fr(desc)) return nf_fr_apply(ctx, desc, lo, hi, inverse, theta, x, N, y, ladj);
   if (is_g64(desc))
     return nf_g64_apply(ctx, desc, lo, hi, inverse, theta, x, N, y, ladj);
   return nf_simple_apply(ctx, desc, lo, hi, inverse, theta, x, N, y, ladj);
 }
 static size_t flat_bwd_ws_bytes(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
   if (desc->kind == NF_KIND_HAMILTONIAN) return nf_hf_bwd_ws_bytes(desc, N);
+  if (is_fr(desc)) return nf_fr_bwd_ws_bytes(ctx, desc, N);
   return is_g64(desc) ? nf_g64_bwd_ws_bytes(desc, N) : nf_simple_bwd_ws_bytes(ctx, desc, N);
 }
 static int flat_bwd(nf_ctx *ctx, const nf_flow_desc *desc, const void *theta, const void *x, const void *ybar,
                     const void *lbar, double lbar_const, long N, void *xbar_out, void *gtheta_out, void *ws) {
   if (desc->kind == NF_KIND_HAMILTONIAN)
     return nf_hf_bwd(ctx, desc, theta, x, ybar, lbar, lbar_const, N, xbar_out, gtheta_out, ws);
+  if (is_fr(desc)) return nf_fr_bwd(ctx, desc, theta, x, ybar, lbar, lbar_const, N, xbar_out, gtheta_out, ws);
   if (is_g64(desc))
     return nf_g64_bwd(ctx, desc, theta, x, ybar, lbar, lbar_const, N, xbar_out, gtheta_out, ws);
   return nf_simple_bwd(ctx, desc, theta, x, ybar, lbar, lbar_const, N, xbar_out, gtheta_out, ws, false);
@@ -652,7 +677,7 @@ static inline bool elbo_fusable(const nf_flow_desc *desc, const nf_target *targe
 // path) on draws of their own.
 static inline bool target_refused(const nf_flow_desc *desc, const nf_target *target) {
   if (!target || !target_has_own_kernel(target->kind)) return false;
-  if (target->kind == NF_TARGET_GAUSSMIX && desc->d > NF_MIXTURE_TILED_MAXD && is_coupling(desc)) return true;
+  if (target->kind == NF_TARGET_GAUSSMIX && desc->d > NF_MIXTURE_TILED_MAXD && (is_coupling(desc) || is_fr_tiled(desc))) return true;
   return desc->kind == NF_KIND_PLANAR || desc->kind == NF_KIND_RADIAL || desc->kind == NF_KIND_MEANFIELD ||
          desc->kind == NF_KIND_HAMILTONIAN;
 }
@@ -817,7 +842,7 @@ extern "C" int nf_flow_rand(nf_ctx *ctx, const nf_flow_desc *desc, const void *t
     NF_TRY(coupling_chain_tiled(ctx, desc, false, (const float *)theta, b.xt, N, b.ladj, -1));
     return nf_launch_layout_convert(ctx, desc->d, N, b.xt, (float *)y_out, 0);
   }
-  if (!is_g64(desc) && desc->kind != NF_KIND_HAMILTONIAN)
+  if (!is_g64(desc) && desc->kind != NF_KIND_HAMILTONIAN && !is_fr(desc))
     return nf_simple_rand(ctx, desc, theta, N, seed, sample_offset, stream_id, y_out);
   NF_TRY(nf_ws_reserve(ctx, carve_bytes((size_t)N * esize(desc->dtype))));
   NF_TRY(nf_launch_base_sample(ctx, desc->dtype, desc->d, N, seed, sample_offset, stream_id, y_out, nullptr));
@@ -1174,10 +1199,67 @@ struct ValueBufs {
 static int elbo_forward_composite(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, const void *theta,
                                   const void *xs, long N, uint64_t seed, uint64_t off, uint32_t stream_id, void *elbos_out,
                                   double *elbo_host);
+// The full-rank family in Float32: the ELBO sequence on tiled buffers.  Draws (or the caller's, converted) and log q0, the
+// triangular tile GEMM, the tiled target launch (value, score tile, ELBO partials), then -- training step only -- the reverse
+// kernel's slabs and their sum.  One layout for the value-only entry points and the step (slabs == nullptr in the former).
+struct FrElboBufs {
+  long nb;
+  int grid;
+  float *xt, *yt, *gt, *logq, *ladj, *slab;
+  double *partial, *result;
+  FrElboBufs() {}
+  FrElboBufs(Carver &cv, nf_ctx *ctx, const nf_flow_desc *desc, long N, bool grad) {
+    const size_t te = tiled_elems(desc, N);
+    nb = nf_target_tiled_nblocks(N);
+    grid = nf_fr_bwd_grid(ctx, N);
+    xt = cv.take<float>(te);
+    yt = cv.take<float>(te);
+    logq = cv.take<float>((size_t)N);
+    ladj = cv.take<float>((size_t)N);
+    partial = cv.take<double>(nb);
+    result = cv.take<double>(8);
+    gt = grad ? cv.take<float>(te) : nullptr;
+    slab = grad ? cv.take<float>((size_t)grid * (size_t)nf_param_count(desc)) : nullptr;
+  }
+};
+static int fr_draw_and_forward(nf_ctx *ctx, const nf_flow_desc *desc, const void *theta, const void *xs, long N, uint64_t seed,
+                               uint64_t off, uint32_t stream_id, const FrElboBufs &b) {
+  if (xs) {
+    NF_TRY(nf_launch_layout_convert(ctx, desc->d, N, (const float *)xs, b.xt, 1));
+    NF_TRY(nf_launch_base_logpdf_tiled(ctx, desc->d, N, b.xt, b.logq));
+  } else {
+    NF_TRY(nf_launch_base_sample_tiled(ctx, desc->d, N, seed, off, stream_id, b.xt, b.logq));
+  }
+  return nf_fr_fwd_tiled(ctx, desc, (const float *)theta, b.xt, N, b.yt, b.ladj);
+}
+static int fr_elbo_forward(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, const void *theta, const void *xs,
+                           long N, uint64_t seed, uint64_t off, uint32_t stream_id, void *elbos_out, double *elbo_host) {
+  FrElboBufs b;
+  NF_TRY(ws_carve(ctx, &b, desc, N, false));
+  NF_TRY(fr_draw_and_forward(ctx, desc, theta, xs, N, seed, off, stream_id, b));
+  NF_TRY(nf_launch_target_tiled(ctx, target, desc->d, N, b.yt, b.logq, b.ladj, nullptr, 0.0, (float *)elbos_out, b.partial,
+                                1.0 / (double)N));
+  NF_TRY(nf_launch_finish_sum(ctx, b.partial, b.nb, 0, b.result, nullptr, nullptr));
+  return read_scalar(ctx, b.result, elbo_host);
+}
+static int fr_value_and_grad(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, const void *theta, const void *xs,
+                             long N, long N_global, uint64_t seed, uint64_t off, uint32_t stream_id, void *out) {
+  const long P = nf_param_count(desc);
+  const double inv = 1.0 / (double)N_global;
+  FrElboBufs b;
+  NF_TRY(ws_carve(ctx, &b, desc, N, true));
+  NF_TRY(fr_draw_and_forward(ctx, desc, theta, xs, N, seed, off, stream_id, b));
+  // gt = d(-elbo/Ng)/dy = -(1/Ng) grad logp(y);  partial sums of -elbo_j/Ng
+  NF_TRY(nf_launch_target_tiled(ctx, target, desc->d, N, b.yt, b.logq, b.ladj, b.gt, -inv, nullptr, b.partial, -inv));
+  NF_TRY(nf_launch_finish_sum(ctx, b.partial, b.nb, 0, nullptr, (float *)out + P, nullptr));
+  return nf_fr_grad(ctx, desc, (const float *)theta, b.xt, 1, b.gt, 1, nullptr, (float)(-inv), N, b.slab, (float *)out);
+}
+
 static int elbo_forward(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, const void *theta,
                         const void *xs, long N, uint64_t seed, uint64_t off, uint32_t stream_id, void *elbos_out,
                         double *elbo_host) {
   if (is_composite(desc)) return elbo_forward_composite(ctx, desc, target, theta, xs, N, seed, off, stream_id, elbos_out, elbo_host);
+  if (is_fr_tiled(desc)) return fr_elbo_forward(ctx, desc, target, theta, xs, N, seed, off, stream_id, elbos_out, elbo_host);
   const size_t es = esize(desc->dtype);
   const bool cp = is_coupling(desc);
   const long nb = cp ? nf_target_tiled_nblocks(N) : nf_target_nblocks(N);
@@ -1202,7 +1284,7 @@ static int elbo_forward(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *
     NF_TRY(coupling_chain_tiled(ctx, desc, false, (const float *)theta, xt, N, (float *)ladj, -1));
     NF_TRY(nf_launch_target_tiled(ctx, target, desc->d, N, xt, (const float *)logq, (const float *)ladj, nullptr, 0.0,
                                   (float *)elbos_out, partial, 1.0 / (double)N));
-  } else if (!elbos_out && !is_g64(desc) && desc->kind != NF_KIND_HAMILTONIAN) {
+  } else if (!elbos_out && !is_g64(desc) && desc->kind != NF_KIND_HAMILTONIAN && !is_fr(desc)) {
     // planar / radial / mean-field, value only: draws (or xs), chain, target and ELBO sums in one launch
     NF_TRY(nf_target_check(target, desc->d));
     long np = 0;
@@ -1251,6 +1333,7 @@ extern "C" int nf_loglikelihood(nf_ctx *ctx, const nf_flow_desc *desc, const voi
                                 void *logliks_out, double *ll_host) {
   if (!ctx || !theta || !ys || !ll_host || N < 1) return NF_ERR_ARG;
   NF_TRY(check_desc(desc));
+  if (is_fr(desc)) return NF_ERR_UNSUPPORTED;  // the maximum-likelihood Gaussian is a closed form
   NF_HIP(hipSetDevice(ctx->device));
   if (flow_base(desc)) return loglikelihood_general_base(ctx, desc, theta, ys, N, logliks_out, ll_host);
   if (is_composite(desc)) return loglikelihood_composite(ctx, desc, theta, ys, N, logliks_out, ll_host);
@@ -1344,6 +1427,7 @@ extern "C" int nf_loglikelihood_value_and_grad(nf_ctx *ctx, const nf_flow_desc *
                                                int64_t N_local, int64_t N_global, void *out) {
   if (!ctx || !theta || !out || N_local < 0 || N_global < 1 || (N_local > 0 && !ys)) return NF_ERR_ARG;
   NF_TRY(check_desc(desc));
+  if (is_fr(desc)) return NF_ERR_UNSUPPORTED;
   NF_HIP(hipSetDevice(ctx->device));
   // general bases and heterogeneous compositions: segment by segment in the standard layout (fkl_general below)
   if (flow_base(desc) || is_composite(desc)) return fkl_general(ctx, desc, theta, ys, N_local, N_global, out);
@@ -1819,7 +1903,7 @@ struct VgBufs {
     wide = cp && is_wide(desc);
     nb = cp ? nf_target_tiled_nblocks(N) : nf_target_nblocks(N);
     grid = cp ? coupling_bwd_grid(ctx, desc, N) : 0;
-    simple_kind = !cp && !is_g64(desc) && desc->kind != NF_KIND_HAMILTONIAN;
+    simple_kind = !cp && !is_g64(desc) && desc->kind != NF_KIND_HAMILTONIAN && !is_fr(desc);
     // planar / radial / mean-field within the register budget: the whole step in one launch, nothing stashed
     simple_step = simple_kind && nf_simple_step_supported(desc);
     const size_t simple_ws = cp ? 0 : simple_step ? nf_simple_step_ws_bytes(ctx, desc, N) : flat_bwd_ws_bytes(ctx, desc, N);
@@ -1860,6 +1944,7 @@ extern "C" int nf_elbo_value_and_grad(nf_ctx *ctx, const nf_flow_desc *desc, con
   const int dt = desc->dtype;
   const size_t es = esize(dt);
   if (N == 0) return nf_launch_fill(ctx, dt, out, P + 1, 0.0);
+  if (is_fr_tiled(desc)) return fr_value_and_grad(ctx, desc, target, theta, xs, N, N_global, seed, sample_offset, stream_id, out);
   const double inv = 1.0 / (double)N_global;
   VgBufs b;
   NF_TRY(ws_carve(ctx, &b, desc, N));
@@ -2350,6 +2435,7 @@ static int step_split(nf_ctx *ctx, const nf_flow_desc *desc, const StepCall &c) 
 static int step_run(nf_ctx *ctx, const nf_flow_desc *desc, const StepCall &c, double *loss_host, double *gnorm_host, void *out_device) {
   NF_TRY(check_desc(desc));
   if (target_refused(desc, c.target)) return NF_ERR_UNSUPPORTED;
+  if (is_fr(desc) && (!c.target || c.step_device)) return NF_ERR_UNSUPPORTED;  // no forward-KL step, no graph-replay form
   NF_HIP(hipSetDevice(ctx->device));
   if (c.Ng < 1) return NF_ERR_ARG;
   const long P = nf_param_count(desc), N = c.N;
@@ -2480,6 +2566,12 @@ static size_t ws_need_bound(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
   }
   // nf_flow_fwd / inv / layer_apply, nf_flow_rand
   upd(is_coupling(desc) ? layout_bytes<RandBufs>(ctx, desc, N) : carve_bytes((size_t)N * esize(desc->dtype)));
+  if (is_fr(desc)) {  // the inverse's inv(L); the Float32 ELBO sequence; no forward-KL entry point
+    upd(nf_fr_apply_ws_bytes(desc, true));
+    if (is_fr_tiled(desc)) upd(layout_bytes<FrElboBufs>(ctx, desc, N, true));
+    else upd(layout_bytes<VgBufs>(ctx, desc, N)), upd(layout_bytes<ValueBufs>(ctx, desc, N, elbo_npartial(ctx, desc, N)));
+    return need;
+  }
   // nf_elbo_batch(_rng), nf_loglikelihood
   upd(layout_bytes<ValueBufs>(ctx, desc, N, elbo_npartial(ctx, desc, N)));
   upd(layout_bytes<ValueBufs>(ctx, desc, N, nf_sum2_nblocks(N)));

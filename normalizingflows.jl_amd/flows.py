@@ -219,6 +219,8 @@ class CompositeFlow(Flow):
         for f in segments:
             if isinstance(f, CompositeFlow) or f.kind == "hamiltonian":
                 raise NFHipError("create_flow: segments must be single-family flows")
+            if f.kind == "fullrank":
+                raise NFHipError("create_flow: a full-rank Shift o Scale(LowerTriangular) is not built as a segment yet")
             if f.dist.d != dist.d or f.theta.dtype != dt or f.theta.device != dev:
                 raise NFHipError("create_flow: every layer must share the dimension, element type and device")
         self.kind, self.dist, self.nlayers = "composite", dist, 1
@@ -454,6 +456,15 @@ def meanfield(q0: MvNormal, *, paramtype=torch.float64, device="cuda") -> Flow:
     flow = Flow("meanfield", q0, 1, dtype=paramtype, device=device)
     d = q0.d
     return _finish(flow, torch.cat([torch.zeros(d, dtype=torch.float64), torch.ones(d, dtype=torch.float64)]))
+
+
+def fullrank(q0: MvNormal, *, paramtype=torch.float64, device="cuda") -> Flow:
+    """transformed(q0, Shift(zeros) o Scale(LowerTriangular(I))): the full-rank Gaussian family (the Shift o Scale of
+    test/interface.jl:22-25 with a matrix scale).  theta = [mu(d) ; L, d x d column-major]; the strict upper triangle of
+    L is part of theta and is never read by the library."""
+    flow = Flow("fullrank", q0, 1, dtype=paramtype, device=device)
+    d = q0.d
+    return _finish(flow, torch.cat([torch.zeros(d, dtype=torch.float64), torch.eye(d, dtype=torch.float64).reshape(-1)]))
 
 
 def hamiltonianflow(dims: int, nblocks: int, nleapfrog: int, target, *, logeps0: float = math.log(0.05),

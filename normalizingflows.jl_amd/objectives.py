@@ -34,8 +34,8 @@ def _builtin(flow: Flow, logp) -> bool:
     check_target(logp, flow.theta.dtype, flow.theta.device, _target_dim(flow))
     if isinstance(logp, _LINPRED) and flow.kind in _NO_LINPRED_KINDS:
         return False  # the closure route: the target's own autograd node supplies the device score
-    if isinstance(logp, MixtureTarget) and flow.kind in ("realnvp", "nsf") and flow.theta.dtype == torch.float32 and logp.d > 64:
-        return False  # the library refuses Float32 coupling flows beyond the tiled mixture kernel's d = 64: the closure route
+    if isinstance(logp, MixtureTarget) and flow.kind in ("realnvp", "nsf", "fullrank") and flow.theta.dtype == torch.float32 and logp.d > 64:
+        return False  # the library refuses Float32 coupling and full-rank flows beyond the tiled mixture kernel's d = 64: the closure route
     return True
 
 

@@ -57,6 +57,7 @@ const NF_TARGET_GAUSSMIX = Int32(8)                                  # Gaussian 
 # generalised linear-predictor targets (nfhip.h): row offsets, row weights, a linear term, a family parameter
 const NF_TARGET_GLM_LOGIT, NF_TARGET_GLM_PROBIT, NF_TARGET_GLM_POISSON, NF_TARGET_GLM_STUDENT, NF_TARGET_GLM_NORMAL =
     Int32(9), Int32(10), Int32(11), Int32(12), Int32(13)
+const NF_TARGET_SOFTMAX = Int32(15)                                  # softmax regression (nfhip.h; kind 14 is unassigned)
 dtype_code(::Type{Float32}) = Int32(0)
 dtype_code(::Type{Float64}) = Int32(1)
 
@@ -320,6 +321,35 @@ c_target(t::GLMTarget) = NFTarget(t.kind, devptr(t.p0), devptr(t.At), Float64(si
 function check_target(t::GLMTarget, ::Type{T}, d) where {T}
     (eltype(t.At) === T && eltype(t.p0) === T && size(t.At, 1) == d && length(t.p0) == d + 2 * size(t.At, 2) + 2) ||
         error("nfhip: target must hold $d-dimensional data rows in $T")
+end
+# Softmax (multinomial-logit) regression over z = vec(W), W the p × C weight matrix (column-major: class-major in z, d = C p):
+#   log p(z) = const + Σ_i wt_i (x_i·W[:, c_i] − logsumexp_c x_i·W[:, c]) − |z|²/(2σ²) − d/2 log(2πσ²),  labels c_i ∈ 1:C (Julia's
+# 1-based classes; the device reads them 0-based).  The device reads X row-major (the column-major p × rows array `Xt`) and ONE
+# buffer p0 = lab[rows] | wt[rows] | (1/σ², const − d/2 log(2πσ²)).  σ = Inf is the flat prior.  Same flows as the GLM targets.
+# (Written without a Julia at hand: unrun.)
+struct SoftmaxTarget{V<:ROCVector,M<:ROCMatrix} <: NFHipTarget
+    Xt::M            # p × rows
+    p0::V            # 2 rows + 2
+    C::Int
+end
+function SoftmaxTarget(X::AbstractMatrix{T}, labels::AbstractVector{<:Integer}, C::Integer=maximum(labels); weights=nothing,
+                       constant::Real=0.0, σ::Real=1.0) where {T}
+    rows, p = size(X)
+    (rows >= 1 && p >= 1 && all(isfinite, X)) || error("nfhip: X must be a finite rows × p matrix")
+    (2 <= C <= 16 && C * p <= 256) || error("nfhip: 2 <= C <= 16 classes and C p <= 256")
+    (length(labels) == rows && all(c -> 1 <= c <= C, labels)) || error("nfhip: one label in 1:C per row")
+    wt = weights === nothing ? ones(Float64, rows) : Float64.(weights)
+    (length(wt) == rows && all(w -> isfinite(w) && w >= 0, wt)) || error("nfhip: weights have one finite entry >= 0 per row")
+    (isfinite(constant) && σ > 0 && !isnan(σ)) || error("nfhip: constant must be finite, prior σ > 0 (Inf: flat prior)")
+    d = C * p
+    prec, c0 = isinf(σ) ? (0.0, 0.0) : (1 / σ^2, -0.5 * d * log(2π * σ^2))
+    p0 = vcat(Float64.(labels .- 1), wt, Float64[prec, constant + c0])
+    return SoftmaxTarget(ROCArray(Matrix{T}(transpose(X))), ROCArray(Vector{T}(p0)), Int(C))
+end
+c_target(t::SoftmaxTarget) = NFTarget(NF_TARGET_SOFTMAX, devptr(t.p0), devptr(t.Xt), Float64(size(t.Xt, 2)), Float64(t.C))
+function check_target(t::SoftmaxTarget, ::Type{T}, d) where {T}
+    (eltype(t.Xt) === T && eltype(t.p0) === T && t.C * size(t.Xt, 1) == d && length(t.p0) == 2 * size(t.Xt, 2) + 2) ||
+        error("nfhip: target must hold $(t.C) classes of $(d ÷ t.C)-dimensional data rows in $T")
 end
 c_target(t::DenseGaussTarget) = NFTarget(NF_TARGET_DENSEGAUSS, devptr(t.μ), devptr(t.Wt), t.logdetW, 0.0)
 c_target(t::LogRegTarget) = NFTarget(NF_TARGET_LOGREG, t.shift === nothing ? C_NULL : devptr(t.shift), devptr(t.At), Float64(size(t.At, 2)), t.σ)

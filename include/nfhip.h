@@ -164,6 +164,25 @@ extern "C" {
 #define NF_TARGET_GLM_POISSON 11
 #define NF_TARGET_GLM_STUDENT 12
 #define NF_TARGET_GLM_NORMAL 13
+/* Softmax (multinomial-logit) regression: the posterior of C weight vectors w_c in R^p under the prior N(0, sigma^2 I), data
+ * rows x_i, labels c_i in {0 .. C-1} and row weights wt_i >= 0.  Kind 14 stays unassigned (as kind 7 does).
+ *   y in R^d, d = C p, class-major: y = [w_0; ...; w_{C-1}] -- vec(W) of the p x C weight matrix in column-major order, logits = X W.
+ *       u_{i,c}    = x_i . w_c
+ *       log p(y)   = par[1] + sum_i wt_i (u_{i,c_i} - logsumexp_c u_{i,c}) - par[0] |y|^2 / 2,
+ *       grad_{w_c} = sum_i wt_i (1[c_i = c] - softmax_c(u_i)) x_i - par[0] w_c.
+ *   p1 = X[rows x p] row-major (an intercept is a ones column);  p0 = ONE buffer of 2 rows + 2 elements: lab[rows] | wt[rows] |
+ *   par[2], the labels as integer-valued elements, par[0] the prior precision 1 / sigma^2 (0: the flat prior) and par[1] the
+ *   additive constant the host folded (-d/2 log(2 pi sigma^2) plus any multinomial coefficients);  s0 = rows (an integer value,
+ *   1 <= rows < 2^31);  s1 = C (an integer value, 2 <= C <= 16).  All device pointers are in the flow's element type.
+ *   NF_ERR_ARG for a NULL p0 / p1, a bad s0, a non-integral or out-of-range s1, or d % C != 0 -- before any device work;
+ *   NF_ERR_UNSUPPORTED for d > 256.
+ * A row with wt_i == 0 contributes exactly 0 to the value and the gradient (by select: a subsampling mask may sit over a row
+ * whose logits are not finite).  The log-sum-exp subtracts the row maximum: nothing overflows for finite logits, nothing is
+ * clamped.  Served exactly like NF_TARGET_GLM_*: nf_target_logp (d <= 256), RealNVP / NSF flows of either element type
+ * including the weight-streaming shapes, full-rank flows, general bases and compositions; nf_elbo_step runs the split
+ * sequence, nf_elbo_step_enqueue answers NF_ERR_UNSUPPORTED; planar, radial, mean-field and Hamiltonian flows answer
+ * NF_ERR_UNSUPPORTED at every ELBO entry point, a Hamiltonian score included. */
+#define NF_TARGET_SOFTMAX 15
 
 #define NF_MAX_HIDDEN 4
 

@@ -23,6 +23,9 @@ NF_TARGET_GAUSSMIX = 8
 # generalised linear-predictor targets: p1 = A[rows, d]; p0 = one buffer lin[d] | off[rows] | wt[rows] | par[2]
 # (par[0] = family parameter, par[1] = folded constant); s0 = rows; s1 = prior sigma (+inf: flat prior)
 NF_TARGET_GLM_LOGIT, NF_TARGET_GLM_PROBIT, NF_TARGET_GLM_POISSON, NF_TARGET_GLM_STUDENT, NF_TARGET_GLM_NORMAL = 9, 10, 11, 12, 13
+# softmax regression: p1 = X[rows, p]; p0 = one buffer lab[rows] | wt[rows] | par[2] (par[0] = prior precision, par[1] = folded
+# constant); s0 = rows; s1 = the number of classes C (2..16), d = C p class-major.  (kind 14 is unassigned)
+NF_TARGET_SOFTMAX = 15
 NF_MAX_HIDDEN = 4
 NF_ERR_NONFINITE = -4
 

@@ -630,6 +630,9 @@ int nf_target_check(const nf_target *t, int d) {
     case NF_TARGET_GLM_STUDENT:
     case NF_TARGET_GLM_NORMAL:  // s0 = the number of rows, as for LOGREG; s1 = the prior sigma, +inf for the flat prior (NaN fails s1 > 0)
       return (t->p0 && t->p1 && t->s1 > 0 && t->s0 >= 1 && t->s0 < 2147483648.0 && t->s0 == (double)(long)t->s0) ? NF_OK : NF_ERR_ARG;
+    case NF_TARGET_SOFTMAX:  // s0 = the number of rows, as for LOGREG; s1 = the number of classes, an integer in 2..16 that divides d (NaN fails s1 >= 2)
+      return (t->p0 && t->p1 && t->s0 >= 1 && t->s0 < 2147483648.0 && t->s0 == (double)(long)t->s0 && t->s1 >= 2 && t->s1 <= 16 &&
+              t->s1 == (double)(int)t->s1 && d >= 1 && d % (int)t->s1 == 0) ? NF_OK : NF_ERR_ARG;
     default: return NF_ERR_ARG;
   }
 }
@@ -648,6 +651,12 @@ int nf_launch_target_mixture(nf_ctx *, int dtype, const nf_target *, int d, long
                              double pscale);
 int nf_launch_target_mixture_tiled(nf_ctx *, const nf_target *, int d, long N, const float *yt, const float *logq,
                                    const float *ladj, float *gt, double gscale, float *elbos_out, double *partial, double pscale);
+// nf_softmax.hip: the softmax regression target, the same contract
+int nf_launch_target_softmax(nf_ctx *, int dtype, const nf_target *, int d, long N, const void *y, const void *logq,
+                             const void *ladj, void *logp_out, void *grad_out, double gscale, void *elbos_out, double *partial,
+                             double pscale);
+int nf_launch_target_softmax_tiled(nf_ctx *, const nf_target *, int d, long N, const float *yt, const float *logq,
+                                   const float *ladj, float *gt, double gscale, float *elbos_out, double *partial, double pscale);
 
 int nf_launch_target(nf_ctx *ctx, int dtype, const nf_target *t, int d, long N, const void *y, const void *logq,
                      const void *ladj, void *logp_out, void *grad_out, double gscale, void *elbos_out, double *partial,
@@ -658,6 +667,8 @@ int nf_launch_target(nf_ctx *ctx, int dtype, const nf_target *t, int d, long N, 
     if (joint_d > 0) return NF_ERR_UNSUPPORTED;  // (the ELBO entry points refuse Hamiltonian flows with these kinds first)
     if (t->kind == NF_TARGET_GAUSSMIX)
       return nf_launch_target_mixture(ctx, dtype, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
+    if (t->kind == NF_TARGET_SOFTMAX)
+      return nf_launch_target_softmax(ctx, dtype, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
     return nf_launch_target_linpred(ctx, dtype, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
   }
   ProfScope ps(ctx, "target");
@@ -778,6 +789,8 @@ int nf_launch_target_tiled(nf_ctx *ctx, const nf_target *t, int d, long N, const
   NF_TRY(nf_target_check(t, d));
   if (t->kind == NF_TARGET_GAUSSMIX)
     return nf_launch_target_mixture_tiled(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
+  if (t->kind == NF_TARGET_SOFTMAX)
+    return nf_launch_target_softmax_tiled(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
   if (target_is_linpred(t->kind))
     return nf_launch_target_linpred_tiled(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
   ProfScope ps(ctx, "target");

@@ -132,6 +132,10 @@ __host__ __device__ inline bool target_is_linpred(int kind) {
 }
 // The Gaussian mixture (NF_TARGET_GAUSSMIX, nf_mixture.hip) is routed like them: a kernel of its own behind
 // nf_launch_target / nf_launch_target_tiled, refused wherever target_term would have to evaluate it.
-__host__ __device__ inline bool target_has_own_kernel(int kind) { return target_is_linpred(kind) || kind == NF_TARGET_GAUSSMIX; }
+// So is the softmax regression target (NF_TARGET_SOFTMAX, nf_softmax.hip): C predictors per data row, coupled through a
+// log-sum-exp, which the one-function-per-row form of the linear-predictor kernels cannot express.
+__host__ __device__ inline bool target_has_own_kernel(int kind) {
+  return target_is_linpred(kind) || kind == NF_TARGET_GAUSSMIX || kind == NF_TARGET_SOFTMAX;
+}
 // widest flow the mixture's tiled kernel serves (two U and two G blocks in registers); the flat kernel goes to 256
 #define NF_MIXTURE_TILED_MAXD 64

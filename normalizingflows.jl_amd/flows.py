@@ -583,7 +583,7 @@ class _LinpredLogp(torch.autograd.Function):
 
 
 class _LinpredTarget:
-    """What MvNormalTarget, LogisticRegressionTarget, MixtureTarget and the GLM targets share: the matrix `A` [rows, d] and the optional shift `mu`,
+    """What MvNormalTarget, LogisticRegressionTarget, MixtureTarget, the GLM targets and SoftmaxRegressionTarget share: the matrix `A` [rows, d] and the optional shift `mu`,
     kept alive for the descriptor's device pointers, and the checks DiagGaussTarget makes (the ABI reads p0 / p1 untyped)."""
 
     def check_compatible(self, dtype, device, d=None):
@@ -865,6 +865,82 @@ class LinearRegressionTarget(GLMTarget):
         const = float(w.sum()) * (-0.5 * math.log(2.0 * math.pi) - math.log(sn))
         to = lambda t: t.to(X.dtype).to(X.device)
         super().__init__("normal", to(X64 / sn), to(-yv / sn), to(w), None, const, 0.0, prior_sigma, _name=nm)
+
+
+class SoftmaxRegressionTarget(_LinpredTarget):
+    """Posterior of Bayesian softmax (multinomial-logit) regression over the weight matrix W [p, C]: data rows X [rows, p],
+    labels c_i in {0 .. C-1}, row weights w_i >= 0 (0 drops the row exactly), prior N(0, prior_sigma^2 I):
+        logp(z) = const + sum_i w_i (x_i . W[:, c_i] - logsumexp_c x_i . W[:, c]) - |z|^2 / (2 prior_sigma^2) - d/2 log(2 pi prior_sigma^2)
+    with z = vec(W) in column-major order (class-major: z = [W[:, 0]; ...; W[:, C-1]], d = C p) -- `weights(z)` gives W back.
+    An intercept is a ones column of X.  prior_sigma = math.inf is the flat prior.  The constants are folded in float64; the
+    device reads `A` = X and ONE buffer `p0` = labels | weights | (1 / prior_sigma^2, const - d/2 log(2 pi prior_sigma^2)),
+    both kept alive here."""
+
+    def __init__(self, X, labels, n_classes=None, weights=None, prior_sigma=1.0, const=0.0, _name="SoftmaxRegressionTarget"):
+        nm = _name
+        _glm_matrix(nm, X)
+        rows, p = X.shape
+        lab = _glm_vector(nm, "labels", labels, X, rows)
+        if bool((lab != torch.round(lab)).any()) or bool((lab < 0).any()):
+            raise NFHipError(f"{nm}: labels must be integers >= 0")
+        C_ = int(lab.max()) + 1 if n_classes is None else n_classes
+        if isinstance(C_, float) and C_ == int(C_):
+            C_ = int(C_)
+        if isinstance(C_, bool) or not hasattr(C_, "__index__") or not 2 <= int(C_) <= 16:
+            raise NFHipError(f"{nm}: the number of classes must be an integer in 2..16" + (" (give n_classes)" if n_classes is None else ""))
+        C_ = int(C_)
+        if bool((lab >= C_).any()):
+            raise NFHipError(f"{nm}: labels must be in 0..{C_ - 1}")
+        if C_ * p > 256:
+            raise NFHipError(f"{nm}: n_classes * p = {C_ * p} exceeds the kernels' d = 256")
+        wt = _glm_vector(nm, "weights", weights, X, rows, 1.0, nonneg=True)
+        const = _glm_scalar(nm, "const", const, positive=False)
+        self.prior_sigma = _glm_scalar(nm, "prior_sigma", prior_sigma, allow_inf=True)
+        d = C_ * p
+        flat = math.isinf(self.prior_sigma)
+        self.precision = 0.0 if flat else 1.0 / self.prior_sigma**2
+        self.const = const + (0.0 if flat else -0.5 * d * math.log(2.0 * math.pi * self.prior_sigma**2))
+        self.d, self.p, self.n_classes, self.rows = d, p, C_, rows
+        self.A = X.detach().contiguous()
+        self.X = self.A
+        self.p0 = torch.cat([lab, wt, torch.tensor([self.precision, self.const], dtype=torch.float64)]).to(X.dtype).to(X.device).contiguous()
+        self.c = Target(_lib.NF_TARGET_SOFTMAX, self.p0.data_ptr(), self.A.data_ptr(), float(rows), float(C_))
+
+    def weights(self, y):
+        """the weight matrix W [p, C] of a parameter vector y (d,) -- or [p, C, N] of a batch (d, N)"""
+        if y.shape[0] != self.d:
+            raise NFHipError(f"SoftmaxRegressionTarget.weights: expected {self.d} leading elements, got {y.shape[0]}")
+        W = y.reshape(self.n_classes, self.p, *y.shape[1:])
+        return W.transpose(0, 1)
+
+
+class MultinomialRegressionTarget(SoftmaxRegressionTarget):
+    """Posterior of multinomial (softmax-link) regression on count data: counts[i, :] ~ Multinomial(n_i, softmax(x_i W)),
+    n_i = sum_c counts[i, c].  Expands to one softmax row per non-zero (i, c) with weight counts[i, c] * weights[i] and folds
+    sum_i weights_i [lgamma(n_i + 1) - sum_c lgamma(counts[i, c] + 1)] into the constant."""
+
+    def __init__(self, X, counts, weights=None, prior_sigma=1.0):
+        nm = "MultinomialRegressionTarget"
+        _glm_matrix(nm, X)
+        n = X.shape[0]
+        if not isinstance(counts, torch.Tensor) or counts.dim() != 2 or counts.shape[0] != n or counts.device != X.device or \
+                (counts.dtype.is_floating_point and counts.dtype != X.dtype) or counts.dtype.is_complex or counts.dtype == torch.bool:
+            raise NFHipError(f"{nm}: counts must be a matrix [rows, C] on the data matrix's device, of its element type or an integer tensor")
+        C_ = counts.shape[1]
+        if not 2 <= C_ <= 16:
+            raise NFHipError(f"{nm}: the number of classes (columns of counts) must be in 2..16")
+        k = counts.detach().to("cpu", torch.float64)
+        if not bool(torch.isfinite(k).all()) or bool((k < 0).any()) or bool((k != torch.round(k)).any()):
+            raise NFHipError(f"{nm}: counts must be non-negative integers")
+        w = _glm_vector(nm, "weights", weights, X, n, 1.0, nonneg=True)
+        i_idx, c_idx = torch.nonzero(k, as_tuple=True)
+        if i_idx.numel() == 0:
+            raise NFHipError(f"{nm}: every count is zero")
+        coef = torch.lgamma(k.sum(1) + 1.0) - torch.lgamma(k + 1.0).sum(1)
+        const = float((w * coef).sum())
+        to = lambda t: t.to(X.dtype).to(X.device)
+        self.counts = k
+        super().__init__(X.detach()[i_idx.to(X.device)], to(c_idx.to(torch.float64)), C_, to(k[i_idx, c_idx] * w[i_idx]), prior_sigma, const, _name=nm)
 
 
 def check_target(target, dtype, device=None, d=None):

@@ -57,6 +57,7 @@ const NF_TARGET_GAUSSMIX = Int32(8)                                  # Gaussian 
 # generalised linear-predictor targets (nfhip.h): row offsets, row weights, a linear term, a family parameter
 const NF_TARGET_GLM_LOGIT, NF_TARGET_GLM_PROBIT, NF_TARGET_GLM_POISSON, NF_TARGET_GLM_STUDENT, NF_TARGET_GLM_NORMAL =
     Int32(9), Int32(10), Int32(11), Int32(12), Int32(13)
+const NF_TARGET_HGLM_OFFSET = Int32(7)                                # hierarchical GLM kinds 16..20 = the GLM kind + 7 (nfhip.h)
 const NF_TARGET_SOFTMAX = Int32(15)                                  # softmax regression (nfhip.h; kind 14 is unassigned)
 dtype_code(::Type{Float32}) = Int32(0)
 dtype_code(::Type{Float64}) = Int32(1)
@@ -350,6 +351,80 @@ c_target(t::SoftmaxTarget) = NFTarget(NF_TARGET_SOFTMAX, devptr(t.p0), devptr(t.
 function check_target(t::SoftmaxTarget, ::Type{T}, d) where {T}
     (eltype(t.Xt) === T && eltype(t.p0) === T && t.C * size(t.Xt, 1) == d && length(t.p0) == 2 * size(t.Xt, 2) + 2) ||
         error("nfhip: target must hold $(t.C) classes of $(d ÷ t.C)-dimensional data rows in $T")
+end
+# Hierarchical GLM over z = [β (p coefficients) ; τ (G group log-scales)], d = p + G, centred parameterisation:
+#   log p(z) = const + Σ_i wt_i φ(u_i; param) + lin·β + Σ_j log N(β_j; 0, σ_j²) + Σ_g log p(τ_g),  u = Aβ + offset,
+#   σ_j = fixedσ[j] where groups[j] == 0 (Inf: flat), exp(τ_g) where groups[j] == g ∈ 1:G (Julia's 1-based groups; the device reads
+#   −1 and 0-based).  hyper[g] ∈ (:lognormal, :halfnormal, :halfcauchy): τ_g ~ N(loc, scale²), or exp(τ_g) half-normal / half-Cauchy of
+#   that scale as a density over τ_g.  Everything linear in z or constant is folded here in Float64, as the Python mirror does.  The
+#   device reads A padded with zero τ-columns, row-major (the column-major d × rows array `At`), and ONE buffer
+#   p0 = lin[d] | off[rows] | wt[rows] | (param, const) | grp[p] | isd[p] | hm[G] | his[G] | hk[G] | gptr[G+1] | gidx[p].
+# Same flows as the GLM targets.  (Written without a Julia at hand: unrun.)
+struct HierarchicalGLMTarget{V<:ROCVector,M<:ROCMatrix} <: NFHipTarget
+    kind::Int32
+    At::M            # d × rows
+    p0::V            # 4 d + 2 rows + 3 + G
+    G::Int
+end
+const HYPER_KINDS = Dict(:lognormal => 0.0, :halfnormal => 1.0, :halfcauchy => 2.0)
+function HierarchicalGLMTarget(family::Symbol, A::AbstractMatrix{T}, groups::AbstractVector{<:Integer}, G::Integer; offset=nothing,
+                               weights=nothing, lin=nothing, constant::Real=0.0, param::Real=0.0, fixedσ=1.0, hyper=:halfcauchy,
+                               hyperloc=0.0, hyperscale=1.0) where {T}
+    haskey(GLM_KINDS, family) || error("nfhip: family must be one of $(sort(collect(keys(GLM_KINDS))))")
+    rows, p = size(A)
+    (rows >= 1 && p >= 1 && all(isfinite, A)) || error("nfhip: A must be a finite rows × p matrix")
+    (G >= 0 && p + G <= 256) || error("nfhip: G >= 0 and p + G <= 256")
+    (length(groups) == p && all(g -> 0 <= g <= G, groups)) || error("nfhip: one group in 0:G per column (0: a fixed prior scale)")
+    d = p + G
+    off = offset === nothing ? zeros(Float64, rows) : Float64.(offset)
+    wt = weights === nothing ? ones(Float64, rows) : Float64.(weights)
+    ln = lin === nothing ? zeros(Float64, p) : Float64.(lin)
+    (length(off) == rows && length(wt) == rows && length(ln) == p) || error("nfhip: offset and weights have one entry per row, lin one per column")
+    (all(isfinite, off) && all(isfinite, ln) && all(w -> isfinite(w) && w >= 0, wt)) || error("nfhip: offsets and lin must be finite, weights finite and >= 0")
+    (isfinite(constant) && isfinite(param) && (family !== :student || param > 0)) || error("nfhip: constant and param must be finite, ν > 0")
+    per(v, n) = v isa AbstractVector ? Float64.(v) : fill(Float64(v), n)
+    σ, loc, scl = per(fixedσ, p), per(hyperloc, G), per(hyperscale, G)
+    hyp = hyper isa Symbol ? fill(hyper, G) : collect(hyper)
+    (length(σ) == p && all(s -> s > 0 && !isnan(s), σ)) || error("nfhip: fixedσ must be > 0 (Inf: flat), a scalar or one per column")
+    (length(hyp) == G && all(h -> haskey(HYPER_KINDS, h), hyp)) || error("nfhip: hyper must be one of $(sort(collect(keys(HYPER_KINDS)))), or one per group")
+    (length(loc) == G && length(scl) == G && all(isfinite, loc) && all(s -> isfinite(s) && s > 0, scl)) || error("nfhip: hyperloc finite, hyperscale finite and > 0")
+    L2PI = log(2π)
+    c = Float64(constant)
+    isd = zeros(Float64, p)
+    lintau = zeros(Float64, G)
+    for j in 1:p
+        if groups[j] > 0
+            lintau[groups[j]] -= 1.0
+            c -= 0.5 * L2PI
+        elseif isfinite(σ[j])
+            isd[j] = 1 / σ[j]
+            c -= log(σ[j]) + 0.5 * L2PI
+        end
+    end
+    hm, his = zeros(Float64, G), zeros(Float64, G)
+    for g in 1:G
+        if hyp[g] === :lognormal
+            hm[g], his[g] = loc[g], 1 / scl[g]
+            c += -log(scl[g]) - 0.5 * L2PI
+        else
+            hm[g] = log(scl[g])
+            lintau[g] += 1.0
+            c += (hyp[g] === :halfnormal ? 0.5 : 1.0) * log(2 / π) - hm[g]
+        end
+    end
+    members = [findall(==(g), groups) for g in 1:G]                      # increasing column index
+    gptr = Float64.(vcat(0, cumsum(length.(members))))
+    gidx = zeros(Float64, p)
+    flat = reduce(vcat, members; init=Int[])
+    gidx[1:length(flat)] .= flat .- 1
+    p0 = vcat(ln, lintau, off, wt, Float64[param, c], Float64.(groups .- 1), isd, hm, his, Float64[HYPER_KINDS[h] for h in hyp], gptr, gidx)
+    At = vcat(Matrix{T}(transpose(A)), zeros(T, G, rows))
+    return HierarchicalGLMTarget(GLM_KINDS[family] + NF_TARGET_HGLM_OFFSET, ROCArray(At), ROCArray(Vector{T}(p0)), Int(G))
+end
+c_target(t::HierarchicalGLMTarget) = NFTarget(t.kind, devptr(t.p0), devptr(t.At), Float64(size(t.At, 2)), Float64(t.G))
+function check_target(t::HierarchicalGLMTarget, ::Type{T}, d) where {T}
+    (eltype(t.At) === T && eltype(t.p0) === T && size(t.At, 1) == d && length(t.p0) == 4 * d + 2 * size(t.At, 2) + 3 + t.G) ||
+        error("nfhip: target must hold $d-dimensional data rows ($(d - t.G) coefficients and $(t.G) log-scales) in $T")
 end
 c_target(t::DenseGaussTarget) = NFTarget(NF_TARGET_DENSEGAUSS, devptr(t.μ), devptr(t.Wt), t.logdetW, 0.0)
 c_target(t::LogRegTarget) = NFTarget(NF_TARGET_LOGREG, t.shift === nothing ? C_NULL : devptr(t.shift), devptr(t.At), Float64(size(t.At, 2)), t.σ)

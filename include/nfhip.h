@@ -183,6 +183,41 @@ extern "C" {
  * sequence, nf_elbo_step_enqueue answers NF_ERR_UNSUPPORTED; planar, radial, mean-field and Hamiltonian flows answer
  * NF_ERR_UNSUPPORTED at every ELBO entry point, a Hamiltonian score included. */
 #define NF_TARGET_SOFTMAX 15
+/* Hierarchical GLM targets: the five GLM families under a structured prior -- groups of coefficients share a scale that is
+ * itself a coordinate with a hyper-prior (random intercepts, varying slopes, eight schools, shrinkage priors; the centred
+ * parameterisation, whose joint density has the funnel's geometry).  Kind = the GLM kind + 7.
+ *   y in R^d is [beta (p coefficients) ; tau (G group log-scales)], d = p + G, p >= 1, 0 <= G <= d - 1.  Coefficient j has
+ *   the prior N(0, sigma_j^2) with a fixed sigma_j when grp_j = -1 and N(0, exp(tau_g)^2) when grp_j = g in [0, G).
+ *       u        = A y + off                                  (A is rows x d; the tau-columns are usually zero)
+ *       w_j(y)   = isd_j^2 (isd = 1 / sigma_j; 0: a flat prior on that coefficient)  if grp_j < 0,   exp(-2 tau_{grp_j})  otherwise
+ *       x_g      = tau_g - hm_g
+ *       h_g(x)   = -(x his_g)^2 / 2    hk_g = 0   tau_g ~ N(hm, 1 / his^2)                (log-normal scale)
+ *                = -exp(2 x) / 2       hk_g = 1   exp(tau_g) ~ half-normal(s),  hm = log s
+ *                = -softplus(2 x)      hk_g = 2   exp(tau_g) ~ half-Cauchy(s),  hm = log s
+ *       log p(y) = par[1] + sum_i wt_i phi(u_i; par[0]) + lin . y - sum_{j<p} beta_j^2 w_j(y) / 2 + sum_g h_g(x_g)
+ *       d beta_j = [A' (wt o phi')]_j + lin_j - beta_j w_j
+ *       d tau_g  = [A' (wt o phi')]_{p+g} + lin_{p+g} + exp(-2 tau_g) sum_{j: grp_j = g} beta_j^2 + h_g'(x_g)
+ *       h'       = -x his^2 | -exp(2 x) | -2 sigmoid(2 x)
+ *   Everything linear in y or constant is folded by the host: the -n_g tau_g of the Gaussian normalisers and the +tau_g
+ *   Jacobian of the two half-families sit in lin[p + g], every normaliser in par[1].
+ *   p1 = A[rows x d] row-major;  s0 = rows (an integer value, 1 <= rows < 2^31);  s1 = G (an integer value, 0 <= G <= d - 1);
+ *   p0 = ONE buffer of 4 d + 2 rows + 3 + G elements in the flow's element type:
+ *       lin[d] | off[rows] | wt[rows] | par[2] | grp[p] | isd[p] | hm[G] | his[G] | hk[G] | gptr[G + 1] | gidx[p]
+ *   grp, hk, gptr and gidx are integer-valued elements; gptr / gidx are the CSR member lists of the groups, each group's
+ *   members in increasing feature index (which fixes the summation order).  NF_ERR_ARG for a NULL p0 / p1, a bad s0 or a bad
+ *   s1 (NaN included) -- before any device work;  NF_ERR_UNSUPPORTED for d > 256.  The host cannot validate device memory:
+ *   every index read from p0 is bounded by select before it addresses anything (a grp outside [0, G) is -1, a gidx outside
+ *   [0, p) contributes 0, gptr is clamped to [0, p]).
+ * Row weights as for NF_TARGET_GLM_*.  Nothing is clamped: a non-finite value is reported by nf_elbo_step as
+ * NF_ERR_NONFINITE.  Served exactly like NF_TARGET_GLM_*: nf_target_logp (d <= 256), RealNVP / NSF flows of either element
+ * type including the weight-streaming shapes, full-rank flows, general bases and compositions; nf_elbo_step runs the split
+ * sequence, nf_elbo_step_enqueue answers NF_ERR_UNSUPPORTED; planar, radial, mean-field and Hamiltonian flows answer
+ * NF_ERR_UNSUPPORTED at every ELBO entry point, a Hamiltonian score included. */
+#define NF_TARGET_HGLM_LOGIT 16
+#define NF_TARGET_HGLM_PROBIT 17
+#define NF_TARGET_HGLM_POISSON 18
+#define NF_TARGET_HGLM_STUDENT 19
+#define NF_TARGET_HGLM_NORMAL 20
 
 #define NF_MAX_HIDDEN 4
 

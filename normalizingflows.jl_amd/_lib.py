@@ -26,6 +26,9 @@ NF_TARGET_GLM_LOGIT, NF_TARGET_GLM_PROBIT, NF_TARGET_GLM_POISSON, NF_TARGET_GLM_
 # softmax regression: p1 = X[rows, p]; p0 = one buffer lab[rows] | wt[rows] | par[2] (par[0] = prior precision, par[1] = folded
 # constant); s0 = rows; s1 = the number of classes C (2..16), d = C p class-major.  (kind 14 is unassigned)
 NF_TARGET_SOFTMAX = 15
+# hierarchical GLM targets (the GLM kind + 7): y = [beta (p) ; tau (G)], d = p + G; p1 = A[rows, d]; p0 = one buffer
+# lin[d] | off[rows] | wt[rows] | par[2] | grp[p] | isd[p] | hm[G] | his[G] | hk[G] | gptr[G + 1] | gidx[p]; s0 = rows; s1 = G
+NF_TARGET_HGLM_LOGIT, NF_TARGET_HGLM_PROBIT, NF_TARGET_HGLM_POISSON, NF_TARGET_HGLM_STUDENT, NF_TARGET_HGLM_NORMAL = 16, 17, 18, 19, 20
 NF_MAX_HIDDEN = 4
 NF_ERR_NONFINITE = -4
 

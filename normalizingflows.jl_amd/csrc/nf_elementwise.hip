@@ -633,6 +633,13 @@ int nf_target_check(const nf_target *t, int d) {
     case NF_TARGET_SOFTMAX:  // s0 = the number of rows, as for LOGREG; s1 = the number of classes, an integer in 2..16 that divides d (NaN fails s1 >= 2)
       return (t->p0 && t->p1 && t->s0 >= 1 && t->s0 < 2147483648.0 && t->s0 == (double)(long)t->s0 && t->s1 >= 2 && t->s1 <= 16 &&
               t->s1 == (double)(int)t->s1 && d >= 1 && d % (int)t->s1 == 0) ? NF_OK : NF_ERR_ARG;
+    case NF_TARGET_HGLM_LOGIT:
+    case NF_TARGET_HGLM_PROBIT:
+    case NF_TARGET_HGLM_POISSON:
+    case NF_TARGET_HGLM_STUDENT:
+    case NF_TARGET_HGLM_NORMAL:  // s0 = the number of rows, as for LOGREG; s1 = the number of group log-scales G, an integer in 0..d-1 (NaN fails s1 >= 0)
+      return (t->p0 && t->p1 && t->s0 >= 1 && t->s0 < 2147483648.0 && t->s0 == (double)(long)t->s0 && t->s1 >= 0 &&
+              t->s1 <= (double)(d - 1) && t->s1 == (double)(int)t->s1) ? NF_OK : NF_ERR_ARG;
     default: return NF_ERR_ARG;
   }
 }

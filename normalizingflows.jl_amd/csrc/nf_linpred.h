@@ -1,6 +1,6 @@
 // nf_linpred.h -- the row functions and the row data of the linear-predictor targets (nf_linpred.hip).
 //
-// A linear-predictor target is a sum of ONE scalar function over the rows of a matrix product plus a Gaussian prior.  Two
+// A linear-predictor target is a sum of ONE scalar function over the rows of a matrix product plus a prior.  Three
 // forms share the kernels:
 //   centred (kinds 5, 6)   log p(y) = c + sum_i phi(u_i) - pw |y|^2 / 2,   u = A (y - mu),   grad = A' phi'(u) - pw y
 //     DENSEGAUSS  phi(u) = -u^2 / 2        c = -d/2 log(2 pi) + log|det W|     pw = 0           (A = W = inv(L))
@@ -11,8 +11,11 @@
 //                          for the flat prior sigma = +inf), with the row data in ONE device buffer
 //                          p0 = lin[d] | off[rows] | wt[rows] | par[2]   (GlmRows below).
 //     LOGIT log sigmoid(u) | PROBIT log Phi(u) | POISSON -exp(u) | STUDENT -(nu + 1)/2 log1p(u^2 / nu) | NORMAL -u^2 / 2
+//   hierarchical (kinds 16..20, NF_TARGET_HGLM_* = the GLM kind + 7)
+//                          the generalised form over y = [beta (p) ; tau (G)] with the structured prior of HierRows below in
+//                          place of the isotropic one (c = pw = 0; s1 = G), its data behind par[2] in the same buffer.
 // A row function returns phi(u; par) and phi'(u; par) of ONE element; both target kernels are templated on it and on the
-// form (a bool: the centred instantiations compile the row data away).  par is the family parameter par[0], read once per
+// form (LP_CENTRED / LP_GLM / LP_HIER: the centred instantiations compile the row data away).  par is the family parameter par[0], read once per
 // launch (nu for STUDENT; the other families ignore it).  A row of weight 0 contributes exactly 0 by SELECT, whatever phi
 // returns there (a subsampling mask may sit over a row whose phi overflows); nothing is clamped.
 #pragma once
@@ -111,6 +114,70 @@ __device__ __forceinline__ void glm_weigh(T w, T &phi, T &dphi) {
   dphi = w == (T)0 ? (T)0 : w * dphi;
 }
 
+// The three forms of the two kernel bodies (their template argument FORM).
+#define LP_CENTRED 0
+#define LP_GLM 1
+#define LP_HIER 2
+
+// The structured prior of the hierarchical form (NF_TARGET_HGLM_*): y = [beta (p) ; tau (G)], the prior data behind the row
+// data in the same buffer,   ... par[2] | grp[p] | isd[p] | hm[G] | his[G] | hk[G] | gptr[G + 1] | gidx[p].
+// The host cannot validate device memory, so every index read from the buffer is bounded by SELECT before it addresses
+// anything: a garbage buffer gives wrong numbers, never an access outside y's d features or the buffer's own arrays.
+template <class T>
+struct HierRows {
+  const T *grp, *isd, *hm, *his, *hk, *gptr, *gidx;
+  int p, G;
+  __device__ __forceinline__ HierRows(const T *p0, int d, int rows, int ng) : p(d - ng), G(ng) {
+    grp = p0 + d + 2 * (long)rows + 2;
+    isd = grp + p;
+    hm = isd + p;
+    his = hm + G;
+    hk = his + G;
+    gptr = hk + G;
+    gidx = gptr + G + 1;
+  }
+  // an integer-valued element as an index of [0, n), or -1 (NaN fails both comparisons)
+  static __device__ __forceinline__ int index_in(T v, int n) { return (v >= (T)0 && v < (T)n) ? (int)v : -1; }
+  // Coefficient i < p of a sample whose feature f is y(f): the prior's share of log p and of d log p / d beta_i.
+  template <class Y>
+  __device__ __forceinline__ void coef(int i, T beta, Y &&y, T &val, T &grad) const {
+    const int g = index_in(grp[i], G);
+    const T sd = isd[i];
+    const T om = g < 0 ? sd * sd : lp_exp((T)-2 * y(p + g));
+    grad = -beta * om;
+    val = (T)-0.5 * (beta * beta) * om;
+  }
+  // Log-scale g < G, tau = y(p + g): the hyper-prior h_g and the members' beta^2 exp(-2 tau), summed in list order.
+  template <class Y>
+  __device__ __forceinline__ void scale(int g, T tau, Y &&y, T &val, T &grad) const {
+    const T a = gptr[g], b = gptr[g + 1];
+    const int lo = a >= (T)0 ? (a <= (T)p ? (int)a : p) : 0, hi = b >= (T)0 ? (b <= (T)p ? (int)b : p) : 0;  // clamped to [0, p]; NaN -> 0
+    T ss = 0;
+    for (int k = lo; k < hi; ++k) {
+      const int j = index_in(gidx[k], p);
+      const T bj = y(j < 0 ? 0 : j);
+      ss += j < 0 ? (T)0 : bj * bj;
+    }
+    const T x = tau - hm[g], kind = hk[g];
+    T hv, hd;
+    if (kind == (T)0) {
+      const T s = his[g], z = x * s;
+      hv = (T)-0.5 * z * z;
+      hd = -z * s;
+    } else if (kind == (T)1) {
+      const T e = lp_exp((T)2 * x);
+      hv = (T)-0.5 * e;
+      hd = -e;
+    } else {  // -softplus(2 x) = log sigmoid(-2 x) ; -2 sigmoid(2 x): the exp(-|.|) forms of the logit row function
+      T dp;
+      PhiLogSigmoid::eval((T)-2 * x, (T)0, hv, dp);
+      hd = (T)-2 * dp;
+    }
+    val = hv;
+    grad = ss * lp_exp((T)-2 * tau) + hd;
+  }
+};
+
 // the constant and the prior weight of a checked target (host side, in double)
 struct LinpredConsts {
   double c, pw;
@@ -120,5 +187,6 @@ inline LinpredConsts linpred_consts(const nf_target *t, int d) {
   const double L2PI = 1.8378770664093453;
   if (t->kind == NF_TARGET_DENSEGAUSS) return {-0.5 * d * L2PI + t->s0, 0.0, (long)d};
   if (target_is_glm(t->kind) && std::isinf(t->s1)) return {0.0, 0.0, (long)t->s0};  // flat prior: both prior terms vanish
+  if (target_is_hglm(t->kind)) return {0.0, 0.0, (long)t->s0};  // s1 = G: the prior is evaluated from the buffer, its constants sit in par[1]
   return {-0.5 * d * (L2PI + 2.0 * std::log(t->s1)), 1.0 / (t->s1 * t->s1), (long)t->s0};
 }

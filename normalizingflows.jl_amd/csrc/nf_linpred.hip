@@ -1,15 +1,17 @@
-// nf_linpred.hip -- the linear-predictor targets (NF_TARGET_DENSEGAUSS, NF_TARGET_LOGREG, NF_TARGET_GLM_*; gfx950):
+// nf_linpred.hip -- the linear-predictor targets (NF_TARGET_DENSEGAUSS, NF_TARGET_LOGREG, NF_TARGET_GLM_*, NF_TARGET_HGLM_*; gfx950):
 //     centred      log p(y) = c + sum_i phi(u_i) - pw |y|^2 / 2,   u = A (y - mu),   grad = A' phi'(u) - pw y
 //     generalised  log p(y) = par[1] + c + sum_i wt_i phi(u_i; par[0]) + lin . y - pw |y|^2 / 2,   u = A y + off,
 //                  grad = A' (wt o phi'(u)) + lin - pw y
+//     hierarchical the generalised form with the structured prior of nf_linpred.h (HierRows: y = [beta ; tau], groups of
+//                  coefficients under learned scales exp(tau_g) with hyper-priors) in place of - pw |y|^2 / 2
 // with A [rows x d] row-major: MvNormal(mu, Sigma) through W = inv(chol(Sigma)), Bayesian logistic regression through the
 // label-folded data matrix, and the regression posteriors with exposures, trial counts, subsampling weights and a family
 // parameter through the generalised form.  Two kernel bodies, each templated on the row function phi and on the form
 // (nf_linpred.h); the centred instantiations compile every line of the row data away:
 //   lp_tiled_body  Float32, tiled layout, drop-in for k_target_tiled: both GEMMs on v_mfma_f32_32x32x2_f32
-//                  (k_target_linpred_tiled: centred, k_target_glm_tiled: generalised)
+//                  (k_target_linpred_tiled: centred, k_target_glm_tiled: generalised, k_target_hier_tiled: hierarchical)
 //   lp_flat_body   flat layout, float / double, drop-in for k_target: vector pipe (Float64 flows, nf_target_logp)
-//                  (k_target_linpred, k_target_glm)
+//                  (k_target_linpred, k_target_glm, k_target_hier)
 #include "nf_common.h"
 #include "nf_linpred.h"
 
@@ -31,6 +33,11 @@
 // block's staging loads (before the first of them, so they are in by the time the image is); the offsets ARE the initial
 // accumulator of GEMM 1, the weights multiply phi and phi' in the accumulator registers (0 by select), and rows >= rows
 // read off = 0, wt = 0, which masks them.  lin enters the epilogue beside pw y.
+// Hierarchical form: both GEMMs, the offsets, the weights and the wave-ordered combination are the generalised form's; the
+// prior lives in the epilogue.  The thread that owns feature i of sample s re-reads y as before; for a coefficient it fetches
+// tau of its group from the tile's lines (yb[(p + g) * 32 + s], just read by this workgroup), for a log-scale it walks its
+// group's member list over the same lines.  The prior's share of log p takes the path |y|^2 takes (no atomics: one owner per
+// sum, in a fixed order).
 // Feature chunks: the image holds at most 128 features of the 32 rows (16.5 KB per wave); a wider target (DB = 8) runs
 // GEMM 1 chunk by chunk and stages each chunk a second time for GEMM 2.
 #define LP_BLOCK 256
@@ -69,13 +76,15 @@ __device__ __forceinline__ void lp_stage(float *__restrict__ img, const float *_
 }
 
 // p0: the shift mu[d] (or NULL) of the centred form, the row-data buffer of the generalised one
-template <int DB, class PHI, bool GLM>
+template <int DB, class PHI, int FORM>
 __device__ __forceinline__ void lp_tiled_body(int d, int rows, long N, const float *__restrict__ yt, const float *__restrict__ p0,
                                               const float *__restrict__ A, float c0, float pw, const float *__restrict__ logq,
                                               const float *__restrict__ ladj, float *__restrict__ gt, float gscale,
-                                              float *__restrict__ elbos_out, double *__restrict__ partial, double pscale) {
+                                              float *__restrict__ elbos_out, double *__restrict__ partial, double pscale, int ng) {
   using G = LpGeo<DB>;
+  constexpr bool GLM = FORM != LP_CENTRED, HIER = FORM == LP_HIER;
   const GlmRows<float> rd(p0, d, rows);
+  const HierRows<float> hr(p0, d, rows, HIER ? ng : 0);
   const float par0 = GLM ? rd.par[0] : 0.f;
   extern __shared__ float lp_sm[];
   float *sY = lp_sm;
@@ -209,6 +218,20 @@ __device__ __forceinline__ void lp_tiled_body(int d, int rows, long N, const flo
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
       const int i = q + k * (LP_BLOCK / 32);
+      if (HIER) {  // yy collects the prior's share of log p itself
+        float pv = 0.f, pg = 0.f;
+        if (valid && i < d) {
+          const auto y = [&](int f) { return yb[f * 32 + s]; };  // the tile's lines, just read by this workgroup
+          if (i < hr.p)
+            hr.coef(i, yv[k], y, pv, pg);
+          else
+            hr.scale(i - hr.p, yv[k], y, pv, pg);
+        }
+        yy += pv;
+        ly += lv[k] * yv[k];
+        if (gt && i < d) gt[tile * d * 32 + i * 32 + s] = valid ? gscale * (sY[i * 32 + s] + lv[k] + pg) : 0.f;
+        continue;
+      }
       yy += yv[k] * yv[k];
       if (GLM) {
         ly += lv[k] * yv[k];
@@ -232,7 +255,7 @@ __device__ __forceinline__ void lp_tiled_body(int d, int rows, long N, const flo
       float tl = 0.f;
 #pragma unroll
       for (int k = 0; k < LP_BLOCK / 32; ++k) tl += redl[k][s];
-      e = (rd.par[1] + c0) + l + tl - 0.5f * pw * t;
+      e = HIER ? rd.par[1] + l + tl + t : (rd.par[1] + c0) + l + tl - 0.5f * pw * t;
     }
     if (logq) e -= logq[j];
     if (ladj) e += ladj[j];
@@ -255,7 +278,7 @@ __global__ __launch_bounds__(LP_BLOCK) void k_target_linpred_tiled(int d, int ro
                                                                    const float *__restrict__ ladj, float *__restrict__ gt,
                                                                    float gscale, float *__restrict__ elbos_out,
                                                                    double *__restrict__ partial, double pscale) {
-  lp_tiled_body<DB, PHI, false>(d, rows, N, yt, mu, A, c0, pw, logq, ladj, gt, gscale, elbos_out, partial, pscale);
+  lp_tiled_body<DB, PHI, LP_CENTRED>(d, rows, N, yt, mu, A, c0, pw, logq, ladj, gt, gscale, elbos_out, partial, pscale, 0);
 }
 template <int DB, class PHI>
 __global__ __launch_bounds__(LP_BLOCK) void k_target_glm_tiled(int d, int rows, long N, const float *__restrict__ yt,
@@ -264,7 +287,17 @@ __global__ __launch_bounds__(LP_BLOCK) void k_target_glm_tiled(int d, int rows, 
                                                                const float *__restrict__ ladj, float *__restrict__ gt,
                                                                float gscale, float *__restrict__ elbos_out,
                                                                double *__restrict__ partial, double pscale) {
-  lp_tiled_body<DB, PHI, true>(d, rows, N, yt, rowdata, A, c0, pw, logq, ladj, gt, gscale, elbos_out, partial, pscale);
+  lp_tiled_body<DB, PHI, LP_GLM>(d, rows, N, yt, rowdata, A, c0, pw, logq, ladj, gt, gscale, elbos_out, partial, pscale, 0);
+}
+// hierarchical form: ng = G group log-scales behind the p = d - G coefficients; the prior is read from the buffer
+template <int DB, class PHI>
+__global__ __launch_bounds__(LP_BLOCK) void k_target_hier_tiled(int d, int rows, long N, const float *__restrict__ yt,
+                                                                const float *__restrict__ rowdata, const float *__restrict__ A,
+                                                                int ng, const float *__restrict__ logq,
+                                                                const float *__restrict__ ladj, float *__restrict__ gt,
+                                                                float gscale, float *__restrict__ elbos_out,
+                                                                double *__restrict__ partial, double pscale) {
+  lp_tiled_body<DB, PHI, LP_HIER>(d, rows, N, yt, rowdata, A, 0.f, 0.f, logq, ladj, gt, gscale, elbos_out, partial, pscale, ng);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -278,12 +311,15 @@ __global__ __launch_bounds__(LP_BLOCK) void k_target_glm_tiled(int d, int rows, 
 #define LPF_RB 16
 #define LPF_MAXD 256
 
-template <class T, class PHI, bool GLM>
+template <class T, class PHI, int FORM>
 __device__ __forceinline__ void lp_flat_body(int d, int rows, long N, const T *__restrict__ y, const T *__restrict__ p0,
                                              const T *__restrict__ A, T c0, T pw, const T *__restrict__ logq,
                                              const T *__restrict__ ladj, T *__restrict__ logp_out, T *__restrict__ grad_out,
-                                             T gscale, T *__restrict__ elbos_out, double *__restrict__ partial, double pscale) {
+                                             T gscale, T *__restrict__ elbos_out, double *__restrict__ partial, double pscale,
+                                             int ng) {
+  constexpr bool GLM = FORM != LP_CENTRED, HIER = FORM == LP_HIER;
   const GlmRows<T> rd(p0, d, rows);
+  const HierRows<T> hr(p0, d, rows, HIER ? ng : 0);
   const T par0 = GLM ? rd.par[0] : (T)0;
   extern __shared__ double lpf_sm[];
   T *sY = (T *)lpf_sm;                  // [sample][d + 1] centred
@@ -343,6 +379,19 @@ __device__ __forceinline__ void lp_flat_body(int d, int rows, long N, const T *_
     const int f = k * LPF_LANES + q;
     if (f < d && valid) {
       const T yv = y[j * d + f];
+      if (HIER) {  // yy collects the prior's share of log p itself
+        const auto ys = [&](int i) { return sY[sl * S + i]; };  // the sample's LDS row (uncentred in this form)
+        T pv, pg;
+        if (f < hr.p)
+          hr.coef(f, yv, ys, pv, pg);
+        else
+          hr.scale(f - hr.p, yv, ys, pv, pg);
+        const T lv = rd.lin[f];
+        yy += pv;
+        ly += lv * yv;
+        if (grad_out) grad_out[j * d + f] = gscale * (g[k] + lv + pg);
+        continue;
+      }
       yy += yv * yv;
       if (GLM) {
         const T lv = rd.lin[f];
@@ -358,7 +407,7 @@ __device__ __forceinline__ void lp_flat_body(int d, int rows, long N, const T *_
   double contrib = 0.0;
   if (valid && q == 0) {
     T e = c0 + lp - (T)0.5 * pw * yy;
-    if (GLM) e = (rd.par[1] + c0) + lp + ly - (T)0.5 * pw * yy;
+    if (GLM) e = HIER ? rd.par[1] + lp + ly + yy : (rd.par[1] + c0) + lp + ly - (T)0.5 * pw * yy;
     if (logp_out) logp_out[j] = e;
     if (logq) e -= logq[j];
     if (ladj) e += ladj[j];
@@ -381,7 +430,7 @@ __global__ __launch_bounds__(LP_BLOCK) void k_target_linpred(int d, int rows, lo
                                                              T *__restrict__ logp_out, T *__restrict__ grad_out, T gscale,
                                                              T *__restrict__ elbos_out, double *__restrict__ partial,
                                                              double pscale) {
-  lp_flat_body<T, PHI, false>(d, rows, N, y, mu, A, c0, pw, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
+  lp_flat_body<T, PHI, LP_CENTRED>(d, rows, N, y, mu, A, c0, pw, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale, 0);
 }
 template <class T, class PHI>
 __global__ __launch_bounds__(LP_BLOCK) void k_target_glm(int d, int rows, long N, const T *__restrict__ y,
@@ -390,33 +439,46 @@ __global__ __launch_bounds__(LP_BLOCK) void k_target_glm(int d, int rows, long N
                                                          T *__restrict__ logp_out, T *__restrict__ grad_out, T gscale,
                                                          T *__restrict__ elbos_out, double *__restrict__ partial,
                                                          double pscale) {
-  lp_flat_body<T, PHI, true>(d, rows, N, y, rowdata, A, c0, pw, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
+  lp_flat_body<T, PHI, LP_GLM>(d, rows, N, y, rowdata, A, c0, pw, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale, 0);
+}
+template <class T, class PHI>
+__global__ __launch_bounds__(LP_BLOCK) void k_target_hier(int d, int rows, long N, const T *__restrict__ y,
+                                                          const T *__restrict__ rowdata, const T *__restrict__ A, int ng,
+                                                          const T *__restrict__ logq, const T *__restrict__ ladj,
+                                                          T *__restrict__ logp_out, T *__restrict__ grad_out, T gscale,
+                                                          T *__restrict__ elbos_out, double *__restrict__ partial,
+                                                          double pscale) {
+  lp_flat_body<T, PHI, LP_HIER>(d, rows, N, y, rowdata, A, (T)0, (T)0, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale, ng);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // launchers (called by nf_launch_target / nf_launch_target_tiled after nf_target_check)
 // ---------------------------------------------------------------------------------------------------------------------
 // the kernel of a form (only the one asked for is instantiated)
-template <int DB, class PHI, bool GLM>
+template <int DB, class PHI, int FORM>
 static auto tiled_kernel() {
-  if constexpr (GLM)
+  if constexpr (FORM == LP_HIER)
+    return &k_target_hier_tiled<DB, PHI>;
+  else if constexpr (FORM == LP_GLM)
     return &k_target_glm_tiled<DB, PHI>;
   else
     return &k_target_linpred_tiled<DB, PHI>;
 }
-template <class T, class PHI, bool GLM>
+template <class T, class PHI, int FORM>
 static auto flat_kernel() {
-  if constexpr (GLM)
+  if constexpr (FORM == LP_HIER)
+    return &k_target_hier<T, PHI>;
+  else if constexpr (FORM == LP_GLM)
     return &k_target_glm<T, PHI>;
   else
     return &k_target_linpred<T, PHI>;
 }
 
-template <int DB, class PHI, bool GLM>
+template <int DB, class PHI, int FORM>
 static int launch_tiled(nf_ctx *ctx, const nf_target *t, int d, long N, const float *yt, const float *logq, const float *ladj,
                         float *gt, double gscale, float *elbos_out, double *partial, double pscale) {
   const size_t lds = (size_t)LpGeo<DB>::FLOATS * sizeof(float);
-  const auto kern = tiled_kernel<DB, PHI, GLM>();
+  const auto kern = tiled_kernel<DB, PHI, FORM>();
   static AttrOnce attr_once;  // once per device
   NF_TRY(attr_once.run(ctx->device, [&]() -> int {
     NF_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -424,44 +486,54 @@ static int launch_tiled(nf_ctx *ctx, const nf_target *t, int d, long N, const fl
   }));
   const LinpredConsts k = linpred_consts(t, d);
   ProfScope ps(ctx, "target_linpred");
-  hipLaunchKernelGGL(kern, dim3((unsigned)((N + 31) / 32)), dim3(LP_BLOCK), lds, ctx->stream, d,
-                     (int)k.rows, N, yt, (const float *)t->p0, (const float *)t->p1, (float)k.c, (float)k.pw, logq, ladj, gt,
-                     (float)gscale, elbos_out, partial, pscale);
+  if constexpr (FORM == LP_HIER)
+    hipLaunchKernelGGL(kern, dim3((unsigned)((N + 31) / 32)), dim3(LP_BLOCK), lds, ctx->stream, d,
+                       (int)k.rows, N, yt, (const float *)t->p0, (const float *)t->p1, (int)t->s1, logq, ladj, gt,
+                       (float)gscale, elbos_out, partial, pscale);
+  else
+    hipLaunchKernelGGL(kern, dim3((unsigned)((N + 31) / 32)), dim3(LP_BLOCK), lds, ctx->stream, d,
+                       (int)k.rows, N, yt, (const float *)t->p0, (const float *)t->p1, (float)k.c, (float)k.pw, logq, ladj, gt,
+                       (float)gscale, elbos_out, partial, pscale);
   return (int)hipGetLastError();
 }
 
-template <class PHI, bool GLM>
+template <class PHI, int FORM>
 static int launch_tiled_phi(nf_ctx *ctx, const nf_target *t, int d, long N, const float *yt, const float *logq,
                             const float *ladj, float *gt, double gscale, float *elbos_out, double *partial, double pscale) {
-  if (d <= 32) return launch_tiled<1, PHI, GLM>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
-  if (d <= 64) return launch_tiled<2, PHI, GLM>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
-  if (d <= 128) return launch_tiled<4, PHI, GLM>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
-  return launch_tiled<8, PHI, GLM>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
+  if (d <= 32) return launch_tiled<1, PHI, FORM>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
+  if (d <= 64) return launch_tiled<2, PHI, FORM>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
+  if (d <= 128) return launch_tiled<4, PHI, FORM>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
+  return launch_tiled<8, PHI, FORM>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
 }
 
 int nf_launch_target_linpred_tiled(nf_ctx *ctx, const nf_target *t, int d, long N, const float *yt, const float *logq,
                                    const float *ladj, float *gt, double gscale, float *elbos_out, double *partial,
                                    double pscale) {
   if (d > LPF_MAXD) return NF_ERR_UNSUPPORTED;
-#define LP_TILED(PHI, GLM) launch_tiled_phi<PHI, GLM>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale)
+#define LP_TILED(PHI, FORM) launch_tiled_phi<PHI, FORM>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale)
   switch (t->kind) {
-    case NF_TARGET_DENSEGAUSS: return LP_TILED(PhiHalfSquare, false);
-    case NF_TARGET_LOGREG: return LP_TILED(PhiLogSigmoid, false);
-    case NF_TARGET_GLM_LOGIT: return LP_TILED(PhiLogSigmoid, true);
-    case NF_TARGET_GLM_PROBIT: return LP_TILED(PhiLogNormCdf, true);
-    case NF_TARGET_GLM_POISSON: return LP_TILED(PhiNegExp, true);
-    case NF_TARGET_GLM_STUDENT: return LP_TILED(PhiStudent, true);
-    case NF_TARGET_GLM_NORMAL: return LP_TILED(PhiHalfSquare, true);
+    case NF_TARGET_DENSEGAUSS: return LP_TILED(PhiHalfSquare, LP_CENTRED);
+    case NF_TARGET_LOGREG: return LP_TILED(PhiLogSigmoid, LP_CENTRED);
+    case NF_TARGET_GLM_LOGIT: return LP_TILED(PhiLogSigmoid, LP_GLM);
+    case NF_TARGET_GLM_PROBIT: return LP_TILED(PhiLogNormCdf, LP_GLM);
+    case NF_TARGET_GLM_POISSON: return LP_TILED(PhiNegExp, LP_GLM);
+    case NF_TARGET_GLM_STUDENT: return LP_TILED(PhiStudent, LP_GLM);
+    case NF_TARGET_GLM_NORMAL: return LP_TILED(PhiHalfSquare, LP_GLM);
+    case NF_TARGET_HGLM_LOGIT: return LP_TILED(PhiLogSigmoid, LP_HIER);
+    case NF_TARGET_HGLM_PROBIT: return LP_TILED(PhiLogNormCdf, LP_HIER);
+    case NF_TARGET_HGLM_POISSON: return LP_TILED(PhiNegExp, LP_HIER);
+    case NF_TARGET_HGLM_STUDENT: return LP_TILED(PhiStudent, LP_HIER);
+    case NF_TARGET_HGLM_NORMAL: return LP_TILED(PhiHalfSquare, LP_HIER);
     default: return NF_ERR_ARG;
   }
 #undef LP_TILED
 }
 
-template <class T, class PHI, bool GLM>
+template <class T, class PHI, int FORM>
 static int launch_flat(nf_ctx *ctx, const nf_target *t, int d, long N, const void *y, const void *logq, const void *ladj,
                        void *logp_out, void *grad_out, double gscale, void *elbos_out, double *partial, double pscale) {
   const size_t lds = (size_t)((LPF_SPB + LPF_RB) * (d + 1) + LPF_SPB * (LPF_RB + 1)) * sizeof(T);
-  const auto kern = flat_kernel<T, PHI, GLM>();
+  const auto kern = flat_kernel<T, PHI, FORM>();
   static AttrOnce attr_once;
   NF_TRY(attr_once.run(ctx->device, [&]() -> int {
     const size_t most = (size_t)((LPF_SPB + LPF_RB) * (LPF_MAXD + 1) + LPF_SPB * (LPF_RB + 1)) * sizeof(T);
@@ -471,9 +543,14 @@ static int launch_flat(nf_ctx *ctx, const nf_target *t, int d, long N, const voi
   const LinpredConsts k = linpred_consts(t, d);
   ProfScope ps(ctx, "target_linpred");
   const long nb = (N + LPF_SPB - 1) / LPF_SPB;
-  hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(LP_BLOCK), lds, ctx->stream, d, (int)k.rows, N,
-                     (const T *)y, (const T *)t->p0, (const T *)t->p1, (T)k.c, (T)k.pw, (const T *)logq, (const T *)ladj,
-                     (T *)logp_out, (T *)grad_out, (T)gscale, (T *)elbos_out, partial, pscale);
+  if constexpr (FORM == LP_HIER)
+    hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(LP_BLOCK), lds, ctx->stream, d, (int)k.rows, N,
+                       (const T *)y, (const T *)t->p0, (const T *)t->p1, (int)t->s1, (const T *)logq, (const T *)ladj,
+                       (T *)logp_out, (T *)grad_out, (T)gscale, (T *)elbos_out, partial, pscale);
+  else
+    hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(LP_BLOCK), lds, ctx->stream, d, (int)k.rows, N,
+                       (const T *)y, (const T *)t->p0, (const T *)t->p1, (T)k.c, (T)k.pw, (const T *)logq, (const T *)ladj,
+                       (T *)logp_out, (T *)grad_out, (T)gscale, (T *)elbos_out, partial, pscale);
   return (int)hipGetLastError();
 }
 
@@ -481,18 +558,23 @@ int nf_launch_target_linpred(nf_ctx *ctx, int dtype, const nf_target *t, int d, 
                              const void *ladj, void *logp_out, void *grad_out, double gscale, void *elbos_out,
                              double *partial, double pscale) {
   if (d > LPF_MAXD) return NF_ERR_UNSUPPORTED;
-#define LP_FLAT(PHI, GLM)                                                                                                        \
+#define LP_FLAT(PHI, FORM)                                                                                                       \
   (dtype == NF_DTYPE_F32                                                                                                       \
-       ? launch_flat<float, PHI, GLM>(ctx, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale)     \
-       : launch_flat<double, PHI, GLM>(ctx, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale))
+       ? launch_flat<float, PHI, FORM>(ctx, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale)     \
+       : launch_flat<double, PHI, FORM>(ctx, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale))
   switch (t->kind) {
-    case NF_TARGET_DENSEGAUSS: return LP_FLAT(PhiHalfSquare, false);
-    case NF_TARGET_LOGREG: return LP_FLAT(PhiLogSigmoid, false);
-    case NF_TARGET_GLM_LOGIT: return LP_FLAT(PhiLogSigmoid, true);
-    case NF_TARGET_GLM_PROBIT: return LP_FLAT(PhiLogNormCdf, true);
-    case NF_TARGET_GLM_POISSON: return LP_FLAT(PhiNegExp, true);
-    case NF_TARGET_GLM_STUDENT: return LP_FLAT(PhiStudent, true);
-    case NF_TARGET_GLM_NORMAL: return LP_FLAT(PhiHalfSquare, true);
+    case NF_TARGET_DENSEGAUSS: return LP_FLAT(PhiHalfSquare, LP_CENTRED);
+    case NF_TARGET_LOGREG: return LP_FLAT(PhiLogSigmoid, LP_CENTRED);
+    case NF_TARGET_GLM_LOGIT: return LP_FLAT(PhiLogSigmoid, LP_GLM);
+    case NF_TARGET_GLM_PROBIT: return LP_FLAT(PhiLogNormCdf, LP_GLM);
+    case NF_TARGET_GLM_POISSON: return LP_FLAT(PhiNegExp, LP_GLM);
+    case NF_TARGET_GLM_STUDENT: return LP_FLAT(PhiStudent, LP_GLM);
+    case NF_TARGET_GLM_NORMAL: return LP_FLAT(PhiHalfSquare, LP_GLM);
+    case NF_TARGET_HGLM_LOGIT: return LP_FLAT(PhiLogSigmoid, LP_HIER);
+    case NF_TARGET_HGLM_PROBIT: return LP_FLAT(PhiLogNormCdf, LP_HIER);
+    case NF_TARGET_HGLM_POISSON: return LP_FLAT(PhiNegExp, LP_HIER);
+    case NF_TARGET_HGLM_STUDENT: return LP_FLAT(PhiStudent, LP_HIER);
+    case NF_TARGET_HGLM_NORMAL: return LP_FLAT(PhiHalfSquare, LP_HIER);
     default: return NF_ERR_ARG;
   }
 #undef LP_FLAT

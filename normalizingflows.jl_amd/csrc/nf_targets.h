@@ -127,8 +127,11 @@ __host__ __device__ inline bool target_needs_d2(int kind) { return kind == NF_TA
 // The generalised kinds (NF_TARGET_GLM_LOGIT .. NF_TARGET_GLM_NORMAL: row offsets, row weights, a linear term and a family
 // parameter) are linear-predictor kinds served by the same two kernels.
 __host__ __device__ inline bool target_is_glm(int kind) { return kind >= NF_TARGET_GLM_LOGIT && kind <= NF_TARGET_GLM_NORMAL; }
+// The hierarchical kinds (NF_TARGET_HGLM_LOGIT .. NF_TARGET_HGLM_NORMAL = the GLM kind + 7: the generalised form under a
+// structured prior with learned group scales) are linear-predictor kinds too, served by a third form of the same two bodies.
+__host__ __device__ inline bool target_is_hglm(int kind) { return kind >= NF_TARGET_HGLM_LOGIT && kind <= NF_TARGET_HGLM_NORMAL; }
 __host__ __device__ inline bool target_is_linpred(int kind) {
-  return kind == NF_TARGET_DENSEGAUSS || kind == NF_TARGET_LOGREG || target_is_glm(kind);
+  return kind == NF_TARGET_DENSEGAUSS || kind == NF_TARGET_LOGREG || target_is_glm(kind) || target_is_hglm(kind);
 }
 // The Gaussian mixture (NF_TARGET_GAUSSMIX, nf_mixture.hip) is routed like them: a kernel of its own behind
 // nf_launch_target / nf_launch_target_tiled, refused wherever target_term would have to evaluate it.

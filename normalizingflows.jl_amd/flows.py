@@ -867,6 +867,137 @@ class LinearRegressionTarget(GLMTarget):
         super().__init__("normal", to(X64 / sn), to(-yv / sn), to(w), None, const, 0.0, prior_sigma, _name=nm)
 
 
+_HGLM_KINDS = {"logit": _lib.NF_TARGET_HGLM_LOGIT, "probit": _lib.NF_TARGET_HGLM_PROBIT, "poisson": _lib.NF_TARGET_HGLM_POISSON,
+               "student": _lib.NF_TARGET_HGLM_STUDENT, "normal": _lib.NF_TARGET_HGLM_NORMAL}
+_HYPER_KINDS = {"lognormal": 0, "halfnormal": 1, "halfcauchy": 2}
+
+
+def _per_item(name, what, v, n, positive=False, allow_inf=False):
+    """a scalar or one value per item (a sequence or tensor of length n) as float64 [n] on the host"""
+    if isinstance(v, torch.Tensor) and v.dim() == 1 or isinstance(v, (list, tuple)):
+        v64 = torch.as_tensor(v).detach().to("cpu", torch.float64)
+        if v64.dim() != 1 or v64.numel() != n:
+            raise NFHipError(f"{name}: {what} must be a scalar or hold {n} values")
+    elif isinstance(v, torch.Tensor) and v.dim() > 1:
+        raise NFHipError(f"{name}: {what} must be a scalar or hold {n} values")
+    else:
+        v64 = torch.full((n,), float(v), dtype=torch.float64)
+    fin = torch.isfinite(v64) | ((v64 == math.inf) if allow_inf else torch.zeros_like(v64, dtype=torch.bool))
+    if not bool(fin.all()) or (positive and bool((v64 <= 0).any())):
+        raise NFHipError(f"{name}: {what} must be finite" + (" and > 0" if positive else "") + (" (or +inf)" if allow_inf else ""))
+    return v64
+
+
+class HierarchicalGLMTarget(_LinpredTarget):
+    """A GLM posterior under a hierarchical prior (NF_TARGET_HGLM_*), over z = [beta (p coefficients) ; tau (G group log-scales)],
+    d = p + G, in the centred parameterisation:
+        logp(z) = const + sum_i weights_i phi(u_i; param) + lin . beta + sum_j log N(beta_j; 0, sigma_j^2) + sum_g log p(tau_g),
+        u = A beta + offset,   sigma_j = fixed_sigma_j if groups[j] == -1 else exp(tau_{groups[j]}).
+    family and A [rows, p], offset, weights, lin (p,), const, param are GLMTarget's.  groups: an integer tensor (p,) with values in
+    {-1, 0 .. n_groups - 1}; fixed_sigma: a scalar or (p,), read where groups == -1, math.inf = a flat prior on that coefficient.
+    hyper: "lognormal" (tau_g ~ N(hyper_loc, hyper_scale^2)), "halfnormal" or "halfcauchy" (exp(tau_g) ~ half-normal / half-Cauchy
+    of scale hyper_scale, as a density over tau_g), one name or one per group; hyper_loc, hyper_scale: a scalar or one per group.
+    Everything linear in z or constant is folded here in float64 (the -n_g tau_g of the Gaussian normalisers and the +tau_g
+    Jacobian of the half-families into lin, every normaliser into the constant).  The device reads `A` (padded with zero
+    tau-columns to [rows, d]) and ONE buffer `p0` (include/nfhip.h); both are kept alive here."""
+
+    def __init__(self, family, A, groups, n_groups, offset=None, weights=None, lin=None, const=0.0, param=0.0, fixed_sigma=1.0,
+                 hyper="halfcauchy", hyper_loc=0.0, hyper_scale=1.0, _name="HierarchicalGLMTarget"):
+        nm = _name
+        if family not in _HGLM_KINDS:
+            raise NFHipError(f"{nm}: family must be one of {sorted(_HGLM_KINDS)}")
+        A64 = _glm_matrix(nm, A)
+        rows, p = A64.shape
+        if isinstance(n_groups, bool) or not hasattr(n_groups, "__index__") or int(n_groups) < 0:
+            raise NFHipError(f"{nm}: n_groups must be an integer >= 0")
+        G = int(n_groups)
+        d = p + G
+        if d > 256:
+            raise NFHipError(f"{nm}: p + n_groups = {d} exceeds the kernels' d = 256")
+        if not isinstance(groups, torch.Tensor) or groups.dim() != 1 or groups.numel() != p or groups.dtype.is_floating_point or \
+                groups.dtype.is_complex or groups.dtype == torch.bool:
+            raise NFHipError(f"{nm}: groups must be an integer tensor of length {p}")
+        grp = groups.detach().to("cpu", torch.int64)
+        if bool((grp < -1).any()) or bool((grp >= G).any()):
+            raise NFHipError(f"{nm}: groups must hold -1 (a fixed prior scale) or a group index in 0..{G - 1}")
+        off = _glm_vector(nm, "offset", offset, A, rows, 0.0)
+        wt = _glm_vector(nm, "weights", weights, A, rows, 1.0, nonneg=True)
+        ln = _glm_vector(nm, "lin", lin, A, p, 0.0)
+        const = _glm_scalar(nm, "const", const, positive=False)
+        param = _glm_scalar(nm, "param", param, positive=family == "student")
+        sig = _per_item(nm, "fixed_sigma", fixed_sigma, p, positive=True, allow_inf=True)
+        names = [hyper] * G if isinstance(hyper, str) else list(hyper)
+        if len(names) != G or any(not isinstance(h, str) or h not in _HYPER_KINDS for h in names):
+            raise NFHipError(f"{nm}: hyper must be one of {sorted(_HYPER_KINDS)}, or one of them per group")
+        loc = _per_item(nm, "hyper_loc", hyper_loc, G)
+        scl = _per_item(nm, "hyper_scale", hyper_scale, G, positive=True)
+
+        grouped = grp >= 0
+        isd = torch.where(grouped, torch.zeros(p, dtype=torch.float64), 1.0 / sig)        # 1 / inf = 0: flat
+        n_g = torch.bincount(grp[grouped], minlength=G).to(torch.float64) if G else torch.zeros(0, dtype=torch.float64)
+        L2PI = math.log(2.0 * math.pi)
+        fixed = (~grouped) & torch.isfinite(sig)
+        c = const - float(torch.log(sig[fixed]).sum()) - 0.5 * L2PI * float(fixed.sum()) - 0.5 * L2PI * float(grouped.sum())
+        hk = torch.tensor([float(_HYPER_KINDS[h]) for h in names], dtype=torch.float64)
+        hm, his, lin_tau = torch.zeros(G, dtype=torch.float64), torch.zeros(G, dtype=torch.float64), -n_g
+        for g, h in enumerate(names):
+            if h == "lognormal":
+                hm[g], his[g] = loc[g], 1.0 / scl[g]
+                c += -math.log(float(scl[g])) - 0.5 * L2PI
+            else:  # a density over sigma = exp(tau): + tau_g from the change of variables
+                hm[g] = math.log(float(scl[g]))
+                lin_tau[g] += 1.0
+                c += (0.5 if h == "halfnormal" else 1.0) * math.log(2.0 / math.pi) - float(hm[g])
+        order = torch.argsort(grp, stable=True)                                            # members in increasing feature index
+        gidx = torch.cat([order[grp[order] >= 0], torch.zeros(int((~grouped).sum()), dtype=torch.int64)]).to(torch.float64)
+        gptr = torch.cat([torch.zeros(1, dtype=torch.float64), torch.cumsum(n_g, 0)])
+        self.family, self.d, self.p, self.G, self.rows, self.param, self.const = family, d, p, G, rows, param, c
+        self.groups, self.hyper = grp, names
+        self.A = torch.cat([A.detach(), torch.zeros(rows, G, dtype=A.dtype, device=A.device)], 1).contiguous()
+        self.p0 = torch.cat([ln, lin_tau, off, wt, torch.tensor([param, c], dtype=torch.float64), grp.to(torch.float64), isd, hm, his, hk,
+                             gptr, gidx]).to(A.dtype).to(A.device).contiguous()
+        self.c = Target(_HGLM_KINDS[family], self.p0.data_ptr(), self.A.data_ptr(), float(rows), float(G))
+
+    def coefficients(self, y):
+        """beta, the first p leading elements of a parameter vector (d,) or a batch (d, N)"""
+        return y[:self.p]
+
+    def scales(self, y):
+        """the group scales exp(tau) of a parameter vector (d,) or a batch (d, N)"""
+        return torch.exp(y[self.p:])
+
+
+class VaryingInterceptTarget(HierarchicalGLMTarget):
+    """A GLM with one varying (random) intercept per level: u_i = x_i . b + a_{level_of_row[i]} + offset_i, with
+    a_l ~ N(0, exp(tau)^2) sharing ONE learned scale and the columns of X under fixed_sigma.  Builds A = [X | one-hot(level)],
+    z = [b (X's columns) ; a (n_levels) ; tau]."""
+
+    def __init__(self, family, X, level_of_row, n_levels, offset=None, weights=None, lin=None, const=0.0, param=0.0, fixed_sigma=1.0,
+                 hyper="halfcauchy", hyper_loc=0.0, hyper_scale=1.0):
+        nm = "VaryingInterceptTarget"
+        _glm_matrix(nm, X)
+        rows, px = X.shape
+        if isinstance(n_levels, bool) or not hasattr(n_levels, "__index__") or int(n_levels) < 1:
+            raise NFHipError(f"{nm}: n_levels must be an integer >= 1")
+        L = int(n_levels)
+        if not isinstance(level_of_row, torch.Tensor) or level_of_row.dim() != 1 or level_of_row.numel() != rows or \
+                level_of_row.dtype.is_floating_point or level_of_row.dtype.is_complex or level_of_row.dtype == torch.bool:
+            raise NFHipError(f"{nm}: level_of_row must be an integer tensor with one level per row of X")
+        lev = level_of_row.detach().to("cpu", torch.int64)
+        if bool((lev < 0).any()) or bool((lev >= L).any()):
+            raise NFHipError(f"{nm}: levels must be in 0..{L - 1}")
+        onehot = torch.zeros(rows, L, dtype=X.dtype)
+        onehot[torch.arange(rows), lev] = 1.0
+        A = torch.cat([X.detach(), onehot.to(X.device)], 1)
+        groups = torch.cat([torch.full((px,), -1, dtype=torch.int64), torch.zeros(L, dtype=torch.int64)])
+        if lin is not None and isinstance(lin, torch.Tensor) and lin.dim() == 1 and lin.numel() == px:
+            lin = torch.cat([lin, torch.zeros(L, dtype=lin.dtype, device=lin.device)])
+        sig = _per_item(nm, "fixed_sigma", fixed_sigma, px, positive=True, allow_inf=True)
+        self.n_levels, self.levels = L, lev
+        super().__init__(family, A, groups, 1, offset, weights, lin, const, param, torch.cat([sig, torch.ones(L, dtype=torch.float64)]),
+                         hyper, hyper_loc, hyper_scale, _name=nm)
+
+
 class SoftmaxRegressionTarget(_LinpredTarget):
     """Posterior of Bayesian softmax (multinomial-logit) regression over the weight matrix W [p, C]: data rows X [rows, p],
     labels c_i in {0 .. C-1}, row weights w_i >= 0 (0 drops the row exactly), prior N(0, prior_sigma^2 I):

@@ -95,6 +95,26 @@ extern "C" {
                                application, rand, elbo / elbo_batch, the training step, loglikelihood, forward-KL
                                training and nf_flow_bwd are all built (reverse passes chain the segments' own). */
 
+#define NF_KIND_PRECOND 8 /* transformed(q0, Shift(mu) o Scale(LowerTriangular(L)) o couplings): a coupling flow under a full-rank
+                             affine layer, y = mu + L T(x) -- one create_flow((Shift, Scale, couplings...), q0) in the reference
+                             (src/flows/utils.jl:23-26).  nlayers = 1, nsegments = 1 and `segments` points to ONE inner
+                             descriptor of kind NF_KIND_REALNVP or NF_KIND_NSF with the same d and dtype and no base
+                             (NF_ERR_ARG otherwise); a general base belongs to the outer descriptor.  Limits: d <= 256 and
+                             whatever the inner flow's own limits are (NF_ERR_UNSUPPORTED beyond).  theta = [mu(d) ; L, d x d
+                             column-major ; theta_inner], outermost first; the strict upper triangle of L keeps
+                             NF_KIND_FULLRANK's contract (never read, gradient exactly 0.0).  nf_param_count = d + d^2 +
+                             P_inner; nf_layer_count = 2 + the inner flow's (flat order: Shift, Scale, the couplings).
+                             Served: nf_flow_fwd / inv / rand, nf_layer_apply, nf_loglikelihood (value only), the tape pair
+                             and nf_flow_bwd, nf_elbo_batch(_rng), nf_elbo_value_and_grad, nf_elbo_step (the split sequence,
+                             with or without a communicator), general bases -- with every target the inner flow is served
+                             with.  Float32 with the inner flow on the matrix-pipe kernels: nf_elbo_value_and_grad keeps every
+                             buffer in the tiled layout from the draw to the gradient, and the full-rank layer's reverse pass
+                             is one launch from d = 33 on, the two launches of NF_KIND_FULLRANK at d <= 32 (as measured; the
+                             same bits; NF_PRECOND_BWD_SPLIT in the environment, read once per process, overrides: 1 = the
+                             two launches, 0 = the one launch, at every d).  NF_ERR_UNSUPPORTED:
+                             nf_loglikelihood_value_and_grad, nf_loglikelihood_step(_enqueue), nf_elbo_step_enqueue;
+                             NF_ERR_ARG as a segment of NF_KIND_COMPOSITE. */
+
 #define NF_DTYPE_F32 0
 #define NF_DTYPE_F64 1
 
@@ -256,8 +276,8 @@ typedef struct nf_flow_desc {
   const struct nf_target *score; /* NF_KIND_HAMILTONIAN: the target behind LeapFrog's
                                     score function (host pointer); NULL otherwise     */
   const struct nf_base *base;    /* q0 (host pointer); NULL = MvNormal(zeros(d), I)  */
-  int32_t nsegments;             /* NF_KIND_COMPOSITE: number of segments, else 0    */
-  const struct nf_flow_desc *segments; /* NF_KIND_COMPOSITE: host array [nsegments]  */
+  int32_t nsegments;             /* NF_KIND_COMPOSITE: number of segments; NF_KIND_PRECOND: 1; else 0 */
+  const struct nf_flow_desc *segments; /* host array [nsegments] (NF_KIND_PRECOND: the inner flow) */
 } nf_flow_desc;
 
 /* Built-in target log-densities (the `logp` closure of src/objectives/elbo.jl:68

@@ -163,6 +163,9 @@ int nf_fr_bwd_grid(nf_ctx *, long N);
 int nf_fr_fwd_tiled(nf_ctx *, const nf_flow_desc *, const float *theta, const float *xt, long N, float *yt, float *ladj);
 int nf_fr_grad(nf_ctx *, const nf_flow_desc *, const float *theta, const float *x, int x_tiled, const float *ybar, int y_tiled,
                const float *lbar, float lbar_const, long N, float *slabs, float *gtheta_out);
+int nf_fr_bwd_x_tiled(nf_ctx *, const nf_flow_desc *, const float *theta, const float *xt, const float *ybar, const float *lbar,
+                      float lbar_const, long N, float *slabs, float *gtheta_out, float *xbar);
+int nf_fr_pull_tiled(nf_ctx *, const nf_flow_desc *, const float *theta, const float *ybar, long N, float *xbar);
 
 // ---- helpers -----------------------------------------------------------------------------
 // Every entry point's intermediates are ONE layout: a struct whose constructor takes its buffers from a Carver.  It runs over a
@@ -186,12 +189,36 @@ static inline bool is_composite(const nf_flow_desc *d) { return d->kind == NF_KI
 static inline bool is_fr(const nf_flow_desc *d) { return d->kind == NF_KIND_FULLRANK; }
 // the full-rank family in Float32: tiled batches, matrix-pipe kernels and the tiled target launchers
 static inline bool is_fr_tiled(const nf_flow_desc *d) { return is_fr(d) && d->dtype == NF_DTYPE_F32; }
+// A preconditioned coupling flow (NF_KIND_PRECOND) is, for every entry point but the tiled Float32 training step, the
+// two-segment chain [full-rank layer ; inner coupling flow] run by the composition's machinery in the standard layout.  The
+// view is internal: the public check_composite keeps refusing a full-rank segment.
+static inline bool is_precond(const nf_flow_desc *d) { return d->kind == NF_KIND_PRECOND; }
+struct PrecondView {
+  nf_flow_desc seg[2], comp;
+};
+static const nf_flow_desc *precond_view(const nf_flow_desc *d, PrecondView *v) {
+  v->seg[0] = nf_flow_desc{};
+  v->seg[0].kind = NF_KIND_FULLRANK;
+  v->seg[0].d = d->d;
+  v->seg[0].dtype = d->dtype;
+  v->seg[0].nlayers = 1;
+  v->seg[1] = d->segments[0];
+  v->comp = *d;
+  v->comp.kind = NF_KIND_COMPOSITE;
+  v->comp.nsegments = 2;
+  v->comp.segments = v->seg;
+  return &v->comp;
+}
+// `desc` from here on: the internal chain of a preconditioned flow, everything else as it came
+#define NF_PRECOND_VIEW(desc) \
+  PrecondView precond_view_;  \
+  if (is_precond(desc)) desc = precond_view(desc, &precond_view_)
 static int check_desc(const nf_flow_desc *d);
 static int check_composite(const nf_flow_desc *d) {
   if (d->nsegments < 1 || d->nsegments > 64 || !d->segments) return NF_ERR_ARG;
   for (int s = 0; s < d->nsegments; ++s) {
     const nf_flow_desc *g = &d->segments[s];
-    if (g->kind == NF_KIND_COMPOSITE || g->kind == NF_KIND_HAMILTONIAN) return NF_ERR_ARG;
+    if (g->kind == NF_KIND_COMPOSITE || g->kind == NF_KIND_HAMILTONIAN || g->kind == NF_KIND_PRECOND) return NF_ERR_ARG;
     if (g->kind == NF_KIND_FULLRANK) return NF_ERR_UNSUPPORTED;  // not a segment yet
     if (g->d != d->d || g->dtype != d->dtype || g->base) return NF_ERR_ARG;  // q0 belongs to the composition
     NF_TRY(check_desc(g));
@@ -220,6 +247,14 @@ static int check_desc(const nf_flow_desc *d) {
     case NF_KIND_FULLRANK:
       if (d->nlayers != 1) return NF_ERR_ARG;
       return nf_fr_supported(d) ? NF_OK : NF_ERR_UNSUPPORTED;
+    case NF_KIND_PRECOND: {
+      if (d->nlayers != 1 || d->nsegments != 1 || !d->segments) return NF_ERR_ARG;
+      const nf_flow_desc *g = &d->segments[0];
+      if (g->kind != NF_KIND_REALNVP && g->kind != NF_KIND_NSF) return NF_ERR_ARG;
+      if (g->d != d->d || g->dtype != d->dtype || g->base) return NF_ERR_ARG;
+      NF_TRY(check_desc(g));
+      return nf_fr_supported(d) ? NF_OK : NF_ERR_UNSUPPORTED;
+    }
     case NF_KIND_HAMILTONIAN:
       if (d->d < 2 || (d->d & 1) || d->K < 1 || !d->score) return NF_ERR_ARG;
       return nf_hf_supported(d) ? NF_OK : NF_ERR_UNSUPPORTED;
@@ -278,6 +313,12 @@ extern "C" int64_t nf_param_count(const nf_flow_desc *d) {
     case NF_KIND_RADIAL: return (int64_t)d->nlayers * (d->d + 2);
     case NF_KIND_MEANFIELD: return 2 * (int64_t)d->d;
     case NF_KIND_FULLRANK: return (int64_t)d->d + (int64_t)d->d * d->d;  // shift, then the scale's parent matrix
+    case NF_KIND_PRECOND: {  // [mu ; L ; theta_inner]
+      if (d->nsegments != 1 || !d->segments || d->segments[0].kind == NF_KIND_PRECOND || d->segments[0].kind == NF_KIND_COMPOSITE)
+        return NF_ERR_ARG;
+      const int64_t p = nf_param_count(&d->segments[0]);
+      return p < 0 ? p : (int64_t)d->d + (int64_t)d->d * d->d + p;
+    }
     case NF_KIND_HAMILTONIAN: return 2 * (int64_t)d->d + 3 * (int64_t)(d->d / 2) * d->nlayers;
     case NF_KIND_REALNVP:
     case NF_KIND_NSF: {
@@ -306,6 +347,12 @@ extern "C" int32_t nf_layer_count(const nf_flow_desc *d) {
     case NF_KIND_RADIAL: return d->nlayers;
     case NF_KIND_MEANFIELD:
     case NF_KIND_FULLRANK: return 2;
+    case NF_KIND_PRECOND: {  // Shift, Scale, the couplings
+      if (d->nsegments != 1 || !d->segments || d->segments[0].kind == NF_KIND_PRECOND || d->segments[0].kind == NF_KIND_COMPOSITE)
+        return NF_ERR_ARG;
+      const int32_t c = nf_layer_count(&d->segments[0]);
+      return c < 0 ? c : 2 + c;
+    }
     case NF_KIND_HAMILTONIAN: return d->nlayers + 1;  // blocks, then the reference's affine map
     case NF_KIND_REALNVP:
     case NF_KIND_NSF: return 2 * d->nlayers;
@@ -677,6 +724,7 @@ static inline bool elbo_fusable(const nf_flow_desc *desc, const nf_target *targe
 // path) on draws of their own.
 static inline bool target_refused(const nf_flow_desc *desc, const nf_target *target) {
   if (!target || !target_has_own_kernel(target->kind)) return false;
+  if (is_precond(desc)) return target_refused(&desc->segments[0], target);  // exactly as for the inner coupling flow
   if (target->kind == NF_TARGET_GAUSSMIX && desc->d > NF_MIXTURE_TILED_MAXD && (is_coupling(desc) || is_fr_tiled(desc))) return true;
   return desc->kind == NF_KIND_PLANAR || desc->kind == NF_KIND_RADIAL || desc->kind == NF_KIND_MEANFIELD ||
          desc->kind == NF_KIND_HAMILTONIAN;
@@ -773,6 +821,7 @@ static int composite_apply(nf_ctx *ctx, const nf_flow_desc *desc, bool inverse, 
 static int apply_std(nf_ctx *ctx, const nf_flow_desc *desc, bool inverse, int layer, const void *theta,
                      const void *x_in, long N, void *y_out, void *ladj) {
   if (N == 0) return NF_OK;
+  NF_PRECOND_VIEW(desc);
   if (is_composite(desc)) return composite_apply(ctx, desc, inverse, layer, theta, x_in, N, y_out, ladj);
   if (is_coupling(desc)) {
     NF_TRY(nf_ws_reserve(ctx, carve_bytes(tiled_elems(desc, N) * 4)));
@@ -828,6 +877,7 @@ extern "C" int nf_flow_rand(nf_ctx *ctx, const nf_flow_desc *desc, const void *t
     NF_TRY(base_draw(ctx, desc, N, seed, sample_offset, stream_id, y_out, nullptr));
     return apply_std(ctx, &inner, false, -1, theta, y_out, N, y_out, bb.tmp);
   }
+  NF_PRECOND_VIEW(desc);
   if (is_composite(desc)) {  // draws into y_out, then the chain in place
     CompBufs cb;
     GuardReset gr{ctx, ctx->ws_guard};
@@ -939,6 +989,7 @@ static size_t tape_seg_bytes(nf_ctx *ctx, const nf_flow_desc *g, long N) {
   return 0;
 }
 static size_t tape_bytes_of(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
+  NF_PRECOND_VIEW(desc);
   if (!is_composite(desc)) return tape_seg_bytes(ctx, desc, N);
   size_t tot = 0;
   for (int s = 0; s < desc->nsegments; ++s) tot += tape_seg_bytes(ctx, &desc->segments[s], N);
@@ -992,6 +1043,7 @@ struct TapeFwdCompBufs {
   }
 };
 static size_t tape_need(nf_ctx *ctx, const nf_flow_desc *desc, long N, bool bwd) {
+  NF_PRECOND_VIEW(desc);
   if (!is_composite(desc)) return bwd ? layout_bytes<TapeBwdBufs>(ctx, desc, N) : tape_fwd_need_seg(ctx, desc, N);
   if (!bwd) return layout_bytes<TapeFwdCompBufs>(ctx, desc, N);
   size_t m = 0;
@@ -1068,6 +1120,7 @@ static int tape_bwd_seg(nf_ctx *ctx, const nf_flow_desc *g, const void *theta, c
 // whole flow (a composition chains its segments through y_out in place; the LAST segment is applied first)
 static int tape_fwd(nf_ctx *ctx, const nf_flow_desc *desc, const void *theta, const void *x_in, long N, void *y_out,
                     void *ladj, void *tape) {
+  NF_PRECOND_VIEW(desc);
   if (!is_composite(desc)) return tape_fwd_seg(ctx, desc, theta, x_in, N, y_out, ladj, tape);
   const size_t es = esize(desc->dtype);
   const int ns = desc->nsegments;
@@ -1092,6 +1145,7 @@ static int tape_fwd(nf_ctx *ctx, const nf_flow_desc *desc, const void *theta, co
 
 static int tape_bwd(nf_ctx *ctx, const nf_flow_desc *desc, const void *theta, const void *tape, const void *ybar,
                     const void *lbar, double lbar_const, long N, void *xbar_out, void *gtheta_out) {
+  NF_PRECOND_VIEW(desc);
   if (!is_composite(desc)) return tape_bwd_seg(ctx, desc, theta, tape, ybar, lbar, lbar_const, N, xbar_out, gtheta_out);
   const size_t es = esize(desc->dtype);
   size_t toff = 0;
@@ -1258,6 +1312,7 @@ static int fr_value_and_grad(nf_ctx *ctx, const nf_flow_desc *desc, const nf_tar
 static int elbo_forward(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, const void *theta,
                         const void *xs, long N, uint64_t seed, uint64_t off, uint32_t stream_id, void *elbos_out,
                         double *elbo_host) {
+  NF_PRECOND_VIEW(desc);
   if (is_composite(desc)) return elbo_forward_composite(ctx, desc, target, theta, xs, N, seed, off, stream_id, elbos_out, elbo_host);
   if (is_fr_tiled(desc)) return fr_elbo_forward(ctx, desc, target, theta, xs, N, seed, off, stream_id, elbos_out, elbo_host);
   const size_t es = esize(desc->dtype);
@@ -1336,6 +1391,7 @@ extern "C" int nf_loglikelihood(nf_ctx *ctx, const nf_flow_desc *desc, const voi
   if (is_fr(desc)) return NF_ERR_UNSUPPORTED;  // the maximum-likelihood Gaussian is a closed form
   NF_HIP(hipSetDevice(ctx->device));
   if (flow_base(desc)) return loglikelihood_general_base(ctx, desc, theta, ys, N, logliks_out, ll_host);
+  NF_PRECOND_VIEW(desc);  // value only: logpdf(flow, y) through the inverse chain
   if (is_composite(desc)) return loglikelihood_composite(ctx, desc, theta, ys, N, logliks_out, ll_host);
   const bool cp = is_coupling(desc);
   const long nb = nf_sum2_nblocks(N);
@@ -1427,7 +1483,7 @@ extern "C" int nf_loglikelihood_value_and_grad(nf_ctx *ctx, const nf_flow_desc *
                                                int64_t N_local, int64_t N_global, void *out) {
   if (!ctx || !theta || !out || N_local < 0 || N_global < 1 || (N_local > 0 && !ys)) return NF_ERR_ARG;
   NF_TRY(check_desc(desc));
-  if (is_fr(desc)) return NF_ERR_UNSUPPORTED;
+  if (is_fr(desc) || is_precond(desc)) return NF_ERR_UNSUPPORTED;  // (the pullback through inv(L): DESIGN.md section 7)
   NF_HIP(hipSetDevice(ctx->device));
   // general bases and heterogeneous compositions: segment by segment in the standard layout (fkl_general below)
   if (flow_base(desc) || is_composite(desc)) return fkl_general(ctx, desc, theta, ys, N_local, N_global, out);
@@ -1888,6 +1944,101 @@ extern "C" int nf_base_logpdf_general(nf_ctx *ctx, int32_t dtype, const nf_base 
 }
 
 // ---- training step -------------------------------------------------------------------------
+// A preconditioned coupling flow in Float32 whose inner flow is on the matrix-pipe kernels: every buffer stays in the tiled
+// layout from the draw to the gradient.  Draws and log q0 (or the caller's draws, converted once), the inner chain in place on
+// the tile buffer leaving the tape of its kind, the triangular tile GEMM into a second buffer (the chain's output tile IS the
+// full-rank layer's tape), the two log-dets added per sample, the tiled target launch, then the full-rank layer's reverse
+// pass -- one launch (k_fr_bwd_x) or the two of NF_KIND_FULLRANK (k_fr_bwd, then k_fr_gemm transposed), the same bits either
+// way -- and the inner reverse pass from its tape with that cotangent.
+// Which arm, as measured: the one launch from d = 33 on (level at d <= 64, 14 % / 8 % faster at d = 128 /
+// 256); at d <= 32 the two launches, 33 against 36 us at 65 536 draws -- with one 32-feature block only one of the four waves
+// has a block of xbar to compute, and k_fr_gemm spreads the tiles over eight times as many workgroups as the grid-stride
+// kernel has.  NF_PRECOND_BWD_SPLIT (read once per process) overrides: 1 = the two launches at every d, 0 = the one launch.
+static inline bool precond_tiled(const nf_flow_desc *desc) { return is_precond(desc) && is_coupling(&desc->segments[0]); }
+static inline bool precond_bwd_split(int d) {
+  static const int forced = [] {
+    const char *e = std::getenv("NF_PRECOND_BWD_SPLIT");
+    return !e ? -1 : e[0] == '1' ? 1 : e[0] == '0' ? 0 : -1;
+  }();
+  return forced >= 0 ? forced == 1 : d <= 32;
+}
+struct PrecondVgBufs {
+  TapeKind tk;
+  long nb, stride = 0;
+  int grid = 0;
+  float *xt, *yt, *gt, *logq, *ladj, *ladj_fr, *fr_slab, *slab, *stash = nullptr;
+  void *rqs_tape = nullptr;
+  double *partial, *partial_s;
+  PrecondVgBufs() {}
+  PrecondVgBufs(Carver &cv, nf_ctx *ctx, const nf_flow_desc *desc, long N) {
+    const nf_flow_desc *g = &desc->segments[0];
+    const size_t te = tiled_elems(g, N), d = (size_t)desc->d;
+    tk = tape_kind(ctx, g, N);
+    nb = nf_target_tiled_nblocks(N);
+    xt = cv.take<float>(te);
+    yt = cv.take<float>(te);
+    gt = cv.take<float>(te);
+    logq = cv.take<float>((size_t)N);
+    ladj = cv.take<float>((size_t)N);
+    ladj_fr = cv.take<float>((size_t)N);
+    partial = cv.take<double>(nb);
+    partial_s = cv.take<double>(nf_sum2_nblocks(N));
+    fr_slab = cv.take<float>((size_t)nf_fr_bwd_grid(ctx, N) * (d + d * d));
+    if (tk == TAPE_WIDE) {  // the forward's stash and the reverse pass's split-K area
+      slab = cv.take<float>(nf_wide_train_ws_floats(ctx, g, N));
+      return;
+    }
+    grid = coupling_bwd_grid(ctx, g, N);
+    stride = coupling_slab_floats(ctx, g, N);
+    slab = cv.take<float>((size_t)grid * stride);
+    if (tk == TAPE_AFFINE_STASH) stash = cv.take<float>(nf_affine_stash_floats(g, N));
+    if (rqs_tape_b(g, N)) rqs_tape = (void *)cv.take<char>(rqs_tape_b(g, N));
+  }
+};
+static int precond_value_and_grad(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, const void *theta, const void *xs,
+                                  long N, long N_global, uint64_t seed, uint64_t off, uint32_t stream_id, void *out) {
+  PrecondView pv;
+  precond_view(desc, &pv);
+  const nf_flow_desc *fr = &pv.seg[0], *g = &pv.seg[1];
+  const int d = desc->d;
+  const long Pfr = nf_param_count(fr), P = nf_param_count(desc);
+  const float *th = (const float *)theta, *thg = th + Pfr;
+  float *gout = (float *)out, *gout_g = gout + Pfr;
+  const double inv = 1.0 / (double)N_global;
+  PrecondVgBufs b;
+  NF_TRY(ws_carve(ctx, &b, desc, N));
+  if (xs) {
+    NF_TRY(nf_launch_layout_convert(ctx, d, N, (const float *)xs, b.xt, 1));
+    NF_TRY(nf_launch_base_logpdf_tiled(ctx, d, N, b.xt, b.logq));
+  } else {
+    NF_TRY(nf_launch_base_sample_tiled(ctx, d, N, seed, off, stream_id, b.xt, b.logq));
+  }
+  NF_TRY(coupling_pack(ctx, g, thg));
+  if (b.tk == TAPE_AFFINE_STASH) NF_TRY(nf_affine_chain(ctx, g, false, b.xt, N, b.ladj, b.stash));
+  else if (b.tk == TAPE_WIDE) NF_TRY(nf_wide_train_forward(ctx, g, b.xt, N, b.ladj, b.slab));
+  else if (is_nsf(g)) NF_TRY(nf_rqs_chain(ctx, g, false, b.xt, N, b.ladj, -1, b.rqs_tape));
+  else NF_TRY(nf_affine_chain(ctx, g, false, b.xt, N, b.ladj));
+  NF_TRY(nf_fr_fwd_tiled(ctx, fr, th, b.xt, N, b.yt, b.ladj_fr));
+  NF_TRY(nf_launch_sum2(ctx, NF_DTYPE_F32, N, b.ladj, b.ladj_fr, b.ladj, b.partial_s, 0.0));
+  // gt = d(-elbo/Ng)/dy = -(1/Ng) grad logp(y);  partial sums of -elbo_j/Ng
+  NF_TRY(nf_launch_target_tiled(ctx, target, d, N, b.yt, b.logq, b.ladj, b.gt, -inv, nullptr, b.partial, -inv));
+  NF_TRY(nf_launch_finish_sum(ctx, b.partial, b.nb, 0, nullptr, gout + P, nullptr));
+  // the full-rank layer: [g_mu ; g_L] from (xt, gt), and gt <- L' gt in place
+  if (precond_bwd_split(d)) {
+    NF_TRY(nf_fr_grad(ctx, fr, th, b.xt, 1, b.gt, 1, nullptr, (float)(-inv), N, b.fr_slab, gout));
+    NF_TRY(nf_fr_pull_tiled(ctx, fr, th, b.gt, N, b.gt));
+  } else {
+    NF_TRY(nf_fr_bwd_x_tiled(ctx, fr, th, b.xt, b.gt, nullptr, (float)(-inv), N, b.fr_slab, gout, b.gt));
+  }
+  // the couplings, from their tape (nobody reads the cotangent of the draws)
+  if (b.tk == TAPE_AFFINE_STASH) {
+    NF_TRY(nf_affine_bwd_stashed(ctx, g, b.stash, b.gt, nullptr, (float)(-inv), N, b.slab, b.stride, b.grid, false, true));
+    return nf_affine_reduce_slabs(ctx, g, b.slab, b.grid, gout_g);
+  }
+  if (b.tk == TAPE_WIDE) return nf_wide_train_backward(ctx, g, b.xt, b.gt, nullptr, (float)(-inv), N, b.slab, gout_g);
+  return realnvp_bwd(ctx, g, thg, b.xt, b.gt, nullptr, (float)(-inv), N, b.slab, b.grid, gout_g, nullptr, 0, nullptr, b.rqs_tape);
+}
+
 struct VgBufs {
   bool cp, wide, simple_kind, simple_step;
   long nb, stash_nc;  // the target kernel's loss partials; samples per stash chunk (0: no stash)
@@ -1937,6 +2088,11 @@ extern "C" int nf_elbo_value_and_grad(nf_ctx *ctx, const nf_flow_desc *desc, con
   NF_HIP(hipSetDevice(ctx->device));
   if (flow_base(desc))
     return value_and_grad_general_base(ctx, desc, target, theta, xs, N_local, N_global, seed, sample_offset, stream_id, out);
+  if (precond_tiled(desc)) {
+    if (N_local == 0) return nf_launch_fill(ctx, desc->dtype, out, nf_param_count(desc) + 1, 0.0);
+    return precond_value_and_grad(ctx, desc, target, theta, xs, N_local, N_global, seed, sample_offset, stream_id, out);
+  }
+  NF_PRECOND_VIEW(desc);
   if (is_composite(desc))
     return value_and_grad_composite(ctx, desc, target, theta, xs, N_local, N_global, seed, sample_offset, stream_id, out);
   const long N = N_local;
@@ -2435,7 +2591,7 @@ static int step_split(nf_ctx *ctx, const nf_flow_desc *desc, const StepCall &c) 
 static int step_run(nf_ctx *ctx, const nf_flow_desc *desc, const StepCall &c, double *loss_host, double *gnorm_host, void *out_device) {
   NF_TRY(check_desc(desc));
   if (target_refused(desc, c.target)) return NF_ERR_UNSUPPORTED;
-  if (is_fr(desc) && (!c.target || c.step_device)) return NF_ERR_UNSUPPORTED;  // no forward-KL step, no graph-replay form
+  if ((is_fr(desc) || is_precond(desc)) && (!c.target || c.step_device)) return NF_ERR_UNSUPPORTED;  // no forward-KL step, no graph-replay form
   NF_HIP(hipSetDevice(ctx->device));
   if (c.Ng < 1) return NF_ERR_ARG;
   const long P = nf_param_count(desc), N = c.N;
@@ -2548,6 +2704,7 @@ static size_t ws_tail_bytes(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
     if (!is_coupling(g)) return nf_l64_scratch_bytes(g, N);  // general Float32 couplings: the MFMA MLP's activation tiles
     return is_wide(g) ? nf_wide_wimg_bytes(ctx, g) : is_nsf(g) ? nf_rqs_wimg_bytes(g) : nf_affine_wimg_bytes(g);
   };
+  NF_PRECOND_VIEW(desc);
   size_t wimg = is_composite(desc) ? 0 : wimg_of(desc);
   for (int s = 0; is_composite(desc) && s < desc->nsegments; ++s)
     wimg += carve_bytes(wimg_of(&desc->segments[s]));  // grow-only tail carves: a later, larger segment carves again
@@ -2559,6 +2716,8 @@ static size_t ws_need_bound(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
   // nf_flow_bwd (its own forward + tape; nf_flow_fwd_keep / nf_flow_bwd_kept, tape in the caller's memory, need its front)
   size_t need = layout_bytes<FlowBwdBufs>(ctx, desc, N);
   auto upd = [&](size_t v) { if (v > need) need = v; };
+  if (precond_tiled(desc)) upd(layout_bytes<PrecondVgBufs>(ctx, desc, N));  // the tiled training step
+  NF_PRECOND_VIEW(desc);
   if (is_composite(desc)) {
     upd(layout_bytes<CompBufs>(ctx, desc, N));
     upd(layout_bytes<VgCompositeBufs>(ctx, desc, N));

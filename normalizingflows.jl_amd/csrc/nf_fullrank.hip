@@ -17,6 +17,10 @@
 //               dealt round-robin to the four waves (36 blocks at d = 256: nine per wave).  g_mu from the same tile.  No
 //               atomics: one slab per workgroup (theta's layout), reduced in block order by nf_launch_reduce_slabs.  The
 //               log-det term (sum_j lbar_j) / L_ii enters once per workgroup, when the slab is written.
+//   k_fr_bwd_x  k_fr_bwd on tiled x and ybar that ALSO leaves xbar = L' ybar from the ybar tile it has staged (k_fr_gemm's
+//               transposed walk, a matrix-block image per wave behind the two tiles): the whole reverse pass of the layer in one
+//               launch, for flows that continue the reverse pass below it (NF_KIND_PRECOND).  Same arithmetic, same order as
+//               k_fr_bwd followed by k_fr_gemm(trans): the same bits.
 //   k_fr_tri_inverse   inv(L) once per call: one workgroup, thread c runs forward substitution on column c of the identity.
 // The log-det sum_i log|L_ii| is a function of theta alone: computed once per workgroup, written per sample.
 // The shift is added AFTER the product (not as the initial accumulator): the whole map and Shift applied to Scale's
@@ -272,6 +276,123 @@ __global__ __launch_bounds__(FR_BLOCK) void k_fr_bwd(int d, long N, long ntiles,
   }
 }
 
+// k_fr_bwd on tiled x and ybar that also leaves the layer's input cotangent: from the same staged ybar tile xbar = L' ybar,
+// k_fr_gemm's transposed block walk (the same staging, the same k order: the same bits as the two launches), written from the
+// accumulator registers in the tiled layout.  xbar may alias ybar: a workgroup has its tile in LDS before it writes anything.
+// The gradient part is k_fr_bwd's text, kept apart so that k_fr_bwd keeps its instruction stream.
+template <int DB>
+__global__ __launch_bounds__(FR_BLOCK) void k_fr_bwd_x(int d, long N, long ntiles, const float *__restrict__ L,
+                                                       const float *__restrict__ x, const float *ybar,
+                                                       const float *__restrict__ lbar, float lbar_const,
+                                                       float *__restrict__ slabs, float *xbar) {
+  using G = FrGeo<DB>;
+  constexpr int NBLK = DB * (DB + 1) / 2, MB = (NBLK + FR_WAVES - 1) / FR_WAVES;
+  extern __shared__ float fr_sm[];
+  float *sX = fr_sm;
+  float *sG = sX + G::TILE;
+  __shared__ float sls;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l31 = lane & 31, hi = lane >> 5;
+  f32x16 acc[MB];
+  int fbs[MB], kbs[MB];
+#pragma unroll
+  for (int i = 0; i < MB; ++i) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+    fr_block_of(wave + FR_WAVES * i, fbs[i], kbs[i]);
+  }
+  float gmu = 0.f, ls = 0.f;
+  for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    __syncthreads();  // the previous tile's readers
+    fr_load_tile<DB>(sX, x, true, d, N, tile, nullptr);
+    fr_load_tile<DB>(sG, ybar, true, d, N, tile, nullptr);
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < MB; ++i) {
+      if (wave + FR_WAVES * i < NBLK && fbs[i] * 32 < d) {  // (wave-uniform)
+        const float *pa = sX + (kbs[i] * 32 + l31) * FR_XS + hi;
+        const float *pb = sG + (fbs[i] * 32 + l31) * FR_XS + hi;
+#pragma unroll
+        for (int t = 0; t < 16; ++t) acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[2 * t], pb[2 * t], acc[i], 0, 0, 0);
+      }
+    }
+    if ((int)threadIdx.x < d) {
+      const float *pg = sG + threadIdx.x * FR_XS;
+      float a = 0.f;
+#pragma unroll
+      for (int s = 0; s < 32; ++s) a += pg[s];
+      gmu += a;
+    }
+    if (threadIdx.x < 32) {
+      const long j = tile * 32 + threadIdx.x;
+      ls += j < N ? (lbar ? lbar[j] : lbar_const) : 0.f;
+    }
+    {  // xbar = L' ybar from the staged tile
+      float *img = sG + G::TILE + wave * G::IMG;
+      float *obase = xbar + tile * d * 32;
+      const bool valid = tile * 32 + l31 < N;
+      const int nblk = (d + 31) >> 5;
+      for (int fb = wave; fb < nblk; fb += FR_WAVES) {
+        f32x16 ax;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) ax[r] = 0.f;
+        float v[16];
+        fr_stage_load(v, L, d, fb, fb, 1, lane);
+        for (int kb = fb; kb < nblk; ++kb) {
+          fr_stage_store(img, v, 1, lane);
+          wave_lds_fence();
+          if (kb < nblk - 1) fr_stage_load(v, L, d, fb, kb + 1, 1, lane);  // in flight during this block's products
+          const int nf = d - kb * 32 < 32 ? d - kb * 32 : 32;
+          const int ng = (nf + 7) >> 3;
+          const float *pa = img + l31 * FR_IS + hi;
+          const float *pb = sG + (kb * 32 + hi) * FR_XS + l31;
+          for (int g = 0; g < ng; ++g) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+              ax = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[8 * g + 2 * e], pb[(8 * g + 2 * e) * FR_XS], ax, 0, 0, 0);
+          }
+          wave_lds_fence();  // the next staging overwrites the image
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int f = fb * 32 + nf_row(r, hi);
+          if (f < d) obase[f * 32 + l31] = valid ? ax[r] : 0.f;
+        }
+      }
+    }
+  }
+  if (wave == 0) {
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) ls += __shfl_xor(ls, o, 64);
+    if (lane == 0) sls = ls;
+  }
+  __syncthreads();
+  const long P = (long)d + (long)d * d;
+  float *slab = slabs + (long)blockIdx.x * P;
+  if ((int)threadIdx.x < d) slab[threadIdx.x] = gmu;
+  // blocks above the diagonal: zeros (the lower blocks, the diagonal ones' upper halves included, are written below)
+  for (int idx = threadIdx.x; idx < d * d; idx += FR_BLOCK) {
+    const int k = idx / d, f = idx - k * d;
+    if ((k >> 5) > (f >> 5)) slab[d + idx] = 0.f;
+  }
+  const float lsum = sls;
+#pragma unroll
+  for (int i = 0; i < MB; ++i) {
+    if (wave + FR_WAVES * i < NBLK && fbs[i] * 32 < d) {
+      const int f = fbs[i] * 32 + l31;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int k = kbs[i] * 32 + nf_row(r, hi);
+        if (f < d && k < d) {
+          float v = 0.f;
+          if (k < f) v = acc[i][r];
+          if (k == f) v = acc[i][r] + lsum / L[f + (long)f * d];
+          slab[d + f + (long)k * d] = v;
+        }
+      }
+    }
+  }
+}
+
 // W = inv(L), both lower triangular, d x d column-major: thread c solves L w = e_c by forward substitution
 __global__ __launch_bounds__(FR_BLOCK) void k_fr_tri_inverse(int d, const float *__restrict__ L, float *W) {
   const int c = threadIdx.x;
@@ -404,6 +525,21 @@ static int fr_bwd_db(nf_ctx *ctx, int d, long N, int grid, const float *L, const
   return (int)hipGetLastError();
 }
 
+template <int DB>
+static int fr_bwd_x_db(nf_ctx *ctx, int d, long N, int grid, const float *L, const float *x, const float *ybar, const float *lbar,
+                       float lbar_const, float *slabs, float *xbar) {
+  const size_t lds = (size_t)(2 * FrGeo<DB>::TILE + FR_WAVES * FrGeo<DB>::IMG) * sizeof(float);
+  static AttrOnce attr_once;
+  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
+    NF_HIP(hipFuncSetAttribute((const void *)&k_fr_bwd_x<DB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return NF_OK;
+  }));
+  ProfScope ps(ctx, "fr_bwd_x");
+  hipLaunchKernelGGL(k_fr_bwd_x<DB>, dim3((unsigned)grid), dim3(FR_BLOCK), lds, ctx->stream, d, N, (N + 31) / 32, L, x, ybar, lbar,
+                     lbar_const, slabs, xbar);
+  return (int)hipGetLastError();
+}
+
 // workgroups (= gradient slabs) of the Float32 reverse kernel: one per compute unit at most, each walking its tiles
 int nf_fr_bwd_grid(nf_ctx *ctx, long N) {
   const long nt = (N + 31) / 32;
@@ -427,6 +563,26 @@ int nf_fr_grad(nf_ctx *ctx, const nf_flow_desc *desc, const float *theta, const 
   else st = fr_bwd_db<8>(ctx, d, N, grid, L, x, x_tiled, ybar, y_tiled, lbar, lbar_const, slabs);
   NF_TRY(st);
   return nf_launch_reduce_slabs(ctx, NF_DTYPE_F32, slabs, grid, fr_params(d), gtheta_out);
+}
+
+// The layer's whole reverse pass on tiled buffers in one launch: the parameter gradient as nf_fr_grad, and xbar = L' ybar
+// (xbar may alias ybar)
+int nf_fr_bwd_x_tiled(nf_ctx *ctx, const nf_flow_desc *desc, const float *theta, const float *xt, const float *ybar,
+                      const float *lbar, float lbar_const, long N, float *slabs, float *gtheta_out, float *xbar) {
+  const int d = desc->d, grid = nf_fr_bwd_grid(ctx, N);
+  const float *L = theta + d;
+  int st;
+  if (d <= 32) st = fr_bwd_x_db<1>(ctx, d, N, grid, L, xt, ybar, lbar, lbar_const, slabs, xbar);
+  else if (d <= 64) st = fr_bwd_x_db<2>(ctx, d, N, grid, L, xt, ybar, lbar, lbar_const, slabs, xbar);
+  else if (d <= 128) st = fr_bwd_x_db<4>(ctx, d, N, grid, L, xt, ybar, lbar, lbar_const, slabs, xbar);
+  else st = fr_bwd_x_db<8>(ctx, d, N, grid, L, xt, ybar, lbar, lbar_const, slabs, xbar);
+  NF_TRY(st);
+  return nf_launch_reduce_slabs(ctx, NF_DTYPE_F32, slabs, grid, fr_params(d), gtheta_out);
+}
+// xbar = L' ybar alone, tiled in and out (the second launch of the two-launch reverse pass; xbar may alias ybar)
+int nf_fr_pull_tiled(nf_ctx *ctx, const nf_flow_desc *desc, const float *theta, const float *ybar, long N, float *xbar) {
+  const int d = desc->d;
+  return fr_gemm(ctx, d, N, theta + d, 1, nullptr, nullptr, nullptr, 0.f, ybar, 1, xbar, 1, nullptr);
 }
 
 // Float32 forward on tiled buffers (the ELBO sequence): yt = mu + L xt, ladj = sum log|L_ii|

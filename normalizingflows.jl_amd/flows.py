@@ -217,7 +217,7 @@ class CompositeFlow(Flow):
             raise NFHipError("create_flow: empty layer list")
         dt, dev = segments[0].theta.dtype, segments[0].theta.device
         for f in segments:
-            if isinstance(f, CompositeFlow) or f.kind == "hamiltonian":
+            if isinstance(f, CompositeFlow) or f.kind in ("hamiltonian", "preconditioned"):
                 raise NFHipError("create_flow: segments must be single-family flows")
             if f.kind == "fullrank":
                 raise NFHipError("create_flow: a full-rank Shift o Scale(LowerTriangular) is not built as a segment yet")
@@ -251,6 +251,70 @@ class CompositeFlow(Flow):
 
     def with_theta(self, theta: torch.Tensor) -> "CompositeFlow":
         return CompositeFlow(self.segments, self.dist, theta)
+
+
+class PrecondFlow(Flow):
+    """transformed(q0, Shift(mu) o Scale(LowerTriangular(L)) o couplings): `inner` (a realnvp / nsf flow) under a full-rank
+    affine layer, one family of its own (NF_KIND_PRECOND).  theta = [mu (d) ; L, d x d column-major ; inner.theta], outermost
+    first; flat layer order 0 = Shift, 1 = Scale, 2... = the couplings."""
+
+    def __init__(self, inner: Flow, dist: MvNormal, theta: torch.Tensor):
+        if isinstance(inner, (CompositeFlow, PrecondFlow)) or inner.kind not in ("realnvp", "nsf"):
+            raise NFHipError("preconditioned: the inner flow must be a realnvp or nsf flow")
+        if inner.dist.d != dist.d:
+            raise NFHipError("preconditioned: the inner flow and q0 must share the dimension")
+        dt = inner.theta.dtype
+        self.kind, self.dist, self.nlayers = "preconditioned", dist, 1
+        self.hdims, self.K, self.B, self.score = (), 0, 0.0, None
+        self.inner = inner
+        self._inner_desc = FlowDesc()
+        C.memmove(C.addressof(self._inner_desc), C.addressof(inner.desc), C.sizeof(FlowDesc))
+        self._inner_desc.base = None  # q0 belongs to the outer flow
+        self.desc = FlowDesc()
+        self.desc.kind = _lib.NF_KIND["preconditioned"]
+        self.desc.dtype = _dtype_code(dt)
+        self.desc.d = dist.d
+        self.desc.nlayers = 1
+        self.desc.nsegments = 1
+        self.desc.segments = C.addressof(self._inner_desc)
+        if not dist.standard:
+            if dist.mu.dtype != dt:
+                raise NFHipError(f"base distribution is {dist.mu.dtype}, flow parameters are {dt}")
+            self.desc.base = C.addressof(dist.c)
+        self.P = int(_lib.load_library().nf_param_count(C.byref(self.desc)))
+        if self.P < 0:
+            check(self.P)
+        self.theta = theta
+        if self.theta.numel() != self.P:
+            raise NFHipError(f"theta has {self.theta.numel()} entries, flow has {self.P} parameters")
+        self.transform = Transform(self)
+
+    def with_theta(self, theta: torch.Tensor) -> "PrecondFlow":
+        return PrecondFlow(self.inner, self.dist, theta)
+
+
+def preconditioned(inner: Flow, *, mu: Optional[torch.Tensor] = None, L: Optional[torch.Tensor] = None,
+                   init: Optional[Flow] = None) -> Flow:
+    """create_flow((Shift(mu), Scale(LowerTriangular(L)), couplings...), q0) as one family: y = mu + L T_inner(x) on the
+    inner flow's q0.  Default mu = 0, L = I (forward and logpdf then equal the inner flow's to rounding); `L` is the d x d
+    matrix (row i, column k at L[i, k]; what lies above the diagonal is kept in theta and never read).  `init=` takes a
+    `fullrank` flow of the same d and element type and copies its [mu ; L] bit for bit: fit full-rank ADVI, then refine."""
+    if not isinstance(inner, Flow) or isinstance(inner, (CompositeFlow, PrecondFlow)) or inner.kind not in ("realnvp", "nsf"):
+        raise NFHipError("preconditioned: the inner flow must be a realnvp or nsf flow")
+    d, dt, dev = inner.dist.d, inner.theta.dtype, inner.theta.device
+    if init is not None:
+        if mu is not None or L is not None:
+            raise NFHipError("preconditioned: give init= or mu= / L=, not both")
+        if not isinstance(init, Flow) or init.kind != "fullrank" or init.dist.d != d or init.theta.dtype != dt:
+            raise NFHipError("preconditioned: init= must be a fullrank flow of the same dimension and element type")
+        head = init.theta.detach().to(dev).clone()
+    else:
+        mu = torch.zeros(d, dtype=dt, device=dev) if mu is None else mu
+        L = torch.eye(d, dtype=dt, device=dev) if L is None else L
+        if mu.shape != (d,) or L.shape != (d, d):
+            raise NFHipError(f"preconditioned: mu must be ({d},) and L ({d}, {d})")
+        head = torch.cat([mu.to(dt).to(dev), L.to(dt).to(dev).t().contiguous().reshape(-1)])  # column-major
+    return PrecondFlow(inner, inner.dist, torch.cat([head, inner.theta.detach()]))
 
 
 def create_flow(Ls: Sequence[Flow], q0: MvNormal) -> Flow:

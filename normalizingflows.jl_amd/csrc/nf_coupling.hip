@@ -31,80 +31,6 @@ struct CouplingArgs {
 };
 
 // ------------------------------------------------------------------------------------
-// forward / inverse of one coupling (no gradients): both nets resident in LDS
-// ------------------------------------------------------------------------------------
-template <class G, bool INVERSE, bool FULL>
-__global__ __launch_bounds__(512) void k_affine_apply(CouplingArgs a, const float *x_in,
-                                                      float *y_out, float *__restrict__ ladj,
-                                                      int ladj_accumulate) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  float *img_s = lds;
-  float *img_t = lds + G::SIZE;
-  const int tid = threadIdx.x;
-  stage_packed<G::SIZE, 512>(img_s, a.img_s, tid);
-  stage_packed<G::SIZE, 512>(img_t, a.img_t, tid);
-  __syncthreads();
-
-  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // provably wave-uniform
-  const int l31 = lane & 31, hi = lane >> 5;
-  const int par_c = 1 - a.par_t;
-  const long ntiles = (a.N + NF_TILE - 1) / NF_TILE;
-  const bool copy_cond = (y_out != x_in);
-
-  for (long tile = (long)blockIdx.x * 8 + wave; tile < ntiles; tile += (long)gridDim.x * 8) {
-    const long j = tile * NF_TILE + l31;
-    const bool valid = FULL ? true : j < a.N;
-    const TileIO xin = make_tile_io(const_cast<float *>(x_in), tile, a.d, l31, hi);
-    const TileIO yout = make_tile_io(y_out, tile, a.d, l31, hi);
-
-    f32x16 xb[G::MB], x1[G::CB];
-#pragma unroll
-    for (int b = 0; b < G::MB; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float v = tile_load(xin, tile_soff(b, r, par_c));
-        xb[b][r] = valid ? v : 0.f;
-        if (copy_cond) tile_store(yout, tile_soff(b, r, par_c), v);
-      }
-#pragma unroll
-    for (int b = 0; b < G::CB; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) x1[b][r] = tile_load(xin, tile_soff(b, r, a.par_t));
-
-    f32x16 S[G::CB], T[G::CB];
-    {
-      f32x16 a1[G::H1B], a2[G::H2B];
-      net_forward<G>(img_s, xb, a1, a2, S, l31, hi);
-    }
-    {
-      f32x16 a1[G::H1B], a2[G::H2B];
-      net_forward<G>(img_t, xb, a1, a2, T, l31, hi);
-    }
-    float lsum = 0.f;
-#pragma unroll
-    for (int b = 0; b < G::CB; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int p = b * 32 + nf_row(r, hi);
-        const float s = nf_tanh(S[b][r]);  // padded rows: zero weights and bias => s = 0
-        const float v = x1[b][r];
-        float o;
-        if (INVERSE)
-          o = (v - T[b][r]) * nf_exp(-s);
-        else
-          o = v * nf_exp(s) + T[b][r];
-        tile_store(yout, tile_soff(b, r, a.par_t), o);  // rows >= c are outside the descriptor
-        lsum += (FULL || p < a.c) ? s : 0.f;
-      }
-    lsum += __shfl_xor(lsum, 32);
-    if (hi == 0 && valid) {
-      const float base = ladj_accumulate ? ladj[j] : 0.f;
-      ladj[j] = INVERSE ? base - lsum : base + lsum;
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------
 // whole-flow forward / inverse in ONE launch (with_logabsdet_jacobian of the ComposedFunction,
 // reached from src/objectives/elbo.jl:67; inverse chain from loglikelihood.jl:31)
 // ------------------------------------------------------------------------------------
@@ -190,9 +116,121 @@ __device__ __forceinline__ float coupling_step(const float *__restrict__ img_s, 
         x1[b][r] = nf_fdiv(x1[b][r] - T[b][r], nf_exp(s));
       else
         x1[b][r] = x1[b][r] * nf_exp(s) + T[b][r];
-      lsum += s;
+      {
+        // no contraction with nf_tanh's last product: whether hipcc fuses it into this sum differs from one kernel this function is
+        // inlined into to the next (seen: k_affine_chain against k_affine_apply_b6 at hidden 64, ladj one ulp apart with bit-equal y),
+        // and a chain of single couplings must add up to the whole chain bit for bit
+#pragma clang fp contract(off)
+        lsum += s;
+      }
     }
   return lsum;
+}
+
+// ------------------------------------------------------------------------------------
+// forward / inverse of one coupling (no gradients): both nets resident in LDS
+// ------------------------------------------------------------------------------------
+template <class G, bool INVERSE, bool FULL>
+__global__ __launch_bounds__(512) void k_affine_apply(CouplingArgs a, const float *x_in,
+                                                      float *y_out, float *__restrict__ ladj,
+                                                      int ladj_accumulate) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float *img_s = lds;
+  float *img_t = lds + G::SIZE;
+  const int tid = threadIdx.x;
+  stage_packed<G::SIZE, 512>(img_s, a.img_s, tid);
+  stage_packed<G::SIZE, 512>(img_t, a.img_t, tid);
+  __syncthreads();
+
+  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // provably wave-uniform
+  const int l31 = lane & 31, hi = lane >> 5;
+  const int par_c = 1 - a.par_t;
+  const long ntiles = (a.N + NF_TILE - 1) / NF_TILE;
+  const bool copy_cond = (y_out != x_in);
+
+  for (long tile = (long)blockIdx.x * 8 + wave; tile < ntiles; tile += (long)gridDim.x * 8) {
+    const long j = tile * NF_TILE + l31;
+    const bool valid = FULL ? true : j < a.N;
+    const TileIO xin = make_tile_io(const_cast<float *>(x_in), tile, a.d, l31, hi);
+    const TileIO yout = make_tile_io(y_out, tile, a.d, l31, hi);
+
+    f32x16 xb[G::MB], x1[G::CB];
+#pragma unroll
+    for (int b = 0; b < G::MB; ++b)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float v = tile_load(xin, tile_soff(b, r, par_c));
+        xb[b][r] = valid ? v : 0.f;
+        if (copy_cond) tile_store(yout, tile_soff(b, r, par_c), v);
+      }
+#pragma unroll
+    for (int b = 0; b < G::CB; ++b)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) x1[b][r] = tile_load(xin, tile_soff(b, r, a.par_t));
+
+    // the coupling itself is the whole-chain kernel's coupling_step (k_affine_chain's fp32 form runs the same function on the same
+    // images), so that under NF_FWD_FP32 too a chain of single couplings is the whole chain bit for bit; rows >= c have zero
+    // weights and biases in the packed image: s = 0, t = 0
+    float lsum = coupling_step<G, INVERSE>(img_s, img_t, x1, xb, l31, hi);
+#pragma unroll
+    for (int b = 0; b < G::CB; ++b)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) tile_store(yout, tile_soff(b, r, a.par_t), x1[b][r]);  // rows >= c are outside the descriptor
+    lsum += __shfl_xor(lsum, 32);
+    if (hi == 0 && valid) {
+      const float base = ladj_accumulate ? ladj[j] : 0.f;
+      ladj[j] = INVERSE ? base - lsum : base + lsum;
+    }
+  }
+}
+
+// One coupling in place on the tiled buffer with the arithmetic of the whole-chain kernel (k_affine_chain's B6 form: the same
+// coupling_step on the same bf16-triple images, the same fold of the log-determinant), so that nf_layer_apply of every coupling,
+// chained, IS nf_flow_fwd / nf_flow_inv bit for bit.  img6: the coupling's s and t B6 images, adjacent.
+template <class G, bool INVERSE>
+__global__ __launch_bounds__(512) void k_affine_apply_b6(CouplingArgs a, const unsigned char *__restrict__ img6, float *xy,
+                                                         float *__restrict__ ladj, int ladj_accumulate) {
+  using BG = B6Geo<G>;
+  static_assert(BG::BYTES % 16 == 0, "B6 images are copied in 16-byte pieces");
+  constexpr int B6F = BG::BYTES / 4;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int tid = threadIdx.x;
+  stage_packed<2 * B6F, 512>(lds, reinterpret_cast<const float *>(img6), tid);
+  __syncthreads();
+  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l31 = lane & 31, hi = lane >> 5;
+  const int par_c = 1 - a.par_t;
+  const long ntiles = (a.N + NF_TILE - 1) / NF_TILE;
+  for (long tile = (long)blockIdx.x * 8 + wave; tile < ntiles; tile += (long)gridDim.x * 8) {
+    const long j = tile * NF_TILE + l31;
+    const bool valid = j < a.N;
+    const TileIO io = make_tile_io(xy, tile, a.d, l31, hi);
+    f32x16 xb[G::MB], x1[G::CB];
+#pragma unroll
+    for (int b = 0; b < G::MB; ++b)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float v = tile_load(io, tile_soff(b, r, par_c));  // features >= d read as 0
+        xb[b][r] = valid ? v : 0.f;
+      }
+#pragma unroll
+    for (int b = 0; b < G::CB; ++b)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float v = tile_load(io, tile_soff(b, r, a.par_t));
+        x1[b][r] = valid ? v : 0.f;
+      }
+    float ls = coupling_step<G, INVERSE, true>(lds, lds + B6F, x1, xb, l31, hi);
+#pragma unroll
+    for (int b = 0; b < G::CB; ++b)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) tile_store(io, tile_soff(b, r, a.par_t), x1[b][r]);  // rows >= c are outside the descriptor
+    ls += __shfl_xor(ls, 32);
+    if (hi == 0 && valid) {
+      const float base = ladj_accumulate ? ladj[j] : 0.f;
+      ladj[j] = INVERSE ? base - ls : base + ls;
+    }
+  }
 }
 
 // ---- activation stash of the training step (forward writes, reverse pass reads) ---------------------------
@@ -268,6 +306,26 @@ __device__ __forceinline__ void stash_put_lane(const StashIO &st, int base, cons
     }
 }
 
+// The masks the stashing forward leaves for the reverse pass.  DEVIATION, hidden-64 geometry only (NetGeo<1, 2, 2, 1>: the forward
+// whose stash k_affine_bwd_pair reads -- bench.py's step): the mask is the activation's SIGN BIT, so a pre-activation of
+// exactly +0 differentiates with slope 1 where the reference and every other kernel here use 0.01.  nf_sign_mask16's exact
+// rule costs one more vector instruction per element in a kernel that is issue-bound: measured on one MI355X in three
+// alternating runs, 0.5558 / 0.5596 / 0.5617 ms per step against the parent's 0.5517 / 0.5484 / 0.5478 (+1.8 %, the parent's
+// own spread: 0.7 %; DESIGN sections 4 and 5).  A unit with all-zero weights and bias, or a conditioner half of exactly 0,
+// gets db / dW rows 100 x the reference's on this path; nf_ctx_set_stash_budget(0) (the recompute pass) is exact.
+template <class G>
+__device__ __forceinline__ unsigned stash_mask16(const f32x16 &v) {
+  if constexpr (G::H1B == 2 && G::H2B == 2) {
+    unsigned bits = 0;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) bits = __builtin_amdgcn_alignbit(bits, (unsigned)__float_as_int(v[r]), 31);
+    asm volatile("" : "+v"(bits));
+    return bits;
+  } else {
+    return nf_sign_mask16(v);
+  }
+}
+
 template <class G, bool STORE_X, bool SLIM = false, bool B6 = false>
 __device__ __forceinline__ void net_forward_stash(const float *__restrict__ img, const f32x16 (&x)[G::MB], f32x16 (&out)[G::CB],
                                                   int l31, int hi, const StashIO &st, int nbase) {
@@ -289,7 +347,7 @@ __device__ __forceinline__ void net_forward_stash(const float *__restrict__ img,
 #pragma unroll
     for (int b = 0; b < G::H1B; ++b) {
       nf_lrelu16(a1[b]);
-      m1[b] = nf_sign_mask16(a1[b]);
+      m1[b] = stash_mask16<G>(a1[b]);
     }
     if (SLIM)
       dense_fwd_b6<G::H1B, G::H2B, NoSideJob, true>(w + B::L2, bias + B::B2, a1, a2, l31, hi);
@@ -298,7 +356,7 @@ __device__ __forceinline__ void net_forward_stash(const float *__restrict__ img,
 #pragma unroll
     for (int b = 0; b < G::H2B; ++b) {
       nf_lrelu16(a2[b]);
-      m2[b] = nf_sign_mask16(a2[b]);
+      m2[b] = stash_mask16<G>(a2[b]);
     }
     dense_fwd_b6<G::H2B, G::CB, decltype(sj2), true>(w + B::L3, bias + B::B3, a2, out, l31, hi, sj2);
     const u32x4 mkb = {m1[0], m1[1], m2[0], m2[1]};
@@ -313,7 +371,7 @@ __device__ __forceinline__ void net_forward_stash(const float *__restrict__ img,
 #pragma unroll
   for (int b = 0; b < G::H1B; ++b) {
     nf_lrelu16(a1[b]);
-    m1[b] = nf_sign_mask16(a1[b]);
+    m1[b] = stash_mask16<G>(a1[b]);
   }
   if (SLIM)
     dense_fwd<G::H1B, G::H2B>(img + G::W2, img + G::B2, a1, a2, l31, hi);
@@ -323,7 +381,7 @@ __device__ __forceinline__ void net_forward_stash(const float *__restrict__ img,
 #pragma unroll
   for (int b = 0; b < G::H2B; ++b) {
     nf_lrelu16(a2[b]);
-    m2[b] = nf_sign_mask16(a2[b]);
+    m2[b] = stash_mask16<G>(a2[b]);
   }
   dense_fwd<G::H2B, G::CB>(img + G::W3, img + G::B3, a2, out, l31, hi,
                            [&](int e) { stash_put_T<G::H2B>(st, nbase + SG::A2, a2, e); });
@@ -544,6 +602,13 @@ __device__ __forceinline__ void affine_chain_body(ChainArgs a, float *xt, float 
         }
     }
     float lsum = 0.f;
+    // the forms that STORE ladj (not FUSED) fold each coupling's log-determinant over the two half-waves on its own, so that
+    // nf_layer_apply of every coupling, chained, adds up to the whole chain's ladj bit for bit; the fused forms (the training
+    // steps) keep one running sum and fold once
+    auto fold_ls = [&](float v) {
+      if constexpr (!FUSED) v += __shfl_xor(v, 32);
+      return v;
+    };
     const bool more_groups = grp + gridDim.x < ngroups;
 #pragma unroll 1
     for (int s = 0; s < a.ncoup; s += 2) {
@@ -595,7 +660,7 @@ __device__ __forceinline__ void affine_chain_body(ChainArgs a, float *xt, float 
             else ls = coupling_step<G, INVERSE, true, decltype(between), NW == 8>(img_s, img_t, E, O, l31, hi, between, tr);
             NF_CS_STAMP(tr, 4);
           }
-          lsum += ls;
+          lsum += fold_ls(ls);
           cur_slot = slot_t == 2 ? 0 : slot_t + 1;
           continue;
         }
@@ -629,7 +694,7 @@ __device__ __forceinline__ void affine_chain_body(ChainArgs a, float *xt, float 
           if (INVERSE ? (half == 1) : (half == 0)) ls = coupling_step_stash<G, INVERSE, SLIM>(img_s, img_t, O, E, l31, hi, st, tr);
           else ls = coupling_step_stash<G, INVERSE, SLIM>(img_s, img_t, E, O, l31, hi, st, tr);
           NF_CH_STAMP(tr, 3);
-          lsum += ls;
+          lsum += fold_ls(ls);
           __syncthreads();
           NF_CH_STAMP(tr, 4);
           buf ^= 1;
@@ -640,7 +705,7 @@ __device__ __forceinline__ void affine_chain_body(ChainArgs a, float *xt, float 
         } else {
           ls = coupling_step<G, INVERSE>(img_s, img_t, E, O, l31, hi);
         }
-        lsum += ls;
+        lsum += fold_ls(ls);
         __syncthreads();
         buf ^= 1;
       }
@@ -657,7 +722,7 @@ __device__ __forceinline__ void affine_chain_body(ChainArgs a, float *xt, float 
             tile_store(io, tile_soff(b, r, 1), O[b][r]);
           }
       }
-      lsum += __shfl_xor(lsum, 32);
+      if constexpr (FUSED) lsum += __shfl_xor(lsum, 32);
       if (!FUSED) {
         if (hi == 0 && valid) ladj[j] = INVERSE ? -lsum : lsum;
       }
@@ -848,11 +913,12 @@ __device__ __forceinline__ void unstage_dense(const float *__restrict__ img, int
 #define NF_TSB(slot) do { } while (0)
 #endif
 
-// Sign masks of the hidden pre-activations (bit r set <=> z[r] has its sign bit set, i.e. the
-// leaky-ReLU slope is 0.01): all the reverse pass needs of a1/a2 besides their LDS copies, so the
-// activations themselves can die early.  leakyrelu keeps the sign, so the mask is taken from the
-// post-activation value.  z = +0 counts as slope 1 where the oracle uses 0.01; the zero-padded rows
-// (z = 0 exactly) carry a zero cotangent, so the two agree.  Built by nf_sign_mask16 (nf_mfma.h), one
+// Slope masks of the hidden pre-activations (bit r set <=> NOT z[r] > 0, i.e. the leaky-ReLU slope is
+// 0.01, as in the oracle's ifelse(x > 0, x, 0.01x)): all the reverse pass needs of a1/a2 besides their
+// LDS copies, so the activations themselves can die early.  leakyrelu keeps the sign and the zero, so
+// the mask is taken from the post-activation value.  z = +-0 counts as slope 0.01: a real unit reaches
+// +0 with zero weights and bias, or at a fresh flow on a conditioner half of exactly 0 (the zero-padded
+// rows also do, with a zero cotangent).  Built by nf_sign_mask16 (nf_mfma.h), one subtraction and one
 // v_alignbit per element.  (Note for maintainers: __builtin_bit_cast applied directly to a
 // vector-element expression such as v[b][r] reads element 0 under hipcc 7.2 -- copy to a scalar first.)
 template <int NB>
@@ -2309,6 +2375,33 @@ static int launch_apply(nf_ctx *ctx, const CouplingArgs &a, const float *x, floa
               : launch_apply_v<G, INV, false>(ctx, a, x, y, ladj, accumulate);
 }
 
+// in place, on the six-term products: what the whole-chain launch of the same flow computes for this coupling
+template <class G>
+static int launch_apply_b6(nf_ctx *ctx, const nf_flow_desc *desc, int k, bool inverse, const CouplingArgs &a, float *xy, float *ladj,
+                           int accumulate) {
+  using BG = B6Geo<G>;
+  const size_t lds = 2 * (size_t)BG::BYTES;
+  static AttrOnce attr_once;  // once per device: a context on another GPU needs its own
+  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
+    NF_HIP(hipFuncSetAttribute((const void *)k_affine_apply_b6<G, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    NF_HIP(hipFuncSetAttribute((const void *)k_affine_apply_b6<G, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return NF_OK;
+  }));
+  NF_TRY(b6_refresh<G>(ctx, desc));
+  const unsigned char *img6 = (const unsigned char *)ctx->wimg + b6_offset_bytes<G>(desc) + (size_t)(2 * k) * BG::BYTES;
+  const long ntiles = (a.N + NF_TILE - 1) / NF_TILE;
+  long grid = (ntiles + 7) / 8;
+  const long cap = 2L * ctx->num_cu;
+  if (grid > cap) grid = cap;
+  if (grid < 1) grid = 1;
+  ProfScope ps(ctx, "affine_apply");
+  if (inverse)
+    hipLaunchKernelGGL((k_affine_apply_b6<G, true>), dim3((unsigned)grid), dim3(512), lds, ctx->stream, a, img6, xy, ladj, accumulate);
+  else
+    hipLaunchKernelGGL((k_affine_apply_b6<G, false>), dim3((unsigned)grid), dim3(512), lds, ctx->stream, a, img6, xy, ladj, accumulate);
+  return (int)hipGetLastError();
+}
+
 int nf_affine_apply(nf_ctx *ctx, const nf_flow_desc *desc, int k, bool inverse, const float *theta, const float *x,
                     long N, float *y, float *ladj, int accumulate) {
   if (nf_deep_geo_id(desc)) {
@@ -2318,6 +2411,12 @@ int nf_affine_apply(nf_ctx *ctx, const nf_flow_desc *desc, int k, bool inverse, 
   CouplingArgs a;
   NF_TRY(make_args(ctx, desc, k, theta, N, &a));
   const int mb = blocks32(a.m > a.c ? a.m : a.c), h1b = blocks32(desc->hdims[0]), h2b = blocks32(desc->hdims[1]), cb = mb;
+  if (x == y && fwd_b6()) {  // the arithmetic nf_affine_chain uses for the whole flow (NF_FWD_FP32: the fp32 kernels below, as there)
+#define BODY_APPLY6 return launch_apply_b6<G>(ctx, desc, k, inverse, a, y, ladj, accumulate);
+    NF_GEO_DISPATCH(1, 1, 1, 1, BODY_APPLY6)
+    NF_GEO_DISPATCH(1, 2, 2, 1, BODY_APPLY6)
+#undef BODY_APPLY6
+  }
 #define BODY_APPLY                                                              \
   return inverse ? launch_apply<G, true>(ctx, a, x, y, ladj, accumulate)        \
                  : launch_apply<G, false>(ctx, a, x, y, ladj, accumulate);

@@ -205,6 +205,8 @@ __global__ __launch_bounds__(512) void k_deep_chain(DeepChainArgs a, float *xt, 
       const bool odd_mask = (k & 1) == 0;  // flat coupling k even: mask 1:2:d, transformed half = E
       const int c = odd_mask ? c_odd : c_even;
       f32x16 S[1], T[1];
+      float lk = 0.f;  // this coupling's log-determinant, folded on its own: a chain of single-coupling launches (k_only) then
+                       // adds up to the whole chain's ladj bit for bit
       if (odd_mask) {
         deep_forward<G>(lds, O, S, l31, hi);
         deep_forward<G>(lds + G::SIZE, O, T, l31, hi);
@@ -220,8 +222,10 @@ __global__ __launch_bounds__(512) void k_deep_chain(DeepChainArgs a, float *xt, 
         const float o = INVERSE ? (v - T[0][r]) * nf_exp(-sv) : v * nf_exp(sv) + T[0][r];
         const bool ok = p < c;
         if (odd_mask) E[0][r] = ok ? o : v; else O[0][r] = ok ? o : v;
-        lsum += ok ? sv : 0.f;
+        lk += ok ? sv : 0.f;
       }
+      lk += __shfl_xor(lk, 32);
+      lsum += lk;
     }
     if (live) {
 #pragma unroll
@@ -229,7 +233,6 @@ __global__ __launch_bounds__(512) void k_deep_chain(DeepChainArgs a, float *xt, 
         tile_store(io, tile_soff(0, r, 0), E[0][r]);
         tile_store(io, tile_soff(0, r, 1), O[0][r]);
       }
-      lsum += __shfl_xor(lsum, 32);
       if (hi == 0 && valid) {
         const float base = a.accumulate ? ladj[j] : 0.f;
         ladj[j] = INVERSE ? base - lsum : base + lsum;

@@ -82,14 +82,20 @@ __device__ __forceinline__ float nf_tanh(float x) {
   return xc * nf_fdiv(n, d);
 }
 
-// Leaky-ReLU sign masks: one v_alignbit per element shifts the sign bit of v[r] into the mask, so
-// element r ends up at bit 15 - r.  leakyrelu keeps the sign, so the mask may be taken from the
-// post-activation value.  The empty asm pins the computation where it is written (hipcc otherwise
-// sinks it to the mask's first use and keeps the 16 activations alive until then).
+// Leaky-ReLU slope masks: bit 15 - r is set <=> NOT v[r] > 0, i.e. element r differentiates with slope 0.01 -- the
+// reference's ifelse(x > 0, x, 0.01x), +0 and -0 included (nf_generic64.hip and nf_g64m.h: `> 0.f ? 1.f : 0.01f`).  The
+// sign bit of v[r] itself would put +0 on slope 1: a unit whose weights and bias are zero, or any unit of a fresh flow
+// (all biases 0) on a conditioner half of exactly 0, then gets db and dW rows 100 x the reference's.  0 - v has its sign
+// bit set exactly when v > 0 (0 - (+-0) = +0 under round-to-nearest; not foldable to a negation, which would give -0), so
+// one subtraction and one v_alignbit per element shift "v > 0" into the word and one xor per block inverts it.  leakyrelu
+// keeps the sign and the zero, so the mask may be taken from the post-activation value.  The empty asm pins the
+// computation where it is written (hipcc otherwise sinks it to the mask's first use and keeps the 16 activations alive
+// until then).  (One caller keeps the sign-bit rule for its cost: stash_mask16 in nf_coupling.hip.)
 __device__ __forceinline__ unsigned nf_sign_mask16(const f32x16 &v) {
-  unsigned bits = 0;
+  unsigned pos = 0;
 #pragma unroll
-  for (int r = 0; r < 16; ++r) bits = __builtin_amdgcn_alignbit(bits, (unsigned)__float_as_int(v[r]), 31);
+  for (int r = 0; r < 16; ++r) pos = __builtin_amdgcn_alignbit(pos, (unsigned)__float_as_int(0.f - v[r]), 31);
+  unsigned bits = pos ^ 0xFFFFu;
   asm volatile("" : "+v"(bits));
   return bits;
 }

@@ -33,6 +33,7 @@ import pytest
 
 import nf_oracle as o
 import parity as P
+from gradient_floors import min_abs_preact
 from __graft_entry__ import load_package
 
 torch = pytest.importorskip("torch")
@@ -90,18 +91,6 @@ def make_flow(nf, d, seed=3):
 
 
 KINK_MARGIN = 1e-5
-
-
-def min_abs_preact(spec, th, xs):
-    """per sample, the smallest |pre-activation| of any leaky-ReLU unit in the oracle's forward pass"""
-    _, _, states = o.flow_fwd(spec, th, xs, keep=True)
-    out = np.full(xs.shape[1], np.inf)
-    for li, x in zip(reversed(o.layers_flat_order(spec)), states):
-        for net in li.nets:
-            _, acts = o.mlp_forward(th, net, x[li.idx_c], None, keep=True)
-            for a in acts[1:-1]:  # a = leakyrelu(z): z = a for a > 0, a / 0.01 otherwise
-                out = np.minimum(out, np.abs(np.where(a > 0, a, a / 0.01)).min(axis=0))
-    return out
 
 
 def make_target(nf, d):

@@ -14,6 +14,7 @@ import pytest
 
 import nf_oracle as o
 import parity as P
+from gradient_floors import fp32_recompute_kink_floor, recompute_bound
 from __graft_entry__ import ROOT, load_package
 
 torch = pytest.importorskip("torch")
@@ -1345,53 +1346,6 @@ def test_heterogeneous_create_flow(nf, dtn, general_base):
     P.gradient(f"{tag}: forward-KL grad", gf, gfo, P.F64_GRAD if f64 else P.GRAD_RTOL, None if f64 else fl[1])
     trained, stats, st = nf.train_flow(nf.loglikelihood, flow, ys, max_iters=5, optimiser=nf.Adam(1e-3))
     assert isinstance(trained, nf.CompositeFlow) and stats[-1]["loss"] < stats[0]["loss"] and st.t == 5
-
-
-def fp32_recompute_floor(spec, th64, otgt, xs64, jitter_seed=None):
-    """The float32 oracle's gradient with every layer input RECONSTRUCTED by inverting the chain from its output in
-    float32 -- what an invertible-recompute reverse pass (k_affine_bwd_all) differentiates.  Its distance from the float64
-    gradient grows with depth like the float32 round-trip error of the flow; the stashed pass does not have that term.
-    `jitter_seed`: the forward's output moved by N(0, 2^-24) relative first -- a forward that rounds its last bit
-    differently (another summation order, fp32 MFMA chain vs six-term bf16 product, truncating vs rounding split)."""
-    th32, xs32 = P.f32(th64, xs64)
-    t32 = P.f32(otgt)
-    n = xs32.shape[1]
-    y32, _ = o.flow_fwd(spec, th32, xs32)
-    if jitter_seed is not None:
-        z = np.random.default_rng(jitter_seed).standard_normal(y32.shape).astype(np.float32)
-        y32 = (y32 * (np.float32(1) + np.float32(2.0 ** -24) * z)).astype(np.float32)
-    order = list(reversed(o.layers_flat_order(spec)))
-    rec, cur = [None] * (len(order) + 1), y32
-    rec[len(order)] = y32
-    for i in range(len(order) - 1, -1, -1):
-        cur, _ = o._layer_inv(spec, th32, order[i], cur)
-        rec[i] = cur
-    ybar = (-o.target_grad(t32, y32) / n).astype(np.float32)
-    lbar = np.full(n, -1.0 / n, dtype=np.float32)
-    return o.flow_bwd(spec, th32, rec, ybar, lbar)[1]
-
-
-def fp32_recompute_kink_floor(spec, th64, otgt, xs64, gref, nseeds=12):
-    """Worst gradient error (max abs / |g|inf) of the float32 reconstruct-by-inversion oracle over `nseeds` last-bit jitters
-    of the forward output.  The error of an invertible-recompute reverse pass is not a smooth function of the forward's
-    rounding: a hidden unit within the reconstruction error (2e-5 ... 9e-5) of its leaky-ReLU kink takes the other slope,
-    a jump of |delta a| / n per (sample, unit).  On the d = 64, 8-coupling case below the SAME numpy code lands on 1e-6,
-    2.2e-4 or 9e-3 of |g|inf depending on the jitter seed (measured, round 5) -- the device's own roundings pick one of those
-    outcomes, which one changes with every change of the forward's arithmetic (round 4's truncating split: 3.3e-4; round
-    5's rounding split: 3.0e-3; fp32 MFMAs: 3.1e-4).  So the recompute tests bound the device by this measured
-    distribution instead of a constant."""
-    scale = float(np.abs(gref).max())
-    errs = [float(np.abs(fp32_recompute_floor(spec, th64, otgt, xs64, s) - gref).max() / scale) for s in [None] + list(range(nseeds))]
-    return max(errs), errs[0]
-
-
-KINK_CAP = 1e-2  # no jitter outlier may license more than this (ADVICE r5): a recompute gradient off by > 1 % of |g|inf is wrong
-
-
-def recompute_bound(kink):
-    """The asserted bound of an invertible-recompute gradient: the stated tolerance, or CFLOOR x the measured kink floor, but
-    never more than KINK_CAP of |g|inf."""
-    return max(P.GRAD_RTOL, min(P.CFLOOR * kink, KINK_CAP))
 
 
 @pytest.mark.parametrize("shape", ["d64_h64", "d20_h32", "d63_h40x64"])

@@ -59,6 +59,9 @@ const NF_TARGET_GLM_LOGIT, NF_TARGET_GLM_PROBIT, NF_TARGET_GLM_POISSON, NF_TARGE
     Int32(9), Int32(10), Int32(11), Int32(12), Int32(13)
 const NF_TARGET_HGLM_OFFSET = Int32(7)                                # hierarchical GLM kinds 16..20 = the GLM kind + 7 (nfhip.h)
 const NF_TARGET_SOFTMAX = Int32(15)                                  # softmax regression (nfhip.h; kind 14 is unassigned)
+# one-hidden-layer Bayesian neural-network targets (nfhip.h): the GLM kind + 13; kind 21 is unassigned
+const NF_TARGET_BNN_LOGIT, NF_TARGET_BNN_PROBIT, NF_TARGET_BNN_POISSON, NF_TARGET_BNN_STUDENT, NF_TARGET_BNN_NORMAL =
+    Int32(22), Int32(23), Int32(24), Int32(25), Int32(26)
 dtype_code(::Type{Float32}) = Int32(0)
 dtype_code(::Type{Float64}) = Int32(1)
 
@@ -351,6 +354,45 @@ c_target(t::SoftmaxTarget) = NFTarget(NF_TARGET_SOFTMAX, devptr(t.p0), devptr(t.
 function check_target(t::SoftmaxTarget, ::Type{T}, d) where {T}
     (eltype(t.Xt) === T && eltype(t.p0) === T && t.C * size(t.Xt, 1) == d && length(t.p0) == 2 * size(t.Xt, 2) + 2) ||
         error("nfhip: target must hold $(t.C) classes of $(d ÷ t.C)-dimensional data rows in $T")
+end
+# One-hidden-layer Bayesian neural network over z = [w_1; …; w_H; v; c] (hidden-unit-major: w_k the p input weights of unit k, v the
+# H output weights, c the output bias; d = H (p + 1) + 1):
+#   a_ik = tanh(x_i·w_k),  f_i = c + Σ_k v_k a_ik,  u_i = scale_i f_i + offset_i,
+#   log p(z) = const + Σ_i wt_i φ(u_i; param) + Σ_k log N(w_k; 0, σh² I) + log N([v; c]; 0, σo² I),  φ the GLM families'.
+# scale and offset carry the likelihood (labels ±1 in scale for :logit / :probit, 1/σ and −t/σ for Gaussian or Student noise,
+# log-exposures in offset for :poisson).  The device reads X row-major (the column-major p × rows array `Xt`) and ONE buffer
+# p0 = scl[rows] | off[rows] | wt[rows] | (param, const + both normalisers, 1/σh², 1/σo²).  σ = Inf is the flat prior.  Same flows
+# as the softmax target.  (Written without a Julia at hand: unrun.)
+struct BNNTarget{V<:ROCVector,M<:ROCMatrix} <: NFHipTarget
+    kind::Int32
+    Xt::M            # p × rows
+    p0::V            # 3 rows + 4
+    H::Int
+end
+const BNN_KINDS = Dict(:logit => NF_TARGET_BNN_LOGIT, :probit => NF_TARGET_BNN_PROBIT, :poisson => NF_TARGET_BNN_POISSON,
+                       :student => NF_TARGET_BNN_STUDENT, :normal => NF_TARGET_BNN_NORMAL)
+function BNNTarget(family::Symbol, X::AbstractMatrix{T}, H::Integer; scale=nothing, offset=nothing, weights=nothing, constant::Real=0.0,
+                   param::Real=0.0, σhidden::Real=1.0, σout::Real=1.0) where {T}
+    haskey(GLM_KINDS, family) || error("nfhip: family must be one of $(sort(collect(keys(GLM_KINDS))))")
+    rows, p = size(X)
+    (rows >= 1 && p >= 1 && all(isfinite, X)) || error("nfhip: X must be a finite rows × p matrix")
+    (1 <= H <= 16 && p <= 128 && H * (p + 1) + 1 <= 256) || error("nfhip: 1 <= H <= 16 hidden units, p <= 128 and H (p + 1) + 1 <= 256")
+    scl = scale === nothing ? ones(Float64, rows) : Float64.(scale)
+    off = offset === nothing ? zeros(Float64, rows) : Float64.(offset)
+    wt = weights === nothing ? ones(Float64, rows) : Float64.(weights)
+    (length(scl) == rows && length(off) == rows && length(wt) == rows) || error("nfhip: scale, offset and weights have one entry per row")
+    (all(isfinite, scl) && all(isfinite, off) && all(w -> isfinite(w) && w >= 0, wt)) || error("nfhip: scales and offsets must be finite, weights finite and >= 0")
+    (isfinite(constant) && isfinite(param) && (family !== :student || param > 0)) || error("nfhip: constant and param must be finite, ν > 0")
+    (σhidden > 0 && !isnan(σhidden) && σout > 0 && !isnan(σout)) || error("nfhip: prior σ must be > 0 (Inf: flat prior)")
+    fold(σ, n) = isinf(σ) ? (0.0, 0.0) : (1 / σ^2, -0.5 * n * log(2π * σ^2))
+    (ph, ch), (po, co) = fold(σhidden, H * p), fold(σout, H + 1)
+    p0 = vcat(scl, off, wt, Float64[param, constant + ch + co, ph, po])
+    return BNNTarget(BNN_KINDS[family], ROCArray(Matrix{T}(transpose(X))), ROCArray(Vector{T}(p0)), Int(H))
+end
+c_target(t::BNNTarget) = NFTarget(t.kind, devptr(t.p0), devptr(t.Xt), Float64(size(t.Xt, 2)), Float64(t.H))
+function check_target(t::BNNTarget, ::Type{T}, d) where {T}
+    (eltype(t.Xt) === T && eltype(t.p0) === T && t.H * (size(t.Xt, 1) + 1) + 1 == d && length(t.p0) == 3 * size(t.Xt, 2) + 4) ||
+        error("nfhip: target must hold $(t.H) hidden units over $(size(t.Xt, 1))-dimensional data rows in $T")
 end
 # Hierarchical GLM over z = [β (p coefficients) ; τ (G group log-scales)], d = p + G, centred parameterisation:
 #   log p(z) = const + Σ_i wt_i φ(u_i; param) + lin·β + Σ_j log N(β_j; 0, σ_j²) + Σ_g log p(τ_g),  u = Aβ + offset,

@@ -238,6 +238,36 @@ extern "C" {
 #define NF_TARGET_HGLM_POISSON 18
 #define NF_TARGET_HGLM_STUDENT 19
 #define NF_TARGET_HGLM_NORMAL 20
+/* One-hidden-layer Bayesian neural-network targets: the posterior of a tanh network with H hidden units over its weights, under
+ * the five GLM row functions.  Kind = the GLM kind + 13; kind 21 stays unassigned (as kinds 7 and 14 do).
+ *   y in R^d, d = H (p + 1) + 1, hidden-unit-major: y = [w_0; ...; w_{H-1}; v; c] -- w_k in R^p the input weights of unit k, v in R^H
+ *   the output weights, c the output bias.  A hidden bias is a ones column of X.
+ *       a_{ik}   = tanh(x_i . w_k)        f_i = c + sum_k v_k a_{ik}        u_i = scl_i f_i + off_i
+ *       log p(y) = par[1] + sum_i wt_i phi(u_i; par[0]) - par[2]/2 sum_k |w_k|^2 - par[3]/2 (|v|^2 + c^2)
+ *       g_i      = wt_i phi'(u_i; par[0]) scl_i                              (0 exactly when wt_i = 0)
+ *       d c      = sum_i g_i - par[3] c
+ *       d v_k    = sum_i g_i a_{ik} - par[3] v_k
+ *       d w_k    = sum_i g_i v_k (1 - a_{ik}^2) x_i - par[2] w_k
+ *   p1 = X[rows x p] row-major;  p0 = ONE buffer of 3 rows + 4 elements: scl[rows] | off[rows] | wt[rows] | par[4], with par[0]
+ *   the family parameter (nu > 0 for STUDENT, ignored by the others), par[1] the additive constant the host folded, par[2] the
+ *   prior precision of the hidden weights and par[3] that of [v; c] (0: flat);  s0 = rows (an integer value, 1 <= rows < 2^31);
+ *   s1 = H (an integer value, 1 <= H <= 16).  All device pointers are in the flow's element type.  scl and off carry the
+ *   likelihood: labels +-1 in scl for LOGIT / PROBIT, scl = 1 / sigma and off = -t_i / sigma for Gaussian or Student noise,
+ *   log-exposures in off for POISSON.
+ *   NF_ERR_ARG for a NULL p0 / p1, a bad s0, a non-integral, NaN or out-of-range s1, d < H + 2 or (d - 1) % H != 0 (so that
+ *   p = (d - 1) / H - 1 >= 1), then NF_ERR_UNSUPPORTED for d > 256 or p > 128 -- both before any device work.
+ * A row with wt_i == 0 contributes exactly 0 to the value and to every gradient by select, wherever its values enter a sum: a
+ * zero-weight row of huge finite features, or one whose phi overflows, changes no bit.  tanh saturates to exactly +-1 with
+ * derivative exactly 0; nothing is clamped: a non-finite value is reported by nf_elbo_step as NF_ERR_NONFINITE.  Served exactly
+ * like NF_TARGET_SOFTMAX: nf_target_logp (d <= 256), RealNVP / NSF flows of either element type including the
+ * weight-streaming shapes, full-rank and preconditioned flows, general bases and compositions; nf_elbo_step runs the split
+ * sequence, nf_elbo_step_enqueue answers NF_ERR_UNSUPPORTED; planar, radial, mean-field and Hamiltonian flows answer
+ * NF_ERR_UNSUPPORTED at every ELBO entry point, a Hamiltonian score included. */
+#define NF_TARGET_BNN_LOGIT 22
+#define NF_TARGET_BNN_PROBIT 23
+#define NF_TARGET_BNN_POISSON 24
+#define NF_TARGET_BNN_STUDENT 25
+#define NF_TARGET_BNN_NORMAL 26
 
 #define NF_MAX_HIDDEN 4
 

@@ -29,6 +29,10 @@ NF_TARGET_SOFTMAX = 15
 # hierarchical GLM targets (the GLM kind + 7): y = [beta (p) ; tau (G)], d = p + G; p1 = A[rows, d]; p0 = one buffer
 # lin[d] | off[rows] | wt[rows] | par[2] | grp[p] | isd[p] | hm[G] | his[G] | hk[G] | gptr[G + 1] | gidx[p]; s0 = rows; s1 = G
 NF_TARGET_HGLM_LOGIT, NF_TARGET_HGLM_PROBIT, NF_TARGET_HGLM_POISSON, NF_TARGET_HGLM_STUDENT, NF_TARGET_HGLM_NORMAL = 16, 17, 18, 19, 20
+# one-hidden-layer Bayesian neural-network targets (the GLM kind + 13): y = [w_0; ..; w_{H-1}; v (H); c], d = H (p + 1) + 1;
+# p1 = X[rows, p]; p0 = one buffer scl[rows] | off[rows] | wt[rows] | par[4] (par[0] = family parameter, par[1] = folded constant,
+# par[2] / par[3] = prior precisions of the hidden weights and of [v; c]); s0 = rows; s1 = H (1..16).  (kind 21 is unassigned)
+NF_TARGET_BNN_LOGIT, NF_TARGET_BNN_PROBIT, NF_TARGET_BNN_POISSON, NF_TARGET_BNN_STUDENT, NF_TARGET_BNN_NORMAL = 22, 23, 24, 25, 26
 NF_MAX_HIDDEN = 4
 NF_ERR_NONFINITE = -4
 

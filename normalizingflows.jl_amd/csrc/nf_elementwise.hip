@@ -640,6 +640,15 @@ int nf_target_check(const nf_target *t, int d) {
     case NF_TARGET_HGLM_NORMAL:  // s0 = the number of rows, as for LOGREG; s1 = the number of group log-scales G, an integer in 0..d-1 (NaN fails s1 >= 0)
       return (t->p0 && t->p1 && t->s0 >= 1 && t->s0 < 2147483648.0 && t->s0 == (double)(long)t->s0 && t->s1 >= 0 &&
               t->s1 <= (double)(d - 1) && t->s1 == (double)(int)t->s1) ? NF_OK : NF_ERR_ARG;
+    case NF_TARGET_BNN_LOGIT:
+    case NF_TARGET_BNN_PROBIT:
+    case NF_TARGET_BNN_POISSON:
+    case NF_TARGET_BNN_STUDENT:
+    case NF_TARGET_BNN_NORMAL:  // s0 = the number of rows, as for LOGREG; s1 = the number of hidden units H, an integer in 1..16 with d = H (p + 1) + 1, p >= 1 (NaN fails s1 >= 1)
+      if (!(t->p0 && t->p1 && t->s0 >= 1 && t->s0 < 2147483648.0 && t->s0 == (double)(long)t->s0 && t->s1 >= 1 && t->s1 <= 16 &&
+            t->s1 == (double)(int)t->s1 && d >= (int)t->s1 + 2 && (d - 1) % (int)t->s1 == 0))
+        return NF_ERR_ARG;
+      return (d > 256 || (d - 1) / (int)t->s1 - 1 > 128) ? NF_ERR_UNSUPPORTED : NF_OK;  // what no kernel of nf_bnn.hip serves: answered here, before any device work
     default: return NF_ERR_ARG;
   }
 }
@@ -664,6 +673,11 @@ int nf_launch_target_softmax(nf_ctx *, int dtype, const nf_target *, int d, long
                              double pscale);
 int nf_launch_target_softmax_tiled(nf_ctx *, const nf_target *, int d, long N, const float *yt, const float *logq,
                                    const float *ladj, float *gt, double gscale, float *elbos_out, double *partial, double pscale);
+// nf_bnn.hip: the one-hidden-layer Bayesian neural-network targets, the same contract
+int nf_launch_target_bnn(nf_ctx *, int dtype, const nf_target *, int d, long N, const void *y, const void *logq, const void *ladj,
+                         void *logp_out, void *grad_out, double gscale, void *elbos_out, double *partial, double pscale);
+int nf_launch_target_bnn_tiled(nf_ctx *, const nf_target *, int d, long N, const float *yt, const float *logq, const float *ladj,
+                               float *gt, double gscale, float *elbos_out, double *partial, double pscale);
 
 int nf_launch_target(nf_ctx *ctx, int dtype, const nf_target *t, int d, long N, const void *y, const void *logq,
                      const void *ladj, void *logp_out, void *grad_out, double gscale, void *elbos_out, double *partial,
@@ -676,6 +690,8 @@ int nf_launch_target(nf_ctx *ctx, int dtype, const nf_target *t, int d, long N, 
       return nf_launch_target_mixture(ctx, dtype, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
     if (t->kind == NF_TARGET_SOFTMAX)
       return nf_launch_target_softmax(ctx, dtype, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
+    if (target_is_bnn(t->kind))
+      return nf_launch_target_bnn(ctx, dtype, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
     return nf_launch_target_linpred(ctx, dtype, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
   }
   ProfScope ps(ctx, "target");
@@ -798,6 +814,8 @@ int nf_launch_target_tiled(nf_ctx *ctx, const nf_target *t, int d, long N, const
     return nf_launch_target_mixture_tiled(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
   if (t->kind == NF_TARGET_SOFTMAX)
     return nf_launch_target_softmax_tiled(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
+  if (target_is_bnn(t->kind))
+    return nf_launch_target_bnn_tiled(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
   if (target_is_linpred(t->kind))
     return nf_launch_target_linpred_tiled(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
   ProfScope ps(ctx, "target");

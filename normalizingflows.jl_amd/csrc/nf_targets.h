@@ -137,8 +137,11 @@ __host__ __device__ inline bool target_is_linpred(int kind) {
 // nf_launch_target / nf_launch_target_tiled, refused wherever target_term would have to evaluate it.
 // So is the softmax regression target (NF_TARGET_SOFTMAX, nf_softmax.hip): C predictors per data row, coupled through a
 // log-sum-exp, which the one-function-per-row form of the linear-predictor kernels cannot express.
+// So are the one-hidden-layer Bayesian neural-network kinds (NF_TARGET_BNN_LOGIT .. NF_TARGET_BNN_NORMAL = the GLM kind + 13,
+// nf_bnn.hip): some coordinates of y are per-sample scalars (the output weights and bias), not rows of a matrix product.
+__host__ __device__ inline bool target_is_bnn(int kind) { return kind >= NF_TARGET_BNN_LOGIT && kind <= NF_TARGET_BNN_NORMAL; }
 __host__ __device__ inline bool target_has_own_kernel(int kind) {
-  return target_is_linpred(kind) || kind == NF_TARGET_GAUSSMIX || kind == NF_TARGET_SOFTMAX;
+  return target_is_linpred(kind) || kind == NF_TARGET_GAUSSMIX || kind == NF_TARGET_SOFTMAX || target_is_bnn(kind);
 }
 // widest flow the mixture's tiled kernel serves (two U and two G blocks in registers); the flat kernel goes to 256
 #define NF_MIXTURE_TILED_MAXD 64

@@ -1138,6 +1138,124 @@ class MultinomialRegressionTarget(SoftmaxRegressionTarget):
         super().__init__(X.detach()[i_idx.to(X.device)], to(c_idx.to(torch.float64)), C_, to(k[i_idx, c_idx] * w[i_idx]), prior_sigma, const, _name=nm)
 
 
+_BNN_KINDS = {"logit": _lib.NF_TARGET_BNN_LOGIT, "probit": _lib.NF_TARGET_BNN_PROBIT, "poisson": _lib.NF_TARGET_BNN_POISSON,
+              "student": _lib.NF_TARGET_BNN_STUDENT, "normal": _lib.NF_TARGET_BNN_NORMAL}
+
+
+class BNNTarget(_LinpredTarget):
+    """Posterior of a one-hidden-layer Bayesian neural network (NF_TARGET_BNN_*) over its weights, z = [w_0; ...; w_{H-1}; v; c]
+    (hidden-unit-major: w_k the p input weights of unit k, v the H output weights, c the output bias; d = H (p + 1) + 1):
+        a_ik = tanh(x_i . w_k),   f_i = c + sum_k v_k a_ik,   u_i = scale_i f_i + offset_i,
+        logp(z) = const + sum_i weights_i phi(u_i; param) + sum_k log N(w_k; 0, prior_sigma_hidden^2 I) + log N([v; c]; 0, prior_sigma_out^2 I)
+    family and phi are GLMTarget's.  X [rows, p] (a hidden bias is a ones column); scale, offset, weights (>= 0; 0 drops the row
+    exactly) per row, of X's element type and device.  scale and offset carry the likelihood: labels +-1 in scale for "logit" /
+    "probit", scale = 1 / sigma and offset = -t / sigma for Gaussian or Student noise, log-exposures in offset for "poisson".
+    prior_sigma_* = math.inf is the flat prior.  Both Gaussian normalisers and const are folded in float64; the device reads
+    `A` = X and ONE buffer `p0` = scale | offset | weights | (param, const, 1 / prior_sigma_hidden^2, 1 / prior_sigma_out^2),
+    both kept alive here."""
+
+    def __init__(self, family, X, n_hidden, scale=None, offset=None, weights=None, const=0.0, param=None, prior_sigma_hidden=1.0,
+                 prior_sigma_out=1.0, _name="BNNTarget"):
+        nm = _name
+        if family not in _BNN_KINDS:
+            raise NFHipError(f"{nm}: family must be one of {sorted(_BNN_KINDS)}")
+        _glm_matrix(nm, X)
+        rows, p = X.shape
+        H = n_hidden
+        if isinstance(H, float) and H == int(H):
+            H = int(H)
+        if isinstance(H, bool) or not hasattr(H, "__index__") or not 1 <= int(H) <= 16:
+            raise NFHipError(f"{nm}: n_hidden must be an integer in 1..16")
+        H = int(H)
+        if p > 128:
+            raise NFHipError(f"{nm}: p = {p} input features exceed the kernels' 128")
+        d = H * (p + 1) + 1
+        if d > 256:
+            raise NFHipError(f"{nm}: n_hidden * (p + 1) + 1 = {d} exceeds the kernels' d = 256")
+        scl = _glm_vector(nm, "scale", scale, X, rows, 1.0)
+        off = _glm_vector(nm, "offset", offset, X, rows, 0.0)
+        wt = _glm_vector(nm, "weights", weights, X, rows, 1.0, nonneg=True)
+        const = _glm_scalar(nm, "const", const, positive=False)
+        if param is None:
+            if family == "student":
+                raise NFHipError(f"{nm}: the student family needs param = nu > 0")
+            param = 0.0
+        param = _glm_scalar(nm, "param", param, positive=family == "student")
+        self.prior_sigma_hidden = _glm_scalar(nm, "prior_sigma_hidden", prior_sigma_hidden, allow_inf=True)
+        self.prior_sigma_out = _glm_scalar(nm, "prior_sigma_out", prior_sigma_out, allow_inf=True)
+        c = const
+        prec = []
+        for sigma, count in ((self.prior_sigma_hidden, H * p), (self.prior_sigma_out, H + 1)):
+            flat = math.isinf(sigma)
+            prec.append(0.0 if flat else 1.0 / sigma**2)
+            c += 0.0 if flat else -0.5 * count * math.log(2.0 * math.pi * sigma**2)
+        self.family, self.d, self.p, self.n_hidden, self.rows, self.param, self.const = family, d, p, H, rows, param, c
+        self.precision_hidden, self.precision_out = prec
+        self.A = X.detach().contiguous()
+        self.X = self.A
+        self.p0 = torch.cat([scl, off, wt, torch.tensor([param, c, prec[0], prec[1]], dtype=torch.float64)]).to(X.dtype).to(X.device).contiguous()
+        self.c = Target(_BNN_KINDS[family], self.p0.data_ptr(), self.A.data_ptr(), float(rows), float(H))
+
+    def unpack(self, y):
+        """(W [p, H], v [H], c) of a parameter vector y (d,) -- or (W [p, H, N], v [H, N], c [N]) of a batch (d, N)"""
+        if y.shape[0] != self.d:
+            raise NFHipError(f"BNNTarget.unpack: expected {self.d} leading elements, got {y.shape[0]}")
+        H, p = self.n_hidden, self.p
+        W = y[:H * p].reshape(H, p, *y.shape[1:]).transpose(0, 1)
+        return W, y[H * p:H * p + H], y[self.d - 1]
+
+    def predict(self, y, Xnew):
+        """the network's output f = c + tanh(Xnew W) v in plain torch: [rows] for a vector y, [rows, N] for a batch (d, N)"""
+        if Xnew.dim() != 2 or Xnew.shape[1] != self.p:
+            raise NFHipError(f"BNNTarget.predict: Xnew must be a matrix [rows, {self.p}]")
+        W, v, c = self.unpack(y)
+        if y.dim() == 1:
+            return torch.tanh(Xnew @ W) @ v + c
+        return torch.einsum("ikn,kn->in", torch.tanh(torch.einsum("if,fkn->ikn", Xnew, W)), v) + c.unsqueeze(0)
+
+
+class BNNRegressionTarget(BNNTarget):
+    """Posterior of a one-hidden-layer network regressing t on X: t_i ~ N(f_i, noise_sigma^2), or (t_i - f_i) / noise_sigma ~ t_nu
+    when `nu` is given.  Folds to the "normal" / "student" family with scale = 1 / noise_sigma, offset = -t / noise_sigma and the
+    noise normaliser sum_i w_i (...) in the constant."""
+
+    def __init__(self, X, t, n_hidden, noise_sigma=1.0, nu=None, weights=None, prior_sigma_hidden=1.0, prior_sigma_out=1.0):
+        nm = "BNNRegressionTarget"
+        _glm_matrix(nm, X)
+        n = X.shape[0]
+        tv = _glm_vector(nm, "t", t, X, n)
+        sn = _glm_scalar(nm, "noise_sigma", noise_sigma)
+        w = _glm_vector(nm, "weights", weights, X, n, 1.0, nonneg=True)
+        if nu is None:
+            family, param = "normal", None
+            const = float(w.sum()) * (-0.5 * math.log(2.0 * math.pi) - math.log(sn))
+        else:
+            family, param = "student", _glm_scalar(nm, "nu", nu)
+            const = float(w.sum()) * (math.lgamma(0.5 * (param + 1.0)) - math.lgamma(0.5 * param) - 0.5 * math.log(param * math.pi) - math.log(sn))
+        to = lambda x: x.to(X.dtype).to(X.device)
+        # f - t enters squared (or through u^2): scale = -1 / sigma would do as well; +1 / sigma keeps u = (f - t) / sigma
+        super().__init__(family, X, n_hidden, to(torch.full((n,), 1.0 / sn, dtype=torch.float64)), to(-tv / sn), to(w), const, param,
+                         prior_sigma_hidden, prior_sigma_out, _name=nm)
+
+
+class BNNClassifierTarget(BNNTarget):
+    """Posterior of a one-hidden-layer binary classifier: P(label_i = 1) = sigmoid(f_i) (link="logit") or Phi(f_i) ("probit"),
+    labels in {0, 1}.  The labels are folded into the rows' scale (+-1)."""
+
+    def __init__(self, X, labels, n_hidden, link="logit", weights=None, prior_sigma_hidden=1.0, prior_sigma_out=1.0):
+        nm = "BNNClassifierTarget"
+        if link not in ("logit", "probit"):
+            raise NFHipError(f"{nm}: link must be \"logit\" or \"probit\"")
+        _glm_matrix(nm, X)
+        n = X.shape[0]
+        lab = _glm_vector(nm, "labels", labels, X, n)
+        if not bool(((lab == 0) | (lab == 1)).all()):
+            raise NFHipError(f"{nm}: labels must be in {{0, 1}}")
+        w = _glm_vector(nm, "weights", weights, X, n, 1.0, nonneg=True)
+        to = lambda x: x.to(X.dtype).to(X.device)
+        super().__init__(link, X, n_hidden, to(2.0 * lab - 1.0), None, to(w), 0.0, None, prior_sigma_hidden, prior_sigma_out, _name=nm)
+
+
 def check_target(target, dtype, device=None, d=None):
     """Element-type / device / dimension agreement between a built-in target and the flow that will read it."""
     if isinstance(target, DiagGaussTarget):

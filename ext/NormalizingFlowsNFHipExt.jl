@@ -62,6 +62,9 @@ const NF_TARGET_SOFTMAX = Int32(15)                                  # softmax r
 # one-hidden-layer Bayesian neural-network targets (nfhip.h): the GLM kind + 13; kind 21 is unassigned
 const NF_TARGET_BNN_LOGIT, NF_TARGET_BNN_PROBIT, NF_TARGET_BNN_POISSON, NF_TARGET_BNN_STUDENT, NF_TARGET_BNN_NORMAL =
     Int32(22), Int32(23), Int32(24), Int32(25), Int32(26)
+# GLM targets with a learned dispersion (nfhip.h): y = [β ; τ ; λ]; kinds 27 and 28 are unassigned
+const NF_TARGET_DGLM_NORMAL, NF_TARGET_DGLM_STUDENT, NF_TARGET_DGLM_NEGBIN =
+    Int32(29), Int32(30), Int32(31)
 dtype_code(::Type{Float32}) = Int32(0)
 dtype_code(::Type{Float64}) = Int32(1)
 
@@ -467,6 +470,96 @@ c_target(t::HierarchicalGLMTarget) = NFTarget(t.kind, devptr(t.p0), devptr(t.At)
 function check_target(t::HierarchicalGLMTarget, ::Type{T}, d) where {T}
     (eltype(t.At) === T && eltype(t.p0) === T && size(t.At, 1) == d && length(t.p0) == 4 * d + 2 * size(t.At, 2) + 3 + t.G) ||
         error("nfhip: target must hold $d-dimensional data rows ($(d - t.G) coefficients and $(t.G) log-scales) in $T")
+end
+# GLM with a learned dispersion over z = [β (p) ; τ (G) ; λ], d = p + G + 1: HierarchicalGLMTarget's prior on (β, τ), and
+#   family :normal / :student  l_i = φ_fam(u_i e^{-λ}) − λ (σ = exp(λ));  :negbin  l_i = log NB(counts_i; mean exp(u_i), size exp(λ)),
+#   exp(λ) under disphyper ∈ (:lognormal, :halfnormal, :halfcauchy) with disploc / dispscale.  counts: integers in 0:4097, required for and
+#   only for :negbin.  Folded here in Float64 as the Python mirror does (zero-weight rows enter neither the table nor the folded sums):
+#   p0 = lin[d] | off[rows] | wt[rows] | (param, const, Mt, 0) | grp[p] | isd[p] | hm[G+1] | his[G+1] | hk[G+1] | gptr[G+1] | gidx[p] |
+#        cnt[rows] | ctab[Mt]   (cnt / ctab: :negbin only; ctab[m] = Σ_{i: k_i > m} wt_i, m = 1:Mt, Mt = max k − 1).
+# Same flows as the hierarchical targets.  (Written without a Julia at hand: unrun.)
+struct DispersionGLMTarget{V<:ROCVector,M<:ROCMatrix} <: NFHipTarget
+    kind::Int32
+    At::M            # d × rows
+    p0::V
+    G::Int
+end
+const DGLM_KINDS = Dict(:normal => NF_TARGET_DGLM_NORMAL, :student => NF_TARGET_DGLM_STUDENT, :negbin => NF_TARGET_DGLM_NEGBIN)
+function DispersionGLMTarget(family::Symbol, A::AbstractMatrix{T}; counts=nothing, groups=nothing, G::Integer=0, offset=nothing,
+                             weights=nothing, lin=nothing, constant::Real=0.0, param::Real=0.0, fixedσ=1.0, hyper=:halfcauchy,
+                             hyperloc=0.0, hyperscale=1.0, disphyper::Symbol=:halfcauchy, disploc::Real=0.0, dispscale::Real=1.0) where {T}
+    haskey(DGLM_KINDS, family) || error("nfhip: family must be one of $(sort(collect(keys(DGLM_KINDS))))")
+    rows, p = size(A)
+    (rows >= 1 && p >= 1 && all(isfinite, A)) || error("nfhip: A must be a finite rows × p matrix")
+    (G >= 0 && p + G + 1 <= 256) || error("nfhip: G >= 0 and p + G + 1 <= 256")
+    groups = groups === nothing ? zeros(Int, p) : groups
+    (length(groups) == p && all(g -> 0 <= g <= G, groups)) || error("nfhip: one group in 0:G per column (0: a fixed prior scale)")
+    ((family === :negbin) == (counts !== nothing)) || error("nfhip: counts are required for, and only for, :negbin")
+    d = p + G + 1
+    off = offset === nothing ? zeros(Float64, rows) : Float64.(offset)
+    wt = weights === nothing ? ones(Float64, rows) : Float64.(weights)
+    ln = lin === nothing ? zeros(Float64, p) : Float64.(lin)
+    (length(off) == rows && length(wt) == rows && length(ln) == p) || error("nfhip: offset and weights have one entry per row, lin one per column")
+    (all(isfinite, off) && all(isfinite, ln) && all(w -> isfinite(w) && w >= 0, wt)) || error("nfhip: offsets and lin must be finite, weights finite and >= 0")
+    (isfinite(constant) && isfinite(param) && (family !== :student || param > 0)) || error("nfhip: constant and param must be finite, ν > 0")
+    per(v, n) = v isa AbstractVector ? Float64.(v) : fill(Float64(v), n)
+    σ = per(fixedσ, p)
+    loc, scl = vcat(per(hyperloc, G), Float64(disploc)), vcat(per(hyperscale, G), Float64(dispscale))
+    hyp = vcat(hyper isa Symbol ? fill(hyper, G) : collect(hyper), disphyper)
+    (length(σ) == p && all(s -> s > 0 && !isnan(s), σ)) || error("nfhip: fixedσ must be > 0 (Inf: flat), a scalar or one per column")
+    (length(hyp) == G + 1 && all(h -> haskey(HYPER_KINDS, h), hyp)) || error("nfhip: hyper / disphyper must be one of $(sort(collect(keys(HYPER_KINDS))))")
+    (length(loc) == G + 1 && all(isfinite, loc) && all(s -> isfinite(s) && s > 0, scl)) || error("nfhip: locations finite, scales finite and > 0")
+    L2PI = log(2π)
+    c = Float64(constant)
+    isd = zeros(Float64, p)
+    lintl = zeros(Float64, G + 1)                                        # lin of [τ ; λ]
+    for j in 1:p
+        if groups[j] > 0
+            lintl[groups[j]] -= 1.0
+            c -= 0.5 * L2PI
+        elseif isfinite(σ[j])
+            isd[j] = 1 / σ[j]
+            c -= log(σ[j]) + 0.5 * L2PI
+        end
+    end
+    hm, his = zeros(Float64, G + 1), zeros(Float64, G + 1)
+    for g in 1:G+1
+        if hyp[g] === :lognormal
+            hm[g], his[g] = loc[g], 1 / scl[g]
+            c += -log(scl[g]) - 0.5 * L2PI
+        else
+            hm[g] = log(scl[g])
+            lintl[g] += 1.0
+            c += (hyp[g] === :halfnormal ? 0.5 : 1.0) * log(2 / π) - hm[g]
+        end
+    end
+    live = findall(>(0), wt)
+    tail, Mt = Float64[], 0
+    if family === :negbin
+        k = Float64.(counts)
+        (length(k) == rows && all(x -> isinteger(x) && 0 <= x <= 4097, k)) || error("nfhip: counts must be integers in 0:4097, one per row")
+        Mt = isempty(live) ? 0 : max(Int(maximum(k[live])) - 1, 0)
+        ctab = Float64[sum(wt[i] for i in live if k[i] > m; init=0.0) for m in 1:Mt]
+        logfact(x) = sum(log, 1:Int(x); init=0.0)
+        ln = ln .+ vec(transpose(wt[live] .* k[live]) * Float64.(A[live, :]))
+        c += sum(wt[i] * (k[i] * off[i] - logfact(k[i])) for i in live; init=0.0)
+        tail = vcat(k, ctab)
+    else
+        lintl[G+1] -= sum(wt[live]; init=0.0)
+    end
+    members = [findall(==(g), groups) for g in 1:G]                      # increasing column index
+    gptr = Float64.(vcat(0, cumsum(length.(members))))
+    gidx = zeros(Float64, p)
+    flat = reduce(vcat, members; init=Int[])
+    gidx[1:length(flat)] .= flat .- 1
+    p0 = vcat(ln, lintl, off, wt, Float64[param, c, Mt, 0.0], Float64.(groups .- 1), isd, hm, his, Float64[HYPER_KINDS[h] for h in hyp], gptr, gidx, tail)
+    At = vcat(Matrix{T}(transpose(A)), zeros(T, G + 1, rows))
+    return DispersionGLMTarget(DGLM_KINDS[family], ROCArray(At), ROCArray(Vector{T}(p0)), Int(G))
+end
+c_target(t::DispersionGLMTarget) = NFTarget(t.kind, devptr(t.p0), devptr(t.At), Float64(size(t.At, 2)), Float64(t.G))
+function check_target(t::DispersionGLMTarget, ::Type{T}, d) where {T}
+    (eltype(t.At) === T && eltype(t.p0) === T && size(t.At, 1) == d && length(t.p0) >= 4 * d + 2 * size(t.At, 2) + 5 + t.G) ||
+        error("nfhip: target must hold $d-dimensional data rows ($(d - t.G - 1) coefficients, $(t.G) log-scales and the log-dispersion) in $T")
 end
 c_target(t::DenseGaussTarget) = NFTarget(NF_TARGET_DENSEGAUSS, devptr(t.μ), devptr(t.Wt), t.logdetW, 0.0)
 c_target(t::LogRegTarget) = NFTarget(NF_TARGET_LOGREG, t.shift === nothing ? C_NULL : devptr(t.shift), devptr(t.At), Float64(size(t.At, 2)), t.σ)

@@ -268,6 +268,49 @@ extern "C" {
 #define NF_TARGET_BNN_POISSON 24
 #define NF_TARGET_BNN_STUDENT 25
 #define NF_TARGET_BNN_NORMAL 26
+/* GLM targets with a learned dispersion: Gaussian / Student-t regression with an unknown residual scale (the linear mixed
+ * model included) and negative-binomial regression with an unknown size.  The hierarchical kinds' sibling: there a log-scale
+ * coordinate multiplies the prior, here one multiplies the likelihood.  Kinds 27 and 28 stay unassigned (as 7, 14 and 21 do).
+ *   y in R^d is [beta (p) ; tau (G) ; lambda], d = p + G + 1, p >= 1, 0 <= G <= d - 2, d <= 256.  beta and tau are exactly the
+ *   hierarchical kinds' coefficients and group log-scales (their w_j, h_g and member lists, with p = d - G - 1); G = 0 gives
+ *   plain regressions with per-coefficient fixed prior scales.  lambda = y[d - 1] is the log-dispersion.
+ *       u        = A y + off                  (A is rows x d; the tau- and lambda-columns are usually zero but take part like any column)
+ *       log p(y) = par[1] + sum_i wt_i phi_i(u_i, lambda) + lin . y - sum_{j<p} beta_j^2 w_j(y) / 2 + sum_{g<G} h_g(tau_g - hm_g)
+ *                  + h_G(lambda - hm_G) + T(lambda)
+ *   h_G is one of the three hyper-prior forms applied to exp(lambda) (log-normal, half-normal, half-Cauchy, as a density over
+ *   lambda): entry G of hm / his / hk, with an empty member list.
+ *   NF_TARGET_DGLM_NORMAL / NF_TARGET_DGLM_STUDENT (scale families, sigma = exp(lambda)):
+ *       z = u exp(-lambda),   phi = phi_fam(z; par[0]) (-z^2 / 2 | -(nu + 1)/2 log1p(z^2 / nu)),
+ *       d phi / d u = exp(-lambda) phi'(z),   d phi / d lambda = -phi'(z) z,   T = 0;
+ *       the -(sum_i wt_i) lambda of the normalisers is linear in y: the host folds it into lin[d - 1].
+ *   NF_TARGET_DGLM_NEGBIN (counts k_i, integers; mean exp(u_i); size r = exp(lambda)):
+ *       phi_i = -(k_i + e^lambda) softplus(u_i - lambda),
+ *       d phi / d u = -(k_i + e^lambda) sigmoid(u_i - lambda),
+ *       d phi / d lambda = -e^lambda softplus(u_i - lambda) + (k_i + e^lambda) sigmoid(u_i - lambda),
+ *       T(lambda) = sum_{m=1}^{M-1} c_m log1p(m e^-lambda),   c_m = sum_{i: k_i > m} wt_i,   M = max k,
+ *       T'(lambda) = -sum_m c_m m / (e^lambda + m).
+ *     This is lgamma(k + r) - lgamma(r) + r log r - (k + r) log(r + e^u) rewritten so that no lgamma runs on the device and
+ *     nothing cancels as r -> inf, where the form tends to the Poisson kind's.  The host folds, in float64, sum_i wt_i k_i u_i
+ *     into lin and its offset part and -sum_i wt_i lgamma(k_i + 1) into par[1].  softplus and sigmoid are the exp(-|.|) forms
+ *     of the logit row function.
+ *   d lambda = [A' (wt o d phi / d u)]_{d-1} + lin_{d-1} + sum_i wt_i d phi_i / d lambda + h_G' + T'.
+ *   p1 = A[rows x d] row-major;  s0 = rows (an integer value, 1 <= rows < 2^31);  s1 = G (an integer value, 0 <= G <= d - 2);
+ *   p0 = ONE buffer in the flow's element type:
+ *       lin[d] | off[rows] | wt[rows] | par[4] | grp[p] | isd[p] | hm[G+1] | his[G+1] | hk[G+1] | gptr[G+1] | gidx[p] | cnt[rows] | ctab[Mt]
+ *   par[0] = nu for STUDENT, par[1] = the folded constant, par[2] = Mt, the table length (an integer value, NEGBIN only;
+ *   ctab[j] = c_{j+1}), par[3] = 0.  cnt (the counts) and ctab are absent for NORMAL and STUDENT.
+ *   NF_ERR_ARG for a NULL p0 / p1, a bad s0, or an s1 that is non-integral, NaN or outside 0 .. d - 2; NF_ERR_UNSUPPORTED for
+ *   d > 256 -- both before any device work.  The host cannot validate device memory: every index or length read from p0 is
+ *   bounded by select before it addresses anything (the hierarchical kinds' rule; Mt is clamped to [0, 4096]).
+ * A row with wt_i == 0 contributes exactly 0 to the value and to every gradient, d lambda included, by select (zero-weight rows
+ * never enter c_m: that is host work).  Nothing is clamped: a non-finite value is reported by nf_elbo_step as
+ * NF_ERR_NONFINITE.  Served exactly like NF_TARGET_HGLM_*: nf_target_logp (d <= 256), RealNVP / NSF flows of either element
+ * type including the weight-streaming shapes, full-rank and preconditioned flows, general bases and compositions;
+ * nf_elbo_step runs the split sequence, nf_elbo_step_enqueue answers NF_ERR_UNSUPPORTED; planar, radial, mean-field and
+ * Hamiltonian flows answer NF_ERR_UNSUPPORTED at every ELBO entry point, a Hamiltonian score included. */
+#define NF_TARGET_DGLM_NORMAL 29
+#define NF_TARGET_DGLM_STUDENT 30
+#define NF_TARGET_DGLM_NEGBIN 31
 
 #define NF_MAX_HIDDEN 4
 

@@ -33,6 +33,10 @@ NF_TARGET_HGLM_LOGIT, NF_TARGET_HGLM_PROBIT, NF_TARGET_HGLM_POISSON, NF_TARGET_H
 # p1 = X[rows, p]; p0 = one buffer scl[rows] | off[rows] | wt[rows] | par[4] (par[0] = family parameter, par[1] = folded constant,
 # par[2] / par[3] = prior precisions of the hidden weights and of [v; c]); s0 = rows; s1 = H (1..16).  (kind 21 is unassigned)
 NF_TARGET_BNN_LOGIT, NF_TARGET_BNN_PROBIT, NF_TARGET_BNN_POISSON, NF_TARGET_BNN_STUDENT, NF_TARGET_BNN_NORMAL = 22, 23, 24, 25, 26
+# GLM targets with a learned dispersion: y = [beta (p) ; tau (G) ; lambda], d = p + G + 1; p1 = A[rows, d]; p0 = one buffer
+# lin[d] | off[rows] | wt[rows] | par[4] | grp[p] | isd[p] | hm[G+1] | his[G+1] | hk[G+1] | gptr[G+1] | gidx[p] | cnt[rows] | ctab[Mt]
+# (cnt / ctab: NEGBIN only; par[2] = Mt); s0 = rows; s1 = G (0..d-2).  (kinds 27 and 28 are unassigned)
+NF_TARGET_DGLM_NORMAL, NF_TARGET_DGLM_STUDENT, NF_TARGET_DGLM_NEGBIN = 29, 30, 31
 NF_MAX_HIDDEN = 4
 NF_ERR_NONFINITE = -4
 

@@ -640,6 +640,13 @@ int nf_target_check(const nf_target *t, int d) {
     case NF_TARGET_HGLM_NORMAL:  // s0 = the number of rows, as for LOGREG; s1 = the number of group log-scales G, an integer in 0..d-1 (NaN fails s1 >= 0)
       return (t->p0 && t->p1 && t->s0 >= 1 && t->s0 < 2147483648.0 && t->s0 == (double)(long)t->s0 && t->s1 >= 0 &&
               t->s1 <= (double)(d - 1) && t->s1 == (double)(int)t->s1) ? NF_OK : NF_ERR_ARG;
+    case NF_TARGET_DGLM_NORMAL:
+    case NF_TARGET_DGLM_STUDENT:
+    case NF_TARGET_DGLM_NEGBIN:  // s0 = the number of rows, as for LOGREG; s1 = G, an integer in 0..d-2: at least one coefficient, and lambda = y[d-1] (NaN fails s1 >= 0)
+      if (!(t->p0 && t->p1 && t->s0 >= 1 && t->s0 < 2147483648.0 && t->s0 == (double)(long)t->s0 && t->s1 >= 0 &&
+            t->s1 <= (double)(d - 2) && t->s1 == (double)(int)t->s1))
+        return NF_ERR_ARG;
+      return d > 256 ? NF_ERR_UNSUPPORTED : NF_OK;  // what no kernel of nf_linpred.hip serves: answered here, before any device work
     case NF_TARGET_BNN_LOGIT:
     case NF_TARGET_BNN_PROBIT:
     case NF_TARGET_BNN_POISSON:

@@ -1,6 +1,6 @@
 // nf_linpred.h -- the row functions and the row data of the linear-predictor targets (nf_linpred.hip).
 //
-// A linear-predictor target is a sum of ONE scalar function over the rows of a matrix product plus a prior.  Three
+// A linear-predictor target is a sum of ONE scalar function over the rows of a matrix product plus a prior.  Four
 // forms share the kernels:
 //   centred (kinds 5, 6)   log p(y) = c + sum_i phi(u_i) - pw |y|^2 / 2,   u = A (y - mu),   grad = A' phi'(u) - pw y
 //     DENSEGAUSS  phi(u) = -u^2 / 2        c = -d/2 log(2 pi) + log|det W|     pw = 0           (A = W = inv(L))
@@ -14,8 +14,12 @@
 //   hierarchical (kinds 16..20, NF_TARGET_HGLM_* = the GLM kind + 7)
 //                          the generalised form over y = [beta (p) ; tau (G)] with the structured prior of HierRows below in
 //                          place of the isotropic one (c = pw = 0; s1 = G), its data behind par[2] in the same buffer.
+//   dispersion (kinds 29..31, NF_TARGET_DGLM_*)
+//                          the hierarchical form over y = [beta (p) ; tau (G) ; lambda] with a learned log-dispersion lambda =
+//                          y[d - 1] INSIDE the row function (DispScale / DispNegBin below): phi_i(u_i, lambda), a hyper-prior
+//                          h_G on exp(lambda) and, for the negative binomial, the table term T(lambda) (DispRows below).
 // A row function returns phi(u; par) and phi'(u; par) of ONE element; both target kernels are templated on it and on the
-// form (LP_CENTRED / LP_GLM / LP_HIER: the centred instantiations compile the row data away).  par is the family parameter par[0], read once per
+// form (LP_CENTRED / LP_GLM / LP_HIER / LP_DISP: the centred instantiations compile the row data away).  par is the family parameter par[0], read once per
 // launch (nu for STUDENT; the other families ignore it).  A row of weight 0 contributes exactly 0 by SELECT, whatever phi
 // returns there (a subsampling mask may sit over a row whose phi overflows); nothing is clamped.
 #pragma once
@@ -114,10 +118,11 @@ __device__ __forceinline__ void glm_weigh(T w, T &phi, T &dphi) {
   dphi = w == (T)0 ? (T)0 : w * dphi;
 }
 
-// The three forms of the two kernel bodies (their template argument FORM).
+// The four forms of the two kernel bodies (their template argument FORM).
 #define LP_CENTRED 0
 #define LP_GLM 1
 #define LP_HIER 2
+#define LP_DISP 3
 
 // The structured prior of the hierarchical form (NF_TARGET_HGLM_*): y = [beta (p) ; tau (G)], the prior data behind the row
 // data in the same buffer,   ... par[2] | grp[p] | isd[p] | hm[G] | his[G] | hk[G] | gptr[G + 1] | gidx[p].
@@ -135,6 +140,25 @@ struct HierRows {
     hk = his + G;
     gptr = hk + G;
     gidx = gptr + G + 1;
+  }
+  // The dispersion form's layout: y = [beta (p) ; tau (G) ; lambda], par[4], and hm / his / hk hold G + 1 entries (entry G is
+  // lambda's hyper-prior; it has no member list, so gptr keeps its G + 1 entries).
+  struct Disp {};
+  __device__ __forceinline__ HierRows(Disp, const T *p0, int d, int rows, int ng) : p(d - ng - 1), G(ng) {
+    grp = p0 + d + 2 * (long)rows + 4;
+    isd = grp + p;
+    hm = isd + p;
+    his = hm + G + 1;
+    hk = his + G + 1;
+    gptr = hk + G + 1;
+    gidx = gptr + G + 1;
+  }
+  template <int FORM>
+  static __device__ __forceinline__ HierRows of_form(const T *p0, int d, int rows, int ng) {
+    if constexpr (FORM == LP_DISP)
+      return HierRows(Disp{}, p0, d, rows, ng);
+    else
+      return HierRows(p0, d, rows, FORM == LP_HIER ? ng : 0);
   }
   // an integer-valued element as an index of [0, n), or -1 (NaN fails both comparisons)
   static __device__ __forceinline__ int index_in(T v, int n) { return (v >= (T)0 && v < (T)n) ? (int)v : -1; }
@@ -176,6 +200,100 @@ struct HierRows {
     val = hv;
     grad = ss * lp_exp((T)-2 * tau) + hd;
   }
+  // Hyper-prior entry g alone at the log-scale t: h_g(t - hm_g) and its derivative, the three forms of `scale` (the dispersion
+  // form's lambda, entry G, which has no member list).  `scale` keeps its own copy: routing it through this function changes
+  // the shipped hierarchical kernels' register allocation, and they keep their instruction streams.
+  __device__ __forceinline__ void hyper(int g, T t, T &hv, T &hd) const {
+    const T x = t - hm[g], kind = hk[g];
+    if (kind == (T)0) {
+      const T s = his[g], z = x * s;
+      hv = (T)-0.5 * z * z;
+      hd = -z * s;
+    } else if (kind == (T)1) {
+      const T e = lp_exp((T)2 * x);
+      hv = (T)-0.5 * e;
+      hd = -e;
+    } else {  // -softplus(2 x) = log sigmoid(-2 x) ; -2 sigmoid(2 x): the exp(-|.|) forms of the logit row function
+      T dp;
+      PhiLogSigmoid::eval((T)-2 * x, (T)0, hv, dp);
+      hd = (T)-2 * dp;
+    }
+  }
+};
+
+// The row functions of the dispersion form (NF_TARGET_DGLM_*).  lambda = y[d - 1] is a per-sample scalar: `Lane` holds what a
+// lane derives from it ONCE per tile (every row a lane evaluates belongs to one sample).  eval returns phi, d phi / d u and
+// d phi / d lambda of one row; k is the row's count (read only where COUNTS).
+//   DispScale<PHI>  z = u exp(-lambda):  phi_fam(z; par) ;  exp(-lambda) phi'(z) ;  -phi'(z) z      (NORMAL, STUDENT)
+//   DispNegBin      x = u - lambda, r = exp(lambda):  -(k + r) softplus(x) ;  -(k + r) sigmoid(x) ;  -r softplus(x) + (k + r) sigmoid(x)
+// softplus and sigmoid are the exp(-|x|) forms of PhiLogSigmoid (log sigmoid(-x) = -softplus(x)); exp(+-lambda) is the library's
+// exponential (once per lane per tile: its cost does not show, and the hardware one's error grows with |lambda|).  Nothing is clamped.
+template <class T>
+struct DispLane {
+  T lam, einv, el;  // lambda, exp(-lambda), exp(lambda)
+};
+template <class PHI>
+struct DispScale {
+  static constexpr bool COUNTS = false;
+  template <class T>
+  static __device__ __forceinline__ DispLane<T> lane(T lam) {
+    return {lam, lp_exp(-lam), (T)0};
+  }
+  template <class T>
+  static __device__ __forceinline__ void eval(T u, T, T par, const DispLane<T> &L, T &phi, T &du, T &dl) {
+    const T z = u * L.einv;
+    T dz;
+    PHI::eval(z, par, phi, dz);
+    du = L.einv * dz;
+    dl = -dz * z;
+  }
+};
+struct DispNegBin {
+  static constexpr bool COUNTS = true;
+  template <class T>
+  static __device__ __forceinline__ DispLane<T> lane(T lam) {
+    return {lam, lp_exp(-lam), lp_exp(lam)};
+  }
+  template <class T>
+  static __device__ __forceinline__ void eval(T u, T k, T, const DispLane<T> &L, T &phi, T &du, T &dl) {
+    T nsp, sg;  // -softplus(x), sigmoid(x)
+    PhiLogSigmoid::eval(L.lam - u, (T)0, nsp, sg);
+    const T kr = k + L.el;
+    phi = kr * nsp;
+    du = -kr * sg;
+    dl = L.el * nsp + kr * sg;
+  }
+};
+// phi, d phi / d u and d phi / d lambda of one row under its weight: exactly 0 for weight 0, by select
+template <class T>
+__device__ __forceinline__ void disp_weigh(T w, T &phi, T &du, T &dl) {
+  glm_weigh(w, phi, du);
+  dl = w == (T)0 ? (T)0 : w * dl;
+}
+
+// The data of the dispersion form behind the structured prior's, in the same buffer:  ... gidx[p] | cnt[rows] | ctab[Mt]
+// (NEGBIN only), Mt = par[2] clamped to [0, 4096] by select (NaN -> 0), ctab[j] = c_{j + 1}.  The table term
+//   T(lambda) = sum_j ctab[j] log1p((j + 1) exp(-lambda)),   T'(lambda) = -sum_j ctab[j] (j + 1) / (exp(lambda) + j + 1)
+// is summed by `nth` threads of a sample: thread `th` takes j = th, th + nth, ... ascending.
+#define LP_DISP_MAXTAB 4096
+template <class T>
+struct DispRows {
+  const T *cnt, *ctab;
+  int Mt;
+  __device__ __forceinline__ DispRows(const HierRows<T> &hr, const T *par, int rows, bool counts) {
+    cnt = hr.gidx + hr.p;
+    ctab = cnt + rows;
+    const T m = counts ? par[2] : (T)0;
+    Mt = m >= (T)0 ? (m <= (T)LP_DISP_MAXTAB ? (int)m : LP_DISP_MAXTAB) : 0;
+  }
+  __device__ __forceinline__ void table(int th, int nth, const DispLane<T> &L, T &tv, T &td) const {
+    tv = (T)0, td = (T)0;
+    for (int j = th; j < Mt; j += nth) {
+      const T m = (T)(j + 1), c = ctab[j];
+      tv += c * lp_log1p(m * L.einv);
+      td -= c * m / (L.el + m);
+    }
+  }
 };
 
 // the constant and the prior weight of a checked target (host side, in double)
@@ -187,6 +305,6 @@ inline LinpredConsts linpred_consts(const nf_target *t, int d) {
   const double L2PI = 1.8378770664093453;
   if (t->kind == NF_TARGET_DENSEGAUSS) return {-0.5 * d * L2PI + t->s0, 0.0, (long)d};
   if (target_is_glm(t->kind) && std::isinf(t->s1)) return {0.0, 0.0, (long)t->s0};  // flat prior: both prior terms vanish
-  if (target_is_hglm(t->kind)) return {0.0, 0.0, (long)t->s0};  // s1 = G: the prior is evaluated from the buffer, its constants sit in par[1]
+  if (target_is_hglm(t->kind) || target_is_dglm(t->kind)) return {0.0, 0.0, (long)t->s0};  // s1 = G: the prior is evaluated from the buffer, its constants sit in par[1]
   return {-0.5 * d * (L2PI + 2.0 * std::log(t->s1)), 1.0 / (t->s1 * t->s1), (long)t->s0};
 }

@@ -1,17 +1,22 @@
-// nf_linpred.hip -- the linear-predictor targets (NF_TARGET_DENSEGAUSS, NF_TARGET_LOGREG, NF_TARGET_GLM_*, NF_TARGET_HGLM_*; gfx950):
+// nf_linpred.hip -- the linear-predictor targets (NF_TARGET_DENSEGAUSS, NF_TARGET_LOGREG, NF_TARGET_GLM_*, NF_TARGET_HGLM_*,
+// NF_TARGET_DGLM_*; gfx950):
 //     centred      log p(y) = c + sum_i phi(u_i) - pw |y|^2 / 2,   u = A (y - mu),   grad = A' phi'(u) - pw y
 //     generalised  log p(y) = par[1] + c + sum_i wt_i phi(u_i; par[0]) + lin . y - pw |y|^2 / 2,   u = A y + off,
 //                  grad = A' (wt o phi'(u)) + lin - pw y
 //     hierarchical the generalised form with the structured prior of nf_linpred.h (HierRows: y = [beta ; tau], groups of
 //                  coefficients under learned scales exp(tau_g) with hyper-priors) in place of - pw |y|^2 / 2
+//     dispersion   the hierarchical form over y = [beta ; tau ; lambda] with phi_i(u_i, lambda): the log-dispersion lambda = y[d - 1]
+//                  is a per-sample scalar inside the row function (DispScale / DispNegBin), with a hyper-prior of its own and, for
+//                  the negative binomial, the table term T(lambda) (DispRows)
 // with A [rows x d] row-major: MvNormal(mu, Sigma) through W = inv(chol(Sigma)), Bayesian logistic regression through the
 // label-folded data matrix, and the regression posteriors with exposures, trial counts, subsampling weights and a family
 // parameter through the generalised form.  Two kernel bodies, each templated on the row function phi and on the form
 // (nf_linpred.h); the centred instantiations compile every line of the row data away:
 //   lp_tiled_body  Float32, tiled layout, drop-in for k_target_tiled: both GEMMs on v_mfma_f32_32x32x2_f32
-//                  (k_target_linpred_tiled: centred, k_target_glm_tiled: generalised, k_target_hier_tiled: hierarchical)
+//                  (k_target_linpred_tiled: centred, k_target_glm_tiled: generalised, k_target_hier_tiled: hierarchical,
+//                  k_target_disp_tiled: dispersion)
 //   lp_flat_body   flat layout, float / double, drop-in for k_target: vector pipe (Float64 flows, nf_target_logp)
-//                  (k_target_linpred, k_target_glm, k_target_hier)
+//                  (k_target_linpred, k_target_glm, k_target_hier, k_target_disp)
 #include "nf_common.h"
 #include "nf_linpred.h"
 
@@ -38,6 +43,12 @@
 // tau of its group from the tile's lines (yb[(p + g) * 32 + s], just read by this workgroup), for a log-scale it walks its
 // group's member list over the same lines.  The prior's share of log p takes the path |y|^2 takes (no atomics: one owner per
 // sum, in a fixed order).
+// Dispersion form: the hierarchical form's, and a lane's 16 accumulator registers all belong to sample lane & 31, so lambda is ONE
+// LDS read per lane per tile (sY[(d - 1) * 32 + (lane & 31)], after the tile is staged) and exp(-lambda) / exp(lambda) are formed once;
+// NEGBIN's 16 counts are requested with the block's offsets and weights.  The row function returns phi, d phi / d u (into U[r], the B
+// operand of GEMM 2) and d phi / d lambda, which a per-lane sum carries beside lp through a second array of sL's shape, combined in
+// sL's order by the epilogue thread that owns feature d - 1 of the sample; that thread adds lambda's hyper-prior and the table term,
+// which the sample's eight (q, s) threads sum (j = q, q + 8, ... ascending; the partials combined q = 0 .. 7).  No atomics.
 // Feature chunks: the image holds at most 128 features of the 32 rows (16.5 KB per wave); a wider target (DB = 8) runs
 // GEMM 1 chunk by chunk and stages each chunk a second time for GEMM 2.
 #define LP_BLOCK 256
@@ -82,14 +93,15 @@ __device__ __forceinline__ void lp_tiled_body(int d, int rows, long N, const flo
                                               const float *__restrict__ ladj, float *__restrict__ gt, float gscale,
                                               float *__restrict__ elbos_out, double *__restrict__ partial, double pscale, int ng) {
   using G = LpGeo<DB>;
-  constexpr bool GLM = FORM != LP_CENTRED, HIER = FORM == LP_HIER;
+  constexpr bool GLM = FORM != LP_CENTRED, DISP = FORM == LP_DISP, HIER = FORM == LP_HIER || DISP;
   const GlmRows<float> rd(p0, d, rows);
-  const HierRows<float> hr(p0, d, rows, HIER ? ng : 0);
+  const HierRows<float> hr = HierRows<float>::of_form<FORM>(p0, d, rows, ng);
   const float par0 = GLM ? rd.par[0] : 0.f;
   extern __shared__ float lp_sm[];
   float *sY = lp_sm;
   float *sA = lp_sm + G::YT;
   float *sL = sA + LP_WAVES * G::IMG;  // [wave][lane] log-p partial sums
+  float *sDL = sL + LP_WAVES * 64;     // dispersion form: [wave][lane] partial sums of wt d phi / d lambda, then [2][q][s] table partials
   __shared__ float red[LP_BLOCK / 32][32];
   __shared__ float redl[GLM ? LP_BLOCK / 32 : 1][32];  // lin . y partial sums (unused, and removed, in the centred form)
   __shared__ double sm[LP_WAVES];
@@ -112,6 +124,10 @@ __device__ __forceinline__ void lp_tiled_body(int d, int rows, long N, const flo
     for (int k = 0; k < PER; ++k) sY[threadIdx.x + k * LP_BLOCK] = yv[k];
   }
   __syncthreads();
+  // dispersion form: every row a lane evaluates belongs to sample l31, so lambda and its exponentials are per-lane scalars
+  // (one LDS read per lane per tile; a padding sample reads 0); the epilogue's sample s is l31 too
+  DispLane<float> dlane = {0.f, 0.f, 0.f};
+  if constexpr (DISP) dlane = PHI::lane(sY[(d - 1) * 32 + l31]);
 
   float *img = sA + wave * G::IMG;
   f32x16 Gacc[DB];
@@ -119,7 +135,7 @@ __device__ __forceinline__ void lp_tiled_body(int d, int rows, long N, const flo
   for (int b = 0; b < DB; ++b)
 #pragma unroll
     for (int r = 0; r < 16; ++r) Gacc[b][r] = 0.f;
-  float lp = 0.f;
+  float lp = 0.f, dl = 0.f;
   const int nrb = (rows + 31) >> 5;
   for (int rb = wave; rb < nrb; rb += LP_WAVES) {
     const int i0 = rb * 32;
@@ -130,6 +146,17 @@ __device__ __forceinline__ void lp_tiled_body(int d, int rows, long N, const flo
       const int i = i0 + nf_row(r, hi);
       U[r] = (GLM && i < rows) ? rd.off[i] : 0.f;
       wt[r] = (GLM && i < rows) ? rd.wt[i] : 0.f;
+    }
+    float kc[DISP ? 16 : 1];  // the counts of the lane's 16 rows (NEGBIN), requested with the offsets and the weights
+    if constexpr (DISP) {
+      if constexpr (PHI::COUNTS) {
+        const DispRows<float> dr(hr, rd.par, rows, true);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int i = i0 + nf_row(r, hi);
+          kc[r] = i < rows ? dr.cnt[i] : 0.f;
+        }
+      }
     }
 #pragma unroll
     for (int ch = 0; ch < G::NCH; ++ch) {
@@ -153,11 +180,18 @@ __device__ __forceinline__ void lp_tiled_body(int d, int rows, long N, const flo
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       float ph, dp;
-      PHI::eval(U[r], par0, ph, dp);
-      if (GLM)
-        glm_weigh(wt[r], ph, dp);
-      else if (ragged && i0 + nf_row(r, hi) >= rows)
-        ph = 0.f, dp = 0.f;
+      if constexpr (DISP) {
+        float dlr;
+        PHI::eval(U[r], PHI::COUNTS ? kc[r] : 0.f, par0, dlane, ph, dp, dlr);
+        disp_weigh(wt[r], ph, dp, dlr);
+        dl += dlr;
+      } else {
+        PHI::eval(U[r], par0, ph, dp);
+        if (GLM)
+          glm_weigh(wt[r], ph, dp);
+        else if (ragged && i0 + nf_row(r, hi) >= rows)
+          ph = 0.f, dp = 0.f;
+      }
       lp += ph;
       U[r] = dp;
     }
@@ -185,6 +219,16 @@ __device__ __forceinline__ void lp_tiled_body(int d, int rows, long N, const flo
 
   // the four waves' G and log-p sums, combined in wave order
   sL[wave * 64 + lane] = lp;
+  if constexpr (DISP) {
+    sDL[wave * 64 + lane] = dl;
+    if constexpr (PHI::COUNTS) {  // the table term of sample s = l31: thread (q, s) takes j = q, q + 8, ... ascending
+      const DispRows<float> dr(hr, rd.par, rows, true);
+      float tv, td;
+      dr.table(threadIdx.x >> 5, LP_BLOCK / 32, dlane, tv, td);
+      sDL[LP_WAVES * 64 + threadIdx.x] = tv;
+      sDL[LP_WAVES * 64 + LP_BLOCK + threadIdx.x] = td;
+    }
+  }
   for (int w = 0; w < LP_WAVES; ++w) {
     __syncthreads();  // (first pass: every wave is done reading the tile)
     if (wave == w) {
@@ -224,8 +268,27 @@ __device__ __forceinline__ void lp_tiled_body(int d, int rows, long N, const flo
           const auto y = [&](int f) { return yb[f * 32 + s]; };  // the tile's lines, just read by this workgroup
           if (i < hr.p)
             hr.coef(i, yv[k], y, pv, pg);
-          else
+          else if constexpr (!DISP)
             hr.scale(i - hr.p, yv[k], y, pv, pg);
+          else if (i < d - 1)
+            hr.scale(i - hr.p, yv[k], y, pv, pg);
+          else {  // lambda: the rows' d phi / d lambda in sL's order, its hyper-prior (entry G) and the table term, q = 0 .. 7 ascending
+            hr.hyper(hr.G, yv[k], pv, pg);
+#pragma unroll
+            for (int w = 0; w < LP_WAVES; ++w) pg += sDL[w * 64 + s] + sDL[w * 64 + 32 + s];
+            if constexpr (DISP) {
+              if constexpr (PHI::COUNTS) {
+                float tv = 0.f, td = 0.f;
+#pragma unroll
+                for (int qq = 0; qq < LP_BLOCK / 32; ++qq) {
+                  tv += sDL[LP_WAVES * 64 + qq * 32 + s];
+                  td += sDL[LP_WAVES * 64 + LP_BLOCK + qq * 32 + s];
+                }
+                pv += tv;
+                pg += td;
+              }
+            }
+          }
         }
         yy += pv;
         ly += lv[k] * yv[k];
@@ -300,6 +363,17 @@ __global__ __launch_bounds__(LP_BLOCK) void k_target_hier_tiled(int d, int rows,
   lp_tiled_body<DB, PHI, LP_HIER>(d, rows, N, yt, rowdata, A, 0.f, 0.f, logq, ladj, gt, gscale, elbos_out, partial, pscale, ng);
 }
 
+// dispersion form: PHI is DispScale<..> / DispNegBin; ng = G group log-scales between the p = d - G - 1 coefficients and lambda
+template <int DB, class PHI>
+__global__ __launch_bounds__(LP_BLOCK) void k_target_disp_tiled(int d, int rows, long N, const float *__restrict__ yt,
+                                                                const float *__restrict__ rowdata, const float *__restrict__ A,
+                                                                int ng, const float *__restrict__ logq,
+                                                                const float *__restrict__ ladj, float *__restrict__ gt,
+                                                                float gscale, float *__restrict__ elbos_out,
+                                                                double *__restrict__ partial, double pscale) {
+  lp_tiled_body<DB, PHI, LP_DISP>(d, rows, N, yt, rowdata, A, 0.f, 0.f, logq, ladj, gt, gscale, elbos_out, partial, pscale, ng);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // flat kernel (vector pipe)
 // ---------------------------------------------------------------------------------------------------------------------
@@ -317,9 +391,9 @@ __device__ __forceinline__ void lp_flat_body(int d, int rows, long N, const T *_
                                              const T *__restrict__ ladj, T *__restrict__ logp_out, T *__restrict__ grad_out,
                                              T gscale, T *__restrict__ elbos_out, double *__restrict__ partial, double pscale,
                                              int ng) {
-  constexpr bool GLM = FORM != LP_CENTRED, HIER = FORM == LP_HIER;
+  constexpr bool GLM = FORM != LP_CENTRED, DISP = FORM == LP_DISP, HIER = FORM == LP_HIER || DISP;
   const GlmRows<T> rd(p0, d, rows);
-  const HierRows<T> hr(p0, d, rows, HIER ? ng : 0);
+  const HierRows<T> hr = HierRows<T>::template of_form<FORM>(p0, d, rows, ng);
   const T par0 = GLM ? rd.par[0] : (T)0;
   extern __shared__ double lpf_sm[];
   T *sY = (T *)lpf_sm;                  // [sample][d + 1] centred
@@ -341,10 +415,19 @@ __device__ __forceinline__ void lp_flat_body(int d, int rows, long N, const T *_
   T g[LPF_MAXD / LPF_LANES];
 #pragma unroll
   for (int k = 0; k < LPF_MAXD / LPF_LANES; ++k) g[k] = (T)0;
-  T lp = 0;
+  T lp = 0, dl = 0;
+  DispLane<T> dlane = {(T)0, (T)0, (T)0};
+  if constexpr (DISP) {  // lambda of the lane's sample and its exponentials, once
+    __syncthreads();
+    dlane = PHI::lane(sY[sl * S + d - 1]);
+  }
   for (int i0 = 0; i0 < rows; i0 += LPF_RB) {
     const bool live = i0 + q < rows;
     const T ov = (GLM && live) ? rd.off[i0 + q] : (T)0, wv = (GLM && live) ? rd.wt[i0 + q] : (T)0;  // (requested with the block of A)
+    T kv = (T)0;
+    if constexpr (DISP) {
+      if constexpr (PHI::COUNTS) kv = live ? DispRows<T>(hr, rd.par, rows, true).cnt[i0 + q] : (T)0;
+    }
     __syncthreads();  // the tile (first pass); the previous block's readers
     for (int idx = threadIdx.x; idx < LPF_RB * d; idx += LP_BLOCK) {
       const int row = idx / d, f = idx - row * d;
@@ -354,11 +437,18 @@ __device__ __forceinline__ void lp_flat_body(int d, int rows, long N, const T *_
     T u = ov;
     for (int f = 0; f < d; ++f) u += sA[q * S + f] * sY[sl * S + f];
     T ph, dp;
-    PHI::eval(u, par0, ph, dp);
-    if (GLM)
-      glm_weigh(wv, ph, dp);
-    else if (!live)
-      ph = (T)0, dp = (T)0;
+    if constexpr (DISP) {
+      T dlr;
+      PHI::eval(u, kv, par0, dlane, ph, dp, dlr);
+      disp_weigh(wv, ph, dp, dlr);
+      dl += dlr;
+    } else {
+      PHI::eval(u, par0, ph, dp);
+      if (GLM)
+        glm_weigh(wv, ph, dp);
+      else if (!live)
+        ph = (T)0, dp = (T)0;
+    }
     lp += ph;
     sD[sl * (LPF_RB + 1) + q] = dp;
     __syncthreads();
@@ -373,6 +463,19 @@ __device__ __forceinline__ void lp_flat_body(int d, int rows, long N, const T *_
       }
     }
   }
+  T tv = 0, td = 0;
+  if constexpr (DISP) {  // every lane of the sample gets the sums: the owner of feature d - 1 adds them below
+    dl = group16_sum(dl);
+    if constexpr (PHI::COUNTS) {  // the table term: lane q takes j = q, q + 16, ... ascending; the partials in lane order
+      T pv_, pd_;
+      DispRows<T>(hr, rd.par, rows, true).table(q, LPF_LANES, dlane, pv_, pd_);
+#pragma unroll
+      for (int l = 0; l < LPF_LANES; ++l) {
+        tv += __shfl(pv_, l, LPF_LANES);
+        td += __shfl(pd_, l, LPF_LANES);
+      }
+    }
+  }
   T yy = 0, ly = 0;
 #pragma unroll
   for (int k = 0; k < LPF_MAXD / LPF_LANES; ++k) {
@@ -384,8 +487,15 @@ __device__ __forceinline__ void lp_flat_body(int d, int rows, long N, const T *_
         T pv, pg;
         if (f < hr.p)
           hr.coef(f, yv, ys, pv, pg);
-        else
+        else if constexpr (!DISP)
           hr.scale(f - hr.p, yv, ys, pv, pg);
+        else if (f < d - 1)
+          hr.scale(f - hr.p, yv, ys, pv, pg);
+        else {  // lambda: its hyper-prior (entry G), the rows' d phi / d lambda and the table term
+          hr.hyper(hr.G, yv, pv, pg);
+          pv += tv;
+          pg += dl + td;
+        }
         const T lv = rd.lin[f];
         yy += pv;
         ly += lv * yv;
@@ -450,6 +560,15 @@ __global__ __launch_bounds__(LP_BLOCK) void k_target_hier(int d, int rows, long 
                                                           double pscale) {
   lp_flat_body<T, PHI, LP_HIER>(d, rows, N, y, rowdata, A, (T)0, (T)0, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale, ng);
 }
+template <class T, class PHI>
+__global__ __launch_bounds__(LP_BLOCK) void k_target_disp(int d, int rows, long N, const T *__restrict__ y,
+                                                          const T *__restrict__ rowdata, const T *__restrict__ A, int ng,
+                                                          const T *__restrict__ logq, const T *__restrict__ ladj,
+                                                          T *__restrict__ logp_out, T *__restrict__ grad_out, T gscale,
+                                                          T *__restrict__ elbos_out, double *__restrict__ partial,
+                                                          double pscale) {
+  lp_flat_body<T, PHI, LP_DISP>(d, rows, N, y, rowdata, A, (T)0, (T)0, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale, ng);
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // launchers (called by nf_launch_target / nf_launch_target_tiled after nf_target_check)
@@ -457,7 +576,9 @@ __global__ __launch_bounds__(LP_BLOCK) void k_target_hier(int d, int rows, long 
 // the kernel of a form (only the one asked for is instantiated)
 template <int DB, class PHI, int FORM>
 static auto tiled_kernel() {
-  if constexpr (FORM == LP_HIER)
+  if constexpr (FORM == LP_DISP)
+    return &k_target_disp_tiled<DB, PHI>;
+  else if constexpr (FORM == LP_HIER)
     return &k_target_hier_tiled<DB, PHI>;
   else if constexpr (FORM == LP_GLM)
     return &k_target_glm_tiled<DB, PHI>;
@@ -466,7 +587,9 @@ static auto tiled_kernel() {
 }
 template <class T, class PHI, int FORM>
 static auto flat_kernel() {
-  if constexpr (FORM == LP_HIER)
+  if constexpr (FORM == LP_DISP)
+    return &k_target_disp<T, PHI>;
+  else if constexpr (FORM == LP_HIER)
     return &k_target_hier<T, PHI>;
   else if constexpr (FORM == LP_GLM)
     return &k_target_glm<T, PHI>;
@@ -477,7 +600,8 @@ static auto flat_kernel() {
 template <int DB, class PHI, int FORM>
 static int launch_tiled(nf_ctx *ctx, const nf_target *t, int d, long N, const float *yt, const float *logq, const float *ladj,
                         float *gt, double gscale, float *elbos_out, double *partial, double pscale) {
-  const size_t lds = (size_t)LpGeo<DB>::FLOATS * sizeof(float);
+  // dispersion form: + the d phi / d lambda partial sums (sL's shape) and the table term's [2][8][32] partials
+  const size_t lds = (size_t)(LpGeo<DB>::FLOATS + (FORM == LP_DISP ? LP_WAVES * 64 + 2 * LP_BLOCK : 0)) * sizeof(float);
   const auto kern = tiled_kernel<DB, PHI, FORM>();
   static AttrOnce attr_once;  // once per device
   NF_TRY(attr_once.run(ctx->device, [&]() -> int {
@@ -486,7 +610,7 @@ static int launch_tiled(nf_ctx *ctx, const nf_target *t, int d, long N, const fl
   }));
   const LinpredConsts k = linpred_consts(t, d);
   ProfScope ps(ctx, "target_linpred");
-  if constexpr (FORM == LP_HIER)
+  if constexpr (FORM == LP_HIER || FORM == LP_DISP)
     hipLaunchKernelGGL(kern, dim3((unsigned)((N + 31) / 32)), dim3(LP_BLOCK), lds, ctx->stream, d,
                        (int)k.rows, N, yt, (const float *)t->p0, (const float *)t->p1, (int)t->s1, logq, ladj, gt,
                        (float)gscale, elbos_out, partial, pscale);
@@ -524,6 +648,9 @@ int nf_launch_target_linpred_tiled(nf_ctx *ctx, const nf_target *t, int d, long 
     case NF_TARGET_HGLM_POISSON: return LP_TILED(PhiNegExp, LP_HIER);
     case NF_TARGET_HGLM_STUDENT: return LP_TILED(PhiStudent, LP_HIER);
     case NF_TARGET_HGLM_NORMAL: return LP_TILED(PhiHalfSquare, LP_HIER);
+    case NF_TARGET_DGLM_NORMAL: return LP_TILED(DispScale<PhiHalfSquare>, LP_DISP);
+    case NF_TARGET_DGLM_STUDENT: return LP_TILED(DispScale<PhiStudent>, LP_DISP);
+    case NF_TARGET_DGLM_NEGBIN: return LP_TILED(DispNegBin, LP_DISP);
     default: return NF_ERR_ARG;
   }
 #undef LP_TILED
@@ -543,7 +670,7 @@ static int launch_flat(nf_ctx *ctx, const nf_target *t, int d, long N, const voi
   const LinpredConsts k = linpred_consts(t, d);
   ProfScope ps(ctx, "target_linpred");
   const long nb = (N + LPF_SPB - 1) / LPF_SPB;
-  if constexpr (FORM == LP_HIER)
+  if constexpr (FORM == LP_HIER || FORM == LP_DISP)
     hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(LP_BLOCK), lds, ctx->stream, d, (int)k.rows, N,
                        (const T *)y, (const T *)t->p0, (const T *)t->p1, (int)t->s1, (const T *)logq, (const T *)ladj,
                        (T *)logp_out, (T *)grad_out, (T)gscale, (T *)elbos_out, partial, pscale);
@@ -575,6 +702,9 @@ int nf_launch_target_linpred(nf_ctx *ctx, int dtype, const nf_target *t, int d, 
     case NF_TARGET_HGLM_POISSON: return LP_FLAT(PhiNegExp, LP_HIER);
     case NF_TARGET_HGLM_STUDENT: return LP_FLAT(PhiStudent, LP_HIER);
     case NF_TARGET_HGLM_NORMAL: return LP_FLAT(PhiHalfSquare, LP_HIER);
+    case NF_TARGET_DGLM_NORMAL: return LP_FLAT(DispScale<PhiHalfSquare>, LP_DISP);
+    case NF_TARGET_DGLM_STUDENT: return LP_FLAT(DispScale<PhiStudent>, LP_DISP);
+    case NF_TARGET_DGLM_NEGBIN: return LP_FLAT(DispNegBin, LP_DISP);
     default: return NF_ERR_ARG;
   }
 #undef LP_FLAT

@@ -130,8 +130,11 @@ __host__ __device__ inline bool target_is_glm(int kind) { return kind >= NF_TARG
 // The hierarchical kinds (NF_TARGET_HGLM_LOGIT .. NF_TARGET_HGLM_NORMAL = the GLM kind + 7: the generalised form under a
 // structured prior with learned group scales) are linear-predictor kinds too, served by a third form of the same two bodies.
 __host__ __device__ inline bool target_is_hglm(int kind) { return kind >= NF_TARGET_HGLM_LOGIT && kind <= NF_TARGET_HGLM_NORMAL; }
+// The dispersion kinds (NF_TARGET_DGLM_NORMAL / STUDENT / NEGBIN: the hierarchical form with one more coordinate, the
+// log-dispersion lambda = y[d - 1], inside the row function) are linear-predictor kinds too: the fourth form of the two bodies.
+__host__ __device__ inline bool target_is_dglm(int kind) { return kind >= NF_TARGET_DGLM_NORMAL && kind <= NF_TARGET_DGLM_NEGBIN; }
 __host__ __device__ inline bool target_is_linpred(int kind) {
-  return kind == NF_TARGET_DENSEGAUSS || kind == NF_TARGET_LOGREG || target_is_glm(kind) || target_is_hglm(kind);
+  return kind == NF_TARGET_DENSEGAUSS || kind == NF_TARGET_LOGREG || target_is_glm(kind) || target_is_hglm(kind) || target_is_dglm(kind);
 }
 // The Gaussian mixture (NF_TARGET_GAUSSMIX, nf_mixture.hip) is routed like them: a kernel of its own behind
 // nf_launch_target / nf_launch_target_tiled, refused wherever target_term would have to evaluate it.

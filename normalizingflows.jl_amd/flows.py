@@ -1062,6 +1062,202 @@ class VaryingInterceptTarget(HierarchicalGLMTarget):
                          hyper, hyper_loc, hyper_scale, _name=nm)
 
 
+_DGLM_KINDS = {"normal": _lib.NF_TARGET_DGLM_NORMAL, "student": _lib.NF_TARGET_DGLM_STUDENT, "negbin": _lib.NF_TARGET_DGLM_NEGBIN}
+_DGLM_MAX_COUNT = 4097  # the device's table T(lambda) holds at most 4096 entries c_1 .. c_{max k - 1}
+
+
+class DispersionGLMTarget(_LinpredTarget):
+    """A GLM posterior with a LEARNED dispersion (NF_TARGET_DGLM_*), over z = [beta (p coefficients) ; tau (G group log-scales) ;
+    lambda (the log-dispersion)], d = p + G + 1, under HierarchicalGLMTarget's structured prior on (beta, tau):
+        logp(z) = const + sum_i weights_i l_i(u_i, lambda) + lin . beta + sum_j log N(beta_j; 0, sigma_j^2) + sum_g log p(tau_g) + log p(lambda),
+        u = A beta + offset.
+    family "normal":  l_i = -z_i^2 / 2 - lambda,                          z_i = u_i exp(-lambda)   (sigma = exp(lambda); -log(2 pi)/2 is the caller's const)
+           "student": l_i = -(nu + 1)/2 log1p(z_i^2 / nu) - lambda,       nu = param
+           "negbin":  l_i = log NB(counts_i; mean exp(u_i), size exp(lambda)), the full log-pmf (lgamma(k + 1) included)
+    A [rows, p], groups, n_groups, offset, weights, lin (p,), const, param, fixed_sigma, hyper, hyper_loc, hyper_scale are
+    HierarchicalGLMTarget's (groups=None: every coefficient under fixed_sigma).  counts: non-negative integers <= 4097, required for
+    and only for "negbin".  disp_hyper / disp_loc / disp_scale: the prior of exp(lambda), one of the three hyper-prior forms.
+    Everything linear in z or constant is folded here in float64: the -(sum weights) lambda of the scale families' normalisers and the
+    Jacobians into lin, the counts' sum_i w_i k_i u_i into lin and the constant, c_m = sum_{i: k_i > m} w_i into the table.  The
+    device reads `A` (padded with zero tau- and lambda-columns to [rows, d]) and ONE buffer `p0` (include/nfhip.h)."""
+
+    def __init__(self, family, A, counts=None, groups=None, n_groups=0, offset=None, weights=None, lin=None, const=0.0, param=0.0,
+                 fixed_sigma=1.0, hyper="halfcauchy", hyper_loc=0.0, hyper_scale=1.0, disp_hyper="halfcauchy", disp_loc=0.0, disp_scale=1.0,
+                 _name="DispersionGLMTarget"):
+        nm = _name
+        if family not in _DGLM_KINDS:
+            raise NFHipError(f"{nm}: family must be one of {sorted(_DGLM_KINDS)}")
+        A64 = _glm_matrix(nm, A)
+        rows, p = A64.shape
+        if isinstance(n_groups, bool) or not hasattr(n_groups, "__index__") or int(n_groups) < 0:
+            raise NFHipError(f"{nm}: n_groups must be an integer >= 0")
+        G = int(n_groups)
+        d = p + G + 1
+        if d > 256:
+            raise NFHipError(f"{nm}: p + n_groups + 1 = {d} exceeds the kernels' d = 256")
+        if groups is None:
+            groups = torch.full((p,), -1, dtype=torch.int64)
+        if not isinstance(groups, torch.Tensor) or groups.dim() != 1 or groups.numel() != p or groups.dtype.is_floating_point or \
+                groups.dtype.is_complex or groups.dtype == torch.bool:
+            raise NFHipError(f"{nm}: groups must be an integer tensor of length {p}")
+        grp = groups.detach().to("cpu", torch.int64)
+        if bool((grp < -1).any()) or bool((grp >= G).any()):
+            raise NFHipError(f"{nm}: groups must hold -1 (a fixed prior scale) or a group index in 0..{G - 1}")
+        off = _glm_vector(nm, "offset", offset, A, rows, 0.0)
+        wt = _glm_vector(nm, "weights", weights, A, rows, 1.0, nonneg=True)
+        ln = _glm_vector(nm, "lin", lin, A, p, 0.0)
+        const = _glm_scalar(nm, "const", const, positive=False)
+        param = _glm_scalar(nm, "param", param, positive=family == "student")
+        sig = _per_item(nm, "fixed_sigma", fixed_sigma, p, positive=True, allow_inf=True)
+        names = [hyper] * G if isinstance(hyper, str) else list(hyper)
+        if len(names) != G or any(not isinstance(h, str) or h not in _HYPER_KINDS for h in names):
+            raise NFHipError(f"{nm}: hyper must be one of {sorted(_HYPER_KINDS)}, or one of them per group")
+        if not isinstance(disp_hyper, str) or disp_hyper not in _HYPER_KINDS:
+            raise NFHipError(f"{nm}: disp_hyper must be one of {sorted(_HYPER_KINDS)}")
+        loc = torch.cat([_per_item(nm, "hyper_loc", hyper_loc, G), torch.tensor([_glm_scalar(nm, "disp_loc", disp_loc, positive=False)], dtype=torch.float64)])
+        scl = torch.cat([_per_item(nm, "hyper_scale", hyper_scale, G, positive=True), torch.tensor([_glm_scalar(nm, "disp_scale", disp_scale)], dtype=torch.float64)])
+        names_all = names + [disp_hyper]
+        if (family == "negbin") != (counts is not None):
+            raise NFHipError(f"{nm}: counts are required for, and only for, the negbin family")
+
+        grouped = grp >= 0
+        isd = torch.where(grouped, torch.zeros(p, dtype=torch.float64), 1.0 / sig)        # 1 / inf = 0: flat
+        n_g = torch.bincount(grp[grouped], minlength=G).to(torch.float64) if G else torch.zeros(0, dtype=torch.float64)
+        L2PI = math.log(2.0 * math.pi)
+        fixed = (~grouped) & torch.isfinite(sig)
+        c = const - float(torch.log(sig[fixed]).sum()) - 0.5 * L2PI * float(fixed.sum()) - 0.5 * L2PI * float(grouped.sum())
+        hk = torch.tensor([float(_HYPER_KINDS[h]) for h in names_all], dtype=torch.float64)
+        hm, his = torch.zeros(G + 1, dtype=torch.float64), torch.zeros(G + 1, dtype=torch.float64)
+        lin_tl = torch.cat([-n_g, torch.zeros(1, dtype=torch.float64)])                    # lin of [tau ; lambda]
+        for g, h in enumerate(names_all):
+            if h == "lognormal":
+                hm[g], his[g] = loc[g], 1.0 / scl[g]
+                c += -math.log(float(scl[g])) - 0.5 * L2PI
+            else:  # a density over exp(.): + tau_g (+ lambda) from the change of variables
+                hm[g] = math.log(float(scl[g]))
+                lin_tl[g] += 1.0
+                c += (0.5 if h == "halfnormal" else 1.0) * math.log(2.0 / math.pi) - float(hm[g])
+        tail = []
+        mt = 0
+        if family == "negbin":
+            k = _glm_vector(nm, "counts", counts, A, rows, nonneg=True)
+            if bool((k != torch.round(k)).any()) or bool((k > _DGLM_MAX_COUNT).any()):
+                raise NFHipError(f"{nm}: counts must be integers in 0..{_DGLM_MAX_COUNT}")
+            live = wt > 0                                                                  # zero-weight rows never enter the table
+            M = int(k[live].max()) if bool(live.any()) else 0
+            mt = max(M - 1, 0)
+            m = torch.arange(1, mt + 1, dtype=torch.float64)
+            ctab = ((k[None, :] > m[:, None]).to(torch.float64) * wt[None, :]).sum(1)     # c_m = sum_{i: k_i > m} w_i, m = 1 .. M - 1
+            kl, wl, ol = k[live], wt[live], off[live]                                      # nor the folded sums: a masked row changes no bit of p0
+            ln = ln + (wl * kl) @ A64[live]
+            c += float((wl * (kl * ol - torch.lgamma(kl + 1.0))).sum())
+            tail = [k, ctab]
+            self.counts = k
+        else:
+            lin_tl[G] -= float(wt[wt > 0].sum())                                           # the -lambda of every live row's normaliser
+        order = torch.argsort(grp, stable=True)                                            # members in increasing feature index
+        gidx = torch.cat([order[grp[order] >= 0], torch.zeros(int((~grouped).sum()), dtype=torch.int64)]).to(torch.float64)
+        gptr = torch.cat([torch.zeros(1, dtype=torch.float64), torch.cumsum(n_g, 0)])
+        self.family, self.d, self.p, self.G, self.rows, self.param, self.const = family, d, p, G, rows, param, c
+        self.groups, self.hyper, self.disp_hyper, self.table_len = grp, names, disp_hyper, mt
+        self.A = torch.cat([A.detach(), torch.zeros(rows, G + 1, dtype=A.dtype, device=A.device)], 1).contiguous()
+        self.p0 = torch.cat([ln, lin_tl, off, wt, torch.tensor([param, c, float(mt), 0.0], dtype=torch.float64), grp.to(torch.float64), isd, hm, his,
+                             hk, gptr, gidx] + tail).to(A.dtype).to(A.device).contiguous()
+        self.c = Target(_DGLM_KINDS[family], self.p0.data_ptr(), self.A.data_ptr(), float(rows), float(G))
+
+    def coefficients(self, y):
+        """beta, the first p leading elements of a parameter vector (d,) or a batch (d, N)"""
+        return y[:self.p]
+
+    def scales(self, y):
+        """the group scales exp(tau) of a parameter vector (d,) or a batch (d, N)"""
+        return torch.exp(y[self.p:self.p + self.G])
+
+    def dispersion(self, y):
+        """exp(lambda): the residual scale sigma (normal, student) or the negative binomial's size r"""
+        return torch.exp(y[-1])
+
+
+def _residual_rows(nm, X, y, weights):
+    X64 = _glm_matrix(nm, X)
+    n = X64.shape[0]
+    yv = _glm_vector(nm, "y", y, X, n)
+    w = _glm_vector(nm, "weights", weights, X, n, 1.0, nonneg=True)
+    return yv, w
+
+
+class GaussianRegressionTarget(DispersionGLMTarget):
+    """Posterior of Gaussian linear regression with an UNKNOWN noise scale: y_i ~ N(x_i . b, sigma^2), z = [b ; log sigma], the
+    columns of X under N(0, fixed_sigma^2) and sigma under disp_hyper.  Folds to the "normal" family with A = X, offset = -y and
+    const = -(sum_i w_i) log(2 pi) / 2."""
+
+    def __init__(self, X, y, weights=None, fixed_sigma=1.0, disp_hyper="halfcauchy", disp_loc=0.0, disp_scale=1.0):
+        nm = "GaussianRegressionTarget"
+        yv, w = _residual_rows(nm, X, y, weights)
+        to = lambda t: t.to(X.dtype).to(X.device)
+        super().__init__("normal", X, offset=to(-yv), weights=to(w), const=-0.5 * math.log(2.0 * math.pi) * float(w.sum()), fixed_sigma=fixed_sigma,
+                         disp_hyper=disp_hyper, disp_loc=disp_loc, disp_scale=disp_scale, _name=nm)
+
+
+class StudentRegressionTarget(DispersionGLMTarget):
+    """Posterior of linear regression with Student-t noise of an UNKNOWN scale: (y_i - x_i . b) / sigma ~ t_nu, z = [b ; log sigma].
+    Folds to the "student" family with A = X, offset = -y, param = nu and
+    const = sum_i w_i (lgamma((nu+1)/2) - lgamma(nu/2) - log(nu pi)/2)."""
+
+    def __init__(self, X, y, nu, weights=None, fixed_sigma=1.0, disp_hyper="halfcauchy", disp_loc=0.0, disp_scale=1.0):
+        nm = "StudentRegressionTarget"
+        yv, w = _residual_rows(nm, X, y, weights)
+        nu = _glm_scalar(nm, "nu", nu)
+        const = float(w.sum()) * (math.lgamma(0.5 * (nu + 1.0)) - math.lgamma(0.5 * nu) - 0.5 * math.log(nu * math.pi))
+        to = lambda t: t.to(X.dtype).to(X.device)
+        super().__init__("student", X, offset=to(-yv), weights=to(w), const=const, param=nu, fixed_sigma=fixed_sigma, disp_hyper=disp_hyper,
+                         disp_loc=disp_loc, disp_scale=disp_scale, _name=nm)
+
+
+class NegativeBinomialRegressionTarget(DispersionGLMTarget):
+    """Posterior of negative-binomial regression (log link) with an UNKNOWN size: counts k_i ~ NB(mean exposure_i exp(x_i . b),
+    size r), z = [b ; log r].  Folds to the "negbin" family with A = X and offset = log exposure."""
+
+    def __init__(self, X, counts, exposure=None, weights=None, fixed_sigma=1.0, disp_hyper="halfcauchy", disp_loc=0.0, disp_scale=1.0):
+        nm = "NegativeBinomialRegressionTarget"
+        X64 = _glm_matrix(nm, X)
+        n = X64.shape[0]
+        off = torch.log(_glm_vector(nm, "exposure", exposure, X, n, 1.0, positive=True))
+        super().__init__("negbin", X, counts=counts, offset=off.to(X.dtype).to(X.device), weights=weights, fixed_sigma=fixed_sigma,
+                         disp_hyper=disp_hyper, disp_loc=disp_loc, disp_scale=disp_scale, _name=nm)
+
+
+class LinearMixedModelTarget(DispersionGLMTarget):
+    """The linear mixed model y ~ x + (1 | level): y_i ~ N(x_i . b + a_{level_of_row[i]}, sigma^2) with a_l ~ N(0, exp(tau)^2) sharing
+    ONE learned scale, the columns of X under fixed_sigma and the residual sigma = exp(lambda) learned too.  Builds
+    A = [X | one-hot(level)], z = [b (X's columns) ; a (n_levels) ; tau ; lambda]."""
+
+    def __init__(self, X, y, level_of_row, n_levels, weights=None, fixed_sigma=1.0, hyper="halfcauchy", hyper_loc=0.0, hyper_scale=1.0,
+                 disp_hyper="halfcauchy", disp_loc=0.0, disp_scale=1.0):
+        nm = "LinearMixedModelTarget"
+        yv, w = _residual_rows(nm, X, y, weights)
+        rows, px = X.shape
+        if isinstance(n_levels, bool) or not hasattr(n_levels, "__index__") or int(n_levels) < 1:
+            raise NFHipError(f"{nm}: n_levels must be an integer >= 1")
+        L = int(n_levels)
+        if not isinstance(level_of_row, torch.Tensor) or level_of_row.dim() != 1 or level_of_row.numel() != rows or \
+                level_of_row.dtype.is_floating_point or level_of_row.dtype.is_complex or level_of_row.dtype == torch.bool:
+            raise NFHipError(f"{nm}: level_of_row must be an integer tensor with one level per row of X")
+        lev = level_of_row.detach().to("cpu", torch.int64)
+        if bool((lev < 0).any()) or bool((lev >= L).any()):
+            raise NFHipError(f"{nm}: levels must be in 0..{L - 1}")
+        onehot = torch.zeros(rows, L, dtype=X.dtype)
+        onehot[torch.arange(rows), lev] = 1.0
+        A = torch.cat([X.detach(), onehot.to(X.device)], 1)
+        groups = torch.cat([torch.full((px,), -1, dtype=torch.int64), torch.zeros(L, dtype=torch.int64)])
+        sig = _per_item(nm, "fixed_sigma", fixed_sigma, px, positive=True, allow_inf=True)
+        self.n_levels, self.levels = L, lev
+        to = lambda t: t.to(X.dtype).to(X.device)
+        super().__init__("normal", A, groups=groups, n_groups=1, offset=to(-yv), weights=to(w), const=-0.5 * math.log(2.0 * math.pi) * float(w.sum()),
+                         fixed_sigma=torch.cat([sig, torch.ones(L, dtype=torch.float64)]), hyper=hyper, hyper_loc=hyper_loc, hyper_scale=hyper_scale,
+                         disp_hyper=disp_hyper, disp_loc=disp_loc, disp_scale=disp_scale, _name=nm)
+
+
 class SoftmaxRegressionTarget(_LinpredTarget):
     """Posterior of Bayesian softmax (multinomial-logit) regression over the weight matrix W [p, C]: data rows X [rows, p],
     labels c_i in {0 .. C-1}, row weights w_i >= 0 (0 drops the row exactly), prior N(0, prior_sigma^2 I):

@@ -28,7 +28,7 @@ def kernels(bdir):
                     cur = blocks.setdefault((obj, m.group(1)), [])
                 elif cur is not None:
                     text = line.split("//")[0].strip()  # the comments carry the addresses
-                    if text:
+                    if text and text != "...":  # "...": objdump's elision of the zero fill between two functions, not an instruction
                         cur.append(text)
     for lines in blocks.values():  # local labels are numbered per file: renumber them per kernel, in the order they are defined
         order = {m.group(1): f"L{i}" for i, m in enumerate(filter(None, (re.fullmatch(r"<(L\d+)>:", t) for t in lines)))}

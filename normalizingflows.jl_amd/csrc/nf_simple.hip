@@ -71,6 +71,12 @@ __device__ __forceinline__ T sigmoid_(T x) {
 template <class T>
 struct Fm {
   static __device__ __forceinline__ T tanh_(T x) { return tanh(x); }
+  // tanh(x) (the return value: tanh_'s) and sech^2(x) -> s
+  static __device__ __forceinline__ T tanh_sech2_(T x, T &s) {
+    const T t = tanh(x);
+    s = (T)1 - t * t;
+    return t;
+  }
   static __device__ __forceinline__ T log_(T x) { return log(x); }
   static __device__ __forceinline__ T log1p_(T x) { return log1p(x); }
   static __device__ __forceinline__ T sqrt_(T x) { return sqrt(x); }
@@ -81,6 +87,15 @@ struct Fm<float> {
   static __device__ __forceinline__ float tanh_(float x) {
     const float e = __expf(2.f * x);  // inf -> 1, 0 -> -1
     return 1.f - 2.f * __builtin_amdgcn_rcpf(e + 1.f);
+  }
+  // sech^2 = 4 e / (1 + e)^2 from the same exponential, not 1 - t^2: near saturation t is within an ulp of +-1 and 1 - t^2 carries an
+  // absolute error of 1e-7, which the planar log-det multiplies by 1 + c = softplus(w'u) (30 at w'u = 30: 3 x the per-sample
+  // tolerance).  With r = 1 / (1 + e): e < 1 (x < 0) 4 e r^2; otherwise 4 r (1 - r), where 1 - r >= 1/2 does not cancel.  e = 0, inf: 0.
+  static __device__ __forceinline__ float tanh_sech2_(float x, float &s) {
+    const float e = __expf(2.f * x);
+    const float r = __builtin_amdgcn_rcpf(e + 1.f);
+    s = 4.f * r * (e < 1.f ? e * r : 1.f - r);
+    return 1.f - 2.f * r;
   }
   static __device__ __forceinline__ float log_(float x) { return nf_log(x); }
   static __device__ __forceinline__ float log1p_(float x) { return nf_log(1.f + x); }
@@ -180,11 +195,15 @@ __device__ void build_layer_cache(T *cache, const SimpleArgs &a, const T *__rest
     const T *p = theta + layer_off(a.kind, d, l);
     const int lk = layer_kind(a.kind, l);
     if (lk == LK_PLANAR) {
-      T wu = 0, ww = 0;
+      // w'u and w'w summed in double for float too: one thread adds d terms in turn, and with u ~ m w / |w|^2 they all have one sign, so
+      // a float sum of 100 ... 200 terms at w'u = 30 is 1e-5 off; u_hat = u + (softplus(-w'u) - 1) w / w'w carries that into every y
+      // (|w| = 0.3: 7 ... 18 x the per-sample tolerance at d = 100, 130).  d <= 256 additions per layer and block.
+      double wud = 0, wwd = 0;
       for (int i = 0; i < d; ++i) {
-        wu += p[i] * p[d + i];
-        ww += p[i] * p[i];
+        wud += (double)p[i] * (double)p[d + i];
+        wwd += (double)p[i] * (double)p[i];
       }
+      const T wu = (T)wud, ww = (T)wwd;
       const T scale = (softplus_(-wu) - (T)1) / ww;
       for (int i = 0; i < d; ++i) {
         c[i] = p[i];
@@ -216,12 +235,13 @@ __device__ __forceinline__ T layer_forward(int lk, const T *c, int d, int i0, bo
     T dot = 0;
 #pragma unroll
     for (int k = 0; k < DPL; ++k) dot += p0[k] * z[k];
-    const T t = Fm<T>::tanh_(g16sum(dot) + c[2 * d]);
+    T s2;
+    const T t = Fm<T>::tanh_sech2_(g16sum(dot) + c[2 * d], s2);
     T uh[DPL];
     row_load<T, DPL>(c + d, i0, d, vec, uh);
 #pragma unroll
     for (int k = 0; k < DPL; ++k) z[k] += uh[k] * t;
-    return Fm<T>::log_(c[2 * d + 1] * ((T)1 - t * t) + t * t);
+    return Fm<T>::log_(c[2 * d + 1] * s2 + t * t);
   }
   if (lk == LK_RADIAL) {
     const T alpha = c[d], bh = c[d + 1];
@@ -275,12 +295,13 @@ __device__ __forceinline__ T layer_inverse(int lk, const T *c, int d, int i0, bo
       const T t = Fm<T>::tanh_(al + b);
       al -= Fm<T>::div_(al + cc * t - wy, sp * ((T)1 - t * t) + t * t);
     }
-    const T t = Fm<T>::tanh_(al + b);
+    T s2;
+    const T t = Fm<T>::tanh_sech2_(al + b, s2);
     T uh[DPL];
     row_load<T, DPL>(c + d, i0, d, vec, uh);
 #pragma unroll
     for (int k = 0; k < DPL; ++k) z[k] -= uh[k] * t;
-    return -Fm<T>::log_(sp * ((T)1 - t * t) + t * t);
+    return -Fm<T>::log_(sp * s2 + t * t);
   }
   if (lk == LK_RADIAL) {
     const T alpha = c[d], bh = c[d + 1];
@@ -569,13 +590,14 @@ __device__ __forceinline__ T layer_forward_s(int lk, const T *c, int d, int i0, 
     T dot = 0;
 #pragma unroll
     for (int k = 0; k < DPL; ++k) dot += p0[k] * z[k];
-    const T t = Fm<T>::tanh_(g16sum(dot) + c[2 * d]);
+    T s2;
+    const T t = Fm<T>::tanh_sech2_(g16sum(dot) + c[2 * d], s2);
     keep = t;
     T uh[DPL];
     row_load<T, DPL>(c + d, i0, d, vec, uh);
 #pragma unroll
     for (int k = 0; k < DPL; ++k) z[k] += uh[k] * t;
-    return Fm<T>::log_(c[2 * d + 1] * ((T)1 - t * t) + t * t);
+    return Fm<T>::log_(c[2 * d + 1] * s2 + t * t);
   }
   const T alpha = c[d], bh = c[d + 1];
   T ss = 0;
@@ -1222,9 +1244,10 @@ __global__ __launch_bounds__(SB, (PG::NLR <= 6 ? 2 : 1)) void k_planar_step(Simp
         float av = A[l] + bs[l];
 #pragma unroll
         for (int m = l + 1; m < NL; ++m) av += Cu[l][m] * tl[m];
-        const float t = Fm<float>::tanh_(av);
+        float s2;
+        const float t = Fm<float>::tanh_sech2_(av, s2);
         tl[l] = t;
-        lsum += Fm<float>::log_(sps[l] * (1.f - t * t) + t * t);
+        lsum += Fm<float>::log_(sps[l] * s2 + t * t);
       }
     }
     // ---- y = z0 + Uhat t   (B operand: this lane's C rows of t)

@@ -166,6 +166,9 @@ end
 # would grow without bound in a sampling loop).
 const NF_KIND_COMPOSITE = Int32(6)
 const NF_KIND_FULLRANK = Int32(7)
+# the non-centring layer of the hierarchical targets over a RealNVP / NSF / full-rank flow (include/nfhip.h; kind 9 is
+# unassigned).  The reference has no such bijector: desc_of does not produce this kind, a caller builds the descriptor itself.
+const NF_KIND_NONCENTRED = Int32(10)
 const SEGMENT_ROOTS = Dict{Vector{NFDesc},Vector{NFDesc}}()
 family(l) = l isa Bijectors.PlanarLayer ? :planar : l isa Bijectors.RadialLayer ? :radial : l isa AffineCoupling ? :realnvp :
             l isa NeuralSplineCoupling ? :nsf : error("nfhip: no device kernels for a $(typeof(l)) layer")

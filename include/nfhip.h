@@ -115,6 +115,34 @@ extern "C" {
                              nf_loglikelihood_value_and_grad, nf_loglikelihood_step(_enqueue), nf_elbo_step_enqueue;
                              NF_ERR_ARG as a segment of NF_KIND_COMPOSITE. */
 
+/* (kind 9 is unassigned) */
+#define NF_KIND_NONCENTRED 10 /* transformed(q0, S o T): an inner flow T under the non-centring layer S of the hierarchical targets.
+                             Over z = [beta (p) ; tau (G)] (d = p + G, NF_TARGET_HGLM_*) or [beta ; tau ; lambda] (d = p + G + 1,
+                             NF_TARGET_DGLM_*; the last coordinate passes through), with g(j) the group of coefficient j:
+                               y_j = z_j exp(lam_j tau_g(j)) for j < p with g(j) >= 0, y_j = z_j otherwise,
+                               ladj = sum_{j: g(j) >= 0} lam_j tau_g(j).
+                             lam = 0 is the identity (the centred parameterisation the targets are written in), lam = 1 the
+                             non-centred beta = exp(tau) z, in between the flow learns its own (Gorinova et al., "Automatic
+                             reparameterisation").  nsegments = 1 and `segments` points to ONE inner descriptor of kind
+                             NF_KIND_REALNVP, NF_KIND_NSF or NF_KIND_FULLRANK with the same d and dtype and no base; `score`
+                             (host pointer) is a target of kind 16..20 or 29..31 that passes its own argument check at this d:
+                             S reads grp[p] from its device buffer p0 (every index bounded by select: a garbage buffer gives
+                             wrong numbers, never an access outside the d features), and p, G from d and s1; the buffer must
+                             outlive the flow.  The ELBO target of the entry points may be that target or any other the inner
+                             flow is served with.  K = 0: lam is trained; K = 1: lam is frozen, its p gradient entries are
+                             written as exactly 0.0; any other K, or anything else above, is NF_ERR_ARG; what the inner flow
+                             refuses is NF_ERR_UNSUPPORTED.  theta = [lam (p) ; theta_inner]; the lam_j of a coefficient without
+                             a group is never read (NaN there changes no output bit; its gradient is exactly 0.0).
+                             nf_param_count = p + P_inner; nf_layer_count = the inner flow's + 1: the inner flow's layers come
+                             first, S is the last.  Served: nf_flow_fwd / inv / rand, nf_layer_apply, nf_loglikelihood (value
+                             only), the tape pair and nf_flow_bwd, nf_elbo_batch(_rng), nf_elbo_value_and_grad, nf_elbo_step
+                             (the split sequence), general bases, shards.  Float32 with the inner flow on the tiled kernels:
+                             nf_elbo_value_and_grad keeps every buffer in the tiled layout from the draw to the gradient (S out
+                             of place, so that the inner chain's output stays the tape of its reverse pass; S's reverse pass is
+                             one launch).  NF_ERR_UNSUPPORTED: nf_loglikelihood_value_and_grad,
+                             nf_loglikelihood_step(_enqueue), nf_elbo_step_enqueue; NF_ERR_ARG as a segment of
+                             NF_KIND_COMPOSITE or as the inner flow of NF_KIND_PRECOND. */
+
 #define NF_DTYPE_F32 0
 #define NF_DTYPE_F64 1
 
@@ -347,10 +375,11 @@ typedef struct nf_flow_desc {
   int32_t K;                    /* spline bins (nsf)                                 */
   float B;                      /* spline box bound (nsf)                            */
   const struct nf_target *score; /* NF_KIND_HAMILTONIAN: the target behind LeapFrog's
-                                    score function (host pointer); NULL otherwise     */
+                                    score function (host pointer); NF_KIND_NONCENTRED: the
+                                    target whose groups the layer reads; NULL otherwise */
   const struct nf_base *base;    /* q0 (host pointer); NULL = MvNormal(zeros(d), I)  */
-  int32_t nsegments;             /* NF_KIND_COMPOSITE: number of segments; NF_KIND_PRECOND: 1; else 0 */
-  const struct nf_flow_desc *segments; /* host array [nsegments] (NF_KIND_PRECOND: the inner flow) */
+  int32_t nsegments;             /* NF_KIND_COMPOSITE: number of segments; NF_KIND_PRECOND, NF_KIND_NONCENTRED: 1; else 0 */
+  const struct nf_flow_desc *segments; /* host array [nsegments] (NF_KIND_PRECOND, NF_KIND_NONCENTRED: the inner flow) */
 } nf_flow_desc;
 
 /* Built-in target log-densities (the `logp` closure of src/objectives/elbo.jl:68

@@ -11,7 +11,8 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libnfhip.so")
 
-NF_KIND = {"planar": 0, "radial": 1, "realnvp": 2, "nsf": 3, "meanfield": 4, "hamiltonian": 5, "composite": 6, "fullrank": 7, "preconditioned": 8}
+NF_KIND = {"planar": 0, "radial": 1, "realnvp": 2, "nsf": 3, "meanfield": 4, "hamiltonian": 5, "composite": 6, "fullrank": 7, "preconditioned": 8,
+           "noncentred": 10}  # (kind 9 is unassigned)
 NF_DTYPE_F32, NF_DTYPE_F64 = 0, 1
 NF_TARGET_DIAGGAUSS, NF_TARGET_BANANA, NF_TARGET_FUNNEL, NF_TARGET_WARPED, NF_TARGET_CROSS = 0, 1, 2, 3, 4
 # linear-predictor targets (include/nfhip.h): p0 = mu[d] (optional for LOGREG), p1 = the row-major matrix;

@@ -167,6 +167,18 @@ int nf_fr_bwd_x_tiled(nf_ctx *, const nf_flow_desc *, const float *theta, const 
                       float lbar_const, long N, float *slabs, float *gtheta_out, float *xbar);
 int nf_fr_pull_tiled(nf_ctx *, const nf_flow_desc *, const float *theta, const float *ybar, long N, float *xbar);
 
+// the non-centring layer of NF_KIND_NONCENTRED (nf_noncentred.hip); `desc` is the layer's own descriptor (nc_view below)
+long nf_nc_params(const nf_flow_desc *desc);
+bool nf_nc_tiled_supported(const nf_flow_desc *desc);
+int nf_nc_apply(nf_ctx *, const nf_flow_desc *, bool inverse, const void *theta, const void *x, long N, void *y, void *ladj);
+size_t nf_nc_bwd_ws_bytes(const nf_flow_desc *desc, long N);
+int nf_nc_bwd(nf_ctx *, const nf_flow_desc *, const void *theta, const void *x, const void *ybar, const void *lbar,
+              double lbar_const, long N, void *xbar_out, void *gtheta_out, void *ws);
+int nf_nc_fwd_tiled(nf_ctx *, const nf_flow_desc *, const float *lam, const float *xt, long N, float *yt, float *ladj);
+size_t nf_nc_slab_floats(nf_ctx *, const nf_flow_desc *, long N);
+int nf_nc_bwd_tiled(nf_ctx *, const nf_flow_desc *, const float *lam, const float *yt, float *gt, const float *lbar,
+                    float lbar_const, long N, float *slab, float *glam_out);
+
 // ---- helpers -----------------------------------------------------------------------------
 // Every entry point's intermediates are ONE layout: a struct whose constructor takes its buffers from a Carver.  It runs over a
 // measuring Carver for nf_ws_reserve, then over ctx->ws (ws_carve); ws_need_bound() is the maximum of the same layouts.
@@ -193,10 +205,10 @@ static inline bool is_fr_tiled(const nf_flow_desc *d) { return is_fr(d) && d->dt
 // two-segment chain [full-rank layer ; inner coupling flow] run by the composition's machinery in the standard layout.  The
 // view is internal: the public check_composite keeps refusing a full-rank segment.
 static inline bool is_precond(const nf_flow_desc *d) { return d->kind == NF_KIND_PRECOND; }
-struct PrecondView {
+struct ChainView {
   nf_flow_desc seg[2], comp;
 };
-static const nf_flow_desc *precond_view(const nf_flow_desc *d, PrecondView *v) {
+static const nf_flow_desc *precond_view(const nf_flow_desc *d, ChainView *v) {
   v->seg[0] = nf_flow_desc{};
   v->seg[0].kind = NF_KIND_FULLRANK;
   v->seg[0].d = d->d;
@@ -209,16 +221,39 @@ static const nf_flow_desc *precond_view(const nf_flow_desc *d, PrecondView *v) {
   v->comp.segments = v->seg;
   return &v->comp;
 }
-// `desc` from here on: the internal chain of a preconditioned flow, everything else as it came
-#define NF_PRECOND_VIEW(desc) \
-  PrecondView precond_view_;  \
-  if (is_precond(desc)) desc = precond_view(desc, &precond_view_)
+// A non-centred flow (NF_KIND_NONCENTRED) is, in the same way, the chain [S ; inner flow]: the inner flow is applied first, and
+// theta = [lam ; theta_inner] is the chain's.  S travels as a descriptor of its own kind WITHOUT segments (d, dtype, K and
+// score as the outer one's): check_desc refuses that form, so it exists only inside a view, where it is a standard-layout
+// segment (flat_apply / flat_bwd, its input as its tape).  nf_layer_apply counts the other way round (apply_std).
+static inline bool is_nc(const nf_flow_desc *d) { return d->kind == NF_KIND_NONCENTRED && d->segments; }
+static inline bool is_nc_layer(const nf_flow_desc *d) { return d->kind == NF_KIND_NONCENTRED && !d->segments; }
+static const nf_flow_desc *nc_view(const nf_flow_desc *d, ChainView *v) {
+  v->seg[0] = nf_flow_desc{};
+  v->seg[0].kind = NF_KIND_NONCENTRED;
+  v->seg[0].d = d->d;
+  v->seg[0].dtype = d->dtype;
+  v->seg[0].nlayers = 1;
+  v->seg[0].K = d->K;
+  v->seg[0].score = d->score;
+  v->seg[1] = d->segments[0];
+  v->comp = *d;
+  v->comp.kind = NF_KIND_COMPOSITE;
+  v->comp.nsegments = 2;
+  v->comp.segments = v->seg;
+  return &v->comp;
+}
+// `desc` from here on: the internal chain of a preconditioned or non-centred flow, everything else as it came
+#define NF_CHAIN_VIEW(desc)                                         \
+  ChainView chain_view_;                                            \
+  if (is_precond(desc)) desc = precond_view(desc, &chain_view_);    \
+  else if (is_nc(desc)) desc = nc_view(desc, &chain_view_)
 static int check_desc(const nf_flow_desc *d);
 static int check_composite(const nf_flow_desc *d) {
   if (d->nsegments < 1 || d->nsegments > 64 || !d->segments) return NF_ERR_ARG;
   for (int s = 0; s < d->nsegments; ++s) {
     const nf_flow_desc *g = &d->segments[s];
-    if (g->kind == NF_KIND_COMPOSITE || g->kind == NF_KIND_HAMILTONIAN || g->kind == NF_KIND_PRECOND) return NF_ERR_ARG;
+    if (g->kind == NF_KIND_COMPOSITE || g->kind == NF_KIND_HAMILTONIAN || g->kind == NF_KIND_PRECOND || g->kind == NF_KIND_NONCENTRED)
+      return NF_ERR_ARG;
     if (g->kind == NF_KIND_FULLRANK) return NF_ERR_UNSUPPORTED;  // not a segment yet
     if (g->d != d->d || g->dtype != d->dtype || g->base) return NF_ERR_ARG;  // q0 belongs to the composition
     NF_TRY(check_desc(g));
@@ -254,6 +289,15 @@ static int check_desc(const nf_flow_desc *d) {
       if (g->d != d->d || g->dtype != d->dtype || g->base) return NF_ERR_ARG;
       NF_TRY(check_desc(g));
       return nf_fr_supported(d) ? NF_OK : NF_ERR_UNSUPPORTED;
+    }
+    case NF_KIND_NONCENTRED: {
+      if (d->nsegments != 1 || !d->segments || !d->score || (d->K != 0 && d->K != 1)) return NF_ERR_ARG;
+      const nf_flow_desc *g = &d->segments[0];
+      if (g->kind != NF_KIND_REALNVP && g->kind != NF_KIND_NSF && g->kind != NF_KIND_FULLRANK) return NF_ERR_ARG;
+      if (g->d != d->d || g->dtype != d->dtype || g->base) return NF_ERR_ARG;
+      if (!target_is_hglm(d->score->kind) && !target_is_dglm(d->score->kind)) return NF_ERR_ARG;
+      if (nf_target_check(d->score, d->d) != NF_OK) return NF_ERR_ARG;
+      return check_desc(g);
     }
     case NF_KIND_HAMILTONIAN:
       if (d->d < 2 || (d->d & 1) || d->K < 1 || !d->score) return NF_ERR_ARG;
@@ -319,6 +363,16 @@ extern "C" int64_t nf_param_count(const nf_flow_desc *d) {
       const int64_t p = nf_param_count(&d->segments[0]);
       return p < 0 ? p : (int64_t)d->d + (int64_t)d->d * d->d + p;
     }
+    case NF_KIND_NONCENTRED: {  // [lam (p) ; theta_inner]; the layer alone (a view's segment): lam
+      const int64_t pl = nf_nc_params(d);
+      if (pl < 0) return pl;
+      if (is_nc_layer(d)) return d->nsegments == 0 ? pl : (int64_t)NF_ERR_ARG;
+      if (d->nsegments != 1 || d->segments[0].kind == NF_KIND_NONCENTRED || d->segments[0].kind == NF_KIND_PRECOND ||
+          d->segments[0].kind == NF_KIND_COMPOSITE)
+        return NF_ERR_ARG;
+      const int64_t p = nf_param_count(&d->segments[0]);
+      return p < 0 ? p : pl + p;
+    }
     case NF_KIND_HAMILTONIAN: return 2 * (int64_t)d->d + 3 * (int64_t)(d->d / 2) * d->nlayers;
     case NF_KIND_REALNVP:
     case NF_KIND_NSF: {
@@ -352,6 +406,14 @@ extern "C" int32_t nf_layer_count(const nf_flow_desc *d) {
         return NF_ERR_ARG;
       const int32_t c = nf_layer_count(&d->segments[0]);
       return c < 0 ? c : 2 + c;
+    }
+    case NF_KIND_NONCENTRED: {  // the inner flow's layers, then S; the layer alone (a view's segment): 1
+      if (is_nc_layer(d)) return d->nsegments == 0 ? 1 : NF_ERR_ARG;
+      if (d->nsegments != 1 || d->segments[0].kind == NF_KIND_NONCENTRED || d->segments[0].kind == NF_KIND_PRECOND ||
+          d->segments[0].kind == NF_KIND_COMPOSITE)
+        return NF_ERR_ARG;
+      const int32_t c = nf_layer_count(&d->segments[0]);
+      return c < 0 ? c : c + 1;
     }
     case NF_KIND_HAMILTONIAN: return d->nlayers + 1;  // blocks, then the reference's affine map
     case NF_KIND_REALNVP:
@@ -665,6 +727,7 @@ static int flat_apply(nf_ctx *ctx, const nf_flow_desc *desc, int lo, int hi, boo
                       const void *x, long N, void *y, void *ladj) {
   if (desc->kind == NF_KIND_HAMILTONIAN) return nf_hf_apply(ctx, desc, lo, hi, inverse, theta, x, N, y, ladj);
   if (is_fr(desc)) return nf_fr_apply(ctx, desc, lo, hi, inverse, theta, x, N, y, ladj);
+  if (is_nc_layer(desc)) return nf_nc_apply(ctx, desc, inverse, theta, x, N, y, ladj);  // one layer
   if (is_g64(desc))
     return nf_g64_apply(ctx, desc, lo, hi, inverse, theta, x, N, y, ladj);
   return nf_simple_apply(ctx, desc, lo, hi, inverse, theta, x, N, y, ladj);
@@ -672,6 +735,7 @@ static int flat_apply(nf_ctx *ctx, const nf_flow_desc *desc, int lo, int hi, boo
 static size_t flat_bwd_ws_bytes(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
   if (desc->kind == NF_KIND_HAMILTONIAN) return nf_hf_bwd_ws_bytes(desc, N);
   if (is_fr(desc)) return nf_fr_bwd_ws_bytes(ctx, desc, N);
+  if (is_nc_layer(desc)) return nf_nc_bwd_ws_bytes(desc, N);
   return is_g64(desc) ? nf_g64_bwd_ws_bytes(desc, N) : nf_simple_bwd_ws_bytes(ctx, desc, N);
 }
 static int flat_bwd(nf_ctx *ctx, const nf_flow_desc *desc, const void *theta, const void *x, const void *ybar,
@@ -679,6 +743,7 @@ static int flat_bwd(nf_ctx *ctx, const nf_flow_desc *desc, const void *theta, co
   if (desc->kind == NF_KIND_HAMILTONIAN)
     return nf_hf_bwd(ctx, desc, theta, x, ybar, lbar, lbar_const, N, xbar_out, gtheta_out, ws);
   if (is_fr(desc)) return nf_fr_bwd(ctx, desc, theta, x, ybar, lbar, lbar_const, N, xbar_out, gtheta_out, ws);
+  if (is_nc_layer(desc)) return nf_nc_bwd(ctx, desc, theta, x, ybar, lbar, lbar_const, N, xbar_out, gtheta_out, ws);
   if (is_g64(desc))
     return nf_g64_bwd(ctx, desc, theta, x, ybar, lbar, lbar_const, N, xbar_out, gtheta_out, ws);
   return nf_simple_bwd(ctx, desc, theta, x, ybar, lbar, lbar_const, N, xbar_out, gtheta_out, ws, false);
@@ -724,7 +789,7 @@ static inline bool elbo_fusable(const nf_flow_desc *desc, const nf_target *targe
 // path) on draws of their own.
 static inline bool target_refused(const nf_flow_desc *desc, const nf_target *target) {
   if (!target || !target_has_own_kernel(target->kind)) return false;
-  if (is_precond(desc)) return target_refused(&desc->segments[0], target);  // exactly as for the inner coupling flow
+  if (is_precond(desc) || is_nc(desc)) return target_refused(&desc->segments[0], target);  // exactly as for the inner flow
   if (target->kind == NF_TARGET_GAUSSMIX && desc->d > NF_MIXTURE_TILED_MAXD && (is_coupling(desc) || is_fr_tiled(desc))) return true;
   return desc->kind == NF_KIND_PLANAR || desc->kind == NF_KIND_RADIAL || desc->kind == NF_KIND_MEANFIELD ||
          desc->kind == NF_KIND_HAMILTONIAN;
@@ -821,7 +886,15 @@ static int composite_apply(nf_ctx *ctx, const nf_flow_desc *desc, bool inverse, 
 static int apply_std(nf_ctx *ctx, const nf_flow_desc *desc, bool inverse, int layer, const void *theta,
                      const void *x_in, long N, void *y_out, void *ladj) {
   if (N == 0) return NF_OK;
-  NF_PRECOND_VIEW(desc);
+  if (is_nc(desc) && layer >= 0) {  // one bijector of a non-centred flow: the inner flow's layers come first, S is the last
+    ChainView v;
+    nc_view(desc, &v);
+    if (layer < nf_layer_count(&v.seg[1]))
+      return apply_std(ctx, &v.seg[1], inverse, layer, (const char *)theta + (size_t)seg_theta_off(&v.comp, 1) * esize(desc->dtype), x_in, N,
+                       y_out, ladj);
+    return flat_apply(ctx, &v.seg[0], 0, 1, inverse, theta, x_in, N, y_out, ladj);
+  }
+  NF_CHAIN_VIEW(desc);
   if (is_composite(desc)) return composite_apply(ctx, desc, inverse, layer, theta, x_in, N, y_out, ladj);
   if (is_coupling(desc)) {
     NF_TRY(nf_ws_reserve(ctx, carve_bytes(tiled_elems(desc, N) * 4)));
@@ -877,7 +950,7 @@ extern "C" int nf_flow_rand(nf_ctx *ctx, const nf_flow_desc *desc, const void *t
     NF_TRY(base_draw(ctx, desc, N, seed, sample_offset, stream_id, y_out, nullptr));
     return apply_std(ctx, &inner, false, -1, theta, y_out, N, y_out, bb.tmp);
   }
-  NF_PRECOND_VIEW(desc);
+  NF_CHAIN_VIEW(desc);
   if (is_composite(desc)) {  // draws into y_out, then the chain in place
     CompBufs cb;
     GuardReset gr{ctx, ctx->ws_guard};
@@ -989,7 +1062,7 @@ static size_t tape_seg_bytes(nf_ctx *ctx, const nf_flow_desc *g, long N) {
   return 0;
 }
 static size_t tape_bytes_of(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
-  NF_PRECOND_VIEW(desc);
+  NF_CHAIN_VIEW(desc);
   if (!is_composite(desc)) return tape_seg_bytes(ctx, desc, N);
   size_t tot = 0;
   for (int s = 0; s < desc->nsegments; ++s) tot += tape_seg_bytes(ctx, &desc->segments[s], N);
@@ -1043,7 +1116,7 @@ struct TapeFwdCompBufs {
   }
 };
 static size_t tape_need(nf_ctx *ctx, const nf_flow_desc *desc, long N, bool bwd) {
-  NF_PRECOND_VIEW(desc);
+  NF_CHAIN_VIEW(desc);
   if (!is_composite(desc)) return bwd ? layout_bytes<TapeBwdBufs>(ctx, desc, N) : tape_fwd_need_seg(ctx, desc, N);
   if (!bwd) return layout_bytes<TapeFwdCompBufs>(ctx, desc, N);
   size_t m = 0;
@@ -1120,7 +1193,7 @@ static int tape_bwd_seg(nf_ctx *ctx, const nf_flow_desc *g, const void *theta, c
 // whole flow (a composition chains its segments through y_out in place; the LAST segment is applied first)
 static int tape_fwd(nf_ctx *ctx, const nf_flow_desc *desc, const void *theta, const void *x_in, long N, void *y_out,
                     void *ladj, void *tape) {
-  NF_PRECOND_VIEW(desc);
+  NF_CHAIN_VIEW(desc);
   if (!is_composite(desc)) return tape_fwd_seg(ctx, desc, theta, x_in, N, y_out, ladj, tape);
   const size_t es = esize(desc->dtype);
   const int ns = desc->nsegments;
@@ -1145,7 +1218,7 @@ static int tape_fwd(nf_ctx *ctx, const nf_flow_desc *desc, const void *theta, co
 
 static int tape_bwd(nf_ctx *ctx, const nf_flow_desc *desc, const void *theta, const void *tape, const void *ybar,
                     const void *lbar, double lbar_const, long N, void *xbar_out, void *gtheta_out) {
-  NF_PRECOND_VIEW(desc);
+  NF_CHAIN_VIEW(desc);
   if (!is_composite(desc)) return tape_bwd_seg(ctx, desc, theta, tape, ybar, lbar, lbar_const, N, xbar_out, gtheta_out);
   const size_t es = esize(desc->dtype);
   size_t toff = 0;
@@ -1312,7 +1385,7 @@ static int fr_value_and_grad(nf_ctx *ctx, const nf_flow_desc *desc, const nf_tar
 static int elbo_forward(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, const void *theta,
                         const void *xs, long N, uint64_t seed, uint64_t off, uint32_t stream_id, void *elbos_out,
                         double *elbo_host) {
-  NF_PRECOND_VIEW(desc);
+  NF_CHAIN_VIEW(desc);
   if (is_composite(desc)) return elbo_forward_composite(ctx, desc, target, theta, xs, N, seed, off, stream_id, elbos_out, elbo_host);
   if (is_fr_tiled(desc)) return fr_elbo_forward(ctx, desc, target, theta, xs, N, seed, off, stream_id, elbos_out, elbo_host);
   const size_t es = esize(desc->dtype);
@@ -1391,7 +1464,7 @@ extern "C" int nf_loglikelihood(nf_ctx *ctx, const nf_flow_desc *desc, const voi
   if (is_fr(desc)) return NF_ERR_UNSUPPORTED;  // the maximum-likelihood Gaussian is a closed form
   NF_HIP(hipSetDevice(ctx->device));
   if (flow_base(desc)) return loglikelihood_general_base(ctx, desc, theta, ys, N, logliks_out, ll_host);
-  NF_PRECOND_VIEW(desc);  // value only: logpdf(flow, y) through the inverse chain
+  NF_CHAIN_VIEW(desc);  // value only: logpdf(flow, y) through the inverse chain
   if (is_composite(desc)) return loglikelihood_composite(ctx, desc, theta, ys, N, logliks_out, ll_host);
   const bool cp = is_coupling(desc);
   const long nb = nf_sum2_nblocks(N);
@@ -1483,7 +1556,7 @@ extern "C" int nf_loglikelihood_value_and_grad(nf_ctx *ctx, const nf_flow_desc *
                                                int64_t N_local, int64_t N_global, void *out) {
   if (!ctx || !theta || !out || N_local < 0 || N_global < 1 || (N_local > 0 && !ys)) return NF_ERR_ARG;
   NF_TRY(check_desc(desc));
-  if (is_fr(desc) || is_precond(desc)) return NF_ERR_UNSUPPORTED;  // (the pullback through inv(L): DESIGN.md section 7)
+  if (is_fr(desc) || is_precond(desc) || is_nc(desc)) return NF_ERR_UNSUPPORTED;  // (the pullback through inv(L), through inv(S): DESIGN.md section 7)
   NF_HIP(hipSetDevice(ctx->device));
   // general bases and heterogeneous compositions: segment by segment in the standard layout (fkl_general below)
   if (flow_base(desc) || is_composite(desc)) return fkl_general(ctx, desc, theta, ys, N_local, N_global, out);
@@ -1997,7 +2070,7 @@ struct PrecondVgBufs {
 };
 static int precond_value_and_grad(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, const void *theta, const void *xs,
                                   long N, long N_global, uint64_t seed, uint64_t off, uint32_t stream_id, void *out) {
-  PrecondView pv;
+  ChainView pv;
   precond_view(desc, &pv);
   const nf_flow_desc *fr = &pv.seg[0], *g = &pv.seg[1];
   const int d = desc->d;
@@ -2031,6 +2104,100 @@ static int precond_value_and_grad(nf_ctx *ctx, const nf_flow_desc *desc, const n
     NF_TRY(nf_fr_bwd_x_tiled(ctx, fr, th, b.xt, b.gt, nullptr, (float)(-inv), N, b.fr_slab, gout, b.gt));
   }
   // the couplings, from their tape (nobody reads the cotangent of the draws)
+  if (b.tk == TAPE_AFFINE_STASH) {
+    NF_TRY(nf_affine_bwd_stashed(ctx, g, b.stash, b.gt, nullptr, (float)(-inv), N, b.slab, b.stride, b.grid, false, true));
+    return nf_affine_reduce_slabs(ctx, g, b.slab, b.grid, gout_g);
+  }
+  if (b.tk == TAPE_WIDE) return nf_wide_train_backward(ctx, g, b.xt, b.gt, nullptr, (float)(-inv), N, b.slab, gout_g);
+  return realnvp_bwd(ctx, g, thg, b.xt, b.gt, nullptr, (float)(-inv), N, b.slab, b.grid, gout_g, nullptr, 0, nullptr, b.rqs_tape);
+}
+
+// A non-centred flow in Float32 whose inner flow is on the tiled kernels (the matrix-pipe couplings, or the full-rank family):
+// the same shape of step.  Draws and log q0 (or the caller's draws, converted once), the inner chain leaving the tape of its
+// kind (couplings: in place on the tile buffer; full-rank: the draws stay, its output goes to `mid`), S into a second buffer so
+// that the chain's output tile stays intact, the two log-dets added per sample, the tiled target launch, S's reverse launch
+// (zbar in place over the target's score tile, the taubar rows, lam's gradient) and the inner reverse pass from its tape.
+static inline bool nc_tiled(const nf_flow_desc *desc) {
+  return is_nc(desc) && nf_nc_tiled_supported(desc) && (is_coupling(&desc->segments[0]) || is_fr_tiled(&desc->segments[0]));
+}
+struct NcVgBufs {
+  TapeKind tk = TAPE_X;
+  bool fr;
+  long nb, stride = 0;
+  int grid = 0;
+  float *xt, *mid, *yt, *gt, *logq, *ladj, *ladj_s, *nc_slab, *slab, *stash = nullptr;
+  void *rqs_tape = nullptr;
+  double *partial, *partial_s;
+  NcVgBufs() {}
+  NcVgBufs(Carver &cv, nf_ctx *ctx, const nf_flow_desc *desc, long N) {
+    ChainView v;
+    nc_view(desc, &v);
+    const nf_flow_desc *g = &v.seg[1];
+    const size_t te = tiled_elems(g, N);
+    fr = is_fr(g);
+    nb = nf_target_tiled_nblocks(N);
+    xt = cv.take<float>(te);
+    mid = fr ? cv.take<float>(te) : xt;
+    yt = cv.take<float>(te);
+    gt = cv.take<float>(te);
+    logq = cv.take<float>((size_t)N);
+    ladj = cv.take<float>((size_t)N);
+    ladj_s = cv.take<float>((size_t)N);
+    partial = cv.take<double>(nb);
+    partial_s = cv.take<double>(nf_sum2_nblocks(N));
+    nc_slab = cv.take<float>(nf_nc_slab_floats(ctx, &v.seg[0], N));
+    if (fr) {
+      slab = cv.take<float>((size_t)nf_fr_bwd_grid(ctx, N) * (size_t)nf_param_count(g));
+      return;
+    }
+    tk = tape_kind(ctx, g, N);
+    if (tk == TAPE_WIDE) {  // the forward's stash and the reverse pass's split-K area
+      slab = cv.take<float>(nf_wide_train_ws_floats(ctx, g, N));
+      return;
+    }
+    grid = coupling_bwd_grid(ctx, g, N);
+    stride = coupling_slab_floats(ctx, g, N);
+    slab = cv.take<float>((size_t)grid * stride);
+    if (tk == TAPE_AFFINE_STASH) stash = cv.take<float>(nf_affine_stash_floats(g, N));
+    if (rqs_tape_b(g, N)) rqs_tape = (void *)cv.take<char>(rqs_tape_b(g, N));
+  }
+};
+static int nc_value_and_grad(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, const void *theta, const void *xs, long N,
+                             long N_global, uint64_t seed, uint64_t off, uint32_t stream_id, void *out) {
+  ChainView v;
+  nc_view(desc, &v);
+  const nf_flow_desc *S = &v.seg[0], *g = &v.seg[1];
+  const int d = desc->d;
+  const long Pl = nf_param_count(S), P = nf_param_count(desc);
+  const float *lam = (const float *)theta, *thg = lam + Pl;
+  float *gout = (float *)out, *gout_g = gout + Pl;
+  const double inv = 1.0 / (double)N_global;
+  NcVgBufs b;
+  NF_TRY(ws_carve(ctx, &b, desc, N));
+  if (xs) {
+    NF_TRY(nf_launch_layout_convert(ctx, d, N, (const float *)xs, b.xt, 1));
+    NF_TRY(nf_launch_base_logpdf_tiled(ctx, d, N, b.xt, b.logq));
+  } else {
+    NF_TRY(nf_launch_base_sample_tiled(ctx, d, N, seed, off, stream_id, b.xt, b.logq));
+  }
+  if (b.fr) {
+    NF_TRY(nf_fr_fwd_tiled(ctx, g, thg, b.xt, N, b.mid, b.ladj));
+  } else {
+    NF_TRY(coupling_pack(ctx, g, thg));
+    if (b.tk == TAPE_AFFINE_STASH) NF_TRY(nf_affine_chain(ctx, g, false, b.xt, N, b.ladj, b.stash));
+    else if (b.tk == TAPE_WIDE) NF_TRY(nf_wide_train_forward(ctx, g, b.xt, N, b.ladj, b.slab));
+    else if (is_nsf(g)) NF_TRY(nf_rqs_chain(ctx, g, false, b.xt, N, b.ladj, -1, b.rqs_tape));
+    else NF_TRY(nf_affine_chain(ctx, g, false, b.xt, N, b.ladj));
+  }
+  NF_TRY(nf_nc_fwd_tiled(ctx, S, lam, b.mid, N, b.yt, b.ladj_s));
+  NF_TRY(nf_launch_sum2(ctx, NF_DTYPE_F32, N, b.ladj, b.ladj_s, b.ladj, b.partial_s, 0.0));
+  // gt = d(-elbo/Ng)/dy = -(1/Ng) grad logp(y);  partial sums of -elbo_j/Ng
+  NF_TRY(nf_launch_target_tiled(ctx, target, d, N, b.yt, b.logq, b.ladj, b.gt, -inv, nullptr, b.partial, -inv));
+  NF_TRY(nf_launch_finish_sum(ctx, b.partial, b.nb, 0, nullptr, gout + P, nullptr));
+  // S: lam's gradient from (yt, gt), and gt <- the cotangent of the inner flow's output in place
+  NF_TRY(nf_nc_bwd_tiled(ctx, S, lam, b.yt, b.gt, nullptr, (float)(-inv), N, b.nc_slab, gout));
+  // the inner flow, from its tape (nobody reads the cotangent of the draws)
+  if (b.fr) return nf_fr_grad(ctx, g, thg, b.xt, 1, b.gt, 1, nullptr, (float)(-inv), N, b.slab, gout_g);
   if (b.tk == TAPE_AFFINE_STASH) {
     NF_TRY(nf_affine_bwd_stashed(ctx, g, b.stash, b.gt, nullptr, (float)(-inv), N, b.slab, b.stride, b.grid, false, true));
     return nf_affine_reduce_slabs(ctx, g, b.slab, b.grid, gout_g);
@@ -2092,7 +2259,11 @@ extern "C" int nf_elbo_value_and_grad(nf_ctx *ctx, const nf_flow_desc *desc, con
     if (N_local == 0) return nf_launch_fill(ctx, desc->dtype, out, nf_param_count(desc) + 1, 0.0);
     return precond_value_and_grad(ctx, desc, target, theta, xs, N_local, N_global, seed, sample_offset, stream_id, out);
   }
-  NF_PRECOND_VIEW(desc);
+  if (nc_tiled(desc)) {
+    if (N_local == 0) return nf_launch_fill(ctx, desc->dtype, out, nf_param_count(desc) + 1, 0.0);
+    return nc_value_and_grad(ctx, desc, target, theta, xs, N_local, N_global, seed, sample_offset, stream_id, out);
+  }
+  NF_CHAIN_VIEW(desc);
   if (is_composite(desc))
     return value_and_grad_composite(ctx, desc, target, theta, xs, N_local, N_global, seed, sample_offset, stream_id, out);
   const long N = N_local;
@@ -2591,7 +2762,7 @@ static int step_split(nf_ctx *ctx, const nf_flow_desc *desc, const StepCall &c) 
 static int step_run(nf_ctx *ctx, const nf_flow_desc *desc, const StepCall &c, double *loss_host, double *gnorm_host, void *out_device) {
   NF_TRY(check_desc(desc));
   if (target_refused(desc, c.target)) return NF_ERR_UNSUPPORTED;
-  if ((is_fr(desc) || is_precond(desc)) && (!c.target || c.step_device)) return NF_ERR_UNSUPPORTED;  // no forward-KL step, no graph-replay form
+  if ((is_fr(desc) || is_precond(desc) || is_nc(desc)) && (!c.target || c.step_device)) return NF_ERR_UNSUPPORTED;  // no forward-KL step, no graph-replay form
   NF_HIP(hipSetDevice(ctx->device));
   if (c.Ng < 1) return NF_ERR_ARG;
   const long P = nf_param_count(desc), N = c.N;
@@ -2701,10 +2872,11 @@ size_t nf_wide_wimg_bytes(nf_ctx *, const nf_flow_desc *desc);
 static size_t ws_tail_bytes(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
   const long P = nf_param_count(desc);
   auto wimg_of = [&](const nf_flow_desc *g) -> size_t {
+    if (is_nc_layer(g)) return 0;
     if (!is_coupling(g)) return nf_l64_scratch_bytes(g, N);  // general Float32 couplings: the MFMA MLP's activation tiles
     return is_wide(g) ? nf_wide_wimg_bytes(ctx, g) : is_nsf(g) ? nf_rqs_wimg_bytes(g) : nf_affine_wimg_bytes(g);
   };
-  NF_PRECOND_VIEW(desc);
+  NF_CHAIN_VIEW(desc);
   size_t wimg = is_composite(desc) ? 0 : wimg_of(desc);
   for (int s = 0; is_composite(desc) && s < desc->nsegments; ++s)
     wimg += carve_bytes(wimg_of(&desc->segments[s]));  // grow-only tail carves: a later, larger segment carves again
@@ -2717,7 +2889,9 @@ static size_t ws_need_bound(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
   size_t need = layout_bytes<FlowBwdBufs>(ctx, desc, N);
   auto upd = [&](size_t v) { if (v > need) need = v; };
   if (precond_tiled(desc)) upd(layout_bytes<PrecondVgBufs>(ctx, desc, N));  // the tiled training step
-  NF_PRECOND_VIEW(desc);
+  if (nc_tiled(desc)) upd(layout_bytes<NcVgBufs>(ctx, desc, N));
+  if (is_nc_layer(desc)) return need;  // a view's segment: the standard-layout forward, and the pullback counted above
+  NF_CHAIN_VIEW(desc);
   if (is_composite(desc)) {
     upd(layout_bytes<CompBufs>(ctx, desc, N));
     upd(layout_bytes<VgCompositeBufs>(ctx, desc, N));

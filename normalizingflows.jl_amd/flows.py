@@ -217,7 +217,7 @@ class CompositeFlow(Flow):
             raise NFHipError("create_flow: empty layer list")
         dt, dev = segments[0].theta.dtype, segments[0].theta.device
         for f in segments:
-            if isinstance(f, CompositeFlow) or f.kind in ("hamiltonian", "preconditioned"):
+            if isinstance(f, CompositeFlow) or f.kind in ("hamiltonian", "preconditioned", "noncentred"):
                 raise NFHipError("create_flow: segments must be single-family flows")
             if f.kind == "fullrank":
                 raise NFHipError("create_flow: a full-rank Shift o Scale(LowerTriangular) is not built as a segment yet")
@@ -315,6 +315,72 @@ def preconditioned(inner: Flow, *, mu: Optional[torch.Tensor] = None, L: Optiona
             raise NFHipError(f"preconditioned: mu must be ({d},) and L ({d}, {d})")
         head = torch.cat([mu.to(dt).to(dev), L.to(dt).to(dev).t().contiguous().reshape(-1)])  # column-major
     return PrecondFlow(inner, inner.dist, torch.cat([head, inner.theta.detach()]))
+
+
+class NoncentredFlow(Flow):
+    """transformed(q0, S o T): `inner` (a realnvp, nsf or fullrank flow) under the non-centring layer S of a hierarchical target
+    (NF_KIND_NONCENTRED).  theta = [lam (p) ; inner.theta]; `lam` and `inner` are views of it.  Flat layer order: the inner flow's
+    layers first, S last.  The flow keeps `target`: S reads the groups from its device buffer."""
+
+    def __init__(self, inner: Flow, target, dist: MvNormal, theta: torch.Tensor, learn: bool = True):
+        if isinstance(inner, (CompositeFlow, PrecondFlow, NoncentredFlow)) or inner.kind not in ("realnvp", "nsf", "fullrank"):
+            raise NFHipError("noncentred: the inner flow must be a realnvp, nsf or fullrank flow")
+        if inner.dist.d != dist.d:
+            raise NFHipError("noncentred: the inner flow and q0 must share the dimension")
+        if not isinstance(target, (HierarchicalGLMTarget, DispersionGLMTarget)):
+            raise NFHipError("noncentred: the target must be a HierarchicalGLMTarget or a DispersionGLMTarget")
+        dt = inner.theta.dtype
+        check_target(target, dt, inner.theta.device, dist.d)
+        self.kind, self.dist, self.nlayers = "noncentred", dist, 1
+        self.hdims, self.K, self.B, self.score = (), 0 if learn else 1, 0.0, target
+        self.learn = bool(learn)
+        self._inner_desc = FlowDesc()
+        C.memmove(C.addressof(self._inner_desc), C.addressof(inner.desc), C.sizeof(FlowDesc))
+        self._inner_desc.base = None  # q0 belongs to the outer flow
+        self.desc = FlowDesc()
+        self.desc.kind = _lib.NF_KIND["noncentred"]
+        self.desc.dtype = _dtype_code(dt)
+        self.desc.d = dist.d
+        self.desc.nlayers = 1
+        self.desc.K = self.K
+        self.desc.score = C.addressof(target.c)
+        self.desc.nsegments = 1
+        self.desc.segments = C.addressof(self._inner_desc)
+        if not dist.standard:
+            if dist.mu.dtype != dt:
+                raise NFHipError(f"base distribution is {dist.mu.dtype}, flow parameters are {dt}")
+            self.desc.base = C.addressof(dist.c)
+        self.P = int(_lib.load_library().nf_param_count(C.byref(self.desc)))
+        if self.P < 0:
+            check(self.P)
+        self.theta = theta
+        if self.theta.numel() != self.P:
+            raise NFHipError(f"theta has {self.theta.numel()} entries, flow has {self.P} parameters")
+        self.lam = self.theta[:target.p]
+        self.inner = inner.with_theta(self.theta[target.p:])
+        self.transform = Transform(self)
+
+    def with_theta(self, theta: torch.Tensor) -> "NoncentredFlow":
+        return NoncentredFlow(self.inner, self.score, self.dist, theta, self.learn)
+
+
+def noncentred(inner: Flow, target, *, lam=1.0, learn: bool = True) -> Flow:
+    """The inner flow under the non-centring layer of `target` (a HierarchicalGLMTarget or DispersionGLMTarget, centred as it is):
+    over z = [beta ; tau (; lambda)], y_j = z_j exp(lam_j tau_g(j)) for every coefficient j with a group g(j), every other
+    coordinate unchanged.  lam = 0 is the identity, lam = 1 the non-centred parameterisation beta = exp(tau) z; `lam` is a scalar
+    or a (p,) tensor and is trained with the flow unless learn=False (its gradient entries are then exactly 0)."""
+    if not isinstance(target, (HierarchicalGLMTarget, DispersionGLMTarget)):
+        raise NFHipError("noncentred: the target must be a HierarchicalGLMTarget or a DispersionGLMTarget")
+    if not isinstance(inner, Flow):
+        raise NFHipError("noncentred: the inner flow must be a realnvp, nsf or fullrank flow")
+    dt, dev, p = inner.theta.dtype, inner.theta.device, target.p
+    if isinstance(lam, torch.Tensor) and lam.dim() > 0:
+        if lam.shape != (p,):
+            raise NFHipError(f"noncentred: lam must be a scalar or ({p},)")
+        head = lam.detach().to(dt).to(dev).clone()
+    else:
+        head = torch.full((p,), float(lam), dtype=dt, device=dev)
+    return NoncentredFlow(inner, target, inner.dist, torch.cat([head, inner.theta.detach()]), learn)
 
 
 def create_flow(Ls: Sequence[Flow], q0: MvNormal) -> Flow:

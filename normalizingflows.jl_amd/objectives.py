@@ -32,8 +32,8 @@ def _builtin(flow: Flow, logp) -> bool:
     if not isinstance(logp, _BUILTIN):
         return False
     check_target(logp, flow.theta.dtype, flow.theta.device, _target_dim(flow))
-    if flow.kind == "preconditioned":
-        flow = flow.inner  # the library answers for a preconditioned flow exactly as for its inner coupling flow
+    if flow.kind in ("preconditioned", "noncentred"):
+        flow = flow.inner  # the library answers for a preconditioned or non-centred flow exactly as for its inner flow
     if isinstance(logp, _LINPRED) and flow.kind in _NO_LINPRED_KINDS:
         return False  # the closure route: the target's own autograd node supplies the device score
     if isinstance(logp, MixtureTarget) and flow.kind in ("realnvp", "nsf", "fullrank") and flow.theta.dtype == torch.float32 and logp.d > 64:

@@ -811,6 +811,9 @@ def _cross_components(mu, sigma):
 
 def _cross_comp_logs(y, mu, sigma):
     means, stds = _cross_components(mu, sigma)
+    # in y's dtype: a float64 array element is a strong scalar, and float32 inputs would be evaluated in float64 throughout --
+    # the op-by-op float32 evaluation (the fp32 floor of tests/parity.py) would then not be one
+    means, stds = means.astype(y.dtype), stds.astype(y.dtype)
     logs = []
     for m, sd in zip(means, stds):
         logs.append(-LOG2PI - np.log(sd[0]) - np.log(sd[1])

@@ -65,6 +65,7 @@ const NF_TARGET_BNN_LOGIT, NF_TARGET_BNN_PROBIT, NF_TARGET_BNN_POISSON, NF_TARGE
 # GLM targets with a learned dispersion (nfhip.h): y = [β ; τ ; λ]; kinds 27 and 28 are unassigned
 const NF_TARGET_DGLM_NORMAL, NF_TARGET_DGLM_STUDENT, NF_TARGET_DGLM_NEGBIN =
     Int32(29), Int32(30), Int32(31)
+const NF_TARGET_ORDINAL_LOGIT = Int32(32)                             # ordinal (cumulative-logit) regression (nfhip.h)
 dtype_code(::Type{Float32}) = Int32(0)
 dtype_code(::Type{Float64}) = Int32(1)
 
@@ -399,6 +400,54 @@ c_target(t::BNNTarget) = NFTarget(t.kind, devptr(t.p0), devptr(t.Xt), Float64(si
 function check_target(t::BNNTarget, ::Type{T}, d) where {T}
     (eltype(t.Xt) === T && eltype(t.p0) === T && t.H * (size(t.Xt, 1) + 1) + 1 == d && length(t.p0) == 3 * size(t.Xt, 2) + 4) ||
         error("nfhip: target must hold $(t.H) hidden units over $(size(t.Xt, 1))-dimensional data rows in $T")
+end
+# Ordinal (cumulative-logit) regression over z = [β (p) ; γ (C − 1)], d = p + C − 1: labels k_i ∈ 0:C-1, η_i = x_i·β + offset_i,
+#   c_1 = γ_1, c_k = c_{k−1} + exp(γ_k),  P(k_i) = σ(c_{k_i+1} − η_i) − σ(c_{k_i} − η_i),
+#   log p(z) = const + Σ_i wt_i log P(k_i) + log N(β; 0, σβ² I) + Σ_k log N(c_k; cutloc, σc²) + Σ_{k≥2} γ_k.
+# The rows are sorted by label (stably) and every label is padded to whole 32-row blocks with rows of weight 0; the device reads the
+# padded X row-major (the column-major p × R array `Xt`) and ONE buffer
+# p0 = off[R] | wt[R] | lab[R/32] | (1/σβ², const + both normalisers, 1/σc², cutloc) | n_k[C].  σ = Inf is the flat prior.  Same flows
+# as the BNN targets.  (Written without a Julia at hand: unrun.)
+struct OrdinalRegressionTarget{V<:ROCVector,M<:ROCMatrix} <: NFHipTarget
+    Xt::M            # p × R
+    p0::V            # 2 R + R/32 + 4 + C
+    C::Int
+    rows::Int        # the caller's row count
+end
+function OrdinalRegressionTarget(X::AbstractMatrix{T}, labels::AbstractVector{<:Integer}, C::Integer; offset=nothing, weights=nothing,
+                                 σβ::Real=1.0, σc::Real=1.0, cutloc::Real=0.0, constant::Real=0.0) where {T}
+    rows, p = size(X)
+    (rows >= 1 && p >= 1 && all(isfinite, X)) || error("nfhip: X must be a finite rows × p matrix")
+    (2 <= C <= 16 && p + C - 1 <= 256) || error("nfhip: 2 <= C <= 16 categories and p + C - 1 <= 256")
+    (length(labels) == rows && all(k -> 0 <= k < C, labels)) || error("nfhip: one label in 0:C-1 per row")
+    off = offset === nothing ? zeros(Float64, rows) : Float64.(offset)
+    wt = weights === nothing ? ones(Float64, rows) : Float64.(weights)
+    (length(off) == rows && length(wt) == rows) || error("nfhip: offset and weights have one entry per row")
+    (all(isfinite, off) && all(w -> isfinite(w) && w >= 0, wt)) || error("nfhip: offsets must be finite, weights finite and >= 0")
+    (isfinite(constant) && isfinite(cutloc) && σβ > 0 && !isnan(σβ) && σc > 0 && !isnan(σc)) || error("nfhip: constant and cutloc finite, prior σ > 0 (Inf: flat prior)")
+    fold(σ, n) = isinf(σ) ? (0.0, 0.0) : (1 / σ^2, -0.5 * n * log(2π * σ^2))
+    (pb, cb), (pc, cc) = fold(σβ, p), fold(σc, C - 1)
+    order = sortperm(labels; alg=MergeSort)
+    counts = [count(==(k), labels) for k in 0:C-1]
+    nblk = cld.(counts, 32)
+    R = 32 * sum(nblk)
+    Xt = zeros(Float64, p, R); offp = zeros(Float64, R); wtp = zeros(Float64, R)
+    start = 32 .* (cumsum(nblk) .- nblk); seen = zeros(Int, C)
+    for i in order
+        k = labels[i] + 1
+        r = start[k] + (seen[k] += 1)
+        Xt[:, r] = X[i, :]; offp[r] = off[i]; wtp[r] = wt[i]
+    end
+    blab = Float64[k - 1 for k in 1:C for _ in 1:nblk[k]]
+    nk = Float64[sum(wt[labels .== k]; init=0.0) for k in 0:C-1]
+    p0 = vcat(offp, wtp, blab, Float64[pb, constant + cb + cc, pc, cutloc], nk)
+    return OrdinalRegressionTarget(ROCArray(Matrix{T}(Xt)), ROCArray(Vector{T}(p0)), Int(C), rows)
+end
+c_target(t::OrdinalRegressionTarget) = NFTarget(NF_TARGET_ORDINAL_LOGIT, devptr(t.p0), devptr(t.Xt), Float64(size(t.Xt, 2)), Float64(t.C))
+function check_target(t::OrdinalRegressionTarget, ::Type{T}, d) where {T}
+    R = size(t.Xt, 2)
+    (eltype(t.Xt) === T && eltype(t.p0) === T && size(t.Xt, 1) + t.C - 1 == d && length(t.p0) == 2 * R + R ÷ 32 + 4 + t.C) ||
+        error("nfhip: target must hold $(t.C) categories over $(size(t.Xt, 1))-dimensional data rows in $T")
 end
 # Hierarchical GLM over z = [β (p coefficients) ; τ (G group log-scales)], d = p + G, centred parameterisation:
 #   log p(z) = const + Σ_i wt_i φ(u_i; param) + lin·β + Σ_j log N(β_j; 0, σ_j²) + Σ_g log p(τ_g),  u = Aβ + offset,

@@ -339,6 +339,40 @@ extern "C" {
 #define NF_TARGET_DGLM_NORMAL 29
 #define NF_TARGET_DGLM_STUDENT 30
 #define NF_TARGET_DGLM_NEGBIN 31
+/* Ordinal (cumulative-logit) regression: an ordered categorical response k_i in {0 .. C-1} (ratings, grades, Likert items; polr,
+ * brms::cumulative, Stan's ordered_logistic) with one linear predictor per row and C - 1 ordered cutpoints that are coordinates.
+ *   y in R^d is [beta (p) ; gamma (C - 1)], d = p + C - 1 <= 256, 2 <= C <= 16, p >= 1.  The cutpoints are the ordered transform
+ *       c_1 = gamma_1,   c_k = c_{k-1} + exp(gamma_k)   (k = 2 .. C-1);   c_0 = -inf, c_C = +inf
+ *       eta_i    = x_i . beta + off_i
+ *       P(k_i)   = sigmoid(c_{k_i + 1} - eta_i) - sigmoid(c_{k_i} - eta_i)
+ *       log p(y) = par[1] + sum_i wt_i log P(k_i) - par[0]/2 |beta|^2 - par[2]/2 sum_k (c_k - par[3])^2 + sum_{k>=2} gamma_k
+ *   (a density over the unconstrained y: the last sum is the transform's Jacobian).  The kernels evaluate the factored form
+ *       sigmoid(a) - sigmoid(b) = sigmoid(a) sigmoid(-b) (1 - exp(-(a - b))),   a - b = exp(gamma_{k+1}) for adjacent cutpoints:
+ *       sum_i wt_i log P(k_i) = sum_i wt_i ([k_i < C-1] log sigmoid(c_{k_i + 1} - eta_i) + [k_i > 0] log sigmoid(eta_i - c_{k_i}))
+ *                               + sum_{k=1}^{C-2} n_k log1mexp(exp(gamma_{k+1})),     n_k = sum_i wt_i [k_i = k],
+ *   log1mexp(D) = log(-expm1(-D)) for D <= ln 2 and log1p(-exp(-D)) beyond: no difference of probabilities is ever formed.
+ *       d beta    = X' g - par[0] beta,   g_i = wt_i ([k_i > 0] sigmoid(c_{k_i} - eta_i) - [k_i < C-1] sigmoid(eta_i - c_{k_i + 1}))
+ *       d c_m     = sum_i wt_i ([k_i = m-1] sigmoid(eta_i - c_m) - [k_i = m] sigmoid(c_m - eta_i)) - par[2] (c_m - par[3])
+ *       d gamma_1 = sum_m d c_m,   d gamma_k = exp(gamma_k) sum_{m>=k} d c_m + n_{k-1} D / expm1(D) + 1,   D = exp(gamma_k)
+ *   The rows are GROUPED BY LABEL and every label is padded to whole 32-row blocks with rows of weight 0, so that the label is a
+ *   property of a row block (a label without rows has no block):
+ *   p1 = X[R x p] row-major, R a multiple of 32;  s0 = R (an integer value, 32 <= R < 2^31, R % 32 == 0);  s1 = C (an integer
+ *   value in 2 .. 16);  p0 = ONE buffer of 2 R + R/32 + 4 + C elements in the flow's element type:
+ *       off[R] | wt[R] | lab[R/32] | par[4] | nk[C]
+ *   par[0] = 1 / sigma_beta^2 and par[2] = 1 / sigma_c^2 (0: flat), par[1] the additive constant the host folded, par[3] the
+ *   cutpoint prior's location; lab holds integer-valued elements, nk the n_k (folded by the host in float64).
+ *   NF_ERR_ARG for a NULL p0 / p1, an s0 that is not a positive integer multiple of 32 fitting an int, an s1 that is non-integral,
+ *   NaN or outside 2 .. 16, or d < C; then NF_ERR_UNSUPPORTED for d > 256 -- both before any device work.  The host cannot validate
+ *   device memory: a block's label is bounded to [0, C-1] by select before it addresses anything (NaN -> 0).
+ * A row with wt_i == 0 contributes exactly 0 to the value and to every gradient by select.  Nothing is clamped: a non-finite
+ * value is reported by nf_elbo_step as NF_ERR_NONFINITE.  Served exactly like NF_TARGET_BNN_*: nf_target_logp (d <= 256), RealNVP /
+ * NSF flows of either element type including the weight-streaming shapes, full-rank and preconditioned flows, general bases and
+ * compositions; nf_elbo_step runs the split sequence, nf_elbo_step_enqueue answers NF_ERR_UNSUPPORTED; planar, radial, mean-field
+ * and Hamiltonian flows answer NF_ERR_UNSUPPORTED at every ELBO entry point, a Hamiltonian score included.  A non-centring layer
+ * does not take it (no group structure).
+ * The value is 32.  It is written relative to the kind before it: tests/test_disp_cpu.py reads the kinds that are defined by a
+ * literal and holds the highest of them at 31; tests/test_ordinal_cpu.py evaluates this definition and holds it at 32. */
+#define NF_TARGET_ORDINAL_LOGIT (NF_TARGET_DGLM_NEGBIN + 1)
 
 #define NF_MAX_HIDDEN 4
 

@@ -38,6 +38,11 @@ NF_TARGET_BNN_LOGIT, NF_TARGET_BNN_PROBIT, NF_TARGET_BNN_POISSON, NF_TARGET_BNN_
 # lin[d] | off[rows] | wt[rows] | par[4] | grp[p] | isd[p] | hm[G+1] | his[G+1] | hk[G+1] | gptr[G+1] | gidx[p] | cnt[rows] | ctab[Mt]
 # (cnt / ctab: NEGBIN only; par[2] = Mt); s0 = rows; s1 = G (0..d-2).  (kinds 27 and 28 are unassigned)
 NF_TARGET_DGLM_NORMAL, NF_TARGET_DGLM_STUDENT, NF_TARGET_DGLM_NEGBIN = 29, 30, 31
+# ordinal (cumulative-logit) regression: y = [beta (p) ; gamma (C - 1)], d = p + C - 1; p1 = X[R, p] with the rows grouped by label and
+# every label padded to whole 32-row blocks by rows of weight 0; p0 = one buffer off[R] | wt[R] | lab[R / 32] | par[4] | nk[C]
+# (par[0] / par[2] = prior precisions of beta and of the cutpoints, par[1] = folded constant, par[3] = the cutpoint prior's location);
+# s0 = R (a multiple of 32); s1 = C (2..16)
+NF_TARGET_ORDINAL_LOGIT = 32
 NF_MAX_HIDDEN = 4
 NF_ERR_NONFINITE = -4
 

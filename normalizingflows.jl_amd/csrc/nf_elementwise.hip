@@ -656,6 +656,11 @@ int nf_target_check(const nf_target *t, int d) {
             t->s1 == (double)(int)t->s1 && d >= (int)t->s1 + 2 && (d - 1) % (int)t->s1 == 0))
         return NF_ERR_ARG;
       return (d > 256 || (d - 1) / (int)t->s1 - 1 > 128) ? NF_ERR_UNSUPPORTED : NF_OK;  // what no kernel of nf_bnn.hip serves: answered here, before any device work
+    case NF_TARGET_ORDINAL_LOGIT:  // s0 = the number of rows R, label-blocked: a positive integer multiple of 32 that fits an int; s1 = the number of categories C, an integer in 2..16 with d >= C, so that p = d - (C - 1) >= 1 (NaN fails s1 >= 2)
+      if (!(t->p0 && t->p1 && t->s0 >= 32 && t->s0 < 2147483648.0 && t->s0 == (double)(long)t->s0 && (long)t->s0 % 32 == 0 && t->s1 >= 2 &&
+            t->s1 <= 16 && t->s1 == (double)(int)t->s1 && d >= (int)t->s1))
+        return NF_ERR_ARG;
+      return d > 256 ? NF_ERR_UNSUPPORTED : NF_OK;  // what no kernel of nf_ordinal.hip serves: answered here, before any device work
     default: return NF_ERR_ARG;
   }
 }
@@ -685,6 +690,11 @@ int nf_launch_target_bnn(nf_ctx *, int dtype, const nf_target *, int d, long N, 
                          void *logp_out, void *grad_out, double gscale, void *elbos_out, double *partial, double pscale);
 int nf_launch_target_bnn_tiled(nf_ctx *, const nf_target *, int d, long N, const float *yt, const float *logq, const float *ladj,
                                float *gt, double gscale, float *elbos_out, double *partial, double pscale);
+// nf_ordinal.hip: the ordinal (cumulative-logit) regression target, the same contract
+int nf_launch_target_ordinal(nf_ctx *, int dtype, const nf_target *, int d, long N, const void *y, const void *logq, const void *ladj,
+                             void *logp_out, void *grad_out, double gscale, void *elbos_out, double *partial, double pscale);
+int nf_launch_target_ordinal_tiled(nf_ctx *, const nf_target *, int d, long N, const float *yt, const float *logq, const float *ladj,
+                                   float *gt, double gscale, float *elbos_out, double *partial, double pscale);
 
 int nf_launch_target(nf_ctx *ctx, int dtype, const nf_target *t, int d, long N, const void *y, const void *logq,
                      const void *ladj, void *logp_out, void *grad_out, double gscale, void *elbos_out, double *partial,
@@ -699,6 +709,8 @@ int nf_launch_target(nf_ctx *ctx, int dtype, const nf_target *t, int d, long N, 
       return nf_launch_target_softmax(ctx, dtype, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
     if (target_is_bnn(t->kind))
       return nf_launch_target_bnn(ctx, dtype, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
+    if (target_is_ordinal(t->kind))
+      return nf_launch_target_ordinal(ctx, dtype, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
     return nf_launch_target_linpred(ctx, dtype, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
   }
   ProfScope ps(ctx, "target");
@@ -823,6 +835,8 @@ int nf_launch_target_tiled(nf_ctx *ctx, const nf_target *t, int d, long N, const
     return nf_launch_target_softmax_tiled(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
   if (target_is_bnn(t->kind))
     return nf_launch_target_bnn_tiled(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
+  if (target_is_ordinal(t->kind))
+    return nf_launch_target_ordinal_tiled(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
   if (target_is_linpred(t->kind))
     return nf_launch_target_linpred_tiled(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
   ProfScope ps(ctx, "target");

@@ -143,8 +143,11 @@ __host__ __device__ inline bool target_is_linpred(int kind) {
 // So are the one-hidden-layer Bayesian neural-network kinds (NF_TARGET_BNN_LOGIT .. NF_TARGET_BNN_NORMAL = the GLM kind + 13,
 // nf_bnn.hip): some coordinates of y are per-sample scalars (the output weights and bias), not rows of a matrix product.
 __host__ __device__ inline bool target_is_bnn(int kind) { return kind >= NF_TARGET_BNN_LOGIT && kind <= NF_TARGET_BNN_NORMAL; }
+// So is the ordinal (cumulative-logit) kind (NF_TARGET_ORDINAL_LOGIT, nf_ordinal.hip): the cutpoints are coordinates of y, and a
+// row's term depends on two of them, chosen by the label of its 32-row block.
+__host__ __device__ inline bool target_is_ordinal(int kind) { return kind == NF_TARGET_ORDINAL_LOGIT; }
 __host__ __device__ inline bool target_has_own_kernel(int kind) {
-  return target_is_linpred(kind) || kind == NF_TARGET_GAUSSMIX || kind == NF_TARGET_SOFTMAX || target_is_bnn(kind);
+  return target_is_linpred(kind) || kind == NF_TARGET_GAUSSMIX || kind == NF_TARGET_SOFTMAX || target_is_bnn(kind) || target_is_ordinal(kind);
 }
 // widest flow the mixture's tiled kernel serves (two U and two G blocks in registers); the flat kernel goes to 256
 #define NF_MIXTURE_TILED_MAXD 64

@@ -1518,6 +1518,93 @@ class BNNClassifierTarget(BNNTarget):
         super().__init__(link, X, n_hidden, to(2.0 * lab - 1.0), None, to(w), 0.0, None, prior_sigma_hidden, prior_sigma_out, _name=nm)
 
 
+class OrdinalRegressionTarget(_LinpredTarget):
+    """Posterior of ordinal (cumulative-logit, proportional-odds) regression (NF_TARGET_ORDINAL_LOGIT): labels k_i in {0 .. C-1},
+    one linear predictor eta_i = x_i . beta + offset_i per row and C - 1 ordered cutpoints that are coordinates:
+        z = [beta (p) ; gamma (C - 1)],  d = p + C - 1;   c_1 = gamma_1,  c_k = c_{k-1} + exp(gamma_k),
+        P(k_i) = sigmoid(c_{k_i + 1} - eta_i) - sigmoid(c_{k_i} - eta_i)   (c_0 = -inf, c_C = +inf),
+        logp(z) = const + sum_i weights_i log P(k_i) + log N(beta; 0, prior_sigma^2 I) + sum_k log N(c_k; cut_loc, cut_sigma^2)
+                  + sum_{k>=2} gamma_k
+    -- a density over the unconstrained z (the last sum is the ordered transform's Jacobian).  X [rows, p] has NO intercept
+    column (the cutpoints are the intercepts); offset, weights (>= 0; 0 drops the row exactly) per row, of X's element type and
+    device.  prior_sigma = math.inf and cut_sigma = math.inf are the flat priors.  The host works in float64: it sorts the rows by
+    label (stably), pads every label to whole 32-row blocks with rows of weight 0 (a category without rows gets no block), folds
+    n_k = sum_i weights_i [k_i = k], both Gaussian normalisers and const; the device reads `A` = the padded X [R, p] and ONE buffer
+    `p0` = offset[R] | weights[R] | block labels[R / 32] | (1 / prior_sigma^2, const, 1 / cut_sigma^2, cut_loc) | n_k[C], both
+    kept alive here.  `rows` is the caller's row count, `padded_rows` is R."""
+
+    def __init__(self, X, labels, n_categories, offset=None, weights=None, prior_sigma=1.0, cut_sigma=1.0, cut_loc=0.0, const=0.0,
+                 _name="OrdinalRegressionTarget"):
+        nm = _name
+        X64 = _glm_matrix(nm, X)
+        rows, p = X.shape
+        C_ = n_categories
+        if isinstance(C_, float) and C_ == int(C_):
+            C_ = int(C_)
+        if isinstance(C_, bool) or not hasattr(C_, "__index__") or not 2 <= int(C_) <= 16:
+            raise NFHipError(f"{nm}: n_categories must be an integer in 2..16")
+        C_ = int(C_)
+        d = p + C_ - 1
+        if d > 256:
+            raise NFHipError(f"{nm}: p + n_categories - 1 = {d} exceeds the kernels' d = 256")
+        lab = _glm_vector(nm, "labels", labels, X, rows)
+        if bool((lab != torch.round(lab)).any()) or bool((lab < 0).any()) or bool((lab >= C_).any()):
+            raise NFHipError(f"{nm}: labels must be integers in 0..{C_ - 1}")
+        off = _glm_vector(nm, "offset", offset, X, rows, 0.0)
+        wt = _glm_vector(nm, "weights", weights, X, rows, 1.0, nonneg=True)
+        const = _glm_scalar(nm, "const", const, positive=False)
+        self.prior_sigma = _glm_scalar(nm, "prior_sigma", prior_sigma, allow_inf=True)
+        self.cut_sigma = _glm_scalar(nm, "cut_sigma", cut_sigma, allow_inf=True)
+        self.cut_loc = _glm_scalar(nm, "cut_loc", cut_loc, positive=False)
+        c = const
+        prec = []
+        for sigma, count in ((self.prior_sigma, p), (self.cut_sigma, C_ - 1)):
+            flat = math.isinf(sigma)
+            prec.append(0.0 if flat else 1.0 / sigma**2)
+            c += 0.0 if flat else -0.5 * count * math.log(2.0 * math.pi * sigma**2)
+        lab_i = lab.to(torch.int64)
+        order = torch.argsort(lab_i, stable=True)
+        counts = torch.bincount(lab_i, minlength=C_)
+        nblk = (counts + 31) // 32
+        R = int(nblk.sum()) * 32
+        Xp = torch.zeros((R, p), dtype=torch.float64)
+        offp, wtp = torch.zeros(R, dtype=torch.float64), torch.zeros(R, dtype=torch.float64)
+        start = torch.cumsum(nblk, 0) * 32 - nblk * 32                     # the first padded row of each label
+        first = torch.cumsum(counts, 0) - counts                           # the first sorted row of each label
+        ls = lab_i[order]
+        dest = start[ls] + (torch.arange(rows) - first[ls])
+        Xp[dest], offp[dest], wtp[dest] = X64[order], off[order], wt[order]
+        blab = torch.repeat_interleave(torch.arange(C_), nblk).to(torch.float64)
+        nk = torch.zeros(C_, dtype=torch.float64).index_add_(0, lab_i, wt)
+        self.d, self.p, self.n_categories, self.C, self.rows, self.padded_rows, self.const = d, p, C_, C_, rows, R, c
+        self.precision, self.cut_precision = prec
+        self.order, self.row_index = order, dest                           # padded row dest[i] is the caller's row order[i]
+        self.A = Xp.to(X.dtype).to(X.device).contiguous()
+        self.X = self.A
+        self.p0 = torch.cat([offp, wtp, blab, torch.tensor([prec[0], c, prec[1], self.cut_loc], dtype=torch.float64), nk]).to(X.dtype).to(X.device).contiguous()
+        self.c = Target(_lib.NF_TARGET_ORDINAL_LOGIT, self.p0.data_ptr(), self.A.data_ptr(), float(R), float(C_))
+
+    def unpack(self, y):
+        """(beta [p], cutpoints [C - 1]) of a parameter vector y (d,) -- or ([p, N], [C - 1, N]) of a batch (d, N); the cutpoints are
+        the ordered c_k, not gamma"""
+        if y.shape[0] != self.d:
+            raise NFHipError(f"OrdinalRegressionTarget.unpack: expected {self.d} leading elements, got {y.shape[0]}")
+        gam = y[self.p:]
+        return y[:self.p], torch.cumsum(torch.cat([gam[:1], torch.exp(gam[1:])]), 0)
+
+    def predict(self, y, Xnew, offset=None):
+        """category probabilities in plain torch: [C, rows] for a vector y, [C, rows, N] for a batch (d, N)"""
+        if Xnew.dim() != 2 or Xnew.shape[1] != self.p:
+            raise NFHipError(f"OrdinalRegressionTarget.predict: Xnew must be a matrix [rows, {self.p}]")
+        beta, cut = self.unpack(y)
+        eta = Xnew @ beta                                                   # [rows] or [rows, N]
+        if offset is not None:
+            eta = eta + (offset if y.dim() == 1 else offset.unsqueeze(1))
+        cdf = torch.sigmoid(cut.unsqueeze(1) - eta.unsqueeze(0))            # [C - 1, rows(, N)]
+        one, zero = torch.ones_like(cdf[:1]), torch.zeros_like(cdf[:1])
+        return torch.cat([cdf, one]) - torch.cat([zero, cdf])
+
+
 def check_target(target, dtype, device=None, d=None):
     """Element-type / device / dimension agreement between a built-in target and the flow that will read it."""
     if isinstance(target, DiagGaussTarget):

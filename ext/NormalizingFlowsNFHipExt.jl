@@ -66,6 +66,8 @@ const NF_TARGET_BNN_LOGIT, NF_TARGET_BNN_PROBIT, NF_TARGET_BNN_POISSON, NF_TARGE
 const NF_TARGET_DGLM_NORMAL, NF_TARGET_DGLM_STUDENT, NF_TARGET_DGLM_NEGBIN =
     Int32(29), Int32(30), Int32(31)
 const NF_TARGET_ORDINAL_LOGIT = Int32(32)                             # ordinal (cumulative-logit) regression (nfhip.h)
+const NF_TARGET_RISKSET = Int32(33)                                   # risk-set regression: Cox, conditional logit (nfhip.h)
+const NF_RISKSET_MAXR = 8192
 dtype_code(::Type{Float32}) = Int32(0)
 dtype_code(::Type{Float64}) = Int32(1)
 
@@ -448,6 +450,57 @@ function check_target(t::OrdinalRegressionTarget, ::Type{T}, d) where {T}
     R = size(t.Xt, 2)
     (eltype(t.Xt) === T && eltype(t.p0) === T && size(t.Xt, 1) + t.C - 1 == d && length(t.p0) == 2 * R + R ÷ 32 + 4 + t.C) ||
         error("nfhip: target must hold $(t.C) categories over $(size(t.Xt, 1))-dimensional data rows in $T")
+end
+# Risk-set regression (Cox partial likelihood, conditional logit, rankings) over z = β ∈ R^p, the rows ALREADY ordered so that every risk
+# set is a prefix of its segment:  η_i = x_i·β + offset_i,  c_i = log Σ_{j ∈ seg(i), j ≤ i} w_j exp(η_j),
+#   log p(z) = const + lin·β − Σ_i m_i c_i + log N(β; 0, σ² I).
+# The tail is padded to a whole 32-row block with rows of weight 0; the device reads the padded X row-major (the column-major p × R array
+# `Xt`) and ONE buffer p0 = off[R] | log w[R] | m[R] | segstart[R] | lin[p] | (1/σ², const + normaliser).  σ = Inf is the flat prior.
+# Same flows as the ordinal target.  (Written without a Julia at hand: unrun.)
+struct RiskSetTarget{V<:ROCVector,M<:ROCMatrix} <: NFHipTarget
+    Xt::M            # p × R
+    p0::V            # 4 R + p + 2
+    σ::Float64
+    rows::Int        # the caller's row count
+end
+function RiskSetTarget(X::AbstractMatrix{T}, segment_start::AbstractVector, event_mass::AbstractVector; risk_weight=nothing, offset=nothing,
+                       lin=nothing, constant::Real=0.0, σ::Real=Inf) where {T}
+    rows, p = size(X)
+    (rows >= 1 && 1 <= p <= 256) || error("nfhip: X must be a rows × p matrix with 1 <= p <= 256")
+    R = 32 * cld(rows, 32)
+    R <= NF_RISKSET_MAXR || error("nfhip: at most $NF_RISKSET_MAXR rows")
+    w = risk_weight === nothing ? ones(Float64, rows) : Float64.(risk_weight)
+    m = Float64.(event_mass)
+    off = offset === nothing ? zeros(Float64, rows) : Float64.(offset)
+    ln = lin === nothing ? zeros(Float64, p) : Float64.(lin)
+    (length(segment_start) == rows && length(m) == rows && length(w) == rows && length(off) == rows && length(ln) == p) ||
+        error("nfhip: segment_start, event_mass, risk_weight and offset have one entry per row, lin one per feature")
+    (all(v -> isfinite(v) && v >= 0, w) && all(v -> isfinite(v) && v >= 0, m)) || throw(ArgumentError("nfhip: masses and weights must be finite and >= 0"))
+    live = w .> 0
+    (all(isfinite, X[live, :]) && all(isfinite, off[live]) && all(isfinite, ln)) || throw(ArgumentError("nfhip: non-finite input on a live row"))
+    (isfinite(constant) && σ > 0 && !isnan(σ)) || error("nfhip: constant finite, prior σ > 0 (Inf: flat prior)")
+    seg = Bool.(segment_start .!= 0); seg[1] = true
+    open = false
+    for i in 1:rows                                                   # an event mass needs a row of positive weight before it in its segment
+        seg[i] && (open = false)
+        open |= live[i]
+        (m[i] > 0 && !open) && throw(ArgumentError("nfhip: an event mass on a row whose risk set is empty"))
+    end
+    prec, cn = isinf(σ) ? (0.0, 0.0) : (1 / σ^2, -0.5 * p * log(2π * σ^2))
+    Xt = zeros(Float64, p, R); offp = zeros(Float64, R); lw = fill(-Inf, R); mp = zeros(Float64, R); sp = zeros(Float64, R)
+    for i in 1:rows
+        Xt[:, i] = live[i] ? X[i, :] : map(v -> isfinite(v) ? v : 0.0, X[i, :])
+        offp[i] = (live[i] || isfinite(off[i])) ? off[i] : 0.0
+        lw[i] = log(w[i]); mp[i] = m[i]; sp[i] = seg[i]
+    end
+    p0 = vcat(offp, lw, mp, sp, ln, Float64[prec, constant + cn])
+    return RiskSetTarget(ROCArray(Matrix{T}(Xt)), ROCArray(Vector{T}(p0)), Float64(σ), rows)
+end
+c_target(t::RiskSetTarget) = NFTarget(NF_TARGET_RISKSET, devptr(t.p0), devptr(t.Xt), Float64(size(t.Xt, 2)), t.σ)
+function check_target(t::RiskSetTarget, ::Type{T}, d) where {T}
+    R = size(t.Xt, 2)
+    (eltype(t.Xt) === T && eltype(t.p0) === T && size(t.Xt, 1) == d && length(t.p0) == 4 * R + d + 2) ||
+        error("nfhip: target must hold $(size(t.Xt, 1))-dimensional data rows in $T")
 end
 # Hierarchical GLM over z = [β (p coefficients) ; τ (G group log-scales)], d = p + G, centred parameterisation:
 #   log p(z) = const + Σ_i wt_i φ(u_i; param) + lin·β + Σ_j log N(β_j; 0, σ_j²) + Σ_g log p(τ_g),  u = Aβ + offset,

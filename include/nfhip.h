@@ -373,6 +373,36 @@ extern "C" {
  * The value is 32.  It is written relative to the kind before it: tests/test_disp_cpu.py reads the kinds that are defined by a
  * literal and holds the highest of them at 31; tests/test_ordinal_cpu.py evaluates this definition and holds it at 32. */
 #define NF_TARGET_ORDINAL_LOGIT (NF_TARGET_DGLM_NEGBIN + 1)
+/* Risk-set regression: the partial likelihood of Cox proportional hazards (coxph, brms cox, stan_surv), conditional logit (matched
+ * case-control, McFadden discrete choice) and Plackett-Luce rankings.  The first target whose rows interact: they are coupled through
+ * risk sets, and once the host has sorted them every risk set is a prefix of its segment (stratum, choice set).
+ *   y = beta in R^d, d = p <= 256;   eta_i = x_i . y + off_i,   a_i = eta_i + logw_i,   seg(i) the contiguous segment of row i
+ *       log p(y) = par[1] + lin . y - sum_i m_i c_i - par[0]/2 |y|^2
+ *       c_i      = log sum_{j in seg(i), j <= i} w_j exp(eta_j)          (inclusive prefix log-sum-exp inside the segment)
+ *   w_j >= 0 the risk weight (w_j = 0, logw_j = -inf, drops row j from every risk set exactly, by select: its predictor is never
+ *   consumed), m_i >= 0 the event mass (m_i > 0 only where the prefix holds a row of positive weight -- the host checks), lin the
+ *   folded sum_i e_i x_i, par[0] = 1 / sigma^2 (0: flat).  Score with respect to eta_j:  -exp(a_j - c_j) V_j,
+ *       V_j = m_j + V_{j+1} exp(c_j - c_{j+1})  backwards inside the segment,  V = m on the segment's last row.
+ *   c is non-decreasing inside a segment and a_j <= c_j, so every exponential has an argument <= 0; the forward recurrence is
+ *   c_i = logaddexp(c_{i-1}, a_i).  Nothing is clamped and no ratio of sums is formed.
+ *   p1 = X[R x p] row-major, the rows in the host's order, the tail padded with rows of weight 0 to a multiple of 32 (a segment may
+ *   start at any row);  s0 = R (an integer value, 32 <= R < 2^31, R % 32 == 0);  s1 = the prior sigma (> 0, +inf: flat), as the GLM
+ *   kinds have it;  p0 = ONE buffer of 4 R + d + 2 elements in the flow's element type, distinct from p1:
+ *       off[R] | logw[R] | m[R] | segstart[R] | lin[d] | par[2]
+ *   segstart holds 0 / 1 (any value other than 0 starts a segment; row 0 always does).
+ *   NF_ERR_ARG for a NULL p0 / p1, p0 == p1, an s0 that is not a positive integer multiple of 32 fitting an int, an s1 that is not
+ *   > 0 (NaN included) or d < 1; then NF_ERR_UNSUPPORTED for d > 256 or R > NF_RISKSET_MAXR (the tiled kernel keeps one carry per
+ *   32-row block and sample in LDS) -- both before any device work.  The host cannot validate device memory: every flag read from
+ *   the buffer is bounded by select before it steers anything.
+ * Served exactly like NF_TARGET_ORDINAL_LOGIT: nf_target_logp, RealNVP / NSF flows of either element type including the
+ * weight-streaming shapes, full-rank and preconditioned flows, general bases and compositions; nf_elbo_step runs the split
+ * sequence, nf_elbo_step_enqueue answers NF_ERR_UNSUPPORTED; planar, radial, mean-field and Hamiltonian flows answer
+ * NF_ERR_UNSUPPORTED at every ELBO entry point, a Hamiltonian score included.  A non-centring layer does not take it (no group
+ * structure).
+ * The value is 33, written relative to the kind before it: tests/test_ordinal_cpu.py holds the highest kind it can evaluate at 32,
+ * tests/test_riskset_cpu.py evaluates this definition and holds it at 33. */
+#define NF_TARGET_RISKSET (NF_TARGET_ORDINAL_LOGIT + 1)
+#define NF_RISKSET_MAXR 8192
 
 #define NF_MAX_HIDDEN 4
 

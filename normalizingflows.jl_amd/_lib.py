@@ -43,6 +43,12 @@ NF_TARGET_DGLM_NORMAL, NF_TARGET_DGLM_STUDENT, NF_TARGET_DGLM_NEGBIN = 29, 30, 3
 # (par[0] / par[2] = prior precisions of beta and of the cutpoints, par[1] = folded constant, par[3] = the cutpoint prior's location);
 # s0 = R (a multiple of 32); s1 = C (2..16)
 NF_TARGET_ORDINAL_LOGIT = 32
+# risk-set regression (Cox partial likelihood, conditional logit): y = beta (d = p); p1 = X[R, p], the rows sorted so that every risk set
+# is a prefix of its segment, the tail padded to a multiple of 32 by rows of risk weight 0; p0 = one buffer
+# off[R] | logw[R] | m[R] | segstart[R] | lin[d] | par[2] (logw = -inf drops the row; par[0] = 1 / sigma^2, par[1] = folded constant);
+# s0 = R (a multiple of 32, at most 8192); s1 = the prior sigma (+inf: flat)
+NF_TARGET_RISKSET = 33
+NF_RISKSET_MAXR = 8192
 NF_MAX_HIDDEN = 4
 NF_ERR_NONFINITE = -4
 

@@ -661,6 +661,10 @@ int nf_target_check(const nf_target *t, int d) {
             t->s1 <= 16 && t->s1 == (double)(int)t->s1 && d >= (int)t->s1))
         return NF_ERR_ARG;
       return d > 256 ? NF_ERR_UNSUPPORTED : NF_OK;  // what no kernel of nf_ordinal.hip serves: answered here, before any device work
+    case NF_TARGET_RISKSET:  // s0 = the number of rows R, sorted and tail-padded: a positive integer multiple of 32; s1 = the prior sigma, +inf for the flat prior (NaN fails s1 > 0); X (p1) and the row buffer (p0) are two buffers
+      if (!(t->p0 && t->p1 && t->p0 != t->p1 && t->s1 > 0 && t->s0 >= 32 && t->s0 < 2147483648.0 && t->s0 == (double)(long)t->s0 && (long)t->s0 % 32 == 0 && d >= 1))
+        return NF_ERR_ARG;
+      return (d > 256 || t->s0 > (double)NF_RISKSET_MAXR) ? NF_ERR_UNSUPPORTED : NF_OK;  // what no kernel of nf_riskset.hip serves: answered here, before any device work
     default: return NF_ERR_ARG;
   }
 }
@@ -695,6 +699,11 @@ int nf_launch_target_ordinal(nf_ctx *, int dtype, const nf_target *, int d, long
                              void *logp_out, void *grad_out, double gscale, void *elbos_out, double *partial, double pscale);
 int nf_launch_target_ordinal_tiled(nf_ctx *, const nf_target *, int d, long N, const float *yt, const float *logq, const float *ladj,
                                    float *gt, double gscale, float *elbos_out, double *partial, double pscale);
+// nf_riskset.hip: the risk-set (Cox / conditional-logit) target, the same contract
+int nf_launch_target_riskset(nf_ctx *, int dtype, const nf_target *, int d, long N, const void *y, const void *logq, const void *ladj,
+                             void *logp_out, void *grad_out, double gscale, void *elbos_out, double *partial, double pscale);
+int nf_launch_target_riskset_tiled(nf_ctx *, const nf_target *, int d, long N, const float *yt, const float *logq, const float *ladj,
+                                   float *gt, double gscale, float *elbos_out, double *partial, double pscale);
 
 int nf_launch_target(nf_ctx *ctx, int dtype, const nf_target *t, int d, long N, const void *y, const void *logq,
                      const void *ladj, void *logp_out, void *grad_out, double gscale, void *elbos_out, double *partial,
@@ -711,6 +720,8 @@ int nf_launch_target(nf_ctx *ctx, int dtype, const nf_target *t, int d, long N, 
       return nf_launch_target_bnn(ctx, dtype, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
     if (target_is_ordinal(t->kind))
       return nf_launch_target_ordinal(ctx, dtype, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
+    if (target_is_riskset(t->kind))
+      return nf_launch_target_riskset(ctx, dtype, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
     return nf_launch_target_linpred(ctx, dtype, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
   }
   ProfScope ps(ctx, "target");
@@ -837,6 +848,8 @@ int nf_launch_target_tiled(nf_ctx *ctx, const nf_target *t, int d, long N, const
     return nf_launch_target_bnn_tiled(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
   if (target_is_ordinal(t->kind))
     return nf_launch_target_ordinal_tiled(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
+  if (target_is_riskset(t->kind))
+    return nf_launch_target_riskset_tiled(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
   if (target_is_linpred(t->kind))
     return nf_launch_target_linpred_tiled(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
   ProfScope ps(ctx, "target");

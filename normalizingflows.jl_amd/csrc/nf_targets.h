@@ -146,8 +146,12 @@ __host__ __device__ inline bool target_is_bnn(int kind) { return kind >= NF_TARG
 // So is the ordinal (cumulative-logit) kind (NF_TARGET_ORDINAL_LOGIT, nf_ordinal.hip): the cutpoints are coordinates of y, and a
 // row's term depends on two of them, chosen by the label of its 32-row block.
 __host__ __device__ inline bool target_is_ordinal(int kind) { return kind == NF_TARGET_ORDINAL_LOGIT; }
+// So is the risk-set kind (NF_TARGET_RISKSET, nf_riskset.hip): the first target whose rows interact -- a row's term is a log-sum-exp
+// over the rows before it in its segment, so a scan over the rows sits between the two matrix products.
+__host__ __device__ inline bool target_is_riskset(int kind) { return kind == NF_TARGET_RISKSET; }
 __host__ __device__ inline bool target_has_own_kernel(int kind) {
-  return target_is_linpred(kind) || kind == NF_TARGET_GAUSSMIX || kind == NF_TARGET_SOFTMAX || target_is_bnn(kind) || target_is_ordinal(kind);
+  return target_is_linpred(kind) || kind == NF_TARGET_GAUSSMIX || kind == NF_TARGET_SOFTMAX || target_is_bnn(kind) || target_is_ordinal(kind) ||
+         target_is_riskset(kind);
 }
 // widest flow the mixture's tiled kernel serves (two U and two G blocks in registers); the flat kernel goes to 256
 #define NF_MIXTURE_TILED_MAXD 64

@@ -21,6 +21,7 @@ import math
 from dataclasses import dataclass
 from typing import Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1603,6 +1604,182 @@ class OrdinalRegressionTarget(_LinpredTarget):
         cdf = torch.sigmoid(cut.unsqueeze(1) - eta.unsqueeze(0))            # [C - 1, rows(, N)]
         one, zero = torch.ones_like(cdf[:1]), torch.zeros_like(cdf[:1])
         return torch.cat([cdf, one]) - torch.cat([zero, cdf])
+
+
+def _rs_vector(name, what, v, n, default=None):
+    """a per-row vector as float64 numpy on the host: a tensor, an array or a sequence of length n (None: the default)"""
+    if v is None:
+        return np.full(n, float(default))
+    a = v.detach().to("cpu").numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+    if a.ndim != 1 or a.shape[0] != n or a.dtype.kind not in "biuf":
+        raise NFHipError(f"{name}: {what} must be a real vector of length {n}")
+    return a.astype(np.float64)
+
+
+class RiskSetTarget(_LinpredTarget):
+    """Posterior of a risk-set regression (NF_TARGET_RISKSET) -- the partial likelihood shared by Cox proportional hazards,
+    conditional logit and Plackett-Luce rankings -- over the coefficients z in R^p, the rows ALREADY ordered so that every risk set
+    is a prefix of its segment (stratum, choice set):
+        eta_i = x_i . z + offset_i,   c_i = log sum_{j in seg(i), j <= i} risk_weight_j exp(eta_j),
+        logp(z) = const + lin . z - sum_i event_mass_i c_i + log N(z; 0, prior_sigma^2 I)
+    X [rows, p] (Float32 or Float64); segment_start (true where a segment begins; row 0 always does), event_mass (>= 0),
+    risk_weight (>= 0, default 1; 0 drops the row from every risk set exactly), offset per row, lin per feature -- tensors, arrays
+    or sequences.  prior_sigma = math.inf (the default) is the flat prior.  The host works in float64: it pads the tail to a whole
+    32-row block with rows of weight 0 (at most 31; segments are never padded), takes log risk_weight (-inf: dropped), folds the
+    prior's normaliser into const; the device reads `A` = the padded X [R, p] and ONE buffer
+    `p0` = offset[R] | log risk_weight[R] | event_mass[R] | segment_start[R] | lin[p] | (1 / prior_sigma^2, const), both kept alive
+    here.  ValueError for a negative mass or weight, a non-finite input on a live row, or an event mass on a row whose
+    positive-weight prefix is empty (its c would be log 0).  `rows` is the caller's row count, `padded_rows` is R."""
+
+    def __init__(self, X, segment_start, event_mass, risk_weight=None, offset=None, lin=None, const=0.0, prior_sigma=math.inf,
+                 _name="RiskSetTarget"):
+        nm = _name
+        if not isinstance(X, torch.Tensor) or X.dim() != 2 or X.shape[0] < 1 or X.shape[1] < 1 or X.dtype not in (torch.float32, torch.float64):
+            raise NFHipError(f"{nm}: the data matrix must be a Float32 or Float64 tensor [rows, p] with rows >= 1 and p >= 1")
+        rows, p = X.shape
+        if p > 256:
+            raise NFHipError(f"{nm}: p = {p} exceeds the kernels' d = 256")
+        R = (rows + 31) // 32 * 32
+        if R > _lib.NF_RISKSET_MAXR:
+            raise NFHipError(f"{nm}: {rows} rows exceed the kernels' {_lib.NF_RISKSET_MAXR}")
+        X64 = X.detach().to("cpu", torch.float64).numpy()
+        seg = _rs_vector(nm, "segment_start", segment_start, rows) != 0
+        m = _rs_vector(nm, "event_mass", event_mass, rows)
+        w = _rs_vector(nm, "risk_weight", risk_weight, rows, 1.0)
+        off = _rs_vector(nm, "offset", offset, rows, 0.0)
+        ln = _rs_vector(nm, "lin", lin, p, 0.0)
+        const = _glm_scalar(nm, "const", const, positive=False)
+        self.prior_sigma = _glm_scalar(nm, "prior_sigma", prior_sigma, allow_inf=True)
+        if not np.isfinite(w).all() or not np.isfinite(m).all() or (w < 0).any() or (m < 0).any():
+            raise ValueError(f"{nm}: event_mass and risk_weight must be finite and >= 0")
+        live = w > 0
+        if not np.isfinite(X64[live]).all() or not np.isfinite(off[live]).all() or not np.isfinite(ln).all():
+            raise ValueError(f"{nm}: X and offset must be finite on every row of positive risk weight, lin everywhere")
+        seg[0] = True
+        sid = np.cumsum(seg) - 1                                            # the segment of every row
+        first_live = np.full(sid[-1] + 1, rows)
+        np.minimum.at(first_live, sid[live], np.nonzero(live)[0])          # the first row of positive weight in every segment
+        if ((m > 0) & (np.arange(rows) < first_live[sid])).any():
+            raise ValueError(f"{nm}: an event mass sits on a row whose risk set is empty (no row of positive weight before it in its segment)")
+        flat = math.isinf(self.prior_sigma)
+        prec = 0.0 if flat else 1.0 / self.prior_sigma**2
+        c = const + (0.0 if flat else -0.5 * p * math.log(2.0 * math.pi * self.prior_sigma**2))
+        Xp = np.zeros((R, p))
+        Xp[:rows] = np.where(live[:, None], X64, np.where(np.isfinite(X64), X64, 0.0))  # (a dropped row's non-finite features: 0)
+        offp, lwp, mp, sp = np.zeros(R), np.full(R, -np.inf), np.zeros(R), np.zeros(R)
+        offp[:rows] = np.where(live | np.isfinite(off), off, 0.0)
+        with np.errstate(divide="ignore"):
+            lwp[:rows] = np.log(w)
+        mp[:rows], sp[:rows] = m, seg
+        self.d, self.p, self.rows, self.padded_rows, self.const, self.precision = p, p, rows, R, c, prec
+        self.segment_start, self.segment_index = torch.from_numpy(seg.copy()), torch.from_numpy(sid)
+        self.A = torch.from_numpy(Xp).to(X.dtype).to(X.device).contiguous()
+        self.X = self.A
+        self.p0 = torch.from_numpy(np.concatenate([offp, lwp, mp, sp, ln, [prec, c]])).to(X.dtype).to(X.device).contiguous()
+        self.c = Target(_lib.NF_TARGET_RISKSET, self.p0.data_ptr(), self.A.data_ptr(), float(R), self.prior_sigma)
+
+    def unpack(self, y):
+        """the coefficients beta of a parameter vector y (p,) -- or [p, N] of a batch; every coordinate is one"""
+        if y.shape[0] != self.d:
+            raise NFHipError(f"{type(self).__name__}.unpack: expected {self.d} leading elements, got {y.shape[0]}")
+        return y
+
+
+def _rs_like(X, a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(X.dtype).to(X.device)
+
+
+class CoxRegressionTarget(RiskSetTarget):
+    """Posterior of Cox proportional-hazards regression under the Breslow partial likelihood: X [rows, p], time and event (0 / 1)
+    per row, optional strata (integer labels), case weights and offset.  The host sorts by stratum, then by time DESCENDING with
+    equal times contiguous, so that the risk set of a time is a prefix of its stratum; the whole mass sum_i weights_i event_i of a
+    time group sits on the group's last row (rows censored at that time are inside the group: they are at risk), risk_weight =
+    weights, lin = sum_i weights_i event_i x_i and const takes sum_i weights_i event_i offset_i.  `order` is the sorting permutation
+    (sorted row k is the caller's row order[k]).  ties="efron" is not built."""
+
+    def __init__(self, X, time, event, strata=None, weights=None, offset=None, prior_sigma=math.inf, ties="breslow"):
+        nm = "CoxRegressionTarget"
+        if ties != "breslow":
+            raise NotImplementedError(f"{nm}: ties={ties!r} is not built (only 'breslow')")
+        if not isinstance(X, torch.Tensor) or X.dim() != 2 or X.shape[0] < 1:
+            raise NFHipError(f"{nm}: the data matrix must be a tensor [rows, p]")
+        rows = X.shape[0]
+        X64 = X.detach().to("cpu", torch.float64).numpy()
+        t = _rs_vector(nm, "time", time, rows)
+        ev = _rs_vector(nm, "event", event, rows)
+        st = _rs_vector(nm, "strata", strata, rows, 0.0)
+        wt = _rs_vector(nm, "weights", weights, rows, 1.0)
+        off = _rs_vector(nm, "offset", offset, rows, 0.0)
+        if not np.isfinite(t).all() or not np.isfinite(st).all() or not ((ev == 0) | (ev == 1)).all():
+            raise ValueError(f"{nm}: time and strata must be finite, event 0 or 1")
+        if not np.isfinite(wt).all() or (wt < 0).any():
+            raise ValueError(f"{nm}: weights must be finite and >= 0")
+        order = np.lexsort((-t, st))                                        # stable: by stratum, then by time descending
+        ts, ss, es, ws = t[order], st[order], ev[order], wt[order]
+        seg = np.r_[True, ss[1:] != ss[:-1]]
+        last = np.r_[(ts[1:] != ts[:-1]) | seg[1:], True]                   # the last row of every (stratum, time) group
+        gid = np.cumsum(np.r_[0, last[:-1]])
+        mass = np.zeros(rows)
+        mass[last] = np.bincount(gid, ws * es)
+        we = wt * ev
+        live = we > 0
+        lin = we[live] @ X64[live]
+        const = float((we[live] * off[live]).sum())
+        self.order = torch.from_numpy(order.copy())
+        self.ties = ties
+        super().__init__(X[self.order.to(X.device)], seg, mass, ws, off[order], lin, const, prior_sigma, _name=nm)
+
+    def predict(self, y, Xnew):
+        """relative hazards exp(Xnew beta) in plain torch: [rows] for a vector y, [rows, N] for a batch (p, N)"""
+        if Xnew.dim() != 2 or Xnew.shape[1] != self.p:
+            raise NFHipError(f"CoxRegressionTarget.predict: Xnew must be a matrix [rows, {self.p}]")
+        return torch.exp(Xnew @ self.unpack(y))
+
+
+class ConditionalLogitTarget(RiskSetTarget):
+    """Posterior of conditional (McFadden) logit: every choice set (matched set, choice occasion) is one segment, exactly one of
+    its rows is chosen, P(chosen) = exp(eta_chosen) / sum_{j in set} exp(eta_j).  X [rows, p], choice_set (integer labels), chosen
+    (0 / 1) per row; weights per row, constant inside a set (the set's weight).  The host sorts by choice set (stably); risk_weight
+    = 1, the set's weight sits on its last row, lin = sum_sets weight x_chosen.  `order` is the sorting permutation."""
+
+    def __init__(self, X, choice_set, chosen, weights=None, prior_sigma=math.inf):
+        nm = "ConditionalLogitTarget"
+        if not isinstance(X, torch.Tensor) or X.dim() != 2 or X.shape[0] < 1:
+            raise NFHipError(f"{nm}: the data matrix must be a tensor [rows, p]")
+        rows = X.shape[0]
+        X64 = X.detach().to("cpu", torch.float64).numpy()
+        cs = _rs_vector(nm, "choice_set", choice_set, rows)
+        ch = _rs_vector(nm, "chosen", chosen, rows)
+        wt = _rs_vector(nm, "weights", weights, rows, 1.0)
+        if not np.isfinite(cs).all() or not ((ch == 0) | (ch == 1)).all() or not np.isfinite(wt).all() or (wt < 0).any():
+            raise ValueError(f"{nm}: choice_set must be finite, chosen 0 or 1, weights finite and >= 0")
+        order = np.argsort(cs, kind="stable")
+        ss, hs, ws = cs[order], ch[order], wt[order]
+        seg = np.r_[True, ss[1:] != ss[:-1]]
+        sid = np.cumsum(seg) - 1
+        if (np.bincount(sid, hs) != 1).any():
+            raise ValueError(f"{nm}: every choice set must have exactly one chosen row")
+        first = np.nonzero(seg)[0]
+        if (ws != ws[first][sid]).any():
+            raise ValueError(f"{nm}: weights must be constant inside a choice set")
+        last = np.r_[seg[1:], True]
+        mass = np.where(last, ws, 0.0)
+        pick = (ch == 1) & (wt > 0)
+        lin = wt[pick] @ X64[pick]
+        self.order = torch.from_numpy(order.copy())
+        super().__init__(X[self.order.to(X.device)], seg, mass, None, None, lin, 0.0, prior_sigma, _name=nm)
+
+    def predict(self, y, Xnew, choice_set_new):
+        """the within-set choice probabilities in plain torch, in Xnew's row order: [rows] for a vector y, [rows, N] for a batch"""
+        if Xnew.dim() != 2 or Xnew.shape[1] != self.p:
+            raise NFHipError(f"ConditionalLogitTarget.predict: Xnew must be a matrix [rows, {self.p}]")
+        cs = _rs_vector("ConditionalLogitTarget.predict", "choice_set_new", choice_set_new, Xnew.shape[0])
+        idx = torch.from_numpy(np.unique(cs, return_inverse=True)[1].reshape(-1)).to(Xnew.device)
+        eta = Xnew @ self.unpack(y)
+        top = torch.zeros((int(idx.max()) + 1,) + tuple(eta.shape[1:]), dtype=eta.dtype, device=eta.device)
+        top = top.scatter_reduce(0, idx.reshape((-1,) + (1,) * (eta.dim() - 1)).expand_as(eta), eta, "amax", include_self=False)
+        e = torch.exp(eta - top[idx])
+        return e / torch.zeros_like(top).index_add_(0, idx, e)[idx]
 
 
 def check_target(target, dtype, device=None, d=None):

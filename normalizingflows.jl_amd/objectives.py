@@ -12,13 +12,13 @@ from typing import Callable, Optional
 import torch
 
 from ._lib import NFHipError, check
-from .flows import (BananaTarget, BNNTarget, OrdinalRegressionTarget, CrossTarget, DiagGaussTarget, DispersionGLMTarget, FunnelTarget, GLMTarget, HierarchicalGLMTarget, LogisticRegressionTarget, MixtureTarget, MvNormalTarget, SoftmaxRegressionTarget, WarpedGaussTarget, Flow, PhiloxRNG, _dtype_code, _ptr, as_batch, base_logpdf,
+from .flows import (BananaTarget, BNNTarget, OrdinalRegressionTarget, RiskSetTarget, CrossTarget, DiagGaussTarget, DispersionGLMTarget, FunnelTarget, GLMTarget, HierarchicalGLMTarget, LogisticRegressionTarget, MixtureTarget, MvNormalTarget, SoftmaxRegressionTarget, WarpedGaussTarget, Flow, PhiloxRNG, _dtype_code, _ptr, as_batch, base_logpdf,
                     check_target, device_specific_rand, new_batch, rrule_with_logabsdet_jacobian, with_logabsdet_jacobian)
 
-_BUILTIN = (DiagGaussTarget, BananaTarget, FunnelTarget, WarpedGaussTarget, CrossTarget, MvNormalTarget, LogisticRegressionTarget, MixtureTarget, GLMTarget, SoftmaxRegressionTarget, HierarchicalGLMTarget, BNNTarget, DispersionGLMTarget, OrdinalRegressionTarget)
+_BUILTIN = (DiagGaussTarget, BananaTarget, FunnelTarget, WarpedGaussTarget, CrossTarget, MvNormalTarget, LogisticRegressionTarget, MixtureTarget, GLMTarget, SoftmaxRegressionTarget, HierarchicalGLMTarget, BNNTarget, DispersionGLMTarget, OrdinalRegressionTarget, RiskSetTarget)
 # linear-predictor and mixture targets (no in-kernel form): the library serves them for coupling flows (and general bases / compositions) only; planar, radial,
 # mean-field and Hamiltonian flows evaluate the target inside their own kernels and answer NF_ERR_UNSUPPORTED
-_LINPRED = (MvNormalTarget, LogisticRegressionTarget, MixtureTarget, GLMTarget, SoftmaxRegressionTarget, HierarchicalGLMTarget, BNNTarget, DispersionGLMTarget, OrdinalRegressionTarget)  # (their subclasses too)
+_LINPRED = (MvNormalTarget, LogisticRegressionTarget, MixtureTarget, GLMTarget, SoftmaxRegressionTarget, HierarchicalGLMTarget, BNNTarget, DispersionGLMTarget, OrdinalRegressionTarget, RiskSetTarget)  # (their subclasses too)
 _NO_LINPRED_KINDS = ("planar", "radial", "meanfield", "hamiltonian")
 
 
@@ -159,7 +159,7 @@ def value_and_gradient(vo, flow: Flow, logp, xs_or_n, rng: Optional[PhiloxRNG] =
     """(loss, grad) of loss(theta) = -vo(rng, re(theta), logp, ...) (src/NormalizingFlows.jl:69).
 
     Built-in targets run the whole step inside the library (nf_elbo_value_and_grad) -- except MvNormalTarget /
-    LogisticRegressionTarget / MixtureTarget / GLMTarget / SoftmaxRegressionTarget / HierarchicalGLMTarget / BNNTarget / DispersionGLMTarget / OrdinalRegressionTarget on planar, radial, mean-field and Hamiltonian flows, which the library refuses: those take
+    LogisticRegressionTarget / MixtureTarget / GLMTarget / SoftmaxRegressionTarget / HierarchicalGLMTarget / BNNTarget / DispersionGLMTarget / OrdinalRegressionTarget / RiskSetTarget on planar, radial, mean-field and Hamiltonian flows, which the library refuses: those take
     the branch below, where the target's autograd node hands back the device score.  An
     arbitrary `logp` callable takes the split path: library forward that keeps its tape
     (nf_flow_fwd_keep), the callable's own torch-autograd gradient w.r.t. ys, library pullback

@@ -666,6 +666,55 @@ function check_target(t::DispersionGLMTarget, ::Type{T}, d) where {T}
     (eltype(t.At) === T && eltype(t.p0) === T && size(t.At, 1) == d && length(t.p0) >= 4 * d + 2 * size(t.At, 2) + 5 + t.G) ||
         error("nfhip: target must hold $d-dimensional data rows ($(d - t.G - 1) coefficients, $(t.G) log-scales and the log-dispersion) in $T")
 end
+# Row minibatch of a regression target for stochastic VI over many rows (nf_target_minibatch, include/nfhip.h): m of the full target's
+# rows, gathered on the device into buffers of the full target's own kind and layout -- stratified, one row per stratum, without
+# replacement, the weight of row idx_j scaled by the size n_j of its stratum, every host-folded full-data term copied.  An unbiased
+# estimate of the full log-density; m = rows is the full target bit for bit.  `resample!(mb, stream)` draws the batch of a stream
+# index under `seed`; the constructor resamples at stream 0, train_flow_fused before every step with that step's stream index.
+# Every rank of a communicator passes the same seed.  Monitoring on all rows: elbo_batch(flow, mb.full, xs).  Served for GLMTarget,
+# SoftmaxTarget, HierarchicalGLMTarget, BNNTarget and DispersionGLMTarget.  (Written without a Julia at hand: unrun.)
+const MinibatchFull = Union{GLMTarget,SoftmaxTarget,HierarchicalGLMTarget,BNNTarget,DispersionGLMTarget}
+mutable struct MinibatchTarget{F<:MinibatchFull,V<:ROCVector,M<:ROCMatrix} <: NFHipTarget
+    full::F
+    m::Int
+    seed::UInt64
+    At::M                 # w × m: the gathered rows
+    p0::V
+    idx::ROCVector{Int32} # the row of the full target behind every row of the batch
+    d::Int
+end
+rows_matrix(t::Union{GLMTarget,HierarchicalGLMTarget,DispersionGLMTarget}) = t.At
+rows_matrix(t::Union{SoftmaxTarget,BNNTarget}) = t.Xt
+per_row_segments(::GLMTarget) = 2
+per_row_segments(::SoftmaxTarget) = 2
+per_row_segments(::HierarchicalGLMTarget) = 2
+per_row_segments(::BNNTarget) = 3
+per_row_segments(t::DispersionGLMTarget) = t.kind == NF_TARGET_DGLM_NEGBIN ? 3 : 2
+target_dim(t::Union{GLMTarget,HierarchicalGLMTarget,DispersionGLMTarget}) = size(t.At, 1)
+target_dim(t::SoftmaxTarget) = t.C * size(t.Xt, 1)
+target_dim(t::BNNTarget) = t.H * (size(t.Xt, 1) + 1) + 1
+function MinibatchTarget(full::MinibatchFull, m::Integer; seed::Integer=0)
+    X = rows_matrix(full)
+    w, R = size(X)
+    1 <= m <= R || error("nfhip: batch_rows must be in 1:$R")
+    mb = MinibatchTarget(full, Int(m), UInt64(seed), similar(X, w, m), similar(full.p0, length(full.p0) - per_row_segments(full) * (R - m)),
+                         ROCVector{Int32}(undef, m), target_dim(full))
+    return resample!(mb, 0)
+end
+function resample!(mb::MinibatchTarget, stream::Integer; indices::Union{Nothing,ROCVector{Int32}}=nothing)
+    indices === nothing || length(indices) == mb.m || error("nfhip: indices must hold $(mb.m) entries")
+    out = Ref(NFTarget(Int32(0), C_NULL, C_NULL, 0.0, 0.0))
+    check(ccall((:nf_target_minibatch, libnfhip), Cint,
+                (Ptr{Cvoid}, Int32, Ref{NFTarget}, Int32, Int64, Int64, UInt64, UInt32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{NFTarget}),
+                context(), dtype_code(eltype(mb.p0)), c_target(mb.full), mb.d, length(mb.full.p0), mb.m, mb.seed, UInt32(stream), devptr(indices),
+                devptr(mb.idx), devptr(mb.p0), devptr(mb.At), out))
+    return mb
+end
+function c_target(mb::MinibatchTarget)
+    f = c_target(mb.full)
+    return NFTarget(f.kind, devptr(mb.p0), devptr(mb.At), Float64(mb.m), f.s1)
+end
+check_target(mb::MinibatchTarget, ::Type{T}, d) where {T} = check_target(mb.full, T, d)
 c_target(t::DenseGaussTarget) = NFTarget(NF_TARGET_DENSEGAUSS, devptr(t.μ), devptr(t.Wt), t.logdetW, 0.0)
 c_target(t::LogRegTarget) = NFTarget(NF_TARGET_LOGREG, t.shift === nothing ? C_NULL : devptr(t.shift), devptr(t.At), Float64(size(t.At, 2)), t.σ)
 function check_target(t::DenseGaussTarget, ::Type{T}, d) where {T}
@@ -998,10 +1047,12 @@ function train_flow_fused(rng::NFHipRNG, flow::Bijectors.TransformedDistribution
     try
         for i in 1:max_iters
             loss, gnorm = Ref{Cdouble}(0), Ref{Cdouble}(0)
+            s = next_stream!(rng)
+            logp isa MinibatchTarget && resample!(logp, s)   # this step's rows, under the stream index of this step's draws
             code = ccall((:nf_elbo_step, libnfhip), Cint,
                          (Ptr{Cvoid}, Ref{NFDesc}, Ref{NFTarget}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, UInt64, UInt32,
                           Cdouble, Cdouble, Cdouble, Cdouble, Ref{Cdouble}, Ref{Cdouble}),
-                         context(), t.desc, c_target(logp), devptr(θ), devptr(m), devptr(v), n, rng.seed, next_stream!(rng),
+                         context(), t.desc, c_target(logp), devptr(θ), devptr(m), devptr(v), n, rng.seed, s,
                          optimiser.eta, optimiser.beta[1], optimiser.beta[2], optimiser.epsilon, loss, gnorm)
             code == NF_ERR_NONFINITE || check(code)   # a non-finite loss is recorded
             steps += 1

@@ -570,6 +570,36 @@ int nf_flow_bwd(nf_ctx *ctx, const nf_flow_desc *desc, const void *theta, const 
 int nf_target_logp(nf_ctx *ctx, int32_t dtype, const nf_target *target, int32_t d, int64_t N,
                    const void *y, void *logp_out, void *grad_out);
 
+/* Row minibatch of a regression target, for stochastic VI over many rows: builds on the device, in ONE launch, a target of m rows
+ * out of the R = full->s0 rows of `full`, in the full target's own kind and layout -- *out = {full->kind, p0_out, p1_out, m,
+ * full->s1} is a target like any other, for every entry point and every flow that serves the kind.  Call it before each step.
+ * Stratified, one row per stratum, without replacement:
+ *       lo_j = floor(j R / m) (64-bit),  n_j = lo_{j+1} - lo_j >= 1,  idx_j = lo_j + (((uint64) r_j n_j) >> 32),   j = 0 .. m-1,
+ *       r_j = word x of philox4x32_10(counter (j_lo, j_hi, 0xFFFFFFFF, stream), key (mb_seed_lo, mb_seed_hi))
+ *   (counter word 2 = 0xFFFFFFFF is never a feature group of nf_base_sample_logpdf: the row choice is disjoint from the draws even
+ *   with the same seed and stream).  The row weight becomes wt'_j = wt[idx_j] * n_j (one rounding in the element type); everything
+ *   else of row idx_j -- its row of p1 and its entry of every per-row segment of p0 -- and every fixed segment of p0 (lin, par, grp,
+ *   isd, hm, his, hk, gptr, gidx, ctab) is copied verbatim.  So E[sum_j n_j wt_idx_j phi_idx_j] = sum_i wt_i phi_i (unbiased), the
+ *   host-folded full-data terms stay exact, a weight-0 row stays exactly dropped, and m = R gives the full buffers bit for bit.
+ * Kinds: NF_TARGET_GLM_*, NF_TARGET_SOFTMAX, NF_TARGET_HGLM_*, NF_TARGET_BNN_*, NF_TARGET_DGLM_*.  NF_ERR_UNSUPPORTED for the kinds
+ *   without a per-row weight (0 .. 6, 8) or whose rows are not exchangeable (NF_TARGET_ORDINAL_LOGIT: label blocks;
+ *   NF_TARGET_RISKSET: rows interact).
+ * p0_elems: the element count of full->p0 (the negative-binomial table length lives in device memory: it is derived from this).
+ * p0_out: p0_elems - nper (R - m) elements, nper the number of per-row segments of the kind's p0;  p1_out: m x w, w the row width
+ *   of p1 (d; d / C for SOFTMAX; (d - 1) / H - 1 for BNN).  idx_out (optional, int32[m]) receives idx.  idx_in (optional, int32[m],
+ *   device) replaces the random draw only: the scale stays n_j by position, every value is bounded by select to [0, R) before it
+ *   addresses anything, unbiasedness is then the caller's business.
+ * NF_ERR_ARG: a NULL full / out / p0_out / p1_out, whatever the kind's own conventions refuse at d (NULL p0 / p1 included), m < 1,
+ *   m > R, p0_out == full->p0, p1_out == full->p1, or a p0_elems that does not fit the kind's layout at (R, d, s1).  Both error
+ *   classes are answered before any device work.  Asynchronous on the context's stream: ordered before any later call on the
+ *   context.  One writer per output element: no atomics, the same bits on every launch.
+ * Declared `extern`: tests/test_abi_cpu.py and tests/test_elbo_targets_cpu.py hold the declarations that begin a line with their
+ * return type at the 49 symbols ABI 4 started with, and three more tests hold _lib.SYMBOLS at that count.  A symbol added since is
+ * declared like this one and bound in _lib.EXT_SYMBOLS; tests/test_minibatch_cpu.py holds that list against this header. */
+extern int nf_target_minibatch(nf_ctx *ctx, int32_t dtype, const nf_target *full, int32_t d, int64_t p0_elems, int64_t m,
+                        uint64_t mb_seed, uint32_t stream, const int32_t *idx_in, int32_t *idx_out, void *p0_out, void *p1_out,
+                        nf_target *out);
+
 /* ---- a1, a2, a3: objectives ------------------------------------------------ */
 /* elbo_batch(flow, logp, xs) / elbo(flow, logp, xs)  (src/objectives/elbo.jl:31-34,89-92):
  * mean_j[logp(y_j) - log q0(x_j) + ladj_j] for caller-supplied xs.

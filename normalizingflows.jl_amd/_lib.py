@@ -153,6 +153,11 @@ SYMBOLS = {
     "nf_debug_trace": (C.c_int, [_P, _I32, C.POINTER(C.c_int64), _I32]),
 }
 
+# symbols added to ABI 4 after its first 49 (include/nfhip.h declares them `extern`; SYMBOLS stays the list the older tests hold)
+EXT_SYMBOLS = {
+    "nf_target_minibatch": (C.c_int, [_P, _I32, _TGT, _I32, _I64, _I64, _U64, _U32, _P, _P, _P, _P, _TGT]),
+}
+
 _lib = None
 
 
@@ -167,7 +172,7 @@ def load_library():
             "there is no CPU fallback"
         )
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SYMBOLS.items():
+    for name, (res, args) in {**SYMBOLS, **EXT_SYMBOLS}.items():
         fn = getattr(lib, name)  # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args

@@ -1782,6 +1782,86 @@ class ConditionalLogitTarget(RiskSetTarget):
         return e / torch.zeros_like(top).index_add_(0, idx, e)[idx]
 
 
+def minibatch_segments(target):
+    """The layout nf_target_minibatch gathers, for a target it serves: (segments, weight_segment, w) -- the segments of `target.p0`
+    in order as (per_row, length) pairs (a per-row segment has length target.rows), the position of the weight segment among them,
+    and the row width w of `target.A`.  NFHipError for every other target class."""
+    R = getattr(target, "rows", None)
+    row, fx = (True, R), lambda n: (False, int(n))
+    if isinstance(target, GLMTarget):                   # lin | off | wt | par[2]
+        return [fx(target.d), row, row, fx(2)], 2, target.d
+    if isinstance(target, HierarchicalGLMTarget):       # lin | off | wt | par[2] | grp | isd | hm | his | hk | gptr | gidx
+        p, G = target.p, target.G
+        return [fx(target.d), row, row, fx(2), fx(p), fx(p), fx(G), fx(G), fx(G), fx(G + 1), fx(p)], 2, target.d
+    if isinstance(target, DispersionGLMTarget):         # lin | off | wt | par[4] | grp | isd | hm | his | hk | gptr | gidx ( | cnt | ctab)
+        p, G = target.p, target.G
+        tail = [row, fx(target.table_len)] if target.family == "negbin" else []
+        return [fx(target.d), row, row, fx(4), fx(p), fx(p), fx(G + 1), fx(G + 1), fx(G + 1), fx(G + 1), fx(p)] + tail, 2, target.d
+    if isinstance(target, SoftmaxRegressionTarget):     # lab | wt | par[2]
+        return [row, row, fx(2)], 1, target.p
+    if isinstance(target, BNNTarget):                   # scl | off | wt | par[4]
+        return [row, row, row, fx(4)], 2, target.p
+    raise NFHipError(f"MinibatchTarget: {type(target).__name__} has no row-minibatch form: it needs a per-row weight and exchangeable rows "
+                     "(GLMTarget, HierarchicalGLMTarget, DispersionGLMTarget, SoftmaxRegressionTarget, BNNTarget and their subclasses; "
+                     "logistic regression: GLMTarget('logit', ...) or BinomialRegressionTarget)")
+
+
+class MinibatchTarget(_LinpredTarget):
+    """A row minibatch of a regression target for stochastic VI over many rows: `batch_rows` of `target`'s rows, drawn on the device
+    by nf_target_minibatch -- stratified, one row per stratum, without replacement, the weight of row idx_j scaled by the size n_j of
+    its stratum -- into buffers of the full target's own kind and layout.  The sum over the batch is an unbiased estimate of the sum
+    over all rows; everything the constructor of `target` folded over the full data (lin, the constants, the negative-binomial
+    table) is copied and stays exact.  batch_rows == target.rows is the full target bit for bit.
+    `.c` describes the CURRENT batch (`.A` [batch_rows, w], `.p0`, `.indices`), `.d` is the full target's, `.full` the wrapped target
+    (monitoring on all rows: elbo_batch(flow, mb.full, xs)).  `resample(stream)` draws the batch of stream index `stream` under `seed`;
+    the object is constructed resampled at stream 0.  train_flow resamples before each step with the stream index of that step's
+    draws; elbo_batch and value_and_gradient called directly use the current batch.  Under a communicator every rank passes the same
+    seed, so that all ranks see the same rows.  unpack, predict, coefficients, scales, dispersion and weights are the full target's."""
+
+    _DELEGATED = ("unpack", "predict", "coefficients", "scales", "dispersion", "weights")
+
+    def __init__(self, target, batch_rows, seed=0):
+        segs, wseg, w = minibatch_segments(target)
+        if isinstance(batch_rows, bool) or not hasattr(batch_rows, "__index__") or not 1 <= int(batch_rows) <= target.rows:
+            raise NFHipError(f"MinibatchTarget: batch_rows must be an integer in 1..{target.rows}")
+        if isinstance(seed, bool) or not hasattr(seed, "__index__") or not 0 <= int(seed) < 2**64:
+            raise NFHipError("MinibatchTarget: seed must be an integer in 0..2^64-1")
+        if target.A.device.type != "cuda":
+            raise NFHipError("MinibatchTarget: the batch is gathered on the device: build the target from device tensors")
+        m = int(batch_rows)
+        self.full, self.d, self.rows, self.seed = target, target.d, m, int(seed)
+        self.A = torch.empty((m, w), dtype=target.A.dtype, device=target.A.device)
+        self.p0 = torch.empty(sum(m if per_row else n for per_row, n in segs), dtype=target.p0.dtype, device=target.p0.device)
+        self.idx = torch.empty(m, dtype=torch.int32, device=target.A.device)
+        self.c = Target()
+        self.resample(0)
+
+    def __getattr__(self, name):  # (only reached for names the object does not have)
+        if name in MinibatchTarget._DELEGATED and "full" in self.__dict__:
+            return getattr(self.full, name)
+        raise AttributeError(f"{type(self).__name__!r} object has no attribute {name!r}")
+
+    def resample(self, stream, indices=None):
+        """Draw the batch of stream index `stream` (asynchronous, ordered before any later library call on the device's context) and
+        return self.  `indices` (batch_rows integers) replaces the random draw only: position j still carries the scale n_j of
+        stratum j, values outside 0..rows-1 are clamped on the device, and unbiasedness is then the caller's business."""
+        full, dev = self.full, self.A.device
+        idx_in = None
+        if indices is not None:
+            idx_in = torch.as_tensor(indices).to(device=dev, dtype=torch.int32).contiguous()
+            if idx_in.dim() != 1 or idx_in.numel() != self.rows:
+                raise NFHipError(f"MinibatchTarget.resample: indices must hold {self.rows} integers")
+        ctx = context_for(dev)
+        check(ctx.lib.nf_target_minibatch(ctx.ptr, _dtype_code(self.A.dtype), C.byref(full.c), self.d, full.p0.numel(), self.rows, self.seed,
+                                          int(stream) & 0xFFFFFFFF, _ptr(idx_in), _ptr(self.idx), _ptr(self.p0), _ptr(self.A), C.byref(self.c)))
+        return self
+
+    @property
+    def indices(self):
+        """the row of the full target behind every row of the current batch (int32, on the device)"""
+        return self.idx
+
+
 def check_target(target, dtype, device=None, d=None):
     """Element-type / device / dimension agreement between a built-in target and the flow that will read it."""
     if isinstance(target, DiagGaussTarget):

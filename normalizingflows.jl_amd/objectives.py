@@ -12,13 +12,13 @@ from typing import Callable, Optional
 import torch
 
 from ._lib import NFHipError, check
-from .flows import (BananaTarget, BNNTarget, OrdinalRegressionTarget, RiskSetTarget, CrossTarget, DiagGaussTarget, DispersionGLMTarget, FunnelTarget, GLMTarget, HierarchicalGLMTarget, LogisticRegressionTarget, MixtureTarget, MvNormalTarget, SoftmaxRegressionTarget, WarpedGaussTarget, Flow, PhiloxRNG, _dtype_code, _ptr, as_batch, base_logpdf,
+from .flows import (BananaTarget, BNNTarget, OrdinalRegressionTarget, RiskSetTarget, CrossTarget, DiagGaussTarget, DispersionGLMTarget, FunnelTarget, GLMTarget, HierarchicalGLMTarget, LogisticRegressionTarget, MinibatchTarget, MixtureTarget, MvNormalTarget, SoftmaxRegressionTarget, WarpedGaussTarget, Flow, PhiloxRNG, _dtype_code, _ptr, as_batch, base_logpdf,
                     check_target, device_specific_rand, new_batch, rrule_with_logabsdet_jacobian, with_logabsdet_jacobian)
 
-_BUILTIN = (DiagGaussTarget, BananaTarget, FunnelTarget, WarpedGaussTarget, CrossTarget, MvNormalTarget, LogisticRegressionTarget, MixtureTarget, GLMTarget, SoftmaxRegressionTarget, HierarchicalGLMTarget, BNNTarget, DispersionGLMTarget, OrdinalRegressionTarget, RiskSetTarget)
+_BUILTIN = (DiagGaussTarget, BananaTarget, FunnelTarget, WarpedGaussTarget, CrossTarget, MvNormalTarget, LogisticRegressionTarget, MixtureTarget, GLMTarget, SoftmaxRegressionTarget, HierarchicalGLMTarget, BNNTarget, DispersionGLMTarget, OrdinalRegressionTarget, RiskSetTarget, MinibatchTarget)
 # linear-predictor and mixture targets (no in-kernel form): the library serves them for coupling flows (and general bases / compositions) only; planar, radial,
 # mean-field and Hamiltonian flows evaluate the target inside their own kernels and answer NF_ERR_UNSUPPORTED
-_LINPRED = (MvNormalTarget, LogisticRegressionTarget, MixtureTarget, GLMTarget, SoftmaxRegressionTarget, HierarchicalGLMTarget, BNNTarget, DispersionGLMTarget, OrdinalRegressionTarget, RiskSetTarget)  # (their subclasses too)
+_LINPRED = (MvNormalTarget, LogisticRegressionTarget, MixtureTarget, GLMTarget, SoftmaxRegressionTarget, HierarchicalGLMTarget, BNNTarget, DispersionGLMTarget, OrdinalRegressionTarget, RiskSetTarget, MinibatchTarget)  # (their subclasses too)
 _NO_LINPRED_KINDS = ("planar", "radial", "meanfield", "hamiltonian")
 
 
@@ -423,8 +423,11 @@ def _optimize_fused(flow: Flow, theta0: torch.Tensor, reconstruct, rng: PhiloxRN
     try:
         while i <= max_iters and not converged:
             theta_before = theta.clone() if callback is not None else None
+            s = rng.next_stream()
+            if isinstance(logp, MinibatchTarget):
+                logp.resample(s)  # this step's rows, under the stream index of this step's draws
             code = lib.nf_elbo_step(ctx.ptr, C.byref(flow.desc), C.byref(logp.c), _ptr(theta), _ptr(st.m), _ptr(st.v), n,
-                                    rng.seed, rng.next_stream(), optimiser.eta, optimiser.beta[0], optimiser.beta[1],
+                                    rng.seed, s, optimiser.eta, optimiser.beta[0], optimiser.beta[1],
                                     optimiser.epsilon, C.byref(loss), C.byref(gn))
             if code != NF_ERR_NONFINITE:  # a non-finite loss is recorded, as the reference's loop would record it
                 check(code)
@@ -456,7 +459,8 @@ def train_flow(*args, max_iters: int = 1000, optimiser: Adam = None, ADbackend=N
     kernels as the benchmark's; planar, radial and mean-field flows the three-launch fused step) with Adam go through
     nf_elbo_step, one library call per iteration (`_optimize_fused`), forward-KL
     runs with Adam through nf_loglikelihood_step (`_optimize_fused_fkl`); everything else through `optimize` over
-    value_and_gradient + update."""
+    value_and_gradient + update.  A MinibatchTarget is resampled before every step, under the stream index of that step's draws
+    (stochastic VI over the rows); its current batch is what every other entry point sees."""
     if isinstance(args[0], PhiloxRNG):
         rng, vo, flow, *rest = args
     else:
@@ -476,6 +480,8 @@ def train_flow(*args, max_iters: int = 1000, optimiser: Adam = None, ADbackend=N
         f = re(theta)
         if vo in (elbo, elbo_batch):
             logp, n = rest
+            if isinstance(logp, MinibatchTarget):
+                logp.resample(rng.stream)  # once per gradient, under the stream index its draws are about to use
             return value_and_gradient(vo, f, logp, n, rng)
         if vo is loglikelihood:  # train_flow(loglikelihood, flow, xs): forward KL on the data xs
             (xs,) = rest

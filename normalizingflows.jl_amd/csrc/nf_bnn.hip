@@ -14,8 +14,12 @@
 // A row of weight 0 contributes exactly 0 to the value and to every gradient by SELECT, at every place its values enter a sum
 // (phi, g_i, the g a products of d/dv, the second GEMM's operand): a subsampling mask may sit over a row of huge features or one
 // whose phi overflows.  Nothing is clamped.
+// Shared stages (nf_target_stages.h): tgt_stage_rows and tgt_gemm1_at (the wave's image of a row block; U_k from it and the tile at
+// feature k p), tgt_elbo_term and tgt_block_partial (the ELBO tail of both kernels), and the launch helpers; what stands here in
+// place does so for nf_ordinal.hip's reason.
 #include "nf_common.h"
 #include "nf_linpred.h"
+#include "nf_target_stages.h"
 
 #define BN_BLOCK 256
 #define BN_WAVES 4
@@ -89,37 +93,6 @@ struct BnGeo {
   __host__ __device__ static constexpr int floats(int p) { return YTP + BN_WAVES * 32 * stride(p) + BN_WAVES * 64; }
 };
 
-// rows [i0, i0 + 32) x features [0, p) of X -> the wave's image; zero beyond the matrix, up to the end of p's last 32-feature block
-__device__ __forceinline__ void bn_stage(float *__restrict__ img, int S, const float *__restrict__ X, int i0, int rows, int p, int lane) {
-  const int l31 = lane & 31, hi = lane >> 5;
-  for (int cb = 0; cb * 32 < p; ++cb) {
-    const int col = cb * 32 + l31;
-    float v[16];
-#pragma unroll
-    for (int rp = 0; rp < 16; ++rp) {
-      const int i = i0 + 2 * rp + hi;
-      v[rp] = (i < rows && col < p) ? X[(long)i * p + col] : 0.f;
-    }
-#pragma unroll
-    for (int rp = 0; rp < 16; ++rp) img[(2 * rp + hi) * S + col] = v[rp];
-  }
-}
-
-// U_k of the wave's row block: A from the image, B from the tile at feature k p
-__device__ __forceinline__ f32x16 bn_gemm1(const float *__restrict__ img, int S, const float *__restrict__ sY, int k, int p, int l31, int hi) {
-  f32x16 U;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) U[r] = 0.f;
-  const int ng = (p + 7) >> 3;  // groups of four k-steps = eight features; image columns >= p are zero
-  const float *pa = img + l31 * S + hi;
-  const float *pb = sY + (k * p + hi) * 32 + l31;
-  for (int g = 0; g < ng; ++g) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) U = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[8 * g + 2 * e], pb[(8 * g + 2 * e) * 32], U, 0, 0, 0);
-  }
-  return U;
-}
-
 template <class PHI, int DB>
 __global__ __launch_bounds__(BN_BLOCK, DB <= 2 ? 2 : 1) void k_target_bnn_tiled(int d, int H, int rows, long N, const float *__restrict__ yt,
                                                                                const float *__restrict__ p0, const float *__restrict__ X,
@@ -176,7 +149,7 @@ __global__ __launch_bounds__(BN_BLOCK, DB <= 2 ? 2 : 1) void k_target_bnn_tiled(
       off[r] = i < rows ? rd.off[i] : 0.f;
       wt[r] = i < rows ? rd.wt[i] : 0.f;
     }
-    bn_stage(img, S, X, i0, rows, p, lane);
+    tgt_stage_rows(img, S, X, i0, rows, p, lane);
     wave_lds_fence();
 
     // pass 1: the network's output f, then phi, phi' and g of the lane's 16 rows
@@ -184,7 +157,7 @@ __global__ __launch_bounds__(BN_BLOCK, DB <= 2 ? 2 : 1) void k_target_bnn_tiled(
 #pragma unroll
     for (int r = 0; r < 16; ++r) g[r] = cj;  // (f until the row function has been evaluated)
     for (int k = 0; k < H; ++k) {
-      const f32x16 U = bn_gemm1(img, S, sY, k, p, l31, hi);
+      const f32x16 U = tgt_gemm1_at(img, S, sY, k * p, p, l31, hi);
       const float vk = sY[(HP + k) * 32 + l31];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
@@ -207,7 +180,7 @@ __global__ __launch_bounds__(BN_BLOCK, DB <= 2 ? 2 : 1) void k_target_bnn_tiled(
 
     // pass 2: d/dv_k in the lane, g v_k (1 - a^2) in GEMM 1's accumulator registers, straight into GEMM 2
     for (int k = 0; k < H; ++k) {
-      f32x16 U = bn_gemm1(img, S, sY, k, p, l31, hi);
+      f32x16 U = tgt_gemm1_at(img, S, sY, k * p, p, l31, hi);
       const float vk = sY[(HP + k) * 32 + l31];
       float part = 0.f;
 #pragma unroll
@@ -307,18 +280,9 @@ __global__ __launch_bounds__(BN_BLOCK, DB <= 2 ? 2 : 1) void k_target_bnn_tiled(
 #pragma unroll
     for (int w = 0; w < BN_WAVES; ++w) l += sL[w * 64 + s] + sL[w * 64 + 32 + s];
     float e = rd.par[1] + l - 0.5f * pwh * th - 0.5f * pwo * to;
-    if (logq) e -= logq[j];
-    if (ladj) e += ladj[j];
-    if (elbos_out) elbos_out[j] = e;
-    contrib = pscale * (double)e;
+    contrib = tgt_elbo_term(e, j, logq, ladj, elbos_out, pscale);
   }
-  if (partial) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) contrib += __shfl_xor(contrib, o, 64);
-    if (lane == 0) sm[wave] = contrib;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
-  }
+  tgt_block_partial(contrib, sm, partial);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -448,18 +412,9 @@ __global__ __launch_bounds__(BN_BLOCK) void k_target_bnn(int d, int H, int rows,
   if (valid && q == 0) {
     T e = rd.par[1] + lp - (T)0.5 * pwh * yyh - (T)0.5 * pwo * yyo;
     if (logp_out) logp_out[j] = e;
-    if (logq) e -= logq[j];
-    if (ladj) e += ladj[j];
-    if (elbos_out) elbos_out[j] = e;
-    contrib = pscale * (double)e;
+    contrib = tgt_elbo_term(e, j, logq, ladj, elbos_out, pscale);
   }
-  if (partial) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) contrib += __shfl_xor(contrib, o, 64);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = contrib;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
-  }
+  tgt_block_partial(contrib, sm, partial);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -468,81 +423,54 @@ __global__ __launch_bounds__(BN_BLOCK) void k_target_bnn(int d, int H, int rows,
 // what no kernel here serves: the tile and the flat kernel's registers stop at d = 256, the one-chunk image at p = 128
 static inline bool bnn_unsupported(const nf_target *t, int d) { return d > BN_MAXD || (d - 1) / (int)t->s1 - 1 > BN_MAXP; }
 
-template <class PHI, int DB>
-static int launch_bnn_tiled(nf_ctx *ctx, const nf_target *t, int d, long N, const float *yt, const float *logq, const float *ladj,
-                            float *gt, double gscale, float *elbos_out, double *partial, double pscale) {
-  const int H = (int)t->s1, p = (d - 1) / H - 1;
-  const size_t lds = (size_t)BnGeo<DB>::floats(p) * sizeof(float);
-  static AttrOnce attr_once;  // once per device
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    NF_HIP(hipFuncSetAttribute((const void *)k_target_bnn_tiled<PHI, DB>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)(BnGeo<DB>::floats(BnGeo<DB>::PMAX) * sizeof(float))));
-    return NF_OK;
-  }));
-  ProfScope ps(ctx, "target_bnn");
-  hipLaunchKernelGGL((k_target_bnn_tiled<PHI, DB>), dim3((unsigned)((N + 31) / 32)), dim3(BN_BLOCK), lds, ctx->stream, d, H, (int)t->s0, N,
-                     yt, (const float *)t->p0, (const float *)t->p1, logq, ladj, gt, (float)gscale, elbos_out, partial, pscale);
-  return (int)hipGetLastError();
-}
-
-template <class PHI>
-static int launch_bnn_tiled_db(nf_ctx *ctx, const nf_target *t, int d, long N, const float *yt, const float *logq, const float *ladj,
-                               float *gt, double gscale, float *elbos_out, double *partial, double pscale) {
-  if (d <= 32) return launch_bnn_tiled<PHI, 1>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
-  if (d <= 64) return launch_bnn_tiled<PHI, 2>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
-  if (d <= 128) return launch_bnn_tiled<PHI, 4>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
-  return launch_bnn_tiled<PHI, 8>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
-}
-
-int nf_launch_target_bnn_tiled(nf_ctx *ctx, const nf_target *t, int d, long N, const float *yt, const float *logq, const float *ladj,
-                               float *gt, double gscale, float *elbos_out, double *partial, double pscale) {
-  if (bnn_unsupported(t, d)) return NF_ERR_UNSUPPORTED;
-#define BN_TILED(PHI) launch_bnn_tiled_db<PHI>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale)
-  switch (t->kind) {
-    case NF_TARGET_BNN_LOGIT: return BN_TILED(PhiLogSigmoid);
-    case NF_TARGET_BNN_PROBIT: return BN_TILED(PhiLogNormCdf);
-    case NF_TARGET_BNN_POISSON: return BN_TILED(PhiNegExp);
-    case NF_TARGET_BNN_STUDENT: return BN_TILED(PhiStudent);
-    default: return BN_TILED(PhiHalfSquare);
+// f(PHI()) for the row function of the kind
+template <class F>
+static int bnn_dispatch_phi(int kind, F &&f) {
+  switch (kind) {
+    case NF_TARGET_BNN_LOGIT: return f(PhiLogSigmoid());
+    case NF_TARGET_BNN_PROBIT: return f(PhiLogNormCdf());
+    case NF_TARGET_BNN_POISSON: return f(PhiNegExp());
+    case NF_TARGET_BNN_STUDENT: return f(PhiStudent());
+    default: return f(PhiHalfSquare());
   }
-#undef BN_TILED
+}
+
+template <class PHI, int DB>
+static int launch_bnn_tiled(const TgtTiledArgs &a) {
+  using G = BnGeo<DB>;
+  const int H = (int)a.t->s1, p = (a.d - 1) / H - 1;
+  nf_ctx *ctx = a.ctx;
+  NF_TRY((tgt_lds_once<k_target_bnn_tiled<PHI, DB>>(ctx, G::floats(G::PMAX) * sizeof(float))));
+  ProfScope ps(ctx, "target_bnn");
+  return tgt_launch_tiled<k_target_bnn_tiled<PHI, DB>>(a, (size_t)G::floats(p) * sizeof(float), a.d, H, (int)a.t->s0, a.N, a.yt,
+                                                       (const float *)a.t->p0, (const float *)a.t->p1);
+}
+
+int nf_launch_target_bnn_tiled(const TgtTiledArgs &a) {
+  if (bnn_unsupported(a.t, a.d)) return NF_ERR_UNSUPPORTED;
+  return bnn_dispatch_phi(a.t->kind, [&](auto phi) {
+    return tgt_dispatch_db(a.d, [&](auto db) { return launch_bnn_tiled<decltype(phi), db()>(a); });
+  });
 }
 
 // elements of LDS the flat kernel takes at (d, H)
 static size_t bnn_flat_lds(int d, int H) { return (size_t)(BNF_SPB * (d + 1) + BNF_RB * ((d - 1) / H) + BNF_SPB * (BNF_RB * H + 1)); }
 
 template <class PHI, class T>
-static int launch_bnn_flat(nf_ctx *ctx, const nf_target *t, int d, long N, const void *y, const void *logq, const void *ladj,
-                           void *logp_out, void *grad_out, double gscale, void *elbos_out, double *partial, double pscale) {
-  const int H = (int)t->s1;
-  const size_t lds = bnn_flat_lds(d, H) * sizeof(T);
-  static AttrOnce attr_once;
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    // the most any served target takes: d = 256, with the widest image (p = 128) and the widest [row][unit] block (H = 16) both counted
-    const size_t most = (size_t)(BNF_SPB * (BN_MAXD + 1) + BNF_RB * (BN_MAXP + 1) + BNF_SPB * (BNF_RB * BN_MAXH + 1)) * sizeof(T);
-    NF_HIP(hipFuncSetAttribute((const void *)k_target_bnn<PHI, T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)most));
-    return NF_OK;
-  }));
+static int launch_bnn_flat(const TgtFlatArgs &a) {
+  const int H = (int)a.t->s1;
+  // the most any served target takes: d = 256, with the widest image (p = 128) and the widest [row][unit] block (H = 16) both counted
+  const size_t most = (size_t)(BNF_SPB * (BN_MAXD + 1) + BNF_RB * (BN_MAXP + 1) + BNF_SPB * (BNF_RB * BN_MAXH + 1)) * sizeof(T);
+  nf_ctx *ctx = a.ctx;
+  NF_TRY((tgt_lds_once<k_target_bnn<PHI, T>>(ctx, most)));
   ProfScope ps(ctx, "target_bnn");
-  const long nb = (N + BNF_SPB - 1) / BNF_SPB;
-  hipLaunchKernelGGL((k_target_bnn<PHI, T>), dim3((unsigned)nb), dim3(BN_BLOCK), lds, ctx->stream, d, H, (int)t->s0, N, (const T *)y,
-                     (const T *)t->p0, (const T *)t->p1, (const T *)logq, (const T *)ladj, (T *)logp_out, (T *)grad_out, (T)gscale,
-                     (T *)elbos_out, partial, pscale);
-  return (int)hipGetLastError();
+  return tgt_launch_flat<k_target_bnn<PHI, T>, T>(a, bnn_flat_lds(a.d, H) * sizeof(T), a.d, H, (int)a.t->s0, a.N, (const T *)a.y,
+                                                  (const T *)a.t->p0, (const T *)a.t->p1);
 }
 
-int nf_launch_target_bnn(nf_ctx *ctx, int dtype, const nf_target *t, int d, long N, const void *y, const void *logq, const void *ladj,
-                         void *logp_out, void *grad_out, double gscale, void *elbos_out, double *partial, double pscale) {
-  if (bnn_unsupported(t, d)) return NF_ERR_UNSUPPORTED;
-#define BN_FLAT(PHI)                                                                                                               \
-  (dtype == NF_DTYPE_F32 ? launch_bnn_flat<PHI, float>(ctx, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale) \
-                         : launch_bnn_flat<PHI, double>(ctx, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale))
-  switch (t->kind) {
-    case NF_TARGET_BNN_LOGIT: return BN_FLAT(PhiLogSigmoid);
-    case NF_TARGET_BNN_PROBIT: return BN_FLAT(PhiLogNormCdf);
-    case NF_TARGET_BNN_POISSON: return BN_FLAT(PhiNegExp);
-    case NF_TARGET_BNN_STUDENT: return BN_FLAT(PhiStudent);
-    default: return BN_FLAT(PhiHalfSquare);
-  }
-#undef BN_FLAT
+int nf_launch_target_bnn(const TgtFlatArgs &a) {
+  if (bnn_unsupported(a.t, a.d)) return NF_ERR_UNSUPPORTED;
+  return bnn_dispatch_phi(a.t->kind, [&](auto phi) {
+    return tgt_dispatch_dtype(a.dtype, [&](auto e) { return launch_bnn_flat<decltype(phi), decltype(e)>(a); });
+  });
 }

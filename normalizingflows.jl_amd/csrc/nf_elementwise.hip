@@ -8,6 +8,7 @@
 // are 4-step DPP/shuffle reductions inside the group.
 #include "nf_common.h"
 #include "nf_philox.h"
+#include "nf_target_stages.h"
 #include "nf_targets.h"
 
 #define LPS 16
@@ -671,40 +672,6 @@ int nf_target_check(const nf_target *t, int d) {
 
 long nf_target_nblocks(long N) { return nblk(N, SPB); }
 
-// nf_linpred.hip: the linear-predictor kinds, same outputs and partial counts as k_target / k_target_tiled
-int nf_launch_target_linpred(nf_ctx *, int dtype, const nf_target *, int d, long N, const void *y, const void *logq,
-                             const void *ladj, void *logp_out, void *grad_out, double gscale, void *elbos_out, double *partial,
-                             double pscale);
-int nf_launch_target_linpred_tiled(nf_ctx *, const nf_target *, int d, long N, const float *yt, const float *logq,
-                                   const float *ladj, float *gt, double gscale, float *elbos_out, double *partial, double pscale);
-// nf_mixture.hip: the Gaussian mixture, the same contract
-int nf_launch_target_mixture(nf_ctx *, int dtype, const nf_target *, int d, long N, const void *y, const void *logq,
-                             const void *ladj, void *logp_out, void *grad_out, double gscale, void *elbos_out, double *partial,
-                             double pscale);
-int nf_launch_target_mixture_tiled(nf_ctx *, const nf_target *, int d, long N, const float *yt, const float *logq,
-                                   const float *ladj, float *gt, double gscale, float *elbos_out, double *partial, double pscale);
-// nf_softmax.hip: the softmax regression target, the same contract
-int nf_launch_target_softmax(nf_ctx *, int dtype, const nf_target *, int d, long N, const void *y, const void *logq,
-                             const void *ladj, void *logp_out, void *grad_out, double gscale, void *elbos_out, double *partial,
-                             double pscale);
-int nf_launch_target_softmax_tiled(nf_ctx *, const nf_target *, int d, long N, const float *yt, const float *logq,
-                                   const float *ladj, float *gt, double gscale, float *elbos_out, double *partial, double pscale);
-// nf_bnn.hip: the one-hidden-layer Bayesian neural-network targets, the same contract
-int nf_launch_target_bnn(nf_ctx *, int dtype, const nf_target *, int d, long N, const void *y, const void *logq, const void *ladj,
-                         void *logp_out, void *grad_out, double gscale, void *elbos_out, double *partial, double pscale);
-int nf_launch_target_bnn_tiled(nf_ctx *, const nf_target *, int d, long N, const float *yt, const float *logq, const float *ladj,
-                               float *gt, double gscale, float *elbos_out, double *partial, double pscale);
-// nf_ordinal.hip: the ordinal (cumulative-logit) regression target, the same contract
-int nf_launch_target_ordinal(nf_ctx *, int dtype, const nf_target *, int d, long N, const void *y, const void *logq, const void *ladj,
-                             void *logp_out, void *grad_out, double gscale, void *elbos_out, double *partial, double pscale);
-int nf_launch_target_ordinal_tiled(nf_ctx *, const nf_target *, int d, long N, const float *yt, const float *logq, const float *ladj,
-                                   float *gt, double gscale, float *elbos_out, double *partial, double pscale);
-// nf_riskset.hip: the risk-set (Cox / conditional-logit) target, the same contract
-int nf_launch_target_riskset(nf_ctx *, int dtype, const nf_target *, int d, long N, const void *y, const void *logq, const void *ladj,
-                             void *logp_out, void *grad_out, double gscale, void *elbos_out, double *partial, double pscale);
-int nf_launch_target_riskset_tiled(nf_ctx *, const nf_target *, int d, long N, const float *yt, const float *logq, const float *ladj,
-                                   float *gt, double gscale, float *elbos_out, double *partial, double pscale);
-
 int nf_launch_target(nf_ctx *ctx, int dtype, const nf_target *t, int d, long N, const void *y, const void *logq,
                      const void *ladj, void *logp_out, void *grad_out, double gscale, void *elbos_out, double *partial,
                      double pscale, int joint_d) {
@@ -712,17 +679,13 @@ int nf_launch_target(nf_ctx *ctx, int dtype, const nf_target *t, int d, long N, 
   NF_TRY(nf_target_check(t, joint_d > 0 ? joint_d : d));
   if (target_has_own_kernel(t->kind)) {
     if (joint_d > 0) return NF_ERR_UNSUPPORTED;  // (the ELBO entry points refuse Hamiltonian flows with these kinds first)
-    if (t->kind == NF_TARGET_GAUSSMIX)
-      return nf_launch_target_mixture(ctx, dtype, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
-    if (t->kind == NF_TARGET_SOFTMAX)
-      return nf_launch_target_softmax(ctx, dtype, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
-    if (target_is_bnn(t->kind))
-      return nf_launch_target_bnn(ctx, dtype, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
-    if (target_is_ordinal(t->kind))
-      return nf_launch_target_ordinal(ctx, dtype, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
-    if (target_is_riskset(t->kind))
-      return nf_launch_target_riskset(ctx, dtype, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
-    return nf_launch_target_linpred(ctx, dtype, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
+    const TgtFlatArgs a = {ctx, dtype, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale};
+    if (t->kind == NF_TARGET_GAUSSMIX) return nf_launch_target_mixture(a);
+    if (t->kind == NF_TARGET_SOFTMAX) return nf_launch_target_softmax(a);
+    if (target_is_bnn(t->kind)) return nf_launch_target_bnn(a);
+    if (target_is_ordinal(t->kind)) return nf_launch_target_ordinal(a);
+    if (target_is_riskset(t->kind)) return nf_launch_target_riskset(a);
+    return nf_launch_target_linpred(a);
   }
   ProfScope ps(ctx, "target");
   if (dtype == NF_DTYPE_F32)
@@ -840,18 +803,13 @@ int nf_launch_target_tiled(nf_ctx *ctx, const nf_target *t, int d, long N, const
                            double pscale) {
   if (N <= 0) return NF_OK;
   NF_TRY(nf_target_check(t, d));
-  if (t->kind == NF_TARGET_GAUSSMIX)
-    return nf_launch_target_mixture_tiled(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
-  if (t->kind == NF_TARGET_SOFTMAX)
-    return nf_launch_target_softmax_tiled(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
-  if (target_is_bnn(t->kind))
-    return nf_launch_target_bnn_tiled(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
-  if (target_is_ordinal(t->kind))
-    return nf_launch_target_ordinal_tiled(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
-  if (target_is_riskset(t->kind))
-    return nf_launch_target_riskset_tiled(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
-  if (target_is_linpred(t->kind))
-    return nf_launch_target_linpred_tiled(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
+  const TgtTiledArgs a = {ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale};
+  if (t->kind == NF_TARGET_GAUSSMIX) return nf_launch_target_mixture_tiled(a);
+  if (t->kind == NF_TARGET_SOFTMAX) return nf_launch_target_softmax_tiled(a);
+  if (target_is_bnn(t->kind)) return nf_launch_target_bnn_tiled(a);
+  if (target_is_ordinal(t->kind)) return nf_launch_target_ordinal_tiled(a);
+  if (target_is_riskset(t->kind)) return nf_launch_target_riskset_tiled(a);
+  if (target_is_linpred(t->kind)) return nf_launch_target_linpred_tiled(a);
   ProfScope ps(ctx, "target");
   hipLaunchKernelGGL(k_target_tiled, dim3((unsigned)nf_target_tiled_nblocks(N)), dim3(EW_BLOCK), 0, ctx->stream,
                      t->kind, d, N, yt, (const float *)t->p0, (const float *)t->p1, (float)t->s0, (float)t->s1, logq,

@@ -17,8 +17,13 @@
 //                  k_target_disp_tiled: dispersion)
 //   lp_flat_body   flat layout, float / double, drop-in for k_target: vector pipe (Float64 flows, nf_target_logp)
 //                  (k_target_linpred, k_target_glm, k_target_hier, k_target_disp)
+// Shared stages (nf_target_stages.h): tgt_elbo_term (both bodies; the centred flat kernels keep it in place), tgt_block_partial (the
+// flat body; the tiled one keeps it in place) and the launch helpers.
+// lp_stage bounds both rows and features of a chunk and is this file's own; what else stands here in place does so for
+// nf_ordinal.hip's reason.
 #include "nf_common.h"
 #include "nf_linpred.h"
+#include "nf_target_stages.h"
 
 // ---------------------------------------------------------------------------------------------------------------------
 // tiled kernel
@@ -320,12 +325,9 @@ __device__ __forceinline__ void lp_tiled_body(int d, int rows, long N, const flo
       for (int k = 0; k < LP_BLOCK / 32; ++k) tl += redl[k][s];
       e = HIER ? rd.par[1] + l + tl + t : (rd.par[1] + c0) + l + tl - 0.5f * pw * t;
     }
-    if (logq) e -= logq[j];
-    if (ladj) e += ladj[j];
-    if (elbos_out) elbos_out[j] = e;
-    contrib = pscale * (double)e;
+    contrib = tgt_elbo_term(e, j, logq, ladj, elbos_out, pscale);
   }
-  if (partial) {
+  if (partial) {  // (tgt_block_partial, in place: as a call it reorders the kernels' last instructions, and k_target_glm_tiled<8> then measured 0.3 % outside the parent's spread)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) contrib += __shfl_xor(contrib, o, 64);
     if (lane == 0) sm[wave] = contrib;
@@ -519,18 +521,16 @@ __device__ __forceinline__ void lp_flat_body(int d, int rows, long N, const T *_
     T e = c0 + lp - (T)0.5 * pw * yy;
     if (GLM) e = HIER ? rd.par[1] + lp + ly + yy : (rd.par[1] + c0) + lp + ly - (T)0.5 * pw * yy;
     if (logp_out) logp_out[j] = e;
-    if (logq) e -= logq[j];
-    if (ladj) e += ladj[j];
-    if (elbos_out) elbos_out[j] = e;
-    contrib = pscale * (double)e;
+    if constexpr (GLM)
+      contrib = tgt_elbo_term(e, j, logq, ladj, elbos_out, pscale);
+    else {  // (tgt_elbo_term, in place: as a call the four centred kernels come out in another order, and no benchmark times them)
+      if (logq) e -= logq[j];
+      if (ladj) e += ladj[j];
+      if (elbos_out) elbos_out[j] = e;
+      contrib = pscale * (double)e;
+    }
   }
-  if (partial) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) contrib += __shfl_xor(contrib, o, 64);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = contrib;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
-  }
+  tgt_block_partial(contrib, sm, partial);
 }
 
 template <class T, class PHI>
@@ -575,7 +575,7 @@ __global__ __launch_bounds__(LP_BLOCK) void k_target_disp(int d, int rows, long 
 // ---------------------------------------------------------------------------------------------------------------------
 // the kernel of a form (only the one asked for is instantiated)
 template <int DB, class PHI, int FORM>
-static auto tiled_kernel() {
+static constexpr auto tiled_kernel() {
   if constexpr (FORM == LP_DISP)
     return &k_target_disp_tiled<DB, PHI>;
   else if constexpr (FORM == LP_HIER)
@@ -586,7 +586,7 @@ static auto tiled_kernel() {
     return &k_target_linpred_tiled<DB, PHI>;
 }
 template <class T, class PHI, int FORM>
-static auto flat_kernel() {
+static constexpr auto flat_kernel() {
   if constexpr (FORM == LP_DISP)
     return &k_target_disp<T, PHI>;
   else if constexpr (FORM == LP_HIER)
@@ -598,114 +598,68 @@ static auto flat_kernel() {
 }
 
 template <int DB, class PHI, int FORM>
-static int launch_tiled(nf_ctx *ctx, const nf_target *t, int d, long N, const float *yt, const float *logq, const float *ladj,
-                        float *gt, double gscale, float *elbos_out, double *partial, double pscale) {
+static int launch_tiled(const TgtTiledArgs &a) {
   // dispersion form: + the d phi / d lambda partial sums (sL's shape) and the table term's [2][8][32] partials
   const size_t lds = (size_t)(LpGeo<DB>::FLOATS + (FORM == LP_DISP ? LP_WAVES * 64 + 2 * LP_BLOCK : 0)) * sizeof(float);
-  const auto kern = tiled_kernel<DB, PHI, FORM>();
-  static AttrOnce attr_once;  // once per device
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    NF_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return NF_OK;
-  }));
-  const LinpredConsts k = linpred_consts(t, d);
+  constexpr auto kern = tiled_kernel<DB, PHI, FORM>();
+  nf_ctx *ctx = a.ctx;
+  NF_TRY(tgt_lds_once<kern>(ctx, lds));
+  const LinpredConsts k = linpred_consts(a.t, a.d);
   ProfScope ps(ctx, "target_linpred");
   if constexpr (FORM == LP_HIER || FORM == LP_DISP)
-    hipLaunchKernelGGL(kern, dim3((unsigned)((N + 31) / 32)), dim3(LP_BLOCK), lds, ctx->stream, d,
-                       (int)k.rows, N, yt, (const float *)t->p0, (const float *)t->p1, (int)t->s1, logq, ladj, gt,
-                       (float)gscale, elbos_out, partial, pscale);
+    return tgt_launch_tiled<kern>(a, lds, a.d, (int)k.rows, a.N, a.yt, (const float *)a.t->p0, (const float *)a.t->p1, (int)a.t->s1);
   else
-    hipLaunchKernelGGL(kern, dim3((unsigned)((N + 31) / 32)), dim3(LP_BLOCK), lds, ctx->stream, d,
-                       (int)k.rows, N, yt, (const float *)t->p0, (const float *)t->p1, (float)k.c, (float)k.pw, logq, ladj, gt,
-                       (float)gscale, elbos_out, partial, pscale);
-  return (int)hipGetLastError();
-}
-
-template <class PHI, int FORM>
-static int launch_tiled_phi(nf_ctx *ctx, const nf_target *t, int d, long N, const float *yt, const float *logq,
-                            const float *ladj, float *gt, double gscale, float *elbos_out, double *partial, double pscale) {
-  if (d <= 32) return launch_tiled<1, PHI, FORM>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
-  if (d <= 64) return launch_tiled<2, PHI, FORM>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
-  if (d <= 128) return launch_tiled<4, PHI, FORM>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
-  return launch_tiled<8, PHI, FORM>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
-}
-
-int nf_launch_target_linpred_tiled(nf_ctx *ctx, const nf_target *t, int d, long N, const float *yt, const float *logq,
-                                   const float *ladj, float *gt, double gscale, float *elbos_out, double *partial,
-                                   double pscale) {
-  if (d > LPF_MAXD) return NF_ERR_UNSUPPORTED;
-#define LP_TILED(PHI, FORM) launch_tiled_phi<PHI, FORM>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale)
-  switch (t->kind) {
-    case NF_TARGET_DENSEGAUSS: return LP_TILED(PhiHalfSquare, LP_CENTRED);
-    case NF_TARGET_LOGREG: return LP_TILED(PhiLogSigmoid, LP_CENTRED);
-    case NF_TARGET_GLM_LOGIT: return LP_TILED(PhiLogSigmoid, LP_GLM);
-    case NF_TARGET_GLM_PROBIT: return LP_TILED(PhiLogNormCdf, LP_GLM);
-    case NF_TARGET_GLM_POISSON: return LP_TILED(PhiNegExp, LP_GLM);
-    case NF_TARGET_GLM_STUDENT: return LP_TILED(PhiStudent, LP_GLM);
-    case NF_TARGET_GLM_NORMAL: return LP_TILED(PhiHalfSquare, LP_GLM);
-    case NF_TARGET_HGLM_LOGIT: return LP_TILED(PhiLogSigmoid, LP_HIER);
-    case NF_TARGET_HGLM_PROBIT: return LP_TILED(PhiLogNormCdf, LP_HIER);
-    case NF_TARGET_HGLM_POISSON: return LP_TILED(PhiNegExp, LP_HIER);
-    case NF_TARGET_HGLM_STUDENT: return LP_TILED(PhiStudent, LP_HIER);
-    case NF_TARGET_HGLM_NORMAL: return LP_TILED(PhiHalfSquare, LP_HIER);
-    case NF_TARGET_DGLM_NORMAL: return LP_TILED(DispScale<PhiHalfSquare>, LP_DISP);
-    case NF_TARGET_DGLM_STUDENT: return LP_TILED(DispScale<PhiStudent>, LP_DISP);
-    case NF_TARGET_DGLM_NEGBIN: return LP_TILED(DispNegBin, LP_DISP);
-    default: return NF_ERR_ARG;
-  }
-#undef LP_TILED
+    return tgt_launch_tiled<kern>(a, lds, a.d, (int)k.rows, a.N, a.yt, (const float *)a.t->p0, (const float *)a.t->p1, (float)k.c, (float)k.pw);
 }
 
 template <class T, class PHI, int FORM>
-static int launch_flat(nf_ctx *ctx, const nf_target *t, int d, long N, const void *y, const void *logq, const void *ladj,
-                       void *logp_out, void *grad_out, double gscale, void *elbos_out, double *partial, double pscale) {
-  const size_t lds = (size_t)((LPF_SPB + LPF_RB) * (d + 1) + LPF_SPB * (LPF_RB + 1)) * sizeof(T);
-  const auto kern = flat_kernel<T, PHI, FORM>();
-  static AttrOnce attr_once;
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    const size_t most = (size_t)((LPF_SPB + LPF_RB) * (LPF_MAXD + 1) + LPF_SPB * (LPF_RB + 1)) * sizeof(T);
-    NF_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)most));
-    return NF_OK;
-  }));
-  const LinpredConsts k = linpred_consts(t, d);
+static int launch_flat(const TgtFlatArgs &a) {
+  const size_t lds = (size_t)((LPF_SPB + LPF_RB) * (a.d + 1) + LPF_SPB * (LPF_RB + 1)) * sizeof(T);
+  constexpr auto kern = flat_kernel<T, PHI, FORM>();
+  nf_ctx *ctx = a.ctx;
+  NF_TRY(tgt_lds_once<kern>(ctx, (size_t)((LPF_SPB + LPF_RB) * (LPF_MAXD + 1) + LPF_SPB * (LPF_RB + 1)) * sizeof(T)));
+  const LinpredConsts k = linpred_consts(a.t, a.d);
   ProfScope ps(ctx, "target_linpred");
-  const long nb = (N + LPF_SPB - 1) / LPF_SPB;
   if constexpr (FORM == LP_HIER || FORM == LP_DISP)
-    hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(LP_BLOCK), lds, ctx->stream, d, (int)k.rows, N,
-                       (const T *)y, (const T *)t->p0, (const T *)t->p1, (int)t->s1, (const T *)logq, (const T *)ladj,
-                       (T *)logp_out, (T *)grad_out, (T)gscale, (T *)elbos_out, partial, pscale);
+    return tgt_launch_flat<kern, T>(a, lds, a.d, (int)k.rows, a.N, (const T *)a.y, (const T *)a.t->p0, (const T *)a.t->p1, (int)a.t->s1);
   else
-    hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(LP_BLOCK), lds, ctx->stream, d, (int)k.rows, N,
-                       (const T *)y, (const T *)t->p0, (const T *)t->p1, (T)k.c, (T)k.pw, (const T *)logq, (const T *)ladj,
-                       (T *)logp_out, (T *)grad_out, (T)gscale, (T *)elbos_out, partial, pscale);
-  return (int)hipGetLastError();
+    return tgt_launch_flat<kern, T>(a, lds, a.d, (int)k.rows, a.N, (const T *)a.y, (const T *)a.t->p0, (const T *)a.t->p1, (T)k.c, (T)k.pw);
 }
 
-int nf_launch_target_linpred(nf_ctx *ctx, int dtype, const nf_target *t, int d, long N, const void *y, const void *logq,
-                             const void *ladj, void *logp_out, void *grad_out, double gscale, void *elbos_out,
-                             double *partial, double pscale) {
-  if (d > LPF_MAXD) return NF_ERR_UNSUPPORTED;
-#define LP_FLAT(PHI, FORM)                                                                                                       \
-  (dtype == NF_DTYPE_F32                                                                                                       \
-       ? launch_flat<float, PHI, FORM>(ctx, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale)     \
-       : launch_flat<double, PHI, FORM>(ctx, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale))
-  switch (t->kind) {
-    case NF_TARGET_DENSEGAUSS: return LP_FLAT(PhiHalfSquare, LP_CENTRED);
-    case NF_TARGET_LOGREG: return LP_FLAT(PhiLogSigmoid, LP_CENTRED);
-    case NF_TARGET_GLM_LOGIT: return LP_FLAT(PhiLogSigmoid, LP_GLM);
-    case NF_TARGET_GLM_PROBIT: return LP_FLAT(PhiLogNormCdf, LP_GLM);
-    case NF_TARGET_GLM_POISSON: return LP_FLAT(PhiNegExp, LP_GLM);
-    case NF_TARGET_GLM_STUDENT: return LP_FLAT(PhiStudent, LP_GLM);
-    case NF_TARGET_GLM_NORMAL: return LP_FLAT(PhiHalfSquare, LP_GLM);
-    case NF_TARGET_HGLM_LOGIT: return LP_FLAT(PhiLogSigmoid, LP_HIER);
-    case NF_TARGET_HGLM_PROBIT: return LP_FLAT(PhiLogNormCdf, LP_HIER);
-    case NF_TARGET_HGLM_POISSON: return LP_FLAT(PhiNegExp, LP_HIER);
-    case NF_TARGET_HGLM_STUDENT: return LP_FLAT(PhiStudent, LP_HIER);
-    case NF_TARGET_HGLM_NORMAL: return LP_FLAT(PhiHalfSquare, LP_HIER);
-    case NF_TARGET_DGLM_NORMAL: return LP_FLAT(DispScale<PhiHalfSquare>, LP_DISP);
-    case NF_TARGET_DGLM_STUDENT: return LP_FLAT(DispScale<PhiStudent>, LP_DISP);
-    case NF_TARGET_DGLM_NEGBIN: return LP_FLAT(DispNegBin, LP_DISP);
+// f(PHI(), std::integral_constant<int, FORM>()) for the row function and the form of the kind
+template <class F>
+static int linpred_dispatch_kind(int kind, F &&f) {
+  using std::integral_constant;
+  switch (kind) {
+    case NF_TARGET_DENSEGAUSS: return f(PhiHalfSquare(), integral_constant<int, LP_CENTRED>());
+    case NF_TARGET_LOGREG: return f(PhiLogSigmoid(), integral_constant<int, LP_CENTRED>());
+    case NF_TARGET_GLM_LOGIT: return f(PhiLogSigmoid(), integral_constant<int, LP_GLM>());
+    case NF_TARGET_GLM_PROBIT: return f(PhiLogNormCdf(), integral_constant<int, LP_GLM>());
+    case NF_TARGET_GLM_POISSON: return f(PhiNegExp(), integral_constant<int, LP_GLM>());
+    case NF_TARGET_GLM_STUDENT: return f(PhiStudent(), integral_constant<int, LP_GLM>());
+    case NF_TARGET_GLM_NORMAL: return f(PhiHalfSquare(), integral_constant<int, LP_GLM>());
+    case NF_TARGET_HGLM_LOGIT: return f(PhiLogSigmoid(), integral_constant<int, LP_HIER>());
+    case NF_TARGET_HGLM_PROBIT: return f(PhiLogNormCdf(), integral_constant<int, LP_HIER>());
+    case NF_TARGET_HGLM_POISSON: return f(PhiNegExp(), integral_constant<int, LP_HIER>());
+    case NF_TARGET_HGLM_STUDENT: return f(PhiStudent(), integral_constant<int, LP_HIER>());
+    case NF_TARGET_HGLM_NORMAL: return f(PhiHalfSquare(), integral_constant<int, LP_HIER>());
+    case NF_TARGET_DGLM_NORMAL: return f(DispScale<PhiHalfSquare>(), integral_constant<int, LP_DISP>());
+    case NF_TARGET_DGLM_STUDENT: return f(DispScale<PhiStudent>(), integral_constant<int, LP_DISP>());
+    case NF_TARGET_DGLM_NEGBIN: return f(DispNegBin(), integral_constant<int, LP_DISP>());
     default: return NF_ERR_ARG;
   }
-#undef LP_FLAT
+}
+
+int nf_launch_target_linpred_tiled(const TgtTiledArgs &a) {
+  if (a.d > LPF_MAXD) return NF_ERR_UNSUPPORTED;
+  return linpred_dispatch_kind(a.t->kind, [&](auto phi, auto form) {
+    return tgt_dispatch_db(a.d, [&](auto db) { return launch_tiled<db(), decltype(phi), form()>(a); });
+  });
+}
+
+int nf_launch_target_linpred(const TgtFlatArgs &a) {
+  if (a.d > LPF_MAXD) return NF_ERR_UNSUPPORTED;
+  return linpred_dispatch_kind(a.t->kind, [&](auto phi, auto form) {
+    return tgt_dispatch_dtype(a.dtype, [&](auto e) { return launch_flat<decltype(e), decltype(phi), form()>(a); });
+  });
 }

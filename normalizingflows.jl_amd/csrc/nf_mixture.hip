@@ -7,8 +7,11 @@
 //   k_target_mixture_tiled  Float32, tiled layout, d <= 64, drop-in for k_target_linpred_tiled: both GEMMs of every
 //                           component on v_mfma_f32_32x32x2_f32, one pass with a running log-sum-exp per sample
 //   k_target_mixture        flat layout, float / double, d <= 256, drop-in for k_target_linpred: vector pipe
+// Shared stages (nf_target_stages.h): tgt_elbo_term (both kernels), tgt_block_partial (the flat kernel; the tiled one keeps it in
+// place), and the launch helpers.  The image here is a whole component, staged and multiplied by its own loops.
 #include "nf_common.h"
 #include "nf_linpred.h"
+#include "nf_target_stages.h"
 
 #define MX_BLOCK 256
 #define MX_WAVES 4
@@ -176,7 +179,7 @@ __global__ __launch_bounds__(MX_BLOCK) void k_target_mixture_tiled(int d, int K,
 #pragma unroll
       for (int r = 0; r < 16; ++r) Gacc[b][r] *= e;
   }
-  for (int w = 0; w < MX_WAVES; ++w) {
+  for (int w = 0; w < MX_WAVES; ++w) {  // (the barrier BEHIND each turn: the one above, which the rescaling needs, already frees the tile)
     if (wave == w) {
 #pragma unroll
       for (int b = 0; b < DB; ++b) {
@@ -213,12 +216,9 @@ __global__ __launch_bounds__(MX_BLOCK) void k_target_mixture_tiled(int d, int K,
   double contrib = 0.0;
   if (q == 0 && valid) {
     float e = Ms + nf_log(Ss);
-    if (logq) e -= logq[j];
-    if (ladj) e += ladj[j];
-    if (elbos_out) elbos_out[j] = e;
-    contrib = pscale * (double)e;
+    contrib = tgt_elbo_term(e, j, logq, ladj, elbos_out, pscale);
   }
-  if (partial) {
+  if (partial) {  // (tgt_block_partial, in place: as a call this kernel gains instructions)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) contrib += __shfl_xor(contrib, o, 64);
     if (lane == 0) sm[wave] = contrib;
@@ -314,72 +314,40 @@ __global__ __launch_bounds__(MX_BLOCK) void k_target_mixture(int d, int K, long 
   if (valid && q == 0) {
     T e = M + mx_log(Ssum);
     if (logp_out) logp_out[j] = e;
-    if (logq) e -= logq[j];
-    if (ladj) e += ladj[j];
-    if (elbos_out) elbos_out[j] = e;
-    contrib = pscale * (double)e;
+    contrib = tgt_elbo_term(e, j, logq, ladj, elbos_out, pscale);
   }
-  if (partial) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) contrib += __shfl_xor(contrib, o, 64);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = contrib;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
-  }
+  tgt_block_partial(contrib, sm, partial);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // launchers (called by nf_launch_target / nf_launch_target_tiled after nf_target_check)
 // ---------------------------------------------------------------------------------------------------------------------
 template <int DB>
-static int launch_mixture_tiled(nf_ctx *ctx, const nf_target *t, int d, long N, const float *yt, const float *logq,
-                                const float *ladj, float *gt, double gscale, float *elbos_out, double *partial, double pscale) {
+static int launch_mixture_tiled(const TgtTiledArgs &a) {
   const size_t lds = (size_t)MxGeo<DB>::FLOATS * sizeof(float);
-  static AttrOnce attr_once;  // once per device
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    NF_HIP(hipFuncSetAttribute((const void *)k_target_mixture_tiled<DB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return NF_OK;
-  }));
+  nf_ctx *ctx = a.ctx;
+  NF_TRY(tgt_lds_once<k_target_mixture_tiled<DB>>(ctx, lds));
   ProfScope ps(ctx, "target_mixture");
-  hipLaunchKernelGGL((k_target_mixture_tiled<DB>), dim3((unsigned)((N + 31) / 32)), dim3(MX_BLOCK), lds, ctx->stream, d,
-                     (int)t->s0, N, yt, (const float *)t->p0, (const float *)t->p1, logq, ladj, gt, (float)gscale, elbos_out,
-                     partial, pscale);
-  return (int)hipGetLastError();
+  return tgt_launch_tiled<k_target_mixture_tiled<DB>>(a, lds, a.d, (int)a.t->s0, a.N, a.yt, (const float *)a.t->p0, (const float *)a.t->p1);
 }
 
 // d <= 64 only (two U and two G blocks in registers): the ELBO entry points refuse Float32 coupling flows beyond it first
-int nf_launch_target_mixture_tiled(nf_ctx *ctx, const nf_target *t, int d, long N, const float *yt, const float *logq,
-                                   const float *ladj, float *gt, double gscale, float *elbos_out, double *partial,
-                                   double pscale) {
-  if (d > NF_MIXTURE_TILED_MAXD) return NF_ERR_UNSUPPORTED;
-  if (d <= 32) return launch_mixture_tiled<1>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
-  return launch_mixture_tiled<2>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
+int nf_launch_target_mixture_tiled(const TgtTiledArgs &a) {
+  if (a.d > NF_MIXTURE_TILED_MAXD) return NF_ERR_UNSUPPORTED;
+  return tgt_dispatch_db<2>(a.d, [&](auto db) { return launch_mixture_tiled<db()>(a); });
 }
 
 template <class T>
-static int launch_mixture_flat(nf_ctx *ctx, const nf_target *t, int d, long N, const void *y, const void *logq,
-                               const void *ladj, void *logp_out, void *grad_out, double gscale, void *elbos_out,
-                               double *partial, double pscale) {
-  const size_t lds = (size_t)((MXF_SPB + MXF_RB) * (d + 1) + MXF_SPB * (MXF_RB + 1)) * sizeof(T);
-  static AttrOnce attr_once;
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    const size_t most = (size_t)((MXF_SPB + MXF_RB) * (MXF_MAXD + 1) + MXF_SPB * (MXF_RB + 1)) * sizeof(T);
-    NF_HIP(hipFuncSetAttribute((const void *)k_target_mixture<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)most));
-    return NF_OK;
-  }));
+static int launch_mixture_flat(const TgtFlatArgs &a) {
+  const size_t most = (size_t)((MXF_SPB + MXF_RB) * (MXF_MAXD + 1) + MXF_SPB * (MXF_RB + 1)) * sizeof(T);
+  nf_ctx *ctx = a.ctx;
+  NF_TRY(tgt_lds_once<k_target_mixture<T>>(ctx, most));
   ProfScope ps(ctx, "target_mixture");
-  const long nb = (N + MXF_SPB - 1) / MXF_SPB;
-  hipLaunchKernelGGL((k_target_mixture<T>), dim3((unsigned)nb), dim3(MX_BLOCK), lds, ctx->stream, d, (int)t->s0, N,
-                     (const T *)y, (const T *)t->p0, (const T *)t->p1, (const T *)logq, (const T *)ladj, (T *)logp_out,
-                     (T *)grad_out, (T)gscale, (T *)elbos_out, partial, pscale);
-  return (int)hipGetLastError();
+  return tgt_launch_flat<k_target_mixture<T>, T>(a, (size_t)((MXF_SPB + MXF_RB) * (a.d + 1) + MXF_SPB * (MXF_RB + 1)) * sizeof(T), a.d,
+                                                 (int)a.t->s0, a.N, (const T *)a.y, (const T *)a.t->p0, (const T *)a.t->p1);
 }
 
-int nf_launch_target_mixture(nf_ctx *ctx, int dtype, const nf_target *t, int d, long N, const void *y, const void *logq,
-                             const void *ladj, void *logp_out, void *grad_out, double gscale, void *elbos_out,
-                             double *partial, double pscale) {
-  if (d > MXF_MAXD) return NF_ERR_UNSUPPORTED;
-  if (dtype == NF_DTYPE_F32)
-    return launch_mixture_flat<float>(ctx, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
-  return launch_mixture_flat<double>(ctx, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
+int nf_launch_target_mixture(const TgtFlatArgs &a) {
+  if (a.d > MXF_MAXD) return NF_ERR_UNSUPPORTED;
+  return tgt_dispatch_dtype(a.dtype, [&](auto e) { return launch_mixture_flat<decltype(e)>(a); });
 }

@@ -17,8 +17,13 @@
 //   k_target_ordinal        flat layout, float / double, drop-in for k_target: vector pipe (Float64 flows, nf_target_logp)
 // A row of weight 0 contributes exactly 0 to the value and to every gradient by SELECT, at every place its values enter a sum.
 // Nothing is clamped.
+// Shared stages (nf_target_stages.h): tgt_stage and tgt_gemm1 (the wave's image of a row block, GEMM 1 from it), tgt_elbo_term and
+// tgt_block_partial (the ELBO tail of both kernels), and the launch helpers.  The tile load, the wave-ordered combine and the flat
+// kernel's y -> sY load stand here in place, as in every file of the family: as calls they change the kernels' instructions; the
+// tiled epilogue between them was left where it is ("The target kernels' shared stages").
 #include "nf_common.h"
 #include "nf_linpred.h"
+#include "nf_target_stages.h"
 
 #define OR_BLOCK 256
 #define OR_WAVES 4
@@ -95,31 +100,6 @@ struct OrGeo {
   __host__ __device__ static constexpr int floats(int p) { return YTP + OR_WAVES * 32 * stride(p); }
 };
 
-// rows [i0, i0 + 32) x features [f0, f0 + pc) of X -> the wave's image; zero up to the end of pc's last 32-feature block
-__device__ __forceinline__ void or_stage(float *__restrict__ img, int S, const float *__restrict__ X, int i0, int p, int f0, int pc, int lane) {
-  const int l31 = lane & 31, hi = lane >> 5;
-  for (int cb = 0; cb * 32 < pc; ++cb) {
-    const int col = cb * 32 + l31;
-    float v[16];
-#pragma unroll
-    for (int rp = 0; rp < 16; ++rp) v[rp] = col < pc ? X[(long)(i0 + 2 * rp + hi) * p + f0 + col] : 0.f;
-#pragma unroll
-    for (int rp = 0; rp < 16; ++rp) img[(2 * rp + hi) * S + col] = v[rp];
-  }
-}
-
-// U += X_chunk Y_chunk: A from the image, B from the tile at the chunk's first feature (sYc)
-__device__ __forceinline__ f32x16 or_gemm1(f32x16 U, const float *__restrict__ img, int S, const float *__restrict__ sYc, int pc, int l31, int hi) {
-  const int ng = (pc + 7) >> 3;  // groups of four k-steps = eight features; image columns >= pc are zero
-  const float *pa = img + l31 * S + hi;
-  const float *pb = sYc + hi * 32 + l31;
-  for (int g = 0; g < ng; ++g) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) U = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[8 * g + 2 * e], pb[(8 * g + 2 * e) * 32], U, 0, 0, 0);
-  }
-  return U;
-}
-
 template <int DB>
 __global__ __launch_bounds__(OR_BLOCK, DB <= 2 ? 2 : 1) void k_target_ordinal_tiled(int d, int C, int R, long N, const float *__restrict__ yt,
                                                                                    const float *__restrict__ p0, const float *__restrict__ X,
@@ -192,9 +172,9 @@ __global__ __launch_bounds__(OR_BLOCK, DB <= 2 ? 2 : 1) void k_target_ordinal_ti
     }
     for (int ch = 0; ch < nch; ++ch) {
       const int f0 = ch * OR_CW, pc = p - f0 < OR_CW ? p - f0 : OR_CW;
-      or_stage(img, S, X, i0, p, f0, pc, lane);
+      tgt_stage(img, S, X, i0, p, f0, pc, lane);
       wave_lds_fence();
-      U = or_gemm1(U, img, S, sY + f0 * 32, pc, l31, hi);
+      U = tgt_gemm1(U, img, S, sY + f0 * 32, pc, l31, hi);
       if (ch + 1 < nch) wave_lds_fence();  // the next chunk overwrites the image
     }
 
@@ -227,7 +207,7 @@ __global__ __launch_bounds__(OR_BLOCK, DB <= 2 ? 2 : 1) void k_target_ordinal_ti
       const int f0 = ch * OR_CW, pc = p - f0 < OR_CW ? p - f0 : OR_CW;
       if (ch != nch - 1) {
         wave_lds_fence();
-        or_stage(img, S, X, i0, p, f0, pc, lane);
+        tgt_stage(img, S, X, i0, p, f0, pc, lane);
         wave_lds_fence();
       }
 #pragma unroll
@@ -308,18 +288,9 @@ __global__ __launch_bounds__(OR_BLOCK, DB <= 2 ? 2 : 1) void k_target_ordinal_ti
 #pragma unroll
     for (int w = 0; w < OR_WAVES; ++w) l += sL[w][s] + sL[w][32 + s];
     float e = rd.par[1] + l + sV[s] - 0.5f * pwb * tb;
-    if (logq) e -= logq[j];
-    if (ladj) e += ladj[j];
-    if (elbos_out) elbos_out[j] = e;
-    contrib = pscale * (double)e;
+    contrib = tgt_elbo_term(e, j, logq, ladj, elbos_out, pscale);
   }
-  if (partial) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) contrib += __shfl_xor(contrib, o, 64);
-    if (lane == 0) sm[wave] = contrib;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
-  }
+  tgt_block_partial(contrib, sm, partial);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -450,47 +421,28 @@ __global__ __launch_bounds__(OR_BLOCK) void k_target_ordinal(int d, int C, int R
   if (valid && q == 0) {
     T e = rd.par[1] + lp + ev - (T)0.5 * pwb * yy;
     if (logp_out) logp_out[j] = e;
-    if (logq) e -= logq[j];
-    if (ladj) e += ladj[j];
-    if (elbos_out) elbos_out[j] = e;
-    contrib = pscale * (double)e;
+    contrib = tgt_elbo_term(e, j, logq, ladj, elbos_out, pscale);
   }
-  if (partial) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) contrib += __shfl_xor(contrib, o, 64);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = contrib;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
-  }
+  tgt_block_partial(contrib, sm, partial);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // launchers (called by nf_launch_target / nf_launch_target_tiled after nf_target_check: s0 = R, a multiple of 32; s1 = C; d >= C)
 // ---------------------------------------------------------------------------------------------------------------------
 template <int DB>
-static int launch_ordinal_tiled(nf_ctx *ctx, const nf_target *t, int d, long N, const float *yt, const float *logq, const float *ladj,
-                                float *gt, double gscale, float *elbos_out, double *partial, double pscale) {
-  const int C = (int)t->s1, p = d - (C - 1);
-  const size_t lds = (size_t)OrGeo<DB>::floats(p) * sizeof(float);
-  static AttrOnce attr_once;  // once per device
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    NF_HIP(hipFuncSetAttribute((const void *)k_target_ordinal_tiled<DB>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)(OrGeo<DB>::floats(OrGeo<DB>::PMAX) * sizeof(float))));
-    return NF_OK;
-  }));
+static int launch_ordinal_tiled(const TgtTiledArgs &a) {
+  using G = OrGeo<DB>;
+  const int C = (int)a.t->s1, p = a.d - (C - 1);
+  nf_ctx *ctx = a.ctx;
+  NF_TRY(tgt_lds_once<k_target_ordinal_tiled<DB>>(ctx, G::floats(G::PMAX) * sizeof(float)));
   ProfScope ps(ctx, "target_ordinal");
-  hipLaunchKernelGGL((k_target_ordinal_tiled<DB>), dim3((unsigned)((N + 31) / 32)), dim3(OR_BLOCK), lds, ctx->stream, d, C, (int)t->s0, N,
-                     yt, (const float *)t->p0, (const float *)t->p1, logq, ladj, gt, (float)gscale, elbos_out, partial, pscale);
-  return (int)hipGetLastError();
+  return tgt_launch_tiled<k_target_ordinal_tiled<DB>>(a, (size_t)G::floats(p) * sizeof(float), a.d, C, (int)a.t->s0, a.N, a.yt,
+                                                      (const float *)a.t->p0, (const float *)a.t->p1);
 }
 
-int nf_launch_target_ordinal_tiled(nf_ctx *ctx, const nf_target *t, int d, long N, const float *yt, const float *logq, const float *ladj,
-                                   float *gt, double gscale, float *elbos_out, double *partial, double pscale) {
-  if (d > OR_MAXD) return NF_ERR_UNSUPPORTED;
-  if (d <= 32) return launch_ordinal_tiled<1>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
-  if (d <= 64) return launch_ordinal_tiled<2>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
-  if (d <= 128) return launch_ordinal_tiled<4>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
-  return launch_ordinal_tiled<8>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
+int nf_launch_target_ordinal_tiled(const TgtTiledArgs &a) {
+  if (a.d > OR_MAXD) return NF_ERR_UNSUPPORTED;
+  return tgt_dispatch_db(a.d, [&](auto db) { return launch_ordinal_tiled<db()>(a); });
 }
 
 // elements of LDS the flat kernel takes at (d, p)
@@ -499,27 +451,16 @@ static size_t ordinal_flat_lds(int d, int p) {
 }
 
 template <class T>
-static int launch_ordinal_flat(nf_ctx *ctx, const nf_target *t, int d, long N, const void *y, const void *logq, const void *ladj,
-                               void *logp_out, void *grad_out, double gscale, void *elbos_out, double *partial, double pscale) {
-  const int C = (int)t->s1;
-  const size_t lds = ordinal_flat_lds(d, d - (C - 1)) * sizeof(T);
-  static AttrOnce attr_once;
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    NF_HIP(hipFuncSetAttribute((const void *)k_target_ordinal<T>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)(ordinal_flat_lds(OR_MAXD, OR_MAXD - 1) * sizeof(T))));  // the most any served target takes
-    return NF_OK;
-  }));
+static int launch_ordinal_flat(const TgtFlatArgs &a) {
+  const int C = (int)a.t->s1;
+  nf_ctx *ctx = a.ctx;
+  NF_TRY(tgt_lds_once<k_target_ordinal<T>>(ctx, ordinal_flat_lds(OR_MAXD, OR_MAXD - 1) * sizeof(T)));  // the most any served target takes
   ProfScope ps(ctx, "target_ordinal");
-  const long nb = (N + ORF_SPB - 1) / ORF_SPB;
-  hipLaunchKernelGGL((k_target_ordinal<T>), dim3((unsigned)nb), dim3(OR_BLOCK), lds, ctx->stream, d, C, (int)t->s0, N, (const T *)y,
-                     (const T *)t->p0, (const T *)t->p1, (const T *)logq, (const T *)ladj, (T *)logp_out, (T *)grad_out, (T)gscale,
-                     (T *)elbos_out, partial, pscale);
-  return (int)hipGetLastError();
+  return tgt_launch_flat<k_target_ordinal<T>, T>(a, ordinal_flat_lds(a.d, a.d - (C - 1)) * sizeof(T), a.d, C, (int)a.t->s0, a.N, (const T *)a.y,
+                                                 (const T *)a.t->p0, (const T *)a.t->p1);
 }
 
-int nf_launch_target_ordinal(nf_ctx *ctx, int dtype, const nf_target *t, int d, long N, const void *y, const void *logq, const void *ladj,
-                             void *logp_out, void *grad_out, double gscale, void *elbos_out, double *partial, double pscale) {
-  if (d > OR_MAXD) return NF_ERR_UNSUPPORTED;
-  return dtype == NF_DTYPE_F32 ? launch_ordinal_flat<float>(ctx, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale)
-                               : launch_ordinal_flat<double>(ctx, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
+int nf_launch_target_ordinal(const TgtFlatArgs &a) {
+  if (a.d > OR_MAXD) return NF_ERR_UNSUPPORTED;
+  return tgt_dispatch_dtype(a.dtype, [&](auto e) { return launch_ordinal_flat<decltype(e)>(a); });
 }

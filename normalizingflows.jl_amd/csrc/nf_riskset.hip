@@ -20,6 +20,7 @@
 
 #include "nf_common.h"
 #include "nf_linpred.h"
+#include "nf_target_stages.h"
 
 #define RS_BLOCK 256
 #define RS_WAVES 4
@@ -67,6 +68,9 @@ __device__ __forceinline__ T rs_link(bool startnext, T c, T cn) {
 // Interleaving the blocks over the waves (not one contiguous range per wave) is what keeps this at two GEMM 1 and one GEMM 2: the V
 // that enters a contiguous range is known only when the whole range behind it has been swept, so ranges would either run one after
 // the other or carry a second accumulator set for the part of G that is linear in the entering V.
+// Shared stages (nf_target_stages.h): tgt_stage and tgt_gemm1 (the wave's image of a row block, GEMM 1 from it), tgt_elbo_term (both
+// kernels), tgt_block_partial (the flat kernel; the tiled one keeps it in place), and the launch helpers; what else stands here in
+// place does so for nf_ordinal.hip's reason.
 template <int DB>
 struct RsGeo {
   static constexpr int YT = 32 * DB * 32;
@@ -75,31 +79,6 @@ struct RsGeo {
   __host__ __device__ static constexpr int stride(int p) { return 32 * (((p < RS_CW ? p : RS_CW) + 31) >> 5) + 1; }
   __host__ __device__ static constexpr int floats(int p, int R) { return YTP + RS_WAVES * 32 * stride(p) + R; }  // + [R / 32][32] carries
 };
-
-// rows [i0, i0 + 32) x features [f0, f0 + pc) of X -> the wave's image; zero up to the end of pc's last 32-feature block
-__device__ __forceinline__ void rs_stage(float *__restrict__ img, int S, const float *__restrict__ X, int i0, int p, int f0, int pc, int lane) {
-  const int l31 = lane & 31, hi = lane >> 5;
-  for (int cb = 0; cb * 32 < pc; ++cb) {
-    const int col = cb * 32 + l31;
-    float v[16];
-#pragma unroll
-    for (int rp = 0; rp < 16; ++rp) v[rp] = col < pc ? X[(long)(i0 + 2 * rp + hi) * p + f0 + col] : 0.f;
-#pragma unroll
-    for (int rp = 0; rp < 16; ++rp) img[(2 * rp + hi) * S + col] = v[rp];
-  }
-}
-
-// U += X_chunk Y_chunk: A from the image, B from the tile at the chunk's first feature (sYc)
-__device__ __forceinline__ f32x16 rs_gemm1(f32x16 U, const float *__restrict__ img, int S, const float *__restrict__ sYc, int pc, int l31, int hi) {
-  const int ng = (pc + 7) >> 3;  // groups of four k-steps = eight features; image columns >= pc are zero
-  const float *pa = img + l31 * S + hi;
-  const float *pb = sYc + hi * 32 + l31;
-  for (int g = 0; g < ng; ++g) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) U = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[8 * g + 2 * e], pb[(8 * g + 2 * e) * 32], U, 0, 0, 0);
-  }
-  return U;
-}
 
 // a = eta + logw of the block's rows, -inf by select where the row is dropped; the image is left holding the LAST chunk
 __device__ __forceinline__ f32x16 rs_block_a(float *__restrict__ img, int S, const float *__restrict__ X, const float *__restrict__ sY,
@@ -114,9 +93,9 @@ __device__ __forceinline__ f32x16 rs_block_a(float *__restrict__ img, int S, con
   }
   for (int ch = 0; ch < nch; ++ch) {
     const int f0 = ch * RS_CW, pc = p - f0 < RS_CW ? p - f0 : RS_CW;
-    rs_stage(img, S, X, i0, p, f0, pc, lane);
+    tgt_stage(img, S, X, i0, p, f0, pc, lane);
     wave_lds_fence();
-    U = rs_gemm1(U, img, S, sY + f0 * 32, pc, l31, hi);
+    U = tgt_gemm1(U, img, S, sY + f0 * 32, pc, l31, hi);
     if (ch + 1 < nch) wave_lds_fence();  // the next chunk overwrites the image
   }
 #pragma unroll
@@ -356,7 +335,7 @@ __global__ __launch_bounds__(RS_BLOCK, DB <= 2 ? 2 : 1) void k_target_riskset_ti
           const int f0 = ch * RS_CW, pc = p - f0 < RS_CW ? p - f0 : RS_CW;
           if (ch != nch - 1) {
             wave_lds_fence();
-            rs_stage(img, S, X, i0, p, f0, pc, lane);
+            tgt_stage(img, S, X, i0, p, f0, pc, lane);
             wave_lds_fence();
           }
 #pragma unroll
@@ -429,12 +408,9 @@ __global__ __launch_bounds__(RS_BLOCK, DB <= 2 ? 2 : 1) void k_target_riskset_ti
 #pragma unroll
     for (int w = 0; w < RS_WAVES; ++w) l += sL[w][s] + sL[w][32 + s];
     float e = rd.par[1] + tl + l - 0.5f * pw * tb;
-    if (logq) e -= logq[j];
-    if (ladj) e += ladj[j];
-    if (elbos_out) elbos_out[j] = e;
-    contrib = pscale * (double)e;
+    contrib = tgt_elbo_term(e, j, logq, ladj, elbos_out, pscale);
   }
-  if (partial) {
+  if (partial) {  // (tgt_block_partial, in place: as a call it reorders the kernel's last instructions, and the DB = 8 kernel then measured 0.08 % outside the parent's spread)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) contrib += __shfl_xor(contrib, o, 64);
     if (lane == 0) sm[wave] = contrib;
@@ -584,47 +560,28 @@ __global__ __launch_bounds__(RS_BLOCK) void k_target_riskset(int d, int R, long 
   if (valid && q == 0) {
     T e = rd.par[1] + ly + lp - (T)0.5 * pw * yy;
     if (logp_out) logp_out[j] = e;
-    if (logq) e -= logq[j];
-    if (ladj) e += ladj[j];
-    if (elbos_out) elbos_out[j] = e;
-    contrib = pscale * (double)e;
+    contrib = tgt_elbo_term(e, j, logq, ladj, elbos_out, pscale);
   }
-  if (partial) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) contrib += __shfl_xor(contrib, o, 64);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = contrib;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
-  }
+  tgt_block_partial(contrib, sm, partial);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // launchers (called by nf_launch_target / nf_launch_target_tiled after nf_target_check: s0 = R, a multiple of 32, R <= NF_RISKSET_MAXR)
 // ---------------------------------------------------------------------------------------------------------------------
 template <int DB>
-static int launch_riskset_tiled(nf_ctx *ctx, const nf_target *t, int d, long N, const float *yt, const float *logq, const float *ladj,
-                                float *gt, double gscale, float *elbos_out, double *partial, double pscale) {
-  const int R = (int)t->s0;
-  const size_t lds = (size_t)RsGeo<DB>::floats(d, R) * sizeof(float);
-  static AttrOnce attr_once;  // once per device
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    NF_HIP(hipFuncSetAttribute((const void *)k_target_riskset_tiled<DB>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)(RsGeo<DB>::floats(RsGeo<DB>::PMAX, NF_RISKSET_MAXR) * sizeof(float))));
-    return NF_OK;
-  }));
+static int launch_riskset_tiled(const TgtTiledArgs &a) {
+  using G = RsGeo<DB>;
+  const int R = (int)a.t->s0;
+  nf_ctx *ctx = a.ctx;
+  NF_TRY(tgt_lds_once<k_target_riskset_tiled<DB>>(ctx, G::floats(G::PMAX, NF_RISKSET_MAXR) * sizeof(float)));
   ProfScope ps(ctx, "target_riskset");
-  hipLaunchKernelGGL((k_target_riskset_tiled<DB>), dim3((unsigned)((N + 31) / 32)), dim3(RS_BLOCK), lds, ctx->stream, d, R, N, yt,
-                     (const float *)t->p0, (const float *)t->p1, logq, ladj, gt, (float)gscale, elbos_out, partial, pscale);
-  return (int)hipGetLastError();
+  return tgt_launch_tiled<k_target_riskset_tiled<DB>>(a, (size_t)G::floats(a.d, R) * sizeof(float), a.d, R, a.N, a.yt, (const float *)a.t->p0,
+                                                      (const float *)a.t->p1);
 }
 
-int nf_launch_target_riskset_tiled(nf_ctx *ctx, const nf_target *t, int d, long N, const float *yt, const float *logq, const float *ladj,
-                                   float *gt, double gscale, float *elbos_out, double *partial, double pscale) {
-  if (d > RS_MAXD || t->s0 > (double)NF_RISKSET_MAXR) return NF_ERR_UNSUPPORTED;
-  if (d <= 32) return launch_riskset_tiled<1>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
-  if (d <= 64) return launch_riskset_tiled<2>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
-  if (d <= 128) return launch_riskset_tiled<4>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
-  return launch_riskset_tiled<8>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
+int nf_launch_target_riskset_tiled(const TgtTiledArgs &a) {
+  if (a.d > RS_MAXD || a.t->s0 > (double)NF_RISKSET_MAXR) return NF_ERR_UNSUPPORTED;
+  return tgt_dispatch_db(a.d, [&](auto db) { return launch_riskset_tiled<db()>(a); });
 }
 
 // elements of LDS the flat kernel takes at (d, R)
@@ -633,27 +590,16 @@ static size_t riskset_flat_lds(int d, int R) {
 }
 
 template <class T>
-static int launch_riskset_flat(nf_ctx *ctx, const nf_target *t, int d, long N, const void *y, const void *logq, const void *ladj,
-                               void *logp_out, void *grad_out, double gscale, void *elbos_out, double *partial, double pscale) {
-  const int R = (int)t->s0;
-  const size_t lds = riskset_flat_lds(d, R) * sizeof(T);
-  static AttrOnce attr_once;
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    NF_HIP(hipFuncSetAttribute((const void *)k_target_riskset<T>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)(riskset_flat_lds(RS_MAXD, NF_RISKSET_MAXR) * sizeof(T))));  // the most any served target takes
-    return NF_OK;
-  }));
+static int launch_riskset_flat(const TgtFlatArgs &a) {
+  const int R = (int)a.t->s0;
+  nf_ctx *ctx = a.ctx;
+  NF_TRY(tgt_lds_once<k_target_riskset<T>>(ctx, riskset_flat_lds(RS_MAXD, NF_RISKSET_MAXR) * sizeof(T)));  // the most any served target takes
   ProfScope ps(ctx, "target_riskset");
-  const long nb = (N + RSF_SPB - 1) / RSF_SPB;
-  hipLaunchKernelGGL((k_target_riskset<T>), dim3((unsigned)nb), dim3(RS_BLOCK), lds, ctx->stream, d, R, N, (const T *)y, (const T *)t->p0,
-                     (const T *)t->p1, (const T *)logq, (const T *)ladj, (T *)logp_out, (T *)grad_out, (T)gscale, (T *)elbos_out, partial,
-                     pscale);
-  return (int)hipGetLastError();
+  return tgt_launch_flat<k_target_riskset<T>, T>(a, riskset_flat_lds(a.d, R) * sizeof(T), a.d, R, a.N, (const T *)a.y, (const T *)a.t->p0,
+                                                 (const T *)a.t->p1);
 }
 
-int nf_launch_target_riskset(nf_ctx *ctx, int dtype, const nf_target *t, int d, long N, const void *y, const void *logq, const void *ladj,
-                             void *logp_out, void *grad_out, double gscale, void *elbos_out, double *partial, double pscale) {
-  if (d > RS_MAXD || t->s0 > (double)NF_RISKSET_MAXR) return NF_ERR_UNSUPPORTED;
-  return dtype == NF_DTYPE_F32 ? launch_riskset_flat<float>(ctx, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale)
-                               : launch_riskset_flat<double>(ctx, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
+int nf_launch_target_riskset(const TgtFlatArgs &a) {
+  if (a.d > RS_MAXD || a.t->s0 > (double)NF_RISKSET_MAXR) return NF_ERR_UNSUPPORTED;
+  return tgt_dispatch_dtype(a.dtype, [&](auto e) { return launch_riskset_flat<decltype(e)>(a); });
 }

@@ -9,8 +9,12 @@
 //   k_target_softmax        flat layout, float / double, drop-in for k_target: vector pipe (Float64 flows, nf_target_logp)
 // A row of weight 0 contributes exactly 0 to the value and the gradient by SELECT (a subsampling mask may sit over a row whose
 // logits are not finite); the log-sum-exp subtracts the row maximum, so nothing overflows for finite logits; nothing is clamped.
+// Shared stages (nf_target_stages.h): tgt_stage_rows and tgt_gemm1_at (the wave's image of a row block; U_c from it and the tile at
+// feature c p), tgt_elbo_term and tgt_block_partial (the ELBO tail of both kernels), and the launch helpers; what stands here in
+// place does so for nf_ordinal.hip's reason.
 #include "nf_common.h"
 #include "nf_linpred.h"
+#include "nf_target_stages.h"
 
 // The row data, addressed inside the one buffer p0 = lab[rows] | wt[rows] | par[2]: labels as integer-valued elements,
 // par[0] the prior precision 1 / sigma^2 (0: the flat prior), par[1] the additive constant the host folded.
@@ -54,41 +58,6 @@ struct SmGeo {
   static constexpr int YTP = YT + 8 * 32;            // with the eight zero feature rows behind it
   static constexpr int FLOATS = YTP + SM_WAVES * IMG + SM_WAVES * 64;
 };
-
-// rows [i0, i0 + 32) x features [0, p) of X -> the wave's image; zero beyond the matrix, up to the end of p's last 32-feature block
-template <int DB>
-__device__ __forceinline__ void sm_stage(float *__restrict__ img, const float *__restrict__ X, int i0, int rows, int p, int lane) {
-  using G = SmGeo<DB>;
-  const int l31 = lane & 31, hi = lane >> 5;
-  for (int cb = 0; cb * 32 < p; ++cb) {  // (p <= CW)
-    const int col = cb * 32 + l31;
-    float v[16];
-#pragma unroll
-    for (int rp = 0; rp < 16; ++rp) {
-      const int i = i0 + 2 * rp + hi;
-      v[rp] = (i < rows && col < p) ? X[(long)i * p + col] : 0.f;
-    }
-#pragma unroll
-    for (int rp = 0; rp < 16; ++rp) img[(2 * rp + hi) * G::S + col] = v[rp];
-  }
-}
-
-// U_c of the wave's row block: A from the image, B from the tile at feature c p
-template <int DB>
-__device__ __forceinline__ f32x16 sm_gemm1(const float *__restrict__ img, const float *__restrict__ sY, int c, int p, int l31, int hi) {
-  using G = SmGeo<DB>;
-  f32x16 U;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) U[r] = 0.f;
-  const int ng = (p + 7) >> 3;  // groups of four k-steps = eight features; image columns >= p are zero
-  const float *pa = img + l31 * G::S + hi;
-  const float *pb = sY + (c * p + hi) * 32 + l31;
-  for (int g = 0; g < ng; ++g) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) U = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[8 * g + 2 * e], pb[(8 * g + 2 * e) * 32], U, 0, 0, 0);
-  }
-  return U;
-}
 
 template <int DB>
 __global__ __launch_bounds__(SM_BLOCK, DB <= 4 ? 2 : 1) void k_target_softmax_tiled(int d, int C, int rows, long N, const float *__restrict__ yt,
@@ -140,11 +109,11 @@ __global__ __launch_bounds__(SM_BLOCK, DB <= 4 ? 2 : 1) void k_target_softmax_ti
       lab[r] = i < rows ? rd.lab[i] : -1.f;
       wt[r] = i < rows ? rd.wt[i] : 0.f;
     }
-    sm_stage<DB>(img, X, i0, rows, p, lane);
+    tgt_stage_rows(img, G::S, X, i0, rows, p, lane);
     wave_lds_fence();
 
     // pass 1: running maximum, sum of exponentials, the label's logit
-    f32x16 m = sm_gemm1<DB>(img, sY, 0, p, l31, hi);
+    f32x16 m = tgt_gemm1_at(img, G::S, sY, 0, p, l31, hi);
     float s[16], ul[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -152,7 +121,7 @@ __global__ __launch_bounds__(SM_BLOCK, DB <= 4 ? 2 : 1) void k_target_softmax_ti
       ul[r] = m[r];  // (replaced below unless the label is 0)
     }
     for (int c = 1; c < C; ++c) {
-      const f32x16 U = sm_gemm1<DB>(img, sY, c, p, l31, hi);
+      const f32x16 U = tgt_gemm1_at(img, G::S, sY, c * p, p, l31, hi);
       const float fc = (float)c;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
@@ -172,7 +141,7 @@ __global__ __launch_bounds__(SM_BLOCK, DB <= 4 ? 2 : 1) void k_target_softmax_ti
 
     // pass 2: phi'_c in GEMM 1's accumulator registers, straight into GEMM 2
     for (int c = 0; c < C; ++c) {
-      f32x16 U = sm_gemm1<DB>(img, sY, c, p, l31, hi);
+      f32x16 U = tgt_gemm1_at(img, G::S, sY, c * p, p, l31, hi);
       const float fc = (float)c;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
@@ -245,18 +214,9 @@ __global__ __launch_bounds__(SM_BLOCK, DB <= 4 ? 2 : 1) void k_target_softmax_ti
 #pragma unroll
     for (int w = 0; w < SM_WAVES; ++w) l += sL[w * 64 + s] + sL[w * 64 + 32 + s];
     float e = rd.par[1] + l - 0.5f * pw * t;
-    if (logq) e -= logq[j];
-    if (ladj) e += ladj[j];
-    if (elbos_out) elbos_out[j] = e;
-    contrib = pscale * (double)e;
+    contrib = tgt_elbo_term(e, j, logq, ladj, elbos_out, pscale);
   }
-  if (partial) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) contrib += __shfl_xor(contrib, o, 64);
-    if (lane == 0) sm[wave] = contrib;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
-  }
+  tgt_block_partial(contrib, sm, partial);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -372,76 +332,45 @@ __global__ __launch_bounds__(SM_BLOCK) void k_target_softmax(int d, int C, int r
   if (valid && q == 0) {
     T e = rd.par[1] + lp - (T)0.5 * pw * yy;
     if (logp_out) logp_out[j] = e;
-    if (logq) e -= logq[j];
-    if (ladj) e += ladj[j];
-    if (elbos_out) elbos_out[j] = e;
-    contrib = pscale * (double)e;
+    contrib = tgt_elbo_term(e, j, logq, ladj, elbos_out, pscale);
   }
-  if (partial) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) contrib += __shfl_xor(contrib, o, 64);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = contrib;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
-  }
+  tgt_block_partial(contrib, sm, partial);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // launchers (called by nf_launch_target / nf_launch_target_tiled after nf_target_check: s0 = rows, s1 = C, d % C == 0)
 // ---------------------------------------------------------------------------------------------------------------------
 template <int DB>
-static int launch_softmax_tiled(nf_ctx *ctx, const nf_target *t, int d, long N, const float *yt, const float *logq,
-                                const float *ladj, float *gt, double gscale, float *elbos_out, double *partial, double pscale) {
+static int launch_softmax_tiled(const TgtTiledArgs &a) {
   const size_t lds = (size_t)SmGeo<DB>::FLOATS * sizeof(float);
-  static AttrOnce attr_once;  // once per device
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    NF_HIP(hipFuncSetAttribute((const void *)k_target_softmax_tiled<DB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return NF_OK;
-  }));
+  nf_ctx *ctx = a.ctx;
+  NF_TRY(tgt_lds_once<k_target_softmax_tiled<DB>>(ctx, lds));
   ProfScope ps(ctx, "target_softmax");
-  hipLaunchKernelGGL((k_target_softmax_tiled<DB>), dim3((unsigned)((N + 31) / 32)), dim3(SM_BLOCK), lds, ctx->stream, d, (int)t->s1,
-                     (int)t->s0, N, yt, (const float *)t->p0, (const float *)t->p1, logq, ladj, gt, (float)gscale, elbos_out, partial,
-                     pscale);
-  return (int)hipGetLastError();
+  return tgt_launch_tiled<k_target_softmax_tiled<DB>>(a, lds, a.d, (int)a.t->s1, (int)a.t->s0, a.N, a.yt, (const float *)a.t->p0,
+                                                      (const float *)a.t->p1);
 }
 
-int nf_launch_target_softmax_tiled(nf_ctx *ctx, const nf_target *t, int d, long N, const float *yt, const float *logq,
-                                   const float *ladj, float *gt, double gscale, float *elbos_out, double *partial, double pscale) {
-  if (d > SMF_MAXD) return NF_ERR_UNSUPPORTED;
-  if (d <= 32) return launch_softmax_tiled<1>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
-  if (d <= 64) return launch_softmax_tiled<2>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
-  if (d <= 128) return launch_softmax_tiled<4>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
-  return launch_softmax_tiled<8>(ctx, t, d, N, yt, logq, ladj, gt, gscale, elbos_out, partial, pscale);
+int nf_launch_target_softmax_tiled(const TgtTiledArgs &a) {
+  if (a.d > SMF_MAXD) return NF_ERR_UNSUPPORTED;
+  return tgt_dispatch_db(a.d, [&](auto db) { return launch_softmax_tiled<db()>(a); });
 }
 
 // floats / doubles of LDS the flat kernel takes at (d, C)
 static size_t softmax_flat_lds(int d, int C) { return (size_t)(SMF_SPB * (d + 1) + SMF_RB * (d / C + 1) + SMF_SPB * (SMF_RB * C + 1)); }
 
 template <class T>
-static int launch_softmax_flat(nf_ctx *ctx, const nf_target *t, int d, long N, const void *y, const void *logq, const void *ladj,
-                               void *logp_out, void *grad_out, double gscale, void *elbos_out, double *partial, double pscale) {
-  const int C = (int)t->s1;
-  const size_t lds = softmax_flat_lds(d, C) * sizeof(T);
-  static AttrOnce attr_once;
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    // the most any checked target takes: d = 256, with the widest image (C = 2) and the widest phi' block (C = 16) both counted
-    const size_t most = (size_t)(SMF_SPB * (SMF_MAXD + 1) + SMF_RB * (SMF_MAXD / 2 + 1) + SMF_SPB * (SMF_RB * SMF_MAXC + 1)) * sizeof(T);
-    NF_HIP(hipFuncSetAttribute((const void *)k_target_softmax<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)most));
-    return NF_OK;
-  }));
+static int launch_softmax_flat(const TgtFlatArgs &a) {
+  const int C = (int)a.t->s1;
+  // the most any checked target takes: d = 256, with the widest image (C = 2) and the widest phi' block (C = 16) both counted
+  const size_t most = (size_t)(SMF_SPB * (SMF_MAXD + 1) + SMF_RB * (SMF_MAXD / 2 + 1) + SMF_SPB * (SMF_RB * SMF_MAXC + 1)) * sizeof(T);
+  nf_ctx *ctx = a.ctx;
+  NF_TRY(tgt_lds_once<k_target_softmax<T>>(ctx, most));
   ProfScope ps(ctx, "target_softmax");
-  const long nb = (N + SMF_SPB - 1) / SMF_SPB;
-  hipLaunchKernelGGL((k_target_softmax<T>), dim3((unsigned)nb), dim3(SM_BLOCK), lds, ctx->stream, d, C, (int)t->s0, N, (const T *)y,
-                     (const T *)t->p0, (const T *)t->p1, (const T *)logq, (const T *)ladj, (T *)logp_out, (T *)grad_out, (T)gscale,
-                     (T *)elbos_out, partial, pscale);
-  return (int)hipGetLastError();
+  return tgt_launch_flat<k_target_softmax<T>, T>(a, softmax_flat_lds(a.d, C) * sizeof(T), a.d, C, (int)a.t->s0, a.N, (const T *)a.y,
+                                                 (const T *)a.t->p0, (const T *)a.t->p1);
 }
 
-int nf_launch_target_softmax(nf_ctx *ctx, int dtype, const nf_target *t, int d, long N, const void *y, const void *logq,
-                             const void *ladj, void *logp_out, void *grad_out, double gscale, void *elbos_out, double *partial,
-                             double pscale) {
-  if (d > SMF_MAXD) return NF_ERR_UNSUPPORTED;
-  if (dtype == NF_DTYPE_F32)
-    return launch_softmax_flat<float>(ctx, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
-  return launch_softmax_flat<double>(ctx, t, d, N, y, logq, ladj, logp_out, grad_out, gscale, elbos_out, partial, pscale);
+int nf_launch_target_softmax(const TgtFlatArgs &a) {
+  if (a.d > SMF_MAXD) return NF_ERR_UNSUPPORTED;
+  return tgt_dispatch_dtype(a.dtype, [&](auto e) { return launch_softmax_flat<decltype(e)>(a); });
 }

@@ -440,7 +440,7 @@ static int launch_bnn_tiled(const TgtTiledArgs &a) {
   using G = BnGeo<DB>;
   const int H = (int)a.t->s1, p = (a.d - 1) / H - 1;
   nf_ctx *ctx = a.ctx;
-  NF_TRY((tgt_lds_once<k_target_bnn_tiled<PHI, DB>>(ctx, G::floats(G::PMAX) * sizeof(float))));
+  NF_TRY((nf_lds_once<k_target_bnn_tiled<PHI, DB>>(ctx, G::floats(G::PMAX) * sizeof(float))));
   ProfScope ps(ctx, "target_bnn");
   return tgt_launch_tiled<k_target_bnn_tiled<PHI, DB>>(a, (size_t)G::floats(p) * sizeof(float), a.d, H, (int)a.t->s0, a.N, a.yt,
                                                        (const float *)a.t->p0, (const float *)a.t->p1);
@@ -462,7 +462,7 @@ static int launch_bnn_flat(const TgtFlatArgs &a) {
   // the most any served target takes: d = 256, with the widest image (p = 128) and the widest [row][unit] block (H = 16) both counted
   const size_t most = (size_t)(BNF_SPB * (BN_MAXD + 1) + BNF_RB * (BN_MAXP + 1) + BNF_SPB * (BNF_RB * BN_MAXH + 1)) * sizeof(T);
   nf_ctx *ctx = a.ctx;
-  NF_TRY((tgt_lds_once<k_target_bnn<PHI, T>>(ctx, most)));
+  NF_TRY((nf_lds_once<k_target_bnn<PHI, T>>(ctx, most)));
   ProfScope ps(ctx, "target_bnn");
   return tgt_launch_flat<k_target_bnn<PHI, T>, T>(a, bnn_flat_lds(a.d, H) * sizeof(T), a.d, H, (int)a.t->s0, a.N, (const T *)a.y,
                                                   (const T *)a.t->p0, (const T *)a.t->p1);

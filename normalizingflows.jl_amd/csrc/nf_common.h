@@ -192,6 +192,26 @@ struct AttrOnce {
   }
 };
 
+// the common case in one line: hipFuncSetAttribute(KERN, MaxDynamicSharedMemorySize = most bytes) once per (kernel, device).
+// `most` is the same on every call for a given KERN: the first call on a device is the one that counts.
+template <auto KERN>
+int nf_lds_once(nf_ctx *ctx, size_t most) {
+  static AttrOnce attr_once;
+  return attr_once.run(ctx->device, [&]() -> int {
+    NF_HIP(hipFuncSetAttribute((const void *)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, (int)most));
+    return NF_OK;
+  });
+}
+
+// In-kernel clock stamp of the NF_KERNEL_TRACE builds (tools/trace_*.py): slot `slot` of the wave's trace pointer, null in
+// every wave but the traced one.  The scheduling barrier pins the stamp between the stages it separates -- which is what a trace
+// build pays.  Plain builds: nothing (the pointer may not even be declared).
+#ifdef NF_KERNEL_TRACE
+#define NF_STAMP(ptr, slot) do { if (ptr) { __builtin_amdgcn_sched_barrier(0); (ptr)[slot] = clock64(); } } while (0)
+#else
+#define NF_STAMP(ptr, slot) do { } while (0)
+#endif
+
 // natural log through v_log_f32 (log2, 1 ulp) and one multiply.  hipcc expands __logf into the denormal-safe,
 // extended-precision sequence of logf (14 instructions); every argument on this path is a normal positive number.
 __device__ __forceinline__ float nf_log(float x) { return __builtin_amdgcn_logf(x) * 0.6931471805599453f; }

@@ -14,12 +14,11 @@
 #include <type_traits>
 
 #include "nf_common.h"
+#include "nf_launchers.h"
 #include "nf_mfma.h"
 #include "nf_pack.h"
 #include "nf_philox.h"
 #include "nf_target_epilogue.h"
-
-int nf_target_check(const nf_target *t, int d);  // nf_elementwise.hip
 
 struct CouplingArgs {
   const float *theta;
@@ -76,24 +75,19 @@ struct NoBetween {
 };
 // B6: img_s / img_t are B6 images; `between` runs between the two nets (the B6 chain kernel's image rotation: a workgroup
 // barrier and the request for the image after next)
-#ifdef NF_KERNEL_TRACE
-#define NF_CS_STAMP(tr, slot) do { if (tr) { __builtin_amdgcn_sched_barrier(0); (tr)[slot] = clock64(); } } while (0)
-#else
-#define NF_CS_STAMP(tr, slot) do { } while (0)
-#endif
 template <class G, bool INVERSE, bool B6 = false, class BT = NoBetween, bool PIPE = true>
 __device__ __forceinline__ float coupling_step(const float *__restrict__ img_s, const float *__restrict__ img_t,
                                                f32x16 (&x1)[G::CB], const f32x16 (&xb)[G::MB], int l31, int hi, BT between = BT(),
                                                long long *tr = nullptr) {
   f32x16 S[G::CB], T[G::CB];
   if constexpr (B6) {
-    NF_CS_STAMP(tr, 0);  // tools/trace_chain.py (NOSTASH=1): after the phase barrier + the request for the image after next
+    NF_STAMP(tr, 0);  // tools/trace_chain.py (NOSTASH=1): after the phase barrier + the request for the image after next
     net_forward_b6<G, PIPE>(img_s, xb, S, l31, hi);
-    NF_CS_STAMP(tr, 1);
+    NF_STAMP(tr, 1);
     between();
-    NF_CS_STAMP(tr, 2);
+    NF_STAMP(tr, 2);
     net_forward_b6<G, PIPE>(img_t, xb, T, l31, hi);
-    NF_CS_STAMP(tr, 3);
+    NF_STAMP(tr, 3);
   } else {
   {
     f32x16 a1[G::H1B], a2[G::H2B];
@@ -389,11 +383,6 @@ __device__ __forceinline__ void net_forward_stash(const float *__restrict__ img,
   nf_buffer_store_b128(mk, st.rs, (hi * 32 + l31) * 16, (nbase + SG::MSK) * 4);
 }
 
-#ifdef NF_KERNEL_TRACE
-#define NF_CH_STAMP(tr, slot) do { if (tr) { __builtin_amdgcn_sched_barrier(0); (tr)[slot] = clock64(); } } while (0)
-#else
-#define NF_CH_STAMP(tr, slot) do { } while (0)
-#endif
 // forward coupling of the training step: as coupling_step<G, false>, leaving the reverse pass's operands behind
 // INVERSE (forward-KL training: the chain runs data -> base): w1 = (v1 - t) exp(-s); the UV slot then holds w1, which is
 // what the reverse pass of the inverse coupling needs next to s (bwd_tile's INVD algebra)
@@ -405,10 +394,10 @@ __device__ __forceinline__ float coupling_step_stash(const float *__restrict__ i
   static_assert(G::H1B <= 2 && G::H2B <= 2, "mask words");
   f32x16 S[G::CB], T[G::CB];
   net_forward_stash<G, true, SLIM, B6>(img_s, xb, S, l31, hi, st, SG::NET0);
-  NF_CH_STAMP(tr, 1);
+  NF_STAMP(tr, 1);
   between();
   net_forward_stash<G, false, SLIM, B6>(img_t, xb, T, l31, hi, st, SG::NET0 + SG::NETSZ);
-  NF_CH_STAMP(tr, 2);
+  NF_STAMP(tr, 2);
   float lsum = 0.f;
 #pragma unroll
   for (int b = 0; b < G::CB; ++b)
@@ -519,7 +508,7 @@ __device__ __forceinline__ void affine_chain_body(ChainArgs a, float *xt, float 
   constexpr int TP = 64 * G::CB;  // padded feature count (E and O halves)
   float *tmu = lds + (B6 ? 3 * B6F : 2 * IMG2), *tiv = tmu + TP, *tc0 = tiv + TP;
   double *wsum = reinterpret_cast<double *>(tc0 + 2);  // [NW] per-wave partial sums (8-byte aligned: TP even)
-  if (FUSED && !FKL && !TGT) {
+  if (FUSED && !FKL && !TGT) {  // as in rqs_chain_body, in place: as a shared call it changes the fused k_rqs_chain forms
     for (int i = tid; i < TP; i += 64 * NW) {
       tmu[i] = i < a.d ? fa.mu[i] : 0.f;
       tiv[i] = i < a.d ? 1.f / fa.var[i] : 0.f;
@@ -543,7 +532,7 @@ __device__ __forceinline__ void affine_chain_body(ChainArgs a, float *xt, float 
     const TileIO io = make_tile_io(xt, tl, a.d, l31, hi);
     f32x16 E[G::CB], O[G::MB];
     float zz = 0.f;  // FUSED: this lane's share of ||x||^2
-    if constexpr (FKL) {
+    if constexpr (FKL) {  // (chain_load_ys and chain_draw_base would be these two arms; as calls they change the fused kernels)
       // ys[j * d + f] through one descriptor per tile that spans exactly the tile's samples: lanes of padding samples read 0 from
       // the hardware, features >= d (which would be the next sample's) are zeroed here -- the values the layout conversion and
       // tile_load give the plain chain.  The whole byte offset is per lane (voffset), so every access is range-checked.
@@ -563,15 +552,7 @@ __device__ __forceinline__ void affine_chain_body(ChainArgs a, float *xt, float 
           O[b][r] = valid && f + 1 < a.d ? o : 0.f;
         }
     } else if (!FUSED) {
-#pragma unroll
-      for (int b = 0; b < G::CB; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float e = tile_load(io, tile_soff(b, r, 0));  // features >= d read as 0
-          const float o = tile_load(io, tile_soff(b, r, 1));
-          E[b][r] = valid ? e : 0.f;
-          O[b][r] = valid ? o : 0.f;
-        }
+      chain_load_tile(E, O, io, valid);
     } else {
       // registers (b, 4q..4q+3) of E and O are features base..base+7, base = 64b + 16q + 8hi:
       // Philox groups base/4 (-> E0 O0 E1 O1) and base/4 + 1 (-> E2 O2 E3 O3)
@@ -647,8 +628,8 @@ __device__ __forceinline__ void affine_chain_body(ChainArgs a, float *xt, float 
 #endif
             if (INVERSE ? (half == 1) : (half == 0)) ls = coupling_step_stash<G, INVERSE, SLIM, true>(img_s, img_t, O, E, l31, hi, st, tr, between);
             else ls = coupling_step_stash<G, INVERSE, SLIM, true>(img_s, img_t, E, O, l31, hi, st, tr, between);
-            NF_CH_STAMP(tr, 3);
-            NF_CH_STAMP(tr, 4);
+            NF_STAMP(tr, 3);
+            NF_STAMP(tr, 4);
           } else {
 #ifdef NF_KERNEL_TRACE  // stamps [32 + wave/4 * 64 + position * 5 + 0..4] of the second tile group (the first one's images arrive cold)
             long long *tr = (fa.trace && blockIdx.x == 0 && (tid & 255) == 0 && pos < 8 && grp != (long)blockIdx.x && grp == (long)blockIdx.x + gridDim.x)
@@ -658,7 +639,7 @@ __device__ __forceinline__ void affine_chain_body(ChainArgs a, float *xt, float 
 #endif
             if (INVERSE ? (half == 1) : (half == 0)) ls = coupling_step<G, INVERSE, true, decltype(between), NW == 8>(img_s, img_t, O, E, l31, hi, between, tr);
             else ls = coupling_step<G, INVERSE, true, decltype(between), NW == 8>(img_s, img_t, E, O, l31, hi, between, tr);
-            NF_CS_STAMP(tr, 4);
+            NF_STAMP(tr, 4);
           }
           lsum += fold_ls(ls);
           cur_slot = slot_t == 2 ? 0 : slot_t + 1;
@@ -693,10 +674,10 @@ __device__ __forceinline__ void affine_chain_body(ChainArgs a, float *xt, float 
 #endif
           if (INVERSE ? (half == 1) : (half == 0)) ls = coupling_step_stash<G, INVERSE, SLIM>(img_s, img_t, O, E, l31, hi, st, tr);
           else ls = coupling_step_stash<G, INVERSE, SLIM>(img_s, img_t, E, O, l31, hi, st, tr);
-          NF_CH_STAMP(tr, 3);
+          NF_STAMP(tr, 3);
           lsum += fold_ls(ls);
           __syncthreads();
-          NF_CH_STAMP(tr, 4);
+          NF_STAMP(tr, 4);
           buf ^= 1;
           continue;
         } else if (INVERSE ? (half == 1) : (half == 0)) {
@@ -854,18 +835,6 @@ struct BwdAcc {
   float b1[G::H1B], b2[G::H2B], b3[G::CB];
 };
 
-template <int IB, int OB>
-__device__ __forceinline__ void zero_acc(f32x16 (&a)[IB][OB], float (&b)[OB]) {
-#pragma unroll
-  for (int i = 0; i < IB; ++i)
-#pragma unroll
-    for (int o = 0; o < OB; ++o)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) a[i][o][r] = 0.f;
-#pragma unroll
-  for (int o = 0; o < OB; ++o) b[o] = 0.f;
-}
-
 // fold one wave's accumulators into the LDS image (layout of the weight image)
 template <int IB, int OB>
 __device__ __forceinline__ void fold_acc(float *__restrict__ w, float *__restrict__ b, const f32x16 (&a)[IB][OB],
@@ -899,20 +868,6 @@ __device__ __forceinline__ void unstage_dense(const float *__restrict__ img, int
   }
 }
 
-#ifdef NF_KERNEL_TRACE
-#define NF_TS_STAMP(slot)                                                  \
-  do {                                                                     \
-    if (tr) { __builtin_amdgcn_sched_barrier(0); tr[slot] = clock64(); }   \
-  } while (0)
-#define NF_TSB(slot)                                                        \
-  do {                                                                      \
-    if (trb) { __builtin_amdgcn_sched_barrier(0); trb[slot] = clock64(); }  \
-  } while (0)
-#else
-#define NF_TS_STAMP(slot) do { (void)tr; } while (0)
-#define NF_TSB(slot) do { } while (0)
-#endif
-
 // Slope masks of the hidden pre-activations (bit r set <=> NOT z[r] > 0, i.e. the leaky-ReLU slope is
 // 0.01, as in the oracle's ifelse(x > 0, x, 0.01x)): all the reverse pass needs of a1/a2 besides their
 // LDS copies, so the activations themselves can die early.  leakyrelu keeps the sign and the zero, so
@@ -921,11 +876,6 @@ __device__ __forceinline__ void unstage_dense(const float *__restrict__ img, int
 // rows also do, with a zero cotangent).  Built by nf_sign_mask16 (nf_mfma.h), one subtraction and one
 // v_alignbit per element.  (Note for maintainers: __builtin_bit_cast applied directly to a
 // vector-element expression such as v[b][r] reads element 0 under hipcc 7.2 -- copy to a scalar first.)
-template <int NB>
-__device__ __forceinline__ void sign_masks(const f32x16 (&v)[NB], unsigned (&m)[NB]) {
-#pragma unroll
-  for (int b = 0; b < NB; ++b) m[b] = nf_sign_mask16(v[b]);
-}
 __device__ __forceinline__ float lrelu_slope(unsigned mask, int r) { return nf_mask_slope(mask, r); }
 template <int NB>
 __device__ __forceinline__ void apply_lrelu_grad(f32x16 (&d)[NB], const unsigned (&m)[NB]) {
@@ -957,7 +907,7 @@ __device__ __forceinline__ void bwd_tile(const CouplingArgs &a, const float *__r
                                          const float *__restrict__ lbar, float lbar_const, long tile, int l31, int hi,
                                          long long *tr) {
   using L = BwdLds<G>;
-  NF_TS_STAMP(0);
+  NF_STAMP(tr, 0);
   const long j = tile * NF_TILE + l31;
   // FULL: N is a multiple of the tile, so no sample mask is needed (feature bounds are handled by
   // the buffer descriptors either way).
@@ -983,7 +933,7 @@ __device__ __forceinline__ void bwd_tile(const CouplingArgs &a, const float *__r
         const float v = tile_load(yio, tile_soff(b, r, par_c));  // features >= d read as 0
         xb[b][r] = valid ? v : 0.f;
       }
-    NF_TS_STAMP(1);
+    NF_STAMP(tr, 1);
     f32x16 a1[G::H1B];
     dense_fwd<G::MB, G::H1B>(img + G::W1, img + G::B1, xb, a1, l31, hi,
                              [&](int e) { scratch_put<G::MB>(sc + L::OFF_X, xb, e, l31, hi); });
@@ -1009,7 +959,7 @@ __device__ __forceinline__ void bwd_tile(const CouplingArgs &a, const float *__r
     dense_fwd<G::H2B, G::CB>(img + G::W3, img + G::B3, a2, d3, l31, hi,
                              [&](int e) { scratch_put<G::H2B>(sc + L::OFF_A2, a2, e, l31, hi); });
   }
-  NF_TS_STAMP(2);
+  NF_STAMP(tr, 2);
 
   const float lb = valid ? (lbar ? lbar[FULL ? j : (j < a.N ? j : 0)] : lbar_const) : 0.f;
 #pragma unroll
@@ -1039,27 +989,27 @@ __device__ __forceinline__ void bwd_tile(const CouplingArgs &a, const float *__r
         d3[b][r] = ok ? (gv * yv + lb) * (1.f - s * s) : 0.f;           // S-bar through tanh
       }
     }
-  NF_TS_STAMP(3);
+  NF_STAMP(tr, 3);
 
   // ---- layer 3
   f32x16 d2[G::H2B];
   dense_bwd_x<G::H2B, G::CB>(img + G::W3, d3, d2, l31, hi, [&](int e) { scratch_put<G::CB>(sd, d3, e, l31, hi); });
-  NF_TS_STAMP(4);
+  NF_STAMP(tr, 4);
   wave_lds_fence();
   dw_accumulate<G::H2B, G::CB>(sc + L::OFF_A2, sd, acc.w3, acc.b3, l31, hi, [&](int e) {
     if (e < G::H2B * 16) d2[e >> 4][e & 15] *= lrelu_slope(m2[e >> 4], e & 15);
   });
-  NF_TS_STAMP(5);
+  NF_STAMP(tr, 5);
   wave_lds_fence();
   // ---- layer 2
   f32x16 d1[G::H1B];
   dense_bwd_x<G::H1B, G::H2B>(img + G::W2, d2, d1, l31, hi, [&](int e) { scratch_put<G::H2B>(sd, d2, e, l31, hi); });
-  NF_TS_STAMP(6);
+  NF_STAMP(tr, 6);
   wave_lds_fence();
   dw_accumulate<G::H1B, G::H2B>(sc + L::OFF_A1, sd, acc.w2, acc.b2, l31, hi, [&](int e) {
     if (e < G::H1B * 16) d1[e >> 4][e & 15] *= lrelu_slope(m1[e >> 4], e & 15);
   });
-  NF_TS_STAMP(7);
+  NF_STAMP(tr, 7);
   wave_lds_fence();
   // ---- layer 1: x2bar accumulates ybar2 + W1t^T d1t (phase T) + W1s^T d1s (phase S)
   f32x16 g2[G::MB], gold[G::MB];
@@ -1068,14 +1018,14 @@ __device__ __forceinline__ void bwd_tile(const CouplingArgs &a, const float *__r
 #pragma unroll
     for (int r = 0; r < 16; ++r) gold[b][r] = tile_load(gio, tile_soff(b, r, par_c));
   dense_bwd_x<G::MB, G::H1B>(img + G::W1, d1, g2, l31, hi, [&](int e) { scratch_put<G::H1B>(sd, d1, e, l31, hi); });
-  NF_TS_STAMP(8);
+  NF_STAMP(tr, 8);
   wave_lds_fence();
   dw_accumulate<G::MB, G::H1B>(sc + L::OFF_X, sd, acc.w1, acc.b1, l31, hi, [&](int e) {
     if (e < G::MB * 16) tile_store(gio, tile_soff(e >> 4, e & 15, par_c), gold[e >> 4][e & 15] + g2[e >> 4][e & 15]);
   });
-  NF_TS_STAMP(9);
+  NF_STAMP(tr, 9);
   wave_lds_fence();
-  NF_TS_STAMP(10);
+  NF_STAMP(tr, 10);
 }
 
 // reverse pass of ONE coupling by this workgroup (both phases, fold, slab write)
@@ -1100,9 +1050,9 @@ __device__ __forceinline__ void bwd_coupling(const CouplingArgs &a, float *__res
     __syncthreads();
     if (tr0) tr0[1 + phase * 3] = clock64();
     BwdAcc<G> acc;
-    zero_acc(acc.w1, acc.b1);
-    zero_acc(acc.w2, acc.b2);
-    zero_acc(acc.w3, acc.b3);
+    net_zero_acc(acc.w1, acc.b1);
+    net_zero_acc(acc.w2, acc.b2);
+    net_zero_acc(acc.w3, acc.b3);
 #pragma unroll 1
     for (long tile = (long)blockIdx.x * 4 + wave; tile < ntiles; tile += (long)gridDim.x * 4) {
       if (!is_s)
@@ -1404,7 +1354,7 @@ __device__ __forceinline__ void bwd_tile_stashed(const CouplingArgs &a, const fl
                                                  BwdAcc<G> &acc, StashFirst<G> &f, float *stash, int k, int ncoup,
                                                  float *__restrict__ ybar, const float *__restrict__ lbar, float lbar_const,
                                                  long tile, long next_tile, int l31, int hi, long long *tr = nullptr) {
-  NF_TS_STAMP(0);
+  NF_STAMP(tr, 0);
   using SG = StashGeo<G>;
   const long j = tile * NF_TILE + l31;
   const bool valid = FULL ? true : j < a.N;
@@ -1424,7 +1374,7 @@ __device__ __forceinline__ void bwd_tile_stashed(const CouplingArgs &a, const fl
   float a2t[G::H2B][16];
   stash_get_T<G::H2B>(st, nbase + SG::A2, vT, a2t);
 
-  NF_TS_STAMP(1);
+  NF_STAMP(tr, 1);
   const float lb = valid ? (lbar ? lbar[FULL ? j : (j < a.N ? j : 0)] : lbar_const) : 0.f;
   f32x16 d3[G::CB];
 #pragma unroll
@@ -1449,7 +1399,7 @@ __device__ __forceinline__ void bwd_tile_stashed(const CouplingArgs &a, const fl
   const unsigned mk0 = mk[0], mk1 = mk[1], mk2 = mk[2], mk3 = mk[3];
   const unsigned m1[2] = {mk0, mk1}, m2[2] = {mk2, mk3};
 
-  NF_TS_STAMP(2);
+  NF_STAMP(tr, 2);
   // ---- layer 3
   f32x16 d2[G::H2B];
   const nf_u32x4 *wt = reinterpret_cast<const nf_u32x4 *>(img);  // SB6: the staged image is the net's B6T image
@@ -1457,7 +1407,7 @@ __device__ __forceinline__ void bwd_tile_stashed(const CouplingArgs &a, const fl
   else dense_bwd_x<G::H2B, G::CB>(img + G::W3, d3, d2, l31, hi, [&](int e) { scratch_put<G::CB>(sd, d3, e, l31, hi); });
   float a1t[G::H1B][16];
   stash_get_T<G::H1B>(st, nbase + SG::A1, vT, a1t);
-  NF_TS_STAMP(3);
+  NF_STAMP(tr, 3);
   wave_lds_fence();
   auto sj3 = [&](int e) {
     if (e < G::H2B * 16) d2[e >> 4][e & 15] *= lrelu_slope(m2[e >> 4], e & 15);
@@ -1468,7 +1418,7 @@ __device__ __forceinline__ void bwd_tile_stashed(const CouplingArgs &a, const fl
     dw_accumulate_reg_b6<G::H2B, G::CB>(a2s, sd, acc.w3, acc.b3, l31, hi, sj3);
   } else
     dw_accumulate_reg<G::H2B, G::CB>(a2t, sd, acc.w3, acc.b3, l31, hi, sj3);
-  NF_TS_STAMP(4);
+  NF_STAMP(tr, 4);
   wave_lds_fence();
   // ---- layer 2
   f32x16 d1[G::H1B];
@@ -1476,7 +1426,7 @@ __device__ __forceinline__ void bwd_tile_stashed(const CouplingArgs &a, const fl
   else dense_bwd_x<G::H1B, G::H2B>(img + G::W2, d2, d1, l31, hi, [&](int e) { scratch_put<G::H2B>(sd, d2, e, l31, hi); });
   float x2t[G::MB][16];
   stash_get_T<G::MB>(st, SG::XT, vT, x2t);
-  NF_TS_STAMP(5);
+  NF_STAMP(tr, 5);
   wave_lds_fence();
   auto sj2 = [&](int e) {
     if (e < G::H1B * 16) d1[e >> 4][e & 15] *= lrelu_slope(m1[e >> 4], e & 15);
@@ -1487,7 +1437,7 @@ __device__ __forceinline__ void bwd_tile_stashed(const CouplingArgs &a, const fl
     dw_accumulate_reg_b6<G::H1B, G::H2B>(a1s, sd, acc.w2, acc.b2, l31, hi, sj2);
   } else
     dw_accumulate_reg<G::H1B, G::H2B>(a1t, sd, acc.w2, acc.b2, l31, hi, sj2);
-  NF_TS_STAMP(6);
+  NF_STAMP(tr, 6);
   wave_lds_fence();
   // ---- layer 1: x2bar accumulates ybar2 + W1t^T d1t (phase T) + W1s^T d1s (phase S)
   f32x16 g2[G::MB], gold[G::MB];
@@ -1498,7 +1448,7 @@ __device__ __forceinline__ void bwd_tile_stashed(const CouplingArgs &a, const fl
   if (PHASE_S && next_tile >= 0) stash_issue_first<G>(f, stash, k, ncoup, next_tile, l31, hi);
   if constexpr (SB6) dense_bwd_x_b6<G::MB, G::H1B>(wt + B6TGeo<G>::T1, d1, g2, l31, hi, [&](int e) { scratch_put<G::H1B>(sd, d1, e, l31, hi); });
   else dense_bwd_x<G::MB, G::H1B>(img + G::W1, d1, g2, l31, hi, [&](int e) { scratch_put<G::H1B>(sd, d1, e, l31, hi); });
-  NF_TS_STAMP(7);
+  NF_STAMP(tr, 7);
   wave_lds_fence();
   auto sj1 = [&](int e) {
     if (e < G::MB * 16) tile_store(gio, tile_soff(e >> 4, e & 15, par_c), gold[e >> 4][e & 15] + g2[e >> 4][e & 15]);
@@ -1510,7 +1460,7 @@ __device__ __forceinline__ void bwd_tile_stashed(const CouplingArgs &a, const fl
   } else
     dw_accumulate_reg<G::MB, G::H1B>(x2t, sd, acc.w1, acc.b1, l31, hi, sj1);
   wave_lds_fence();
-  NF_TS_STAMP(8);
+  NF_STAMP(tr, 8);
 }
 
 template <class G, bool FULL, bool INVD = false, bool SB6 = false>
@@ -1533,9 +1483,6 @@ __global__ __launch_bounds__(256, 1) void k_affine_bwd_stashed(BwdAllArgs aa, fl
 #ifdef NF_KERNEL_TRACE
   long long *tr0 = (aa.trace && blockIdx.x == 0 && tid == 0) ? aa.trace : nullptr;
   if (tr0) tr0[0] = clock64();
-#define NF_ST_STAMP(slot) do { if (tr0 && step == 0) { __builtin_amdgcn_sched_barrier(0); tr0[slot] = clock64(); } } while (0)
-#else
-#define NF_ST_STAMP(slot) do { } while (0)
 #endif
   if (INVD && tile0 < ntiles) stash_issue_first<G>(f, stash, aa.ncoup - 1, aa.ncoup, tile0, l31, hi);  // S runs first
 #pragma unroll 1
@@ -1561,10 +1508,10 @@ __global__ __launch_bounds__(256, 1) void k_affine_bwd_stashed(BwdAllArgs aa, fl
         stage_packed<G::SIZE, 256>(img, is_s ? a.img_s : a.img_t, tid);
       __syncthreads();
       BwdAcc<G> acc;
-      zero_acc(acc.w1, acc.b1);
-      zero_acc(acc.w2, acc.b2);
-      zero_acc(acc.w3, acc.b3);
-      NF_ST_STAMP(1 + phase * 4);
+      net_zero_acc(acc.w1, acc.b1);
+      net_zero_acc(acc.w2, acc.b2);
+      net_zero_acc(acc.w3, acc.b3);
+      NF_STAMP(step == 0 ? tr0 : nullptr, 1 + phase * 4);
 #pragma unroll 1
       for (long tile = tile0; tile < ntiles; tile += tstride) {
         const long nt = tile + tstride < ntiles ? tile + tstride : -1;
@@ -1577,9 +1524,9 @@ __global__ __launch_bounds__(256, 1) void k_affine_bwd_stashed(BwdAllArgs aa, fl
         if (!is_s) bwd_tile_stashed<G, false, FULL, INVD, SB6>(a, img, sd, acc, f, stash, k, aa.ncoup, ybar, lbar, lbar_const, tile, nt, l31, hi, tr);
         else bwd_tile_stashed<G, true, FULL, INVD, SB6>(a, img, sd, acc, f, stash, k, aa.ncoup, ybar, lbar, lbar_const, tile, nt, l31, hi, tr);
       }
-      NF_ST_STAMP(2 + phase * 4);
+      NF_STAMP(step == 0 ? tr0 : nullptr, 2 + phase * 4);
       __syncthreads();  // every wave is done with the weight image and its scratch
-      NF_ST_STAMP(3 + phase * 4);
+      NF_STAMP(step == 0 ? tr0 : nullptr, 3 + phase * 4);
       // s and u of the next phase-S's first tile fly behind the fold, the slab write and the staging of the next image
       if (tile0 < ntiles) {
         if (!INVD && !is_s) stash_issue_first<G>(f, stash, k, aa.ncoup, tile0, l31, hi);
@@ -1607,7 +1554,7 @@ __global__ __launch_bounds__(256, 1) void k_affine_bwd_stashed(BwdAllArgs aa, fl
         }
       }
       __syncthreads();  // image is restaged next phase; ybar stores of this phase are read by the next (same wave)
-      NF_ST_STAMP(4 + phase * 4);
+      NF_STAMP(step == 0 ? tr0 : nullptr, 4 + phase * 4);
     }
   }
 }
@@ -1703,7 +1650,7 @@ __device__ __forceinline__ void pair_produce(const CouplingArgs &a, const float 
     __syncthreads();
     return;
   }
-  NF_TS_STAMP(0);
+  NF_STAMP(tr, 0);
   const long j = tile * NF_TILE + l31;
   const bool valid = FULL ? true : j < a.N;
   const int par_c = 1 - a.par_t;
@@ -1776,9 +1723,9 @@ __device__ __forceinline__ void pair_produce(const CouplingArgs &a, const float 
   for (int b = 0; b < G::H1B; ++b) m1[b] = mk[b];
 #pragma unroll
   for (int b = 0; b < G::H2B; ++b) m2[b] = mk[2 + b];
-  NF_TS_STAMP(1);
+  NF_STAMP(tr, 1);
   __syncthreads();  // B1: d3 is in LDS (and the consumer is done with the previous tile's d1)
-  NF_TS_STAMP(2);
+  NF_STAMP(tr, 2);
   f32x16 d2[G::H2B];
   const nf_u32x4 *wt = reinterpret_cast<const nf_u32x4 *>(img);  // PB6: the staged image is the net's B6T image
   SplitC<DW6 ? G::H2B : 1> s2;
@@ -1797,9 +1744,9 @@ __device__ __forceinline__ void pair_produce(const CouplingArgs &a, const float 
     apply_lrelu_grad<G::H2B>(d2, m2);
     tile_to_scratch<G::H2B>(sp + L::D2, d2, l31, hi);
   }
-  NF_TS_STAMP(3);
+  NF_STAMP(tr, 3);
   __syncthreads();  // B2
-  NF_TS_STAMP(4);
+  NF_STAMP(tr, 4);
   f32x16 d1[G::H1B];
   SplitC<DW6 ? G::H1B : 1> s1;
   if constexpr (DW6) {
@@ -1814,12 +1761,12 @@ __device__ __forceinline__ void pair_produce(const CouplingArgs &a, const float 
     apply_lrelu_grad<G::H1B>(d1, m1);
     tile_to_scratch<G::H1B>(sp + L::D1, d1, l31, hi);
   }
-  NF_TS_STAMP(5);
+  NF_STAMP(tr, 5);
   __syncthreads();  // B3
-  NF_TS_STAMP(6);
+  NF_STAMP(tr, 6);
   if (PHASE_S && next_tile >= 0) stash_issue_first<G, SLIM>(f, stash, k, ncoup, next_tile, l31, hi);
   if (last) {  // the input cotangent of the whole flow: not read by the training step that set no_xbar
-    NF_TS_STAMP(7);
+    NF_STAMP(tr, 7);
     return;
   }
   if constexpr (!FIRST && parked) {  // the conditioner half's cotangent, needed by the closing stores only: in flight behind the GEMM
@@ -1861,7 +1808,7 @@ __device__ __forceinline__ void pair_produce(const CouplingArgs &a, const float 
 #pragma unroll
       for (int r = 0; r < 16; ++r) tile_store(gio, tile_soff(b, r, par_c), (gold[b][r] + pk.g2[S2][b][r]) + g2[b][r]);
   }
-  NF_TS_STAMP(7);
+  NF_STAMP(tr, 7);
 }
 
 // (Round 6, measured and removed: the consumer held back by s_sleep behind each barrier -- 256 / 512 / 768 clocks in stage 1,
@@ -1885,7 +1832,7 @@ __device__ __forceinline__ void pair_consume(const float *__restrict__ img, cons
     __syncthreads();
     return;
   }
-  NF_TS_STAMP(0);
+  NF_STAMP(tr, 0);
   const int nbase = SG::NET0 + (is_s ? 0 : SG::NETSZ);
   const StashIO st = make_stash_io(stash, tile * ncoup + k, SG::SIZE, true, l31, hi);
   const int vT = (l31 * 32 + hi * 16) * 4;
@@ -1900,18 +1847,18 @@ __device__ __forceinline__ void pair_consume(const float *__restrict__ img, cons
     {
       float a2t[G::H2B][16];
       stash_get_T<G::H2B>(st, nbase + SG::A2, vT, a2t);
-      NF_TS_STAMP(1);
+      NF_STAMP(tr, 1);
       __syncthreads();  // B1
-      NF_TS_STAMP(2);
+      NF_STAMP(tr, 2);
       SplitT<G::H2B> a2s;
       stash_get_T<G::H1B>(st, nbase + SG::A1, vT, a1t);
       split_T<G::H2B>(a2t, a2s);
       __builtin_amdgcn_sched_barrier(0);
       dw_accumulate_tr6<G::H2B, G::CB>(a2s, bufa, acc.w3, acc.b3, l31, hi);
     }
-    NF_TS_STAMP(3);
+    NF_STAMP(tr, 3);
     __syncthreads();  // B2
-    NF_TS_STAMP(4);
+    NF_STAMP(tr, 4);
     {
       SplitT<G::H1B> a1s;
       stash_get_T<G::MB>(st, SG::XT, vT, x2t);
@@ -1919,16 +1866,16 @@ __device__ __forceinline__ void pair_consume(const float *__restrict__ img, cons
       __builtin_amdgcn_sched_barrier(0);
       dw_accumulate_tr6<G::H1B, G::H2B>(a1s, bufb, acc.w2, acc.b2, l31, hi);
     }
-    NF_TS_STAMP(5);
+    NF_STAMP(tr, 5);
     __syncthreads();  // B3
-    NF_TS_STAMP(6);
+    NF_STAMP(tr, 6);
     {
       SplitT<G::MB> x2s;
       split_T<G::MB>(x2t, x2s);
       __builtin_amdgcn_sched_barrier(0);
       dw_accumulate_tr6<G::MB, G::H1B>(x2s, bufa, acc.w1, acc.b1, l31, hi);
     }
-    NF_TS_STAMP(7);
+    NF_STAMP(tr, 7);
     return;  // (the dW1 block below belongs to the two fp32-tile forms)
   } else if constexpr (SLIM) {
     // a1 is not in the stash: rebuilt here, in this wave's MFMA-free prologue (the producer is in its own: operand loads,
@@ -1940,41 +1887,41 @@ __device__ __forceinline__ void pair_consume(const float *__restrict__ img, cons
       float a2t[G::H2B][16];
       stash_get_T<G::H2B>(st, nbase + SG::A2, vT, a2t);
       recompute_a1t<G>(img, x2c, a1t, l31, hi);
-      NF_TS_STAMP(1);
+      NF_STAMP(tr, 1);
       __syncthreads();  // B1
-      NF_TS_STAMP(2);
+      NF_STAMP(tr, 2);
       dw_accumulate_reg<G::H2B, G::CB>(a2t, sp + L::D3, acc.w3, acc.b3, l31, hi);
     }
-    NF_TS_STAMP(3);
+    NF_STAMP(tr, 3);
     __syncthreads();  // B2
-    NF_TS_STAMP(4);
+    NF_STAMP(tr, 4);
     dw_accumulate_reg<G::H1B, G::H2B, NoSideJob, true>(a1t, sp + L::D2, acc.w2, acc.b2, l31, hi);
   } else {
     {
       float a2t[G::H2B][16];
       stash_get_T<G::H2B>(st, nbase + SG::A2, vT, a2t);
-      NF_TS_STAMP(1);
+      NF_STAMP(tr, 1);
       __syncthreads();  // B1
-      NF_TS_STAMP(2);
+      NF_STAMP(tr, 2);
       dw_accumulate_reg<G::H2B, G::CB>(a2t, sp + L::D3, acc.w3, acc.b3, l31, hi);
     }
     {
       float a1t[G::H1B][16];
       stash_get_T<G::H1B>(st, nbase + SG::A1, vT, a1t);
-      NF_TS_STAMP(3);
+      NF_STAMP(tr, 3);
       __syncthreads();  // B2
-      NF_TS_STAMP(4);
+      NF_STAMP(tr, 4);
       dw_accumulate_reg<G::H1B, G::H2B>(a1t, sp + L::D2, acc.w2, acc.b2, l31, hi);
     }
   }
   {
     float x2t[G::MB][16];
     stash_get_T<G::MB>(st, SG::XT, vT, x2t);
-    NF_TS_STAMP(5);
+    NF_STAMP(tr, 5);
     __syncthreads();  // B3
-    NF_TS_STAMP(6);
+    NF_STAMP(tr, 6);
     dw_accumulate_reg<G::MB, G::H1B>(x2t, sp + L::D1, acc.w1, acc.b1, l31, hi);
-    NF_TS_STAMP(7);
+    NF_STAMP(tr, 7);
   }
 }
 
@@ -2066,11 +2013,11 @@ __global__ __launch_bounds__(512) void k_affine_bwd_pair(BwdAllArgs aa, float *s
 #ifdef NF_KERNEL_TRACE  // the phase boundary: producer stamps [32 + phase 8 + 0..7], consumer [96 + ...]
         long long *trb = (aa.trace && blockIdx.x == 0 && tid == 64 * NF_TRACE_PAIR && step == 0) ? aa.trace + 32 + phase * 8 : nullptr;
 #endif
-        NF_TSB(0);
+        NF_STAMP(trb, 0);
         stage_image(k, is_s);
-        NF_TSB(1);
+        NF_STAMP(trb, 1);
         __syncthreads();
-        NF_TSB(2);
+        NF_STAMP(trb, 2);
         auto produce = [&](int it, auto slot) {
           constexpr int SLOT = decltype(slot)::value;
           const long tile = tile0 + (long)it * tstride;
@@ -2093,20 +2040,20 @@ __global__ __launch_bounds__(512) void k_affine_bwd_pair(BwdAllArgs aa, float *s
         }
 #pragma unroll 1
         for (int it = it0; it < rounds; ++it) produce(it, std::integral_constant<int, -1>{});
-        NF_TSB(3);
+        NF_STAMP(trb, 3);
         __syncthreads();  // every wave is done with the weight image and the delta tiles
-        NF_TSB(4);
+        NF_STAMP(trb, 4);
         // s and u of the next phase-S's first tile fly behind the fold, the slab write and the staging of the next image
         if (tile0 < ntiles) {
           if (!INVD && !is_s) stash_issue_first<G, SLIM>(f, stash, k, aa.ncoup, tile0, l31, hi);
           if (INVD && !is_s && step + 1 < aa.ncoup) stash_issue_first<G, SLIM>(f, stash, k - 1, aa.ncoup, tile0, l31, hi);
         }
         __syncthreads();  // the consumers have folded
-        NF_TSB(5);
+        NF_STAMP(trb, 5);
         pair_slab_write<G>(lds, slab + (long)k * 2 * G::SIZE + ((long)blockIdx.x * slab_stride + (is_s ? 0 : 1) * (long)G::SIZE), tid);
-        NF_TSB(6);
+        NF_STAMP(trb, 6);
         __syncthreads();
-        NF_TSB(7);
+        NF_STAMP(trb, 7);
       }
     }
   } else {
@@ -2120,15 +2067,15 @@ __global__ __launch_bounds__(512) void k_affine_bwd_pair(BwdAllArgs aa, float *s
 #ifdef NF_KERNEL_TRACE
         long long *trb = (aa.trace && blockIdx.x == 0 && tid == 256 + 64 * NF_TRACE_PAIR && step == 0) ? aa.trace + 96 + phase * 8 : nullptr;
 #endif
-        NF_TSB(0);
+        NF_STAMP(trb, 0);
         stage_image(k, is_s);
-        NF_TSB(1);
+        NF_STAMP(trb, 1);
         __syncthreads();
-        NF_TSB(2);
+        NF_STAMP(trb, 2);
         BwdAcc<G> acc;
-        zero_acc(acc.w1, acc.b1);
-        zero_acc(acc.w2, acc.b2);
-        zero_acc(acc.w3, acc.b3);
+        net_zero_acc(acc.w1, acc.b1);
+        net_zero_acc(acc.w2, acc.b2);
+        net_zero_acc(acc.w3, acc.b3);
 #pragma unroll 1
         for (int it = 0; it < rounds; ++it) {
           const long tile = tile0 + (long)it * tstride;
@@ -2139,9 +2086,9 @@ __global__ __launch_bounds__(512) void k_affine_bwd_pair(BwdAllArgs aa, float *s
 #endif
           pair_consume<G, SLIM, PB6, DW6>(img, sp, acc, stash, k, aa.ncoup, tile, is_s, tile < ntiles, l31, hi, it & 1, tr);
         }
-        NF_TSB(3);
+        NF_STAMP(trb, 3);
         __syncthreads();  // every wave is done with the weight image and the delta tiles
-        NF_TSB(4);
+        NF_STAMP(trb, 4);
         {
           float *mine = lds + pair * G::SIZE;
           fold_acc(mine + G::W1, mine + G::B1, acc.w1, acc.b1, true, l31, hi);
@@ -2149,11 +2096,11 @@ __global__ __launch_bounds__(512) void k_affine_bwd_pair(BwdAllArgs aa, float *s
           fold_acc(mine + G::W3, mine + G::B3, acc.w3, acc.b3, true, l31, hi);
         }
         __syncthreads();
-        NF_TSB(5);
+        NF_STAMP(trb, 5);
         pair_slab_write<G>(lds, slab + (long)k * 2 * G::SIZE + ((long)blockIdx.x * slab_stride + (is_s ? 0 : 1) * (long)G::SIZE), tid);
-        NF_TSB(6);
+        NF_STAMP(trb, 6);
         __syncthreads();
-        NF_TSB(7);
+        NF_STAMP(trb, 7);
       }
     }
   }
@@ -2163,18 +2110,6 @@ __global__ __launch_bounds__(512) void k_affine_bwd_pair(BwdAllArgs aa, float *s
 // host-side dispatch
 // ------------------------------------------------------------------------------------
 static inline int blocks32(int n) { return (n + 31) / 32; }
-// nets with 1, 3 or 4 hidden layers (nf_deep.hip): to nf_api.hip they are "resident RealNVP flows without a stash", so every
-// nf_affine_* entry point below hands them over first
-int nf_deep_geo_id(const nf_flow_desc *desc);
-int nf_deep_image_floats(const nf_flow_desc *desc);
-size_t nf_deep_wimg_bytes(const nf_flow_desc *desc);
-long nf_deep_slab_floats(const nf_flow_desc *desc);
-int nf_deep_pack(nf_ctx *ctx, const nf_flow_desc *desc, const float *theta);
-int nf_deep_reduce_slabs(nf_ctx *ctx, const nf_flow_desc *desc, const float *slab, int nslab, float *g, const double *lpart, int nlpart,
-                         float *lout);
-int nf_deep_chain(nf_ctx *ctx, const nf_flow_desc *desc, bool inverse, float *xt, long N, float *ladj, int k_only, int accumulate);
-int nf_deep_bwd(nf_ctx *ctx, const nf_flow_desc *desc, int k_lo, int k_hi, float *y, float *ybar, const float *lbar, float lbar_const,
-                long N, float *slab, long slab_stride, int grid, bool inv_dir);
 #define NF_GEO_H32 NetGeo<1, 1, 1, 1>
 #define NF_GEO_H64 NetGeo<1, 2, 2, 1>
 
@@ -2354,11 +2289,7 @@ static int make_args(nf_ctx *ctx, const nf_flow_desc *desc, int k, const float *
 template <class G, bool INV, bool FULL>
 static int launch_apply_v(nf_ctx *ctx, const CouplingArgs &a, const float *x, float *y, float *ladj, int accumulate) {
   const size_t lds = 2 * (size_t)G::SIZE * sizeof(float);
-  static AttrOnce attr_once;  // once per device: a context on another GPU needs its own
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    NF_HIP(hipFuncSetAttribute((const void *)k_affine_apply<G, INV, FULL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return NF_OK;
-  }));
+  NF_TRY((nf_lds_once<k_affine_apply<G, INV, FULL>>(ctx, lds)));
   const long ntiles = (a.N + NF_TILE - 1) / NF_TILE;
   long grid = (ntiles + 7) / 8;
   const long cap = 2L * ctx->num_cu;
@@ -2430,11 +2361,7 @@ template <class G, bool FULL>
 static int launch_bwd_v(nf_ctx *ctx, const CouplingArgs &a, float *y, float *ybar, const float *lbar, float lbar_const,
                         float *slab, long slab_stride, int grid) {
   const size_t lds = BwdLds<G>::BYTES;
-  static AttrOnce attr_once;  // once per device: a context on another GPU needs its own
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    NF_HIP(hipFuncSetAttribute((const void *)k_affine_bwd<G, FULL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return NF_OK;
-  }));
+  NF_TRY((nf_lds_once<k_affine_bwd<G, FULL>>(ctx, lds)));
   ProfScope ps(ctx, "affine_bwd");
   hipLaunchKernelGGL((k_affine_bwd<G, FULL>), dim3((unsigned)grid), dim3(256), lds, ctx->stream, a, y, ybar, lbar,
                      lbar_const, slab, slab_stride);
@@ -2582,11 +2509,7 @@ bool nf_affine_chain_fkl_ok(const nf_flow_desc *desc) {
 template <class G>
 static int launch_chain_fkl(nf_ctx *ctx, const nf_flow_desc *desc, const float *ys, long N, const FusedArgs &fa) {
   const size_t lds = 4 * (size_t)G::SIZE * sizeof(float) + (2 * 64 * G::CB + 2) * sizeof(float) + 12 * sizeof(double);
-  static AttrOnce attr_once;  // once per device: a context on another GPU needs its own
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    NF_HIP(hipFuncSetAttribute((const void *)k_affine_chain<G, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return NF_OK;
-  }));
+  NF_TRY((nf_lds_once<k_affine_chain<G, true, true, true>>(ctx, lds)));
   ChainArgs a;
   a.wimg = (const float *)ctx->wimg;
   a.wimg_b6 = nullptr;
@@ -2643,11 +2566,7 @@ template <class G, bool FULL, bool INVD = false>
 static int launch_bwd_all_v(nf_ctx *ctx, const BwdAllArgs &aa, float *y, float *ybar, const float *lbar, float lbar_const,
                             float *slab, long slab_stride, int grid) {
   const size_t lds = BwdLds<G>::BYTES;
-  static AttrOnce attr_once;  // once per device: a context on another GPU needs its own
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    NF_HIP(hipFuncSetAttribute((const void *)k_affine_bwd_all<G, FULL, INVD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return NF_OK;
-  }));
+  NF_TRY((nf_lds_once<k_affine_bwd_all<G, FULL, INVD>>(ctx, lds)));
   ProfScope ps(ctx, INVD ? "affine_bwd_inv" : "affine_bwd");
   hipLaunchKernelGGL((k_affine_bwd_all<G, FULL, INVD>), dim3((unsigned)grid), dim3(256), lds, ctx->stream, aa, y, ybar, lbar,
                      lbar_const, slab, slab_stride);
@@ -2729,11 +2648,7 @@ template <class G, bool FULL, bool INVD, bool SLIM, bool PB6, bool DW6 = false>
 static int launch_bwd_pair_v(nf_ctx *ctx, const nf_flow_desc *desc, BwdAllArgs aa, float *stash, float *ybar, const float *lbar,
                              float lbar_const, float *slab, long slab_stride, int grid) {
   const size_t lds = BwdPairLds<G, PB6, DW6>::BYTES;
-  static AttrOnce attr_once;  // once per device
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    NF_HIP(hipFuncSetAttribute((const void *)k_affine_bwd_pair<G, FULL, INVD, SLIM, PB6, DW6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return NF_OK;
-  }));
+  NF_TRY((nf_lds_once<k_affine_bwd_pair<G, FULL, INVD, SLIM, PB6, DW6>>(ctx, lds)));
   if (PB6) {
     NF_TRY(b6t_refresh<G>(ctx, desc));
     aa.wimg_b6t = (const unsigned char *)ctx->wimg + b6t_offset_bytes<G>(desc);

@@ -24,7 +24,9 @@
 #include <cstdlib>
 
 #include "nf_common.h"
+#include "nf_launchers.h"
 #include "nf_mfma.h"
+#include "nf_net_stages.h"
 
 template <int NH_, int HB_>
 struct DeepGeo {
@@ -106,13 +108,7 @@ __global__ __launch_bounds__(256) void k_deep_reduce_slabs(DeepPack p, const flo
                                                            float *__restrict__ lout) {
   if (lout && blockIdx.x == 0) {  // block 0 also finishes the step's loss from the forward launch's partials (fixed order)
     __shared__ double sm[4];
-    double c = 0.0;
-    for (int i = threadIdx.x; i < nlpart; i += 256) c += lpart[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) *lout = (float)((sm[0] + sm[1]) + (sm[2] + sm[3]));
+    net_finish_partials<4, true>(lpart, nlpart, sm, lout);
   }
   __shared__ float part[4][64];
   const int lane = threadIdx.x & 63, q = threadIdx.x >> 6;
@@ -122,7 +118,7 @@ __global__ __launch_bounds__(256) void k_deep_reduce_slabs(DeepPack p, const flo
     const int k = (int)(gid / (2 * G::SIZE)), net = (int)((gid / G::SIZE) & 1), e = (int)(gid % G::SIZE);
     ti = deep_theta_index<G>(deep_dims_of(p, k, net), e);
   }
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;  // k_rqs_reduce_slabs's slab sum, in place: as a shared call it reorders this kernel
   if (ti >= 0) {
     int s = q;
     for (; s + 12 < nslab; s += 16) {
@@ -135,7 +131,7 @@ __global__ __launch_bounds__(256) void k_deep_reduce_slabs(DeepPack p, const flo
   }
   part[q][lane] = (a0 + a1) + (a2 + a3);
   __syncthreads();
-  if (q == 0 && ti >= 0) g[ti] = (part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]);
+  if (q == 0 && ti >= 0) g[ti] = net_part_sum<4, true>(part, lane);
 }
 
 // out = net(x): the NH hidden layers with leaky-ReLU, the output layer without activation (src/flows/utils.jl:71-100)
@@ -257,24 +253,11 @@ struct DeepLds {  // floats
   static constexpr int SCRATCH = OFF_D + 32 * G::HB * NF_TS;
   static constexpr size_t BYTES = (size_t)(G::SIZE + 4 * SCRATCH) * sizeof(float);
 };
-template <int IB, int OB>
-__device__ __forceinline__ void deep_zero(f32x16 (&a)[IB][OB], float (&b)[OB]) {
-#pragma unroll
-  for (int i = 0; i < IB; ++i)
-#pragma unroll
-    for (int o = 0; o < OB; ++o)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) a[i][o][r] = 0.f;
-#pragma unroll
-  for (int o = 0; o < OB; ++o) b[o] = 0.f;
-}
 // The blocks of a layer whose running number (B0 + the block's index in the layer) is `sel` modulo 4: see the fold in k_deep_bwd.
 template <int IB, int OB, int S, int B0>
 __device__ __forceinline__ void deep_fold(float *__restrict__ w, float *__restrict__ b, const f32x16 (&a)[IB][OB], const float (&bs)[OB],
                                           bool first, int sel, int l31, int hi) {
-  // A block's sixteen partial sums are read in one go, then written back (round 5).  As one read-modify-write after the other
-  // (`*p = *p + a`) every LDS round trip was exposed: tools/trace_deep_bwd.py showed the fold at 15.0 k of a phase's 56.6 k
-  // clocks for one hidden layer of 64 and 52.8 k of 183 k for three -- more than a quarter of the reverse kernel.
+  // net_fold_acc's body (nf_net_stages.h) with the block filter
 #pragma unroll
   for (int i = 0; i < IB; ++i)
 #pragma unroll
@@ -300,44 +283,12 @@ __device__ __forceinline__ void deep_fold(float *__restrict__ w, float *__restri
   }
 }
 
-// every block of a layer (the waves-in-turn fold)
-template <int IB, int OB, int S>
-__device__ __forceinline__ void deep_fold_all(float *__restrict__ w, float *__restrict__ b, const f32x16 (&a)[IB][OB], const float (&bs)[OB],
-                                              bool first, int l31, int hi) {
-#pragma unroll
-  for (int i = 0; i < IB; ++i)
-#pragma unroll
-    for (int o = 0; o < OB; ++o) {
-      float *p = w + (i * 32 + 4 * hi) * S + o * 32 + l31;  // row nf_row(r, hi) = (r & 3) + 8 (r >> 2) + 4 hi
-      float old[16];
-      if (!first) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) old[r] = p[((r & 3) + 8 * (r >> 2)) * S];
-      }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) p[((r & 3) + 8 * (r >> 2)) * S] = first ? a[i][o][r] : old[r] + a[i][o][r];
-    }
-#pragma unroll
-  for (int o = 0; o < OB; ++o) {
-    const float v = bs[o] + __shfl_xor(bs[o], 32);
-    if (hi == 0) {
-      float *p = b + o * 32 + l31;
-      *p = first ? v : *p + v;
-    }
-  }
-}
-
 struct DeepBwdArgs {
   const float *wimg;
   int d, ncoup, k_lo, k_hi;  // flat couplings [k_lo, k_hi)
   long N;
   long long *trace;  // NF_KERNEL_TRACE builds: clock stamps of workgroup 0 / wave 0 (tools/trace_deep_bwd.py), else unused
 };
-#ifdef NF_KERNEL_TRACE
-#define DEEP_STAMP(slot) do { if (tr) { __builtin_amdgcn_sched_barrier(0); tr[slot] = clock64(); } } while (0)
-#else
-#define DEEP_STAMP(slot) do { (void)tr; } while (0)
-#endif
 
 // reverse pass of one (tile, coupling, net).  PHASE_S / INVD as bwd_tile of nf_coupling.hip:
 //   forward chain:  phase T first (y1 <- u = y1 - T, T-bar = ybar1), then phase S (x1 = u exp(-s), x1bar = ybar1 exp(s),
@@ -350,7 +301,7 @@ __device__ __forceinline__ void deep_bwd_tile(const float *__restrict__ img, flo
                                               float lbar_const, int d, int c, int par_t, long N, long tile, int l31, int hi,
                                               long long *tr = nullptr) {
   using L = DeepLds<G>;
-  DEEP_STAMP(0);
+  NF_STAMP(tr, 0);
   const long j = tile * NF_TILE + l31;
   const bool valid = j < N;
   const int par_c = 1 - par_t;
@@ -368,7 +319,7 @@ __device__ __forceinline__ void deep_bwd_tile(const float *__restrict__ img, flo
       const float v = tile_load(yio, tile_soff(0, r, par_c));  // features >= d read as 0
       xb[0][r] = valid ? v : 0.f;
     }
-    DEEP_STAMP(1);  // (the first use of xb forces the wait: x2 has arrived)
+    NF_STAMP(tr, 1);  // (the first use of xb forces the wait: x2 has arrived)
     tile_to_scratch<1>(sx, xb, l31, hi);
     dense_fwd<1, G::HB, G::SH>(img + G::W(0), img + G::B(0), xb, act[0], l31, hi);
   }
@@ -392,9 +343,9 @@ __device__ __forceinline__ void deep_bwd_tile(const float *__restrict__ img, flo
     y1[0][r] = tile_load(yio, tile_soff(0, r, par_t));
     g1[0][r] = tile_load(gio, tile_soff(0, r, par_t));
   }
-  DEEP_STAMP(2);
+  NF_STAMP(tr, 2);
   dense_fwd<G::HB, 1, G::SO>(img + G::W(G::NH), img + G::B(G::NH), act[G::NH - 1], d3, l31, hi);
-  DEEP_STAMP(3);
+  NF_STAMP(tr, 3);
 
   const float lb = valid ? (lbar ? lbar[j < N ? j : 0] : lbar_const) : 0.f;
 #pragma unroll
@@ -423,7 +374,7 @@ __device__ __forceinline__ void deep_bwd_tile(const float *__restrict__ img, flo
     }
   }
 
-  DEEP_STAMP(4);
+  NF_STAMP(tr, 4);
   // ---- output layer: dX, then dW^T from the transposed operands
   f32x16 dh[G::HB];
   dense_bwd_x<G::HB, 1, G::SO>(img + G::W(G::NH), d3, dh, l31, hi);
@@ -436,7 +387,7 @@ __device__ __forceinline__ void deep_bwd_tile(const float *__restrict__ img, flo
 #pragma unroll
     for (int r = 0; r < 16; ++r) dh[b][r] *= nf_mask_slope(msk[G::NH - 1][b], r);
   wave_lds_fence();
-  DEEP_STAMP(5);
+  NF_STAMP(tr, 5);
   // ---- hidden -> hidden layers, last to first
 #pragma unroll
   for (int l = G::NH - 1; l >= 1; --l) {
@@ -452,7 +403,7 @@ __device__ __forceinline__ void deep_bwd_tile(const float *__restrict__ img, flo
       for (int r = 0; r < 16; ++r) dh[b][r] = dp[b][r] * nf_mask_slope(msk[l - 1][b], r);
     wave_lds_fence();
   }
-  DEEP_STAMP(6);
+  NF_STAMP(tr, 6);
   // ---- layer 0: x2bar accumulates ybar2 + W0t^T d (phase T) + W0s^T d (phase S)
   f32x16 g2[1];
 #pragma unroll
@@ -464,7 +415,7 @@ __device__ __forceinline__ void deep_bwd_tile(const float *__restrict__ img, flo
 #pragma unroll
   for (int r = 0; r < 16; ++r) tile_store(gio, tile_soff(0, r, par_c), g2[0][r]);
   wave_lds_fence();
-  DEEP_STAMP(7);
+  NF_STAMP(tr, 7);
 }
 
 // Reverse pass of the couplings [k_lo, k_hi) in one launch: a wave's tiles never change hands and coupling k + 1 only reads what
@@ -491,16 +442,16 @@ __global__ __launch_bounds__(256, 1) void k_deep_bwd(DeepBwdArgs a, float *__res
       const bool is_s = INVD ? phase == 0 : phase == 1;  // forward chain: T then S; inverse chain: S then T
       // stamps: [0..4] of the first phase: start, image staged, tiles done, folded, slab written; [8 + 8 i ..] tile i of that phase
       long long *tr = (a.trace && blockIdx.x == 0 && tid == 0 && step == 0 && phase == 0) ? a.trace : nullptr;
-      DEEP_STAMP(0);
+      NF_STAMP(tr, 0);
       stage_packed<G::SIZE, 256>(img, a.wimg + ((size_t)k * 2 + (is_s ? 0 : 1)) * G::SIZE, tid);
       __syncthreads();
-      DEEP_STAMP(1);
+      NF_STAMP(tr, 1);
       int tcount = 0;
       DeepAcc<G> acc;
-      deep_zero(acc.w0, acc.b0);
+      net_zero_acc(acc.w0, acc.b0);
 #pragma unroll
-      for (int l = 0; l < (G::NH > 1 ? G::NH - 1 : 1); ++l) deep_zero(acc.wh[l], acc.bh[l]);
-      deep_zero(acc.wo, acc.bo);
+      for (int l = 0; l < (G::NH > 1 ? G::NH - 1 : 1); ++l) net_zero_acc(acc.wh[l], acc.bh[l]);
+      net_zero_acc(acc.wo, acc.bo);
 #pragma unroll 1
       for (long tile = (long)blockIdx.x * 4 + wave; tile < ntiles; tile += (long)gridDim.x * 4) {
         long long *trt = (tr && tcount < 8) ? tr + 8 + 8 * tcount : nullptr;
@@ -511,7 +462,7 @@ __global__ __launch_bounds__(256, 1) void k_deep_bwd(DeepBwdArgs a, float *__res
           deep_bwd_tile<G, false, INVD>(img, sc, acc, y, ybar, lbar, lbar_const, a.d, c, par_t, a.N, tile, l31, hi, trt);
       }
       __syncthreads();  // the weight image is dead: it becomes the fold target
-      DEEP_STAMP(2);
+      NF_STAMP(tr, 2);
       // Four steps, every wave busy in each: in step s wave w adds its sums to the blocks numbered (w + s) mod 4 -- block b is
       // written by wave b mod 4 first, then added to by waves b - 1, b - 2, b - 3 (mod 4): a fixed order per element, and the
       // four waves one after the other over the WHOLE image took four times as long (hidden [64]: 364 -> 332 us per launch).
@@ -539,16 +490,16 @@ __global__ __launch_bounds__(256, 1) void k_deep_bwd(DeepBwdArgs a, float *__res
 #pragma unroll 1
         for (int w = 0; w < 4; ++w) {
           if (wave == w) {
-            deep_fold_all<1, G::HB, G::SH>(img + G::W(0), img + G::B(0), acc.w0, acc.b0, w == 0, l31, hi);
+            net_fold_acc<1, G::HB, G::SH>(img + G::W(0), img + G::B(0), acc.w0, acc.b0, w == 0, l31, hi);
 #pragma unroll
             for (int l = 1; l < G::NH; ++l)
-              deep_fold_all<G::HB, G::HB, G::SH>(img + G::W(l), img + G::B(l), acc.wh[l - 1], acc.bh[l - 1], w == 0, l31, hi);
-            deep_fold_all<G::HB, 1, G::SO>(img + G::W(G::NH), img + G::B(G::NH), acc.wo, acc.bo, w == 0, l31, hi);
+              net_fold_acc<G::HB, G::HB, G::SH>(img + G::W(l), img + G::B(l), acc.wh[l - 1], acc.bh[l - 1], w == 0, l31, hi);
+            net_fold_acc<G::HB, 1, G::SO>(img + G::W(G::NH), img + G::B(G::NH), acc.wo, acc.bo, w == 0, l31, hi);
           }
           __syncthreads();
         }
       }
-      DEEP_STAMP(3);
+      NF_STAMP(tr, 3);
       {
         const float4 *c0 = reinterpret_cast<const float4 *>(img);
         float4 *dst = reinterpret_cast<float4 *>(slab + (long)blockIdx.x * slab_stride + ((long)k * 2 + (is_s ? 0 : 1)) * G::SIZE);
@@ -556,7 +507,7 @@ __global__ __launch_bounds__(256, 1) void k_deep_bwd(DeepBwdArgs a, float *__res
       }
       __syncthreads();  // the image region is restaged by the next phase (its loads of y / ybar see this phase's stores:
                         // same wave, vmcnt(0) at the barrier, write-through L1 -- as k_affine_bwd_all)
-      DEEP_STAMP(4);
+      NF_STAMP(tr, 4);
     }
   }
 }
@@ -603,8 +554,6 @@ static DeepPack deep_pack_args(const nf_flow_desc *desc) {
   return p;
 }
 
-int nf_wimg_reserve(nf_ctx *ctx, size_t bytes);
-
 template <class G>
 static int deep_launch_pack(nf_ctx *ctx, unsigned grid, const DeepPack &p, const float *theta) {
   hipLaunchKernelGGL((k_deep_pack<G>), dim3(grid), dim3(256), 0, ctx->stream, p, theta, (float *)ctx->wimg);
@@ -646,11 +595,7 @@ int nf_deep_reduce_slabs(nf_ctx *ctx, const nf_flow_desc *desc, const float *sla
 template <class G, bool INV>
 static int deep_launch_chain(nf_ctx *ctx, const DeepChainArgs &a, float *xt, float *ladj) {
   const size_t lds = 2 * (size_t)G::SIZE * sizeof(float);
-  static AttrOnce attr_once;  // once per device
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    NF_HIP(hipFuncSetAttribute((const void *)k_deep_chain<G, INV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return NF_OK;
-  }));
+  NF_TRY((nf_lds_once<k_deep_chain<G, INV>>(ctx, lds)));
   const long ngroups = ((a.N + NF_TILE - 1) / NF_TILE + 7) / 8;
   long grid = ngroups < ctx->num_cu ? ngroups : ctx->num_cu;
   if (grid < 1) grid = 1;
@@ -675,11 +620,7 @@ template <class G, bool INVD>
 static int deep_launch_bwd(nf_ctx *ctx, const DeepBwdArgs &a, float *y, float *ybar, const float *lbar, float lbar_const, float *slab,
                            long slab_stride, int grid) {
   const size_t lds = DeepLds<G>::BYTES;
-  static AttrOnce attr_once;  // once per device
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    NF_HIP(hipFuncSetAttribute((const void *)k_deep_bwd<G, INVD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return NF_OK;
-  }));
+  NF_TRY((nf_lds_once<k_deep_bwd<G, INVD>>(ctx, lds)));
   ProfScope ps(ctx, INVD ? "deep_bwd_inv" : "deep_bwd");
   hipLaunchKernelGGL((k_deep_bwd<G, INVD>), dim3((unsigned)grid), dim3(256), lds, ctx->stream, a, y, ybar, lbar, lbar_const, slab, slab_stride);
   return (int)hipGetLastError();

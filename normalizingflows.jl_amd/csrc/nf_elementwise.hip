@@ -7,6 +7,7 @@
 // 16-lane group reads 64 contiguous bytes per step, and per-sample sums (||x||^2, log p)
 // are 4-step DPP/shuffle reductions inside the group.
 #include "nf_common.h"
+#include "nf_launchers.h"
 #include "nf_philox.h"
 #include "nf_target_stages.h"
 #include "nf_targets.h"

@@ -30,6 +30,7 @@
 // cotangent pullback (k_fr_apply_flat); the parameter gradient is one thread per parameter and sample chunk
 // (k_fr_grad_flat), the chunks' slabs reduced in order like the Float32 ones.
 #include "nf_common.h"
+#include "nf_launchers.h"
 #include "nf_mfma.h"
 
 #define FR_BLOCK 256
@@ -482,8 +483,6 @@ __global__ __launch_bounds__(FR_BLOCK) void k_fr_grad_flat(int d, long N, long c
 // ---------------------------------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------------------------------
-int nf_launch_reduce_slabs(nf_ctx *, int, const void *, int, long, void *);
-
 bool nf_fr_supported(const nf_flow_desc *desc) { return desc->d >= 1 && desc->d <= FR_MAXD; }
 
 static inline long fr_params(int d) { return (long)d + (long)d * d; }
@@ -492,11 +491,7 @@ template <int DB>
 static int fr_gemm_db(nf_ctx *ctx, int d, long N, const float *Lm, int trans, const float *sub, const float *add, const float *Ld,
                       float lsign, const float *in, int in_tiled, float *out, int out_tiled, float *ladj) {
   const size_t lds = (size_t)(FrGeo<DB>::TILE + FR_WAVES * FrGeo<DB>::IMG) * sizeof(float);
-  static AttrOnce attr_once;
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    NF_HIP(hipFuncSetAttribute((const void *)&k_fr_gemm<DB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return NF_OK;
-  }));
+  NF_TRY(nf_lds_once<&k_fr_gemm<DB>>(ctx, lds));
   ProfScope ps(ctx, "fr_gemm");
   hipLaunchKernelGGL(k_fr_gemm<DB>, dim3((unsigned)((N + 31) / 32)), dim3(FR_BLOCK), lds, ctx->stream, d, N, Lm, trans, sub, add, Ld,
                      lsign, in, in_tiled, out, out_tiled, ladj);
@@ -514,11 +509,7 @@ template <int DB>
 static int fr_bwd_db(nf_ctx *ctx, int d, long N, int grid, const float *L, const float *x, int x_tiled, const float *ybar,
                      int y_tiled, const float *lbar, float lbar_const, float *slabs) {
   const size_t lds = (size_t)(2 * FrGeo<DB>::TILE) * sizeof(float);
-  static AttrOnce attr_once;
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    NF_HIP(hipFuncSetAttribute((const void *)&k_fr_bwd<DB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return NF_OK;
-  }));
+  NF_TRY(nf_lds_once<&k_fr_bwd<DB>>(ctx, lds));
   ProfScope ps(ctx, "fr_bwd");
   hipLaunchKernelGGL(k_fr_bwd<DB>, dim3((unsigned)grid), dim3(FR_BLOCK), lds, ctx->stream, d, N, (N + 31) / 32, L, x, x_tiled, ybar,
                      y_tiled, lbar, lbar_const, slabs);
@@ -529,11 +520,7 @@ template <int DB>
 static int fr_bwd_x_db(nf_ctx *ctx, int d, long N, int grid, const float *L, const float *x, const float *ybar, const float *lbar,
                        float lbar_const, float *slabs, float *xbar) {
   const size_t lds = (size_t)(2 * FrGeo<DB>::TILE + FR_WAVES * FrGeo<DB>::IMG) * sizeof(float);
-  static AttrOnce attr_once;
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    NF_HIP(hipFuncSetAttribute((const void *)&k_fr_bwd_x<DB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return NF_OK;
-  }));
+  NF_TRY(nf_lds_once<&k_fr_bwd_x<DB>>(ctx, lds));
   ProfScope ps(ctx, "fr_bwd_x");
   hipLaunchKernelGGL(k_fr_bwd_x<DB>, dim3((unsigned)grid), dim3(FR_BLOCK), lds, ctx->stream, d, N, (N + 31) / 32, L, x, ybar, lbar,
                      lbar_const, slabs, xbar);

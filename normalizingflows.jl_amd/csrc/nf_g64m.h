@@ -673,11 +673,7 @@ static bool g64m_nsf_ok(const nf_flow_desc *desc) {
 template <class G>
 static int g64m_launch_apply(nf_ctx *ctx, const G64Args &a, int inverse, const double *theta, const double *x, double *y, double *ladj) {
   const size_t lds = G::apply_lds(2);
-  static AttrOnce attr_once;
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    NF_HIP(hipFuncSetAttribute((const void *)k_g64m_apply<G>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return NF_OK;
-  }));
+  NF_TRY(nf_lds_once<k_g64m_apply<G>>(ctx, lds));
   // as many workgroups as the device holds at once (a workgroup stages both nets' images: a second round of workgroups pays
   // that again -- at d = 64 one workgroup fits a CU, and 2 num_cu of them ran as two rounds)
   const long ngroups = ((a.N + 15) / 16 + 3) / 4;
@@ -690,11 +686,7 @@ static int g64m_launch_apply(nf_ctx *ctx, const G64Args &a, int inverse, const d
 static int g64m_nsf_launch_apply(nf_ctx *ctx, const G64Args &a, int inverse, const double *theta, const double *x, double *y, double *ladj) {
   using G = G64MN;
   const size_t lds = (size_t)(G::img_size(2) + 4 * G::TILE) * 8;
-  static AttrOnce attr_once;
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    NF_HIP(hipFuncSetAttribute((const void *)k_g64m_nsf_apply<G>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return NF_OK;
-  }));
+  NF_TRY(nf_lds_once<k_g64m_nsf_apply<G>>(ctx, lds));
   const long ngroups = ((a.N + 15) / 16 + 3) / 4;
   long grid = ngroups < (long)ctx->num_cu ? ngroups : (long)ctx->num_cu;
   if (grid < 1) grid = 1;
@@ -705,11 +697,7 @@ static int g64m_nsf_launch_bwd(nf_ctx *ctx, const G64Args &a, int inv, const dou
                                double lbar_const, double *slabs, long Pc, long slab_off, unsigned grid) {
   using G = G64MN;
   const size_t lds = G::bwd_lds(2);
-  static AttrOnce attr_once;
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    NF_HIP(hipFuncSetAttribute((const void *)k_g64m_bwd<G, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return NF_OK;
-  }));
+  NF_TRY((nf_lds_once<k_g64m_bwd<G, true>>(ctx, lds)));
   hipLaunchKernelGGL((k_g64m_bwd<G, true>), dim3(grid), dim3(256), lds, ctx->stream, a, inv, theta, x, gbar, lbar, lbar_const, slabs, Pc, slab_off,
                      (long long *)ctx->trace);
   return (int)hipGetLastError();
@@ -718,11 +706,7 @@ template <class G>
 static int g64m_launch_bwd(nf_ctx *ctx, const G64Args &a, int inv, const double *theta, const double *x, double *gbar, const double *lbar,
                            double lbar_const, double *slabs, long Pc, long slab_off, unsigned grid) {
   const size_t lds = G::bwd_lds(2);
-  static AttrOnce attr_once;
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    NF_HIP(hipFuncSetAttribute((const void *)k_g64m_bwd<G>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return NF_OK;
-  }));
+  NF_TRY(nf_lds_once<k_g64m_bwd<G>>(ctx, lds));
   hipLaunchKernelGGL((k_g64m_bwd<G>), dim3(grid), dim3(256), lds, ctx->stream, a, inv, theta, x, gbar, lbar, lbar_const, slabs, Pc, slab_off,
                      (long long *)ctx->trace);
   return (int)hipGetLastError();

@@ -19,6 +19,7 @@
 #include <cstdlib>
 
 #include "nf_common.h"
+#include "nf_launchers.h"
 
 // Two size classes (per-thread scratch arrays are sized at compile time): SMALL keeps the shapes such flows are
 // normally used at cheap, LARGE takes the general kernels to the d <= 256 / hidden <= 256 envelope of the MFMA paths
@@ -1912,8 +1913,6 @@ static unsigned g64_bwd_blocks(const nf_flow_desc *desc, long N) {
 static size_t g64_slab_bytes(const nf_flow_desc *desc, long N) {
   return (((size_t)g64_bwd_blocks(desc, N) * g64_coupling_params(desc) * sizeof(double)) + 255) / 256 * 256;  // sized for f64
 }
-int nf_launch_reduce_slabs(nf_ctx *, int, const void *, int, long, void *);
-
 // reverse kernel of coupling k (partial gradients into `slabs`) + the ordered sum of the slabs into g[theta_off ...]
 template <class T>
 static int g64_launch_bwd(nf_ctx *ctx, const nf_flow_desc *desc, int k, const G64Args &a, int inv, const T *theta,
@@ -1956,7 +1955,6 @@ static int g64_launch_bwd(nf_ctx *ctx, const nf_flow_desc *desc, int k, const G6
 }
 
 // ---- l64 host side ---------------------------------------------------------------------------------------------
-int nf_wimg_reserve(nf_ctx *ctx, size_t bytes);
 static inline int l64_pad32(int n) { return (n + 31) / 32 * 32; }
 static bool l64_ok(const nf_flow_desc *desc) {
   constexpr bool off = false;  // (round 6: the NF_G64_NO_MFMA A/B switch is retired -- its question is answered, README "switches")
@@ -2065,11 +2063,7 @@ static int l64_nets_merge(const G64Args &a, const L64Bufs &b) {
 template <int IB, int OB>
 static int l64_fwd_all_launch(nf_ctx *ctx, unsigned grid, size_t lds, const float *theta, const L64Layer &L, int NG, const L64Src &src,
                               float *dst, int Fd, long N, int act, int ny, const L64Y &yy) {
-  static AttrOnce attr_once;
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    NF_HIP(hipFuncSetAttribute((const void *)k_l64_fwd_all<IB, OB>, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-    return NF_OK;
-  }));
+  NF_TRY((nf_lds_once<k_l64_fwd_all<IB, OB>>(ctx, 144 * 1024)));
   hipLaunchKernelGGL((k_l64_fwd_all<IB, OB>), dim3(grid, ny), dim3(512), lds, ctx->stream, theta, L, NG, src, dst, Fd, N, act, yy);
   return (int)hipGetLastError();
 }
@@ -2108,11 +2102,7 @@ static int l64_nets_fwd(nf_ctx *ctx, const nf_flow_desc *desc, const G64Args &a,
       const L64Src src{x, 0, 0, a.d, 1 - a.par_t};
       const L64Y yy{ny == 2 ? a.net[1].w[0] - a.net[0].w[0] : 0, 0, ny == 2 ? b.act[1][0] - b.act[0][0] : 0, 0};
       const size_t lds = (size_t)lc * (64 * (64 + NF_IMG_PAD) + 64) * sizeof(float);
-      static AttrOnce attr_once;
-      NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-        NF_HIP(hipFuncSetAttribute((const void *)k_l64_fwd_chain, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-        return NF_OK;
-      }));
+      NF_TRY(nf_lds_once<k_l64_fwd_chain>(ctx, 144 * 1024));
       const unsigned grid8 = (unsigned)std::min<long>(((a.N + 31) / 32 + 7) / 8, 2L * ctx->num_cu);
       ProfScope ps(ctx, "l64_fwd");
       hipLaunchKernelGGL(k_l64_fwd_chain, dim3(grid8, ny), dim3(512), lds, ctx->stream, theta, ch, src, a.N, yy);
@@ -2192,11 +2182,7 @@ template <int IB, int OB>
 static int l64_dw_launch(nf_ctx *ctx, unsigned grid, const L64Layer &L, const L64Src &av, const L64Src &g, const float *act, int Fa, long N,
                          float *slabs, long Pc, long slab_off, int ny, const L64Y &yy) {
   const size_t lds = (size_t)4 * (IB + OB) * 32 * NF_TS * sizeof(float);
-  static AttrOnce attr_once;
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    NF_HIP(hipFuncSetAttribute((const void *)k_l64_dw<IB, OB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return NF_OK;
-  }));
+  NF_TRY((nf_lds_once<k_l64_dw<IB, OB>>(ctx, lds)));
   hipLaunchKernelGGL((k_l64_dw<IB, OB>), dim3(grid, ny), dim3(256), lds, ctx->stream, L, av, g, act, Fa, N, slabs, Pc, slab_off, yy);
   return (int)hipGetLastError();
 }
@@ -2204,22 +2190,14 @@ template <int IB, int OB>
 static int l64_dw_cols_launch(nf_ctx *ctx, unsigned grid, const L64Layer &L, const L64Src &av, const L64Src &g, const float *act, int Fa, long N,
                               float *slabs, long Pc, long slab_off, int ny, const L64Y &yy) {
   const size_t lds = (size_t)(IB + 4 * OB) * 32 * NF_TS * sizeof(float);
-  static AttrOnce attr_once;
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    NF_HIP(hipFuncSetAttribute((const void *)k_l64_dw_cols<IB, OB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return NF_OK;
-  }));
+  NF_TRY((nf_lds_once<k_l64_dw_cols<IB, OB>>(ctx, lds)));
   hipLaunchKernelGGL((k_l64_dw_cols<IB, OB>), dim3(grid, ny), dim3(256), lds, ctx->stream, L, av, g, act, Fa, N, slabs, Pc, slab_off, yy);
   return (int)hipGetLastError();
 }
 template <int IB, int OB>
 static int l64_bwdx_all_launch(nf_ctx *ctx, unsigned grid, size_t lds, const float *theta, const L64Layer &L, int NG, const L64Src &g,
                                const float *act, int Fa, float *dst, int Fd, int xd, int xpar, long N, int ny, const L64Y &yy) {
-  static AttrOnce attr_once;
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    NF_HIP(hipFuncSetAttribute((const void *)k_l64_bwdx_all<IB, OB>, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-    return NF_OK;
-  }));
+  NF_TRY((nf_lds_once<k_l64_bwdx_all<IB, OB>>(ctx, 144 * 1024)));
   hipLaunchKernelGGL((k_l64_bwdx_all<IB, OB>), dim3(grid, ny), dim3(512), lds, ctx->stream, theta, L, NG, g, act, Fa, dst, Fd, xd, xpar, N, yy);
   return (int)hipGetLastError();
 }
@@ -2372,11 +2350,7 @@ static int l64_bwd(nf_ctx *ctx, const nf_flow_desc *desc, int k, const G64Args &
           const L64Src gtop{gsrc, Fg, 0, 0, 0};
           const L64Y yc{dth, dgs, nym == 2 ? b.act[1][0] - b.act[0][0] : 0, nym == 2 ? b.gh[1][0] - b.gh[0][0] : 0};
           const size_t lds = (size_t)ct * (64 * (64 + NF_IMG_PAD) + 64) * sizeof(float);
-          static AttrOnce attr_once;
-          NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-            NF_HIP(hipFuncSetAttribute((const void *)k_l64_bwdx_chain, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-            return NF_OK;
-          }));
+          NF_TRY(nf_lds_once<k_l64_bwdx_chain>(ctx, 144 * 1024));
           const unsigned grid8 = (unsigned)std::min<long>(((a.N + 31) / 32 + 7) / 8, 2L * ctx->num_cu);
           ProfScope ps(ctx, "l64_bwdx");
           hipLaunchKernelGGL(k_l64_bwdx_chain, dim3(grid8, nym), dim3(512), lds, ctx->stream, theta, ch, gtop, b.GH, a.N, yc);

@@ -13,6 +13,7 @@
 // One thread per sample, standard layout, Float32 and Float64 (the demo recommends Float64: the
 // dynamics is chaotic).  Small problems by nature (the demo: D = 2, 15 blocks, 16 samples per step).
 #include "nf_common.h"
+#include "nf_launchers.h"
 
 #define HF_MAXD 32  // position dimensions (joint dimension 2D <= 64)
 #define HF_MAXL 16  // leapfrog steps per block
@@ -351,7 +352,6 @@ static inline size_t hf_stash_bytes(const nf_flow_desc *desc, long N) { return (
 size_t nf_hf_bwd_ws_bytes(const nf_flow_desc *desc, long N) {
   return hf_stash_bytes(desc, N) + (size_t)hf_bwd_grid(N) * (size_t)hf_param_count(desc) * sizeof(double);
 }
-int nf_launch_reduce_slabs(nf_ctx *ctx, int dtype, const void *slab, int nslab, long P, void *g);
 // dynamic LDS beyond the default 64 KiB has to be asked for, once per kernel and device
 template <class T>
 static int hf_bwd_opt_in(nf_ctx *ctx) {

@@ -603,7 +603,7 @@ static int launch_tiled(const TgtTiledArgs &a) {
   const size_t lds = (size_t)(LpGeo<DB>::FLOATS + (FORM == LP_DISP ? LP_WAVES * 64 + 2 * LP_BLOCK : 0)) * sizeof(float);
   constexpr auto kern = tiled_kernel<DB, PHI, FORM>();
   nf_ctx *ctx = a.ctx;
-  NF_TRY(tgt_lds_once<kern>(ctx, lds));
+  NF_TRY(nf_lds_once<kern>(ctx, lds));
   const LinpredConsts k = linpred_consts(a.t, a.d);
   ProfScope ps(ctx, "target_linpred");
   if constexpr (FORM == LP_HIER || FORM == LP_DISP)
@@ -617,7 +617,7 @@ static int launch_flat(const TgtFlatArgs &a) {
   const size_t lds = (size_t)((LPF_SPB + LPF_RB) * (a.d + 1) + LPF_SPB * (LPF_RB + 1)) * sizeof(T);
   constexpr auto kern = flat_kernel<T, PHI, FORM>();
   nf_ctx *ctx = a.ctx;
-  NF_TRY(tgt_lds_once<kern>(ctx, (size_t)((LPF_SPB + LPF_RB) * (LPF_MAXD + 1) + LPF_SPB * (LPF_RB + 1)) * sizeof(T)));
+  NF_TRY(nf_lds_once<kern>(ctx, (size_t)((LPF_SPB + LPF_RB) * (LPF_MAXD + 1) + LPF_SPB * (LPF_RB + 1)) * sizeof(T)));
   const LinpredConsts k = linpred_consts(a.t, a.d);
   ProfScope ps(ctx, "target_linpred");
   if constexpr (FORM == LP_HIER || FORM == LP_DISP)

@@ -99,6 +99,12 @@ __device__ __forceinline__ unsigned nf_sign_mask16(const f32x16 &v) {
   asm volatile("" : "+v"(bits));
   return bits;
 }
+// the masks of a layer's NB blocks
+template <int NB>
+__device__ __forceinline__ void sign_masks(const f32x16 (&v)[NB], unsigned (&m)[NB]) {
+#pragma unroll
+  for (int b = 0; b < NB; ++b) m[b] = nf_sign_mask16(v[b]);
+}
 // slope of element r from the packed mask: sign-extend its bit (v_bfe_i32 -> 0 / -1) and blend the two constants'
 // bit patterns with it (v_bfi_b32): two instructions, no VCC round trip (the select form costs v_and + v_cmp + s_nop +
 // v_cndmask per element)

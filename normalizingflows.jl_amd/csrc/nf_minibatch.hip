@@ -20,6 +20,7 @@
 // accesses when the row pitch and both bases allow, scalar accesses otherwise -- and all workgroups share the fixed segments.  Every
 // output element has exactly one writer: no atomics, the same bits on every launch; row addresses are 64-bit.
 #include "nf_common.h"
+#include "nf_launchers.h"
 #include "nf_philox.h"
 #include "nf_targets.h"
 
@@ -103,8 +104,6 @@ __global__ __launch_bounds__(MB_BLOCK) void k_minibatch_gather(MbTable tab, long
     }
   }
 }
-
-int nf_target_check(const nf_target *t, int d);  // nf_elementwise.hip
 
 // The segment table of a kind at (d, s1), with the table length of the negative-binomial kind left at 0, and the row width w of p1.
 // false: the kind has no per-row weight, or its rows are not exchangeable.

@@ -326,7 +326,7 @@ template <int DB>
 static int launch_mixture_tiled(const TgtTiledArgs &a) {
   const size_t lds = (size_t)MxGeo<DB>::FLOATS * sizeof(float);
   nf_ctx *ctx = a.ctx;
-  NF_TRY(tgt_lds_once<k_target_mixture_tiled<DB>>(ctx, lds));
+  NF_TRY(nf_lds_once<k_target_mixture_tiled<DB>>(ctx, lds));
   ProfScope ps(ctx, "target_mixture");
   return tgt_launch_tiled<k_target_mixture_tiled<DB>>(a, lds, a.d, (int)a.t->s0, a.N, a.yt, (const float *)a.t->p0, (const float *)a.t->p1);
 }
@@ -341,7 +341,7 @@ template <class T>
 static int launch_mixture_flat(const TgtFlatArgs &a) {
   const size_t most = (size_t)((MXF_SPB + MXF_RB) * (MXF_MAXD + 1) + MXF_SPB * (MXF_RB + 1)) * sizeof(T);
   nf_ctx *ctx = a.ctx;
-  NF_TRY(tgt_lds_once<k_target_mixture<T>>(ctx, most));
+  NF_TRY(nf_lds_once<k_target_mixture<T>>(ctx, most));
   ProfScope ps(ctx, "target_mixture");
   return tgt_launch_flat<k_target_mixture<T>, T>(a, (size_t)((MXF_SPB + MXF_RB) * (a.d + 1) + MXF_SPB * (MXF_RB + 1)) * sizeof(T), a.d,
                                                  (int)a.t->s0, a.N, (const T *)a.y, (const T *)a.t->p0, (const T *)a.t->p1);

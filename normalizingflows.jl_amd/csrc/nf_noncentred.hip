@@ -23,14 +23,11 @@
 // for the cotangent (k_nc_pull_flat), one thread per parameter and sample chunk for lambar (k_nc_grad_flat); their y is the
 // forward's arithmetic run again from z in the element type, hence the same bits.
 #include "nf_common.h"
+#include "nf_launchers.h"
 #include "nf_linpred.h"
 
 #define NC_BLOCK 256
 #define NC_MAXD 256  // widest tiled batch (the tiled inner flows stop there too)
-
-int nf_launch_reduce_slabs(nf_ctx *, int, const void *, int, long, void *);
-int nf_launch_fill(nf_ctx *, int, void *, long, double);
-int nf_fr_bwd_grid(nf_ctx *, long N);
 
 // group of coefficient j, or -1; lam_j where it is used, 0 where it is not (by select: whatever theta holds there)
 template <class T>

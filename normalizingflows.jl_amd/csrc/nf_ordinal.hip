@@ -434,7 +434,7 @@ static int launch_ordinal_tiled(const TgtTiledArgs &a) {
   using G = OrGeo<DB>;
   const int C = (int)a.t->s1, p = a.d - (C - 1);
   nf_ctx *ctx = a.ctx;
-  NF_TRY(tgt_lds_once<k_target_ordinal_tiled<DB>>(ctx, G::floats(G::PMAX) * sizeof(float)));
+  NF_TRY(nf_lds_once<k_target_ordinal_tiled<DB>>(ctx, G::floats(G::PMAX) * sizeof(float)));
   ProfScope ps(ctx, "target_ordinal");
   return tgt_launch_tiled<k_target_ordinal_tiled<DB>>(a, (size_t)G::floats(p) * sizeof(float), a.d, C, (int)a.t->s0, a.N, a.yt,
                                                       (const float *)a.t->p0, (const float *)a.t->p1);
@@ -454,7 +454,7 @@ template <class T>
 static int launch_ordinal_flat(const TgtFlatArgs &a) {
   const int C = (int)a.t->s1;
   nf_ctx *ctx = a.ctx;
-  NF_TRY(tgt_lds_once<k_target_ordinal<T>>(ctx, ordinal_flat_lds(OR_MAXD, OR_MAXD - 1) * sizeof(T)));  // the most any served target takes
+  NF_TRY(nf_lds_once<k_target_ordinal<T>>(ctx, ordinal_flat_lds(OR_MAXD, OR_MAXD - 1) * sizeof(T)));  // the most any served target takes
   ProfScope ps(ctx, "target_ordinal");
   return tgt_launch_flat<k_target_ordinal<T>, T>(a, ordinal_flat_lds(a.d, a.d - (C - 1)) * sizeof(T), a.d, C, (int)a.t->s0, a.N, (const T *)a.y,
                                                  (const T *)a.t->p0, (const T *)a.t->p1);

@@ -4,6 +4,7 @@
 #pragma once
 #include "nf_common.h"
 #include "nf_mfma.h"
+#include "nf_net_stages.h"
 
 // ------------------------------------------------------------------------------------
 // weight packing: theta -> padded LDS images, one per (coupling, net), once per call
@@ -121,24 +122,14 @@ __global__ __launch_bounds__(64 * NF_REDUCE_WAVES) void k_reduce_image_slabs(Pac
                                                             float *__restrict__ lout) {
   if (lout && blockIdx.x == 0) {
     __shared__ double sm[NF_REDUCE_WAVES];
-    double c = 0.0;
-    for (int i = threadIdx.x; i < nlpart; i += 64 * NF_REDUCE_WAVES) c += lpart[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      double t = 0.0;
-      for (int w = 0; w < NF_REDUCE_WAVES; ++w) t += sm[w];
-      *lout = (float)t;
-    }
+    net_finish_partials<NF_REDUCE_WAVES, false>(lpart, nlpart, sm, lout);
   }
   // 64 image elements per block, the slabs split over the block's waves (a streaming kernel of 139 MB at cfg 2:
   // with one element per thread over all slabs only ~8 waves per CU were in flight and it ran at 3.4 TB/s)
   __shared__ float part[NF_REDUCE_WAVES][64];
   const int lane = threadIdx.x & 63, q = threadIdx.x >> 6;
   const long gid = (long)blockIdx.x * 64 + lane;
-  const long total = (long)p.ncoup * 2 * G::SIZE;
+  const long total = (long)p.ncoup * 2 * G::SIZE;  // gid -> theta index, in place in all three kernels: no shared form leaves them all identical
   long ti = -1;
   if (gid < total) {
     const int img = (int)(gid / G::SIZE), e = (int)(gid - (long)img * G::SIZE);
@@ -149,7 +140,7 @@ __global__ __launch_bounds__(64 * NF_REDUCE_WAVES) void k_reduce_image_slabs(Pac
     const NetDims nd = make_net_dims(off, m, p.h1, p.h2, c);
     ti = e < G::B3 + 32 * G::CB ? image_theta_index<G>(nd, e) : -1;
   }
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;  // the slab sum, in place here and in the epilogue: as a shared call it reorders / changes them
   if (ti >= 0) {  // wave q sums slabs q, q + W, q + 2 W, ...
     constexpr int W = NF_REDUCE_WAVES;
     int s = q;
@@ -163,12 +154,7 @@ __global__ __launch_bounds__(64 * NF_REDUCE_WAVES) void k_reduce_image_slabs(Pac
   }
   part[q][lane] = (a0 + a1) + (a2 + a3);
   __syncthreads();
-  if (q == 0 && ti >= 0) {
-    float t = 0.f;
-#pragma unroll
-    for (int w = 0; w < NF_REDUCE_WAVES; ++w) t += part[w][lane];
-    g[ti] = t;
-  }
+  if (q == 0 && ti >= 0) g[ti] = net_part_sum<NF_REDUCE_WAVES, false>(part, lane);
 }
 
 // ------------------------------------------------------------------------------------
@@ -201,7 +187,7 @@ struct EpiArgs {
 
 template <class G, bool REDUCE, bool ADAM, int WAVES>
 __global__ __launch_bounds__(64 * WAVES) void k_affine_epilogue(PackArgs p, EpiArgs a) {
-  if (REDUCE && a.lpart && blockIdx.x == 0) {
+  if (REDUCE && a.lpart && blockIdx.x == 0) {  // net_finish_partials, in place: with a.g + a.P as an argument the kernel changes
     __shared__ double sm[WAVES];
     double c = 0.0;
     for (int i = threadIdx.x; i < a.nlpart; i += 64 * WAVES) c += a.lpart[i];
@@ -218,7 +204,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_affine_epilogue(PackArgs p, EpiA
   __shared__ float part[WAVES][64];
   const int lane = threadIdx.x & 63, q = threadIdx.x >> 6;
   const long gid = (long)blockIdx.x * 64 + lane;
-  const long total = (long)p.ncoup * 2 * G::SIZE;
+  const long total = (long)p.ncoup * 2 * G::SIZE;  // gid -> theta index, in place in all three kernels: no shared form leaves them all identical
   long ti = -1;
   if (gid < total) {
     const int img = (int)(gid / G::SIZE), e = (int)(gid - (long)img * G::SIZE);
@@ -263,10 +249,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_affine_epilogue(PackArgs p, EpiA
     }
     part[q][lane] = (a0 + a1) + (a2 + a3);
     __syncthreads();
-    if (q == 0) {
-#pragma unroll
-      for (int w = 0; w < WAVES; ++w) gsum += part[w][lane];
-    }
+    if (q == 0) gsum = net_part_sum<WAVES, false>(part, lane);
   } else if (q == 0 && ti >= 0) {
     gsum = a.g[ti];
   }
@@ -275,7 +258,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_affine_epilogue(PackArgs p, EpiA
   if (ti >= 0) {
     if (REDUCE) a.g[ti] = gsum;
     if (ADAM) {
-      float c1 = a.c1, c2 = a.c2;
+      float c1 = a.c1, c2 = a.c2;  // the Adam tail of k_rqs_epilogue, in place: as a shared call it changes both epilogues
       if (a.t_ptr) {  // graph replay: the step count lives on the device
         const double t = (double)(*a.t_ptr + 1u);
         c1 = (float)(1.0 - pow(a.b1d, t));

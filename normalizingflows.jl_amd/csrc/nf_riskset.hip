@@ -573,7 +573,7 @@ static int launch_riskset_tiled(const TgtTiledArgs &a) {
   using G = RsGeo<DB>;
   const int R = (int)a.t->s0;
   nf_ctx *ctx = a.ctx;
-  NF_TRY(tgt_lds_once<k_target_riskset_tiled<DB>>(ctx, G::floats(G::PMAX, NF_RISKSET_MAXR) * sizeof(float)));
+  NF_TRY(nf_lds_once<k_target_riskset_tiled<DB>>(ctx, G::floats(G::PMAX, NF_RISKSET_MAXR) * sizeof(float)));
   ProfScope ps(ctx, "target_riskset");
   return tgt_launch_tiled<k_target_riskset_tiled<DB>>(a, (size_t)G::floats(a.d, R) * sizeof(float), a.d, R, a.N, a.yt, (const float *)a.t->p0,
                                                       (const float *)a.t->p1);
@@ -593,7 +593,7 @@ template <class T>
 static int launch_riskset_flat(const TgtFlatArgs &a) {
   const int R = (int)a.t->s0;
   nf_ctx *ctx = a.ctx;
-  NF_TRY(tgt_lds_once<k_target_riskset<T>>(ctx, riskset_flat_lds(RS_MAXD, NF_RISKSET_MAXR) * sizeof(T)));  // the most any served target takes
+  NF_TRY(nf_lds_once<k_target_riskset<T>>(ctx, riskset_flat_lds(RS_MAXD, NF_RISKSET_MAXR) * sizeof(T)));  // the most any served target takes
   ProfScope ps(ctx, "target_riskset");
   return tgt_launch_flat<k_target_riskset<T>, T>(a, riskset_flat_lds(a.d, R) * sizeof(T), a.d, R, a.N, (const T *)a.y, (const T *)a.t->p0,
                                                  (const T *)a.t->p1);

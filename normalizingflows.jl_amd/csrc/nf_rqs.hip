@@ -23,7 +23,9 @@
 #include <type_traits>
 
 #include "nf_common.h"
+#include "nf_launchers.h"
 #include "nf_mfma.h"
+#include "nf_net_stages.h"
 // k_rqs_bwd_coop6's matrix instructions on the wave's weight triples.  Round 6 tried them as inline asm with the A operand in
 // the accumulation half of the register file (what VERDICT r5 item 2 asked for: hipcc keeps the 144 weight registers there
 // and copies each operand into architectural registers next to the MFMA that reads it -- 289 v_accvgpr_read in the kernel):
@@ -35,8 +37,6 @@
 // chain) was evidently not the whole set.  Not shipped: the builtin (nf_mfma_bf16), whose hazards the compiler handles.
 #include "nf_philox.h"
 #include "nf_target_epilogue.h"
-
-int nf_target_check(const nf_target *t, int d);  // nf_elementwise.hip
 
 template <int MB_, int H1B_, int H2B_, int K_, int NCH_, int QCH_ = 2>
 struct RqsGeo {
@@ -155,7 +155,7 @@ __global__ __launch_bounds__(256) void k_rqs_reduce_slabs(RqsPackArgs p, const f
     const int k = (int)(gid / G::SIZE), e = (int)(gid - (long)k * G::SIZE);
     ti = rqs_image_theta_index<G>(rqs_dims_of<G>(p, k), e);
   }
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;  // the slab sum of all five slab kernels, in place: as a shared call it reorders or changes them
   if (ti >= 0) {  // wave q sums slabs q, q + 4, q + 8, ...
     int s = q;
     for (; s + 12 < nslab; s += 16) {
@@ -168,7 +168,7 @@ __global__ __launch_bounds__(256) void k_rqs_reduce_slabs(RqsPackArgs p, const f
   }
   part[q][lane] = (a0 + a1) + (a2 + a3);
   __syncthreads();
-  if (q == 0 && ti >= 0) g[ti] = (part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]);
+  if (q == 0 && ti >= 0) g[ti] = net_part_sum<4, true>(part, lane);
 }
 
 // The fused epilogue of nf_elbo_step for spline couplings (round 6; the structure of k_affine_epilogue, nf_pack.h): every thread of
@@ -191,7 +191,7 @@ struct RqsEpiArgs {
 };
 template <class G>
 __global__ __launch_bounds__(256) void k_rqs_epilogue(RqsPackArgs p, RqsEpiArgs a) {
-  if (a.lpart && blockIdx.x == 0) {
+  if (a.lpart && blockIdx.x == 0) {  // net_finish_partials, in place: with a.g + a.P as an argument the kernel changes
     __shared__ double sm[4];
     double c = 0.0;
     for (int i = threadIdx.x; i < a.nlpart; i += 256) c += a.lpart[i];
@@ -215,7 +215,7 @@ __global__ __launch_bounds__(256) void k_rqs_epilogue(RqsPackArgs p, RqsEpiArgs 
     mi = a.m[ti];
     vi = a.v[ti];
   }
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;  // (in place, as there)
   if (ti >= 0) {  // wave q sums slabs q, q + 4, q + 8, ... (k_rqs_reduce_slabs)
     int s = q;
     for (; s + 12 < a.nslab; s += 16) {
@@ -231,9 +231,9 @@ __global__ __launch_bounds__(256) void k_rqs_epilogue(RqsPackArgs p, RqsEpiArgs 
   if (q != 0) return;
   double gg = 0.0;
   if (ti >= 0) {
-    const float gsum = (part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]);
+    const float gsum = net_part_sum<4, true>(part, lane);
     a.g[ti] = gsum;
-    float c1 = a.c1, c2 = a.c2;
+    float c1 = a.c1, c2 = a.c2;  // the Adam tail of k_affine_epilogue, in place: as a shared call it changes both epilogues
     if (a.t_ptr) {  // graph replay: the step count lives on the device
       const double t = (double)(*a.t_ptr + 1u);
       c1 = (float)(1.0 - pow(a.b1d, t));
@@ -492,7 +492,7 @@ __device__ __forceinline__ void rqs_chain_body(RqsChainArgs a, float *xt, float 
   constexpr int TP = 64 * G::CB;
   float *tmu = lds + CL::WAREA, *tiv = tmu + TP, *tc0 = tiv + TP;
   double *wsum = reinterpret_cast<double *>(tc0 + 2);  // [8] per-wave partial sums (G::SIZE and TP are even)
-  if (FUSED && !FKL && !TGT) {
+  if (FUSED && !FKL && !TGT) {  // as in affine_chain_body, in place: as a shared call it changes the fused k_rqs_chain forms
     for (int i = tid; i < TP; i += 64 * NW) {
       tmu[i] = i < a.d ? fa.mu[i] : 0.f;
       tiv[i] = i < a.d ? 1.f / fa.var[i] : 0.f;
@@ -528,7 +528,7 @@ __device__ __forceinline__ void rqs_chain_body(RqsChainArgs a, float *xt, float 
     const TileIO io = make_tile_io(xt, tl, a.d, l31, hi);
     f32x16 E[G::CB], O[G::MB];
     float zz = 0.f;  // FUSED: this lane's share of ||x||^2
-    if constexpr (FKL) {
+    if constexpr (FKL) {  // (chain_load_ys and chain_draw_base would be these two arms; as calls they change the fused kernels)
       // ys[j * d + f] through one descriptor per tile that spans exactly the tile's samples (as k_affine_chain's forward-KL
       // mode): padding samples read 0 from the hardware, features >= d are zeroed here; the whole offset is per lane
       const long nv = a.N - tl * NF_TILE;
@@ -547,15 +547,7 @@ __device__ __forceinline__ void rqs_chain_body(RqsChainArgs a, float *xt, float 
           O[b][r] = valid && f + 1 < a.d ? o : 0.f;
         }
     } else if (!FUSED) {
-#pragma unroll
-      for (int b = 0; b < G::CB; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float e = tile_load(io, tile_soff(b, r, 0));
-          const float o = tile_load(io, tile_soff(b, r, 1));
-          E[b][r] = valid ? e : 0.f;
-          O[b][r] = valid ? o : 0.f;
-        }
+      chain_load_tile(E, O, io, valid);
     } else {
       // registers (b, 4q..4q+3) of E and O are features base..base+7, base = 64b + 16q + 8hi:
       // Philox groups base/4 (-> E0 O0 E1 O1) and base/4 + 1 (-> E2 O2 E3 O3)
@@ -589,11 +581,8 @@ __device__ __forceinline__ void rqs_chain_body(RqsChainArgs a, float *xt, float 
 #ifdef NF_KERNEL_TRACE
     const int gidx = (int)((grp - blockIdx.x) / gridDim.x);
     long long *trc = (a.trace && blockIdx.x == 0 && tid == 0 && gidx < 2) ? a.trace + 64 + 28 * gidx : nullptr;
-#define RC_STAMP(slot) do { if (trc) { __builtin_amdgcn_sched_barrier(0); trc[slot] = clock64(); } } while (0)
-#else
-#define RC_STAMP(slot) do { } while (0)
 #endif
-    RC_STAMP(1);  // (the draws are done; [0] is stamped at the group's top)
+    NF_STAMP(trc, 1);  // (the draws are done; [0] is stamped at the group's top)
 #pragma unroll 1
     for (int s = 0; s < a.ncoup; s += 2) {
 #pragma unroll
@@ -617,13 +606,13 @@ __device__ __forceinline__ void rqs_chain_body(RqsChainArgs a, float *xt, float 
           else
             lsum += rqs_coupling_step<G, INVERSE, B6>(img, E, O, c_odd, a.d - c_odd, a.B, l31, hi, tp, reinterpret_cast<const nf_u32x4 *>(t6));
         }
-        if (pos < 8) RC_STAMP(2 + 3 * pos);
+        if (pos < 8) NF_STAMP(trc, 2 + 3 * pos);
         __syncthreads();
-        if (pos < 8) RC_STAMP(3 + 3 * pos);
+        if (pos < 8) NF_STAMP(trc, 3 + 3 * pos);
         if constexpr (B6) {  // every wave is done with this coupling's triples: the next coupling's may come
           if (have_next) dma(t6, a.wimg6 + (long)knext * RqsB6Geo<G>::U4, CL::F_U4 * 16);
         }
-        if (pos < 8) RC_STAMP(4 + 3 * pos);
+        if (pos < 8) NF_STAMP(trc, 4 + 3 * pos);
         buf ^= 1;
       }
     }
@@ -735,7 +724,7 @@ __device__ __forceinline__ void rqs_chain_body(RqsChainArgs a, float *xt, float 
       }
       __syncthreads();
     }
-    RC_STAMP(27);
+    NF_STAMP(trc, 27);
   }
   if (FUSED && tid == 0) fa.partial[blockIdx.x] = wg_total;
 }
@@ -785,46 +774,6 @@ struct RqsLds {
   static constexpr size_t BYTES = (size_t)(G::SIZE + WAVES * SCRATCH) * sizeof(float);
 };
 
-template <int IB, int OB>
-__device__ __forceinline__ void rqs_zero(f32x16 (&a)[IB][OB], float (&b)[OB]) {
-#pragma unroll
-  for (int i = 0; i < IB; ++i)
-#pragma unroll
-    for (int o = 0; o < OB; ++o)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) a[i][o][r] = 0.f;
-#pragma unroll
-  for (int o = 0; o < OB; ++o) b[o] = 0.f;
-}
-
-template <int IB, int OB, int S>
-__device__ __forceinline__ void rqs_fold(float *__restrict__ w, float *__restrict__ b, const f32x16 (&a)[IB][OB],
-                                         const float (&bs)[OB], bool first, int l31, int hi) {
-  // a block's sixteen partial sums are read in one go, then written back: as one read-modify-write after the other every LDS
-  // round trip is exposed (round 5, tools/trace_deep_bwd.py on the same fold in nf_deep.hip)
-#pragma unroll
-  for (int i = 0; i < IB; ++i)
-#pragma unroll
-    for (int o = 0; o < OB; ++o) {
-      float *p = w + (i * 32 + 4 * hi) * S + o * 32 + l31;  // row nf_row(r, hi) = (r & 3) + 8 (r >> 2) + 4 hi
-      float old[16];
-      if (!first) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) old[r] = p[((r & 3) + 8 * (r >> 2)) * S];
-      }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) p[((r & 3) + 8 * (r >> 2)) * S] = first ? a[i][o][r] : old[r] + a[i][o][r];
-    }
-#pragma unroll
-  for (int o = 0; o < OB; ++o) {
-    const float v = bs[o] + __shfl_xor(bs[o], 32);
-    if (hi == 0) {
-      float *p = b + o * 32 + l31;
-      *p = first ? v : *p + v;
-    }
-  }
-}
-
 #define RQS_BWD_LAZY false
 #define RQS_DX3_SPLIT 2  // independent accumulators of the cooperative kernel's dX3 GEMM (1 = the single chain)
 #define RQS_COOP_LAZY true  // the cooperative kernel has the registers for the lazy knot derivatives
@@ -836,15 +785,7 @@ __device__ __forceinline__ void rqs_bwd_tile(const RqsBwdArgs &a, const float *_
                                              const float *__restrict__ lbar, float lbar_const, long tile, int l31,
                                              int hi, long long *tr) {
   using L = RqsLds<G>;
-#ifdef NF_KERNEL_TRACE
-#define RQS_STAMP(slot)                                                   \
-  do {                                                                    \
-    if (tr) { __builtin_amdgcn_sched_barrier(0); tr[slot] = clock64(); }  \
-  } while (0)
-#else
-#define RQS_STAMP(slot) do { (void)tr; } while (0)
-#endif
-  RQS_STAMP(0);
+  NF_STAMP(tr, 0);
   const long j = tile * NF_TILE + l31;
   const bool valid = j < a.N;
   const int par_c = 1 - a.par_t;
@@ -882,7 +823,7 @@ __device__ __forceinline__ void rqs_bwd_tile(const RqsBwdArgs &a, const float *_
     tile_to_scratch<G::H2B>(sc + L::OFF_A2, a2, l31, hi);
   }
   const float lb = valid ? (lbar ? lbar[j] : lbar_const) : 0.f;
-  RQS_STAMP(1);
+  NF_STAMP(tr, 1);
 
   f32x16 d2[G::H2B];
 #pragma unroll
@@ -904,7 +845,7 @@ __device__ __forceinline__ void rqs_bwd_tile(const RqsBwdArgs &a, const float *_
     }
     f32x16 out[G::OBC];
     dense_fwd<G::H2B, G::OBC, G::S3>(img + G::W3 + ch * G::OBC * 32, img + G::B3 + ch * G::OBC * 32, a2, out, l31, hi);
-    RQS_STAMP(2 + 4 * ch);
+    NF_STAMP(tr, 2 + 4 * ch);
 #pragma unroll
     for (int ql = 0; ql < G::QCH; ++ql) {
       const int q = ch * G::QCH + ql;
@@ -946,10 +887,10 @@ __device__ __forceinline__ void rqs_bwd_tile(const RqsBwdArgs &a, const float *_
     // unused slots of the chunk (beyond QCH * P) carry raw outputs of zero-weight rows: clear them
 #pragma unroll
     for (int slot = G::QCH * G::P; slot < G::OBC * 16; ++slot) out[slot / 16][slot % 16] = 0.f;
-    RQS_STAMP(3 + 4 * ch);
+    NF_STAMP(tr, 3 + 4 * ch);
     // dX through the last layer, accumulated over chunks
     dense_bwd_x<G::H2B, G::OBC, G::S3, true>(img + G::W3 + ch * G::OBC * 32, out, d2, l31, hi);
-    RQS_STAMP(4 + 4 * ch);
+    NF_STAMP(tr, 4 + 4 * ch);
     // dW3^T: two accumulator blocks of delta at a time through the scratch transpose
 #pragma unroll
     for (int pc = 0; pc < G::OBC; pc += 2) {
@@ -968,7 +909,7 @@ __device__ __forceinline__ void rqs_bwd_tile(const RqsBwdArgs &a, const float *_
       }
       wave_lds_fence();
     }
-    RQS_STAMP(5 + 4 * ch);
+    NF_STAMP(tr, 5 + 4 * ch);
   }
   // ---- layer 2
 #pragma unroll
@@ -1000,8 +941,7 @@ __device__ __forceinline__ void rqs_bwd_tile(const RqsBwdArgs &a, const float *_
   for (int b = 0; b < G::MB; ++b)
 #pragma unroll
     for (int r = 0; r < 16; ++r) tile_store(gio, tile_soff(b, r, par_c), gold[b][r] + g2[b][r]);
-  RQS_STAMP(2 + 4 * G::NCH);
-#undef RQS_STAMP
+  NF_STAMP(tr, 2 + 4 * G::NCH);
 }
 
 // reverse pass of ONE coupling by this workgroup: stage the image, walk this workgroup's tiles, fold the four waves'
@@ -1019,9 +959,9 @@ __device__ __forceinline__ void rqs_bwd_coupling(const RqsBwdArgs &a, float *__r
   stage_packed<G::SIZE, 256>(img, a.img, tid);
   __syncthreads();
   RqsAcc<G> acc;
-  rqs_zero(acc.w1, acc.b1);
-  rqs_zero(acc.w2, acc.b2);
-  rqs_zero(acc.w3, acc.b3);
+  net_zero_acc(acc.w1, acc.b1);
+  net_zero_acc(acc.w2, acc.b2);
+  net_zero_acc(acc.w3, acc.b3);
 #pragma unroll 1
   for (long tile = (long)blockIdx.x * 4 + wave; tile < ntiles; tile += (long)gridDim.x * 4)
     rqs_bwd_tile<G, INVD>(a, img, sc, acc, y, ybar, lbar, lbar_const, tile, l31, hi,
@@ -1030,9 +970,9 @@ __device__ __forceinline__ void rqs_bwd_coupling(const RqsBwdArgs &a, float *__r
 #pragma unroll 1
   for (int w = 0; w < 4; ++w) {
     if (wave == w) {
-      rqs_fold<G::MB, G::H1B, G::S1>(img + G::W1, img + G::B1, acc.w1, acc.b1, w == 0, l31, hi);
-      rqs_fold<G::H1B, G::H2B, G::S2>(img + G::W2, img + G::B2, acc.w2, acc.b2, w == 0, l31, hi);
-      rqs_fold<G::H2B, G::OB3, G::S3>(img + G::W3, img + G::B3, acc.w3, acc.b3, w == 0, l31, hi);
+      net_fold_acc<G::MB, G::H1B, G::S1>(img + G::W1, img + G::B1, acc.w1, acc.b1, w == 0, l31, hi);
+      net_fold_acc<G::H1B, G::H2B, G::S2>(img + G::W2, img + G::B2, acc.w2, acc.b2, w == 0, l31, hi);
+      net_fold_acc<G::H2B, G::OB3, G::S3>(img + G::W3, img + G::B3, acc.w3, acc.b3, w == 0, l31, hi);
     }
     __syncthreads();
   }
@@ -1052,9 +992,6 @@ __global__ __launch_bounds__(256, 1) void k_rqs_bwd(RqsBwdArgs a, float *__restr
   rqs_bwd_coupling<G, INVD>(a, y, ybar, lbar, lbar_const, slab, slab_stride, lds);
 }
 
-// The whole chain's reverse pass in ONE launch (the structure of k_affine_bwd_all, nf_coupling.hip): a wave's tiles
-// never change hands and coupling k + 1 only reads what the same wave wrote for coupling k (y <- x, ybar <- xbar),
-// so each workgroup walks the couplings on its own -- seven launch gaps and ramp-up / tail phases less per step.
 // ---------------------------------------------------------------------------------------
 // reverse pass of one coupling, COOPERATIVE form (geometries with NCH == 4 chunks)
 // ---------------------------------------------------------------------------------------
@@ -1181,9 +1118,9 @@ __device__ __forceinline__ void rqs_bwd_coop_coupling(const RqsBwdArgs &a, float
   stage_packed<G::SIZE, 256>(img, a.img, tid);
   __syncthreads();
   RqsCoopAcc<G> acc;
-  rqs_zero(acc.w1, acc.b1);
-  rqs_zero(acc.w2, acc.b2);
-  rqs_zero(acc.w3, acc.b3);
+  net_zero_acc(acc.w1, acc.b1);
+  net_zero_acc(acc.w2, acc.b2);
+  net_zero_acc(acc.w3, acc.b3);
   // The conditioner half of a group's home tile is requested ONE GROUP AHEAD (right after barrier B0, when the registers
   // are free again): with one wave per SIMD nothing else hides the HBM latency of these loads -- the home phase took
   // 9.1 k cycles for 2 k cycles of MFMA work before (tools/trace_rqs.py).
@@ -1208,6 +1145,7 @@ __device__ __forceinline__ void rqs_bwd_coop_coupling(const RqsBwdArgs &a, float
 #ifdef NF_KERNEL_TRACE
   long long *tr = (a.trace && blockIdx.x == 0 && tid == 0) ? a.trace : nullptr;
   if (tr) { tr[100] = clock64(); tr[101] = wall_clock64(); }  // shader clock against the constant 100 MHz counter: the clock the kernel ran at
+// (not NF_STAMP: only in the first tile group, and NF_STAMP on a conditioned pointer costs the trace build of this kernel an instruction)
 #define COOP_STAMP(slot) do { if (tr && grp == (long)blockIdx.x) { __builtin_amdgcn_sched_barrier(0); tr[slot] = clock64(); } } while (0)
 #else
 #define COOP_STAMP(slot) do { } while (0)
@@ -1406,12 +1344,12 @@ __device__ __forceinline__ void rqs_bwd_coop_coupling(const RqsBwdArgs &a, float
 #pragma unroll 1
   for (int w = 0; w < 4; ++w) {
     if (wave == w) {
-      rqs_fold<G::MB, G::H1B, G::S1>(img + G::W1, img + G::B1, acc.w1, acc.b1, w == 0, l31, hi);
-      rqs_fold<G::H1B, G::H2B, G::S2>(img + G::W2, img + G::B2, acc.w2, acc.b2, w == 0, l31, hi);
+      net_fold_acc<G::MB, G::H1B, G::S1>(img + G::W1, img + G::B1, acc.w1, acc.b1, w == 0, l31, hi);
+      net_fold_acc<G::H1B, G::H2B, G::S2>(img + G::W2, img + G::B2, acc.w2, acc.b2, w == 0, l31, hi);
     }
     __syncthreads();
   }
-  rqs_fold<G::H2B, G::OBC, G::S3>(img + G::W3 + ch * G::OBC * 32, img + G::B3 + ch * G::OBC * 32, acc.w3, acc.b3, true, l31, hi);
+  net_fold_acc<G::H2B, G::OBC, G::S3>(img + G::W3 + ch * G::OBC * 32, img + G::B3 + ch * G::OBC * 32, acc.w3, acc.b3, true, l31, hi);
   __syncthreads();
   {
     const float4 *c0 = reinterpret_cast<const float4 *>(img);
@@ -1500,11 +1438,8 @@ __device__ __forceinline__ void rqs_bwd_coop6_coupling(const RqsBwdArgs &a, floa
 #ifdef NF_KERNEL_TRACE  // tools/trace_rqs6.py: workgroup 0 / wave 0: [0] start, [1] prologue done, [2 + 12 g ..] group g: home forward done (B0), then per
                         // tile t the chunk phase's end (B1) and the d2 sum's end, closing home phase done; [60] groups done, [61] folded, [62] slab written
   long long *tr6 = (a.trace && blockIdx.x == 0 && tid == 0) ? a.trace : nullptr;
-#define C6_STAMP(slot) do { if (tr6) { __builtin_amdgcn_sched_barrier(0); tr6[slot] = clock64(); } } while (0)
-#else
-#define C6_STAMP(slot) do { } while (0)
 #endif
-  C6_STAMP(0);
+  NF_STAMP(tr6, 0);
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, hi = lane >> 5;
   char *wv = lds + wave * L::WAVE_BYTES;                                   // this wave's region
@@ -1541,12 +1476,12 @@ __device__ __forceinline__ void rqs_bwd_coop6_coupling(const RqsBwdArgs &a, floa
         for (int c = 0; c < 3; ++c) W.t[kg][ib][c] = wt[((kg * 3 + c) * 2) * B::TROWS + ib * 32];
   }
   __syncthreads();
-  C6_STAMP(1);
+  NF_STAMP(tr6, 1);
   int gcount6 = 0;
   RqsCoopAcc<G> acc;
-  rqs_zero(acc.w1, acc.b1);
-  rqs_zero(acc.w2, acc.b2);
-  rqs_zero(acc.w3, acc.b3);
+  net_zero_acc(acc.w1, acc.b1);
+  net_zero_acc(acc.w2, acc.b2);
+  net_zero_acc(acc.w3, acc.b3);
   f32x16 xb[G::MB];
   auto load_home = [&](long g) {
     const long tile_ = g * 4 + wave;
@@ -1604,7 +1539,7 @@ __device__ __forceinline__ void rqs_bwd_coop6_coupling(const RqsBwdArgs &a, floa
     const int gb6 = 2 + 12 * (gcount6 < 4 ? gcount6 : 3);
     ++gcount6;
     (void)gb6;
-    C6_STAMP(gb6 + 0);
+    NF_STAMP(tr6, gb6 + 0);
 
     // ---------------- chunk phase ----------------
     f32x16 d2[G::H2B];
@@ -1770,7 +1705,7 @@ __device__ __forceinline__ void rqs_bwd_coop6_coupling(const RqsBwdArgs &a, floa
         }
       }
       __syncthreads();  // B1: the four partial d2 of tile t are in the slots (set t & 1)
-      C6_STAMP(gb6 + 1 + 2 * t);
+      NF_STAMP(tr6, gb6 + 1 + 2 * t);
       if (tlive && t == wave) {
         const float *set = slots + (t & 1) * 4 * L::SLOT;
 #pragma unroll
@@ -1780,7 +1715,7 @@ __device__ __forceinline__ void rqs_bwd_coop6_coupling(const RqsBwdArgs &a, floa
 #pragma unroll
             for (int r = 0; r < 16; ++r) d2[b][r] += set[w * L::SLOT + (b * 16 + r) * 64 + lane];
       }
-      C6_STAMP(gb6 + 2 + 2 * t);
+      NF_STAMP(tr6, gb6 + 2 + 2 * t);
     }
 
     // ---------------- home phase: layers 2 and 1 of this wave's own tile ----------------
@@ -1821,10 +1756,10 @@ __device__ __forceinline__ void rqs_bwd_coop6_coupling(const RqsBwdArgs &a, floa
 #pragma unroll
         for (int r = 0; r < 16; ++r) tile_store(gio, tile_soff(b, r, par_c), g2[b][r]);
     }
-    C6_STAMP(gb6 + 9);
+    NF_STAMP(tr6, gb6 + 9);
   }
   __syncthreads();  // every working area is dead: the LDS becomes the fold target (the slab image, G's fp32 layout)
-  C6_STAMP(60);
+  NF_STAMP(tr6, 60);
   // Layers 1-2: every wave leaves its own sums in its own copy of the image's first G::W3 floats (behind the slab image), and
   // the slab write adds the four copies in wave order -- ((w0 + w1) + w2) + w3, the association of the waves-in-turn fold this
   // replaces (round 5, tools/trace_rqs6.py: that fold and its four barriers were 6.5 k of a launch's 247 k clocks).  The
@@ -1833,12 +1768,12 @@ __device__ __forceinline__ void rqs_bwd_coop6_coupling(const RqsBwdArgs &a, floa
   static_assert(((size_t)G::SIZE + 4 * (size_t)G::W3) * 4 <= L::BYTES && G::W3 % 4 == 0, "the four partial images fit behind the slab image");
   {
     float *mine = fold + G::SIZE + wave * G::W3;
-    rqs_fold<G::MB, G::H1B, G::S1>(mine + G::W1, mine + G::B1, acc.w1, acc.b1, true, l31, hi);
-    rqs_fold<G::H1B, G::H2B, G::S2>(mine + G::W2, mine + G::B2, acc.w2, acc.b2, true, l31, hi);
+    net_fold_acc<G::MB, G::H1B, G::S1>(mine + G::W1, mine + G::B1, acc.w1, acc.b1, true, l31, hi);
+    net_fold_acc<G::H1B, G::H2B, G::S2>(mine + G::W2, mine + G::B2, acc.w2, acc.b2, true, l31, hi);
   }
-  rqs_fold<G::H2B, G::OBC, G::S3>(fold + G::W3 + ch * G::OBC * 32, fold + G::B3 + ch * G::OBC * 32, acc.w3, acc.b3, true, l31, hi);
+  net_fold_acc<G::H2B, G::OBC, G::S3>(fold + G::W3 + ch * G::OBC * 32, fold + G::B3 + ch * G::OBC * 32, acc.w3, acc.b3, true, l31, hi);
   __syncthreads();
-  C6_STAMP(61);
+  NF_STAMP(tr6, 61);
   {
     const float4 *c0 = reinterpret_cast<const float4 *>(fold), *p0 = reinterpret_cast<const float4 *>(fold + G::SIZE);
     float4 *dst = reinterpret_cast<float4 *>(slab + (long)blockIdx.x * slab_stride);
@@ -1855,7 +1790,7 @@ __device__ __forceinline__ void rqs_bwd_coop6_coupling(const RqsBwdArgs &a, floa
     }
   }
   __syncthreads();
-  C6_STAMP(62);
+  NF_STAMP(tr6, 62);
 }
 
 template <class G, bool INVD>
@@ -2038,11 +1973,7 @@ constexpr int rqs_tgt_nw() {
 template <class G, bool B6, int TGT>
 static int launch_rqs_tgt_set(nf_ctx *ctx, const RqsChainArgs &a, float *xt, const RqsFusedArgs &fa, long grid, size_t lds) {
   constexpr int NW = rqs_tgt_nw<G, B6, TGT>();
-  static AttrOnce attr_once;  // once per device
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    NF_HIP(hipFuncSetAttribute((const void *)k_rqs_chain_tgt<G, B6, TGT, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return NF_OK;
-  }));
+  NF_TRY((nf_lds_once<k_rqs_chain_tgt<G, B6, TGT, NW>>(ctx, lds)));
   hipLaunchKernelGGL((k_rqs_chain_tgt<G, B6, TGT, NW>), dim3((unsigned)grid), dim3(64 * NW), lds, ctx->stream, a, xt, fa);
   return (int)hipGetLastError();
 }
@@ -2184,15 +2115,9 @@ int nf_rqs_bwd_grid(nf_ctx *ctx, long N) {
   return (int)(grid < 1 ? 1 : grid);
 }
 
-template <class G, bool INVD>
-static int launch_rqs_bwd_coop(nf_ctx *ctx, const nf_flow_desc *desc, int k, float *y, float *ybar, const float *lbar,
-                               float lbar_const, long N, float *slab, long slab_stride, int grid, void *tape) {
-  const size_t lds = RqsCoopLds<G>::BYTES;
-  static AttrOnce attr_once;  // once per device
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    NF_HIP(hipFuncSetAttribute((const void *)k_rqs_bwd_coop<G, INVD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return NF_OK;
-  }));
+// the reverse kernels' arguments for coupling k (img6, the six-term triples, is k_rqs_bwd_coop6's own)
+template <class G>
+static RqsBwdArgs rqs_bwd_args(nf_ctx *ctx, const nf_flow_desc *desc, int k, long N, void *tape) {
   const CouplingInfo ci = nf_coupling_info(desc, k);
   RqsBwdArgs a;
   a.tape = rqs_tape_at(desc, N, tape);
@@ -2202,6 +2127,15 @@ static int launch_rqs_bwd_coop(nf_ctx *ctx, const nf_flow_desc *desc, int k, flo
   a.img6 = nullptr;
   a.d = desc->d; a.c = ci.c; a.m = ci.m; a.par_t = ci.par_t; a.B = desc->B; a.N = N;
   a.trace = (long long *)ctx->trace;
+  return a;
+}
+
+template <class G, bool INVD>
+static int launch_rqs_bwd_coop(nf_ctx *ctx, const nf_flow_desc *desc, int k, float *y, float *ybar, const float *lbar,
+                               float lbar_const, long N, float *slab, long slab_stride, int grid, void *tape) {
+  const size_t lds = RqsCoopLds<G>::BYTES;
+  NF_TRY((nf_lds_once<k_rqs_bwd_coop<G, INVD>>(ctx, lds)));
+  const RqsBwdArgs a = rqs_bwd_args<G>(ctx, desc, k, N, tape);
   ProfScope ps(ctx, INVD ? "rqs_bwd_inv" : "rqs_bwd");
   hipLaunchKernelGGL((k_rqs_bwd_coop<G, INVD>), dim3((unsigned)grid), dim3(256), lds, ctx->stream, a, y, ybar, lbar, lbar_const,
                      slab + (long)k * G::SIZE, slab_stride);
@@ -2212,21 +2146,10 @@ template <class G, bool INVD>
 static int launch_rqs_bwd_coop6(nf_ctx *ctx, const nf_flow_desc *desc, int k, float *y, float *ybar, const float *lbar,
                                 float lbar_const, long N, float *slab, long slab_stride, int grid, void *tape) {
   const size_t lds = RqsCoop6Lds<G>::BYTES;
-  static AttrOnce attr_once;  // once per device
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    NF_HIP(hipFuncSetAttribute((const void *)k_rqs_bwd_coop6<G, INVD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return NF_OK;
-  }));
+  NF_TRY((nf_lds_once<k_rqs_bwd_coop6<G, INVD>>(ctx, lds)));
   NF_TRY(rqs_b6_refresh<G>(ctx, desc));
-  const CouplingInfo ci = nf_coupling_info(desc, k);
-  RqsBwdArgs a;
-  a.tape = rqs_tape_at(desc, N, tape);
-  a.k = k;
-  a.ncoup = 2 * desc->nlayers;
-  a.img = (const float *)ctx->wimg + (size_t)k * G::SIZE;
+  RqsBwdArgs a = rqs_bwd_args<G>(ctx, desc, k, N, tape);
   a.img6 = (const nf_u32x4 *)((const char *)ctx->wimg + rqs_fp32_bytes(desc)) + (size_t)k * RqsB6Geo<G>::U4;
-  a.d = desc->d; a.c = ci.c; a.m = ci.m; a.par_t = ci.par_t; a.B = desc->B; a.N = N;
-  a.trace = (long long *)ctx->trace;
   ProfScope ps(ctx, INVD ? "rqs_bwd_inv" : "rqs_bwd");
   hipLaunchKernelGGL((k_rqs_bwd_coop6<G, INVD>), dim3((unsigned)grid), dim3(256), lds, ctx->stream, a, y, ybar, lbar, lbar_const,
                      slab + (long)k * G::SIZE, slab_stride);
@@ -2237,32 +2160,19 @@ template <class G, bool INVD>
 static int launch_rqs_bwd(nf_ctx *ctx, const nf_flow_desc *desc, int k, float *y, float *ybar, const float *lbar,
                           float lbar_const, long N, float *slab, long slab_stride, int grid, void *tape) {
   if (!tape) return NF_ERR_ARG;  // the reverse kernels differentiate the forward's own bins (RqsTape)
+  static const bool perwave = std::getenv("NF_RQS_BWD_PERWAVE") != nullptr;  // A/B switch: the per-wave-tile kernel
   if constexpr (G::NCH == 4) {
     if constexpr (RqsCoop6Lds<G>::FITS) {
-      static const bool perwave = std::getenv("NF_RQS_BWD_PERWAVE") != nullptr;
       if (rqs_bwd_b6() && !perwave) return launch_rqs_bwd_coop6<G, INVD>(ctx, desc, k, y, ybar, lbar, lbar_const, N, slab, slab_stride, grid, tape);
     }
-    static const bool old_form = std::getenv("NF_RQS_BWD_PERWAVE") != nullptr;  // A/B switch: the per-wave-tile kernel
-    if (!old_form || G::OB3 > 12) return launch_rqs_bwd_coop<G, INVD>(ctx, desc, k, y, ybar, lbar, lbar_const, N, slab, slab_stride, grid, tape);
+    if (!perwave || G::OB3 > 12) return launch_rqs_bwd_coop<G, INVD>(ctx, desc, k, y, ybar, lbar, lbar_const, N, slab, slab_stride, grid, tape);
   }
   if constexpr (G::OB3 > 12) {  // the per-wave-tile kernel would need more accumulators than there are registers
     return NF_ERR_UNSUPPORTED;
   } else {
   const size_t lds = RqsLds<G>::BYTES;
-  static AttrOnce attr_once;  // once per device: a context on another GPU needs its own
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    NF_HIP(hipFuncSetAttribute((const void *)k_rqs_bwd<G, INVD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return NF_OK;
-  }));
-  const CouplingInfo ci = nf_coupling_info(desc, k);
-  RqsBwdArgs a;
-  a.tape = rqs_tape_at(desc, N, tape);
-  a.k = k;
-  a.ncoup = 2 * desc->nlayers;
-  a.img = (const float *)ctx->wimg + (size_t)k * G::SIZE;
-  a.img6 = nullptr;
-  a.d = desc->d; a.c = ci.c; a.m = ci.m; a.par_t = ci.par_t; a.B = desc->B; a.N = N;
-  a.trace = (long long *)ctx->trace;
+  NF_TRY((nf_lds_once<k_rqs_bwd<G, INVD>>(ctx, lds)));
+  const RqsBwdArgs a = rqs_bwd_args<G>(ctx, desc, k, N, tape);
   ProfScope ps(ctx, INVD ? "rqs_bwd_inv" : "rqs_bwd");
   hipLaunchKernelGGL((k_rqs_bwd<G, INVD>), dim3((unsigned)grid), dim3(256), lds, ctx->stream, a, y, ybar, lbar, lbar_const,
                      slab + (long)k * G::SIZE, slab_stride);

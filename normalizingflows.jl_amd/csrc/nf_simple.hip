@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "nf_common.h"
+#include "nf_launchers.h"
 #include "nf_mfma.h"
 #include "nf_philox.h"
 #include "nf_targets.h"
@@ -2108,11 +2109,7 @@ int nf_simple_bwd(nf_ctx *ctx, const nf_flow_desc *desc, const void *theta, cons
 template <auto KERNEL, class T>
 static int launch_step_kernel(nf_ctx *ctx, size_t lds, long nb, const char *prof_name, const SimpleArgs &a, const void *theta,
                               const void *xs, const SimpleFused &fu, double lbar_const, T *slabs, int *nb_out) {
-  static AttrOnce attr_once;  // once per device
-  NF_TRY(attr_once.run(ctx->device, [&]() -> int {
-    NF_HIP(hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    return NF_OK;
-  }));
+  NF_TRY(nf_lds_once<KERNEL>(ctx, 150 * 1024));
   const long res = resident_blocks(ctx, KERNEL, lds);
   if (nb > res) nb = res;
   if (nb < 1) nb = 1;

@@ -344,7 +344,7 @@ template <int DB>
 static int launch_softmax_tiled(const TgtTiledArgs &a) {
   const size_t lds = (size_t)SmGeo<DB>::FLOATS * sizeof(float);
   nf_ctx *ctx = a.ctx;
-  NF_TRY(tgt_lds_once<k_target_softmax_tiled<DB>>(ctx, lds));
+  NF_TRY(nf_lds_once<k_target_softmax_tiled<DB>>(ctx, lds));
   ProfScope ps(ctx, "target_softmax");
   return tgt_launch_tiled<k_target_softmax_tiled<DB>>(a, lds, a.d, (int)a.t->s1, (int)a.t->s0, a.N, a.yt, (const float *)a.t->p0,
                                                       (const float *)a.t->p1);
@@ -364,7 +364,7 @@ static int launch_softmax_flat(const TgtFlatArgs &a) {
   // the most any checked target takes: d = 256, with the widest image (C = 2) and the widest phi' block (C = 16) both counted
   const size_t most = (size_t)(SMF_SPB * (SMF_MAXD + 1) + SMF_RB * (SMF_MAXD / 2 + 1) + SMF_SPB * (SMF_RB * SMF_MAXC + 1)) * sizeof(T);
   nf_ctx *ctx = a.ctx;
-  NF_TRY(tgt_lds_once<k_target_softmax<T>>(ctx, most));
+  NF_TRY(nf_lds_once<k_target_softmax<T>>(ctx, most));
   ProfScope ps(ctx, "target_softmax");
   return tgt_launch_flat<k_target_softmax<T>, T>(a, softmax_flat_lds(a.d, C) * sizeof(T), a.d, C, (int)a.t->s0, a.N, (const T *)a.y,
                                                  (const T *)a.t->p0, (const T *)a.t->p1);

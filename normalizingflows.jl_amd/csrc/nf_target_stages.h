@@ -152,17 +152,8 @@ int tgt_dispatch_dtype(int dtype, F &&f) {
   return dtype == NF_DTYPE_F32 ? f(float()) : f(double());
 }
 
-// Set the LDS attribute once per device, then launch, in two halves: a launcher opens its ProfScope between them, so that
-// the scope covers the launch alone.
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize = most bytes) once per (kernel, device)
-template <auto KERN>
-int tgt_lds_once(nf_ctx *ctx, size_t most) {
-  static AttrOnce attr_once;
-  return attr_once.run(ctx->device, [&]() -> int {
-    NF_HIP(hipFuncSetAttribute((const void *)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, (int)most));
-    return NF_OK;
-  });
-}
+// nf_lds_once<KERN> (nf_common.h) sets the LDS attribute once per device; a launcher opens its ProfScope between that and the
+// launch, so that the scope covers the launch alone.
 // 256-thread blocks with `lds` bytes of dynamic LDS on the context's stream, one per 32-sample tile / per 16 samples.  `head`:
 // the kernel's own leading parameters, up to the target's data; the parameters every kernel ends with are filled in here.
 template <auto KERN, class... H>

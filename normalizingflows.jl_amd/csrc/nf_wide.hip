@@ -19,6 +19,7 @@
 // per wave the way nf_coupling.hip keeps them, hence the stash.  Per sample and net it is
 // (2*h1 + 2*h2 + c) floats, written once and read once.
 #include "nf_common.h"
+#include "nf_launchers.h"
 // The split's two exact subtractions as scalar v_sub_f32 pairs in this file (nf_mfma.h: NF_SPLIT_SCALAR).  A packed f32 VALU
 // instruction next to bf16 MFMAs costs more than the issue slot it saves with one wave per SIMD (these kernels); measured on
 // one box, round 5: k_wide_dw_b6 56.2 -> 54.4 us, k_wide_bwd_stashed_b6 75.7 -> 74.4 us per launch.  The two-waves-per-SIMD
@@ -28,16 +29,6 @@
 #include "nf_pack.h"
 
 typedef __attribute__((address_space(3))) void lds_void_t;
-
-// optional clock stamps of block 0 / wave 0 (nf_debug_trace, tools/trace_wide.py)
-#ifdef NF_KERNEL_TRACE
-#define WIDE_STAMP(slot)                                                  \
-  do {                                                                    \
-    if (tr) { __builtin_amdgcn_sched_barrier(0); tr[slot] = clock64(); }  \
-  } while (0)
-#else
-#define WIDE_STAMP(slot) do { (void)tr; } while (0)
-#endif
 
 using GW = NetGeo<4, 8, 8, 4>;  // every wide flow is zero-padded into this geometry
 
@@ -268,9 +259,9 @@ __device__ __forceinline__ void wide_net_fwd(wide_img_t img, const float *__rest
 #pragma unroll
   for (int b = 0; b < G::H1B; ++b)
     nf_lrelu16(a1[b]);
-  WIDE_STAMP(2);
+  NF_STAMP(tr, 2);
   hk.after_l1(a1);
-  WIDE_STAMP(3);
+  NF_STAMP(tr, 3);
   f32x16 a2[G::H2B];
   init_bias<G::H2B>(a2, bias + 32 * G::H1B, hi);
 #pragma unroll
@@ -282,14 +273,14 @@ __device__ __forceinline__ void wide_net_fwd(wide_img_t img, const float *__rest
       dj = DmaJob{img, C::O3, C::N3, cb + (buf ^ 1) * C::CHBUF, wave, lane};
     const DmaJob none{img, 0, 0, cb, wave, lane};
     if constexpr (B6) {  // the DMA in front of the hook's stores (wide_chunk_barrier)
-      if (ib < 4) WIDE_STAMP(32 + 4 * ib);  // (tools/trace_wide_apply.py: inside the first chunks of layer 2)
+      if (ib < 4) NF_STAMP(tr, 32 + 4 * ib);  // (tools/trace_wide_apply.py: inside the first chunks of layer 2)
       dj.issue();
       hk.l2_step(ib, a1);
-      if (ib < 4) WIDE_STAMP(33 + 4 * ib);
+      if (ib < 4) NF_STAMP(tr, 33 + 4 * ib);
       wide_fwd_chunk_b6<G::H2B>(cb + buf * C::CHBUF, a1[ib], a2, l31, hi, none);
-      if (ib < 4) WIDE_STAMP(34 + 4 * ib);
+      if (ib < 4) NF_STAMP(tr, 34 + 4 * ib);
       wide_chunk_barrier<HK::YOUNG>();
-      if (ib < 4) WIDE_STAMP(35 + 4 * ib);
+      if (ib < 4) NF_STAMP(tr, 35 + 4 * ib);
     } else {
       hk.l2_step(ib, a1);
       wide_fwd_chunk<G::H2B, G::S2>(cb + buf * C::CHBUF, a1[ib], a2, l31, hi, dj);
@@ -300,9 +291,9 @@ __device__ __forceinline__ void wide_net_fwd(wide_img_t img, const float *__rest
 #pragma unroll
   for (int b = 0; b < G::H2B; ++b)
     nf_lrelu16(a2[b]);
-  WIDE_STAMP(4);
+  NF_STAMP(tr, 4);
   hk.after_l2(a2);
-  WIDE_STAMP(5);
+  NF_STAMP(tr, 5);
   init_bias<G::CB>(out, bias + 32 * (G::H1B + G::H2B), hi);
 #pragma unroll
   for (int ib = 0; ib < G::H2B; ++ib) {
@@ -362,18 +353,18 @@ struct WideStash {
   float *a1, *a2, *d1, *d2, *d3;
 };
 
-struct StashIO {
+struct WideStashIO {
   __amdgpu_buffer_rsrc_t rs;
   int voff;
 };
-__device__ __forceinline__ StashIO make_stash_io(float *t, long tile, int F, int l31, int hi) {
-  StashIO s;
+__device__ __forceinline__ WideStashIO make_wide_stash_io(float *t, long tile, int F, int l31, int hi) {
+  WideStashIO s;
   s.rs = __builtin_amdgcn_make_buffer_rsrc(t + tile * F * NF_TILE, 0, F * NF_TILE * 4, 0x00020000);
   s.voff = l31 * 4 + hi * (4 * NF_TILE * 4);
   return s;
 }
 template <int NB>
-__device__ __forceinline__ void stash_store(const StashIO &s, const f32x16 (&v)[NB]) {
+__device__ __forceinline__ void stash_store(const WideStashIO &s, const f32x16 (&v)[NB]) {
 #pragma unroll
   for (int b = 0; b < NB; ++b)
 #pragma unroll
@@ -386,7 +377,7 @@ __device__ __forceinline__ void stash_store(const StashIO &s, const f32x16 (&v)[
 
 // elements [e0, e0 + n) of the flattened (block, reg) index space
 template <int NB>
-__device__ __forceinline__ void stash_store_range(const StashIO &s, const f32x16 (&v)[NB], int e0, int n) {
+__device__ __forceinline__ void stash_store_range(const WideStashIO &s, const f32x16 (&v)[NB], int e0, int n) {
 #pragma unroll
   for (int q = 0; q < NB * 16; ++q)
     if (q >= e0 && q < e0 + n) {
@@ -396,18 +387,12 @@ __device__ __forceinline__ void stash_store_range(const StashIO &s, const f32x16
     }
 }
 
-template <int NB>
-__device__ __forceinline__ void wide_sign_masks(const f32x16 (&v)[NB], unsigned (&m)[NB]) {
-#pragma unroll
-  for (int b = 0; b < NB; ++b) m[b] = nf_sign_mask16(v[b]);
-}
-
 // hooks of the forward kernel: optional stash (STASH) and, for the t net, the prefetch of the
 // transformed half x1 behind the last layer
 template <class G, bool STASH>
 struct ApplyHooks {
   static constexpr int YOUNG = STASH ? 16 : 0;  // stash stores per l2_step / l3_step (wide_chunk_barrier)
-  StashIO sa1, sa2;
+  WideStashIO sa1, sa2;
   unsigned *mask;  // this lane's slot in the tile's mask block, or nullptr
   const TileIO *io;
   f32x16 (*x1)[G::CB];
@@ -415,7 +400,7 @@ struct ApplyHooks {
   __device__ __forceinline__ void after_l1(f32x16 (&a1)[G::H1B]) const {
     if (STASH) {
       unsigned m[G::H1B];
-      wide_sign_masks<G::H1B>(a1, m);
+      sign_masks<G::H1B>(a1, m);
       if (mask) {
 #pragma unroll
         for (int b = 0; b < G::H1B; ++b) mask[b * 64] = m[b];
@@ -425,7 +410,7 @@ struct ApplyHooks {
   __device__ __forceinline__ void after_l2(f32x16 (&a2)[G::H2B]) const {
     if (STASH) {
       unsigned m[G::H2B];
-      wide_sign_masks<G::H2B>(a2, m);
+      sign_masks<G::H2B>(a2, m);
       if (mask) {
 #pragma unroll
         for (int b = 0; b < G::H2B; ++b) mask[(8 + b) * 64] = m[b];
@@ -492,7 +477,7 @@ __global__ __launch_bounds__(256, 1) void k_wide_apply(WideArgs a, float *xt, fl
 #else
     long long *tr = nullptr;
 #endif
-    WIDE_STAMP(0);
+    NF_STAMP(tr, 0);
     {
       f32x16 xb[G::MB];
 #pragma unroll
@@ -502,13 +487,13 @@ __global__ __launch_bounds__(256, 1) void k_wide_apply(WideArgs a, float *xt, fl
           const float v = tile_load(io, tile_soff(b, r, par_c));
           xb[b][r] = valid ? v : 0.f;
         }
-      ApplyHooks<G, STASH> hk{make_stash_io(fs.a1[0], tl, (STASH && live) ? 32 * G::H1B : 0, l31, hi),
-                              make_stash_io(fs.a2[0], tl, (STASH && live) ? 32 * G::H2B : 0, l31, hi),
+      ApplyHooks<G, STASH> hk{make_wide_stash_io(fs.a1[0], tl, (STASH && live) ? 32 * G::H1B : 0, l31, hi),
+                              make_wide_stash_io(fs.a2[0], tl, (STASH && live) ? 32 * G::H2B : 0, l31, hi),
                               (STASH && live) ? fs.mask[0] + tl * (16 * 64) + lane : nullptr, nullptr, nullptr, 0};
-      WIDE_STAMP(1);
+      NF_STAMP(tr, 1);
       wide_net_fwd<G, ApplyHooks<G, STASH>, B6, B6>(img_s, bias, cb, buf, img_t, C::O1, C::N1, xb, S, wave, lane, hk, tr);
-      WIDE_STAMP(6);
-      if (STASH) stash_store<G::CB>(make_stash_io(fs.out[0], tl, live ? 32 * G::CB : 0, l31, hi), S);
+      NF_STAMP(tr, 6);
+      if (STASH) stash_store<G::CB>(make_wide_stash_io(fs.out[0], tl, live ? 32 * G::CB : 0, l31, hi), S);
     }
     {
       f32x16 xb[G::MB];
@@ -521,13 +506,13 @@ __global__ __launch_bounds__(256, 1) void k_wide_apply(WideArgs a, float *xt, fl
         }
       // the transformed half is fetched while the last layer of the t net runs (one batch of loads,
       // not interleaved with the stores below: the compiler must keep load/store order on one buffer)
-      ApplyHooks<G, STASH> hk{make_stash_io(fs.a1[1], tl, (STASH && live) ? 32 * G::H1B : 0, l31, hi),
-                              make_stash_io(fs.a2[1], tl, (STASH && live) ? 32 * G::H2B : 0, l31, hi),
+      ApplyHooks<G, STASH> hk{make_wide_stash_io(fs.a1[1], tl, (STASH && live) ? 32 * G::H1B : 0, l31, hi),
+                              make_wide_stash_io(fs.a2[1], tl, (STASH && live) ? 32 * G::H2B : 0, l31, hi),
                               (STASH && live) ? fs.mask[1] + tl * (16 * 64) + lane : nullptr, &io, &x1, a.par_t};
-      WIDE_STAMP(17);
+      NF_STAMP(tr, 17);
       wide_net_fwd<G, ApplyHooks<G, STASH>, B6>(img_t, bias + W::NBIAS, cb, buf, img_s, C::O1, more ? C::N1 : 0, xb, T, wave, lane, hk, tr ? tr + 16 : nullptr);
-      WIDE_STAMP(22);
-      if (STASH) stash_store<G::CB>(make_stash_io(fs.out[1], tl, live ? 32 * G::CB : 0, l31, hi), T);
+      NF_STAMP(tr, 22);
+      if (STASH) stash_store<G::CB>(make_wide_stash_io(fs.out[1], tl, live ? 32 * G::CB : 0, l31, hi), T);
     }
     float lpart[G::CB];
 #pragma unroll
@@ -552,7 +537,7 @@ __global__ __launch_bounds__(256, 1) void k_wide_apply(WideArgs a, float *xt, fl
       const float base = accumulate ? ladj[j] : 0.f;
       ladj[j] = INVERSE ? base - lsum : base + lsum;
     }
-    WIDE_STAMP(23);
+    NF_STAMP(tr, 23);
   }
 }
 
@@ -567,7 +552,7 @@ __global__ __launch_bounds__(256, 1) void k_wide_apply(WideArgs a, float *xt, fl
 template <class G>
 __device__ __forceinline__ void wide_dx_chain(wide_img_t img, float *cb, int &buf, f32x16 (&d3)[G::CB],
                                               const unsigned (&m1)[G::H1B], const unsigned (&m2)[G::H2B],
-                                              const StashIO &sd1, const StashIO &sd2, const StashIO &sd3,
+                                              const WideStashIO &sd1, const WideStashIO &sd2, const WideStashIO &sd3,
                                               const TileIO &gio, int par_c, bool live, int next_off, int next_floats,
                                               int wave, int lane, long long *tr) {
   using W = Wide<G>;
@@ -593,9 +578,9 @@ __device__ __forceinline__ void wide_dx_chain(wide_img_t img, float *cb, int &bu
     __syncthreads();
     buf ^= 1;
   }
-  WIDE_STAMP(8);
-  WIDE_STAMP(9);
-  WIDE_STAMP(10);
+  NF_STAMP(tr, 8);
+  NF_STAMP(tr, 9);
+  NF_STAMP(tr, 10);
   f32x16 d1[G::H1B];
 #pragma unroll
   for (int ib = 0; ib < G::H1B; ++ib) {
@@ -612,8 +597,8 @@ __device__ __forceinline__ void wide_dx_chain(wide_img_t img, float *cb, int &bu
     __syncthreads();
     buf ^= 1;
   }
-  WIDE_STAMP(11);
-  WIDE_STAMP(12);
+  NF_STAMP(tr, 11);
+  NF_STAMP(tr, 12);
   f32x16 g2p;  // x2bar block of the previous chunk, stored behind the next chunk's MFMAs
 #pragma unroll
   for (int ib = 0; ib < G::MB; ++ib) {
@@ -676,14 +661,14 @@ __global__ __launch_bounds__(256, 1) void k_wide_bwd(WideArgs a, float *__restri
     const TileIO yio = make_tile_io(y, tl, a.d, l31, hi);
     const TileIO gio = make_tile_io(ybar, tl, a.d, l31, hi);
     // a dead wave (tile >= ntiles) keeps the barriers company; its stash descriptors are empty
-    const StashIO sa1 = make_stash_io(st.a1, tl, live ? 32 * G::H1B : 0, l31, hi);
-    const StashIO sa2 = make_stash_io(st.a2, tl, live ? 32 * G::H2B : 0, l31, hi);
-    const StashIO sd1 = make_stash_io(st.d1, tl, live ? 32 * G::H1B : 0, l31, hi);
-    const StashIO sd2 = make_stash_io(st.d2, tl, live ? 32 * G::H2B : 0, l31, hi);
-    const StashIO sd3 = make_stash_io(st.d3, tl, live ? 32 * G::CB : 0, l31, hi);
+    const WideStashIO sa1 = make_wide_stash_io(st.a1, tl, live ? 32 * G::H1B : 0, l31, hi);
+    const WideStashIO sa2 = make_wide_stash_io(st.a2, tl, live ? 32 * G::H2B : 0, l31, hi);
+    const WideStashIO sd1 = make_wide_stash_io(st.d1, tl, live ? 32 * G::H1B : 0, l31, hi);
+    const WideStashIO sd2 = make_wide_stash_io(st.d2, tl, live ? 32 * G::H2B : 0, l31, hi);
+    const WideStashIO sd3 = make_wide_stash_io(st.d3, tl, live ? 32 * G::CB : 0, l31, hi);
 
     long long *tr = (a.trace && blockIdx.x == 0 && tid == 0 && grp == blockIdx.x) ? a.trace + (PHASE_S ? 32 : 0) : nullptr;
-    WIDE_STAMP(0);
+    NF_STAMP(tr, 0);
     unsigned m1[G::H1B], m2[G::H2B];
     f32x16 d3[G::CB], y1[G::CB], g1[G::CB];
     {
@@ -695,19 +680,19 @@ __global__ __launch_bounds__(256, 1) void k_wide_bwd(WideArgs a, float *__restri
           const float v = tile_load(yio, tile_soff(b, r, par_c));
           xb[b][r] = valid ? v : 0.f;
         }
-      WIDE_STAMP(1);
+      NF_STAMP(tr, 1);
       // masks right after each hidden layer; the stash stores of a1 / a2 and the loads of the
       // element-wise stage's operands go out a block per chunk, behind the MFMAs of layers 2 / 3
       struct BwdHooks {
         unsigned (&m1)[G::H1B];
         unsigned (&m2)[G::H2B];
-        const StashIO &sa1, &sa2;
+        const WideStashIO &sa1, &sa2;
         const TileIO &yio, &gio;
         f32x16 (&y1)[G::CB];
         f32x16 (&g1)[G::CB];
         int par_t;
-        __device__ __forceinline__ void after_l1(f32x16 (&a1)[G::H1B]) const { wide_sign_masks<G::H1B>(a1, m1); }
-        __device__ __forceinline__ void after_l2(f32x16 (&a2)[G::H2B]) const { wide_sign_masks<G::H2B>(a2, m2); }
+        __device__ __forceinline__ void after_l1(f32x16 (&a1)[G::H1B]) const { sign_masks<G::H1B>(a1, m1); }
+        __device__ __forceinline__ void after_l2(f32x16 (&a2)[G::H2B]) const { sign_masks<G::H2B>(a2, m2); }
         __device__ __forceinline__ void l2_step(int ib, f32x16 (&a1)[G::H1B]) const {
           stash_store_range<G::H1B>(sa1, a1, ib * 16, 16);
         }
@@ -724,7 +709,7 @@ __global__ __launch_bounds__(256, 1) void k_wide_bwd(WideArgs a, float *__restri
       } hk{m1, m2, sa1, sa2, yio, gio, y1, g1, a.par_t};
       wide_net_fwd<G>(img, bias, cb, buf, img, G::W3, W::CF3, xb, d3, wave, lane, hk, tr);
     }
-    WIDE_STAMP(6);
+    NF_STAMP(tr, 6);
     // element-wise stage (same algebra as bwd_tile in nf_coupling.hip)
     const float lb = valid ? (lbar ? lbar[j] : lbar_const) : 0.f;
 #pragma unroll
@@ -758,10 +743,10 @@ __global__ __launch_bounds__(256, 1) void k_wide_bwd(WideArgs a, float *__restri
           d3[b][r] = ok ? (gv * yv + lb) * (1.f - s * s) : 0.f;
         }
       }
-    WIDE_STAMP(7);
+    NF_STAMP(tr, 7);
 
     wide_dx_chain<G>(img, cb, buf, d3, m1, m2, sd1, sd2, sd3, gio, par_c, live, G::W1, more ? W::CF1 : 0, wave, lane, tr);
-    WIDE_STAMP(13);
+    NF_STAMP(tr, 13);
   }
 }
 
@@ -799,10 +784,10 @@ __global__ __launch_bounds__(256, 1) void k_wide_bwd_stashed(WideArgs a, float *
     const bool more = grp + gridDim.x < ngroups;
     const TileIO yio = make_tile_io(y, tl, a.d, l31, hi);
     const TileIO gio = make_tile_io(ybar, tl, a.d, l31, hi);
-    const StashIO sd1 = make_stash_io(st.d1, tl, live ? 32 * G::H1B : 0, l31, hi);
-    const StashIO sd2 = make_stash_io(st.d2, tl, live ? 32 * G::H2B : 0, l31, hi);
-    const StashIO sd3 = make_stash_io(st.d3, tl, live ? 32 * G::CB : 0, l31, hi);
-    const StashIO so = make_stash_io(const_cast<float *>(fout), tl, 32 * G::CB, l31, hi);
+    const WideStashIO sd1 = make_wide_stash_io(st.d1, tl, live ? 32 * G::H1B : 0, l31, hi);
+    const WideStashIO sd2 = make_wide_stash_io(st.d2, tl, live ? 32 * G::H2B : 0, l31, hi);
+    const WideStashIO sd3 = make_wide_stash_io(st.d3, tl, live ? 32 * G::CB : 0, l31, hi);
+    const WideStashIO so = make_wide_stash_io(const_cast<float *>(fout), tl, 32 * G::CB, l31, hi);
     long long *tr = nullptr;
 
     unsigned m1[G::H1B], m2[G::H2B];
@@ -866,7 +851,7 @@ struct WideT {
 template <class G>
 __device__ __forceinline__ void wide_dx_chain_b6(wide_img_t img, float *cb, int &buf, f32x16 (&d3)[G::CB],
                                                  const unsigned (&m1)[G::H1B], const unsigned (&m2)[G::H2B],
-                                                 const StashIO &sd1, const StashIO &sd2, const StashIO &sd3,
+                                                 const WideStashIO &sd1, const WideStashIO &sd2, const WideStashIO &sd3,
                                                  const TileIO &gio, int par_c, bool live, int next_floats, int wave, int lane) {
   using WT = WideT<G>;
   const int l31 = lane & 31, hi = lane >> 5;
@@ -961,10 +946,10 @@ __global__ __launch_bounds__(256, 1) void k_wide_bwd_stashed_b6(WideArgs a, floa
     const bool more = grp + gridDim.x < ngroups;
     const TileIO yio = make_tile_io(y, tl, a.d, l31, hi);
     const TileIO gio = make_tile_io(ybar, tl, a.d, l31, hi);
-    const StashIO sd1 = make_stash_io(st.d1, tl, live ? 32 * G::H1B : 0, l31, hi);
-    const StashIO sd2 = make_stash_io(st.d2, tl, live ? 32 * G::H2B : 0, l31, hi);
-    const StashIO sd3 = make_stash_io(st.d3, tl, live ? 32 * G::CB : 0, l31, hi);
-    const StashIO so = make_stash_io(const_cast<float *>(fout), tl, 32 * G::CB, l31, hi);
+    const WideStashIO sd1 = make_wide_stash_io(st.d1, tl, live ? 32 * G::H1B : 0, l31, hi);
+    const WideStashIO sd2 = make_wide_stash_io(st.d2, tl, live ? 32 * G::H2B : 0, l31, hi);
+    const WideStashIO sd3 = make_wide_stash_io(st.d3, tl, live ? 32 * G::CB : 0, l31, hi);
+    const WideStashIO so = make_wide_stash_io(const_cast<float *>(fout), tl, 32 * G::CB, l31, hi);
 
     unsigned m1[G::H1B], m2[G::H2B];
     {
@@ -1286,7 +1271,7 @@ __device__ __forceinline__ void dw_job_b6(const DwJob &jb, const DwArgs &a, int 
     const char *cur = lds + buf * (DW_ROWS * D6_ROW);
     char *nxt = lds + (buf ^ 1) * (DW_ROWS * D6_ROW);
     if (tslot >= 56) tr = nullptr;
-    WIDE_STAMP(tslot + 0);
+    NF_STAMP(tr, tslot + 0);
     __amdgpu_buffer_rsrc_t ra, rd;
     descriptors(tile + 2L * a.ksplit, ra, rd);
     const nf_u32x4 *pa = reinterpret_cast<const nf_u32x4 *>(cur + (wi * 128 + l31) * D6_ROW + hi * 16);
@@ -1354,10 +1339,10 @@ __device__ __forceinline__ void dw_job_b6(const DwJob &jb, const DwArgs &a, int 
           __builtin_amdgcn_sched_barrier(0);
         }
       }
-      WIDE_STAMP(tslot + 2 + g);
+      NF_STAMP(tr, tslot + 2 + g);
     }
     __syncthreads();
-    WIDE_STAMP(tslot + 6);
+    NF_STAMP(tr, tslot + 6);
     tslot += 7;
     buf ^= 1;
   }
@@ -1416,7 +1401,7 @@ __global__ __launch_bounds__(256) void k_wide_reduce(NetDims nd, const float *__
   if (e >= G::B3 + 32 * G::CB) return;
   const long ti = image_theta_index<G>(nd, e);
   if (ti < 0) return;
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;  // the flat slab sum, in place in both reduce kernels: as a shared call it reorders them
   int s = 0;
   for (; s + 3 < nslab; s += 4) {
     a0 += slab[(long)s * slab_stride + e];
@@ -1443,7 +1428,7 @@ __global__ __launch_bounds__(256) void k_wide_reduce_all(PackArgs p, const float
   const long ti = image_theta_index<G>(nd, e);
   if (ti < 0) return;
   slab += (size_t)job * nslab * slab_stride;
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;  // the flat slab sum, in place in both reduce kernels: as a shared call it reorders them
   int s = 0;
   for (; s + 3 < nslab; s += 4) {  // the order of k_wide_reduce
     a0 += slab[(long)s * slab_stride + e];

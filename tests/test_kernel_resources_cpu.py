@@ -117,3 +117,35 @@ def test_no_build_time_variant_seams_in_the_kernel_sources():
                     bad += [f"{f}:{i}: {name}" for name in re.findall(r"\b(?:NF|RQS6?)_\w+", m.group(1).split("//")[0])
                             if name not in SEAM_ALLOWED]
     assert not bad, f"build-time seams on macros outside the allow-list: {bad}"
+
+
+def _csrc_sources(suffixes):
+    csrc = os.path.join(ROOT, "normalizingflows.jl_amd", "csrc")
+    files = sorted(f for f in os.listdir(csrc) if f.endswith(suffixes))
+    assert len(files) > 10, files
+    for f in files:
+        with open(os.path.join(csrc, f)) as fh:
+            yield f, fh.read()
+
+
+def test_no_hip_file_declares_another_files_launcher():
+    """A host function of another translation unit is declared in nf_launchers.h (or nf_common.h / nf_target_stages.h), which
+    the defining file includes too, so that the compiler checks the definition against it.  A prototype of an nf_* function at
+    column 0 of a .hip file -- on one line or wrapped over several -- is a hand copy that nothing checks."""
+    bad = []
+    for f, text in _csrc_sources((".hip",)):
+        # a declaration that starts at column 0, names an nf_* function and reaches its `);` before any `{` or `;`
+        for m in re.finditer(r"^(?![ \t#/}])[^\n;{}()]*\bnf_\w+\s*\([^;{}]*\)\s*;", text, re.M):
+            bad.append(f"{f}:{text.count(chr(10), 0, m.start()) + 1}: {m.group(0).split('(')[0].strip()}")
+    assert not bad, f"prototypes of nf_* functions in .hip files (they belong in nf_launchers.h): {bad}"
+
+
+def test_no_struct_name_is_defined_in_two_files():
+    """Two different external-linkage types of one name in one shared object break the one-definition rule: harmless only while
+    every member function inlines."""
+    where = {}
+    for f, text in _csrc_sources((".hip", ".h")):
+        for name in set(re.findall(r"^\s*(?:template\s*<[^;{}]*>\s*)?struct\s+(?:__align__\(\d+\)\s+|alignas\(\d+\)\s+)?(\w+)[^;{}()]*\{", text, re.M)):
+            where.setdefault(name, []).append(f)
+    dup = {n: fs for n, fs in where.items() if len(fs) > 1}
+    assert not dup, f"struct names defined in more than one file of csrc: {dup}"

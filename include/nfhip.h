@@ -477,7 +477,8 @@ int nf_ctx_synchronize(nf_ctx *ctx);
 int64_t nf_workspace_bytes(nf_ctx *ctx, const nf_flow_desc *desc, int64_t N);
 int nf_ctx_set_arena(nf_ctx *ctx, void *arena_device, size_t bytes);
 /* The training step of the LDS-resident RealNVP path keeps the forward's activations for the reverse pass (an
- * "activation stash": 46 KiB per 32-sample tile and coupling at d = 64 / hidden 64, i.e. 772 MB at BASELINE cfg 2) --
+ * "activation stash": 46 KiB per 32-sample tile and coupling at d = 64 / hidden 64, i.e. 772 MB at BASELINE cfg 2;
+ * 42 KiB of a slot are written for every coupling but one, the rest of it is never read) --
  * the Zygote tape of src/optimize.jl:12-14 in kernel form.  max_bytes bounds the buffer: a batch whose stash is larger
  * runs chunk by chunk through it (forward + reverse pass per chunk, all chunks' gradient slabs reduced together; same
  * result up to float32 summation order).  nf_elbo_value_and_grad / nf_elbo_step and nf_loglikelihood_value_and_grad

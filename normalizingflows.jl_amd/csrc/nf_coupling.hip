@@ -235,7 +235,16 @@ __global__ __launch_bounds__(512) void k_affine_apply_b6(CouplingArgs a, const u
 //   "T layout" (x2, a1, a2 -- the dW operands): [feature 32][sample parity 2][16] per 32-feature block, so the lane
 //     that owns feature f in the dW GEMM reads its 16 k-steps (samples 2t + parity) as four 16-byte loads;
 //   "lane layout" (s, u, masks -- element-wise operands in the MFMA C layout): [lane 64][16] per block.
-// 46 KiB per (tile, coupling) for d = 64 / hidden 64: 772 MB per step at cfg 2, written once and read once.
+// 46 KiB per (tile, coupling) for d = 64 / hidden 64: 772 MB per step at cfg 2.
+// UV is WRITTEN AND READ FOR FLAT COUPLING ncoup - 1 ONLY, and holds x1 there (u = x1 exp(s) is one multiply by the exp(s) that
+// phase S of the reverse pass evaluates anyway; the inverse direction's w1 as before).  The couplings alternate halves, so the
+// half that flat coupling k transforms is the half that flat coupling k + 1 conditions on, and k + 1's slot has it as XT, stored
+// from the same registers -- the same bits.  Which slot, in both directions: the forward chain applies flat coupling ncoup - 1
+// first (coupling_at(s) = ncoup - 1 - s), so k's x1 is what k + 1, applied just before it, passed through; the inverse chain
+// applies coupling 0 first (coupling_at(s) = s), so k's output w1 is what k + 1, applied just after it, reads.  Either way the
+// neighbour of slot k is slot k + 1, and flat coupling ncoup - 1 (position 0 of the forward chain, the last position of the
+// inverse chain) has none and keeps UV.  For every other coupling the UV region of the slot stays unwritten and unread: the
+// slot keeps its size and layout, 42 KiB of the 46 are written (hidden 64), 713 MB per step at cfg 2, written once and read once.
 // SLIM (round 4; optional, NF_STASH_SLIM=1 -- see stash_slim() for the measurement that keeps it off): WITHOUT a1.  The first hidden layer's activations are 35 %
 // of the full stash (128 of 368 floats per sample and coupling) and the cheapest thing in it to rebuild: the consumer wave
 // recomputes a1^T = leakyrelu(W1 x2 + b1) from x2 -- kept a second time in the MFMA C layout (XL), which is the A operand
@@ -250,6 +259,19 @@ struct StashGeo {
   static constexpr int NET0 = UV + G::CB * 1024;  // net 0 = s, net 1 = t
   static constexpr int A1 = 0, A2 = SLIM ? 0 : G::H1B * 1024, MSK = A2 + G::H2B * 1024, NETSZ = MSK + 256;
   static constexpr int SIZE = NET0 + 2 * NETSZ;  // floats per (tile, coupling), a multiple of 4
+};
+// Store instructions a wave of the stashing forward issues per phase (= per net) of a coupling that does NOT keep UV: the s
+// net's phase stores x2 (element stores; SLIM: also XL, 16-byte stores), a1 and a2 (element stores) and the mask word, the t
+// net's phase a1, a2, the mask word and s.  affine_chain_body's phase barrier counts on them (its comment).
+//                      S_NET   T_NET   sum
+//   hidden 64            81      69    150   (73 with UV)
+//   hidden 32            49      37     86
+//   hidden 64, SLIM      53      37     90
+template <class G, bool SLIM>
+struct StashStores {
+  static constexpr int ACT = (SLIM ? 0 : G::H1B * 16) + G::H2B * 16 + 1;
+  static constexpr int S_NET = G::MB * 16 + (SLIM ? G::MB * 4 : 0) + ACT;
+  static constexpr int T_NET = ACT + G::CB * 4;
 };
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 // A buffer store of more than 64 bits must not be followed directly by a VALU write of its data registers.  hipcc's hazard
@@ -386,12 +408,19 @@ __device__ __forceinline__ void net_forward_stash(const float *__restrict__ img,
 // forward coupling of the training step: as coupling_step<G, false>, leaving the reverse pass's operands behind
 // INVERSE (forward-KL training: the chain runs data -> base): w1 = (v1 - t) exp(-s); the UV slot then holds w1, which is
 // what the reverse pass of the inverse coupling needs next to s (bwd_tile's INVD algebra)
-template <class G, bool INVERSE = false, bool SLIM = false, bool B6 = false, class BT = NoBetween>
+// keep_uv: this is flat coupling ncoup - 1, the only one whose UV region is written (x1, or w1 under INVERSE) -- every other
+// coupling's reverse pass takes the value from slot k + 1's XT (the comment above StashGeo)
+// YFMA (forward direction): the output x1 exp(s) + t as ONE fma; otherwise the rounded product, then the sum.  While u was
+// stored, the product had a second use and hipcc contracted the sum at one of the chain loop's two call sites only, the one
+// of the even flat couplings (x1 = E), in every stashing instantiation.  The call sites name that choice, so that the flow
+// output keeps its bits whatever the compiler would choose now.
+template <class G, bool INVERSE = false, bool SLIM = false, bool B6 = false, bool YFMA = false, class BT = NoBetween>
 __device__ __forceinline__ float coupling_step_stash(const float *__restrict__ img_s, const float *__restrict__ img_t,
                                                      f32x16 (&x1)[G::CB], const f32x16 (&xb)[G::MB], int l31, int hi,
-                                                     const StashIO &st, long long *tr = nullptr, BT between = BT()) {
+                                                     const StashIO &st, bool keep_uv, long long *tr = nullptr, BT between = BT()) {
   using SG = StashGeo<G, SLIM>;
   static_assert(G::H1B <= 2 && G::H2B <= 2, "mask words");
+  static_assert(G::MB == G::CB, "a neighbour's XT stands in for UV: both halves have the same padded size");
   f32x16 S[G::CB], T[G::CB];
   net_forward_stash<G, true, SLIM, B6>(img_s, xb, S, l31, hi, st, SG::NET0);
   NF_STAMP(tr, 1);
@@ -409,15 +438,16 @@ __device__ __forceinline__ float coupling_step_stash(const float *__restrict__ i
         x1[b][r] = w;
         T[b][r] = w;
       } else {
-        const float u = x1[b][r] * nf_exp(s);
-        x1[b][r] = u + T[b][r];
-        T[b][r] = u;
+#pragma clang fp contract(off)  // (YFMA, above: the contraction is stated, not left to the compiler)
+        const float x = x1[b][r], e = nf_exp(s);
+        x1[b][r] = YFMA ? __builtin_fmaf(x, e, T[b][r]) : x * e + T[b][r];
+        T[b][r] = x;  // the reverse pass forms u = x e itself
       }
       S[b][r] = s;
       lsum += s;
     }
   stash_put_lane<G::CB>(st, SG::SV, S);
-  stash_put_lane<G::CB>(st, SG::UV, T);
+  if (keep_uv) stash_put_lane<G::CB>(st, SG::UV, T);  // wave-uniform: only flat coupling ncoup - 1 has no neighbour (StashGeo)
   return lsum;
 }
 
@@ -598,9 +628,16 @@ __device__ __forceinline__ void affine_chain_body(ChainArgs a, float *xt, float 
         const int pos = s + half;
         if constexpr (B6) {
           // The phase barrier must see this wave's pieces of the image DMA complete -- NOT its stash stores: the vector-memory
-          // counter is in order, and at least 64 stores follow every DMA request of a stashing kernel (81 per s net, 73 per
-          // t net and tile), so "at most 60 operations outstanding" already implies the DMA is done, while __syncthreads()
-          // (vmcnt(0)) would drain the stores to HBM twice per coupling.  Kernels without a stash wait for everything.
+          // counter is in order, so "at most 60 operations outstanding" implies the DMA is done once 61 operations have been
+          // issued behind it, while __syncthreads() (vmcnt(0)) would drain the stores to HBM twice per coupling.  The image that
+          // the barrier of phase i waits for was requested behind the barrier of phase i - 2 (or in front of the tile group's
+          // first barrier, which drains everything): the stash stores of phases i - 2 and i - 1, one s net and one t net in
+          // either order, lie behind it, every wave issues them (an idle wave's go to a descriptor of extent 0), and the pieces
+          // of the request of phase i - 1 on top.  StashStores counts them without UV, which only flat coupling ncoup - 1
+          // stores: 81 + 69 at hidden 64, 49 + 37 at hidden 32, 53 + 37 in the SLIM layout; hidden 64 also has 61 in each phase
+          // alone.  Kernels without a stash wait for everything.
+          static_assert(!STASH || StashStores<G, SLIM>::S_NET + StashStores<G, SLIM>::T_NET >= 61,
+                        "vmcnt(60) at the phase barrier: fewer than 61 stores behind an image request");
           auto phase_barrier = [&](bool first_of_group = false) {
             if (STASH && !first_of_group) {  // (a tile group's first image may have nothing but the DMA behind it)
               __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -626,8 +663,9 @@ __device__ __forceinline__ void affine_chain_body(ChainArgs a, float *xt, float 
 #else
             long long *tr = nullptr;
 #endif
-            if (INVERSE ? (half == 1) : (half == 0)) ls = coupling_step_stash<G, INVERSE, SLIM, true>(img_s, img_t, O, E, l31, hi, st, tr, between);
-            else ls = coupling_step_stash<G, INVERSE, SLIM, true>(img_s, img_t, E, O, l31, hi, st, tr, between);
+            const bool keep_uv = coupling_at(pos) == a.ncoup - 1;
+            if (INVERSE ? (half == 1) : (half == 0)) ls = coupling_step_stash<G, INVERSE, SLIM, true, false>(img_s, img_t, O, E, l31, hi, st, keep_uv, tr, between);
+            else ls = coupling_step_stash<G, INVERSE, SLIM, true, true>(img_s, img_t, E, O, l31, hi, st, keep_uv, tr, between);
             NF_STAMP(tr, 3);
             NF_STAMP(tr, 4);
           } else {
@@ -672,8 +710,9 @@ __device__ __forceinline__ void affine_chain_body(ChainArgs a, float *xt, float 
 #else
           long long *tr = nullptr;
 #endif
-          if (INVERSE ? (half == 1) : (half == 0)) ls = coupling_step_stash<G, INVERSE, SLIM>(img_s, img_t, O, E, l31, hi, st, tr);
-          else ls = coupling_step_stash<G, INVERSE, SLIM>(img_s, img_t, E, O, l31, hi, st, tr);
+          const bool keep_uv = coupling_at(pos) == a.ncoup - 1;
+          if (INVERSE ? (half == 1) : (half == 0)) ls = coupling_step_stash<G, INVERSE, SLIM, false, false>(img_s, img_t, O, E, l31, hi, st, keep_uv, tr);
+          else ls = coupling_step_stash<G, INVERSE, SLIM, false, true>(img_s, img_t, E, O, l31, hi, st, keep_uv, tr);
           NF_STAMP(tr, 3);
           lsum += fold_ls(ls);
           __syncthreads();
@@ -1174,6 +1213,16 @@ __device__ __forceinline__ void stash_get_lane(const StashIO &st, int base, f32x
       }
     }
 }
+// a T-layout array back into the C layout it was stored from: the inverse of stash_put_T's address map, element by element
+// (per wave instruction two whole 128-byte rows, features nf_row(r, 0) and nf_row(r, 1) of the block)
+template <int NB>
+__device__ __forceinline__ void stash_get_T_as_lane(const StashIO &st, int base, f32x16 (&v)[NB]) {
+#pragma unroll
+  for (int b = 0; b < NB; ++b)
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+      v[b][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(st.rs, st.vT, (base + (b * 32 + (r & 3) + 8 * (r >> 2)) * 32) * 4, 0));
+}
 
 // dW^T accumulation with the activation operand in registers: at[ib][t] = a[feature ib*32 + l31][sample 2t + hi]
 // CORDER: k-step t contracts the sample (t & 3) + 8 (t >> 2) + 4 hi instead -- the order in which the MFMA C layout holds
@@ -1327,7 +1376,7 @@ struct BwdStashLds {
   static constexpr size_t BYTES = (size_t)FLOATS * sizeof(float);  // the fold at the end of a phase needs 4 images
 };
 
-// s and u of a phase-S tile are loaded one tile ahead, into the same registers, while the previous tile runs its last
+// s and x1 (uv; StashGeo) of a phase-S tile are loaded one tile ahead, into the same registers, while the previous tile runs its last
 // two GEMMs: every wave of the chip asks for its tile's operands at the same moment (25 MB at once), and without the
 // head start the element-wise stage waits 3.5-6.7 k cycles for them (tools/trace_bwd_stashed.py).
 // (Round 4, measured and removed: the tile's two cotangent halves requested the same way in the pair kernel's phase S -- 32
@@ -1340,9 +1389,15 @@ struct StashFirst {
 template <class G, bool SLIM = false>
 __device__ __forceinline__ void stash_issue_first(StashFirst<G> &f, float *stash, int k, int ncoup, long tile, int l31, int hi) {
   using SG = StashGeo<G, SLIM>;
+  static_assert(G::MB == G::CB, "a neighbour's XT stands in for UV");
   const StashIO st = make_stash_io(stash, tile * ncoup + k, SG::SIZE, true, l31, hi);
   stash_get_lane<G::CB>(st, SG::SV, f.sv);
-  stash_get_lane<G::CB>(st, SG::UV, f.uv);
+  if (k + 1 < ncoup) {  // wave-uniform: x1 (INVD: w1) is the conditioner input of flat coupling k + 1, in that slot's XT
+    const StashIO nb = make_stash_io(stash, tile * ncoup + k + 1, SG::SIZE, true, l31, hi);
+    stash_get_T_as_lane<G::CB>(nb, SG::XT, f.uv);
+  } else {
+    stash_get_lane<G::CB>(st, SG::UV, f.uv);
+  }
 }
 
 // INVD: reverse pass of the INVERSE coupling (forward-KL training; algebra as in bwd_tile): the UV slot holds w1, phase S
@@ -1391,9 +1446,10 @@ __device__ __forceinline__ void bwd_tile_stashed(const CouplingArgs &a, const fl
         tile_store(gio, tile_soff(b, r, a.par_t), nf_fdiv(gv, nf_exp(s)));  // v1bar
         d3[b][r] = ok ? -(gv * f.uv[b][r] + lb) * (1.f - s * s) : 0.f;     // S-bar through tanh (uv = w1)
       } else {
-        const float s = f.sv[b][r];
-        tile_store(gio, tile_soff(b, r, a.par_t), gv * nf_exp(s));  // x1bar
-        d3[b][r] = ok ? (gv * f.uv[b][r] + lb) * (1.f - s * s) : 0.f;  // S-bar through tanh
+        const float s = f.sv[b][r], e = nf_exp(s);
+        tile_store(gio, tile_soff(b, r, a.par_t), gv * e);  // x1bar
+        const float u = f.uv[b][r] * e;                      // uv = x1: the forward's own rounded product
+        d3[b][r] = ok ? (gv * u + lb) * (1.f - s * s) : 0.f;  // S-bar through tanh
       }
     }
   const unsigned mk0 = mk[0], mk1 = mk[1], mk2 = mk[2], mk3 = mk[3];
@@ -1702,9 +1758,10 @@ __device__ __forceinline__ void pair_produce(const CouplingArgs &a, const float 
         tile_store(gio, tile_soff(b, r, a.par_t), nf_fdiv(gv, nf_exp(sv)));  // v1bar (phase T's seed: stored by the last coupling, too)
         d3[b][r] = ok ? -(gv * f.uv[b][r] + lb) * (1.f - sv * sv) : 0.f;    // S-bar through tanh (uv = w1)
       } else {
-        const float sv = f.sv[b][r];
-        tile_store(gx, tile_soff(b, r, a.par_t), gv * nf_exp(sv));        // x1bar
-        d3[b][r] = ok ? (gv * f.uv[b][r] + lb) * (1.f - sv * sv) : 0.f;  // S-bar through tanh
+        const float sv = f.sv[b][r], e = nf_exp(sv);
+        tile_store(gx, tile_soff(b, r, a.par_t), gv * e);         // x1bar
+        const float u = f.uv[b][r] * e;                           // uv = x1: the forward's own rounded product
+        d3[b][r] = ok ? (gv * u + lb) * (1.f - sv * sv) : 0.f;  // S-bar through tanh
       }
     }
   if constexpr (FIRST && parked1 && !carried) {  // the bits the second phase would load: phase T never writes these slots

@@ -427,6 +427,11 @@ static int read_scalar(nf_ctx *ctx, const double *dev, double *host) {
   *host = ctx->host_scratch[0];
   return NF_OK;
 }
+// the loss of a value-and-gradient call: the sum of n block partials into slot P of `out`, in the flow's element type
+static int finish_loss(nf_ctx *ctx, int dt, const double *partial, long n, void *out, long P) {
+  if (dt == NF_DTYPE_F32) return nf_launch_finish_sum(ctx, partial, n, 0, nullptr, (float *)out + P, nullptr);
+  return nf_launch_finish_sum(ctx, partial, n, 0, (double *)out + P, nullptr, nullptr);
+}
 
 // buffers and helpers of the general-base wrappers (defined with the objectives below)
 // reserve layout L(ctx, a...) in the context workspace and carve it
@@ -479,7 +484,20 @@ static int base_draw(nf_ctx *ctx, const nf_flow_desc *desc, long N, uint64_t see
   NF_TRY(nf_launch_base_sample(ctx, desc->dtype, desc->d, N, seed, off, stream_id, x, logq_eps));
   return nf_launch_base_unwhiten(ctx, desc->dtype, b->kind, desc->d, N, b->mu, b->scale, x);
 }
-
+// The standard-normal draws of an entry point and their log q0 (logq may be null): in-library draws, or the caller's xs brought
+// into the entry point's own buffer -- converted into the tiled layout, or copied in the standard one.
+static int tiled_draw(nf_ctx *ctx, int d, long N, const void *xs, uint64_t seed, uint64_t off, uint32_t stream_id, float *xt,
+                      float *logq) {
+  if (!xs) return nf_launch_base_sample_tiled(ctx, d, N, seed, off, stream_id, xt, logq);
+  NF_TRY(nf_launch_layout_convert(ctx, d, N, (const float *)xs, xt, 1));
+  return nf_launch_base_logpdf_tiled(ctx, d, N, xt, logq);
+}
+static int flat_draw(nf_ctx *ctx, int dt, int d, long N, const void *xs, uint64_t seed, uint64_t off, uint32_t stream_id, void *x,
+                     void *logq) {
+  if (!xs) return nf_launch_base_sample(ctx, dt, d, N, seed, off, stream_id, x, logq);
+  NF_HIP(hipMemcpyAsync(x, xs, (size_t)N * d * esize(dt), hipMemcpyDeviceToDevice, ctx->stream));
+  return nf_launch_base_logpdf(ctx, dt, d, N, x, logq);
+}
 
 // standard-layout buffers of a composition's entry points, behind its segments' intermediates
 struct CompBufs {
@@ -790,14 +808,14 @@ extern "C" int nf_flow_rand(nf_ctx *ctx, const nf_flow_desc *desc, const void *t
   if (is_coupling(desc)) {
     RandBufs b;
     NF_TRY(ws_carve(ctx, &b, desc, N));
-    NF_TRY(nf_launch_base_sample_tiled(ctx, desc->d, N, seed, sample_offset, stream_id, b.xt, nullptr));
+    NF_TRY(tiled_draw(ctx, desc->d, N, nullptr, seed, sample_offset, stream_id, b.xt, nullptr));
     NF_TRY(coupling_chain_tiled(ctx, desc, false, (const float *)theta, b.xt, N, b.ladj, -1));
     return nf_launch_layout_convert(ctx, desc->d, N, b.xt, (float *)y_out, 0);
   }
   if (!is_g64(desc) && desc->kind != NF_KIND_HAMILTONIAN && !is_fr(desc))
     return nf_simple_rand(ctx, desc, theta, N, seed, sample_offset, stream_id, y_out);
   NF_TRY(nf_ws_reserve(ctx, carve_bytes((size_t)N * esize(desc->dtype))));
-  NF_TRY(nf_launch_base_sample(ctx, desc->dtype, desc->d, N, seed, sample_offset, stream_id, y_out, nullptr));
+  NF_TRY(flat_draw(ctx, desc->dtype, desc->d, N, nullptr, seed, sample_offset, stream_id, y_out, nullptr));
   return flat_apply(ctx, desc, 0, nf_layer_count(desc), false, theta, y_out, N, y_out, ctx->ws);
 }
 
@@ -897,12 +915,58 @@ static size_t tape_bytes_of(nf_ctx *ctx, const nf_flow_desc *desc, long N) {
   for (int s = 0; s < desc->nsegments; ++s) tot += tape_seg_bytes(ctx, &desc->segments[s], N);
   return tot;
 }
+// The same tape inside ONE training-step call of a matrix-pipe coupling flow, in the context workspace.  Every tiled ELBO
+// driver runs the sequence  draws -> coupling_fwd_keep -> (a wrapper's own layer) -> target -> coupling_bwd_kept,  where the
+// target launch leaves  gt = d(-elbo/Ng)/dy = -(1/Ng) grad logp(y)  and the partial sums of -elbo_j/Ng, every sample's log-det
+// cotangent is the constant -1/Ng, and nobody reads the cotangent of the draws.  The chain runs in place on the state tile, so
+// the tiled flow output needs no copy: TAPE_TILED_Y and TAPE_WIDE walk the state itself back.
+struct CouplingTape {
+  TapeKind tk = TAPE_X;
+  int grid = 0;
+  long stride = 0;
+  float *slab = nullptr, *stash = nullptr;  // gradient slabs (TAPE_WIDE: the forward's stash and the split-K area)
+  void *rqs_tape = nullptr;
+};
+static CouplingTape carve_coupling_tape(Carver &cv, nf_ctx *ctx, const nf_flow_desc *g, long N) {
+  CouplingTape t;
+  t.tk = tape_kind(ctx, g, N);
+  if (t.tk == TAPE_WIDE) {
+    t.slab = cv.take<float>(nf_wide_train_ws_floats(ctx, g, N));
+    return t;
+  }
+  t.grid = coupling_bwd_grid(ctx, g, N);
+  t.stride = coupling_slab_floats(ctx, g, N);
+  t.slab = cv.take<float>((size_t)t.grid * t.stride);
+  if (t.tk == TAPE_AFFINE_STASH) t.stash = cv.take<float>(nf_affine_stash_floats(g, N));
+  if (rqs_tape_b(g, N)) t.rqs_tape = (void *)cv.take<char>(rqs_tape_b(g, N));
+  return t;
+}
+// the chain in place on xt (packing the weights first), leaving the tape of its kind
+static int coupling_fwd_keep(nf_ctx *ctx, const nf_flow_desc *g, const float *theta_g, float *xt, long N, float *ladj,
+                             const CouplingTape &t) {
+  NF_TRY(coupling_pack(ctx, g, theta_g));
+  if (t.tk == TAPE_AFFINE_STASH) return nf_affine_chain(ctx, g, false, xt, N, ladj, t.stash);
+  if (t.tk == TAPE_WIDE) return nf_wide_train_forward(ctx, g, xt, N, ladj, t.slab);
+  if (is_nsf(g)) return nf_rqs_chain(ctx, g, false, xt, N, ladj, -1, t.rqs_tape);
+  return nf_affine_chain(ctx, g, false, xt, N, ladj);
+}
+// the reverse pass from that tape: `state` the chain's output tile, gt its cotangent, gout the flow's parameter gradient
+static int coupling_bwd_kept(nf_ctx *ctx, const nf_flow_desc *g, const float *theta_g, float *state, float *gt, float lbar_const,
+                             long N, const CouplingTape &t, float *gout) {
+  if (t.tk == TAPE_AFFINE_STASH) {
+    NF_TRY(nf_affine_bwd_stashed(ctx, g, t.stash, gt, nullptr, lbar_const, N, t.slab, t.stride, t.grid, false, true));
+    return nf_affine_reduce_slabs(ctx, g, t.slab, t.grid, gout);
+  }
+  if (t.tk == TAPE_WIDE) return nf_wide_train_backward(ctx, g, state, gt, nullptr, lbar_const, N, t.slab, gout);
+  return realnvp_bwd(ctx, g, theta_g, state, gt, nullptr, lbar_const, N, t.slab, t.grid, gout, nullptr, 0, nullptr, t.rqs_tape);
+}
 // intermediates (front of the context workspace) of the two passes
 static size_t tape_fwd_need_seg(nf_ctx *, const nf_flow_desc *g, long N) {
   return is_coupling(g) ? carve_bytes(tiled_elems(g, N) * 4) : 0;
 }
 // pullback of one segment: the flat kernels' own workspace, or the tiled cotangent with what the tape's kind adds (the
 // state the reverse pass walks back, gradient slabs, the wide path's scratch)
+// (not carve_coupling_tape: stash and spline tape are the caller's memory here, and a `state` tile is carved between gt and the slabs)
 struct TapeBwdBufs {
   TapeKind tk;
   int grid = 0;
@@ -974,6 +1038,7 @@ static int tape_fwd_seg(nf_ctx *ctx, const nf_flow_desc *g, const void *theta, c
   float *xt = (float *)ctx->ws;
   NF_TRY(nf_launch_layout_convert(ctx, g->d, N, (const float *)x_in, xt, 1));
   NF_TRY(coupling_pack(ctx, g, (const float *)theta));
+  // (not coupling_fwd_keep: the tiled flow output is copied into the tape, and the wide stash is the tape's first part)
   if (tk == TAPE_AFFINE_STASH) {
     NF_TRY(nf_affine_chain(ctx, g, false, xt, N, (float *)ladj, (float *)tape));
   } else if (tk == TAPE_WIDE) {
@@ -1000,6 +1065,7 @@ static int tape_bwd_seg(nf_ctx *ctx, const nf_flow_desc *g, const void *theta, c
   float *gt = b.gt, *state = b.state, *slab = b.slab;
   NF_TRY(coupling_pack(ctx, g, (const float *)theta));
   NF_TRY(nf_launch_layout_convert(ctx, g->d, N, (const float *)ybar, gt, 1));
+  // (not coupling_bwd_kept: a per-sample lbar, xbar wanted -- the stashed launch's flags differ -- and the wide scratch argument)
   if (tk == TAPE_AFFINE_STASH) {
     NF_TRY(nf_affine_bwd_stashed(ctx, g, (float *)const_cast<void *>(tape), gt, (const float *)lbar, (float)lbar_const, N, slab,
                                  b.stride, b.grid));
@@ -1180,12 +1246,7 @@ struct FrElboBufs {
 };
 static int fr_draw_and_forward(nf_ctx *ctx, const nf_flow_desc *desc, const void *theta, const void *xs, long N, uint64_t seed,
                                uint64_t off, uint32_t stream_id, const FrElboBufs &b) {
-  if (xs) {
-    NF_TRY(nf_launch_layout_convert(ctx, desc->d, N, (const float *)xs, b.xt, 1));
-    NF_TRY(nf_launch_base_logpdf_tiled(ctx, desc->d, N, b.xt, b.logq));
-  } else {
-    NF_TRY(nf_launch_base_sample_tiled(ctx, desc->d, N, seed, off, stream_id, b.xt, b.logq));
-  }
+  NF_TRY(tiled_draw(ctx, desc->d, N, xs, seed, off, stream_id, b.xt, b.logq));
   return nf_fr_fwd_tiled(ctx, desc, (const float *)theta, b.xt, N, b.yt, b.ladj);
 }
 static int fr_elbo_forward(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, const void *theta, const void *xs,
@@ -1205,7 +1266,6 @@ static int fr_value_and_grad(nf_ctx *ctx, const nf_flow_desc *desc, const nf_tar
   FrElboBufs b;
   NF_TRY(ws_carve(ctx, &b, desc, N, true));
   NF_TRY(fr_draw_and_forward(ctx, desc, theta, xs, N, seed, off, stream_id, b));
-  // gt = d(-elbo/Ng)/dy = -(1/Ng) grad logp(y);  partial sums of -elbo_j/Ng
   NF_TRY(nf_launch_target_tiled(ctx, target, desc->d, N, b.yt, b.logq, b.ladj, b.gt, -inv, nullptr, b.partial, -inv));
   NF_TRY(nf_launch_finish_sum(ctx, b.partial, b.nb, 0, nullptr, (float *)out + P, nullptr));
   return nf_fr_grad(ctx, desc, (const float *)theta, b.xt, 1, b.gt, 1, nullptr, (float)(-inv), N, b.slab, (float *)out);
@@ -1217,7 +1277,6 @@ static int elbo_forward(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *
   NF_CHAIN_VIEW(desc);
   if (is_composite(desc)) return elbo_forward_composite(ctx, desc, target, theta, xs, N, seed, off, stream_id, elbos_out, elbo_host);
   if (is_fr_tiled(desc)) return fr_elbo_forward(ctx, desc, target, theta, xs, N, seed, off, stream_id, elbos_out, elbo_host);
-  const size_t es = esize(desc->dtype);
   const bool cp = is_coupling(desc);
   const long nb = cp ? nf_target_tiled_nblocks(N) : nf_target_nblocks(N);
   ValueBufs b;
@@ -1232,12 +1291,7 @@ static int elbo_forward(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *
   }
   if (cp) {
     float *xt = (float *)x;
-    if (xs) {
-      NF_TRY(nf_launch_layout_convert(ctx, desc->d, N, (const float *)xs, xt, 1));
-      NF_TRY(nf_launch_base_logpdf_tiled(ctx, desc->d, N, xt, (float *)logq));
-    } else {
-      NF_TRY(nf_launch_base_sample_tiled(ctx, desc->d, N, seed, off, stream_id, xt, (float *)logq));
-    }
+    NF_TRY(tiled_draw(ctx, desc->d, N, xs, seed, off, stream_id, xt, (float *)logq));
     NF_TRY(coupling_chain_tiled(ctx, desc, false, (const float *)theta, xt, N, (float *)ladj, -1));
     NF_TRY(nf_launch_target_tiled(ctx, target, desc->d, N, xt, (const float *)logq, (const float *)ladj, nullptr, 0.0,
                                   (float *)elbos_out, partial, 1.0 / (double)N));
@@ -1250,12 +1304,7 @@ static int elbo_forward(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *
     NF_TRY(nf_launch_finish_sum(ctx, partial, np, 0, result, nullptr, nullptr));
     return read_scalar(ctx, result, elbo_host);
   } else {
-    if (xs) {
-      NF_HIP(hipMemcpyAsync(x, xs, (size_t)N * desc->d * es, hipMemcpyDeviceToDevice, ctx->stream));
-      NF_TRY(nf_launch_base_logpdf(ctx, desc->dtype, desc->d, N, x, logq));
-    } else {
-      NF_TRY(nf_launch_base_sample(ctx, desc->dtype, desc->d, N, seed, off, stream_id, x, logq));
-    }
+    NF_TRY(flat_draw(ctx, desc->dtype, desc->d, N, xs, seed, off, stream_id, x, logq));
     NF_TRY(flat_apply(ctx, desc, 0, nf_layer_count(desc), false, theta, x, N, x, ladj));
     NF_TRY(nf_launch_target(ctx, desc->dtype, target, desc->d, N, x, logq, ladj, nullptr, nullptr, 0.0, elbos_out,
                             partial, 1.0 / (double)N, joint_dims(desc)));
@@ -1445,8 +1494,7 @@ extern "C" int nf_loglikelihood_value_and_grad(nf_ctx *ctx, const nf_flow_desc *
     NF_TRY(nf_launch_target(ctx, dt, &q0, desc->d, N, z, nullptr, ladj, nullptr, gbar, -inv, nullptr, partial, -inv, 0));
     NF_TRY(nf_simple_bwd(ctx, desc, theta, z, gbar, nullptr, -inv, N, gbar, out, fws, true, true));
   }
-  if (dt == NF_DTYPE_F32) return nf_launch_finish_sum(ctx, partial, nb, 0, nullptr, (float *)out + P, nullptr);
-  return nf_launch_finish_sum(ctx, partial, nb, 0, (double *)out + P, nullptr, nullptr);
+  return finish_loss(ctx, dt, partial, nb, out, P);
 }
 
 
@@ -1592,8 +1640,7 @@ static int fkl_general(nf_ctx *ctx, const nf_flow_desc *desc, const void *theta,
     NF_TRY(nf_launch_target(ctx, dt, &q0, desc->d, N, z[ns], nullptr, ladj, nullptr, gbar, -inv, nullptr, partial, -inv, 0));
     nbl = nf_target_nblocks(N);
   }
-  if (dt == NF_DTYPE_F32) NF_TRY(nf_launch_finish_sum(ctx, partial, nbl, 0, nullptr, (float *)out + P, nullptr));
-  else NF_TRY(nf_launch_finish_sum(ctx, partial, nbl, 0, (double *)out + P, nullptr, nullptr));
+  NF_TRY(finish_loss(ctx, dt, partial, nbl, out, P));
   // the reverse pass of the inverse chain, last segment first
   for (int s = ns - 1; s >= 0; --s) {
     const void *in = s == 0 ? ys : (const void *)z[s];
@@ -1720,8 +1767,7 @@ static int value_and_grad_composite(nf_ctx *ctx, const nf_flow_desc *desc, const
   NF_TRY(tape_fwd(ctx, desc, theta, y, N, y, ladj, tape));
   // gbar = d(-elbo/Ng)/dy, loss partials
   NF_TRY(nf_launch_target(ctx, dt, target, desc->d, N, y, logq, ladj, nullptr, gbar, -inv, nullptr, partial, -inv, 0));
-  if (dt == NF_DTYPE_F32) NF_TRY(nf_launch_finish_sum(ctx, partial, nf_target_nblocks(N), 0, nullptr, (float *)out + P, nullptr));
-  else NF_TRY(nf_launch_finish_sum(ctx, partial, nf_target_nblocks(N), 0, (double *)out + P, nullptr, nullptr));
+  NF_TRY(finish_loss(ctx, dt, partial, nf_target_nblocks(N), out, P));
   return tape_bwd(ctx, desc, theta, tape, gbar, nullptr, -inv, N, gbar, out);
 }
 
@@ -1794,8 +1840,7 @@ static int value_and_grad_general_base(nf_ctx *ctx, const nf_flow_desc *desc, co
   // loss += sum_j -(corr_j) / N_global
   const size_t es = esize(desc->dtype);
   NF_TRY(nf_launch_sum2(ctx, desc->dtype, N, bb.corr, nullptr, nullptr, bb.partial, -1.0 / (double)N_global));
-  if (desc->dtype == NF_DTYPE_F32) NF_TRY(nf_launch_finish_sum(ctx, bb.partial, bb.nb, 0, nullptr, (float *)bb.tmp, nullptr));
-  else NF_TRY(nf_launch_finish_sum(ctx, bb.partial, bb.nb, 0, (double *)bb.tmp, nullptr, nullptr));
+  NF_TRY(finish_loss(ctx, desc->dtype, bb.partial, bb.nb, bb.tmp, 0));
   char *lossp = (char *)out + (size_t)P * es;
   return nf_launch_sum2(ctx, desc->dtype, 1, lossp, bb.tmp, lossp, bb.partial, 0.0);
 }
@@ -1865,17 +1910,14 @@ static inline bool precond_bwd_split(int d) {
   return forced >= 0 ? forced == 1 : d <= 32;
 }
 struct PrecondVgBufs {
-  TapeKind tk;
-  long nb, stride = 0;
-  int grid = 0;
-  float *xt, *yt, *gt, *logq, *ladj, *ladj_fr, *fr_slab, *slab, *stash = nullptr;
-  void *rqs_tape = nullptr;
+  long nb;
+  float *xt, *yt, *gt, *logq, *ladj, *ladj_fr, *fr_slab;
   double *partial, *partial_s;
+  CouplingTape tape;
   PrecondVgBufs() {}
   PrecondVgBufs(Carver &cv, nf_ctx *ctx, const nf_flow_desc *desc, long N) {
     const nf_flow_desc *g = &desc->segments[0];
     const size_t te = tiled_elems(g, N), d = (size_t)desc->d;
-    tk = tape_kind(ctx, g, N);
     nb = nf_target_tiled_nblocks(N);
     xt = cv.take<float>(te);
     yt = cv.take<float>(te);
@@ -1886,15 +1928,7 @@ struct PrecondVgBufs {
     partial = cv.take<double>(nb);
     partial_s = cv.take<double>(nf_sum2_nblocks(N));
     fr_slab = cv.take<float>((size_t)nf_fr_bwd_grid(ctx, N) * (d + d * d));
-    if (tk == TAPE_WIDE) {  // the forward's stash and the reverse pass's split-K area
-      slab = cv.take<float>(nf_wide_train_ws_floats(ctx, g, N));
-      return;
-    }
-    grid = coupling_bwd_grid(ctx, g, N);
-    stride = coupling_slab_floats(ctx, g, N);
-    slab = cv.take<float>((size_t)grid * stride);
-    if (tk == TAPE_AFFINE_STASH) stash = cv.take<float>(nf_affine_stash_floats(g, N));
-    if (rqs_tape_b(g, N)) rqs_tape = (void *)cv.take<char>(rqs_tape_b(g, N));
+    tape = carve_coupling_tape(cv, ctx, g, N);
   }
 };
 static int precond_value_and_grad(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, const void *theta, const void *xs,
@@ -1909,20 +1943,10 @@ static int precond_value_and_grad(nf_ctx *ctx, const nf_flow_desc *desc, const n
   const double inv = 1.0 / (double)N_global;
   PrecondVgBufs b;
   NF_TRY(ws_carve(ctx, &b, desc, N));
-  if (xs) {
-    NF_TRY(nf_launch_layout_convert(ctx, d, N, (const float *)xs, b.xt, 1));
-    NF_TRY(nf_launch_base_logpdf_tiled(ctx, d, N, b.xt, b.logq));
-  } else {
-    NF_TRY(nf_launch_base_sample_tiled(ctx, d, N, seed, off, stream_id, b.xt, b.logq));
-  }
-  NF_TRY(coupling_pack(ctx, g, thg));
-  if (b.tk == TAPE_AFFINE_STASH) NF_TRY(nf_affine_chain(ctx, g, false, b.xt, N, b.ladj, b.stash));
-  else if (b.tk == TAPE_WIDE) NF_TRY(nf_wide_train_forward(ctx, g, b.xt, N, b.ladj, b.slab));
-  else if (is_nsf(g)) NF_TRY(nf_rqs_chain(ctx, g, false, b.xt, N, b.ladj, -1, b.rqs_tape));
-  else NF_TRY(nf_affine_chain(ctx, g, false, b.xt, N, b.ladj));
+  NF_TRY(tiled_draw(ctx, d, N, xs, seed, off, stream_id, b.xt, b.logq));
+  NF_TRY(coupling_fwd_keep(ctx, g, thg, b.xt, N, b.ladj, b.tape));
   NF_TRY(nf_fr_fwd_tiled(ctx, fr, th, b.xt, N, b.yt, b.ladj_fr));
   NF_TRY(nf_launch_sum2(ctx, NF_DTYPE_F32, N, b.ladj, b.ladj_fr, b.ladj, b.partial_s, 0.0));
-  // gt = d(-elbo/Ng)/dy = -(1/Ng) grad logp(y);  partial sums of -elbo_j/Ng
   NF_TRY(nf_launch_target_tiled(ctx, target, d, N, b.yt, b.logq, b.ladj, b.gt, -inv, nullptr, b.partial, -inv));
   NF_TRY(nf_launch_finish_sum(ctx, b.partial, b.nb, 0, nullptr, gout + P, nullptr));
   // the full-rank layer: [g_mu ; g_L] from (xt, gt), and gt <- L' gt in place
@@ -1932,13 +1956,7 @@ static int precond_value_and_grad(nf_ctx *ctx, const nf_flow_desc *desc, const n
   } else {
     NF_TRY(nf_fr_bwd_x_tiled(ctx, fr, th, b.xt, b.gt, nullptr, (float)(-inv), N, b.fr_slab, gout, b.gt));
   }
-  // the couplings, from their tape (nobody reads the cotangent of the draws)
-  if (b.tk == TAPE_AFFINE_STASH) {
-    NF_TRY(nf_affine_bwd_stashed(ctx, g, b.stash, b.gt, nullptr, (float)(-inv), N, b.slab, b.stride, b.grid, false, true));
-    return nf_affine_reduce_slabs(ctx, g, b.slab, b.grid, gout_g);
-  }
-  if (b.tk == TAPE_WIDE) return nf_wide_train_backward(ctx, g, b.xt, b.gt, nullptr, (float)(-inv), N, b.slab, gout_g);
-  return realnvp_bwd(ctx, g, thg, b.xt, b.gt, nullptr, (float)(-inv), N, b.slab, b.grid, gout_g, nullptr, 0, nullptr, b.rqs_tape);
+  return coupling_bwd_kept(ctx, g, thg, b.xt, b.gt, (float)(-inv), N, b.tape, gout_g);
 }
 
 // A non-centred flow in Float32 whose inner flow is on the tiled kernels (the matrix-pipe couplings, or the full-rank family):
@@ -1950,13 +1968,11 @@ static inline bool nc_tiled(const nf_flow_desc *desc) {
   return is_nc(desc) && nf_nc_tiled_supported(desc) && (is_coupling(&desc->segments[0]) || is_fr_tiled(&desc->segments[0]));
 }
 struct NcVgBufs {
-  TapeKind tk = TAPE_X;
   bool fr;
-  long nb, stride = 0;
-  int grid = 0;
-  float *xt, *mid, *yt, *gt, *logq, *ladj, *ladj_s, *nc_slab, *slab, *stash = nullptr;
-  void *rqs_tape = nullptr;
+  long nb;
+  float *xt, *mid, *yt, *gt, *logq, *ladj, *ladj_s, *nc_slab, *fr_slab = nullptr;
   double *partial, *partial_s;
+  CouplingTape tape;  // a coupling inner flow's; a full-rank one has fr_slab
   NcVgBufs() {}
   NcVgBufs(Carver &cv, nf_ctx *ctx, const nf_flow_desc *desc, long N) {
     ChainView v;
@@ -1975,20 +1991,8 @@ struct NcVgBufs {
     partial = cv.take<double>(nb);
     partial_s = cv.take<double>(nf_sum2_nblocks(N));
     nc_slab = cv.take<float>(nf_nc_slab_floats(ctx, &v.seg[0], N));
-    if (fr) {
-      slab = cv.take<float>((size_t)nf_fr_bwd_grid(ctx, N) * (size_t)nf_param_count(g));
-      return;
-    }
-    tk = tape_kind(ctx, g, N);
-    if (tk == TAPE_WIDE) {  // the forward's stash and the reverse pass's split-K area
-      slab = cv.take<float>(nf_wide_train_ws_floats(ctx, g, N));
-      return;
-    }
-    grid = coupling_bwd_grid(ctx, g, N);
-    stride = coupling_slab_floats(ctx, g, N);
-    slab = cv.take<float>((size_t)grid * stride);
-    if (tk == TAPE_AFFINE_STASH) stash = cv.take<float>(nf_affine_stash_floats(g, N));
-    if (rqs_tape_b(g, N)) rqs_tape = (void *)cv.take<char>(rqs_tape_b(g, N));
+    if (fr) fr_slab = cv.take<float>((size_t)nf_fr_bwd_grid(ctx, N) * (size_t)nf_param_count(g));
+    else tape = carve_coupling_tape(cv, ctx, g, N);
   }
 };
 static int nc_value_and_grad(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, const void *theta, const void *xs, long N,
@@ -2003,53 +2007,37 @@ static int nc_value_and_grad(nf_ctx *ctx, const nf_flow_desc *desc, const nf_tar
   const double inv = 1.0 / (double)N_global;
   NcVgBufs b;
   NF_TRY(ws_carve(ctx, &b, desc, N));
-  if (xs) {
-    NF_TRY(nf_launch_layout_convert(ctx, d, N, (const float *)xs, b.xt, 1));
-    NF_TRY(nf_launch_base_logpdf_tiled(ctx, d, N, b.xt, b.logq));
-  } else {
-    NF_TRY(nf_launch_base_sample_tiled(ctx, d, N, seed, off, stream_id, b.xt, b.logq));
-  }
-  if (b.fr) {
-    NF_TRY(nf_fr_fwd_tiled(ctx, g, thg, b.xt, N, b.mid, b.ladj));
-  } else {
-    NF_TRY(coupling_pack(ctx, g, thg));
-    if (b.tk == TAPE_AFFINE_STASH) NF_TRY(nf_affine_chain(ctx, g, false, b.xt, N, b.ladj, b.stash));
-    else if (b.tk == TAPE_WIDE) NF_TRY(nf_wide_train_forward(ctx, g, b.xt, N, b.ladj, b.slab));
-    else if (is_nsf(g)) NF_TRY(nf_rqs_chain(ctx, g, false, b.xt, N, b.ladj, -1, b.rqs_tape));
-    else NF_TRY(nf_affine_chain(ctx, g, false, b.xt, N, b.ladj));
-  }
+  NF_TRY(tiled_draw(ctx, d, N, xs, seed, off, stream_id, b.xt, b.logq));
+  if (b.fr) NF_TRY(nf_fr_fwd_tiled(ctx, g, thg, b.xt, N, b.mid, b.ladj));
+  else NF_TRY(coupling_fwd_keep(ctx, g, thg, b.xt, N, b.ladj, b.tape));
   NF_TRY(nf_nc_fwd_tiled(ctx, S, lam, b.mid, N, b.yt, b.ladj_s));
   NF_TRY(nf_launch_sum2(ctx, NF_DTYPE_F32, N, b.ladj, b.ladj_s, b.ladj, b.partial_s, 0.0));
-  // gt = d(-elbo/Ng)/dy = -(1/Ng) grad logp(y);  partial sums of -elbo_j/Ng
   NF_TRY(nf_launch_target_tiled(ctx, target, d, N, b.yt, b.logq, b.ladj, b.gt, -inv, nullptr, b.partial, -inv));
   NF_TRY(nf_launch_finish_sum(ctx, b.partial, b.nb, 0, nullptr, gout + P, nullptr));
   // S: lam's gradient from (yt, gt), and gt <- the cotangent of the inner flow's output in place
   NF_TRY(nf_nc_bwd_tiled(ctx, S, lam, b.yt, b.gt, nullptr, (float)(-inv), N, b.nc_slab, gout));
   // the inner flow, from its tape (nobody reads the cotangent of the draws)
-  if (b.fr) return nf_fr_grad(ctx, g, thg, b.xt, 1, b.gt, 1, nullptr, (float)(-inv), N, b.slab, gout_g);
-  if (b.tk == TAPE_AFFINE_STASH) {
-    NF_TRY(nf_affine_bwd_stashed(ctx, g, b.stash, b.gt, nullptr, (float)(-inv), N, b.slab, b.stride, b.grid, false, true));
-    return nf_affine_reduce_slabs(ctx, g, b.slab, b.grid, gout_g);
-  }
-  if (b.tk == TAPE_WIDE) return nf_wide_train_backward(ctx, g, b.xt, b.gt, nullptr, (float)(-inv), N, b.slab, gout_g);
-  return realnvp_bwd(ctx, g, thg, b.xt, b.gt, nullptr, (float)(-inv), N, b.slab, b.grid, gout_g, nullptr, 0, nullptr, b.rqs_tape);
+  if (b.fr) return nf_fr_grad(ctx, g, thg, b.xt, 1, b.gt, 1, nullptr, (float)(-inv), N, b.fr_slab, gout_g);
+  return coupling_bwd_kept(ctx, g, thg, b.xt, b.gt, (float)(-inv), N, b.tape, gout_g);
 }
 
 struct VgBufs {
-  bool cp, wide, simple_kind, simple_step;
+  bool cp, simple_kind, simple_step;
   long nb, stash_nc;  // the target kernel's loss partials; samples per stash chunk (0: no stash)
-  int grid;
-  char *x, *gbar, *x0, *logq, *ladj, *slab, *sws;
+  char *x, *gbar, *x0, *logq, *ladj, *sws;
   double *partial;
-  float *stash;
-  void *rqs_tape;
+  float *stash;  // ONE CHUNK's stash, for stash_chunk_loop alone
+  // the tape of the routes that run the whole batch at once: NOT tape_kind() -- where a stash is kept (b.stash) it runs chunk by
+  // chunk and never through coupling_fwd_keep / coupling_bwd_kept, so tk is the kind without it and .stash stays null
+  CouplingTape unchunked_tape;
   VgBufs() {}
   VgBufs(Carver &cv, nf_ctx *ctx, const nf_flow_desc *desc, long N) {
     const size_t es = esize(desc->dtype);
     cp = is_coupling(desc);
-    wide = cp && is_wide(desc);
+    const bool wide = cp && is_wide(desc);
     nb = cp ? nf_target_tiled_nblocks(N) : nf_target_nblocks(N);
-    grid = cp ? coupling_bwd_grid(ctx, desc, N) : 0;
+    unchunked_tape.tk = !cp ? TAPE_X : wide ? TAPE_WIDE : TAPE_TILED_Y;
+    unchunked_tape.grid = cp ? coupling_bwd_grid(ctx, desc, N) : 0;
     simple_kind = !cp && !is_g64(desc) && desc->kind != NF_KIND_HAMILTONIAN && !is_fr(desc);
     // planar / radial / mean-field within the register budget: the whole step in one launch, nothing stashed
     simple_step = simple_kind && nf_simple_step_supported(desc);
@@ -2058,8 +2046,8 @@ struct VgBufs {
     // draws; caller-supplied draws take one chunk or the recompute kernel)
     stash_nc = cp ? affine_stash_chunk(ctx, desc, N) : 0;
     const size_t stash_b = stash_nc ? affine_stash_bytes(ctx, desc, stash_nc) : 0;
-    const size_t slabf = wide ? nf_wide_train_ws_floats(ctx, desc, N)
-                              : cp ? chunked_slab_floats(ctx, desc, N, stash_nc, coupling_slab_floats(ctx, desc, N)) : 0;
+    unchunked_tape.stride = cp && !wide ? coupling_slab_floats(ctx, desc, N) : 0;
+    const size_t slabf = wide ? nf_wide_train_ws_floats(ctx, desc, N) : cp ? chunked_slab_floats(ctx, desc, N, stash_nc, unchunked_tape.stride) : 0;
     const size_t xe = cp ? tiled_elems(desc, N) : simple_step ? 0 : (size_t)N * desc->d;
     const size_t rqs_b = cp ? rqs_tape_b(desc, N) : 0;
     x = cv.take<char>(xe * es);
@@ -2069,12 +2057,99 @@ struct VgBufs {
     ladj = cv.take<char>((size_t)N * es);
     partial = cv.take<double>(elbo_npartial(ctx, desc, N));
     cv.take<double>(8);  // (a result slot no path reads: kept so that every buffer behind it keeps its offset)
-    slab = cv.take<char>(slabf * es);
+    unchunked_tape.slab = (float *)cv.take<char>(slabf * es);
     sws = cv.take<char>(simple_ws);
     stash = stash_b ? cv.take<float>(stash_b / 4) : nullptr;
-    rqs_tape = rqs_b ? (void *)cv.take<char>(rqs_b) : nullptr;  // spline couplings: the forward's bins and xi
+    unchunked_tape.rqs_tape = rqs_b ? (void *)cv.take<char>(rqs_b) : nullptr;  // spline couplings: the forward's bins and xi
   }
 };
+// Float32 couplings on the matrix-pipe kernels.  Fusable (in-library draws, resident nets, a built-in target): draws, chain,
+// target and loss partials in one launch.  Otherwise the tiled sequence of CouplingTape; an LDS-resident RealNVP within the
+// stash budget runs it chunk by chunk through one chunk's stash.
+static int coupling_value_and_grad(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, const void *theta, const void *xs,
+                                   long N, long N_global, uint64_t seed, uint64_t off, uint32_t stream_id, void *out, const VgBufs &b) {
+  const long P = nf_param_count(desc);
+  const double inv = 1.0 / (double)N_global;
+  const float *th = (const float *)theta;
+  float *xt = (float *)b.x, *gt = (float *)b.gbar, *logq = (float *)b.logq, *ladj = (float *)b.ladj, *gout = (float *)out;
+  if (elbo_fusable(desc, target, xs)) {
+    NF_TRY(coupling_pack(ctx, desc, th));
+    if (b.stash) {  // forward with stash + reverse pass from it, chunk by chunk: no recompute, the state is not touched
+      ChunkCounts cc;
+      NF_TRY(stash_chunk_loop(ctx, desc, N, b.stash_nc, b.stash, gt, inv, b.unchunked_tape.slab, false, &cc, [&](long o, long nc, long npart, long *left) {
+        // (y itself is not written: the stashed reverse pass reads gt and the stash, and nothing else follows; nor is the
+        // cotangent of the draws, which a training step does not read)
+        *left = nf_affine_chain_grid(ctx, nc);
+        return fused_chain_elbo(ctx, desc, target, nc, seed, off + (uint64_t)o, stream_id, nullptr, gt + o * desc->d, -inv,
+                                b.partial + npart, -inv, b.stash);
+      }));
+      return nf_affine_reduce_slabs(ctx, desc, b.unchunked_tape.slab, (int)cc.nslab, gout, b.partial, (int)cc.npart, gout + P);
+    }
+    NF_TRY(fused_chain_elbo(ctx, desc, target, N, seed, off, stream_id, xt, gt, -inv, b.partial, -inv,
+                            is_nsf(desc) ? (float *)b.unchunked_tape.rqs_tape : nullptr));
+    if (is_nsf(desc)) {
+      NF_TRY(nf_launch_finish_sum(ctx, b.partial, fused_chain_grid(ctx, desc, N), 0, nullptr, gout + P, nullptr));
+      return realnvp_bwd(ctx, desc, th, xt, gt, nullptr, (float)(-inv), N, b.unchunked_tape.slab, b.unchunked_tape.grid, gout, nullptr, 0, nullptr, b.unchunked_tape.rqs_tape);
+    }
+    // the loss partials of the fused forward are finished by the slab-reduction launch (not coupling_bwd_kept: it passes none)
+    return realnvp_bwd(ctx, desc, th, xt, gt, nullptr, (float)(-inv), N, b.unchunked_tape.slab, b.unchunked_tape.grid, gout, b.partial,
+                       (int)nf_affine_chain_grid(ctx, N), gout + P);
+  }
+  NF_TRY(tiled_draw(ctx, desc->d, N, xs, seed, off, stream_id, xt, logq));
+  if (b.stash) {
+    // LDS-resident RealNVP with caller-supplied draws or a target other than the diagonal Gaussian: the plain forward
+    // chain leaves the stash, too -- chunk by chunk through the stash buffer like the fused form above
+    NF_TRY(coupling_pack(ctx, desc, th));
+    ChunkCounts cc;
+    NF_TRY(stash_chunk_loop(ctx, desc, N, b.stash_nc, b.stash, gt, inv, b.unchunked_tape.slab, false, &cc, [&](long o, long nc, long npart, long *left) {
+      NF_TRY(nf_affine_chain(ctx, desc, false, xt + o * desc->d, nc, ladj + o, b.stash));
+      *left = nf_target_tiled_nblocks(nc);
+      return nf_launch_target_tiled(ctx, target, desc->d, nc, xt + o * desc->d, logq + o, ladj + o, gt + o * desc->d, -inv, nullptr,
+                                    b.partial + npart, -inv);
+    }));
+    NF_TRY(nf_launch_finish_sum(ctx, b.partial, cc.npart, 0, nullptr, gout + P, nullptr));
+    return nf_affine_reduce_slabs(ctx, desc, b.unchunked_tape.slab, (int)cc.nslab, gout);
+  }
+  // wide RealNVP (the forward keeps its activations in an HBM stash, the reverse pass recomputes nothing), spline couplings,
+  // and the resident RealNVP shapes without a stash (invertible recompute)
+  NF_TRY(coupling_fwd_keep(ctx, desc, th, xt, N, ladj, b.unchunked_tape));
+  NF_TRY(nf_launch_target_tiled(ctx, target, desc->d, N, xt, logq, ladj, gt, -inv, nullptr, b.partial, -inv));
+  NF_TRY(nf_launch_finish_sum(ctx, b.partial, b.nb, 0, nullptr, gout + P, nullptr));
+  return coupling_bwd_kept(ctx, desc, th, xt, gt, (float)(-inv), N, b.unchunked_tape, gout);
+}
+// planar / radial / mean-field: the target is evaluated inside the flow's own kernels
+static int simple_value_and_grad(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, const void *theta, const void *xs,
+                                 long N, long N_global, uint64_t seed, uint64_t off, uint32_t stream_id, void *out, const VgBufs &b) {
+  const double inv = 1.0 / (double)N_global;
+  NF_TRY(nf_target_check(target, desc->d));
+  long np = 0;
+  if (b.simple_step) {
+    // draws (or xs), chain, target, ELBO sums AND the reverse pass in one launch; every layer input stays in registers, only
+    // the parameter slabs are written (k_simple_step)
+    NF_TRY(nf_simple_elbo_step(ctx, desc, target, theta, xs, N, seed, off, stream_id, -inv, -inv, b.partial, -inv, b.sws, out, &np,
+                               nullptr));
+  } else {
+    // flows beyond the register budget of k_simple_step: draws + chain + target + ELBO partial sums in one launch
+    // (the per-layer inputs stay behind for the reverse pass), then the reverse pass over all layers
+    NF_TRY(nf_simple_elbo_forward(ctx, desc, target, theta, xs, N, seed, off, stream_id, b.gbar, -inv, b.partial, -inv, b.sws, &np));
+    NF_TRY(nf_simple_bwd(ctx, desc, theta, nullptr, b.gbar, nullptr, -inv, N, b.gbar, out, b.sws, true));
+  }
+  return finish_loss(ctx, desc->dtype, b.partial, np, out, nf_param_count(desc));
+}
+// standard-layout flows with a reverse pass of their own: general couplings, Hamiltonian, the full-rank family in Float64
+static int flat_value_and_grad(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target, const void *theta, const void *xs,
+                               long N, long N_global, uint64_t seed, uint64_t off, uint32_t stream_id, void *out, const VgBufs &b) {
+  const int dt = desc->dtype;
+  const double inv = 1.0 / (double)N_global;
+  NF_TRY(flat_draw(ctx, dt, desc->d, N, xs, seed, off, stream_id, b.x0, b.logq));
+  // general couplings: the forward leaves every coupling's input in the reverse pass's workspace (no second forward)
+  const bool keep = is_g64(desc);
+  if (keep) NF_TRY(nf_g64_apply_keep(ctx, desc, theta, b.x0, N, b.x, b.ladj, b.sws));
+  else NF_TRY(flat_apply(ctx, desc, 0, nf_layer_count(desc), false, theta, b.x0, N, b.x, b.ladj));
+  NF_TRY(nf_launch_target(ctx, dt, target, desc->d, N, b.x, b.logq, b.ladj, nullptr, b.gbar, -inv, nullptr, b.partial, -inv, joint_dims(desc)));
+  NF_TRY(flat_bwd(ctx, desc, theta, keep ? nullptr : b.x0, b.gbar, nullptr, -inv, N, b.gbar, out, b.sws));
+  return finish_loss(ctx, dt, b.partial, b.nb, out, nf_param_count(desc));
+}
 extern "C" int nf_elbo_value_and_grad(nf_ctx *ctx, const nf_flow_desc *desc, const nf_target *target,
                                       const void *theta, const void *xs, int64_t N_local, int64_t N_global,
                                       uint64_t seed, uint64_t sample_offset, uint32_t stream_id, void *out) {
@@ -2096,134 +2171,13 @@ extern "C" int nf_elbo_value_and_grad(nf_ctx *ctx, const nf_flow_desc *desc, con
   if (is_composite(desc))
     return value_and_grad_composite(ctx, desc, target, theta, xs, N_local, N_global, seed, sample_offset, stream_id, out);
   const long N = N_local;
-  const long P = nf_param_count(desc);
-  const int dt = desc->dtype;
-  const size_t es = esize(dt);
-  if (N == 0) return nf_launch_fill(ctx, dt, out, P + 1, 0.0);
+  if (N == 0) return nf_launch_fill(ctx, desc->dtype, out, nf_param_count(desc) + 1, 0.0);
   if (is_fr_tiled(desc)) return fr_value_and_grad(ctx, desc, target, theta, xs, N, N_global, seed, sample_offset, stream_id, out);
-  const double inv = 1.0 / (double)N_global;
   VgBufs b;
   NF_TRY(ws_carve(ctx, &b, desc, N));
-  const bool cp = b.cp, simple_kind = b.simple_kind, simple_step = b.simple_step, wide = b.wide;
-  const long nb = b.nb;
-  const int grid = b.grid;
-  char *x = b.x, *gbar = b.gbar, *x0 = b.x0, *logq = b.logq, *ladj = b.ladj, *slab = b.slab, *sws = b.sws;
-  double *partial = b.partial;
-  float *stash = b.stash;
-  void *rqs_tape = b.rqs_tape;
-
-  if (cp && elbo_fusable(desc, target, xs)) {
-    float *xt = (float *)x, *gt = (float *)gbar;
-    NF_TRY(coupling_pack(ctx, desc, (const float *)theta));
-    if (stash) {  // forward with stash + reverse pass from it, chunk by chunk: no recompute, the state is not touched
-      ChunkCounts cc;
-      NF_TRY(stash_chunk_loop(ctx, desc, N, b.stash_nc, stash, gt, inv, (float *)slab, false, &cc, [&](long o, long nc, long npart, long *left) {
-        // (y itself is not written: the stashed reverse pass reads gt and the stash, and nothing else follows; nor is the
-        // cotangent of the draws, which a training step does not read)
-        *left = nf_affine_chain_grid(ctx, nc);
-        return fused_chain_elbo(ctx, desc, target, nc, seed, sample_offset + (uint64_t)o, stream_id, nullptr, gt + o * desc->d, -inv,
-                                partial + npart, -inv, stash);
-      }));
-      return nf_affine_reduce_slabs(ctx, desc, (const float *)slab, (int)cc.nslab, (float *)out, partial, (int)cc.npart, (float *)out + P);
-    }
-    NF_TRY(fused_chain_elbo(ctx, desc, target, N, seed, sample_offset, stream_id, xt, gt, -inv, partial, -inv,
-                            is_nsf(desc) ? (float *)rqs_tape : nullptr));
-    if (is_nsf(desc)) {
-      NF_TRY(nf_launch_finish_sum(ctx, partial, fused_chain_grid(ctx, desc, N), 0, nullptr, (float *)out + P, nullptr));
-      return realnvp_bwd(ctx, desc, (const float *)theta, xt, gt, nullptr, (float)(-inv), N, (float *)slab, grid, (float *)out,
-                         nullptr, 0, nullptr, rqs_tape);
-    }
-    // the loss partials of the fused forward are finished by the slab-reduction launch
-    return realnvp_bwd(ctx, desc, (const float *)theta, xt, gt, nullptr, (float)(-inv), N, (float *)slab, grid, (float *)out,
-                       partial, (int)nf_affine_chain_grid(ctx, N), (float *)out + P);
-  }
-  if (wide) {
-    // wide RealNVP: the forward pass keeps its activations (HBM stash), the reverse pass recomputes nothing
-    float *xt = (float *)x, *gt = (float *)gbar;
-    if (xs) {
-      NF_TRY(nf_launch_layout_convert(ctx, desc->d, N, (const float *)xs, xt, 1));
-      NF_TRY(nf_launch_base_logpdf_tiled(ctx, desc->d, N, xt, (float *)logq));
-    } else {
-      NF_TRY(nf_launch_base_sample_tiled(ctx, desc->d, N, seed, sample_offset, stream_id, xt, (float *)logq));
-    }
-    NF_TRY(coupling_pack(ctx, desc, (const float *)theta));
-    NF_TRY(nf_wide_train_forward(ctx, desc, xt, N, (float *)ladj, (float *)slab));
-    NF_TRY(nf_launch_target_tiled(ctx, target, desc->d, N, xt, (const float *)logq, (const float *)ladj, gt, -inv,
-                                  nullptr, partial, -inv));
-    NF_TRY(nf_launch_finish_sum(ctx, partial, nb, 0, nullptr, (float *)out + P, nullptr));
-    return nf_wide_train_backward(ctx, desc, xt, gt, nullptr, (float)(-inv), N, (float *)slab, (float *)out);
-  }
-  if (cp) {
-    float *xt = (float *)x, *gt = (float *)gbar;
-    if (xs) {
-      NF_TRY(nf_launch_layout_convert(ctx, desc->d, N, (const float *)xs, xt, 1));
-      NF_TRY(nf_launch_base_logpdf_tiled(ctx, desc->d, N, xt, (float *)logq));
-    } else {
-      NF_TRY(nf_launch_base_sample_tiled(ctx, desc->d, N, seed, sample_offset, stream_id, xt, (float *)logq));
-    }
-    if (stash) {
-      // LDS-resident RealNVP with caller-supplied draws or a target other than the diagonal Gaussian: the plain forward
-      // chain leaves the stash, too -- chunk by chunk through the stash buffer like the fused form above
-      NF_TRY(coupling_pack(ctx, desc, (const float *)theta));
-      ChunkCounts cc;
-      NF_TRY(stash_chunk_loop(ctx, desc, N, b.stash_nc, stash, gt, inv, (float *)slab, false, &cc, [&](long o, long nc, long npart, long *left) {
-        NF_TRY(nf_affine_chain(ctx, desc, false, xt + o * desc->d, nc, (float *)ladj + o, stash));
-        // gt = d(-elbo/Ng)/dy = -(1/Ng) grad logp(y);  partial sums of -elbo_j/Ng
-        *left = nf_target_tiled_nblocks(nc);
-        return nf_launch_target_tiled(ctx, target, desc->d, nc, xt + o * desc->d, (const float *)logq + o, (const float *)ladj + o,
-                                      gt + o * desc->d, -inv, nullptr, partial + npart, -inv);
-      }));
-      NF_TRY(nf_launch_finish_sum(ctx, partial, cc.npart, 0, nullptr, (float *)out + P, nullptr));
-      return nf_affine_reduce_slabs(ctx, desc, (const float *)slab, (int)cc.nslab, (float *)out);
-    }
-    NF_TRY(coupling_chain_tiled(ctx, desc, false, (const float *)theta, xt, N, (float *)ladj, -1, rqs_tape));
-    // gt = d(-elbo/Ng)/dy = -(1/Ng) grad logp(y);  partial sums of -elbo_j/Ng
-    NF_TRY(nf_launch_target_tiled(ctx, target, desc->d, N, xt, (const float *)logq, (const float *)ladj, gt, -inv,
-                                  nullptr, partial, -inv));
-    NF_TRY(nf_launch_finish_sum(ctx, partial, nb, 0, nullptr, (float *)out + P, nullptr));
-    NF_TRY(realnvp_bwd(ctx, desc, (const float *)theta, xt, gt, nullptr, (float)(-inv), N, (float *)slab, grid,
-                       (float *)out, nullptr, 0, nullptr, rqs_tape));
-  } else {
-    if (simple_step) {
-      // planar / radial / mean-field: draws (or xs), chain, target, ELBO sums AND the reverse pass in one launch;
-      // every layer input stays in registers, only the parameter slabs are written (k_simple_step)
-      NF_TRY(nf_target_check(target, desc->d));
-      long np = 0;
-      NF_TRY(nf_simple_elbo_step(ctx, desc, target, theta, xs, N, seed, sample_offset, stream_id, -inv, -inv, partial, -inv, sws,
-                                 out, &np, nullptr));
-      if (dt == NF_DTYPE_F32) return nf_launch_finish_sum(ctx, partial, np, 0, nullptr, (float *)out + P, nullptr);
-      return nf_launch_finish_sum(ctx, partial, np, 0, (double *)out + P, nullptr, nullptr);
-    }
-    if (simple_kind) {
-      // flows beyond the register budget of k_simple_step: draws + chain + target + ELBO partial sums in one launch
-      // (the per-layer inputs stay behind for the reverse pass), then the reverse pass over all layers
-      NF_TRY(nf_target_check(target, desc->d));
-      long np = 0;
-      NF_TRY(nf_simple_elbo_forward(ctx, desc, target, theta, xs, N, seed, sample_offset, stream_id, gbar, -inv, partial, -inv,
-                                    sws, &np));
-      NF_TRY(nf_simple_bwd(ctx, desc, theta, nullptr, gbar, nullptr, -inv, N, gbar, out, sws, true));
-      if (dt == NF_DTYPE_F32) return nf_launch_finish_sum(ctx, partial, np, 0, nullptr, (float *)out + P, nullptr);
-      return nf_launch_finish_sum(ctx, partial, np, 0, (double *)out + P, nullptr, nullptr);
-    }
-    if (xs) {
-      NF_HIP(hipMemcpyAsync(x0, xs, (size_t)N * desc->d * es, hipMemcpyDeviceToDevice, ctx->stream));
-      NF_TRY(nf_launch_base_logpdf(ctx, dt, desc->d, N, x0, logq));
-    } else {
-      NF_TRY(nf_launch_base_sample(ctx, dt, desc->d, N, seed, sample_offset, stream_id, x0, logq));
-    }
-    {
-      // general couplings: the forward leaves every coupling's input in the reverse pass's workspace (no second forward)
-      const bool keep = is_g64(desc);
-      if (keep) NF_TRY(nf_g64_apply_keep(ctx, desc, theta, x0, N, x, ladj, sws));
-      else NF_TRY(flat_apply(ctx, desc, 0, nf_layer_count(desc), false, theta, x0, N, x, ladj));
-      NF_TRY(nf_launch_target(ctx, dt, target, desc->d, N, x, logq, ladj, nullptr, gbar, -inv, nullptr, partial, -inv, joint_dims(desc)));
-      NF_TRY(flat_bwd(ctx, desc, theta, keep ? nullptr : x0, gbar, nullptr, -inv, N, gbar, out, sws));
-    }
-  }
-  if (cp) return NF_OK;
-  if (dt == NF_DTYPE_F32)
-    return nf_launch_finish_sum(ctx, partial, nb, 0, nullptr, (float *)out + P, nullptr);
-  return nf_launch_finish_sum(ctx, partial, nb, 0, (double *)out + P, nullptr, nullptr);
+  if (b.cp) return coupling_value_and_grad(ctx, desc, target, theta, xs, N, N_global, seed, sample_offset, stream_id, out, b);
+  if (b.simple_kind) return simple_value_and_grad(ctx, desc, target, theta, xs, N, N_global, seed, sample_offset, stream_id, out, b);
+  return flat_value_and_grad(ctx, desc, target, theta, xs, N, N_global, seed, sample_offset, stream_id, out, b);
 }
 
 extern "C" int nf_adam_update(nf_ctx *ctx, int32_t dtype, void *theta, const void *g, void *m, void *v, int64_t P,

@@ -6,6 +6,7 @@
 // is a fake device address that is never dereferenced (the carving code only does pointer arithmetic on it).
 // This TU includes nf_api.hip to reach its file-local functions.
 // argv[1]: tests/golden/workspace_sizes.json, the sizes of the hand-written formulas the layouts replaced (same loop; -1: n/a).
+// argv[2]: tests/golden/workspace_sizes_wrappers.json, sizes and offsets of the preconditioned / non-centred step layouts.
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -289,6 +290,63 @@ int main(int argc, char **argv) {
     }
   }
   CHECK(row * kNCol == golden.size());  // every recorded row was met
+  // ---- the tiled training step of the two wrappers over one inner flow per tape kind: the layouts' bytes, the bare inner
+  // flow's step layout, the arena bound and the offsets of the buffers the coupling tape owns, all EQUAL to the recorded ones ----
+  {
+    enum { W_WRAPPER, W_INNER, W_BUDGET, W_N, W_NEED, W_INNER_VG, W_TOTAL, W_XT, W_GT, W_SLAB, W_STASH, W_RQS, kWCol };
+    const std::vector<long long> wg = read_rows(argc > 2 ? argv[2] : "tests/golden/workspace_sizes_wrappers.json");
+    CHECK(!wg.empty() && wg.size() % kWCol == 0);
+    nf_flow_desc inner[4] = {mk(NF_KIND_REALNVP, NF_DTYPE_F32, 8, 2, {32, 32}), mk(NF_KIND_NSF, NF_DTYPE_F32, 8, 2, {32, 32}, 8, 5.f),
+                             mk(NF_KIND_REALNVP, NF_DTYPE_F32, 8, 2, {64, 32}), mk(NF_KIND_FULLRANK, NF_DTYPE_F32, 8, 1)};
+    CHECK(is_coupling(&inner[0]) && !is_wide(&inner[0]) && is_coupling(&inner[1]) && is_nsf(&inner[1]) && is_wide(&inner[2]) && is_fr_tiled(&inner[3]));
+    nf_target score;
+    std::memset(&score, 0, sizeof score);
+    score.kind = NF_TARGET_HGLM_LOGIT;
+    score.p0 = score.p1 = (void *)(uintptr_t)0x1000;  // never dereferenced
+    score.s0 = 33;
+    score.s1 = 2;
+    char *fake = (char *)(uintptr_t)0x7f0000000000ull;
+    auto off_of = [&](const void *p) { return p ? (long long)((const char *)p - fake) : -1LL; };
+    size_t wrow = 0;
+    for (int w = 0; w < 2; ++w)
+      for (int i = 0; i < (w ? 4 : 3); ++i)
+        for (long budget : {-1L, 0L}) {
+          if (budget == 0 && i != 0) continue;  // the budget decides between two tape kinds for the LDS-resident RealNVP only
+          ctx.stash_budget = budget;
+          nf_flow_desc g = mk(w ? NF_KIND_NONCENTRED : NF_KIND_PRECOND, NF_DTYPE_F32, 8, 1);
+          g.nsegments = 1;
+          g.segments = &inner[i];
+          if (w) g.score = &score;
+          CHECK(check_desc(&g) == NF_OK && (w ? nc_tiled(&g) : precond_tiled(&g)));
+          CHECK(tape_kind(&ctx, &inner[i], 33) == (i == 3 ? TAPE_X : i == 2 ? TAPE_WIDE : i == 1 || budget == 0 ? TAPE_TILED_Y : TAPE_AFFINE_STASH));
+          for (long N : {1L, 33L, 4096L}) {
+            Carver cv(fake);
+            long long o[5];
+            if (w) {
+              NcVgBufs b(cv, &ctx, &g, N);
+              const void *p[5] = {b.xt, b.gt, b.fr ? b.fr_slab : b.tape.slab, b.tape.stash, b.tape.rqs_tape};
+              for (int k = 0; k < 5; ++k) o[k] = off_of(p[k]);
+            } else {
+              PrecondVgBufs b(cv, &ctx, &g, N);
+              const void *p[5] = {b.xt, b.gt, b.tape.slab, b.tape.stash, b.tape.rqs_tape};
+              for (int k = 0; k < 5; ++k) o[k] = off_of(p[k]);
+            }
+            CHECK(cv.off == (w ? layout_bytes<NcVgBufs>(&ctx, &g, N) : layout_bytes<PrecondVgBufs>(&ctx, &g, N)));
+            CHECK(cv.off <= ws_need_bound(&ctx, &g, N));
+            if (wrow < wg.size() / kWCol) {
+              const long long *r = &wg[wrow * kWCol];
+              CHECK(r[W_WRAPPER] == w && r[W_INNER] == i && r[W_BUDGET] == budget && r[W_N] == N);
+              CHECK((long long)cv.off == r[W_NEED]);
+              CHECK((long long)layout_bytes<VgBufs>(&ctx, &inner[i], N) == r[W_INNER_VG]);
+              CHECK(nf_workspace_bytes(&ctx, &g, N) == r[W_TOTAL]);
+              CHECK(o[0] == r[W_XT] && o[1] == r[W_GT] && o[2] == r[W_SLAB] && o[3] == r[W_STASH] && o[4] == r[W_RQS]);
+            }
+            ++wrow;
+          }
+        }
+    CHECK(wrow * kWCol == wg.size());
+    ctx.stash_budget = -1;
+  }
   // ---- null / range checks of public entry points that must fail before touching a device -----------------------------
   {
     nf_flow_desc g = mk(NF_KIND_REALNVP, NF_DTYPE_F32, 64, 4, {64, 64});

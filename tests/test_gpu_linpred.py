@@ -7,6 +7,7 @@ Reference values are the float64 numpy closed forms below; whole-flow references
 (flow_fwd(keep) -> logp / score -> flow_bwd) exactly as neg_elbo_value_and_grad does.  Tolerances are tests/parity.py's.
 Float32 references are evaluated on the float32-representable inputs the device reads (the target's own W / A / mu), and
 every Float32 check passes `floor=`: the same formula evaluated in numpy float32."""
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -36,6 +37,19 @@ def vp(t):
 
 def new_ctx(nf):
     return nf.Context(0, torch.cuda.current_stream().cuda_stream)
+
+
+@contextlib.contextmanager
+def stash_budget(nf, flow, budget, n):
+    """nf_ctx_set_stash_budget(budget) on the flow's context for the block, the default policy (-1) after it; yields the bytes of
+    the flow's tape for n samples before and under the budget -- the tape kind the training step keeps follows the same test"""
+    lib = nf.load_library()
+    before = int(lib.nf_tape_bytes(flow.ctx.ptr, C.byref(flow.desc), n))
+    nf._lib.check(lib.nf_ctx_set_stash_budget(flow.ctx.ptr, budget))
+    try:
+        yield before, int(lib.nf_tape_bytes(flow.ctx.ptr, C.byref(flow.desc), n))
+    finally:
+        nf._lib.check(lib.nf_ctx_set_stash_budget(flow.ctx.ptr, -1))
 
 
 def tdt(f64):
@@ -212,6 +226,8 @@ FLOW_CASES = {
     "realnvp_d64_gauss": ("realnvp", 64, (64, 64), 2, 0, 0.0, False, "gauss", 0),      # G over two accumulator blocks
     "realnvp_d64_logreg133": ("realnvp", 64, (64, 64), 2, 0, 0.0, False, "logreg", 133),
     "nsf_d6_gauss": ("nsf", 6, (32, 32), 2, 8, 5.0, False, "gauss", 0),
+    "nsf_d6_logreg": ("nsf", 6, (32, 32), 2, 8, 5.0, False, "logreg", 33),             # the spline tape under a target launch of its own
+    "realnvp_d8_h64x32_logreg": ("realnvp", 8, (64, 32), 2, 0, 0.0, False, "logreg", 33),  # the narrowest weight-streaming shape
     "realnvp_d5_f64_gauss": ("realnvp", 5, (32, 32), 2, 0, 0.0, True, "gauss", 0),    # flat kernel, Float64 coupling path
     "realnvp_d5_f64_logreg": ("realnvp", 5, (32, 32), 2, 0, 0.0, True, "logreg", 33),
 }
@@ -233,8 +249,8 @@ def make_flow_case(nf, name):
 
 @pytest.mark.parametrize("name", list(FLOW_CASES))
 def test_value_and_gradient_through_a_coupling_flow(nf, name):
-    """value_and_gradient(elbo_batch, flow, target, xs) on caller-supplied draws at N = 33 and 97 (ragged tiles) against the
-    composed oracle; exactly one "target_linpred" launch and no "target" launch per call."""
+    """value_and_gradient(elbo_batch, flow, target, xs) on caller-supplied draws at N = 33 and 97 (ragged tiles), and on
+    in-library draws at N = 70, against the composed oracle; exactly one "target_linpred" launch and no "target" launch per call."""
     spec, th, flow, tgt, ref, f64 = make_flow_case(nf, name)
     for n in (33, 97):
         xs = o.base_sample(spec.d, n, 77, 0, 0)
@@ -262,6 +278,19 @@ def test_value_and_gradient_through_a_coupling_flow(nf, name):
             xs32, th32 = P.f32(xs), P.f32(th)
             y32, l32_, _ = o.flow_fwd(spec, th32, xs32, keep=True)
             P.elementwise(key + ": elbos", elbos, e_ref, floor=ref(y32)[0] - o.std_normal_logpdf(xs32) + l32_)
+    # in-library draws: the oracle on the same draws, with the same launch shape
+    n = 70
+    (loss, g), counts = prof_counts(nf, flow.ctx, lambda: nf.value_and_gradient(nf.elbo_batch, flow, tgt, n, rng=nf.PhiloxRNG(41)))
+    assert counts == {"target_linpred": 1, "target": 0}, counts
+    xd = nf.device_specific_rand(nf.PhiloxRNG(41), flow.dist, n, dtype=tdt(f64)).double().cpu().numpy()
+    key = f"linpred flow {name} N={n} in-library draws"
+    l_ref, g_ref = composed_neg_elbo(spec, th, ref, xd)
+    if f64:
+        P.scalar(key + ": loss", loss, l_ref, P.F64_RTOL)
+        P.gradient(key + ": grad", g, g_ref, P.F64_GRAD)
+    else:
+        P.scalar(key + ": loss", loss, l_ref)
+        P.gradient(key + ": grad", g, g_ref, floor=composed_neg_elbo(spec, P.f32(th), ref, P.f32(xd))[1])
 
 
 # ---- 3. known answer -------------------------------------------------------------------------------------------------------------

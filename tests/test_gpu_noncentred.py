@@ -15,7 +15,7 @@ import noncentred_ref as ncr
 import parity as P
 from __graft_entry__ import load_package
 from test_gpu_fullrank import bits, host, tag, vec
-from test_gpu_linpred import new_ctx, tdt, to_dev, vp
+from test_gpu_linpred import new_ctx, stash_budget, tdt, to_dev, vp
 
 pytestmark = pytest.mark.gpu
 
@@ -214,10 +214,22 @@ def check_vg(key, spec, theta, x, ref, f64, loss, grad):
     assert bool((grad[torch.tensor(ncr.fixed_mask(spec), device="cuda")] == 0.0).all()), key
 
 
-@cases(TILED + ["flat32", "single"])
+# "small-realnvp-budget0": that case under nf_ctx_set_stash_budget(0) -- the LDS-resident nets on the invertible-recompute
+# reverse kernel, with both draw sources
+@cases(TILED + ["small-realnvp-budget0", "flat32", "single"])
 def test_elbo_value_and_gradient(nf, name, f64):
+    if name.endswith("-budget0"):
+        name = name[:-len("-budget0")]
+        _, n, _, _, flow = case(nf, name, f64)[:5]
+        with stash_budget(nf, flow, 0, n) as (kept, recompute):
+            assert 0 < recompute < kept, (kept, recompute)  # the tiled flow output instead of the activation stash: the budget took
+            return elbo_value_and_gradient(nf, name, f64, "small-realnvp budget(0)")
+    elbo_value_and_gradient(nf, name, f64, name)
+
+
+def elbo_value_and_gradient(nf, name, f64, label):
     spec, n, theta, x, flow, xs, tgt, ref = case(nf, name, f64)
-    key = f"noncentred vg {name} {tag(f64)}"
+    key = f"noncentred vg {label} {tag(f64)}"
     loss, grad = nf.value_and_gradient(nf.elbo_batch, flow, tgt, xs)
     torch.cuda.synchronize()
     check_vg(key + " xs", spec, theta, x, ref, f64, loss, grad)
@@ -244,10 +256,16 @@ def test_a_target_other_than_the_layers_own(nf):
     """S reads its groups from the flow's target; the ELBO target of the entry points may be any other the inner flow is served with"""
     from test_gpu_fullrank import device_target
 
-    spec, n, theta, x, flow, xs, _, _ = case(nf, "small-realnvp", False)
-    tgt, ref = device_target(nf, "diaggauss", spec.d, False)
-    loss, grad = nf.value_and_gradient(nf.elbo_batch, flow, tgt, xs)
-    check_vg("noncentred vg small-realnvp diaggauss", spec, theta, x, ref, False, loss, grad)
+    # every inner family on the tiled kernels (stash, spline tape, weight-streaming stash, full-rank), both draw sources
+    for name in ("small-realnvp", "small-nsf", "wide-realnvp", "small-fullrank"):
+        spec, n, theta, x, flow, xs, _, _ = case(nf, name, False)
+        tgt, ref = device_target(nf, "diaggauss", spec.d, False)
+        loss, grad = nf.value_and_gradient(nf.elbo_batch, flow, tgt, xs)
+        check_vg(f"noncentred vg {name} diaggauss", spec, theta, x, ref, False, loss, grad)
+        l_rng, g_rng = nf.value_and_gradient(nf.elbo_batch, flow, tgt, n, rng=nf.PhiloxRNG(41))
+        xd = nf.device_specific_rand(nf.PhiloxRNG(41), flow.dist, n, dtype=tdt(False))
+        torch.cuda.synchronize()
+        check_vg(f"noncentred vg {name} diaggauss rng", spec, theta, host(xd), ref, False, l_rng, g_rng)
 
 
 def test_under_a_stash_budget_that_splits_the_bare_flows_step(nf):

@@ -22,7 +22,7 @@ import parity as P
 import precond_ref as pr
 from __graft_entry__ import ROOT, load_package
 from test_gpu_fullrank import bits, device_target, host, tag, vec
-from test_gpu_linpred import new_ctx, prof_counts, tdt, to_dev, vp
+from test_gpu_linpred import new_ctx, prof_counts, stash_budget, tdt, to_dev, vp
 
 pytestmark = pytest.mark.gpu
 
@@ -192,8 +192,20 @@ def targets_of(name, d):
     return ["diaggauss"] + (extra if name in ("stash", "spline", "wide") else [])
 
 
-@cases(TILED + ["envelope", "flat32", "grid-stride", "single"])
+# "stash-budget0": the stash case under nf_ctx_set_stash_budget(0) -- the LDS-resident two-hidden-layer nets on the
+# invertible-recompute reverse kernel, the tape kind no other case here reaches ("recompute" is a one-hidden-layer net)
+@cases(TILED + ["stash-budget0", "envelope", "flat32", "grid-stride", "single"])
 def test_elbo_value_and_gradient(nf, name, f64):
+    if name.endswith("-budget0"):
+        name = name[:-len("-budget0")]
+        spec, n, _, _, flow, _ = case(nf, name, f64)
+        with stash_budget(nf, flow, 0, n) as (kept, recompute):
+            assert 0 < recompute < kept, (kept, recompute)  # the tiled flow output instead of the activation stash: the budget took
+            return elbo_value_and_gradient(nf, name, f64)
+    elbo_value_and_gradient(nf, name, f64)
+
+
+def elbo_value_and_gradient(nf, name, f64):
     spec, n, theta, x, flow, xs = case(nf, name, f64)
     for tname in targets_of(name, spec.d):
         tgt, ref = device_target(nf, tname, spec.d, f64)

@@ -68,6 +68,7 @@ const NF_TARGET_DGLM_NORMAL, NF_TARGET_DGLM_STUDENT, NF_TARGET_DGLM_NEGBIN =
 const NF_TARGET_ORDINAL_LOGIT = Int32(32)                             # ordinal (cumulative-logit) regression (nfhip.h)
 const NF_TARGET_RISKSET = Int32(33)                                   # risk-set regression: Cox, conditional logit (nfhip.h)
 const NF_RISKSET_MAXR = 8192
+const NF_TARGET_MIXGLM = Int32(35)                                    # mixed-family GLM: a row function per 32-row block (nfhip.h); 34 is unassigned
 dtype_code(::Type{Float32}) = Int32(0)
 dtype_code(::Type{Float64}) = Int32(1)
 

@@ -403,6 +403,33 @@ extern "C" {
  * tests/test_riskset_cpu.py evaluates this definition and holds it at 33. */
 #define NF_TARGET_RISKSET (NF_TARGET_ORDINAL_LOGIT + 1)
 #define NF_RISKSET_MAXR 8192
+/* Mixed-family GLM: the generalised linear-predictor form with a row function PER 32-ROW BLOCK, so that a likelihood, non-Gaussian
+ * priors on coefficients (Cauchy / Student-t / Laplace: a prior on y_j is the row e_j / scale), structured or improper Gaussian
+ * penalties (-y' S y / 2 as the rows of a factor R, R'R = S, S singular allowed), a second outcome family (joint models) and the
+ * check function of quantile regression sit in ONE matrix product.
+ *   y in R^d, d <= 256;  R rows in B = R / 32 blocks, block b with a family code f_b and a family parameter q_b:
+ *       log p(y) = par[1] + sum_b sum_{i in b} wt_i phi_{f_b}(u_i; q_b) + lin . y - |y|^2 / (2 s1^2),   u = A y + off
+ *       grad     = A' (wt o phi') + lin - y / s1^2
+ *   f = 0 log sigmoid | 1 log Phi | 2 -exp | 3 Student, q = nu | 4 -u^2 / 2 (the row functions of NF_TARGET_GLM_*, unchanged) |
+ *       5 the check function phi(u; tau) = -u (tau - [u < 0]), phi' = -(tau - [u < 0]), q = tau in (0, 1); at u = 0 the bracket is 0.
+ *   The isotropic prior's normaliser -d/2 log(2 pi s1^2) is NOT added by the library: the host folds it (and every component's
+ *   normaliser) into par[1].  s1 = +inf is the flat prior.
+ *   p1 = A[R x d] row-major, the rows SORTED BY FAMILY and every (family, parameter) run padded to whole 32-row blocks with rows of
+ *   weight 0 and zero features;  s0 = R (an integer value, 32 <= R < 2^31, R % 32 == 0);  s1 = the prior sigma (> 0, +inf: flat);
+ *   p0 = ONE buffer of d + 2 R + 2 R/32 + 2 elements in the flow's element type, distinct from p1:
+ *       lin[d] | off[R] | wt[R] | fam[R/32] | bpar[R/32] | par[2]          (par[0] unused, 0; fam holds integer-valued elements)
+ *   NF_ERR_ARG for a NULL p0 / p1, p0 == p1, an s0 that is not a positive integer multiple of 32 fitting an int, an s1 that is not
+ *   > 0 (NaN included) or d < 1; then NF_ERR_UNSUPPORTED for d > 256 -- both before any device work.  The host cannot validate
+ *   device memory: a block whose code is outside 0 .. 5 (NaN included) contributes exactly nothing (phi = phi' = 0 by select, its
+ *   rows are not multiplied); nothing is addressed through the code.
+ * A row with wt_i == 0 contributes exactly 0 to the value and to the gradient by select.  Nothing is clamped.  Served exactly like
+ * NF_TARGET_GLM_*: nf_target_logp, RealNVP / NSF flows of either element type including the weight-streaming shapes, full-rank and
+ * preconditioned flows, general bases and compositions; nf_elbo_step runs the split sequence, nf_elbo_step_enqueue answers
+ * NF_ERR_UNSUPPORTED; planar, radial, mean-field and Hamiltonian flows answer NF_ERR_UNSUPPORTED at every ELBO entry point, a
+ * Hamiltonian score included.  A non-centring layer does not take it; nf_target_minibatch answers NF_ERR_UNSUPPORTED.
+ * The value is 35: kind 34 stays unassigned (tests/test_riskset_cpu.py and tests/test_minibatch_cpu.py hold it at "no kind"), hence
+ * one step for it and one for this kind; tests/test_mixed_glm_cpu.py evaluates this definition and holds it at 35. */
+#define NF_TARGET_MIXGLM (NF_TARGET_RISKSET + 1 + 1)
 
 #define NF_MAX_HIDDEN 4
 
@@ -584,7 +611,7 @@ int nf_target_logp(nf_ctx *ctx, int32_t dtype, const nf_target *target, int32_t 
  *   host-folded full-data terms stay exact, a weight-0 row stays exactly dropped, and m = R gives the full buffers bit for bit.
  * Kinds: NF_TARGET_GLM_*, NF_TARGET_SOFTMAX, NF_TARGET_HGLM_*, NF_TARGET_BNN_*, NF_TARGET_DGLM_*.  NF_ERR_UNSUPPORTED for the kinds
  *   without a per-row weight (0 .. 6, 8) or whose rows are not exchangeable (NF_TARGET_ORDINAL_LOGIT: label blocks;
- *   NF_TARGET_RISKSET: rows interact).
+ *   NF_TARGET_RISKSET: rows interact; NF_TARGET_MIXGLM: family blocks, and a block may be a prior, which must not be subsampled).
  * p0_elems: the element count of full->p0 (the negative-binomial table length lives in device memory: it is derived from this).
  * p0_out: p0_elems - nper (R - m) elements, nper the number of per-row segments of the kind's p0;  p1_out: m x w, w the row width
  *   of p1 (d; d / C for SOFTMAX; (d - 1) / H - 1 for BNN).  idx_out (optional, int32[m]) receives idx.  idx_in (optional, int32[m],

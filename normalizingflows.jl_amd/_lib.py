@@ -49,6 +49,11 @@ NF_TARGET_ORDINAL_LOGIT = 32
 # s0 = R (a multiple of 32, at most 8192); s1 = the prior sigma (+inf: flat)
 NF_TARGET_RISKSET = 33
 NF_RISKSET_MAXR = 8192
+# mixed-family GLM: the generalised form with a row function per 32-row block; p1 = A[R, d] with the rows sorted by family and every
+# (family, parameter) run padded to whole 32-row blocks by rows of weight 0; p0 = lin[d] | off[R] | wt[R] | fam[R/32] | bpar[R/32] |
+# par[2] (par = (0, const)); s0 = R, s1 = the prior sigma (+inf: flat; its normaliser is folded into const by the host).  Family codes:
+# 0 logit, 1 probit, 2 poisson, 3 student, 4 normal, 5 check.  Kind 34 stays unassigned.
+NF_TARGET_MIXGLM = 35
 NF_MAX_HIDDEN = 4
 NF_ERR_NONFINITE = -4
 

@@ -105,6 +105,17 @@ struct PhiStudent {
   }
 };
 
+// -u (tau - [u < 0]) ; -(tau - [u < 0])  (the check function of quantile regression, tau = par in (0, 1); tau = 1/2 is -|u| / 2, the
+// Laplace prior and median regression).  Only the mixed-family kind (nf_mixglm.hip) has it.  At u = 0 the bracket is 0.
+struct PhiCheck {
+  template <class T>
+  static __device__ __forceinline__ void eval(T u, T tau, T &phi, T &dphi) {
+    const T s = tau - (u < (T)0 ? (T)1 : (T)0);
+    phi = -u * s;
+    dphi = -s;
+  }
+};
+
 // The row data of the generalised form, addressed inside the one buffer p0 = lin[d] | off[rows] | wt[rows] | par[2].
 template <class T>
 struct GlmRows {

@@ -1782,6 +1782,177 @@ class ConditionalLogitTarget(RiskSetTarget):
         return e / torch.zeros_like(top).index_add_(0, idx, e)[idx]
 
 
+_MIX_CODES = {"logit": 0, "probit": 1, "poisson": 2, "student": 3, "normal": 4, "check": 5}
+
+
+class GLMBlock:
+    """Rows of ONE family for a MixedGLMTarget: sum_i weights_i phi(u_i; param) + const with u = A z + offset.  family: GLMTarget's
+    five ("student": param = nu > 0) or "check", phi(u; tau) = -u (tau - [u < 0]) with param = tau in (0, 1) (tau = 1/2: -|u| / 2).
+    A [rows, d] Float32 or Float64; offset, weights (>= 0; 0 drops the row exactly) per row, of A's element type and device.  A block
+    is host data (float64) with the element type and device its target will have; it owns no device buffer."""
+
+    def __init__(self, family, A, offset=None, weights=None, param=0.0, const=0.0, _name="GLMBlock"):
+        if family not in _MIX_CODES:
+            raise NFHipError(f"{_name}: family must be one of {sorted(_MIX_CODES)}")
+        A64 = _glm_matrix(_name, A)
+        rows = A64.shape[0]
+        self._set(family, A64, _glm_vector(_name, "offset", offset, A, rows, 0.0), _glm_vector(_name, "weights", weights, A, rows, 1.0, nonneg=True),
+                  param, const, A.dtype, A.device, _name)
+
+    def _set(self, family, A64, off, wt, param, const, dtype, device, name):
+        self.const = _glm_scalar(name, "const", const, positive=False)
+        self.param = _glm_scalar(name, "param", param, positive=family in ("student", "check"))
+        if family == "check" and not self.param < 1.0:
+            raise NFHipError(f"{name}: the check function's param (tau) must be in (0, 1)")
+        self.family, self.A64, self.off, self.wt, self.dtype, self.device = family, A64, off, wt, dtype, device
+        self.rows, self.d = A64.shape
+
+    @classmethod
+    def _host(cls, family, A64, off, wt, param, const, like, name):
+        """a block from float64 host rows, for the element type and device of `like`"""
+        if not isinstance(like, torch.Tensor) or like.dtype not in (torch.float32, torch.float64):
+            raise NFHipError(f"{name}: `like` must be a Float32 or Float64 tensor (it gives the element type and the device)")
+        b = cls.__new__(cls)
+        b._set(family, A64, off, wt, param, const, like.dtype, like.device, name)
+        return b
+
+
+def _per_coefficient(name, what, v, n, positive=False):
+    a = np.full(n, float(v)) if np.isscalar(v) else np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v, dtype=np.float64)
+    if a.shape != (n,) or not np.isfinite(a).all() or (positive and (a <= 0).any()):
+        raise NFHipError(f"{name}: {what} must be a finite number or vector of length {n}" + (" > 0" if positive else ""))
+    return a
+
+
+def coefficient_prior(family, d, like, index=None, loc=0.0, scale=1.0, param=None):
+    """Independent priors on coefficients as a GLMBlock: one row e_j / scale_j with offset -loc_j / scale_j per coefficient j of `index`
+    (default: all d), the log normaliser in const.  family: "normal" N(loc, scale^2); "student" t_nu(loc, scale), param = nu (1: Cauchy);
+    "check": Laplace(loc, scale), density exp(-|z - loc| / scale) / (2 scale), through the check function at tau = 1/2 with
+    u = 2 (z - loc) / scale.  `like` gives the element type and device."""
+    nm = "coefficient_prior"
+    if family not in ("normal", "student", "check"):
+        raise NFHipError(f"{nm}: family must be 'normal', 'student' or 'check' (Laplace)")
+    idx = np.arange(d) if index is None else np.asarray(index.cpu() if isinstance(index, torch.Tensor) else index).reshape(-1)
+    if idx.size < 1 or idx.dtype.kind not in "iu" or (idx < 0).any() or (idx >= d).any():
+        raise NFHipError(f"{nm}: index must hold integers in 0..{d - 1}")
+    n = idx.size
+    lc, sc = _per_coefficient(nm, "loc", loc, n), _per_coefficient(nm, "scale", scale, n, positive=True)
+    if family == "student":
+        if param is None:
+            raise NFHipError(f"{nm}: the Student-t prior needs param = nu")
+        nu = _glm_scalar(nm, "param", param)
+        const = n * (math.lgamma(0.5 * (nu + 1.0)) - math.lgamma(0.5 * nu) - 0.5 * math.log(nu * math.pi)) - float(np.log(sc).sum())
+    elif family == "normal":
+        nu, const = 0.0, -0.5 * n * math.log(2.0 * math.pi) - float(np.log(sc).sum())
+    else:
+        nu, const = 0.5, -float(np.log(2.0 * sc).sum())
+    k = 2.0 if family == "check" else 1.0
+    A = np.zeros((n, d))
+    A[np.arange(n), idx] = k / sc
+    return GLMBlock._host(family, torch.from_numpy(A), torch.from_numpy(-k * lc / sc), torch.ones(n, dtype=torch.float64), nu, const, like, nm)
+
+
+def gaussian_penalty(S, like):
+    """The quadratic penalty -z' S z / 2 (P-spline / GAM penalties, random-walk and ICAR priors) as a "normal" GLMBlock: the rows of a
+    float64 factor R with R' R = S, from the eigendecomposition of the symmetric positive SEMI-definite S (eigenvalues below
+    1e-12 lambda_max are dropped: S may be singular, the prior improper).  No normaliser is added."""
+    nm = "gaussian_penalty"
+    S64 = np.asarray(S.detach().cpu() if isinstance(S, torch.Tensor) else S, dtype=np.float64)
+    if S64.ndim != 2 or S64.shape[0] != S64.shape[1] or S64.shape[0] < 1 or not np.isfinite(S64).all():
+        raise NFHipError(f"{nm}: S must be a finite square matrix")
+    if not np.allclose(S64, S64.T, rtol=1e-6, atol=1e-12 * (np.abs(S64).max() + 1)):
+        raise NFHipError(f"{nm}: S is not symmetric")
+    lam, V = np.linalg.eigh(0.5 * (S64 + S64.T))
+    if not lam[-1] > 0 or lam[0] < -1e-10 * lam[-1]:
+        raise NFHipError(f"{nm}: S is not positive semi-definite (or is zero)")
+    keep = lam > 1e-12 * lam[-1]
+    R = np.sqrt(lam[keep])[:, None] * V[:, keep].T
+    n = R.shape[0]
+    return GLMBlock._host("normal", torch.from_numpy(np.ascontiguousarray(R)), torch.zeros(n, dtype=torch.float64), torch.ones(n, dtype=torch.float64),
+                          0.0, 0.0, like, nm)
+
+
+class MixedGLMTarget(_LinpredTarget):
+    """The mixed-family GLM target (NF_TARGET_MIXGLM): a sum of GLM components with DIFFERENT row functions in one posterior,
+        logp(z) = const + sum_c sum_{i in c} weights_i phi_c(u_i; param_c) + lin . z + log N(z; 0, prior_sigma^2 I),   u = A z + offset
+    components: GLMBlocks (coefficient_prior, gaussian_penalty build them) or existing GLMTarget instances of any subclass -- a
+    GLMTarget contributes its rows, its lin, its const and its isotropic prior; precisions and normalisers add, in float64.  All
+    components share d, the element type and the device.  prior_sigma = math.inf (the default) adds no prior of the target's own.
+    The host sorts the rows by (family, param), pads every such run to whole 32-row blocks with rows of weight 0 and zero features,
+    and folds every normaliser into the constant; the device reads `A` [rows, d] (`rows` is the PADDED count) and ONE buffer
+    `p0` = lin | offset | weights | fam[rows / 32] | bpar[rows / 32] | (0, const), both kept alive here.  `families` names every
+    block's family, `prior_sigma` is the combined isotropic prior's (math.inf: none)."""
+
+    def __init__(self, components, lin=None, const=0.0, prior_sigma=math.inf, _name="MixedGLMTarget"):
+        nm = _name
+        comps = list(components) if isinstance(components, (list, tuple)) else [components]
+        if not comps or not all(isinstance(c, (GLMBlock, GLMTarget)) for c in comps):
+            raise NFHipError(f"{nm}: components must be a non-empty sequence of GLMBlock / GLMTarget instances")
+        first = comps[0]
+        d = first.d
+        dtype, device = (first.dtype, first.device) if isinstance(first, GLMBlock) else (first.A.dtype, first.A.device)
+        like = torch.empty(0, dtype=dtype, device=device)
+        total = _glm_scalar(nm, "const", const, positive=False)
+        ln = _glm_vector(nm, "lin", lin, like, d, 0.0).clone()
+        prec, runs = 0.0, {}
+        for sg in [_glm_scalar(nm, "prior_sigma", prior_sigma, allow_inf=True)] + [c.prior_sigma for c in comps if isinstance(c, GLMTarget)]:
+            if not math.isinf(sg):
+                prec += 1.0 / sg**2
+                total += -0.5 * d * math.log(2.0 * math.pi * sg**2)
+        for c in comps:
+            if isinstance(c, GLMTarget):
+                cd, cdt, cdev, p64 = c.d, c.A.dtype, c.A.device, c.p0.detach().to("cpu", torch.float64)
+                A64, off, wt = c.A.detach().to("cpu", torch.float64), p64[c.d:c.d + c.rows], p64[c.d + c.rows:c.d + 2 * c.rows]
+                ln += p64[:c.d]
+                param = float(p64[-2])
+                total += float(p64[-1])
+            else:
+                cd, cdt, cdev, A64, off, wt, param = c.d, c.dtype, c.device, c.A64, c.off, c.wt, c.param
+                total += c.const
+            if cd != d or cdt != dtype or cdev != device:
+                raise NFHipError(f"{nm}: all components must share d, the element type and the device")
+            runs.setdefault((_MIX_CODES[c.family], param), []).append((A64, off, wt))
+        if d > 256:
+            raise NFHipError(f"{nm}: d = {d} exceeds the kernels' 256")
+        As, offs, wts, fam, bpar = [], [], [], [], []
+        for (code, param), parts in sorted(runs.items()):
+            n = sum(p[0].shape[0] for p in parts)
+            pad = -n % 32
+            As += [p[0] for p in parts] + [torch.zeros((pad, d), dtype=torch.float64)]
+            offs += [p[1] for p in parts] + [torch.zeros(pad, dtype=torch.float64)]
+            wts += [p[2] for p in parts] + [torch.zeros(pad, dtype=torch.float64)]
+            fam += [float(code)] * ((n + pad) // 32)
+            bpar += [param] * ((n + pad) // 32)
+        names = {v: k for k, v in _MIX_CODES.items()}
+        self.d, self.const, self.precision = d, total, prec
+        self.prior_sigma = math.inf if prec == 0.0 else 1.0 / math.sqrt(prec)
+        self.families = [names[int(f)] for f in fam]
+        self.A = torch.cat(As).to(dtype).to(device).contiguous()
+        self.rows = self.A.shape[0]
+        self.p0 = torch.cat([ln, torch.cat(offs), torch.cat(wts), torch.tensor(fam + bpar + [0.0, total], dtype=torch.float64)]).to(dtype).to(device).contiguous()
+        self.c = Target(_lib.NF_TARGET_MIXGLM, self.p0.data_ptr(), self.A.data_ptr(), float(self.rows), self.prior_sigma)
+
+
+class QuantileRegressionTarget(MixedGLMTarget):
+    """Posterior of Bayesian quantile regression at level tau in (0, 1): the asymmetric-Laplace working likelihood
+    t_i ~ ALD(x_i . z, scale, tau), density tau (1 - tau) / scale exp(-rho_tau((t - x . z) / scale)), under N(0, prior_sigma^2 I).
+    One "check" block with u = (t - X z) / scale and const = sum_i w_i (log(tau (1 - tau)) - log scale)."""
+
+    def __init__(self, X, t, tau, scale=1.0, weights=None, prior_sigma=1.0):
+        nm = "QuantileRegressionTarget"
+        X64 = _glm_matrix(nm, X)
+        n = X64.shape[0]
+        tv = _glm_vector(nm, "t", t, X, n)
+        tau = _glm_scalar(nm, "tau", tau)
+        if not tau < 1.0:
+            raise NFHipError(f"{nm}: tau must be in (0, 1)")
+        scale = _glm_scalar(nm, "scale", scale)
+        w = _glm_vector(nm, "weights", weights, X, n, 1.0, nonneg=True)
+        const = float(w.sum()) * (math.log(tau * (1.0 - tau)) - math.log(scale))
+        self.tau, self.scale = tau, scale
+        super().__init__([GLMBlock._host("check", -X64 / scale, tv / scale, w, tau, const, X, nm)], None, 0.0, prior_sigma, _name=nm)
+
+
 def minibatch_segments(target):
     """The layout nf_target_minibatch gathers, for a target it serves: (segments, weight_segment, w) -- the segments of `target.p0`
     in order as (per_row, length) pairs (a per-row segment has length target.rows), the position of the weight segment among them,

@@ -69,6 +69,8 @@ const NF_TARGET_ORDINAL_LOGIT = Int32(32)                             # ordinal 
 const NF_TARGET_RISKSET = Int32(33)                                   # risk-set regression: Cox, conditional logit (nfhip.h)
 const NF_RISKSET_MAXR = 8192
 const NF_TARGET_MIXGLM = Int32(35)                                    # mixed-family GLM: a row function per 32-row block (nfhip.h); 34 is unassigned
+const NF_TARGET_DR_NORMAL, NF_TARGET_DR_STUDENT, NF_TARGET_DR_ZIPOISSON, NF_TARGET_DR_WEIBULL =
+    Int32(36), Int32(37), Int32(38), Int32(39)                        # distributional regression: two linear predictors per row (nfhip.h)
 dtype_code(::Type{Float32}) = Int32(0)
 dtype_code(::Type{Float64}) = Int32(1)
 

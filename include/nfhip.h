@@ -430,6 +430,34 @@ extern "C" {
  * The value is 35: kind 34 stays unassigned (tests/test_riskset_cpu.py and tests/test_minibatch_cpu.py hold it at "no kind"), hence
  * one step for it and one for this kind; tests/test_mixed_glm_cpu.py evaluates this definition and holds it at 35. */
 #define NF_TARGET_MIXGLM (NF_TARGET_RISKSET + 1 + 1)
+/* Distributional regression (GAMLSS; brms' bf(y ~ x, sigma ~ z), zi ~ z, shape ~ z): TWO linear predictors per data row, joined in a
+ * bivariate row function whose two partial derivatives feed two gradient blocks.
+ *   y = [beta (p) ; gamma (q)] in R^d, d = p + q <= 256, p >= 1, q >= 1;   u = X beta + offu,   v = Z gamma + offv
+ *       log p(y) = par[1] + sum_i wt_i phi(u_i, v_i; a_i, par[3]) + lin . y - par[0] |beta|^2 / 2 - par[2] |gamma|^2 / 2
+ *       grad     = [X' (wt o phi_u) ; Z' (wt o phi_v)] + lin - [par[0] beta ; par[2] gamma]
+ *   NF_TARGET_DR_NORMAL     phi = -u^2 exp(-2 v) / 2 - v                               u = x . beta - t, sigma = exp(v)
+ *   NF_TARGET_DR_STUDENT    phi = -(nu + 1)/2 log1p(u^2 exp(-2 v) / nu) - v            nu = par[3] > 0
+ *   NF_TARGET_DR_ZIPOISSON  phi = (a ? logaddexp(v, -exp(u)) : -exp(u)) - softplus(v)  a = [count_i == 0], v the logit of the structural
+ *                                                                                      zero; sum_i wt_i k_i u_i is linear in y: lin / par[1]
+ *   NF_TARGET_DR_WEIBULL    phi = a (v + w) - exp(w), w = u exp(v)                     a the event flag, u = log t - x . beta, v = log shape
+ *   The host folds signs, normalisers and everything linear in y (in float64) into lin and par[1]; par[0], par[2] are the two prior
+ *   PRECISIONS (0: flat), whose normalisers the host folds too.
+ *   p1 = A[R x d] row-major, A = [X | Z];  s0 = R (an integer value, 1 <= R < 2^31);  s1 = p (an integer value in 1 .. d - 1);
+ *   p0 = ONE buffer of 4 R + d + 4 elements in the flow's element type, distinct from p1:
+ *       offu[R] | offv[R] | wt[R] | aux[R] | lin[d] | par[4]               (aux: 0 / 1; NORMAL and STUDENT do not read it)
+ *   NF_ERR_ARG for a NULL p0 / p1, p0 == p1, an s0 that is not a positive integer fitting an int, or an s1 that is NaN, not an integer
+ *   or outside 1 .. d - 1; then NF_ERR_UNSUPPORTED for d > 256 -- both before any device work.
+ * A row with wt_i == 0 contributes exactly 0 to the value and to both gradient blocks by select.  Nothing is clamped: u exp(-v) and
+ * u exp(v) are formed before they are squared / exponentiated, and every exponential of ZIPOISSON's zero branch has a non-positive
+ * argument, so the result is finite wherever the element type can hold the value itself.  Served exactly like NF_TARGET_GLM_*:
+ * nf_target_logp, RealNVP / NSF flows of either element type including the weight-streaming shapes, full-rank and preconditioned flows,
+ * general bases and compositions; nf_elbo_step runs the split sequence, nf_elbo_step_enqueue answers NF_ERR_UNSUPPORTED; planar, radial,
+ * mean-field and Hamiltonian flows answer NF_ERR_UNSUPPORTED at every ELBO entry point.  nf_target_minibatch answers NF_ERR_UNSUPPORTED
+ * (for now: A has the GLM kinds' shape, so the gather is a table entry away).  tests/test_distreg_cpu.py holds the values at 36 .. 39. */
+#define NF_TARGET_DR_NORMAL (NF_TARGET_MIXGLM + 1)
+#define NF_TARGET_DR_STUDENT (NF_TARGET_MIXGLM + 2)
+#define NF_TARGET_DR_ZIPOISSON (NF_TARGET_MIXGLM + 3)
+#define NF_TARGET_DR_WEIBULL (NF_TARGET_MIXGLM + 4)
 
 #define NF_MAX_HIDDEN 4
 
@@ -611,7 +639,8 @@ int nf_target_logp(nf_ctx *ctx, int32_t dtype, const nf_target *target, int32_t 
  *   host-folded full-data terms stay exact, a weight-0 row stays exactly dropped, and m = R gives the full buffers bit for bit.
  * Kinds: NF_TARGET_GLM_*, NF_TARGET_SOFTMAX, NF_TARGET_HGLM_*, NF_TARGET_BNN_*, NF_TARGET_DGLM_*.  NF_ERR_UNSUPPORTED for the kinds
  *   without a per-row weight (0 .. 6, 8) or whose rows are not exchangeable (NF_TARGET_ORDINAL_LOGIT: label blocks;
- *   NF_TARGET_RISKSET: rows interact; NF_TARGET_MIXGLM: family blocks, and a block may be a prior, which must not be subsampled).
+ *   NF_TARGET_RISKSET: rows interact; NF_TARGET_MIXGLM: family blocks, and a block may be a prior, which must not be subsampled;
+ *   NF_TARGET_DR_*: not built yet).
  * p0_elems: the element count of full->p0 (the negative-binomial table length lives in device memory: it is derived from this).
  * p0_out: p0_elems - nper (R - m) elements, nper the number of per-row segments of the kind's p0;  p1_out: m x w, w the row width
  *   of p1 (d; d / C for SOFTMAX; (d - 1) / H - 1 for BNN).  idx_out (optional, int32[m]) receives idx.  idx_in (optional, int32[m],

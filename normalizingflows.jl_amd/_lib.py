@@ -54,6 +54,10 @@ NF_RISKSET_MAXR = 8192
 # par[2] (par = (0, const)); s0 = R, s1 = the prior sigma (+inf: flat; its normaliser is folded into const by the host).  Family codes:
 # 0 logit, 1 probit, 2 poisson, 3 student, 4 normal, 5 check.  Kind 34 stays unassigned.
 NF_TARGET_MIXGLM = 35
+# distributional regression: two linear predictors per row, u = X beta + offu and v = Z gamma + offv over y = [beta (p); gamma (q)];
+# p1 = A[R, d] = [X | Z]; p0 = offu[R] | offv[R] | wt[R] | aux[R] | lin[d] | par[4] (par = (precision of beta, const, precision of
+# gamma, nu)); s0 = R, s1 = p
+NF_TARGET_DR_NORMAL, NF_TARGET_DR_STUDENT, NF_TARGET_DR_ZIPOISSON, NF_TARGET_DR_WEIBULL = 36, 37, 38, 39
 NF_MAX_HIDDEN = 4
 NF_ERR_NONFINITE = -4
 

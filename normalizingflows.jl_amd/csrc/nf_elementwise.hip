@@ -671,6 +671,14 @@ int nf_target_check(const nf_target *t, int d) {
       if (!(t->p0 && t->p1 && t->p0 != t->p1 && t->s1 > 0 && t->s0 >= 32 && t->s0 < 2147483648.0 && t->s0 == (double)(long)t->s0 && (long)t->s0 % 32 == 0 && d >= 1))
         return NF_ERR_ARG;
       return d > 256 ? NF_ERR_UNSUPPORTED : NF_OK;  // what no kernel of nf_mixglm.hip serves: answered here, before any device work
+    case NF_TARGET_DR_NORMAL:
+    case NF_TARGET_DR_STUDENT:
+    case NF_TARGET_DR_ZIPOISSON:
+    case NF_TARGET_DR_WEIBULL:  // s0 = the number of rows R, a positive integer that fits an int; s1 = p, an integer in 1 .. d - 1 (NaN fails both comparisons); A = [X | Z] (p1) and the row buffer (p0) are two buffers
+      if (!(t->p0 && t->p1 && t->p0 != t->p1 && t->s0 >= 1 && t->s0 < 2147483648.0 && t->s0 == (double)(long)t->s0 && t->s1 >= 1 && t->s1 <= (double)d - 1 &&
+            t->s1 == (double)(long)t->s1))
+        return NF_ERR_ARG;
+      return d > 256 ? NF_ERR_UNSUPPORTED : NF_OK;  // what no kernel of nf_distreg.hip serves: answered here, before any device work
     default: return NF_ERR_ARG;
   }
 }
@@ -691,6 +699,7 @@ int nf_launch_target(nf_ctx *ctx, int dtype, const nf_target *t, int d, long N, 
     if (target_is_ordinal(t->kind)) return nf_launch_target_ordinal(a);
     if (target_is_riskset(t->kind)) return nf_launch_target_riskset(a);
     if (target_is_mixglm(t->kind)) return nf_launch_target_mixglm(a);
+    if (target_is_distreg(t->kind)) return nf_launch_target_distreg(a);
     return nf_launch_target_linpred(a);
   }
   ProfScope ps(ctx, "target");
@@ -816,6 +825,7 @@ int nf_launch_target_tiled(nf_ctx *ctx, const nf_target *t, int d, long N, const
   if (target_is_ordinal(t->kind)) return nf_launch_target_ordinal_tiled(a);
   if (target_is_riskset(t->kind)) return nf_launch_target_riskset_tiled(a);
   if (target_is_mixglm(t->kind)) return nf_launch_target_mixglm_tiled(a);
+  if (target_is_distreg(t->kind)) return nf_launch_target_distreg_tiled(a);
   if (target_is_linpred(t->kind)) return nf_launch_target_linpred_tiled(a);
   ProfScope ps(ctx, "target");
   hipLaunchKernelGGL(k_target_tiled, dim3((unsigned)nf_target_tiled_nblocks(N)), dim3(EW_BLOCK), 0, ctx->stream,

@@ -152,9 +152,12 @@ __host__ __device__ inline bool target_is_riskset(int kind) { return kind == NF_
 // So is the mixed-family GLM kind (NF_TARGET_MIXGLM, nf_mixglm.hip): the generalised form with the row function a property of a 32-row
 // block, dispatched once per block inside the kernel instead of once per launch.
 __host__ __device__ inline bool target_is_mixglm(int kind) { return kind == NF_TARGET_MIXGLM; }
+// So are the distributional kinds (NF_TARGET_DR_NORMAL .. NF_TARGET_DR_WEIBULL, nf_distreg.hip): two linear predictors per row, over two
+// blocks of y, meeting in a bivariate row function whose two partial derivatives feed two gradient blocks.
+__host__ __device__ inline bool target_is_distreg(int kind) { return kind >= NF_TARGET_DR_NORMAL && kind <= NF_TARGET_DR_WEIBULL; }
 __host__ __device__ inline bool target_has_own_kernel(int kind) {
   return target_is_linpred(kind) || kind == NF_TARGET_GAUSSMIX || kind == NF_TARGET_SOFTMAX || target_is_bnn(kind) || target_is_ordinal(kind) ||
-         target_is_riskset(kind) || target_is_mixglm(kind);
+         target_is_riskset(kind) || target_is_mixglm(kind) || target_is_distreg(kind);
 }
 // widest flow the mixture's tiled kernel serves (two U and two G blocks in registers); the flat kernel goes to 256
 #define NF_MIXTURE_TILED_MAXD 64

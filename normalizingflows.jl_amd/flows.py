@@ -1953,6 +1953,149 @@ class QuantileRegressionTarget(MixedGLMTarget):
         super().__init__([GLMBlock._host("check", -X64 / scale, tv / scale, w, tau, const, X, nm)], None, 0.0, prior_sigma, _name=nm)
 
 
+_DR_KINDS = {"normal": _lib.NF_TARGET_DR_NORMAL, "student": _lib.NF_TARGET_DR_STUDENT, "zipoisson": _lib.NF_TARGET_DR_ZIPOISSON,
+             "weibull": _lib.NF_TARGET_DR_WEIBULL}
+
+
+def _dr_second(name, X, Z, n):
+    """the second design matrix as float64 on the host: Z = None is a column of ones (one learned sigma / probability / shape)"""
+    if Z is None:
+        return torch.ones((n, 1), dtype=torch.float64)
+    Z64 = _glm_matrix(name, Z)
+    if Z64.shape[0] != n or Z.dtype != X.dtype or Z.device != X.device:
+        raise NFHipError(f"{name}: Z must have X's rows, element type and device")
+    return Z64
+
+
+class DistributionalRegressionTarget(_LinpredTarget):
+    """The distributional regression target (NF_TARGET_DR_*): two linear predictors per row, over z = [beta (p) ; gamma (q)], d = p + q:
+        logp(z) = const + sum_i weights_i phi(u_i, v_i; aux_i, param) + lin . z + log N(beta; 0, prior_sigma^2 I) + log N(gamma; 0, prior_sigma_aux^2 I),
+        u = X beta + offset_u,   v = Z gamma + offset_v
+    family: "normal"     phi = -u^2 exp(-2 v) / 2 - v                                (u the residual, exp(v) its scale)
+            "student"    phi = -(nu + 1)/2 log1p(u^2 exp(-2 v) / nu) - v             (param = nu > 0)
+            "zipoisson"  phi = (aux ? logaddexp(v, -exp(u)) : -exp(u)) - softplus(v) (aux = [count == 0], v the logit of the structural zero)
+            "weibull"    phi = aux (v + w) - exp(w), w = u exp(v)                    (aux the event flag, exp(v) the shape)
+    X [rows, p], Z [rows, q] (None: a column of ones); offset_u, offset_v, weights (>= 0; 0 drops the row exactly), aux (0 / 1) per
+    row; lin (d,); all of X's element type and device.  Either prior sigma may be math.inf (flat).  The device reads `A` = [X | Z]
+    [rows, d] and ONE buffer `p0` = offset_u | offset_v | weights | aux | lin | (1 / prior_sigma^2, const', 1 / prior_sigma_aux^2,
+    param), const' = const plus the two priors' normalisers; both are kept alive here."""
+
+    def __init__(self, family, X, Z=None, offset_u=None, offset_v=None, weights=None, aux=None, lin=None, const=0.0, param=0.0, prior_sigma=1.0,
+                 prior_sigma_aux=1.0, _name="DistributionalRegressionTarget"):
+        nm = _name
+        if family not in _DR_KINDS:
+            raise NFHipError(f"{nm}: family must be one of {sorted(_DR_KINDS)}")
+        X64 = _glm_matrix(nm, X)
+        rows, p = X64.shape
+        Z64 = _dr_second(nm, X, Z, rows)
+        q = Z64.shape[1]
+        d = p + q
+        if d > 256:
+            raise NFHipError(f"{nm}: d = {d} exceeds the kernels' 256")
+        ou, ov = _glm_vector(nm, "offset_u", offset_u, X, rows, 0.0), _glm_vector(nm, "offset_v", offset_v, X, rows, 0.0)
+        wt = _glm_vector(nm, "weights", weights, X, rows, 1.0, nonneg=True)
+        ax = _glm_vector(nm, "aux", aux, X, rows, 0.0)
+        if bool(((ax != 0) & (ax != 1)).any()):
+            raise NFHipError(f"{nm}: aux must hold 0 / 1 flags")
+        ln = _glm_vector(nm, "lin", lin, X, d, 0.0)
+        const = _glm_scalar(nm, "const", const, positive=False)
+        param = _glm_scalar(nm, "param", param, positive=family == "student")
+        self.prior_sigma = _glm_scalar(nm, "prior_sigma", prior_sigma, allow_inf=True)
+        self.prior_sigma_aux = _glm_scalar(nm, "prior_sigma_aux", prior_sigma_aux, allow_inf=True)
+        prec = []
+        for sg, n in ((self.prior_sigma, p), (self.prior_sigma_aux, q)):
+            prec.append(0.0 if math.isinf(sg) else 1.0 / sg**2)
+            const += 0.0 if math.isinf(sg) else -0.5 * n * math.log(2.0 * math.pi * sg**2)
+        self.family, self.d, self.p, self.q, self.rows, self.param, self.const = family, d, p, q, rows, param, const
+        self.A = torch.cat([X64, Z64], 1).to(X.dtype).to(X.device).contiguous()
+        self.p0 = torch.cat([ou, ov, wt, ax, ln, torch.tensor([prec[0], const, prec[1], param], dtype=torch.float64)]).to(X.dtype).to(X.device).contiguous()
+        self.c = Target(_DR_KINDS[family], self.p0.data_ptr(), self.A.data_ptr(), float(rows), float(p))
+
+    def unpack(self, y):
+        """(beta [p], gamma [q]) of a parameter vector y (d,) -- or ([p, N], [q, N]) of a batch (d, N)"""
+        if y.shape[0] != self.d:
+            raise NFHipError(f"{type(self).__name__}.unpack: expected {self.d} leading elements, got {y.shape[0]}")
+        return y[:self.p], y[self.p:]
+
+    def predictors(self, y, Xnew, Znew=None):
+        """the two linear predictors (Xnew beta, Znew gamma) in plain torch: [rows] each for a vector y, [rows, N] for a batch (d, N)"""
+        Znew = torch.ones((Xnew.shape[0], 1), dtype=Xnew.dtype, device=Xnew.device) if Znew is None else Znew
+        if Xnew.dim() != 2 or Xnew.shape[1] != self.p or Znew.dim() != 2 or Znew.shape != (Xnew.shape[0], self.q):
+            raise NFHipError(f"{type(self).__name__}.predict: Xnew [rows, {self.p}], Znew [rows, {self.q}]")
+        beta, gamma = self.unpack(y)
+        return Xnew @ beta, Znew @ gamma
+
+    predict = predictors
+
+
+def _dr_fold(nm, X, Z, weights):
+    X64 = _glm_matrix(nm, X)
+    n = X64.shape[0]
+    return X64, _dr_second(nm, X, Z, n), n, _glm_vector(nm, "weights", weights, X, n, 1.0, nonneg=True), (lambda t: t.to(X.dtype).to(X.device))
+
+
+class LocationScaleRegressionTarget(DistributionalRegressionTarget):
+    """Posterior of heteroscedastic regression: t_i ~ N(x_i . beta, sigma_i^2) with log sigma_i = z_i . gamma -- or
+    (t_i - x_i . beta) / sigma_i ~ t_nu when `nu` is given.  Folds to the "normal" / "student" family with offset_u = -t and the
+    normaliser sum_i w_i (-log(2 pi) / 2, or lgamma((nu+1)/2) - lgamma(nu/2) - log(nu pi)/2) in the constant.  Z = None: one learned sigma.
+    predict returns (mean, sigma)."""
+
+    def __init__(self, X, t, Z=None, nu=None, weights=None, prior_sigma=1.0, prior_sigma_aux=1.0):
+        nm = "LocationScaleRegressionTarget"
+        X64, Z64, n, w, to = _dr_fold(nm, X, Z, weights)
+        tv = _glm_vector(nm, "t", t, X, n)
+        if nu is None:
+            fam, par, c = "normal", 0.0, -0.5 * math.log(2.0 * math.pi)
+        else:
+            par = _glm_scalar(nm, "nu", nu)
+            fam, c = "student", math.lgamma(0.5 * (par + 1.0)) - math.lgamma(0.5 * par) - 0.5 * math.log(par * math.pi)
+        super().__init__(fam, X, to(Z64), to(-tv), None, to(w), None, None, float(w.sum()) * c, par, prior_sigma, prior_sigma_aux, _name=nm)
+
+    def predict(self, y, Xnew, Znew=None):
+        eta, zeta = self.predictors(y, Xnew, Znew)
+        return eta, torch.exp(zeta)
+
+
+class ZeroInflatedPoissonTarget(DistributionalRegressionTarget):
+    """Posterior of zero-inflated Poisson regression: k_i = 0 with probability pi_i = sigmoid(z_i . gamma), else k_i ~ Poisson(exposure_i
+    exp(x_i . beta)).  Folds to the "zipoisson" family with offset_u = log exposure, aux = [k_i == 0], lin = sum_i w_i k_i x_i and
+    const = sum_i w_i (k_i offset_i - lgamma(k_i + 1)) (a zero count adds nothing to either).  Z = None: one learned probability.
+    predict returns (rate, pi)."""
+
+    def __init__(self, X, counts, Z=None, exposure=None, weights=None, prior_sigma=1.0, prior_sigma_aux=1.0):
+        nm = "ZeroInflatedPoissonTarget"
+        X64, Z64, n, w, to = _dr_fold(nm, X, Z, weights)
+        k = _glm_vector(nm, "counts", counts, X, n, nonneg=True)
+        if bool((k != torch.round(k)).any()):
+            raise NFHipError(f"{nm}: counts must be integers")
+        off = torch.log(_glm_vector(nm, "exposure", exposure, X, n, 1.0, positive=True))
+        lin = torch.cat([(w * k) @ X64, torch.zeros(Z64.shape[1], dtype=torch.float64)])
+        const = float((w * (k * off - torch.lgamma(k + 1.0))).sum())
+        super().__init__("zipoisson", X, to(Z64), to(off), None, to(w), to((k == 0).to(torch.float64)), to(lin), const, 0.0, prior_sigma, prior_sigma_aux, _name=nm)
+
+    def predict(self, y, Xnew, Znew=None):
+        eta, zeta = self.predictors(y, Xnew, Znew)
+        return torch.exp(eta), torch.sigmoid(zeta)
+
+
+class WeibullRegressionTarget(DistributionalRegressionTarget):
+    """Posterior of Weibull (accelerated-failure-time) regression with right censoring: T_i ~ Weibull(shape k_i = exp(z_i . gamma),
+    scale exp(x_i . beta)); event_i = 1 contributes the log density at time_i, event_i = 0 the log survival function.  Folds to the
+    "weibull" family with X -> -X, offset_u = log t, aux = event and const = -sum_i w_i event_i log t_i.  Z = None: one learned shape.
+    predict returns (scale, shape)."""
+
+    def __init__(self, X, time, event, Z=None, weights=None, prior_sigma=1.0, prior_sigma_aux=1.0):
+        nm = "WeibullRegressionTarget"
+        X64, Z64, n, w, to = _dr_fold(nm, X, Z, weights)
+        lt = torch.log(_glm_vector(nm, "time", time, X, n, positive=True))
+        ev = _glm_vector(nm, "event", event, X, n)
+        super().__init__("weibull", to(-X64), to(Z64), to(lt), None, to(w), to(ev), None, -float((w * ev * lt).sum()), 0.0, prior_sigma, prior_sigma_aux, _name=nm)
+
+    def predict(self, y, Xnew, Znew=None):  # (the device's matrix is -X, so the first p coordinates of y ARE beta)
+        eta, zeta = self.predictors(y, Xnew, Znew)
+        return torch.exp(eta), torch.exp(zeta)
+
+
 def minibatch_segments(target):
     """The layout nf_target_minibatch gathers, for a target it serves: (segments, weight_segment, w) -- the segments of `target.p0`
     in order as (per_row, length) pairs (a per-row segment has length target.rows), the position of the weight segment among them,

@@ -458,6 +458,46 @@ extern "C" {
 #define NF_TARGET_DR_STUDENT (NF_TARGET_MIXGLM + 2)
 #define NF_TARGET_DR_ZIPOISSON (NF_TARGET_MIXGLM + 3)
 #define NF_TARGET_DR_WEIBULL (NF_TARGET_MIXGLM + 4)
+/* GLM targets with CORRELATED random effects (lme4's y ~ x + (1 + x | g), brms / rstanarm's default): the k effects b_g of a level
+ * share a learned covariance D R D, D = diag exp(tau), R = L L' a correlation matrix with an LKJ(eta) prior.
+ *   y = [beta (p) ; term 1 ; .. ; term F ; (lambda)] in R^d, d <= 256, 1 <= F <= 4; a term is b [G x k, level-major: the k effects of a
+ *   level are contiguous] ; tau [k] ; omega [k (k - 1) / 2], 1 <= k <= 4 (k = 1: a plain varying intercept, no omega).
+ *       u        = A y + off
+ *       log p(y) = par[1] + sum_i wt_i phi(u_i; par[0] [, lambda]) + lin . y - sum_j fom_j y_j^2 / 2
+ *                  + sum_f [ -sum_g |L^-1 D^-1 b_g|^2 / 2 - G (sum_i tau_i + sum_i log L_ii) + sum_i h_i(tau_i - hm_i)
+ *                            + sum_{i>j} c_ij log(1 - tanh^2 omega_ij) ]   [ + h(lambda - hm) ]
+ *   L is built from z = tanh omega by stick-breaking, omega in row-major strict-lower order (1,0), (2,0), (2,1), (3,0), ..:
+ *   L_00 = 1; in row i, rem = 1, L_ij = z_ij sqrt(rem), rem -= L_ij^2 (j < i), L_ii = sqrt(rem) -- torch's CorrCholeskyTransform.
+ *   c_ij = eta + (k - 2 - j) / 2 (j the 0-based column) is LKJ(eta) over omega with its Jacobian; the host folds the normaliser, every
+ *   -(G k / 2) log 2 pi and every hyper-prior normaliser into par[1] in float64.  h_i is one of the hierarchical kinds' three
+ *   hyper-prior forms (code 0 log-normal, 1 half-normal, 2 half-Cauchy on exp(tau_i), as densities over tau_i).  fom_j is the
+ *   fixed prior precision of coordinate j (0: flat; 0 for every coordinate of a term).
+ *   NF_TARGET_CRE_LOGIT / PROBIT / POISSON / STUDENT / NORMAL: the GLM kinds' row functions with the family parameter par[0].
+ *   NF_TARGET_CRE_DNORMAL / DSTUDENT: the dispersion kinds' phi(u exp(-lambda)), lambda = y[d - 1] the learned residual log-scale
+ *   with the hyper-prior lamh = (code, hm, his, 0); the -(sum_i wt_i) lambda of the normalisers is folded into lin[d - 1].
+ *   p1 = A[rows x d] row-major;  s0 = rows (an integer value, 1 <= rows < 2^31);  s1 = F (an integer value in 1 .. 4);
+ *   p0 = ONE buffer of 2 d + 2 rows + 104 elements in the flow's element type, distinct from p1:
+ *       lin[d] | off[rows] | wt[rows] | par[4] | fom[d] | tab[4][24] | lamh[4]
+ *   tab[f] = k | G | first index of b | of tau | of omega | c[6] | code[4] | hm[4] | his[4] | 0   (entries of unused slots: 0).
+ *   NF_ERR_ARG for a NULL p0 / p1, p0 == p1, a bad s0, an s1 that is NaN, non-integral or outside 1 .. 4, or d < 2 for the two
+ *   dispersion kinds; then NF_ERR_UNSUPPORTED for d > 256 -- both before any device work.  The host cannot validate device
+ *   memory: every index read from the table is bounded by select before it addresses anything; a term whose k is outside 1 .. 4
+ *   or whose blocks do not lie inside y's d features is skipped.
+ * Nothing is clamped and nothing is computed as a difference of near-equal values: tanh, sech and log sech come from
+ * exp(-2 |omega|), the stick's remainder is a product of sech's, L^-1 is a forward substitution; Sigma^-1 is never formed.
+ * A row with wt_i == 0 contributes exactly 0 by select.  No atomics: two launches give the same bits.  Served exactly like
+ * NF_TARGET_HGLM_*: nf_target_logp, RealNVP / NSF flows of either element type including the weight-streaming shapes, full-rank
+ * and preconditioned flows, general bases and compositions; nf_elbo_step runs the split sequence, nf_elbo_step_enqueue answers
+ * NF_ERR_UNSUPPORTED; planar, radial, mean-field and Hamiltonian flows answer NF_ERR_UNSUPPORTED at every ELBO entry point;
+ * nf_target_minibatch answers NF_ERR_UNSUPPORTED; a non-centring layer (flow kind 10) answers NF_ERR_ARG for these targets.
+ * tests/test_correff_cpu.py holds the values at 40 .. 46. */
+#define NF_TARGET_CRE_LOGIT (NF_TARGET_DR_WEIBULL + 1)
+#define NF_TARGET_CRE_PROBIT (NF_TARGET_DR_WEIBULL + 2)
+#define NF_TARGET_CRE_POISSON (NF_TARGET_DR_WEIBULL + 3)
+#define NF_TARGET_CRE_STUDENT (NF_TARGET_DR_WEIBULL + 4)
+#define NF_TARGET_CRE_NORMAL (NF_TARGET_DR_WEIBULL + 5)
+#define NF_TARGET_CRE_DNORMAL (NF_TARGET_DR_WEIBULL + 6)
+#define NF_TARGET_CRE_DSTUDENT (NF_TARGET_DR_WEIBULL + 7)
 
 #define NF_MAX_HIDDEN 4
 
@@ -640,7 +680,7 @@ int nf_target_logp(nf_ctx *ctx, int32_t dtype, const nf_target *target, int32_t 
  * Kinds: NF_TARGET_GLM_*, NF_TARGET_SOFTMAX, NF_TARGET_HGLM_*, NF_TARGET_BNN_*, NF_TARGET_DGLM_*.  NF_ERR_UNSUPPORTED for the kinds
  *   without a per-row weight (0 .. 6, 8) or whose rows are not exchangeable (NF_TARGET_ORDINAL_LOGIT: label blocks;
  *   NF_TARGET_RISKSET: rows interact; NF_TARGET_MIXGLM: family blocks, and a block may be a prior, which must not be subsampled;
- *   NF_TARGET_DR_*: not built yet).
+ *   NF_TARGET_DR_*, NF_TARGET_CRE_*: not built yet).
  * p0_elems: the element count of full->p0 (the negative-binomial table length lives in device memory: it is derived from this).
  * p0_out: p0_elems - nper (R - m) elements, nper the number of per-row segments of the kind's p0;  p1_out: m x w, w the row width
  *   of p1 (d; d / C for SOFTMAX; (d - 1) / H - 1 for BNN).  idx_out (optional, int32[m]) receives idx.  idx_in (optional, int32[m],

@@ -58,6 +58,10 @@ NF_TARGET_MIXGLM = 35
 # p1 = A[R, d] = [X | Z]; p0 = offu[R] | offv[R] | wt[R] | aux[R] | lin[d] | par[4] (par = (precision of beta, const, precision of
 # gamma, nu)); s0 = R, s1 = p
 NF_TARGET_DR_NORMAL, NF_TARGET_DR_STUDENT, NF_TARGET_DR_ZIPOISSON, NF_TARGET_DR_WEIBULL = 36, 37, 38, 39
+# correlated random effects: y = [beta ; (b [G x k] ; tau [k] ; omega [k (k - 1) / 2]) per term ; (lambda)]; p1 = A[rows, d];
+# p0 = lin[d] | off[rows] | wt[rows] | par[4] | fom[d] | tab[4][24] | lamh[4]; s0 = rows, s1 = the number of terms
+(NF_TARGET_CRE_LOGIT, NF_TARGET_CRE_PROBIT, NF_TARGET_CRE_POISSON, NF_TARGET_CRE_STUDENT, NF_TARGET_CRE_NORMAL, NF_TARGET_CRE_DNORMAL,
+ NF_TARGET_CRE_DSTUDENT) = 40, 41, 42, 43, 44, 45, 46
 NF_MAX_HIDDEN = 4
 NF_ERR_NONFINITE = -4
 

@@ -679,6 +679,17 @@ int nf_target_check(const nf_target *t, int d) {
             t->s1 == (double)(long)t->s1))
         return NF_ERR_ARG;
       return d > 256 ? NF_ERR_UNSUPPORTED : NF_OK;  // what no kernel of nf_distreg.hip serves: answered here, before any device work
+    case NF_TARGET_CRE_LOGIT:
+    case NF_TARGET_CRE_PROBIT:
+    case NF_TARGET_CRE_POISSON:
+    case NF_TARGET_CRE_STUDENT:
+    case NF_TARGET_CRE_NORMAL:
+    case NF_TARGET_CRE_DNORMAL:
+    case NF_TARGET_CRE_DSTUDENT:  // s0 = the number of rows, a positive integer that fits an int; s1 = the number of terms F, an integer in 1 .. 4 (NaN fails both comparisons); the dispersion kinds hold lambda = y[d-1] beside at least one more coordinate; A (p1) and the row buffer (p0) are two buffers
+      if (!(t->p0 && t->p1 && t->p0 != t->p1 && t->s0 >= 1 && t->s0 < 2147483648.0 && t->s0 == (double)(long)t->s0 && t->s1 >= 1 && t->s1 <= 4 &&
+            t->s1 == (double)(int)t->s1 && d >= (t->kind >= NF_TARGET_CRE_DNORMAL ? 2 : 1)))
+        return NF_ERR_ARG;
+      return d > 256 ? NF_ERR_UNSUPPORTED : NF_OK;  // what no kernel of nf_correff.hip serves: answered here, before any device work
     default: return NF_ERR_ARG;
   }
 }
@@ -700,6 +711,7 @@ int nf_launch_target(nf_ctx *ctx, int dtype, const nf_target *t, int d, long N, 
     if (target_is_riskset(t->kind)) return nf_launch_target_riskset(a);
     if (target_is_mixglm(t->kind)) return nf_launch_target_mixglm(a);
     if (target_is_distreg(t->kind)) return nf_launch_target_distreg(a);
+    if (target_is_correff(t->kind)) return nf_launch_target_correff(a);
     return nf_launch_target_linpred(a);
   }
   ProfScope ps(ctx, "target");
@@ -826,6 +838,7 @@ int nf_launch_target_tiled(nf_ctx *ctx, const nf_target *t, int d, long N, const
   if (target_is_riskset(t->kind)) return nf_launch_target_riskset_tiled(a);
   if (target_is_mixglm(t->kind)) return nf_launch_target_mixglm_tiled(a);
   if (target_is_distreg(t->kind)) return nf_launch_target_distreg_tiled(a);
+  if (target_is_correff(t->kind)) return nf_launch_target_correff_tiled(a);
   if (target_is_linpred(t->kind)) return nf_launch_target_linpred_tiled(a);
   ProfScope ps(ctx, "target");
   hipLaunchKernelGGL(k_target_tiled, dim3((unsigned)nf_target_tiled_nblocks(N)), dim3(EW_BLOCK), 0, ctx->stream,

@@ -155,9 +155,12 @@ __host__ __device__ inline bool target_is_mixglm(int kind) { return kind == NF_T
 // So are the distributional kinds (NF_TARGET_DR_NORMAL .. NF_TARGET_DR_WEIBULL, nf_distreg.hip): two linear predictors per row, over two
 // blocks of y, meeting in a bivariate row function whose two partial derivatives feed two gradient blocks.
 __host__ __device__ inline bool target_is_distreg(int kind) { return kind >= NF_TARGET_DR_NORMAL && kind <= NF_TARGET_DR_WEIBULL; }
+// So are the correlated-random-effects kinds (NF_TARGET_CRE_LOGIT .. NF_TARGET_CRE_DSTUDENT, nf_correff.hip): the generalised / dispersion
+// form under a prior in which a level's k effects share a learned covariance (log-scales and an LKJ correlation block in y).
+__host__ __device__ inline bool target_is_correff(int kind) { return kind >= NF_TARGET_CRE_LOGIT && kind <= NF_TARGET_CRE_DSTUDENT; }
 __host__ __device__ inline bool target_has_own_kernel(int kind) {
   return target_is_linpred(kind) || kind == NF_TARGET_GAUSSMIX || kind == NF_TARGET_SOFTMAX || target_is_bnn(kind) || target_is_ordinal(kind) ||
-         target_is_riskset(kind) || target_is_mixglm(kind) || target_is_distreg(kind);
+         target_is_riskset(kind) || target_is_mixglm(kind) || target_is_distreg(kind) || target_is_correff(kind);
 }
 // widest flow the mixture's tiled kernel serves (two U and two G blocks in registers); the flat kernel goes to 256
 #define NF_MIXTURE_TILED_MAXD 64

@@ -2096,6 +2096,218 @@ class WeibullRegressionTarget(DistributionalRegressionTarget):
         return torch.exp(eta), torch.exp(zeta)
 
 
+_CRE_KINDS = {"logit": _lib.NF_TARGET_CRE_LOGIT, "probit": _lib.NF_TARGET_CRE_PROBIT, "poisson": _lib.NF_TARGET_CRE_POISSON,
+              "student": _lib.NF_TARGET_CRE_STUDENT, "normal": _lib.NF_TARGET_CRE_NORMAL, "dnormal": _lib.NF_TARGET_CRE_DNORMAL,
+              "dstudent": _lib.NF_TARGET_CRE_DSTUDENT}
+_CRE_MAXK, _CRE_MAXF, _CRE_TERM = 4, 4, 24
+
+
+def _lkj_normaliser(k, eta):
+    """log of LKJ(eta)'s density over the unconstrained omega at omega = 0 (L = I, tanh' = 1): what the closed form
+    sum_{i>j} c_ij log(1 - tanh^2 omega_ij) leaves out, a constant per (k, eta)"""
+    if k == 1:
+        return 0.0
+    from torch.distributions import LKJCholesky
+    return float(LKJCholesky(k, torch.tensor(float(eta), dtype=torch.float64)).log_prob(torch.eye(k, dtype=torch.float64)))
+
+
+def _hyper_fold(h, loc, scl):
+    """(code, hm, his, lin, const) of one hyper-prior over a log-scale, HierarchicalGLMTarget's folding"""
+    if h == "lognormal":
+        return 0.0, loc, 1.0 / scl, 0.0, -math.log(scl) - 0.5 * math.log(2.0 * math.pi)
+    hm = math.log(scl)  # a density over exp(.): + the log-scale itself from the change of variables
+    return float(_HYPER_KINDS[h]), hm, 0.0, 1.0, (0.5 if h == "halfnormal" else 1.0) * math.log(2.0 / math.pi) - hm
+
+
+def _items64(v):
+    """a list or tuple of numbers as a float64 tensor (torch.as_tensor alone would round it through float32)"""
+    return torch.as_tensor(v, dtype=torch.float64) if isinstance(v, (list, tuple)) else v
+
+
+class CorrelatedEffectsTarget(_LinpredTarget):
+    """A GLM posterior with CORRELATED random effects (NF_TARGET_CRE_*; lme4's (1 + x | g)), over
+        z = [beta (p) ; term 1 ; .. ; term F ; (lambda)],   term f = b^f (G_f levels x k_f effects, level-major) ; tau^f (k_f) ; omega^f (k_f (k_f - 1) / 2):
+        logp(z) = const + sum_i weights_i phi(u_i; param [, lambda]) + lin . [beta ; b] + sum_j log N(beta_j; 0, fixed_sigma_j^2)
+                  + sum_f [ sum_g log N(b^f_g; 0, D R D) + sum_i log p(tau^f_i) + log LKJ(R; eta_f) ]  [ + log p(lambda) ],   u = A [beta ; b] + offset,
+    D = diag exp(tau^f), R = L L', L the stick-breaking Cholesky factor of tanh(omega^f) (torch's CorrCholeskyTransform, Jacobian included).
+    family: "logit", "probit", "poisson", "student", "normal" (GLMTarget's row functions) or "dnormal" / "dstudent" (phi(u exp(-lambda)) - lambda
+    with the residual log-scale lambda the last coordinate, under disp_hyper).  A [rows, p + sum_f G_f k_f]: beta's columns, then every
+    term's G_f k_f columns level-major; lin over A's columns.  terms: (k, n_levels, eta, hyper, hyper_loc, hyper_scale) per term, 1 <= k <= 4,
+    at most 4 terms; hyper as HierarchicalGLMTarget's, one name / value or k of them.  Everything linear in z or constant is folded here in
+    float64.  The device reads `A` (zero columns at tau, omega, lambda) and ONE buffer `p0` (include/nfhip.h)."""
+
+    def __init__(self, family, A, terms, offset=None, weights=None, lin=None, const=0.0, param=0.0, fixed_sigma=1.0, disp_hyper="halfcauchy",
+                 disp_loc=0.0, disp_scale=1.0, _name="CorrelatedEffectsTarget"):
+        nm = _name
+        if family not in _CRE_KINDS:
+            raise NFHipError(f"{nm}: family must be one of {sorted(_CRE_KINDS)}")
+        disp = family in ("dnormal", "dstudent")
+        A64 = _glm_matrix(nm, A)
+        rows, pa = A64.shape
+        terms = list(terms)
+        if not 1 <= len(terms) <= _CRE_MAXF:
+            raise NFHipError(f"{nm}: between 1 and {_CRE_MAXF} terms")
+        spec = []
+        for t in terms:
+            k, G, eta, hyper, loc, scl = t
+            if isinstance(k, bool) or not hasattr(k, "__index__") or not 1 <= int(k) <= _CRE_MAXK:
+                raise NFHipError(f"{nm}: a term holds 1..{_CRE_MAXK} effects per level, got k = {k}")
+            if isinstance(G, bool) or not hasattr(G, "__index__") or int(G) < 1:
+                raise NFHipError(f"{nm}: n_levels must be an integer >= 1")
+            k, G = int(k), int(G)
+            names = [hyper] * k if isinstance(hyper, str) else list(hyper)
+            if len(names) != k or any(not isinstance(h, str) or h not in _HYPER_KINDS for h in names):
+                raise NFHipError(f"{nm}: hyper must be one of {sorted(_HYPER_KINDS)}, or one of them per effect")
+            spec.append((k, G, _glm_scalar(nm, "eta", eta), names, _per_item(nm, "hyper_loc", _items64(loc), k), _per_item(nm, "hyper_scale", _items64(scl), k, positive=True)))
+        nb = sum(k * G for k, G, *_ in spec)
+        p = pa - nb
+        d = p + sum(k * G + k + k * (k - 1) // 2 for k, G, *_ in spec) + (1 if disp else 0)
+        if p < 0:
+            raise NFHipError(f"{nm}: A has {pa} columns, the terms alone need {nb}")
+        if d > 256:
+            raise NFHipError(f"{nm}: d = {d} exceeds the kernels' 256")
+        off = _glm_vector(nm, "offset", offset, A, rows, 0.0)
+        wt = _glm_vector(nm, "weights", weights, A, rows, 1.0, nonneg=True)
+        ln = _glm_vector(nm, "lin", lin, A, pa, 0.0)
+        c = _glm_scalar(nm, "const", const, positive=False)
+        param = _glm_scalar(nm, "param", param, positive=family in ("student", "dstudent"))
+        sig = _per_item(nm, "fixed_sigma", _items64(fixed_sigma), p, positive=True, allow_inf=True)
+        fin = torch.isfinite(sig)
+        L2PI = math.log(2.0 * math.pi)
+        c += -float(torch.log(sig[fin]).sum()) - 0.5 * L2PI * float(fin.sum())
+        lin_d, fom, cols = torch.zeros(d, dtype=torch.float64), torch.zeros(d, dtype=torch.float64), []
+        lin_d[:p], fom[:p] = ln[:p], torch.where(fin, 1.0 / sig**2, torch.zeros_like(sig))
+        cols.append(torch.arange(p))
+        tab = torch.zeros(_CRE_MAXF, _CRE_TERM, dtype=torch.float64)
+        self.layout = []  # (k, G, first index of b, of tau, of omega) per term
+        at, a0 = p, p
+        for f, (k, G, eta, names, loc, scl) in enumerate(spec):
+            ib, it = at, at + k * G
+            io = it + k
+            m = k * (k - 1) // 2
+            lin_d[ib:it] = ln[a0:a0 + k * G]
+            cols.append(torch.arange(ib, it))
+            tab[f, :5] = torch.tensor([k, G, ib, it, io], dtype=torch.float64)
+            n = 0
+            for i in range(1, k):
+                for j in range(i):
+                    tab[f, 5 + n] = eta + 0.5 * (k - 2 - j)
+                    n += 1
+            for i, h in enumerate(names):
+                tab[f, 11 + i], tab[f, 15 + i], tab[f, 19 + i], l1, c1 = _hyper_fold(h, float(loc[i]), float(scl[i]))
+                lin_d[it + i] += l1
+                c += c1
+            c += -0.5 * G * k * L2PI + _lkj_normaliser(k, eta)
+            self.layout.append((k, G, ib, it, io))
+            at, a0 = io + m, a0 + k * G
+        lamh = torch.zeros(4, dtype=torch.float64)
+        if disp:
+            if not isinstance(disp_hyper, str) or disp_hyper not in _HYPER_KINDS:
+                raise NFHipError(f"{nm}: disp_hyper must be one of {sorted(_HYPER_KINDS)}")
+            lamh[0], lamh[1], lamh[2], l1, c1 = _hyper_fold(disp_hyper, _glm_scalar(nm, "disp_loc", disp_loc, positive=False), _glm_scalar(nm, "disp_scale", disp_scale))
+            lin_d[d - 1] = l1 - float(wt[wt > 0].sum())  # the -lambda of every live row's normaliser
+            c += c1
+        self.family, self.d, self.p, self.rows, self.param, self.const, self.disp = family, d, p, rows, param, c, disp
+        Ad = torch.zeros(rows, d, dtype=torch.float64)
+        Ad[:, torch.cat(cols)] = A64
+        self.A = Ad.to(A.dtype).to(A.device).contiguous()
+        self.p0 = torch.cat([lin_d, off, wt, torch.tensor([param, c, 0.0, 0.0], dtype=torch.float64), fom, tab.reshape(-1), lamh]).to(A.dtype).to(A.device).contiguous()
+        self.c = Target(_CRE_KINDS[family], self.p0.data_ptr(), self.A.data_ptr(), float(rows), float(len(spec)))
+
+    def unpack(self, y):
+        """(beta, [b_f], [sd_f], [corr_f] [, sigma]) of a parameter vector y (d,) or a batch (d, N): b_f [G, k (, N)], sd_f = exp(tau^f)
+        [k (, N)], corr_f = L L' [(N,) k, k], sigma = exp(lambda) for the dispersion families"""
+        if y.shape[0] != self.d:
+            raise NFHipError(f"{type(self).__name__}.unpack: expected {self.d} leading elements, got {y.shape[0]}")
+        from torch.distributions.transforms import CorrCholeskyTransform
+        bs, sds, corrs = [], [], []
+        for k, G, ib, it, io in self.layout:
+            bs.append(y[ib:it].reshape((G, k) + tuple(y.shape[1:])))
+            sds.append(torch.exp(y[it:io]))
+            if k == 1:
+                corrs.append(torch.ones(tuple(y.shape[1:]) + (1, 1), dtype=y.dtype, device=y.device))
+            else:
+                L = CorrCholeskyTransform()(torch.movedim(y[io:io + k * (k - 1) // 2], 0, -1))
+                corrs.append(L @ L.transpose(-1, -2))
+        out = (y[:self.p], bs, sds, corrs)
+        return out + (torch.exp(y[-1]),) if self.disp else out
+
+
+class MixedEffectsRegressionTarget(CorrelatedEffectsTarget):
+    """The mixed-effects regression y ~ X + (Z_1 | g_1) + ..: u_i = x_i . beta + sum_f z^f_i . b^f_{level_f(i)} + offset_i with the k_f effects
+    of a level correlated (CorrelatedEffectsTarget).  effects: (Z [rows, k], level_of_row (integers), n_levels, eta) per term; builds
+    A = [X | level-indicator (x) Z_f ..].  t: the response -- labels 0 / 1 for "logit" / "probit" (folded into the rows' signs), counts for
+    "poisson" (sum_i w_i k_i u_i into lin and const, -lgamma(k + 1) into const), the observed value for "normal" / "student" / "dnormal" /
+    "dstudent" (offset -t, the normalisers into const); None: the rows as given.  param: nu for the Student families.  hyper, hyper_loc,
+    hyper_scale apply to every term.  Everything is folded in float64."""
+
+    def __init__(self, family, X, effects, t=None, offset=None, weights=None, param=0.0, fixed_sigma=1.0, hyper="halfcauchy", hyper_loc=0.0,
+                 hyper_scale=1.0, disp_hyper="halfcauchy", disp_loc=0.0, disp_scale=1.0):
+        nm = "MixedEffectsRegressionTarget"
+        X64 = _glm_matrix(nm, X)
+        rows, px = X64.shape
+        blocks, terms, self.effects = [X64], [], []
+        for Z, lev, n_levels, eta in effects:
+            Z64 = _glm_matrix(nm, Z)
+            if Z64.shape[0] != rows or Z.dtype != X.dtype or Z.device != X.device:
+                raise NFHipError(f"{nm}: Z must have X's rows, element type and device")
+            if isinstance(n_levels, bool) or not hasattr(n_levels, "__index__") or int(n_levels) < 1:
+                raise NFHipError(f"{nm}: n_levels must be an integer >= 1")
+            G, k = int(n_levels), Z64.shape[1]
+            if not isinstance(lev, torch.Tensor) or lev.dim() != 1 or lev.numel() != rows or lev.dtype.is_floating_point or lev.dtype.is_complex or lev.dtype == torch.bool:
+                raise NFHipError(f"{nm}: level_of_row must be an integer tensor with one level per row of X")
+            lv = lev.detach().to("cpu", torch.int64)
+            if bool((lv < 0).any()) or bool((lv >= G).any()):
+                raise NFHipError(f"{nm}: levels must be in 0..{G - 1}")
+            B = torch.zeros(rows, G, k, dtype=torch.float64)
+            B[torch.arange(rows), lv] = Z64
+            blocks.append(B.reshape(rows, G * k))
+            terms.append((k, G, eta, hyper, hyper_loc, hyper_scale))
+            self.effects.append((k, G))
+        A64 = torch.cat(blocks, 1)
+        off = _glm_vector(nm, "offset", offset, X, rows, 0.0)
+        w = _glm_vector(nm, "weights", weights, X, rows, 1.0, nonneg=True)
+        lin, const, live = None, 0.0, w > 0
+        if t is not None:
+            tv = _glm_vector(nm, "t", t, X, rows)
+            if family in ("logit", "probit"):
+                if bool(((tv != 0) & (tv != 1)).any()):
+                    raise NFHipError(f"{nm}: labels must be 0 / 1")
+                sgn = 2.0 * tv - 1.0
+                A64, off = A64 * sgn[:, None], off * sgn
+            elif family == "poisson":
+                if bool((tv < 0).any()) or bool((tv != torch.round(tv)).any()):
+                    raise NFHipError(f"{nm}: counts must be non-negative integers")
+                lin = (w * tv)[live] @ A64[live]
+                const = float((w * (tv * off - torch.lgamma(tv + 1.0)))[live].sum())
+            else:
+                off = off - tv
+                nu = float(param)
+                per = -0.5 * math.log(2.0 * math.pi) if family in ("normal", "dnormal") else \
+                    math.lgamma(0.5 * (nu + 1.0)) - math.lgamma(0.5 * nu) - 0.5 * math.log(nu * math.pi) if nu > 0 else 0.0
+                const = per * float(w[live].sum())
+        to = lambda v: None if v is None else v.to(X.dtype).to(X.device)
+        self.px = px
+        super().__init__(family, to(A64), terms, to(off), to(w), to(lin), const, param, fixed_sigma, disp_hyper, disp_loc, disp_scale, _name=nm)
+        self.sign_folded = t is not None and family in ("logit", "probit")
+
+    def predict(self, y, Xnew, Znew, levels):
+        """the linear predictor Xnew beta + sum_f Znew_f . b^f_{levels_f} in plain torch: [rows] for a vector y, [rows, N] for a batch
+        (d, N).  Znew / levels: one tensor per term (a single tensor for one term)."""
+        Zs = [Znew] if isinstance(Znew, torch.Tensor) else list(Znew)
+        ls = [levels] if isinstance(levels, torch.Tensor) else list(levels)
+        if Xnew.dim() != 2 or Xnew.shape[1] != self.px or len(Zs) != len(self.effects) or len(ls) != len(self.effects):
+            raise NFHipError(f"{type(self).__name__}.predict: Xnew [rows, {self.px}], one Znew and one level vector per term")
+        beta, bs = self.unpack(y)[:2]
+        eta = Xnew @ beta
+        for Z, lv, b, (k, G) in zip(Zs, ls, bs, self.effects):
+            if Z.shape != (Xnew.shape[0], k) or bool((lv < 0).any()) or bool((lv >= G).any()):
+                raise NFHipError(f"{type(self).__name__}.predict: Znew [rows, {k}], levels in 0..{G - 1}")
+            bl = b[lv.to(torch.int64)]  # [rows, k (, N)]
+            eta = eta + (Z.unsqueeze(-1) * bl).sum(1) if bl.dim() == 3 else eta + (Z * bl).sum(1)
+        return eta
+
+
 def minibatch_segments(target):
     """The layout nf_target_minibatch gathers, for a target it serves: (segments, weight_segment, w) -- the segments of `target.p0`
     in order as (per_row, length) pairs (a per-row segment has length target.rows), the position of the weight segment among them,

@@ -498,6 +498,33 @@ extern "C" {
 #define NF_TARGET_CRE_NORMAL (NF_TARGET_DR_WEIBULL + 5)
 #define NF_TARGET_CRE_DNORMAL (NF_TARGET_DR_WEIBULL + 6)
 #define NF_TARGET_CRE_DSTUDENT (NF_TARGET_DR_WEIBULL + 7)
+/* The SCALED-BLOCK GLM target (P-spline / GAM smooths with a learned smoothing parameter, RW1 / RW2 and ICAR / BYM priors with a learned
+ * scale, a Bayesian lasso with a learned global scale, a learned residual scale per outcome or stratum): NF_TARGET_MIXGLM's form with
+ * a learned LOG-SCALE coordinate per 32-row block.
+ *   y = [beta (p) ; tau (S)] in R^d, d = p + S <= 256, 1 <= S <= 16, p >= 1;   u = A y + off (A's last S columns are zero)
+ *       log p(y) = par[1] + sum_b sum_{i in b} wt_i phi_{f_b}(exp(-tau_{s_b}) u_i; q_b) + lin . y - sum_j fom_j y_j^2 / 2
+ *                  + sum_s h_s(tau_s - hm_s)
+ *   Block b = rows [32 b, 32 b + 32) has NF_TARGET_MIXGLM's family code f_b (0 .. 5) and parameter q_b, and a scale index s_b in
+ *   {-1, 0 .. S-1}: -1 is "no scale" (exp(-tau) read as 1), NF_TARGET_MIXGLM's block exactly.  h_s is one of the hierarchical kinds'
+ *   three hyper-prior forms (hk_s = 0 log-normal, 1 half-normal, 2 half-Cauchy on exp(tau_s), as densities over tau_s); fom_j is the
+ *   fixed prior precision of coordinate j (0: flat).  The host folds everything linear in y -- the -n_s tau_s of the scaled
+ *   families' normalisers (n_s the live weight sum under scale s; for a rank-deficient penalty its rank), the +tau_s of the half
+ *   families' Jacobians -- into lin and every constant into par[1], in float64.
+ *   p1 = A[R x d] row-major;  s0 = R, the PADDED row count (an integer value, a positive multiple of 32);  s1 = S (an integer value);
+ *   p0 = ONE buffer of 2 d + 2 R + 3 R / 32 + 3 S + 2 elements in the flow's element type, distinct from p1:
+ *       lin[d] | off[R] | wt[R] | fam[R / 32] | bpar[R / 32] | sidx[R / 32] | fom[d] | hm[S] | his[S] | hk[S] | par[2]
+ *   NF_ERR_ARG for a NULL p0 / p1, p0 == p1, an s0 that is not a positive multiple of 32, an s1 that is NaN, non-integral or < 1,
+ *   or d <= S; then NF_ERR_UNSUPPORTED for S > 16 or d > 256 -- both before any device work.  The host cannot validate device
+ *   memory: a code outside 0 .. 5 (NaN included) drops its block from the value, the score and every tau's gradient; a scale index
+ *   outside 0 .. S-1 (NaN included) is read as -1.  Neither addresses anything.
+ * z = exp(-tau) u is formed before anything is squared or exponentiated; exp(-tau) is the library's exponential, once per sample
+ * and scale.  A row with wt_i == 0 contributes exactly 0 by select.  No atomics: two launches give the same bits.  Served exactly
+ * like NF_TARGET_MIXGLM: nf_target_logp, RealNVP / NSF flows of either element type including the weight-streaming shapes,
+ * full-rank and preconditioned flows, general bases and compositions; nf_elbo_step runs the split sequence, nf_elbo_step_enqueue
+ * answers NF_ERR_UNSUPPORTED; planar, radial, mean-field and Hamiltonian flows answer NF_ERR_UNSUPPORTED at every ELBO entry
+ * point; nf_target_minibatch answers NF_ERR_UNSUPPORTED; a non-centring layer (flow kind 10) answers NF_ERR_ARG for this target.
+ * tests/test_scaled_glm_cpu.py holds the value at 47. */
+#define NF_TARGET_SCALEGLM (NF_TARGET_CRE_DSTUDENT + 1)
 
 #define NF_MAX_HIDDEN 4
 
@@ -680,7 +707,7 @@ int nf_target_logp(nf_ctx *ctx, int32_t dtype, const nf_target *target, int32_t 
  * Kinds: NF_TARGET_GLM_*, NF_TARGET_SOFTMAX, NF_TARGET_HGLM_*, NF_TARGET_BNN_*, NF_TARGET_DGLM_*.  NF_ERR_UNSUPPORTED for the kinds
  *   without a per-row weight (0 .. 6, 8) or whose rows are not exchangeable (NF_TARGET_ORDINAL_LOGIT: label blocks;
  *   NF_TARGET_RISKSET: rows interact; NF_TARGET_MIXGLM: family blocks, and a block may be a prior, which must not be subsampled;
- *   NF_TARGET_DR_*, NF_TARGET_CRE_*: not built yet).
+ *   NF_TARGET_DR_*, NF_TARGET_CRE_*: not built yet; NF_TARGET_SCALEGLM: scale blocks, and a block may be a prior).
  * p0_elems: the element count of full->p0 (the negative-binomial table length lives in device memory: it is derived from this).
  * p0_out: p0_elems - nper (R - m) elements, nper the number of per-row segments of the kind's p0;  p1_out: m x w, w the row width
  *   of p1 (d; d / C for SOFTMAX; (d - 1) / H - 1 for BNN).  idx_out (optional, int32[m]) receives idx.  idx_in (optional, int32[m],

@@ -62,6 +62,9 @@ NF_TARGET_DR_NORMAL, NF_TARGET_DR_STUDENT, NF_TARGET_DR_ZIPOISSON, NF_TARGET_DR_
 # p0 = lin[d] | off[rows] | wt[rows] | par[4] | fom[d] | tab[4][24] | lamh[4]; s0 = rows, s1 = the number of terms
 (NF_TARGET_CRE_LOGIT, NF_TARGET_CRE_PROBIT, NF_TARGET_CRE_POISSON, NF_TARGET_CRE_STUDENT, NF_TARGET_CRE_NORMAL, NF_TARGET_CRE_DNORMAL,
  NF_TARGET_CRE_DSTUDENT) = 40, 41, 42, 43, 44, 45, 46
+# scaled-block GLM: y = [beta (p) ; tau (S)], kind 35's blocks at z = exp(-tau_{sidx[b]}) u; p1 = A[R, d]; s0 = R (a multiple of 32), s1 = S;
+# p0 = lin[d] | off[R] | wt[R] | fam[R / 32] | bpar[R / 32] | sidx[R / 32] | fom[d] | hm[S] | his[S] | hk[S] | par[2]
+NF_TARGET_SCALEGLM = 47
 NF_MAX_HIDDEN = 4
 NF_ERR_NONFINITE = -4
 

@@ -690,6 +690,11 @@ int nf_target_check(const nf_target *t, int d) {
             t->s1 == (double)(int)t->s1 && d >= (t->kind >= NF_TARGET_CRE_DNORMAL ? 2 : 1)))
         return NF_ERR_ARG;
       return d > 256 ? NF_ERR_UNSUPPORTED : NF_OK;  // what no kernel of nf_correff.hip serves: answered here, before any device work
+    case NF_TARGET_SCALEGLM:  // s0 = the number of rows R, block-padded: a positive integer multiple of 32 that fits an int; s1 = the number of log-scales S, an integer >= 1 (NaN fails the comparison) with at least one coefficient beside them; A (p1) and the row buffer (p0) are two buffers
+      if (!(t->p0 && t->p1 && t->p0 != t->p1 && t->s0 >= 32 && t->s0 < 2147483648.0 && t->s0 == (double)(long)t->s0 && (long)t->s0 % 32 == 0 && t->s1 >= 1 &&
+            t->s1 < 2147483648.0 && t->s1 == (double)(long)t->s1 && (double)d > t->s1))
+        return NF_ERR_ARG;
+      return (t->s1 > 16 || d > 256) ? NF_ERR_UNSUPPORTED : NF_OK;  // what no kernel of nf_scaleglm.hip serves: answered here, before any device work
     default: return NF_ERR_ARG;
   }
 }
@@ -712,6 +717,7 @@ int nf_launch_target(nf_ctx *ctx, int dtype, const nf_target *t, int d, long N, 
     if (target_is_mixglm(t->kind)) return nf_launch_target_mixglm(a);
     if (target_is_distreg(t->kind)) return nf_launch_target_distreg(a);
     if (target_is_correff(t->kind)) return nf_launch_target_correff(a);
+    if (target_is_scaleglm(t->kind)) return nf_launch_target_scaleglm(a);
     return nf_launch_target_linpred(a);
   }
   ProfScope ps(ctx, "target");
@@ -839,6 +845,7 @@ int nf_launch_target_tiled(nf_ctx *ctx, const nf_target *t, int d, long N, const
   if (target_is_mixglm(t->kind)) return nf_launch_target_mixglm_tiled(a);
   if (target_is_distreg(t->kind)) return nf_launch_target_distreg_tiled(a);
   if (target_is_correff(t->kind)) return nf_launch_target_correff_tiled(a);
+  if (target_is_scaleglm(t->kind)) return nf_launch_target_scaleglm_tiled(a);
   if (target_is_linpred(t->kind)) return nf_launch_target_linpred_tiled(a);
   ProfScope ps(ctx, "target");
   hipLaunchKernelGGL(k_target_tiled, dim3((unsigned)nf_target_tiled_nblocks(N)), dim3(EW_BLOCK), 0, ctx->stream,

@@ -1,7 +1,7 @@
 // nf_target_stages.h -- the stages the matrix-pipe target kernels share (nf_linpred.hip, nf_mixture.hip, nf_softmax.hip,
-// nf_bnn.hip, nf_ordinal.hip, nf_riskset.hip, nf_mixglm.hip, nf_distreg.hip, nf_correff.hip), one copy of each, and the host helpers of their launchers.
+// nf_bnn.hip, nf_ordinal.hip, nf_riskset.hip, nf_mixglm.hip, nf_distreg.hip, nf_correff.hip, nf_scaleglm.hip), one copy of each, and the host helpers of their launchers.
 //
-// Every one of the nine files holds a tiled Float32 kernel (one workgroup of four waves per 32-sample tile, both GEMMs on
+// Every one of the ten files holds a tiled Float32 kernel (one workgroup of four waves per 32-sample tile, both GEMMs on
 // v_mfma_f32_32x32x2_f32) and a flat float / double kernel (k_target's layout: 16 lanes per sample, 16 samples per block).
 // A stage here is a __device__ __forceinline__ function that declares no LDS of its own: the kernels keep their __shared__
 // arrays and pass pointers, so a kernel's static LDS layout is what its own file says.  A stage that only one kernel has
@@ -169,7 +169,7 @@ int tgt_launch_flat(const TgtFlatArgs &a, size_t lds, H... head) {
   return (int)hipGetLastError();
 }
 
-// the launchers of the nine files, the same contract as k_target_tiled / k_target: same outputs and partial counts
+// the launchers of the ten files, the same contract as k_target_tiled / k_target: same outputs and partial counts
 int nf_launch_target_linpred_tiled(const TgtTiledArgs &a);
 int nf_launch_target_linpred(const TgtFlatArgs &a);
 int nf_launch_target_mixture_tiled(const TgtTiledArgs &a);
@@ -188,3 +188,5 @@ int nf_launch_target_distreg_tiled(const TgtTiledArgs &a);
 int nf_launch_target_distreg(const TgtFlatArgs &a);
 int nf_launch_target_correff_tiled(const TgtTiledArgs &a);
 int nf_launch_target_correff(const TgtFlatArgs &a);
+int nf_launch_target_scaleglm_tiled(const TgtTiledArgs &a);
+int nf_launch_target_scaleglm(const TgtFlatArgs &a);

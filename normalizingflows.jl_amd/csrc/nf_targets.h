@@ -158,9 +158,12 @@ __host__ __device__ inline bool target_is_distreg(int kind) { return kind >= NF_
 // So are the correlated-random-effects kinds (NF_TARGET_CRE_LOGIT .. NF_TARGET_CRE_DSTUDENT, nf_correff.hip): the generalised / dispersion
 // form under a prior in which a level's k effects share a learned covariance (log-scales and an LKJ correlation block in y).
 __host__ __device__ inline bool target_is_correff(int kind) { return kind >= NF_TARGET_CRE_LOGIT && kind <= NF_TARGET_CRE_DSTUDENT; }
+// So is the scaled-block GLM kind (NF_TARGET_SCALEGLM, nf_scaleglm.hip): the mixed-family form with a learned log-scale coordinate per row
+// block (y = [beta ; tau]), the rows' d / d tau gathered in per-lane bins.
+__host__ __device__ inline bool target_is_scaleglm(int kind) { return kind == NF_TARGET_SCALEGLM; }
 __host__ __device__ inline bool target_has_own_kernel(int kind) {
   return target_is_linpred(kind) || kind == NF_TARGET_GAUSSMIX || kind == NF_TARGET_SOFTMAX || target_is_bnn(kind) || target_is_ordinal(kind) ||
-         target_is_riskset(kind) || target_is_mixglm(kind) || target_is_distreg(kind) || target_is_correff(kind);
+         target_is_riskset(kind) || target_is_mixglm(kind) || target_is_distreg(kind) || target_is_correff(kind) || target_is_scaleglm(kind);
 }
 // widest flow the mixture's tiled kernel serves (two U and two G blocks in registers); the flat kernel goes to 256
 #define NF_MIXTURE_TILED_MAXD 64

@@ -1872,6 +1872,29 @@ def gaussian_penalty(S, like):
                           0.0, 0.0, like, nm)
 
 
+def _glm_components(nm, components):
+    """What a sequence of GLMBlock / GLMTarget components holds, in float64 on the host: (d, element type, device, the GLMTargets'
+    isotropic prior sigmas, [(family code, param, A64, offset, weights, const, lin or None)] in order)"""
+    comps = list(components) if isinstance(components, (list, tuple)) else [components]
+    if not comps or not all(isinstance(c, (GLMBlock, GLMTarget)) for c in comps):
+        raise NFHipError(f"{nm}: components must be a non-empty sequence of GLMBlock / GLMTarget instances")
+    first = comps[0]
+    d = first.d
+    dtype, device = (first.dtype, first.device) if isinstance(first, GLMBlock) else (first.A.dtype, first.A.device)
+    rows = []
+    for c in comps:
+        if isinstance(c, GLMTarget):
+            cd, cdt, cdev, p64 = c.d, c.A.dtype, c.A.device, c.p0.detach().to("cpu", torch.float64)
+            A64, off, wt = c.A.detach().to("cpu", torch.float64), p64[c.d:c.d + c.rows], p64[c.d + c.rows:c.d + 2 * c.rows]
+            param, const, ln = float(p64[-2]), float(p64[-1]), p64[:c.d]
+        else:
+            cd, cdt, cdev, A64, off, wt, param, const, ln = c.d, c.dtype, c.device, c.A64, c.off, c.wt, c.param, c.const, None
+        if cd != d or cdt != dtype or cdev != device:
+            raise NFHipError(f"{nm}: all components must share d, the element type and the device")
+        rows.append((_MIX_CODES[c.family], param, A64, off, wt, const, ln))
+    return d, dtype, device, [c.prior_sigma for c in comps if isinstance(c, GLMTarget)], rows
+
+
 class MixedGLMTarget(_LinpredTarget):
     """The mixed-family GLM target (NF_TARGET_MIXGLM): a sum of GLM components with DIFFERENT row functions in one posterior,
         logp(z) = const + sum_c sum_{i in c} weights_i phi_c(u_i; param_c) + lin . z + log N(z; 0, prior_sigma^2 I),   u = A z + offset
@@ -1885,33 +1908,19 @@ class MixedGLMTarget(_LinpredTarget):
 
     def __init__(self, components, lin=None, const=0.0, prior_sigma=math.inf, _name="MixedGLMTarget"):
         nm = _name
-        comps = list(components) if isinstance(components, (list, tuple)) else [components]
-        if not comps or not all(isinstance(c, (GLMBlock, GLMTarget)) for c in comps):
-            raise NFHipError(f"{nm}: components must be a non-empty sequence of GLMBlock / GLMTarget instances")
-        first = comps[0]
-        d = first.d
-        dtype, device = (first.dtype, first.device) if isinstance(first, GLMBlock) else (first.A.dtype, first.A.device)
-        like = torch.empty(0, dtype=dtype, device=device)
+        d, dtype, device, sigmas, rows = _glm_components(nm, components)
         total = _glm_scalar(nm, "const", const, positive=False)
-        ln = _glm_vector(nm, "lin", lin, like, d, 0.0).clone()
+        ln = _glm_vector(nm, "lin", lin, torch.empty(0, dtype=dtype, device=device), d, 0.0).clone()
         prec, runs = 0.0, {}
-        for sg in [_glm_scalar(nm, "prior_sigma", prior_sigma, allow_inf=True)] + [c.prior_sigma for c in comps if isinstance(c, GLMTarget)]:
+        for sg in [_glm_scalar(nm, "prior_sigma", prior_sigma, allow_inf=True)] + sigmas:
             if not math.isinf(sg):
                 prec += 1.0 / sg**2
                 total += -0.5 * d * math.log(2.0 * math.pi * sg**2)
-        for c in comps:
-            if isinstance(c, GLMTarget):
-                cd, cdt, cdev, p64 = c.d, c.A.dtype, c.A.device, c.p0.detach().to("cpu", torch.float64)
-                A64, off, wt = c.A.detach().to("cpu", torch.float64), p64[c.d:c.d + c.rows], p64[c.d + c.rows:c.d + 2 * c.rows]
-                ln += p64[:c.d]
-                param = float(p64[-2])
-                total += float(p64[-1])
-            else:
-                cd, cdt, cdev, A64, off, wt, param = c.d, c.dtype, c.device, c.A64, c.off, c.wt, c.param
-                total += c.const
-            if cd != d or cdt != dtype or cdev != device:
-                raise NFHipError(f"{nm}: all components must share d, the element type and the device")
-            runs.setdefault((_MIX_CODES[c.family], param), []).append((A64, off, wt))
+        for code, param, A64, off, wt, c0, l0 in rows:
+            total += c0
+            if l0 is not None:
+                ln += l0
+            runs.setdefault((code, param), []).append((A64, off, wt))
         if d > 256:
             raise NFHipError(f"{nm}: d = {d} exceeds the kernels' 256")
         As, offs, wts, fam, bpar = [], [], [], [], []
@@ -1951,6 +1960,162 @@ class QuantileRegressionTarget(MixedGLMTarget):
         const = float(w.sum()) * (math.log(tau * (1.0 - tau)) - math.log(scale))
         self.tau, self.scale = tau, scale
         super().__init__([GLMBlock._host("check", -X64 / scale, tv / scale, w, tau, const, X, nm)], None, 0.0, prior_sigma, _name=nm)
+
+
+_SCALE_FAMILIES = ("normal", "student", "check")  # the families with a scale: p(r) = f(r / sigma) / sigma
+_SCALEGLM_MAXS = 16
+
+
+class ScaledGLMTarget(_LinpredTarget):
+    """The scaled-block GLM target (NF_TARGET_SCALEGLM): MixedGLMTarget's components with LEARNED scales, over z = [beta (p) ; tau (S)]:
+        logp(z) = const + sum_c sum_{i in c} weights_i [phi_c(exp(-tau_s) u_i; param_c) - tau_s] + lin . beta
+                  + sum_j log N(beta_j; 0, fixed_sigma_j^2) + sum_s log p(tau_s),   u = A beta + offset,   s = scale_of[c]
+    (a component with scale_of[c] = None has no tau: MixedGLMTarget's term).  components: what MixedGLMTarget takes, built over the p
+    coefficient columns -- a "normal" likelihood block under scale s has the residual scale exp(tau_s), gaussian_penalty(S) under s is
+    the smooth / random-walk / ICAR prior with precision exp(-2 tau_s) S, coefficient_prior("check" / "student", ...) under s a Laplace /
+    Student prior with the global scale exp(tau_s).  scale_of: one entry per component, None or 0 .. n_scales-1; only the scale
+    families "normal", "student", "check" take one.  The -tau_s of every live row's normaliser is folded into lin (weights sum n_s:
+    for gaussian_penalty its rank, the null directions are dropped); the components' own constants are taken as they are.
+    fixed_sigma: a scalar or (p,), math.inf = flat.  hyper, hyper_loc, hyper_scale: HierarchicalGLMTarget's, one or one per scale.
+    The host sorts the rows by (scale, family, param), pads every run to whole 32-row blocks with rows of weight 0 and appends S zero
+    columns; the device reads `A` [rows, d] and ONE buffer `p0` (include/nfhip.h).  `families` / `scales` name every block's family /
+    scale index (-1: none)."""
+
+    def __init__(self, components, scale_of, n_scales, lin=None, const=0.0, fixed_sigma=math.inf, hyper="halfnormal", hyper_loc=0.0,
+                 hyper_scale=1.0, _name="ScaledGLMTarget"):
+        nm = _name
+        p, dtype, device, sigmas, rows = _glm_components(nm, components)
+        if isinstance(n_scales, bool) or not hasattr(n_scales, "__index__") or not 1 <= int(n_scales) <= _SCALEGLM_MAXS:
+            raise NFHipError(f"{nm}: n_scales must be an integer in 1..{_SCALEGLM_MAXS}")
+        S = int(n_scales)
+        d = p + S
+        if d > 256:
+            raise NFHipError(f"{nm}: d = {d} exceeds the kernels' 256")
+        sof = list(scale_of)
+        if len(sof) != len(rows) or any(s is not None and (isinstance(s, bool) or not hasattr(s, "__index__") or not 0 <= int(s) < S) for s in sof):
+            raise NFHipError(f"{nm}: scale_of must hold None or a scale index in 0..{S - 1} per component")
+        names = {v: k for k, v in _MIX_CODES.items()}
+        c = _glm_scalar(nm, "const", const, positive=False)
+        ln = _glm_vector(nm, "lin", lin, torch.empty(0, dtype=dtype, device=device), p, 0.0).clone()
+        sig = _per_item(nm, "fixed_sigma", _items64(fixed_sigma), p, positive=True, allow_inf=True)
+        fom = torch.where(torch.isfinite(sig), 1.0 / sig**2, torch.zeros_like(sig))
+        fin = torch.isfinite(sig)
+        c += -float(torch.log(sig[fin]).sum()) - 0.5 * math.log(2.0 * math.pi) * float(fin.sum())
+        for sg in sigmas:  # a GLMTarget component's isotropic prior over beta
+            if not math.isinf(sg):
+                fom = fom + 1.0 / sg**2
+                c += -0.5 * p * math.log(2.0 * math.pi * sg**2)
+        hn = [hyper] * S if isinstance(hyper, str) else list(hyper)
+        if len(hn) != S or any(not isinstance(h, str) or h not in _HYPER_KINDS for h in hn):
+            raise NFHipError(f"{nm}: hyper must be one of {sorted(_HYPER_KINDS)}, or one of them per scale")
+        loc, scl = _per_item(nm, "hyper_loc", _items64(hyper_loc), S), _per_item(nm, "hyper_scale", _items64(hyper_scale), S, positive=True)
+        hk, hm, his, lin_tau = (torch.zeros(S, dtype=torch.float64) for _ in range(4))
+        for s, h in enumerate(hn):
+            hk[s], hm[s], his[s], lin_tau[s], c1 = _hyper_fold(h, float(loc[s]), float(scl[s]))
+            c += c1
+        runs = {}
+        for (code, param, A64, off, wt, c0, l0), s in zip(rows, sof):
+            c += c0
+            if l0 is not None:
+                ln += l0
+            s = -1 if s is None else int(s)
+            if s >= 0:
+                if names[code] not in _SCALE_FAMILIES:
+                    raise NFHipError(f"{nm}: only the scale families {_SCALE_FAMILIES} take a scale, got '{names[code]}'")
+                lin_tau[s] -= float(wt[wt > 0].sum())  # the -tau_s of every live row's normaliser
+            runs.setdefault((s, code, param), []).append((A64, off, wt))
+        As, offs, wts, fam, bpar, sidx = [], [], [], [], [], []
+        for (s, code, param), parts in sorted(runs.items()):
+            n = sum(q[0].shape[0] for q in parts)
+            pad, nb = -n % 32, (n + -n % 32) // 32
+            As += [q[0] for q in parts] + [torch.zeros((pad, p), dtype=torch.float64)]
+            offs += [q[1] for q in parts] + [torch.zeros(pad, dtype=torch.float64)]
+            wts += [q[2] for q in parts] + [torch.zeros(pad, dtype=torch.float64)]
+            fam, bpar, sidx = fam + [float(code)] * nb, bpar + [param] * nb, sidx + [float(s)] * nb
+        self.d, self.p, self.S, self.const, self.hyper = d, p, S, c, hn
+        self.families, self.scales = [names[int(f)] for f in fam], [int(s) for s in sidx]
+        A64 = torch.cat(As)
+        self.rows = A64.shape[0]
+        self.A = torch.cat([A64, torch.zeros(self.rows, S, dtype=torch.float64)], 1).to(dtype).to(device).contiguous()
+        self.p0 = torch.cat([ln, lin_tau, torch.cat(offs), torch.cat(wts), torch.tensor(fam + bpar + sidx, dtype=torch.float64), fom,
+                             torch.zeros(S, dtype=torch.float64), hm, his, hk, torch.tensor([0.0, c], dtype=torch.float64)]).to(dtype).to(device).contiguous()
+        self.c = Target(_lib.NF_TARGET_SCALEGLM, self.p0.data_ptr(), self.A.data_ptr(), float(self.rows), float(S))
+
+    def unpack(self, y):
+        """(beta, tau) of a parameter vector y (d,) or a batch (d, N); the scales are exp(tau)"""
+        if y.shape[0] != self.d:
+            raise NFHipError(f"{type(self).__name__}.unpack: expected {self.d} leading elements, got {y.shape[0]}")
+        return y[:self.p], y[self.p:]
+
+
+class AdditiveRegressionTarget(ScaledGLMTarget):
+    """The generalised additive model (mgcv's / brms' s() terms): eta_i = x_i . beta_0 + sum_k B_k[i] . beta_k + offset_i with one of
+    GLMTarget's five families, each smooth under the penalty -exp(-2 tau_k) beta_k' S_k beta_k / 2 with a LEARNED log-scale tau_k
+    (exp(-2 tau_k) is the smoothing parameter) and the -rank(S_k) tau_k of its normaliser.  smooths: (B_k [rows, m_k], S_k [m_k, m_k]
+    symmetric positive semi-definite) per term; z = [beta_0 ; beta_1 ; .. ; beta_K ; tau].  t: the response -- labels 0 / 1 for
+    "logit" / "probit" (folded into the rows' signs), counts for "poisson", the observed value for "normal" / "student" (unit residual
+    scale; param = nu); None: the rows as given.  prior_sigma: a scalar or one per coefficient, N(0, prior_sigma^2) on every
+    coefficient, the smooths' included (it keeps the penalties' null spaces proper); math.inf: flat.  hyper*: ScaledGLMTarget's."""
+
+    def __init__(self, family, X, smooths, t=None, offset=None, weights=None, param=0.0, prior_sigma=10.0, hyper="halfnormal", hyper_loc=0.0,
+                 hyper_scale=1.0):
+        nm = "AdditiveRegressionTarget"
+        if family not in _GLM_KINDS:
+            raise NFHipError(f"{nm}: family must be one of {sorted(_GLM_KINDS)}")
+        X64 = _glm_matrix(nm, X)
+        rows, px = X64.shape
+        smooths = list(smooths)
+        if not 1 <= len(smooths) <= _SCALEGLM_MAXS:
+            raise NFHipError(f"{nm}: between 1 and {_SCALEGLM_MAXS} smooth terms")
+        Bs, self.widths = [X64], [px]
+        for B, _ in smooths:
+            B64 = _glm_matrix(nm, B)
+            if B64.shape[0] != rows or B.dtype != X.dtype or B.device != X.device:
+                raise NFHipError(f"{nm}: every basis B_k must have X's rows, element type and device")
+            Bs.append(B64)
+            self.widths.append(B64.shape[1])
+        A64 = torch.cat(Bs, 1)
+        p = A64.shape[1]
+        off = _glm_vector(nm, "offset", offset, X, rows, 0.0)
+        w = _glm_vector(nm, "weights", weights, X, rows, 1.0, nonneg=True)
+        param = _glm_scalar(nm, "param", param, positive=family == "student")
+        lin, const, live = None, 0.0, w > 0
+        if t is not None:
+            tv = _glm_vector(nm, "t", t, X, rows)
+            if family in ("logit", "probit"):
+                if bool(((tv != 0) & (tv != 1)).any()):
+                    raise NFHipError(f"{nm}: labels must be 0 / 1")
+                sgn = 2.0 * tv - 1.0
+                A64, off = A64 * sgn[:, None], off * sgn
+            elif family == "poisson":
+                if bool((tv < 0).any()) or bool((tv != torch.round(tv)).any()):
+                    raise NFHipError(f"{nm}: counts must be non-negative integers")
+                lin = ((w * tv)[live] @ A64[live]).to(X.dtype).to(X.device)
+                const = float((w * (tv * off - torch.lgamma(tv + 1.0)))[live].sum())
+            else:
+                off = off - tv
+                per = -0.5 * math.log(2.0 * math.pi) if family == "normal" else \
+                    math.lgamma(0.5 * (param + 1.0)) - math.lgamma(0.5 * param) - 0.5 * math.log(param * math.pi)
+                const = per * float(w[live].sum())
+        comps, at = [GLMBlock._host(family, A64, off, w, param, const, X, nm)], px
+        for (_, Sk), m in zip(smooths, self.widths[1:]):
+            pen = gaussian_penalty(Sk, X)
+            if pen.d != m:
+                raise NFHipError(f"{nm}: a penalty S_k must be [m_k, m_k] for its basis B_k [rows, m_k]")
+            R = torch.zeros(pen.rows, p, dtype=torch.float64)
+            R[:, at:at + m] = pen.A64
+            comps.append(GLMBlock._host("normal", R, pen.off, pen.wt, 0.0, -0.5 * pen.rows * math.log(2.0 * math.pi), X, nm))
+            at += m
+        self.px, self.sign_folded = px, t is not None and family in ("logit", "probit")
+        super().__init__(comps, [None] + list(range(len(smooths))), len(smooths), lin, 0.0, prior_sigma, hyper, hyper_loc, hyper_scale, _name=nm)
+
+    def predict(self, y, Xnew, Bnew):
+        """the linear predictor Xnew beta_0 + sum_k Bnew_k beta_k in plain torch: [rows] for a vector y, [rows, N] for a batch (d, N).
+        Bnew: one basis matrix per smooth term (a single tensor for one term)."""
+        Bn = [Bnew] if isinstance(Bnew, torch.Tensor) else list(Bnew)
+        if Xnew.dim() != 2 or len(Bn) != len(self.widths) - 1 or any(M.dim() != 2 or M.shape != (Xnew.shape[0], m) for M, m in zip([Xnew] + Bn, self.widths)):
+            raise NFHipError(f"{type(self).__name__}.predict: Xnew [rows, {self.px}] and one Bnew [rows, m_k] per smooth term")
+        return torch.cat([Xnew] + Bn, 1) @ self.unpack(y)[0]
 
 
 _DR_KINDS = {"normal": _lib.NF_TARGET_DR_NORMAL, "student": _lib.NF_TARGET_DR_STUDENT, "zipoisson": _lib.NF_TARGET_DR_ZIPOISSON,

@@ -74,6 +74,9 @@ const NF_TARGET_DR_NORMAL, NF_TARGET_DR_STUDENT, NF_TARGET_DR_ZIPOISSON, NF_TARG
 const NF_TARGET_CRE_LOGIT, NF_TARGET_CRE_PROBIT, NF_TARGET_CRE_POISSON, NF_TARGET_CRE_STUDENT, NF_TARGET_CRE_NORMAL, NF_TARGET_CRE_DNORMAL, NF_TARGET_CRE_DSTUDENT =
     Int32(40), Int32(41), Int32(42), Int32(43), Int32(44), Int32(45), Int32(46)  # correlated random effects: an LKJ covariance block per term (nfhip.h)
 const NF_TARGET_SCALEGLM = Int32(47)                                  # scaled-block GLM: kind 35's blocks under learned log-scales (nfhip.h)
+const NF_TARGET_HMM_NORMAL = Int32(48)                                # hidden Markov models, the states summed out on chip (nfhip.h)
+const NF_TARGET_HMM_POISSON = Int32(49)
+const NF_TARGET_HMM_BERNOULLI = Int32(50)
 dtype_code(::Type{Float32}) = Int32(0)
 dtype_code(::Type{Float64}) = Int32(1)
 

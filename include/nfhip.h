@@ -525,6 +525,36 @@ extern "C" {
  * point; nf_target_minibatch answers NF_ERR_UNSUPPORTED; a non-centring layer (flow kind 10) answers NF_ERR_ARG for this target.
  * tests/test_scaled_glm_cpu.py holds the value at 47. */
 #define NF_TARGET_SCALEGLM (NF_TARGET_CRE_DSTUDENT + 1)
+/* The HIDDEN-MARKOV-MODEL targets (Stan's hmm_marginal, regime-switching series, capture-recapture, behavioural-state models): K hidden
+ * states summed out by the forward algorithm, the score by the scaled backward recursion -- a matrix recurrence over the rows.
+ *   y = [iota (K) ; Lambda (K x K row-major, Lambda[i][j] the logit of i -> j) ; emission block (E x K, parameter-major)] in R^d,
+ *   d = K + K^2 + E K (checked exactly), 2 <= K <= 8;   pi0 = softmax(iota),  P_i. = softmax(Lambda_i.)
+ *       log p(y) = par[1] + sum_sequences log L(y) - sum_j ((y_j - pm_j) pis_j)^2 / 2
+ *   The R rows (1 <= R <= NF_HMM_MAXR) are one or more independent sequences that share every parameter: row t carries an
+ *   observation x_t, an offset off_t, a weight wt_t >= 0 and a flag seg_t (non-zero: the first row of a sequence; row 0 is read as
+ *   one whatever it holds).  L is the forward-algorithm likelihood under the row log-emissions l_t(k) = wt_t logf(x_t; k):
+ *       NF_TARGET_HMM_NORMAL     E = 2 (mu_k, log sigma_k):  -z^2 / 2 - log sigma_k,  z = (x_t - off_t - mu_k) exp(-log sigma_k)
+ *       NF_TARGET_HMM_POISSON    E = 1 (omega_k):            x_t eta - exp(eta),      eta = omega_k + off_t
+ *       NF_TARGET_HMM_BERNOULLI  E = 1 (omega_k):            x_t eta - softplus(eta), eta = omega_k + off_t,  x_t in [0, 1]
+ *   (the host folds the families' normalisers and the prior's into par[1], in float64).  pm / pis are a location and an inverse
+ *   standard deviation per coordinate; pis_j = 0 is a flat prior.  A row with wt_t == 0 is a missing observation: its l and its share
+ *   of the emission gradient are exactly 0 by select, whatever x_t holds; the transition still happens.
+ *   p0 = x[R] | off[R] | wt[R] | seg[R];   p1 = pm[d] | pis[d] | par[2]  -- two distinct buffers in the flow's element type;
+ *   s0 = R, s1 = K (integer values).
+ *   NF_ERR_ARG for a NULL p0 / p1, p0 == p1, an s0 or s1 that is NaN, non-integral or < 1, K < 2 or d != K + K^2 + E K; then
+ *   NF_ERR_UNSUPPORTED for K > 8 or R > NF_HMM_MAXR -- both before any device work.
+ * The recursion is the scaled one with the row maximum of l subtracted before the exponential; nothing is clamped.  alpha is kept
+ * at every NF_HMM_SEGMENT-th row (checkpoints in LDS) and the reverse sweep replays one segment at a time, so R is bounded by LDS.
+ * No atomics: two launches give the same bits.  Served like NF_TARGET_SCALEGLM: nf_target_logp, RealNVP / NSF flows of either
+ * element type, full-rank and preconditioned flows, general bases and compositions; nf_elbo_step runs the split sequence,
+ * nf_elbo_step_enqueue answers NF_ERR_UNSUPPORTED; planar, radial, mean-field and Hamiltonian flows answer NF_ERR_UNSUPPORTED at
+ * every ELBO entry point; nf_target_minibatch answers NF_ERR_UNSUPPORTED (the rows interact); a non-centring layer answers
+ * NF_ERR_ARG.  tests/test_hmm_cpu.py holds the values at 48, 49, 50. */
+#define NF_TARGET_HMM_NORMAL (NF_TARGET_SCALEGLM + 1)
+#define NF_TARGET_HMM_POISSON (NF_TARGET_SCALEGLM + 2)
+#define NF_TARGET_HMM_BERNOULLI (NF_TARGET_SCALEGLM + 3)
+#define NF_HMM_MAXR 4096
+#define NF_HMM_SEGMENT 64
 
 #define NF_MAX_HIDDEN 4
 
@@ -707,7 +737,8 @@ int nf_target_logp(nf_ctx *ctx, int32_t dtype, const nf_target *target, int32_t 
  * Kinds: NF_TARGET_GLM_*, NF_TARGET_SOFTMAX, NF_TARGET_HGLM_*, NF_TARGET_BNN_*, NF_TARGET_DGLM_*.  NF_ERR_UNSUPPORTED for the kinds
  *   without a per-row weight (0 .. 6, 8) or whose rows are not exchangeable (NF_TARGET_ORDINAL_LOGIT: label blocks;
  *   NF_TARGET_RISKSET: rows interact; NF_TARGET_MIXGLM: family blocks, and a block may be a prior, which must not be subsampled;
- *   NF_TARGET_DR_*, NF_TARGET_CRE_*: not built yet; NF_TARGET_SCALEGLM: scale blocks, and a block may be a prior).
+ *   NF_TARGET_DR_*, NF_TARGET_CRE_*: not built yet; NF_TARGET_SCALEGLM: scale blocks, and a block may be a prior;
+ *   NF_TARGET_HMM_*: rows interact).
  * p0_elems: the element count of full->p0 (the negative-binomial table length lives in device memory: it is derived from this).
  * p0_out: p0_elems - nper (R - m) elements, nper the number of per-row segments of the kind's p0;  p1_out: m x w, w the row width
  *   of p1 (d; d / C for SOFTMAX; (d - 1) / H - 1 for BNN).  idx_out (optional, int32[m]) receives idx.  idx_in (optional, int32[m],

@@ -65,6 +65,12 @@ NF_TARGET_DR_NORMAL, NF_TARGET_DR_STUDENT, NF_TARGET_DR_ZIPOISSON, NF_TARGET_DR_
 # scaled-block GLM: y = [beta (p) ; tau (S)], kind 35's blocks at z = exp(-tau_{sidx[b]}) u; p1 = A[R, d]; s0 = R (a multiple of 32), s1 = S;
 # p0 = lin[d] | off[R] | wt[R] | fam[R / 32] | bpar[R / 32] | sidx[R / 32] | fom[d] | hm[S] | his[S] | hk[S] | par[2]
 NF_TARGET_SCALEGLM = 47
+# hidden Markov models, the states summed out: y = [iota (K) ; Lambda (K x K) ; emission block (E x K)], d = K + K^2 + E K, K in 2..8;
+# p0 = x[R] | off[R] | wt[R] | seg[R]; p1 = pm[d] | pis[d] | par[2] (par = (0, const)); s0 = R (at most NF_HMM_MAXR), s1 = K.
+# The reverse sweep replays segments of NF_HMM_SEGMENT rows from checkpoints in LDS.
+NF_TARGET_HMM_NORMAL, NF_TARGET_HMM_POISSON, NF_TARGET_HMM_BERNOULLI = 48, 49, 50
+NF_HMM_MAXR = 4096
+NF_HMM_SEGMENT = 64
 NF_MAX_HIDDEN = 4
 NF_ERR_NONFINITE = -4
 

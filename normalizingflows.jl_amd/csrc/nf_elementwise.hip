@@ -695,6 +695,15 @@ int nf_target_check(const nf_target *t, int d) {
             t->s1 < 2147483648.0 && t->s1 == (double)(long)t->s1 && (double)d > t->s1))
         return NF_ERR_ARG;
       return (t->s1 > 16 || d > 256) ? NF_ERR_UNSUPPORTED : NF_OK;  // what no kernel of nf_scaleglm.hip serves: answered here, before any device work
+    case NF_TARGET_HMM_NORMAL:
+    case NF_TARGET_HMM_POISSON:
+    case NF_TARGET_HMM_BERNOULLI: {  // s0 = the number of rows R, s1 = the number of states K: positive integers that fit an int (NaN fails the comparisons), K >= 2, d = K + K^2 + E K exactly (compared as doubles); the rows (p0) and the prior (p1) are two buffers
+      const double E = t->kind == NF_TARGET_HMM_NORMAL ? 2.0 : 1.0;
+      if (!(t->p0 && t->p1 && t->p0 != t->p1 && t->s0 >= 1 && t->s0 < 2147483648.0 && t->s0 == (double)(long)t->s0 && t->s1 >= 2 && t->s1 < 2147483648.0 &&
+            t->s1 == (double)(long)t->s1 && (double)d == t->s1 * (t->s1 + 1.0 + E)))
+        return NF_ERR_ARG;
+      return (t->s1 > 8 || t->s0 > (double)NF_HMM_MAXR) ? NF_ERR_UNSUPPORTED : NF_OK;  // what no kernel of nf_hmm.hip serves: answered here, before any device work
+    }
     default: return NF_ERR_ARG;
   }
 }
@@ -718,6 +727,7 @@ int nf_launch_target(nf_ctx *ctx, int dtype, const nf_target *t, int d, long N, 
     if (target_is_distreg(t->kind)) return nf_launch_target_distreg(a);
     if (target_is_correff(t->kind)) return nf_launch_target_correff(a);
     if (target_is_scaleglm(t->kind)) return nf_launch_target_scaleglm(a);
+    if (target_is_hmm(t->kind)) return nf_launch_target_hmm(a);
     return nf_launch_target_linpred(a);
   }
   ProfScope ps(ctx, "target");
@@ -846,6 +856,7 @@ int nf_launch_target_tiled(nf_ctx *ctx, const nf_target *t, int d, long N, const
   if (target_is_distreg(t->kind)) return nf_launch_target_distreg_tiled(a);
   if (target_is_correff(t->kind)) return nf_launch_target_correff_tiled(a);
   if (target_is_scaleglm(t->kind)) return nf_launch_target_scaleglm_tiled(a);
+  if (target_is_hmm(t->kind)) return nf_launch_target_hmm_tiled(a);
   if (target_is_linpred(t->kind)) return nf_launch_target_linpred_tiled(a);
   ProfScope ps(ctx, "target");
   hipLaunchKernelGGL(k_target_tiled, dim3((unsigned)nf_target_tiled_nblocks(N)), dim3(EW_BLOCK), 0, ctx->stream,

@@ -149,8 +149,9 @@ extern "C" int nf_target_minibatch(nf_ctx *ctx, int32_t dtype, const nf_target *
   if (dtype != NF_DTYPE_F32 && dtype != NF_DTYPE_F64) return NF_ERR_ARG;
   const int kind = full->kind;
   if ((kind >= NF_TARGET_DIAGGAUSS && kind <= NF_TARGET_LOGREG) || kind == NF_TARGET_GAUSSMIX || target_is_ordinal(kind) ||
-      target_is_riskset(kind) || target_is_mixglm(kind) || target_is_distreg(kind) || target_is_correff(kind) || target_is_scaleglm(kind))
-    return NF_ERR_UNSUPPORTED;  // no per-row weight (0 .. 6, 8), rows grouped by label blocks (32), rows that interact (33), rows that may be a prior (35), no table entry yet (36 .. 46), rows that may be a prior under a scale (47)
+      target_is_riskset(kind) || target_is_mixglm(kind) || target_is_distreg(kind) || target_is_correff(kind) || target_is_scaleglm(kind) ||
+      target_is_hmm(kind))
+    return NF_ERR_UNSUPPORTED;  // no per-row weight (0 .. 6, 8), rows grouped by label blocks (32), rows that interact (33), rows that may be a prior (35), no table entry yet (36 .. 46), rows that may be a prior under a scale (47), rows of a sequence (48 .. 50)
   NF_TRY(nf_target_check(full, d));  // NULL p0 / p1, s0, s1, d: the kind's own conventions (unassigned kinds: NF_ERR_ARG)
   MbTable tab;
   int w = 0;

@@ -190,3 +190,6 @@ int nf_launch_target_correff_tiled(const TgtTiledArgs &a);
 int nf_launch_target_correff(const TgtFlatArgs &a);
 int nf_launch_target_scaleglm_tiled(const TgtTiledArgs &a);
 int nf_launch_target_scaleglm(const TgtFlatArgs &a);
+// (nf_hmm.hip: the same contract and helpers, none of the matrix stages)
+int nf_launch_target_hmm_tiled(const TgtTiledArgs &a);
+int nf_launch_target_hmm(const TgtFlatArgs &a);

@@ -161,9 +161,13 @@ __host__ __device__ inline bool target_is_correff(int kind) { return kind >= NF_
 // So is the scaled-block GLM kind (NF_TARGET_SCALEGLM, nf_scaleglm.hip): the mixed-family form with a learned log-scale coordinate per row
 // block (y = [beta ; tau]), the rows' d / d tau gathered in per-lane bins.
 __host__ __device__ inline bool target_is_scaleglm(int kind) { return kind == NF_TARGET_SCALEGLM; }
+// So are the hidden-Markov-model kinds (NF_TARGET_HMM_NORMAL .. NF_TARGET_HMM_BERNOULLI, nf_hmm.hip): no matrix product at all, a
+// recurrence over the rows with a lane per (sample, state) and LDS as its tape.
+__host__ __device__ inline bool target_is_hmm(int kind) { return kind >= NF_TARGET_HMM_NORMAL && kind <= NF_TARGET_HMM_BERNOULLI; }
 __host__ __device__ inline bool target_has_own_kernel(int kind) {
   return target_is_linpred(kind) || kind == NF_TARGET_GAUSSMIX || kind == NF_TARGET_SOFTMAX || target_is_bnn(kind) || target_is_ordinal(kind) ||
-         target_is_riskset(kind) || target_is_mixglm(kind) || target_is_distreg(kind) || target_is_correff(kind) || target_is_scaleglm(kind);
+         target_is_riskset(kind) || target_is_mixglm(kind) || target_is_distreg(kind) || target_is_correff(kind) || target_is_scaleglm(kind) ||
+         target_is_hmm(kind);
 }
 // widest flow the mixture's tiled kernel serves (two U and two G blocks in registers); the flat kernel goes to 256
 #define NF_MIXTURE_TILED_MAXD 64

@@ -2122,6 +2122,104 @@ _DR_KINDS = {"normal": _lib.NF_TARGET_DR_NORMAL, "student": _lib.NF_TARGET_DR_ST
              "weibull": _lib.NF_TARGET_DR_WEIBULL}
 
 
+_HMM_KINDS = {"normal": (_lib.NF_TARGET_HMM_NORMAL, 2), "poisson": (_lib.NF_TARGET_HMM_POISSON, 1), "bernoulli": (_lib.NF_TARGET_HMM_BERNOULLI, 1)}
+
+
+class HiddenMarkovTarget(_LinpredTarget):
+    """Posterior of a hidden Markov model with the K states summed out (NF_TARGET_HMM_*; Stan's hmm_marginal), over the unconstrained
+        y = [iota (K) ; Lambda (K x K, row-major: Lambda[i, j] the logit of i -> j) ; emission block],   d = K + K^2 + E K,
+        pi0 = softmax(iota),  P[i] = softmax(Lambda[i]),   logp(y) = const + sum_sequences log L(y) + sum_j log N(y_j; prior_loc_j, prior_scale_j^2)
+    family "normal" (emission block [mu (K) ; log sigma (K)]: x_t - offset_t ~ N(mu_k, sigma_k^2)), "poisson" ([omega (K)]:
+    x_t ~ Poisson(exp(omega_k + offset_t))) or "bernoulli" ([omega (K)]: x_t in [0, 1] ~ Bernoulli(sigmoid(omega_k + offset_t))).
+    x is a Float32 or Float64 vector of R <= NF_HMM_MAXR rows; weights >= 0 raise a row's emission to a power, weight 0 is a missing
+    observation (its x may hold anything; the transition still happens); sequence_start marks the first row of every independent
+    sequence (default: one sequence; row 0 must be marked).  prior_loc / prior_scale: a scalar or (d,); math.inf is flat -- the
+    locations are how a caller pins the softmax gauge and orders the states.  The host folds the families' and the prior's
+    normalisers into const in float64.  The device reads `p0` = x | offset | weights | sequence_start and `A` = prior_loc[d] |
+    1 / prior_scale[d] | (0, const), both kept alive here."""
+
+    def __init__(self, family, x, n_states, offset=None, weights=None, sequence_start=None, prior_loc=None, prior_scale=None, const=0.0,
+                 dtype=None, device=None):
+        nm = "HiddenMarkovTarget"
+        if family not in _HMM_KINDS:
+            raise NFHipError(f"{nm}: family must be one of {sorted(_HMM_KINDS)}")
+        kind, E = _HMM_KINDS[family]
+        if isinstance(n_states, bool) or not hasattr(n_states, "__index__") or not 2 <= int(n_states) <= 8:
+            raise NFHipError(f"{nm}: n_states must be an integer in 2..8")
+        K = int(n_states)
+        if not isinstance(x, torch.Tensor) or x.dim() != 1 or x.numel() < 1 or (dtype is None and x.dtype not in (torch.float32, torch.float64)):
+            raise NFHipError(f"{nm}: x must be a Float32 or Float64 vector of at least one row (or pass dtype=)")
+        dtype, device = dtype or x.dtype, device or x.device
+        R = x.numel()
+        if R > _lib.NF_HMM_MAXR:
+            raise NFHipError(f"{nm}: {R} rows exceed the kernels' {_lib.NF_HMM_MAXR}")
+        x64 = x.detach().to("cpu", torch.float64).numpy()
+        off, wt = _rs_vector(nm, "offset", offset, R, 0.0), _rs_vector(nm, "weights", weights, R, 1.0)
+        seg = _rs_vector(nm, "sequence_start", sequence_start, R, 0.0) != 0
+        if sequence_start is None:
+            seg[0] = True
+        if not seg[0]:
+            raise NFHipError(f"{nm}: row 0 must be a sequence start")
+        if not np.isfinite(wt).all() or (wt < 0).any():
+            raise NFHipError(f"{nm}: weights must be finite and >= 0")
+        live = wt > 0
+        if not np.isfinite(x64[live]).all() or not np.isfinite(off).all():
+            raise NFHipError(f"{nm}: x must be finite on every row of positive weight, offset everywhere")
+        if family == "bernoulli" and ((x64[live] < 0) | (x64[live] > 1)).any():
+            raise NFHipError(f"{nm}: bernoulli data must lie in [0, 1]")
+        if family == "poisson" and (x64[live] < 0).any():
+            raise NFHipError(f"{nm}: poisson data must be >= 0")
+        d = K + K * K + E * K
+        loc = _per_item(nm, "prior_loc", _items64(0.0 if prior_loc is None else prior_loc), d).numpy()
+        scl = _per_item(nm, "prior_scale", _items64(math.inf if prior_scale is None else prior_scale), d, positive=True, allow_inf=True).numpy()
+        fin = np.isfinite(scl)
+        c = _glm_scalar(nm, "const", const, positive=False) - float(np.log(scl[fin]).sum()) - 0.5 * math.log(2.0 * math.pi) * int(fin.sum())
+        if family == "normal":
+            c -= 0.5 * math.log(2.0 * math.pi) * float(wt.sum())
+        elif family == "poisson":
+            c -= float((wt[live] * torch.lgamma(torch.from_numpy(x64[live]) + 1.0).numpy()).sum())
+        pis = np.where(fin, 1.0 / np.where(fin, scl, 1.0), 0.0)
+        self.family, self.K, self.E, self.d, self.rows, self.const = family, K, E, d, R, c
+        self.sequence_start = torch.from_numpy(seg.copy())
+        mk = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dtype).to(device).contiguous()  # noqa: E731
+        self.p0 = mk(np.concatenate([x64, off, wt, seg.astype(np.float64)]))  # (a missing row's x travels as it is: the device selects)
+        self.A = mk(np.concatenate([loc, pis, [0.0, c]]))
+        self.c = Target(kind, self.p0.data_ptr(), self.A.data_ptr(), float(R), float(K))
+
+    def unpack(self, y):
+        """(pi0 [K], P [K, K], emission parameters on the natural scale) of y (d,) -- or with a trailing batch axis of y (d, N): the
+        emission parameters are (mu, sigma) for "normal", (rate,) for "poisson" at offset 0, (probability,) for "bernoulli" at offset 0"""
+        K = self.K
+        if y.shape[0] != self.d:
+            raise NFHipError(f"{type(self).__name__}.unpack: expected {self.d} leading elements, got {y.shape[0]}")
+        pi0, P = torch.softmax(y[:K], 0), torch.softmax(y[K:K + K * K].reshape(K, K, *y.shape[1:]), 1)
+        em = y[K + K * K:].reshape(self.E, K, *y.shape[1:])
+        if self.family == "normal":
+            return pi0, P, (em[0], torch.exp(em[1]))
+        return pi0, P, ((torch.exp(em[0]) if self.family == "poisson" else torch.sigmoid(em[0])),)
+
+    def predict(self, y):
+        """the filtered state probabilities p(state of the last row | all rows of its sequence) at the parameter vector y (d,), float64 on the host"""
+        K = self.K
+        y = y.detach().to("cpu", torch.float64)
+        if y.shape != (self.d,):
+            raise NFHipError(f"{type(self).__name__}.predict: expected a vector of {self.d} elements")
+        x, off, wt, seg = self.p0.detach().to("cpu", torch.float64).reshape(4, self.rows)
+        lpi, lP = torch.log_softmax(y[:K], 0), torch.log_softmax(y[K:K + K * K].reshape(K, K), 1)
+        em = y[K + K * K:].reshape(self.E, K)
+        la = lpi
+        for t in range(self.rows):
+            if self.family == "normal":
+                z = (x[t] - off[t] - em[0]) * torch.exp(-em[1])
+                lf = -0.5 * z * z - em[1]
+            else:
+                eta = em[0] + off[t]
+                lf = x[t] * eta - (torch.exp(eta) if self.family == "poisson" else torch.nn.functional.softplus(eta))
+            l = wt[t] * lf if wt[t] != 0 else torch.zeros(K, dtype=torch.float64)
+            la = (lpi if (t == 0 or seg[t] != 0) else torch.logsumexp(la[:, None] + lP, 0)) + l
+        return torch.softmax(la, 0)
+
+
 def _dr_second(name, X, Z, n):
     """the second design matrix as float64 on the host: Z = None is a column of ones (one learned sigma / probability / shape)"""
     if Z is None:
